@@ -16,12 +16,19 @@ fuses its sub-box of the output: no data-path collective, "scaling": "strong".
 --mode replica: one mosaic per rank (independent positions), "scaling": "weak".
 
 value   = fused output Mvoxels/s of the whole job (register + fuse time, max over ranks)
+ms_per_step = milliseconds of one timed step (--steps of them between two synchronisations)
 roofline = algorithmic HBM bytes of the dominant kernel (fuse: every input voxel once + every
            output voxel once) / its HIP-event duration, vs 8 TB/s
 roofline_register = algorithmic bytes of the pairwise registrations / their wall time
+
+A plain run sets up, warms up, times the steps and prints the line; the figures above come from the timed steps themselves.
+--full adds the legs that take runs of their own (the --no-* options skip single ones):
 value_incl_pcie = the same mosaic with tiles starting and the result ending in pinned host memory
            (uploads overlapped with registration, downloads with fusion); N > 1 (shard): every rank its own pipeline
 cpu_baseline = the numpy/scipy oracle timed on this box on a bounded sample (rank 0, N=1 only)
+c3_content_based, c5_stream, fuse_host_arrays, roofline.by_class, config.fuse_default_chunksize_ms, config.step_new_geometry_ms
+           (N = 1 only); without --full they are null.
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs) so that two builds can be compared on the same inputs.
 """
 import argparse
 import json
@@ -58,7 +65,16 @@ def parse_args():
     ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive pipeline leg (N = 1 and --mode shard)")
     ap.add_argument("--no-c3", action="store_true", help="skip the content-based leg (BASELINE config C3; N = 1 only)")
     ap.add_argument("--no-c5", action="store_true", help="skip the Zarr-streamed leg (BASELINE config C5, a z-slab of its grid; N = 1 only)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beyond the headline figure: cpu_baseline, value_incl_pcie, C3, C5, "
+                         "host arrays, default chunk size, new geometry, roofline.by_class (the --no-* options still skip single legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy: a seeded sample of the fused mosaic (float32) with "
+                         "its flat indices and shape (float64), and the registered affine of every tile (float64)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def make_mosaic_on_device(torch, dev, grid, tile, overlap, seed, max_jitter=3, return_ground_truth=False):
@@ -772,6 +788,67 @@ def pcie_pipeline(torch, dev, local_rank, sims, tiles, args, key_in, key_out, sh
                                            "that needs them: h2d_gb is their sum) and downloads its sub-box" if shard else "")}
 
 
+DUMP_SAMPLE_VOXELS = 1 << 22     # fused voxels --dump-outputs writes (all of them when the mosaic has fewer): 48 MB with the indices
+DUMP_SAMPLE_SEED = 20240611
+
+
+class _Int16View:
+    """A contiguous uint16 DeviceArray seen as int16 through __cuda_array_interface__ (torch gathers int16 everywhere)."""
+
+    def __init__(self, a):
+        self.__cuda_array_interface__ = dict(a.__cuda_array_interface__, typestr="<i2")
+
+
+def dump_outputs(dump_dir, torch, dev, fused, box, sims, key, rank, shard, dist, backend):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files in ``dump_dir`` (rank 0 writes them).
+    fused_sample.npy (float32) = the fused mosaic at DUMP_SAMPLE_VOXELS flat indices drawn with a fixed seed (sorted; every voxel
+    when the mosaic is smaller), fused_sample_index.npy (float64) = those flat indices, fused_shape.npy (float64) = the mosaic's
+    shape, registered_affines.npy (float64, tiles x 4 x 4) = every tile's affine under ``key`` (None: fuse only, not written).
+    The values are gathered on the device; shard: every rank fills the indices inside its sub-box, the sum over ranks is the
+    mosaic (sub-boxes are disjoint and cover it)."""
+    from multiview_stitcher_amd import param_utils
+    from multiview_stitcher_amd import spatial_image_utils as si
+
+    if not shard and rank != 0:      # (replica: every rank has a mosaic of its own; rank 0's is written)
+        return
+    local_shape = np.array([int(v) for v in fused.shape])
+    off = np.array([int(box["index_offset"][d]) for d in "zyx"]) if box is not None else np.zeros(3, dtype=int)
+    on_host = backend != "nccl"
+    shape = local_shape + off
+    if shard:
+        t = torch.tensor(shape.tolist(), dtype=torch.int64, device="cpu" if on_host else dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        shape = np.array([int(v) for v in t.tolist()])
+    total = int(np.prod(shape))
+    if total <= DUMP_SAMPLE_VOXELS:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, total, DUMP_SAMPLE_VOXELS, dtype=np.int64))
+    zyx = np.stack(np.unravel_index(idx, tuple(shape)), axis=1) - off
+    inside = np.all((zyx >= 0) & (zyx < local_shape), axis=1)
+    local_idx = np.ravel_multi_index(tuple(zyx[inside].T), tuple(local_shape)) if inside.any() else np.zeros(0, dtype=np.int64)
+    data = fused.data
+    if not data.is_contiguous() or data.dtype != np.uint16:
+        raise RuntimeError(f"--dump-outputs expects a contiguous uint16 mosaic, got {data!r}")
+    flat = torch.as_tensor(_Int16View(data), device=dev).reshape(-1)
+    got = flat[torch.from_numpy(local_idx).to(dev)].cpu().numpy().view(np.uint16)
+    vals = np.zeros(idx.size, dtype=np.float64)
+    vals[inside] = got
+    if shard:
+        t = torch.from_numpy(vals) if on_host else torch.from_numpy(vals).to(dev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        vals = t.cpu().numpy()
+    if rank != 0:
+        return
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "fused_sample.npy"), vals.astype(np.float32))
+    np.save(os.path.join(dump_dir, "fused_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(dump_dir, "fused_shape.npy"), shape.astype(np.float64))
+    if key is not None:
+        aff = np.stack([param_utils.select_time(si.get_affine_from_sim(s, key), 0) for s in sims]).astype(np.float64)
+        np.save(os.path.join(dump_dir, "registered_affines.npy"), aff)
+
+
 def main():
     args = parse_args()
     # one compact block of CPUs per process, before torch / HIP start their threads (executors.pin_process_to_compact_cpus: the
@@ -968,6 +1045,9 @@ def main():
         with open(os.path.join(dump_dir, f"fused_rank{rank}of{world}.json"), "w") as f:
             json.dump({"index_offset": off, "shape": [int(v) for v in out_shape], "pairs_registered": int(reg_pairs),
                        "tiles_held": int(n_held), "halo_exchange_ms": halo_ms, "mode": "shard" if shard else "replica"}, f)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, dev, fused, out_holder.get("box"), sims, key_out if do_register else None,
+                     rank, shard, dist, backend)
     out_vox_local = float(np.prod(out_shape))
     es = 2
     # algorithmic bytes of THIS rank's fuse launch: every input voxel that reaches into its output box once + every
@@ -1005,7 +1085,7 @@ def main():
     # (two calls: the first may have to hipMalloc a second mosaic-sized result -- ~240 ms for 10.7 GB -- while the timed loop's result
     # is still alive; the pool hands the block back to the second call)
     default_chunks_ms = default_chunks_first_ms = None
-    if world == 1:
+    if args.full and world == 1:
         for rep in range(2):
             _lib.synchronize(local_rank)
             t_d = time.perf_counter()
@@ -1021,7 +1101,7 @@ def main():
     # of every pair (~2 ms of scipy each, on a thread of its own next to the GPU's pair loop).  What a series of DIFFERENT mosaics pays
     # per mosaic, between the cold first call and the steady state of one repeated geometry that `value` is.
     new_geo = {}
-    if world == 1 and do_register:
+    if args.full and world == 1 and do_register:
         try:
             sims_b = build_sims(tiles, origins + 3.0, local_rank, tile_shape=tile)
             out_holder.clear()
@@ -1037,13 +1117,13 @@ def main():
         except Exception as e:   # noqa: BLE001 - an optional figure must not take the bench line down
             new_geo = {"step_new_geometry_error": repr(e)[:200]}
     by_class = None
-    if world == 1:
+    if args.full and world == 1:
         try:
             by_class = fuse_by_class(_lib, fusion, sims, key_out if do_register else key_in, local_rank)
         except Exception as e:   # noqa: BLE001 - an optional leg must not take the bench line down
             by_class = {"error": repr(e)[:300]}
     pcie = None
-    if (world == 1 or shard) and do_register and not args.no_pcie:
+    if args.full and (world == 1 or shard) and do_register and not args.no_pcie:
         out_holder.clear()
         shard_ctx = {"rank": rank, "world": world, "executor": executor, "dist": dist, "backend": backend} if shard else None
         if shard:
@@ -1065,13 +1145,13 @@ def main():
             except Exception as e:   # noqa: BLE001 - an optional leg must not take the bench line down
                 pcie = {"error": repr(e)[:300]}
     c3 = None
-    if world == 1 and not args.no_c3:
+    if args.full and world == 1 and not args.no_c3:
         try:
             c3 = c3_content_based_leg(torch, dev, local_rank, args)
         except Exception as e:   # noqa: BLE001 - an optional leg must not take the bench line down
             c3 = {"error": repr(e)[:300]}
     host_fuse = None
-    if world == 1 and not args.no_pcie:
+    if args.full and world == 1 and not args.no_pcie:
         out_holder.clear()
         try:
             with _original_affinity():
@@ -1079,7 +1159,7 @@ def main():
         except Exception as e:   # noqa: BLE001 - an optional leg must not take the bench line down
             host_fuse = {"error": repr(e)[:300]}
     c5 = None
-    if world == 1 and not args.no_c5:
+    if args.full and world == 1 and not args.no_c5:
         out_holder.clear()
         try:
             with _original_affinity():
@@ -1196,7 +1276,7 @@ def main():
                 "note": "duration = wall time of compute_pairwise_registrations (kernels of the context lanes (8 by default) overlap; includes host round trips)",
             },
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(args, grid, tile, overlap)
         else:
             result["cpu_baseline"] = None

@@ -34,15 +34,15 @@ def _run(cmd, env, timeout=900):
 
 
 def test_two_ranks_one_mosaic_equals_single_rank(hip_device, tmp_path):
-    # (the PCIe-inclusive leg stays on: at N = 2 every rank runs its own upload -> register -> fuse -> download pipeline)
-    common = ["--grid", "2,2,2", "--tile", "256,256,256", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-c3", "--no-c5"]
+    # (the PCIe-inclusive leg stays on (--full): at N = 2 every rank runs its own upload -> register -> fuse -> download pipeline)
+    common = ["--grid", "2,2,2", "--tile", "256,256,256", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-c3", "--no-c5"]
     d1, d2 = tmp_path / "n1", tmp_path / "n2"
     d1.mkdir()
     d2.mkdir()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    one = _run([sys.executable, "bench.py", "--gpus", "1"] + common, dict(env, MVS_BENCH_DUMP=str(d1)))
+    one = _run([sys.executable, "bench.py", "--gpus", "1"] + common + ["--dump-outputs", str(d1 / "out")], dict(env, MVS_BENCH_DUMP=str(d1)))
     two = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                "--master-port", str(_free_port()), "bench.py", "--gpus", "2"] + common,
+                "--master-port", str(_free_port()), "bench.py", "--gpus", "2"] + common + ["--dump-outputs", str(d2 / "out")],
                dict(env, MVS_BENCH_DUMP=str(d2), MVS_BENCH_BACKEND="gloo"))
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     assert two["config"]["mode"] == "shard" and two["scaling"] == "strong"
@@ -75,6 +75,48 @@ def test_two_ranks_one_mosaic_equals_single_rank(hip_device, tmp_path):
     # every rank fuses its sub-box in the index frame of the whole mosaic (sharding.fuse_shard -> fuse(frame_origin=...)):
     # the union equals the single-rank mosaic voxel for voxel
     np.testing.assert_array_equal(got, full)
+    # --dump-outputs of the sharded run (every rank fills the sampled voxels of its sub-box) == that of the single-rank run
+    _check_dump(d1 / "out", full, 8)
+    _same_dump(d2 / "out", d1 / "out")
+
+
+def _same_dump(got, want):
+    """Two --dump-outputs directories: the same mosaic sample, the same affines (up to the resolution's round-off)."""
+    for name in ("fused_sample", "fused_sample_index", "fused_shape"):
+        np.testing.assert_array_equal(np.load(got / f"{name}.npy"), np.load(want / f"{name}.npy"))
+    np.testing.assert_allclose(np.load(got / "registered_affines.npy"), np.load(want / "registered_affines.npy"), rtol=0, atol=1e-9)
+
+
+def _check_dump(out, full, n_tiles):
+    """--dump-outputs: float32 / float64 files of at most 64 MB in all; the sample is the fused mosaic at the listed flat indices."""
+    files = sorted(os.listdir(out))
+    assert files == ["fused_sample.npy", "fused_sample_index.npy", "fused_shape.npy", "registered_affines.npy"], files
+    assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+    sample, idx, shape, aff = (np.load(out / f) for f in files)
+    assert sample.dtype == np.float32 and idx.dtype == shape.dtype == aff.dtype == np.float64
+    assert shape.tolist() == list(full.shape) and aff.shape == (n_tiles, 4, 4)
+    assert idx.shape == sample.shape and np.all(np.diff(idx) >= 0) and idx[-1] < full.size
+    np.testing.assert_array_equal(sample, full.reshape(-1)[idx.astype(np.int64)].astype(np.float32))
+    return sample, idx, aff
+
+
+def test_plain_run_dumps_its_last_step(hip_device, tmp_path):
+    """A run without --full times the steps and prints the line, nothing more: the legs with runs of their own are null.
+    --dump-outputs leaves a seeded sample of the last step's mosaic (the mosaic is larger than the sample here) and the registered
+    affines; a second run with the same arguments writes the same files."""
+    args = [sys.executable, "bench.py", "--gpus", "1", "--grid", "2,2,2", "--tile", "128,160,192", "--steps", "2", "--warmup", "1"]
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    a = _run(args + ["--dump-outputs", str(tmp_path / "a")], dict(env, MVS_BENCH_DUMP=str(tmp_path)))
+    assert a["steps"] == 2 and a["warmup"] == 1 and a["ms_per_step"] > 0 and a["value"] > 0 and a["higher_is_better"] is True
+    for leg in ("value_incl_pcie", "cpu_baseline", "c3_content_based", "c5_stream", "fuse_host_arrays"):
+        assert a[leg] is None, leg
+    assert a["roofline"]["by_class"] is None and a["config"]["step_new_geometry_ms"] is None
+    full = np.load(tmp_path / "fused_rank0of1.npy")
+    sample, idx, aff = _check_dump(tmp_path / "a", full, 8)
+    assert sample.size == 1 << 22 < full.size
+    assert np.all(aff[:, 3] == [0, 0, 0, 1]) and not np.all(aff[:, :3, 3] == aff[0, :3, 3])
+    _run(args + ["--dump-outputs", str(tmp_path / "b")], env)
+    _same_dump(tmp_path / "b", tmp_path / "a")
 
 
 def test_eight_ranks_one_mosaic_equals_single_rank(hip_device, tmp_path):

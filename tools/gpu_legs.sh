@@ -2,7 +2,7 @@
 # the side legs of the bench line on a short main loop (PCIe-inclusive, C3, C5) + the launch tests.  usage: [LEGS="..."] bash tools/gpu_legs.sh
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/legs; mkdir -p $O
-timeout 900 python bench.py --steps 3 --warmup 1 --no-cpu-baseline ${LEGS} > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; tail -3 $O/bench.err
+timeout 900 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline ${LEGS} > $O/bench.json 2> $O/bench.err; echo "bench rc $?"; tail -3 $O/bench.err
 python - <<PY
 import json
 d = json.load(open("$O/bench.json"))

@@ -7,7 +7,7 @@
 #      geometry, fractional offsets, single-tile calibration, the 128-byte-aligned geometry) and of the content-based chunk pipeline
 #   3. HIP-event timings: fuse launch variants + the alignment bound (overlap 102 / 104 / 128 px, forked and class by class),
 #      content-based probe, host phases
-#   4. the bench line itself (cpu_baseline, PCIe leg, C3 and C5 legs, by_class)
+#   4. the bench line itself with --full (cpu_baseline, PCIe leg, C3 and C5 legs, by_class)
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 ROUND=${ROUND:-round6}
@@ -51,5 +51,5 @@ cd $R
 python tools/cb_probe.py > $O/cb_probe.txt 2>&1
 python tools/host_profile.py 2>&1 | cut -c1-170 | grep -v "^$" | head -110 > $O/host_profile.txt
 python tools/register_phases.py > $O/register_phases.txt 2>&1
-timeout 1500 python bench.py --steps 20 --warmup 3 > $O/bench_line.json 2> $O/bench_line.err
+timeout 1500 python bench.py --full --steps 20 --warmup 3 > $O/bench_line.json 2> $O/bench_line.err
 tail -3 $O/bench.log | head -c 400; echo; cat $O/fuse_variants.txt; cat $O/fuse_alignment.txt; tail -2 $O/cb_probe.txt; head -c 1500 $O/bench_line.json
