@@ -108,7 +108,8 @@ const char* mvs_last_error(int device);
 int mvs_set_stream(int device, void* hip_stream);
 int mvs_synchronize(int device);
 /* Tuning / test switches. "force_generic" = 1: mvs_fuse_chunk never takes the translation fast
- * path (both paths must agree; tests compare them).  "no_regions" = 1: skip the region kernels.
+ * path (both paths must agree; tests compare them).  "no_regions" = 1: skip the region kernels. "deconv_general" = 1: mvs_mv_deconv
+ * convolves through the general direct path even when separable factors are passed (tests compare both paths).
  * "pool_cache_limit_mb": bytes (MiB) mvs_free may keep cached for later mvs_malloc calls
  * (default 32768; 0 = release immediately).  "materialize_shifts" = 1: mvs_score_candidates / mvs_register_crops
  * always write the shifted copies of the moving image (by default finite-only crops evaluate them inside the SSIM z
@@ -221,6 +222,35 @@ int mvs_resample(int device, const mvs_view_t* view, const int64_t out_shape[3],
  * (weights.py:391-511): resampled 5^ndim support + cosine ramp, NOT normalised. */
 int mvs_blend_weights(int device, const mvs_view_t* view, int32_t ndim,
                       const int64_t out_shape[3], float* out, int32_t out_mem);
+
+/* ---- multi-view deconvolution ------------------------------------------------- *
+ * Options of mvs_mv_deconv (fusion/mv_deconv.py:251-264 of the reference). */
+typedef struct mvs_deconv_opts_t {
+    int32_t n_iterations;  /* n_iterations (mv_deconv.py:255)                                  */
+    int32_t erosion_px;    /* sample_boundary_erosion_px (:261, applied at :485-499)           */
+    double lambda_reg;     /* Tikhonov strength; 0 = off (:256, :468-479)                      */
+    double min_value;      /* clamp of the estimate and of the denominators (:257), used as float32 */
+    int64_t trim[3];       /* halo trimmed off the result per axis z,y,x (fusion/_core.py:1687-1711) */
+    int32_t out_dtype;     /* enum mvs_dtype of the result: nan_to_num + astype (_core.py:1713; :501) */
+    int32_t flags;         /* MVS_DECONV_PREPARE_WEIGHTS: `weights` holds raw blending weights (mvs_blend_weights); they are
+                              masked by the views' coverage and normalised in place first (_core.py:1648-1649,
+                              weights.py:325-345) */
+} mvs_deconv_opts_t;
+#define MVS_DECONV_PREPARE_WEIGHTS 1
+
+/* mvs_mv_deconv == fusion.multi_view_deconvolution (fusion/mv_deconv.py:251-501): Richardson-Lucy with sequential
+ * per-view updates, every step on the device.  views / weights: device float32, n_views x shape (z,y,x; 2D data as
+ * shape[0] == 1), NaN in a view = outside it, weights normalised (fusion/_core.py:1640-1649) unless opts->flags says otherwise.  kernels1 / kernels2: host
+ * float32, n_views x ksize each, the forward PSFs and the compound back-projection kernels (:363-404) in
+ * scipy.ndimage.convolve orientation (out[i] = sum_j k[j] in[i + K//2 - j]); every axis <= 63, else MVS_ERR_UNSUPPORTED.
+ * sep1 / sep2 (both or neither; NULL = general path): host float32, n_views x (kz + ky + kx) 1-D factors (z, y, x) whose
+ * outer product is the kernel of the same view -- the three-pass separable path.  Init (:409-414), forward convolution
+ * with mode "mirror" + quotient + weighting (:434-462), back-projection with mode "constant", cval 1 + update (:464-483),
+ * erosion of the union coverage (:485-499); then the result is trimmed by opts->trim, nan_to_num'd and cast to
+ * opts->out_dtype into `out` (shape - 2 trim; host or device per out_mem).  A device result is not waited for. */
+int mvs_mv_deconv(int device, const float* views, float* weights, int32_t n_views, const int64_t shape[3], int32_t ndim,
+                  const float* kernels1, const float* kernels2, const int64_t ksize[3], const float* sep1, const float* sep2,
+                  const mvs_deconv_opts_t* opts, void* out, int32_t out_mem);
 
 /* ---- registration ------------------------------------------------------------ *
  * mvs_phasecorr == skimage.registration.phase_cross_correlation(fixed, moving,

@@ -58,6 +58,21 @@ class mvs_fuse_opts_t(C.Structure):
     ]
 
 
+class mvs_deconv_opts_t(C.Structure):
+    _fields_ = [
+        ("n_iterations", C.c_int32),
+        ("erosion_px", C.c_int32),
+        ("lambda_reg", C.c_double),
+        ("min_value", C.c_double),
+        ("trim", C.c_int64 * 3),
+        ("out_dtype", C.c_int32),
+        ("flags", C.c_int32),
+    ]
+
+
+MVS_DECONV_PREPARE_WEIGHTS = 1
+
+
 class mvs_pair_job_t(C.Structure):
     _fields_ = [
         ("fixed", mvs_view_t),
@@ -94,6 +109,11 @@ SIGNATURES = {
     "mvs_fuse_chunk": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(mvs_fuse_opts_t), C.c_void_p]),
     "mvs_resample": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.POINTER(C.c_int64), C.c_int32, C.c_float, C.c_void_p, C.c_int32]),
     "mvs_blend_weights": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_int32]),
+    "mvs_mv_deconv": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
+         C.c_void_p, C.c_void_p, C.POINTER(mvs_deconv_opts_t), C.c_void_p, C.c_int32],
+    ),
     "mvs_phasecorr": (
         C.c_int,
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_int32,

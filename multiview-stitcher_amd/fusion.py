@@ -22,7 +22,8 @@ import time
 
 import numpy as np
 
-from . import _lib, mv_graph, param_utils, weights
+from . import _lib, mv_deconv, mv_graph, param_utils, weights
+from .mv_deconv import PSFType, multi_view_deconvolution  # noqa: F401  (fusion.multi_view_deconvolution, fusion.PSFType)
 from . import spatial_image_utils as si_utils
 from .device import DeviceArray, is_device_array
 from .transformation import _as_zyx, embed3_stack, fill_view_geometry, get_pixel_affine, get_pixel_affines, shape3
@@ -71,6 +72,7 @@ BUILTIN = {
     "max_fusion": max_fusion,
     "simple_average_fusion": simple_average_fusion,
     "content_based": content_based,
+    "multi_view_deconvolution": multi_view_deconvolution,   # not a kernel mode: fuse_np's deconvolution branch
 }
 
 
@@ -190,6 +192,10 @@ def fuse_np(
     input_dtype = np.dtype(sims[0].dtype)
     if input_dtype not in _lib.DTYPE_CODES:
         raise TypeError(f"unsupported dtype {input_dtype} (uint8/uint16/float32)")
+    if fusion_func is multi_view_deconvolution:
+        return _fuse_np_deconvolution(
+            sims, params, out_bb, sdims, input_dtype, fusion_func_kwargs, trim_overlap_in_pixels, interpolation_order,
+            full_view_bbs, spacings, blending_widths, shrink_distance, output_on_backend, out, device)
     if fusion_func not in _FUSION_CODES or (weights_func is not None and weights_func is not content_based):
         # user callables (docs/extension_api_fusion.md): they run after the resample, so the chunk cannot be fused in one
         # kernel; the voxel work that is ours (resample, blending weights) still runs on the device
@@ -334,6 +340,78 @@ def fuse_np(
     rc = lib.mvs_fuse_chunk(device, views, n, C.byref(opts), result.ctypes.data)
     _lib.check(rc, device, "mvs_fuse_chunk")
     return result
+
+
+def _fuse_np_deconvolution(sims, params, out_bb, sdims, input_dtype, fusion_func_kwargs, trim_overlap_in_pixels,
+                           interpolation_order, full_view_bbs, spacings, blending_widths, shrink_distance, output_on_backend,
+                           out, device):
+    """fuse_np with ``fusion_func=multi_view_deconvolution`` (_core.py:1608-1713 around mv_deconv.py:251-501), all on the
+    device: every view resampled by mvs_resample (float32, NaN outside) and its blending weights by mvs_blend_weights
+    into two (V, *S) stacks; mvs_mv_deconv masks the weights by ~isnan and normalises them, deconvolves, trims the halo,
+    applies nan_to_num and casts to the input dtype.  ``output_spacing`` is the chunk spacing unless the caller passed
+    one (_core.py:1658-1662).  Only the result crosses PCIe, and only when a host result is asked for."""
+    from .transformation import fill_view_geometry
+
+    lib = _lib.init(device)
+    ndim = len(sdims)
+    kw = dict(fusion_func_kwargs or {})
+    for k in ("transformed_views", "blending_weights", "device"):
+        if k in kw:
+            raise TypeError(f"fusion_func_kwargs must not set {k!r}: fuse_np supplies it")
+    if kw.get("output_spacing") is None:
+        kw["output_spacing"] = dict(out_bb["spacing"])
+    if spacings is None:
+        spacings = [fvb["spacing"] for fvb in full_view_bbs] if full_view_bbs is not None else [None] * len(sims)
+    if full_view_bbs is None:
+        full_view_bbs = [si_utils.get_stack_properties_from_sim(s) for s in sims]
+    out_shape = tuple(int(out_bb["shape"][d]) for d in sdims)
+    o_origin, o_spacing = _as_zyx(out_bb["origin"], sdims), _as_zyx(out_bb["spacing"], sdims)
+    n = len(sims)
+    kernels = mv_deconv._kernels(n, ndim, kw.get("psfs"), kw.get("psf_type", PSFType.EFFICIENT_BAYESIAN), kw["output_spacing"],
+                                 kw.get("na", 0.8), kw.get("wavelength_um", 0.5))
+    S = int(np.prod(out_shape))
+    views_t = DeviceArray.empty((n,) + out_shape, np.float32, device)
+    blend = DeviceArray.empty((n,) + out_shape, np.float32, device)
+    s3 = _lib.i64x3(shape3(out_shape))
+    keep = []
+    for i, (sim, param, spacing) in enumerate(zip(sims, params, spacings)):
+        p_inv = np.linalg.inv(np.asarray(param, dtype=np.float64))
+        in_spacing = spacing if spacing is not None else si_utils.get_spacing_from_sim(sim)
+        matrix, offset = get_pixel_affine(p_inv, si_utils.get_origin_from_sim(sim, asarray=True), _as_zyx(in_spacing, sdims),
+                                          o_origin, o_spacing)
+        data = sim.data
+        view = _lib.mvs_view_t()
+        if is_device_array(data):
+            data = data.on_device(device)
+            data.wait_ready(device)
+            if data.dtype not in _lib.DTYPE_CODES:
+                raise TypeError(f"unsupported dtype {data.dtype}")
+            fill_view_geometry(view, data.ptr, _lib.DTYPE_CODES[data.dtype], _lib.MVS_MEM_DEVICE, data.shape, data.strides, matrix, offset)
+        else:
+            data = np.ascontiguousarray(data)
+            if data.dtype not in _lib.DTYPE_CODES:
+                data = data.astype(np.float32)
+            fill_view_geometry(view, data.ctypes.data, _lib.DTYPE_CODES[data.dtype], _lib.MVS_MEM_HOST, data.shape,
+                               [int(np.prod(data.shape[k + 1:])) for k in range(data.ndim)], matrix, offset)
+        keep.append(data)
+        rc = lib.mvs_resample(device, C.byref(view), s3, int(interpolation_order), float("nan"), C.c_void_p(views_t.ptr + 4 * i * S),
+                              _lib.MVS_MEM_DEVICE)
+        _lib.check(rc, device, "mvs_resample")
+        wview = _lib.mvs_view_t()
+        weights.fill_view_weights(wview, _bb_dicts(full_view_bbs[i], sdims), param, o_origin, o_spacing, blending_widths,
+                                  shrink_distance)
+        rc = lib.mvs_blend_weights(device, C.byref(wview), ndim, s3, C.c_void_p(blend.ptr + 4 * i * S), _lib.MVS_MEM_DEVICE)
+        _lib.check(rc, device, "mvs_blend_weights")
+    if not isinstance(trim_overlap_in_pixels, dict):
+        trim = [int(trim_overlap_in_pixels)] * ndim
+    else:
+        trim = [int(trim_overlap_in_pixels.get(d, 0)) for d in sdims]
+    on_device = out is not None or output_on_backend
+    res = mv_deconv._run(views_t, blend, ndim, kernels, kw.get("n_iterations", 10), kw.get("lambda_reg", 0.0),
+                         kw.get("min_value", 1e-4), kw.get("sample_boundary_erosion_px", 0), trim, input_dtype, on_device, device,
+                         prepare_weights=True, out=out)
+    del keep
+    return res
 
 
 def _host_weighted_average_fusion(transformed_views, blending_weights, fusion_weights=None):
