@@ -337,10 +337,10 @@ extern "C" int mvs_mv_deconv(int device, const float* views, float* weights, int
     // host tap tables in correlation order: general [set][v][kz][ky][kxp] (x zero-padded), separable [set][v][kz + ky + kx]
     const long long kvol = (long long)kz * ky * kx, kvolp = (long long)kz * ky * kxp, ksep = kz + ky + kx;
     std::vector<float> htaps;
-    float sep_cval[64][2];                // per view: cval of the y and z passes of the back projection
+    std::vector<float> sep_cval;          // per view: cval of the y and z passes of the back projection
     if (separable) {
-        if (V > 64) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: at most 64 views on the separable path");
         htaps.resize(2 * V * ksep);
+        sep_cval.resize(2 * (size_t)V);
         for (int s = 0; s < 2; ++s)
             for (int v = 0; v < V; ++v) {
                 const float* src = (s ? sep2 : sep1) + v * ksep;
@@ -355,8 +355,8 @@ extern "C" int mvs_mv_deconv(int device, const float* views, float* weights, int
                     double sx = 0.0, sy = 0.0;
                     for (int j = 0; j < kx; ++j) sx += src[kz + ky + j];
                     for (int j = 0; j < ky; ++j) sy += src[kz + j];
-                    sep_cval[v][0] = (float)sx;
-                    sep_cval[v][1] = (float)(sx * sy);
+                    sep_cval[2 * v] = (float)sx;
+                    sep_cval[2 * v + 1] = (float)(sx * sy);
                 }
             }
     } else {
@@ -461,9 +461,9 @@ extern "C" int mvs_mv_deconv(int device, const float* views, float* weights, int
                 hipLaunchKernelGGL((deconv_pass<1, 0, 0>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)pa, pb, t1 + kz, nz, ny, nx, ky, ay, 0.f, e);
                 hipLaunchKernelGGL((deconv_pass<0, 0, 1>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)pb, wr, t1, nz, ny, nx, kz, az, 0.f, e);
                 hipLaunchKernelGGL((deconv_pass<2, 1, 0>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)wr, pa, t2 + kz + ky, nz, ny, nx, kx, ax, 1.f, e);
-                hipLaunchKernelGGL((deconv_pass<1, 1, 0>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)pa, pb, t2 + kz, nz, ny, nx, ky, ay, sep_cval[v][0], e);
+                hipLaunchKernelGGL((deconv_pass<1, 1, 0>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)pa, pb, t2 + kz, nz, ny, nx, ky, ay, sep_cval[2 * v], e);
                 hipLaunchKernelGGL((deconv_pass<0, 1, 2>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)pb, (float*)nullptr, t2, nz, ny, nx, kz, az,
-                                   sep_cval[v][1], e);
+                                   sep_cval[2 * v + 1], e);
                 DECONV_TRY(hipGetLastError());
             }
         }

@@ -79,9 +79,21 @@ def kernels(n_views, ndim, psfs=None, psf_type="EFFICIENT_BAYESIAN", output_spac
     return out, [back_kernel(v, out, psf_type) for v in range(n_views)]
 
 
+def forward_convolve(psi, kernel):
+    """mv_deconv.py:437-440: the forward projection."""
+    return ndimage.convolve(psi, kernel, mode="mirror")
+
+
+def back_convolve(wr, kernel):
+    """mv_deconv.py:464-467: the back projection."""
+    return ndimage.convolve(wr, kernel, mode="constant", cval=1.0)
+
+
 def deconvolve(views, blend, psfs=None, psf_type="EFFICIENT_BAYESIAN", n_iterations=10, lambda_reg=0.0, min_value=1e-4,
-               output_spacing=None, na=0.8, wavelength_um=0.5, sample_boundary_erosion_px=0):
-    """mv_deconv.py:251-501 on host arrays."""
+               output_spacing=None, na=0.8, wavelength_um=0.5, sample_boundary_erosion_px=0, convolutions=None):
+    """mv_deconv.py:251-501 on host arrays.  ``convolutions``: an optional (forward, back) pair of callables
+    f(array, kernel) -> array replacing forward_convolve / back_convolve (the tests inject deliberate mistakes with it)."""
+    fwd, back = convolutions or (forward_convolve, back_convolve)
     views = np.asarray(views)
     n_views, ndim, dtype = views.shape[0], views.ndim - 1, views.dtype
     covered = ~np.isnan(views)                                                     # :354-355
@@ -95,10 +107,10 @@ def deconvolve(views, blend, psfs=None, psf_type="EFFICIENT_BAYESIAN", n_iterati
     one = np.float32(1.0)
     for _ in range(n_iterations):                                                    # :428-483
         for v in range(n_views):
-            blurred = ndimage.convolve(psi, k1[v], mode="mirror")
+            blurred = fwd(psi, k1[v])
             ratio = np.where(covered[v], obs[v] / np.maximum(blurred, mv), np.ones_like(blurred))
             wr = one + blend[v] * (ratio - one)
-            value = psi * ndimage.convolve(wr, k2[v], mode="constant", cval=1.0)
+            value = psi * back(wr, k2[v])
             if lambda_reg > 0:
                 x = np.maximum(value, np.float32(0.0)) / peak
                 value = (np.sqrt(one + np.float32(2.0 * lambda_reg) * x) - one) / np.float32(lambda_reg) * peak
@@ -162,6 +174,129 @@ def cases():
     out["2d_thin"] = (v, w, dict(psf_type="OPTIMIZATION_II"))
     v, w = _views(26, 1, (24, 28))
     out["2d_one_view"] = (v, w, dict(min_value=1e-3))
+    v, w = _views(27, 2, (10, 14, 18), nan_views=(0,))
+    out["3d_even_asymmetric"] = (v, w, dict(psfs=[_psf2(8, (4, 6, 4)), _psf2(9, (4, 6, 4))]))
+    v, w = _views(28, 2, (10, 14, 18))
+    out["3d_rank1_asymmetric"] = (v, w, dict(psfs=[_rank1(10, (3, 4, 5)), _rank1(11, (3, 4, 5))], psf_type="OPTIMIZATION_I"))
+    return out
+
+
+# --- edge cases of the GPU kernels (tile edges, wide / even / asymmetric kernels, thin chunks, zero coverage); checked
+# against deconvolve() directly, never stored in the fixture ---
+def _hf_views(seed, n_views, shape, holes=False):
+    """Views with high-frequency content (white noise plus sparse bright beads, so a shifted or flipped kernel shows)
+    and normalised blending weights.  ``holes``: every view loses a border block and an interior block (NaN), so some
+    voxels have no view at all and their weights normalise 0 -> 0 / 1."""
+    rng = np.random.default_rng(seed)
+    base = rng.random(shape) * 100.0 + 20.0
+    base[rng.random(shape) < 0.01] += 1500.0
+    views = np.stack([base * (0.8 + 0.4 * rng.random()) + rng.random(shape) * 20.0 for _ in range(n_views)]).astype(np.float32)
+    if holes:
+        corner = tuple(slice(0, max(1, n // 3)) for n in shape)
+        inner = tuple(slice(n // 2, n // 2 + max(1, n // 5)) for n in shape)
+        views[(slice(None),) + corner] = np.nan
+        views[(slice(None),) + inner] = np.nan
+    w = rng.random((n_views,) + tuple(shape)).astype(np.float32) + np.float32(0.05)
+    w = w * ~np.isnan(views)
+    s = np.nansum(w, axis=0)
+    s[s == 0] = 1
+    return views, (w / s).astype(np.float32)
+
+
+def _rand_psf(seed, shape):
+    """A random positive PSF that is far from rank 1 and from symmetric (a few taps dominate)."""
+    return (np.random.default_rng(seed).random(shape) ** 6 + 0.01).astype(np.float32)
+
+
+def _rank1(seed, shape):
+    """Outer product of random asymmetric positive 1-D factors: rank 1, so it takes the separable path."""
+    rng = np.random.default_rng(seed)
+    k = np.ones((), np.float64)
+    for n in shape:
+        k = np.multiply.outer(k, rng.random(n) ** 2 + 0.05)
+    return k.astype(np.float32)
+
+
+def edge_cases():
+    """name -> (views, blending_weights, kwargs of multi_view_deconvolution, n_iterations)."""
+    out = {}
+    # 2D: partial x and y tiles of the direct path (64 x 32), the widest window (kx = 63 -> kxp = 64), an even PSF padded
+    # asymmetrically to the common shape, a halo taller than the tile (ky = 63), kx = 5 -> kxp = 8
+    v, w = _hf_views(100, 2, (100, 200))
+    out["2d_wide_63x63"] = (v, w, dict(psfs=[_rand_psf(101, (63, 63)), _rand_psf(102, (61, 62))]), 1)
+    v, w = _hf_views(103, 2, (90, 150))
+    out["2d_tall_63x5"] = (v, w, dict(psfs=[_rand_psf(104, (63, 5)), _rand_psf(105, (63, 5))]), 1)
+    v, w = _hf_views(106, 2, (40, 140))
+    out["2d_flat_5x63"] = (v, w, dict(psfs=[_rand_psf(107, (5, 63)), _rand_psf(108, (4, 62))], psf_type="INDEPENDENT"), 2)
+    v, w = _hf_views(109, 2, (70, 130))
+    out["2d_even_62x4"] = (v, w, dict(psfs=[_rand_psf(110, (62, 4)), _rand_psf(111, (62, 4))], psf_type="OPTIMIZATION_II"), 2)
+    # 3D direct path across x and y tiles, flip and origin along every axis
+    v, w = _hf_views(112, 2, (7, 45, 150))
+    out["3d_direct_odd"] = (v, w, dict(psfs=[_rand_psf(113, (5, 7, 9)), _rand_psf(114, (5, 7, 9))]), 2)
+    v, w = _hf_views(115, 2, (7, 45, 150))
+    out["3d_direct_even"] = (v, w, dict(psfs=[_rand_psf(116, (4, 6, 8)), _rand_psf(117, (4, 6, 8))]), 2)
+    # 3D separable path: asymmetric and even factors, every compound kernel type
+    for i, t in enumerate(PSF_TYPES):
+        for parity, ks in (("even", (4, 6, 10)), ("odd", (5, 7, 9))):
+            v, w = _hf_views(120 + 2 * i + (parity == "odd"), 2, (9, 40, 130))
+            psfs = [_rank1(130 + 4 * i + 2 * (parity == "odd"), ks), _rank1(131 + 4 * i + 2 * (parity == "odd"), ks)]
+            out[f"3d_rank1_{parity}_{t}"] = (v, w, dict(psfs=psfs, psf_type=t), 2)
+    # a length-1 kernel axis; kx a multiple of 4 (no x padding)
+    v, w = _hf_views(150, 2, (8, 30, 140))
+    out["3d_ky1_kx12"] = (v, w, dict(psfs=[_rand_psf(151, (5, 1, 12)), _rand_psf(152, (5, 1, 12))]), 2)
+    v, w = _hf_views(153, 2, (8, 30, 140))
+    out["3d_rank1_kz1_kx12"] = (v, w, dict(psfs=[_rank1(154, (1, 7, 12)), _rank1(155, (1, 7, 12))]), 2)
+    # chunks thinner than the kernel: mirror wraps periodically, a length-1 axis is constant (rank 1: both paths)
+    v, w = _hf_views(156, 2, (1, 40, 70))
+    out["3d_nz1_kz9"] = (v, w, dict(psfs=[_rank1(157, (9, 5, 6)), _rank1(158, (9, 5, 6))]), 2)
+    v, w = _hf_views(159, 2, (2, 30, 70))
+    out["3d_nz2_kz15"] = (v, w, dict(psfs=[_rank1(160, (15, 3, 5)), _rank1(161, (15, 3, 5))]), 2)
+    v, w = _hf_views(162, 2, (10, 3, 70))
+    out["3d_ny3_ky15"] = (v, w, dict(psfs=[_rank1(163, (3, 15, 5)), _rank1(164, (3, 15, 5))]), 2)
+    # voxels no view covers (a border block and an interior hole in every view), 2D erosion, the peak of lambda_reg
+    for ndim, shape in ((2, (40, 60)), (3, (10, 30, 40))):
+        for erosion, lam in ((0, 0.01), (3, 0.0), (3, 0.01)):
+            v, w = _hf_views(170 + 10 * ndim + erosion + int(lam > 0), 2, shape, holes=True)
+            kw = dict(sample_boundary_erosion_px=erosion, lambda_reg=lam)
+            out[f"{ndim}d_uncovered_erosion{erosion}_lambda{int(lam > 0)}"] = (v, w, kw, 2)
+    # the view count of the separable path's per-view tables
+    for n in (64, 65):
+        v, w = _hf_views(200 + n, n, (16, 20))
+        out[f"2d_views{n}"] = (v, w, {}, 1)
+    # no iteration: init, clamp, erosion mask and cast only
+    v, w = _hf_views(210, 2, (6, 20, 30), holes=True)
+    out["3d_zero_iterations"] = (v, w, dict(sample_boundary_erosion_px=1), 0)
+    return out
+
+
+# mistakes each edge case must catch (tests/test_mv_deconv_host.py injects them through deconvolve's ``convolutions``):
+# flip_<axis> flips the kernel along one axis, origin_<axis> shifts it by one voxel along an even axis, reflect uses
+# mode "reflect" for the forward projection, cval0 pads the back projection with 0, sep_cval1 runs the back projection
+# as three 1-D passes whose later passes pad with 1 instead of the product of the earlier factors' sums.
+def edge_mutations():
+    flips2, flips3 = ("flip_y", "flip_x"), ("flip_z", "flip_y", "flip_x")
+    bounds = ("reflect", "cval0")
+    out = {
+        "2d_wide_63x63": flips2 + bounds,
+        "2d_tall_63x5": flips2 + bounds,
+        "2d_flat_5x63": flips2 + bounds,
+        "2d_even_62x4": flips2 + ("origin_y", "origin_x") + bounds,
+        "3d_direct_odd": flips3 + bounds,
+        "3d_direct_even": flips3 + ("origin_z", "origin_y", "origin_x") + bounds,
+        "3d_ky1_kx12": ("flip_z", "flip_x", "origin_x") + bounds,
+        "3d_rank1_kz1_kx12": ("flip_y", "flip_x", "origin_x") + bounds + ("sep_cval1",),
+        "3d_nz1_kz9": flips2 + bounds + ("sep_cval1",),
+        "3d_nz2_kz15": flips2 + bounds + ("sep_cval1",),
+        "3d_ny3_ky15": ("flip_z", "flip_x") + bounds + ("sep_cval1",),
+        "2d_views64": bounds,
+        "2d_views65": bounds,
+    }
+    for t in PSF_TYPES:
+        out[f"3d_rank1_even_{t}"] = flips3 + ("origin_z", "origin_y", "origin_x") + bounds + ("sep_cval1",)
+        out[f"3d_rank1_odd_{t}"] = flips3 + bounds + ("sep_cval1",)
+    for ndim in (2, 3):
+        for erosion, lam in ((0, 1), (3, 0), (3, 1)):
+            out[f"{ndim}d_uncovered_erosion{erosion}_lambda{lam}"] = bounds
     return out
 
 

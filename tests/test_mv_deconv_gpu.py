@@ -1,7 +1,11 @@
 """GPU: multi-view deconvolution (fusion.multi_view_deconvolution, csrc/mvs_deconv.hip) against the numpy / scipy
 restatement of the reference (tests/deconv_oracle.py): the direct function on both convolution paths, fuse_np against
 the oracle chain resample + blending weights + restatement, a chunked fuse() (in memory and to Zarr) against the
-per-chunk oracle composed into the mosaic, and DeviceArray in / out."""
+per-chunk oracle composed into the mosaic, and DeviceArray in / out.  The edge cases (do.edge_cases(): tile edges, the
+widest and tallest kernels, even and asymmetric kernels on both paths, thin chunks, voxels no view covers, 65 views)
+run a few iterations each; tests/test_mv_deconv_host.py shows that each would catch the kernel mistakes it targets."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -43,6 +47,47 @@ def test_direct_call_matches_restatement(hip_device, conv_path, name):
     _close(got, want)
 
 
+@functools.lru_cache(maxsize=None)
+def _edge_cases():
+    return do.edge_cases()
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_want(name, dtype=np.float32):
+    """The restatement's result of an edge case (computed once for both paths); integer dtypes take the views with
+    NaN -> 0 cast to that dtype."""
+    views, blend, kw, it = _edge_cases()[name]
+    if np.dtype(dtype) != np.float32:
+        views = np.nan_to_num(views).astype(dtype)
+    return views, do.deconvolve(views, blend, n_iterations=it, **kw)
+
+
+@pytest.mark.parametrize("name", sorted(do.edge_cases()))
+def test_edge_case_matches_restatement(hip_device, conv_path, name):
+    from multiview_stitcher_amd import fusion
+
+    views, blend, kw, it = _edge_cases()[name]
+    _, want = _edge_want(name)
+    got = fusion.multi_view_deconvolution(views, blend, n_iterations=it, device=hip_device, **kw)
+    assert got.dtype == want.dtype and got.shape == want.shape
+    if kw.get("sample_boundary_erosion_px"):
+        np.testing.assert_array_equal(got == 0, want == 0)
+    _close(got, want)
+
+
+@pytest.mark.parametrize("name", ["3d_rank1_even_OPTIMIZATION_I", "3d_direct_even", "2d_uncovered_erosion3_lambda1"])
+def test_edge_case_integer_output(hip_device, conv_path, name):
+    from multiview_stitcher_amd import fusion
+
+    _, blend, kw, it = _edge_cases()[name]
+    views, want = _edge_want(name, np.uint16)
+    got = fusion.multi_view_deconvolution(views, blend, n_iterations=it, device=hip_device, **kw)
+    assert got.dtype == want.dtype == np.uint16 and got.shape == want.shape
+    assert np.abs(got.astype(np.int64) - want.astype(np.int64)).max() <= 1
+    if kw.get("sample_boundary_erosion_px"):
+        np.testing.assert_array_equal(got == 0, want == 0)
+
+
 def test_separable_path_is_taken_for_gaussians(hip_device):
     """The default PSF and its compound kernels pass the rank-1 test (both tables present); a non-separable PSF does not."""
     from multiview_stitcher_amd import mv_deconv
@@ -61,6 +106,21 @@ def test_uint16_direct_call_casts_like_astype(hip_device):
     want = do.deconvolve(v16, blend, n_iterations=ITERATIONS)
     got = fusion.multi_view_deconvolution(v16, blend, n_iterations=ITERATIONS, device=hip_device)
     assert got.dtype == np.uint16
+    assert np.abs(got.astype(np.int64) - want.astype(np.int64)).max() <= 1
+
+
+def test_uint8_direct_call_casts_like_astype(hip_device, conv_path):
+    """uint8 views kept well below 255 (the result must not overshoot: numpy's out-of-range float -> uint cast is
+    platform-dependent)."""
+    from multiview_stitcher_amd import fusion
+
+    views, blend, kw = do.cases()["3d_default"]
+    v8 = (np.nan_to_num(views) * np.float32(0.5)).astype(np.uint8)
+    assert v8.max() <= 120
+    want = do.deconvolve(v8, blend, n_iterations=ITERATIONS)
+    assert want.max() < 200
+    got = fusion.multi_view_deconvolution(v8, blend, n_iterations=ITERATIONS, device=hip_device)
+    assert got.dtype == np.uint8
     assert np.abs(got.astype(np.int64) - want.astype(np.int64)).max() <= 1
 
 
@@ -88,6 +148,8 @@ def _rotated_pair(dtype, ndim=3):
     from scipy import ndimage
 
     base = ndimage.gaussian_filter(base, 1.5) * 3
+    if dtype == np.uint8:
+        base = base * np.float32(110.0 / base.max())
     sims, params = [], []
     for i in range(2):
         arr = base.astype(dtype)
@@ -107,14 +169,16 @@ def _translated_pair(dtype):
     from multiview_stitcher_amd import sample_data
 
     sims, _, _ = sample_data.generate_tiled_dataset(ndim=3, tile_shape=(10, 30, 34), tiles=(1, 1, 2), overlap=(0, 0, 12),
-                                                    dtype=dtype, max_jitter=0)
+                                                    dtype=np.float32 if dtype == np.uint8 else dtype, max_jitter=0)
     sims = [squeeze_field(s) for s in sims]
+    if dtype == np.uint8:        # values in [5, 115], so the result does not overshoot 255
+        sims = [s.copy(data=(np.asarray(s.data) * np.float32(110.0) + np.float32(5.0)).astype(np.uint8)) for s in sims]
     params = [np.eye(4) for _ in sims]
     params[1][:3, 3] = [0.0, 0.4, -1.7]
     return sims, params
 
 
-@pytest.mark.parametrize("dtype", [np.uint16, np.float32])
+@pytest.mark.parametrize("dtype", [np.uint16, np.float32, np.uint8])
 @pytest.mark.parametrize("geometry", ["translated", "rotated"])
 def test_fuse_np_matches_oracle_chain(hip_device, dtype, geometry):
     from multiview_stitcher_amd import fusion, spatial_image_utils as si
@@ -129,7 +193,9 @@ def test_fuse_np_matches_oracle_chain(hip_device, dtype, geometry):
                          fusion_func_kwargs=kw, full_view_bbs=[bb_to_dicts(b, sdims) for b in bbs],
                          trim_overlap_in_pixels={"z": 0, "y": 2, "x": 2}, device=hip_device)
     assert got.dtype == want.dtype and got.shape == want.shape
-    if dtype == np.uint16:
+    if dtype == np.uint8:
+        assert want.max() < 200
+    if dtype != np.float32:
         assert np.abs(got.astype(np.int64) - want.astype(np.int64)).max() <= 1
     else:
         _close(got, want)
@@ -139,6 +205,42 @@ def test_fuse_np_matches_oracle_chain(hip_device, dtype, geometry):
     np.testing.assert_array_equal(dev.get(), got)
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.uint16])
+def test_fuse_np_2d_three_rotated_views(hip_device, dtype):
+    """fuse_np in 2D with three rotated and shifted views: the union box has corners no view covers (weights 0 / 1,
+    ratio 1) and every voxel of the chunk has its own mix of weights."""
+    from multiview_stitcher_amd import fusion
+    from multiview_stitcher_amd import spatial_image_utils as si
+    from scipy import ndimage
+
+    rng = np.random.default_rng(11)
+    base = ndimage.gaussian_filter(rng.random((40, 46)) * 300.0, 1.0) + rng.random((40, 46)) * 40.0 + 20.0
+    sims, params = [], []
+    for angle, shift in ((0.0, (0.0, 0.0)), (9.0, (2.4, -3.1)), (-14.0, (-1.7, 2.6))):
+        s = si.get_sim_from_array(base.astype(dtype), dims=["y", "x"], scale={"y": 1.0, "x": 1.0}, translation={"y": 0.0, "x": 0.0})
+        sims.append(squeeze_field(s))
+        a = np.deg2rad(angle)
+        p = np.eye(3)
+        p[:2, :2] = [[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]
+        p[:2, 2] = shift
+        params.append(p)
+    sdims = ["y", "x"]
+    views, bbs = zip(*[sim_to_view(s) for s in sims])
+    out_bb = union_bb(bbs, params, np.ones(2))
+    kw = {"n_iterations": 4, "psf_type": "OPTIMIZATION_II", "sample_boundary_erosion_px": 1}
+    want = _oracle_chunk(views, params, out_bb, bbs, (2, 2), kw, dtype)
+    got = fusion.fuse_np(list(sims), params, bb_to_dicts(out_bb, sdims), fusion_func=fusion.multi_view_deconvolution,
+                         fusion_func_kwargs=kw, full_view_bbs=[bb_to_dicts(b, sdims) for b in bbs],
+                         trim_overlap_in_pixels={"y": 2, "x": 2}, device=hip_device)
+    assert got.dtype == want.dtype and got.shape == want.shape
+    assert (want == 0).any() and (want > 0).mean() > 0.5       # uncovered corners, eroded to 0
+    np.testing.assert_array_equal(got == 0, want == 0)
+    if dtype == np.uint16:
+        assert np.abs(got.astype(np.int64) - want.astype(np.int64)).max() <= 1
+    else:
+        _close(got, want)
+
+
 def _params_of(sim, key):
     from multiview_stitcher_amd import spatial_image_utils as si
 
@@ -146,26 +248,21 @@ def _params_of(sim, key):
     return p.reshape((-1,) + p.shape[-2:])[0]
 
 
-def test_fuse_chunked_mosaic_matches_per_chunk_oracle(hip_device, tmp_path):
-    from multiview_stitcher_amd import fusion, mv_graph, sample_data
+def _per_chunk_oracle(sims, fused, key, chunks, kw):
+    """The mosaic that fuse() with ``fusion_func=multi_view_deconvolution`` should produce: the plan oracle's chunks
+    (with the deconvolution's halo), each run through the oracle chain of fuse_np, trimmed and composed.  Returns the
+    mosaic (in the fused result's dtype) and the number of chunks that had views."""
+    from multiview_stitcher_amd import fusion, mv_graph
     from multiview_stitcher_amd import spatial_image_utils as si
 
-    key = sample_data.METADATA_TRANSFORM_KEY
-    sims, _, _ = sample_data.generate_tiled_dataset(ndim=3, tile_shape=(8, 28, 30), tiles=(2, 2, 2), overlap=(3, 8, 8),
-                                                    max_jitter=0, dtype=np.uint16)
-    kw = {"n_iterations": 4, "psf_type": "OPTIMIZATION_I"}
-    chunks = {"z": 7, "y": 20, "x": 24}
-    fused = fusion.fuse(sims, transform_key=key, fusion_func=fusion.multi_view_deconvolution, fusion_func_kwargs=kw,
-                        output_chunksize=chunks, device=hip_device)
-    got = np.asarray(fused.data).reshape(np.asarray(fused.data).shape[-3:])
-
+    got_dtype = np.asarray(fused.data).dtype
+    shape = np.asarray(fused.data).shape[-3:]
     sq = [squeeze_field(s) for s in sims]
     sdims = si.get_spatial_dims_from_sim(sq[0])
     params = [_params_of(s, key) for s in sims]
     bbs = [si.get_stack_properties_from_sim(s) for s in sq]
     osp = si.get_stack_properties_from_sim(squeeze_field(fused))
     halo = fusion.multi_view_deconvolution.required_overlap(kw)
-    assert halo == 4
     overlap = {d: halo for d in sdims}
     cbb, bidx = mv_graph.get_chunk_bbs(osp, chunks)
     cbb_ov = [cb | {"origin": {d: cb["origin"][d] - overlap[d] * osp["spacing"][d] for d in sdims}}
@@ -174,7 +271,7 @@ def test_fuse_chunked_mosaic_matches_per_chunk_oracle(hip_device, tmp_path):
         sparams=params, views_bb=bbs, output_stack_properties=osp, output_chunksize=chunks, output_chunk_bbs=cbb,
         output_chunk_bbs_with_overlap=cbb_ov, output_chunk_bbs_for_result=cbb, block_indices=bidx, overlap_in_pixels=overlap,
         trim_overlap=True, interpolation_order=1, sdims=sdims)
-    want = np.zeros(got.shape, got.dtype)
+    want = np.zeros(shape, got_dtype)
     n_chunks = 0
     for entry in plan["per_chunk_entries"]:
         if not entry["views"]:
@@ -190,10 +287,27 @@ def test_fuse_chunked_mosaic_matches_per_chunk_oracle(hip_device, tmp_path):
                               [bbs[iv]["shape"][d] for d in sdims]))
         ob = entry["output_bb_overlap"]
         out_bb = fo.bb([ob["origin"][d] for d in sdims], [ob["spacing"][d] for d in sdims], [ob["shape"][d] for d in sdims])
-        chunk = _oracle_chunk(views, vparams, out_bb, fbbs, (halo,) * 3, kw, np.uint16)
+        chunk = _oracle_chunk(views, vparams, out_bb, fbbs, (halo,) * 3, kw, got_dtype)
         res = entry["output_bb_result"]
         lo = [int(round((res["origin"][d] - osp["origin"][d]) / osp["spacing"][d])) for d in sdims]
         want[tuple(slice(a, a + n) for a, n in zip(lo, chunk.shape))] = chunk
+    return want, n_chunks
+
+
+def test_fuse_chunked_mosaic_matches_per_chunk_oracle(hip_device, tmp_path):
+    from multiview_stitcher_amd import fusion, sample_data
+
+    key = sample_data.METADATA_TRANSFORM_KEY
+    sims, _, _ = sample_data.generate_tiled_dataset(ndim=3, tile_shape=(8, 28, 30), tiles=(2, 2, 2), overlap=(3, 8, 8),
+                                                    max_jitter=0, dtype=np.uint16)
+    kw = {"n_iterations": 4, "psf_type": "OPTIMIZATION_I"}
+    chunks = {"z": 7, "y": 20, "x": 24}
+    fused = fusion.fuse(sims, transform_key=key, fusion_func=fusion.multi_view_deconvolution, fusion_func_kwargs=kw,
+                        output_chunksize=chunks, device=hip_device)
+    got = np.asarray(fused.data).reshape(np.asarray(fused.data).shape[-3:])
+
+    assert fusion.multi_view_deconvolution.required_overlap(kw) == 4
+    want, n_chunks = _per_chunk_oracle(sims, fused, key, chunks, kw)
     assert n_chunks > 4
     assert np.abs(got.astype(np.int64) - want.astype(np.int64)).max() <= 1
 
@@ -204,16 +318,22 @@ def test_fuse_chunked_mosaic_matches_per_chunk_oracle(hip_device, tmp_path):
 
 def test_single_plane_chunks(hip_device):
     """fuse() with a z chunk of 1 on the views' z grid: every chunk is one plane plus the 4-voxel halo, thinner than the
-    PSF (mirror boundaries wrap periodically there)."""
+    PSF (mirror boundaries wrap periodically there); the mosaic equals the per-chunk oracle."""
     from multiview_stitcher_amd import fusion, sample_data
 
     key = sample_data.METADATA_TRANSFORM_KEY
     sims, _, _ = sample_data.generate_tiled_dataset(ndim=3, tile_shape=(4, 24, 26), tiles=(1, 2, 2), overlap=(0, 8, 8),
                                                     max_jitter=0, dtype=np.uint16)
+    kw = {"n_iterations": 3}
+    chunks = {"z": 1, "y": 24, "x": 24}
     fused = fusion.fuse(sims, transform_key=key, fusion_func=fusion.multi_view_deconvolution,
-                        fusion_func_kwargs={"n_iterations": 3}, output_chunksize={"z": 1, "y": 24, "x": 24}, device=hip_device)
+                        fusion_func_kwargs=kw, output_chunksize=chunks, device=hip_device)
     d = np.asarray(fused.data)
     assert d.shape[-3] == 4 and d.max() > 0
+    got = d.reshape(d.shape[-3:])
+    want, n_chunks = _per_chunk_oracle(sims, fused, key, chunks, kw)
+    assert n_chunks >= 4 * 4
+    assert np.abs(got.astype(np.int64) - want.astype(np.int64)).max() <= 1
 
 
 def test_device_arrays_in_and_out(hip_device):

@@ -2,10 +2,12 @@
 compound-kernel helpers against the reference's outputs (tests/golden/mv_deconv_ref.npz), required_overlap, the
 rank-1 test, the public names, the C ABI's struct and argument checks (no device needed)."""
 import ctypes
+import functools
 import os
 
 import numpy as np
 import pytest
+from scipy import ndimage
 
 from tests import deconv_oracle as do
 
@@ -127,3 +129,100 @@ def test_abi_refuses_bad_arguments():
     assert call(o=bad) == -1
     bad.out_dtype, bad.trim[1] = _lib.MVS_F32, 2
     assert call(o=bad) == -1                            # the trim leaves nothing
+
+
+# --- the edge cases of the GPU tests can fail: each mistake their row targets, injected into the restatement, moves the
+# result by at least 20 times the GPU tests' tolerance (2e-4 of the maximum) ---
+GPU_REL_TOL = 2e-4
+_AXIS_FROM_END = {"z": 3, "y": 2, "x": 1}
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_case(name):
+    return do.edge_cases()[name]
+
+
+@functools.lru_cache(maxsize=4)
+def _edge_truth(name):
+    views, blend, kw, _ = _edge_case(name)
+    return do.deconvolve(views, blend, n_iterations=1, **kw)
+
+
+def _separable_back(wr, kernel, later_cval_one):
+    """The back projection as three 1-D passes (x, then y, then z) with factors whose sums are not 1 (x factor doubled,
+    first factor halved; the kernel, their outer product, is unchanged).  The later passes pad with the product of the
+    earlier factors' sums, or with 1 when ``later_cval_one``."""
+    k = np.asarray(kernel, np.float64)
+    nd, total = k.ndim, k.sum()
+    f = [k.sum(axis=tuple(a for a in range(nd) if a != d)) for d in range(nd)]
+    f = [g / total for g in f[:-1]] + [f[-1]]
+    f[-1], f[0] = f[-1] * 2.0, f[0] * 0.5
+    out, cval = wr.astype(np.float64), 1.0
+    for d in reversed(range(nd)):
+        out = ndimage.convolve1d(out, f[d], axis=d, mode="constant", cval=1.0 if later_cval_one else cval)
+        cval *= f[d].sum()
+    return out.astype(np.float32)
+
+
+def _mutation(name, ndim):
+    fwd, back = do.forward_convolve, do.back_convolve
+    if name.startswith("flip_"):
+        a = ndim - _AXIS_FROM_END[name[-1]]
+        return (lambda p, k: fwd(p, np.flip(k, a)), lambda p, k: back(p, np.flip(k, a)))
+    if name.startswith("origin_"):
+        origin = [0] * ndim
+        origin[ndim - _AXIS_FROM_END[name[-1]]] = -1
+        return (lambda p, k: ndimage.convolve(p, k, mode="mirror", origin=origin),
+                lambda p, k: ndimage.convolve(p, k, mode="constant", cval=1.0, origin=origin))
+    if name == "reflect":
+        return (lambda p, k: ndimage.convolve(p, k, mode="reflect"), back)
+    if name == "cval0":
+        return (fwd, lambda p, k: ndimage.convolve(p, k, mode="constant", cval=0.0))
+    if name == "sep_cval1":
+        return (fwd, lambda p, k: _separable_back(p, k, True))
+    raise KeyError(name)
+
+
+@pytest.mark.parametrize("name,mutation", [(n, m) for n, ms in sorted(do.edge_mutations().items()) for m in ms])
+def test_edge_case_catches_mutation(name, mutation):
+    views, blend, kw, _ = _edge_case(name)
+    want = _edge_truth(name)
+    got = do.deconvolve(views, blend, n_iterations=1, convolutions=_mutation(mutation, views.ndim - 1), **kw)
+    err = float(np.abs(got.astype(np.float64) - want).max())
+    assert err >= 20 * GPU_REL_TOL * float(np.abs(want).max()), (err, float(np.abs(want).max()))
+
+
+@pytest.mark.parametrize("name", sorted(n for n, ms in do.edge_mutations().items() if "sep_cval1" in ms))
+def test_separable_back_projection_harness(name):
+    """The three-pass back projection with the right pad values restates the direct one, so sep_cval1 is the only
+    change its mutation makes."""
+    views, blend, kw, _ = _edge_case(name)
+    want = _edge_truth(name)
+    got = do.deconvolve(views, blend, n_iterations=1, convolutions=(do.forward_convolve, lambda p, k: _separable_back(p, k, False)),
+                        **kw)
+    assert np.abs(got.astype(np.float64) - want).max() <= 1e-5 * np.abs(want).max()
+
+
+def test_edge_cases_are_separate_and_targeted():
+    """Edge cases stay out of the fixture's cases; every case with a kernel mistake to catch has its mutations listed;
+    each case takes the convolution path and kernel geometry it is there for."""
+    from multiview_stitcher_amd import mv_deconv
+
+    edge, muts = do.edge_cases(), do.edge_mutations()
+    assert not set(edge) & set(do.cases())
+    assert set(muts) == set(edge) - {"3d_zero_iterations"}
+    want_shape = {"2d_wide_63x63": (63, 63), "2d_tall_63x5": (63, 5), "2d_flat_5x63": (5, 63), "2d_even_62x4": (62, 4),
+                  "3d_direct_even": (4, 6, 8), "3d_ky1_kx12": (5, 1, 12), "3d_rank1_kz1_kx12": (1, 7, 12),
+                  "3d_nz1_kz9": (9, 5, 6), "3d_nz2_kz15": (15, 3, 5), "3d_ny3_ky15": (3, 15, 5)}
+    for name, (views, blend, kw, it) in edge.items():
+        assert views.dtype == np.float32 and blend.shape == views.shape and it in (0, 1, 2, 3), name
+        ndim = views.ndim - 1
+        k1, _, s1, s2 = mv_deconv._kernels(views.shape[0], ndim, kw.get("psfs"), kw.get("psf_type", "EFFICIENT_BAYESIAN"),
+                                           None, 0.8, 0.5)
+        separable = "rank1" in name or name.startswith(("3d_nz", "3d_ny")) or kw.get("psfs") is None
+        assert (s1 is not None and s2 is not None) == separable, name
+        if name in want_shape:
+            assert k1.shape[1 + 3 - ndim:] == want_shape[name], name
+        if "uncovered" in name or name == "3d_zero_iterations":
+            assert np.all(np.isnan(views), axis=0).any(), name
+    assert edge["2d_views65"][0].shape[0] == 65
