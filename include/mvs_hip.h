@@ -109,7 +109,8 @@ int mvs_set_stream(int device, void* hip_stream);
 int mvs_synchronize(int device);
 /* Tuning / test switches. "force_generic" = 1: mvs_fuse_chunk never takes the translation fast
  * path (both paths must agree; tests compare them).  "no_regions" = 1: skip the region kernels. "deconv_general" = 1: mvs_mv_deconv
- * convolves through the general direct path even when separable factors are passed (tests compare both paths).
+ * convolves through the general direct path even when separable factors are passed (tests compare both paths).  "dct_general" = 1:
+ * the DCT quality pass of mvs_fuse_chunk_dct / mvs_content_dct_weights takes its general path (tests compare both paths).
  * "pool_cache_limit_mb": bytes (MiB) mvs_free may keep cached for later mvs_malloc calls
  * (default 32768; 0 = release immediately).  "materialize_shifts" = 1: mvs_score_candidates / mvs_register_crops
  * always write the shifted copies of the moving image (by default finite-only crops evaluate them inside the SSIM z
@@ -222,6 +223,34 @@ int mvs_resample(int device, const mvs_view_t* view, const int64_t out_shape[3],
  * (weights.py:391-511): resampled 5^ndim support + cosine ramp, NOT normalised. */
 int mvs_blend_weights(int device, const mvs_view_t* view, int32_t ndim,
                       const int64_t out_shape[3], float* out, int32_t out_mem);
+
+/* ---- DCT-entropy fusion weights ------------------------------------------------ *
+ * Options of weights.content_based_dct (weights.py:77-290 of the reference). */
+typedef struct mvs_dct_opts_t {
+    int64_t dct_size[3];          /* requested block size per axis z,y,x (2D: [0] is ignored), each >= 1               */
+    int64_t output_chunksize[3];  /* per-axis clamp of the block size, read when has_output_chunksize                 */
+    double exponent;              /* exponent (weights.py:80)                                                          */
+    double otf_support_fraction;  /* read when has_otf; has_otf == 0 is otf_support_fraction=None (the L1 branch)      */
+    int32_t has_otf;
+    int32_t has_output_chunksize;
+} mvs_dct_opts_t;
+
+/* mvs_fuse_chunk_dct == fuse_np(fusion_func=weighted_average_fusion, weights_func=content_based_dct) for one chunk
+ * (fusion/_core.py:1620-1713, weights.py:77-290): every view is resampled onto the chunk (NaN outside), per view and
+ * block of the chunk the DCT-entropy quality is computed (blocks anchored at chunk index 0, sizes per `dopts` clamped to
+ * the chunk), the quality grids are shifted by their minimum over the views and normalised, and the weighted average of
+ * mvs_fuse_chunk runs with every view's weight multiplied by its trilinear, clamped lookup into its grid.  opts->weights
+ * must be MVS_WEIGHTS_NONE, opts->fusion MVS_FUSE_WEIGHTED_AVERAGE, opts->index_origin and the views' index_offset 0.
+ * Option "dct_general" = 1: the quality pass takes its general path (global scratch) even for blocks of <= 32 per axis. */
+int mvs_fuse_chunk_dct(int device, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts,
+                       const mvs_dct_opts_t* dopts, void* out);
+
+/* mvs_content_dct_weights == weights.content_based_dct on a float32 stack `views` (n_views x shape, z,y,x; 2D data as
+ * shape[0] == 1; NaN = outside the view): writes the normalised weights (n_views x shape, float32) to weights_out and,
+ * when quality_out is not NULL, the raw per-block qualities (n_views x nb0 x nb1 x nb2, before the shift by the minimum)
+ * to quality_out.  views, weights_out and quality_out all live in `mem` (MVS_MEM_HOST or MVS_MEM_DEVICE). */
+int mvs_content_dct_weights(int device, const float* views, int32_t n_views, const int64_t shape[3], int32_t ndim,
+                            const mvs_dct_opts_t* opts, float* weights_out, float* quality_out, int32_t mem);
 
 /* ---- multi-view deconvolution ------------------------------------------------- *
  * Options of mvs_mv_deconv (fusion/mv_deconv.py:251-264 of the reference). */

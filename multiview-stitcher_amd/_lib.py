@@ -73,6 +73,17 @@ class mvs_deconv_opts_t(C.Structure):
 MVS_DECONV_PREPARE_WEIGHTS = 1
 
 
+class mvs_dct_opts_t(C.Structure):
+    _fields_ = [
+        ("dct_size", C.c_int64 * 3),
+        ("output_chunksize", C.c_int64 * 3),
+        ("exponent", C.c_double),
+        ("otf_support_fraction", C.c_double),
+        ("has_otf", C.c_int32),
+        ("has_output_chunksize", C.c_int32),
+    ]
+
+
 class mvs_pair_job_t(C.Structure):
     _fields_ = [
         ("fixed", mvs_view_t),
@@ -109,6 +120,10 @@ SIGNATURES = {
     "mvs_fuse_chunk": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(mvs_fuse_opts_t), C.c_void_p]),
     "mvs_resample": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.POINTER(C.c_int64), C.c_int32, C.c_float, C.c_void_p, C.c_int32]),
     "mvs_blend_weights": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_int32]),
+    "mvs_fuse_chunk_dct": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(mvs_fuse_opts_t), C.POINTER(mvs_dct_opts_t),
+                                     C.c_void_p]),
+    "mvs_content_dct_weights": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(mvs_dct_opts_t),
+                                          C.c_void_p, C.c_void_p, C.c_int32]),
     "mvs_mv_deconv": (
         C.c_int,
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),

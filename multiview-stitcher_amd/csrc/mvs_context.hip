@@ -376,6 +376,10 @@ int mvs_set_option(int device, const char* key, int64_t value) {
         c->deconv_general = value != 0;
         return MVS_OK;
     }
+    if (!strcmp(key, "dct_general")) {
+        c->dct_general = value != 0;
+        return MVS_OK;
+    }
     if (!strcmp(key, "rows_v1")) {
         c->rows_v1 = value != 0;
         return MVS_OK;

@@ -1,0 +1,556 @@
+// mvs_dct_weights.hip -- DCT Shannon-entropy fusion weights (weights.content_based_dct, weights.py:77-290 of the
+// reference; Royer et al. 2016).
+//
+// Per view and block of the chunk (blocks of the clamped dct sizes, anchored at chunk index 0, smaller at the far edges):
+//   valid   fewer than 0.2 * size non-NaN voxels -> quality 0 (:212-214)
+//   fill    NaN voxels <- nanmin(block) if that is > 1e-4, else 0 (:216-219)
+//   DCT     orthonormal DCT-II along every axis (scipy.fftpack.dctn(norm="ortho"), any length) (:221)
+//   quality OTF branch: l2 = |d|_2, p = |d[sum(k) < r_o]| / l2, q = sign * ((2 / r_o^2) H) ** exponent (:223-240)
+//           L1 branch:  dsl1 = mean |d|, p = |d| / dsl1, q = (dsl1 H) ** exponent (:242-251),  H = -sum p log2 p (p > 0)
+// then Q -= nanmin over the views, normalize_weights (:253-255), and per voxel the trilinear clamped lookup into Q_v
+// (affine_transform(order=1, mode="nearest"), :260-281) -- normalised again for the standalone weights, or multiplied
+// into the weighted average of mvs_fuse.hip for the fused chunk (the voxel-level normalisations cancel there).
+//
+// Two quality paths, one workgroup per (view, block) work item:
+//   LDS     every block extent <= 32: the block (x rows padded to an odd pitch) sits in LDS (<= 132 KiB), each thread
+//           transforms whole lines in registers against a zero-padded 32 x 32 coefficient table read with uniform
+//           (scalar) loads
+//   general any extent: two ping-pong buffers and the coefficient tables in a bounded global scratch area, one slot
+//           per resident workgroup, the work items striding over the slots
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "mvs_internal.h"
+#include "mvs_fuse_dev.h"
+#include "mvs_dct_dev.h"
+
+namespace {
+
+constexpr int kLdsMax = 32;               // largest block extent per axis of the LDS path
+constexpr int kLdsThreads = 1024;
+constexpr int kGenThreads = 256;
+constexpr size_t kGenBudget = (size_t)256 << 20;   // bytes of global scratch of the general path
+
+struct DctGeom {
+    int S[3];          // chunk shape (z, y, x)
+    int ds[3];         // clamped block sizes (2D: ds[0] == 1)
+    int nb[3];         // blocks per axis
+    int nblocks;
+    int otf;           // 1: OTF branch (r_o), 0: L1 branch
+    double r_o;
+    double exponent;
+};
+
+// orthonormal DCT-II coefficient: s_k cos(pi k (2n + 1) / (2L)), the argument reduced exactly modulo 2 pi
+__device__ __forceinline__ float dct_coef(int L, int k, int n) {
+    const long long m = ((long long)(2 * n + 1) * k) % (4LL * L);
+    const double s = k == 0 ? sqrt(1.0 / L) : sqrt(2.0 / L);
+    return (float)(s * cospi((double)m / (2.0 * L)));
+}
+
+// tables of the LDS path: T[L - 1][k][n] for L = 1..32, zero outside k, n < L
+__global__ void dct_table_kernel(float* __restrict__ T) {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < kLdsMax * kLdsMax * kLdsMax; i += gridDim.x * blockDim.x) {
+        const int n = i % kLdsMax, k = (i / kLdsMax) % kLdsMax, L = i / (kLdsMax * kLdsMax) + 1;
+        T[i] = (k < L && n < L) ? dct_coef(L, k, n) : 0.f;
+    }
+}
+
+struct Blk {
+    int o[3], e[3];    // origin in the chunk, extent
+    int px;            // x pitch of the block buffer
+    int vol;
+};
+
+__device__ __forceinline__ void block_of(const DctGeom& g, int b, bool pad, Blk& k) {
+    const int bx = b % g.nb[2], t = b / g.nb[2], by = t % g.nb[1], bz = t / g.nb[1];
+    const int bi[3] = {bz, by, bx};
+    for (int d = 0; d < 3; ++d) {
+        k.o[d] = bi[d] * g.ds[d];
+        k.e[d] = min(g.ds[d], g.S[d] - k.o[d]);
+    }
+    k.px = pad ? (k.e[2] | 1) : k.e[2];
+    k.vol = k.e[0] * k.e[1] * k.e[2];
+}
+
+template <int NT>
+__device__ __forceinline__ double wg_sum(double v, double* red) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double r = 0.0;
+    for (int i = 0; i < NT / 64; ++i) r += red[i];
+    return r;
+}
+
+template <int NT>
+__device__ __forceinline__ float wg_min(float v, float* red) {
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_down(v, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float r = INFINITY;
+    for (int i = 0; i < NT / 64; ++i) r = fminf(r, red[i]);
+    return r;
+}
+
+__device__ __forceinline__ int buf_index(const Blk& k, int z, int y, int x) { return (z * k.e[1] + y) * k.px + x; }
+
+// copy the block of one view into `buf`, count its valid voxels and fill the NaN ones; false: quality 0 (too few valid)
+template <int NT>
+__device__ bool load_block(const float* __restrict__ src, const DctGeom& g, const Blk& k, float* buf, double* redd, float* redf) {
+    double cnt = 0.0;
+    float mn = INFINITY;
+    for (int i = threadIdx.x; i < k.vol; i += NT) {
+        const int x = i % k.e[2], r = i / k.e[2], y = r % k.e[1], z = r / k.e[1];
+        const float v = src[((long long)(k.o[0] + z) * g.S[1] + (k.o[1] + y)) * g.S[2] + k.o[2] + x];
+        buf[buf_index(k, z, y, x)] = v;
+        if (v == v) {
+            cnt += 1.0;
+            mn = fminf(mn, v);
+        }
+    }
+    const double n_valid = wg_sum<NT>(cnt, redd);
+    if (n_valid < 0.2 * (double)k.vol) return false;
+    if (n_valid < (double)k.vol) {
+        const float m = wg_min<NT>(mn, redf);
+        const float fill = (double)m > 0.0001 ? m : 0.f;
+        for (int i = threadIdx.x; i < k.vol; i += NT) {
+            const int x = i % k.e[2], r = i / k.e[2], y = r % k.e[1], z = r / k.e[1];
+            float& v = buf[buf_index(k, z, y, x)];
+            if (v != v) v = fill;
+        }
+    }
+    __syncthreads();
+    return true;
+}
+
+// line `l` of the pass along `axis`: first element and stride in the block buffer
+__device__ __forceinline__ void line_of(const Blk& k, int axis, int l, int& base, int& stride) {
+    if (axis == 2) {
+        base = l * k.px;               // l = z * e1 + y
+        stride = 1;
+    } else if (axis == 1) {
+        const int z = l / k.e[2], x = l % k.e[2];
+        base = z * k.e[1] * k.px + x;
+        stride = k.px;
+    } else {
+        const int y = l / k.e[2], x = l % k.e[2];
+        base = y * k.px + x;
+        stride = k.e[1] * k.px;
+    }
+}
+
+// entropy quality of the transformed block (weights.py:223-251)
+template <int NT>
+__device__ float block_quality(const float* buf, const DctGeom& g, const Blk& k, double* redd) {
+    if (g.otf) {
+        double ss = 0.0;
+        for (int i = threadIdx.x; i < k.vol; i += NT) {
+            const int x = i % k.e[2], r = i / k.e[2], y = r % k.e[1], z = r / k.e[1];
+            const double d = buf[buf_index(k, z, y, x)];
+            ss += d * d;
+        }
+        const float l2 = (float)sqrt(wg_sum<NT>(ss, redd));
+        if (l2 == 0.f) return 0.f;
+        double h = 0.0;
+        for (int i = threadIdx.x; i < k.vol; i += NT) {
+            const int x = i % k.e[2], r = i / k.e[2], y = r % k.e[1], z = r / k.e[1];
+            if (!((double)(x + y + z) < g.r_o)) continue;
+            const float p = fabsf(buf[buf_index(k, z, y, x)]) / l2;
+            if (p > 0.f) h -= (double)(p * log2f(p));
+        }
+        h = wg_sum<NT>(h, redd);
+        float q = (float)((2.0 / (g.r_o * g.r_o)) * h);
+        const float sg = q > 0.f ? 1.f : (q < 0.f ? -1.f : q);      // np.sign (0 -> 0, NaN -> NaN)
+        q = powf(q, (float)g.exponent);
+        return q * sg;
+    }
+    double sa = 0.0;
+    for (int i = threadIdx.x; i < k.vol; i += NT) {
+        const int x = i % k.e[2], r = i / k.e[2], y = r % k.e[1], z = r / k.e[1];
+        sa += fabs((double)buf[buf_index(k, z, y, x)]);
+    }
+    const float dsl1 = (float)(wg_sum<NT>(sa, redd) / (double)k.vol);
+    if (dsl1 == 0.f) return 0.f;
+    double h = 0.0;
+    for (int i = threadIdx.x; i < k.vol; i += NT) {
+        const int x = i % k.e[2], r = i / k.e[2], y = r % k.e[1], z = r / k.e[1];
+        const float p = fabsf(buf[buf_index(k, z, y, x)]) / dsl1;
+        if (p > 0.f) h -= (double)(p * log2f(p));
+    }
+    h = wg_sum<NT>(h, redd);
+    return (float)pow((double)dsl1 * h, g.exponent);      // a negative base with a fractional exponent: NaN
+}
+
+// LDS path: one workgroup per (view, block); `stack` [view][S], Q [view][nblocks]
+__global__ __launch_bounds__(kLdsThreads) void dct_quality_lds(const float* __restrict__ stack, DctGeom g, const float* __restrict__ tabs,
+                                                               float* __restrict__ Q) {
+    extern __shared__ float4 lds4[];
+    float* buf = reinterpret_cast<float*>(lds4);
+    __shared__ double redd[kLdsThreads / 64];
+    __shared__ float redf[kLdsThreads / 64];
+    const int v = blockIdx.x / g.nblocks, b = blockIdx.x % g.nblocks;
+    Blk k;
+    block_of(g, b, true, k);
+    const long long S = (long long)g.S[0] * g.S[1] * g.S[2];
+    if (!load_block<kLdsThreads>(stack + v * S, g, k, buf, redd, redf)) {
+        if (threadIdx.x == 0) Q[blockIdx.x] = 0.f;
+        return;
+    }
+    for (int axis = 2; axis >= 0; --axis) {
+        const int len = k.e[axis];
+        if (len == 1) continue;          // the length-1 orthonormal DCT is the identity
+        const int nl = k.vol / len;
+        const float* T = tabs + (len - 1) * (kLdsMax * kLdsMax);
+        for (int l = threadIdx.x; l < nl; l += kLdsThreads) {
+            int base, stride;
+            line_of(k, axis, l, base, stride);
+            float xv[kLdsMax];
+#pragma unroll
+            for (int n = 0; n < kLdsMax; ++n) xv[n] = n < len ? buf[base + n * stride] : 0.f;
+            for (int kk = 0; kk < len; ++kk) {
+                const float* t = T + kk * kLdsMax;
+                float acc = 0.f;
+#pragma unroll
+                for (int n = 0; n < kLdsMax; ++n) acc = fmaf(t[n], xv[n], acc);
+                buf[base + kk * stride] = acc;
+            }
+        }
+        __syncthreads();
+    }
+    const float q = block_quality<kLdsThreads>(buf, g, k, redd);
+    if (threadIdx.x == 0) Q[blockIdx.x] = q;
+}
+
+// general path: workgroup w owns scratch slot w (two block buffers + the tables of the block's three lengths) and takes
+// the work items w, w + gridDim.x, ...
+__global__ __launch_bounds__(kGenThreads) void dct_quality_general(const float* __restrict__ stack, DctGeom g, float* __restrict__ scratch,
+                                                                   long long slot_floats, int n_items, float* __restrict__ Q) {
+    __shared__ double redd[kGenThreads / 64];
+    __shared__ float redf[kGenThreads / 64];
+    const long long bvol = (long long)g.ds[0] * g.ds[1] * g.ds[2];
+    float* bufA = scratch + (long long)blockIdx.x * slot_floats;
+    float* bufB = bufA + bvol;
+    float* tab = bufB + bvol;
+    const long long S = (long long)g.S[0] * g.S[1] * g.S[2];
+    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const int v = item / g.nblocks, b = item % g.nblocks;
+        Blk k;
+        block_of(g, b, false, k);
+        __syncthreads();                 // (the previous item's readers of the slot are done)
+        if (!load_block<kGenThreads>(stack + v * S, g, k, bufA, redd, redf)) {
+            if (threadIdx.x == 0) Q[item] = 0.f;
+            continue;
+        }
+        const int toff[3] = {0, k.e[0] * k.e[0], k.e[0] * k.e[0] + k.e[1] * k.e[1]};
+        for (int axis = 0; axis < 3; ++axis) {
+            const int L = k.e[axis];
+            for (int i = threadIdx.x; i < L * L; i += kGenThreads) tab[toff[axis] + i] = dct_coef(L, i / L, i % L);
+        }
+        __syncthreads();
+        float* in = bufA;
+        float* out = bufB;
+        for (int axis = 2; axis >= 0; --axis) {
+            const int len = k.e[axis];
+            if (len == 1) continue;
+            const int nl = k.vol / len;
+            const float* T = tab + toff[axis];
+            for (long long it = threadIdx.x; it < (long long)nl * len; it += kGenThreads) {
+                const int kk = (int)(it % len), l = (int)(it / len);
+                int base, stride;
+                line_of(k, axis, l, base, stride);
+                const float* t = T + (long long)kk * len;
+                float acc = 0.f;
+                for (int n = 0; n < len; ++n) acc = fmaf(t[n], in[base + (long long)n * stride], acc);
+                out[base + (long long)kk * stride] = acc;
+            }
+            __syncthreads();
+            float* t = in;
+            in = out;
+            out = t;
+        }
+        const float q = block_quality<kGenThreads>(in, g, k, redd);
+        if (threadIdx.x == 0) Q[item] = q;
+    }
+}
+
+// Q -= nanmin over the views; normalize_weights over the views (nansum, 0 -> 1) (weights.py:253-255, 325-345)
+__global__ void dct_normalize_kernel(const float* __restrict__ Q, int n_views, int nblocks, float* __restrict__ Qn) {
+    for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < nblocks; b += gridDim.x * blockDim.x) {
+        float m = NAN;
+        for (int v = 0; v < n_views; ++v) {
+            const float q = Q[(long long)v * nblocks + b];
+            if (q == q) m = (m == m) ? fminf(m, q) : q;
+        }
+        float sum = 0.f;
+        for (int v = 0; v < n_views; ++v) {
+            const float s = Q[(long long)v * nblocks + b] - m;
+            Qn[(long long)v * nblocks + b] = s;
+            if (s == s) sum += s;
+        }
+        if (sum == 0.f) sum = 1.f;
+        for (int v = 0; v < n_views; ++v) Qn[(long long)v * nblocks + b] = Qn[(long long)v * nblocks + b] / sum;
+    }
+}
+
+// per voxel: every view's lookup into its normalised grid, then normalize_weights over the views (weights.py:270-283)
+__global__ void dct_interp_kernel(DctLookup L, int n_views, int sz, int sy, int sx, float* __restrict__ W) {
+    const long long S = (long long)sz * sy * sx;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < S; i += (long long)gridDim.x * blockDim.x) {
+        const int x = (int)(i % sx), y = (int)((i / sx) % sy), z = (int)(i / ((long long)sx * sy));
+        float sum = 0.f;
+        for (int v = 0; v < n_views; ++v) {
+            const float w = dct_lookup(L, v, (double)z, (double)y, (double)x);
+            W[v * S + i] = w;
+            if (w == w) sum += w;
+        }
+        if (sum == 0.f) sum = 1.f;
+        for (int v = 0; v < n_views; ++v) W[v * S + i] = W[v * S + i] / sum;
+    }
+}
+
+int grid_for(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 256 * 32)); }
+size_t align_up(size_t v) { return (v + 255) / 256 * 256; }
+
+// clamped block sizes, grid and branch of weights.py:165-203
+int dct_geometry(MvsContext* c, const char* who, const int64_t shape[3], int ndim, const mvs_dct_opts_t* o, DctGeom* g) {
+    int min_ds = 0x7fffffff;
+    for (int a = 0; a < 3; ++a) {
+        g->S[a] = (int)shape[a];
+        if (a < 3 - ndim) {
+            g->ds[a] = 1;
+            g->nb[a] = 1;
+            continue;
+        }
+        long long ds = o->dct_size[a];
+        if (ds < 1) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: dct_size on axis %d must be >= 1", who, a);
+        if (o->has_output_chunksize) {
+            if (o->output_chunksize[a] < 1) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: output_chunksize on axis %d must be >= 1", who, a);
+            ds = std::min<long long>(ds, o->output_chunksize[a]);
+        }
+        ds = std::min<long long>(ds, shape[a]);
+        g->ds[a] = (int)ds;
+        g->nb[a] = (int)std::max<long long>(1, (shape[a] + ds - 1) / ds);
+        min_ds = std::min(min_ds, (int)ds);
+    }
+    g->nblocks = g->nb[0] * g->nb[1] * g->nb[2];
+    g->otf = o->has_otf ? 1 : 0;
+    g->r_o = o->has_otf ? o->otf_support_fraction * (double)min_ds : 0.0;
+    g->exponent = o->exponent;
+    return MVS_OK;
+}
+
+// device bytes of the quality pass beyond the stack and the two grids
+size_t quality_scratch_bytes(const MvsContext* c, const DctGeom& g, int n_views, bool* lds, int* slots, long long* slot_floats) {
+    *lds = !c->dct_general && g.ds[0] <= kLdsMax && g.ds[1] <= kLdsMax && g.ds[2] <= kLdsMax;
+    if (*lds) return (size_t)kLdsMax * kLdsMax * kLdsMax * 4;
+    const long long bvol = (long long)g.ds[0] * g.ds[1] * g.ds[2];
+    *slot_floats = 2 * bvol + (long long)g.ds[0] * g.ds[0] + (long long)g.ds[1] * g.ds[1] + (long long)g.ds[2] * g.ds[2];
+    const long long items = (long long)n_views * g.nblocks;
+    long long n = (long long)(kGenBudget / ((size_t)*slot_floats * 4));
+    n = std::max<long long>(1, std::min<long long>({n, items, 4096}));
+    *slots = (int)n;
+    return (size_t)n * (size_t)*slot_floats * 4;
+}
+
+// quality + normalisation of the grids (stream-ordered, nothing waited for)
+int run_quality(MvsContext* c, const DctGeom& g, int n_views, const float* stack, float* Q, float* Qn, void* qscratch, bool lds, int slots,
+                long long slot_floats) {
+    const long long items = (long long)n_views * g.nblocks;
+    if (lds) {
+        const size_t lds_bytes = (size_t)g.ds[0] * g.ds[1] * (g.ds[2] | 1) * 4;
+        MVS_HIP_TRY(c, hipFuncSetAttribute((const void*)dct_quality_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        hipLaunchKernelGGL(dct_table_kernel, dim3(32), dim3(256), 0, c->stream, (float*)qscratch);
+        hipLaunchKernelGGL(dct_quality_lds, dim3((unsigned)items), dim3(kLdsThreads), lds_bytes, c->stream, stack, g, (const float*)qscratch, Q);
+    } else {
+        hipLaunchKernelGGL(dct_quality_general, dim3(slots), dim3(kGenThreads), 0, c->stream, stack, g, (float*)qscratch, slot_floats, (int)items, Q);
+    }
+    MVS_HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(dct_normalize_kernel, dim3(grid_for(g.nblocks)), dim3(256), 0, c->stream, (const float*)Q, n_views, g.nblocks, Qn);
+    MVS_HIP_TRY(c, hipGetLastError());
+    return MVS_OK;
+}
+
+DctLookup lookup_of(const DctGeom& g, const float* Qn) {
+    DctLookup L{};
+    L.q = Qn;
+    L.nblocks = g.nblocks;
+    for (int d = 0; d < 3; ++d) {
+        L.nb[d] = g.nb[d];
+        L.scale[d] = 1.0 / (double)g.ds[d];
+        L.offset[d] = -((double)g.ds[d] - 1.0) / (2.0 * (double)g.ds[d]);
+    }
+    return L;
+}
+
+}  // namespace
+
+extern "C" int mvs_content_dct_weights(int device, const float* views, int32_t n_views, const int64_t shape[3], int32_t ndim,
+                                       const mvs_dct_opts_t* opts, float* weights_out, float* quality_out, int32_t mem) {
+    MvsContext* c0 = mvs_ctx(device);
+    if (!views || !shape || !opts || !weights_out) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_content_dct_weights: NULL argument");
+    if (n_views < 1) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_content_dct_weights: n_views must be >= 1");
+    if (ndim != 2 && ndim != 3) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_content_dct_weights: ndim must be 2 or 3");
+    if (mem != MVS_MEM_HOST && mem != MVS_MEM_DEVICE) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_content_dct_weights: bad mem");
+    for (int k = 0; k < 3; ++k)
+        if (shape[k] < 1 || shape[k] > 0x7fffffffLL) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_content_dct_weights: bad shape on axis %d", k);
+    if (ndim == 2 && shape[0] != 1) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_content_dct_weights: 2D data has shape[0] == 1");
+    const long long S = (long long)shape[0] * shape[1] * shape[2];
+    if (S * n_views > (1LL << 40) || S > 0x7fffffffLL) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_content_dct_weights: too large");
+
+    MvsContext* c;
+    int rc = mvs_check_ready(device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
+    DctGeom g;
+    rc = dct_geometry(c, "mvs_content_dct_weights", shape, ndim, opts, &g);
+    if (rc) return rc;
+    bool lds = false;
+    int slots = 0;
+    long long slot_floats = 0;
+    const size_t qs_bytes = quality_scratch_bytes(c, g, n_views, &lds, &slots, &slot_floats);
+    const size_t vol_bytes = (size_t)S * n_views * 4, grid_bytes = align_up((size_t)g.nblocks * n_views * 4);
+    const bool host = mem == MVS_MEM_HOST;
+    // work area: [stack | weights] (host data only) | Q | Qn | quality scratch
+    const size_t off_st = 0, off_w = off_st + (host ? align_up(vol_bytes) : 0), off_q = off_w + (host ? align_up(vol_bytes) : 0);
+    const size_t off_qn = off_q + grid_bytes, off_s = off_qn + grid_bytes, total = off_s + qs_bytes;
+    void* work = nullptr;
+    rc = mvs_malloc(device, total, &work);
+    if (rc) return rc;
+    char* W = (char*)work;
+    const float* stack = host ? (const float*)(W + off_st) : views;
+    float* dw = host ? (float*)(W + off_w) : weights_out;
+    float* Q = (float*)(W + off_q);
+    float* Qn = (float*)(W + off_qn);
+    auto fail = [&](int code) {
+        hipStreamSynchronize(c->stream);
+        mvs_free(device, work);
+        return code;
+    };
+#define DCT_TRY(expr)                                                                                                    \
+    do {                                                                                                                 \
+        hipError_t _e = (expr);                                                                                          \
+        if (_e != hipSuccess) {                                                                                          \
+            (void)hipGetLastError();                                                                                     \
+            mvs_fail(c, _e == hipErrorOutOfMemory ? MVS_ERR_OUT_OF_MEMORY : MVS_ERR_HIP, "%s failed: %s (%s:%d)", #expr,  \
+                     hipGetErrorString(_e), __FILE__, __LINE__);                                                         \
+            return fail(c->last_code);                                                                                   \
+        }                                                                                                                \
+    } while (0)
+    if (host) DCT_TRY(hipMemcpyAsync((void*)stack, views, vol_bytes, hipMemcpyHostToDevice, c->stream));
+    DCT_TRY(hipEventRecord(c->ev_start, c->stream));
+    rc = run_quality(c, g, n_views, stack, Q, Qn, W + off_s, lds, slots, slot_floats);
+    if (rc) return fail(rc);
+    hipLaunchKernelGGL(dct_interp_kernel, dim3(grid_for(S)), dim3(256), 0, c->stream, lookup_of(g, Qn), (int)n_views, g.S[0], g.S[1], g.S[2], dw);
+    DCT_TRY(hipGetLastError());
+    DCT_TRY(hipEventRecord(c->ev_stop, c->stream));
+    c->timing_valid = true;
+    const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (host) DCT_TRY(hipMemcpyAsync(weights_out, dw, vol_bytes, back, c->stream));
+    if (quality_out) DCT_TRY(hipMemcpyAsync(quality_out, Q, (size_t)g.nblocks * n_views * 4, back, c->stream));
+    if (host) DCT_TRY(hipStreamSynchronize(c->stream));
+#undef DCT_TRY
+    return mvs_free(device, work);
+}
+
+extern "C" int mvs_fuse_chunk_dct(int device, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts,
+                                  const mvs_dct_opts_t* dopts, void* out) {
+    MvsContext* c0 = mvs_ctx(device);
+    if (!views || n_views < 1 || !opts || !dopts || !out) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: NULL/empty argument");
+    if (opts->ndim != 2 && opts->ndim != 3) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: ndim must be 2 or 3");
+    if (opts->order != 0 && opts->order != 1) return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_fuse_chunk_dct: interpolation order %d (only 0|1)", opts->order);
+    if (opts->fusion != MVS_FUSE_WEIGHTED_AVERAGE || opts->weights != MVS_WEIGHTS_NONE)
+        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: needs fusion weighted_average and weights none");
+    for (int k = 0; k < 3; ++k) {
+        if (opts->out_shape[k] < 1 || opts->out_shape[k] > 0x7fffffffLL || opts->trim[k] < 0 || opts->out_shape[k] - 2 * opts->trim[k] < 1)
+            return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: bad out_shape/trim on axis %d", k);
+        if (opts->index_origin[k] != 0) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: index_origin must be 0");
+    }
+    if (opts->ndim == 2 && opts->out_shape[0] != 1) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: 2D chunks need out_shape[0] == 1");
+    const long long S = (long long)opts->out_shape[0] * opts->out_shape[1] * opts->out_shape[2];
+    if (S * n_views > (1LL << 40) || S > 0x7fffffffLL) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: chunk too large");
+    for (int i = 0; i < n_views; ++i) {
+        if (!mvs_dtype_size(views[i].dtype) || views[i].dtype != views[0].dtype)
+            return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: views must share one valid dtype");
+        if (views[i].index_offset[0] || views[i].index_offset[1] || views[i].index_offset[2])
+            return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: index_offset must be 0");
+        if (views[i].mem == MVS_MEM_HOST &&
+            (views[i].stride[2] != 1 || views[i].stride[1] != views[i].shape[2] || views[i].stride[0] != views[i].shape[1] * views[i].shape[2]))
+            return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_fuse_chunk_dct: host slabs must be C-contiguous");
+    }
+
+    MvsContext* c;
+    int rc = mvs_check_ready(device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
+    DctGeom g;
+    rc = dct_geometry(c, "mvs_fuse_chunk_dct", opts->out_shape, opts->ndim, dopts, &g);
+    if (rc) return rc;
+    bool lds = false;
+    int slots = 0;
+    long long slot_floats = 0;
+    const size_t qs_bytes = quality_scratch_bytes(c, g, n_views, &lds, &slots, &slot_floats);
+    const size_t es = mvs_dtype_size(views[0].dtype);
+    size_t host_bytes = 0;
+    for (int i = 0; i < n_views; ++i)
+        if (views[i].mem == MVS_MEM_HOST) host_bytes += align_up((size_t)views[i].shape[0] * views[i].shape[1] * views[i].shape[2] * es);
+    // work area: host slabs | resampled stack | Q | Qn | quality scratch
+    const size_t grid_bytes = align_up((size_t)g.nblocks * n_views * 4);
+    const size_t off_st = host_bytes, off_q = off_st + align_up((size_t)S * n_views * 4), off_qn = off_q + grid_bytes, off_s = off_qn + grid_bytes;
+    void* work = nullptr;
+    rc = mvs_malloc(device, off_s + qs_bytes, &work);
+    if (rc) return rc;
+    char* W = (char*)work;
+    float* stack = (float*)(W + off_st);
+    float* Q = (float*)(W + off_q);
+    float* Qn = (float*)(W + off_qn);
+    auto fail = [&](int code) {
+        hipStreamSynchronize(c->stream);
+        mvs_free(device, work);
+        return code;
+    };
+#define DCT_TRY(expr)                                                                                                    \
+    do {                                                                                                                 \
+        hipError_t _e = (expr);                                                                                          \
+        if (_e != hipSuccess) {                                                                                          \
+            (void)hipGetLastError();                                                                                     \
+            mvs_fail(c, _e == hipErrorOutOfMemory ? MVS_ERR_OUT_OF_MEMORY : MVS_ERR_HIP, "%s failed: %s (%s:%d)", #expr,  \
+                     hipGetErrorString(_e), __FILE__, __LINE__);                                                         \
+            return fail(c->last_code);                                                                                   \
+        }                                                                                                                \
+    } while (0)
+    // host slabs are staged once; the fuse launch reads the same device copies
+    std::vector<mvs_view_t> dv(views, views + n_views);
+    size_t cursor = 0;
+    for (int i = 0; i < n_views; ++i)
+        if (views[i].mem == MVS_MEM_HOST) {
+            const size_t nb = (size_t)views[i].shape[0] * views[i].shape[1] * views[i].shape[2] * es;
+            DCT_TRY(hipMemcpyAsync(W + cursor, views[i].data, nb, hipMemcpyHostToDevice, c->stream));
+            dv[i].data = W + cursor;
+            dv[i].mem = MVS_MEM_DEVICE;
+            cursor += align_up(nb);
+        }
+    DCT_TRY(hipEventRecord(c->ev_start, c->stream));
+    // transformed_views (_core.py:1622-1633): the views resampled onto the whole chunk, NaN outside
+    for (int i = 0; i < n_views; ++i) {
+        DevView d;
+        rc = mvs_fill_dev_view(c, dv[i], opts->ndim, dv[i].data, &d);
+        if (rc) return fail(rc);
+        mvs_launch_resample(c, d, dv[i].dtype, opts->order, NAN, stack + (long long)i * S, opts->out_shape);
+        DCT_TRY(hipGetLastError());
+    }
+    rc = run_quality(c, g, n_views, stack, Q, Qn, W + off_s, lds, slots, slot_floats);
+    if (rc) return fail(rc);
+    const DctLookup L = lookup_of(g, Qn);
+    rc = mvs_fuse_chunk_impl(device, dv.data(), n_views, opts, out, &L, true);
+    if (rc) return fail(rc);
+    if (opts->out_mem != MVS_MEM_HOST && host_bytes) DCT_TRY(hipStreamSynchronize(c->stream));   // (the caller may free its slabs)
+#undef DCT_TRY
+    return mvs_free(device, work);
+}

@@ -23,6 +23,7 @@
 // NI_GeometricTransform does; interpolation and accumulation are float32.
 #include "mvs_internal.h"
 #include "mvs_fuse_dev.h"
+#include "mvs_dct_dev.h"
 #include "mvs_fuse_tr.h"
 
 #include <cmath>
@@ -45,6 +46,7 @@ struct FuseParams {
     int bz, by;            // brick extent along z and y
     const int* cull;       // fast path: [6][nviews] valid chunk-index boxes (zlo,zhi,ylo,yhi,xlo,xhi)
     int ablate;            // profiling only: 1 skip weights, 2 skip loads, 4 skip epilogue math, 8 skip accumulate
+    DctLookup dct;         // DCT-entropy quality grids (fuse_kernel<..., DCT = true> only)
 };
 
 template <typename T> __device__ __forceinline__ float load_as_float(const T* p, long long i);
@@ -190,7 +192,9 @@ __device__ __forceinline__ bool brick_hits_view(const DevView& V, const int lo[3
 template <typename TOut>
 __device__ __forceinline__ void store_row4(TOut* out, long long row, int x0, int ox, const float r[4]);
 
-template <typename TIn, typename TOut, int ORDER, int FUSION>
+// DCT: the weighted average's weight of every view is multiplied by its lookup into the normalised DCT-entropy quality
+// grid (mvs_fuse_chunk_dct; a NaN factor drops the view like the reference's nansum does)
+template <typename TIn, typename TOut, int ORDER, int FUSION, bool DCT = false>
 __global__ __launch_bounds__(256) void fuse_kernel(FuseParams P) {
     __shared__ int s_act[64];
     __shared__ int s_nact;
@@ -287,6 +291,11 @@ __global__ __launch_bounds__(256) void fuse_kernel(FuseParams P) {
                     float w;
                     if (a < kLdsTables) w = blend_weight<true>(s_edt[a], V.wnz, cwz, cwy, cwx);
                     else w = blend_weight<false>(V.edt, V.wnz, cwz, cwy, cwx);
+                    if (DCT) {
+                        const float f = dct_lookup(P.dct, vi, pz, py, px0 + dj);
+                        if (f != f) continue;
+                        w *= f;
+                    }
                     wa_update(acc[j], den[j], w, val);
                 } else if (FUSION == MVS_FUSE_MAX) {
                     acc[j] = fmaxf(acc[j], val);
@@ -1291,7 +1300,10 @@ int fill_dev_view(MvsContext* c, const mvs_view_t& v, int ndim, const void* dev_
 template <typename TIn, typename TOut>
 void launch_fuse(const FuseParams& P, int order, int fusion, int nblocks, hipStream_t s) {
 #define MVS_LAUNCH(O, F) hipLaunchKernelGGL((fuse_kernel<TIn, TOut, O, F>), dim3(nblocks), dim3(256), 0, s, P)
-    if (order == 0) {
+    if (P.dct.q) {     // (weighted average only, checked by the caller)
+        if (order == 0) hipLaunchKernelGGL((fuse_kernel<TIn, TOut, 0, MVS_FUSE_WEIGHTED_AVERAGE, true>), dim3(nblocks), dim3(256), 0, s, P);
+        else hipLaunchKernelGGL((fuse_kernel<TIn, TOut, 1, MVS_FUSE_WEIGHTED_AVERAGE, true>), dim3(nblocks), dim3(256), 0, s, P);
+    } else if (order == 0) {
         if (fusion == MVS_FUSE_WEIGHTED_AVERAGE) MVS_LAUNCH(0, MVS_FUSE_WEIGHTED_AVERAGE);
         else if (fusion == MVS_FUSE_MAX) MVS_LAUNCH(0, MVS_FUSE_MAX);
         else MVS_LAUNCH(0, MVS_FUSE_SIMPLE_AVERAGE);
@@ -1363,6 +1375,12 @@ int mvs_fuse_content_based(MvsContext* c, const mvs_view_t* views, int32_t n_vie
 
 extern "C" int mvs_fuse_chunk(int device, const mvs_view_t* views, int32_t n_views,
                               const mvs_fuse_opts_t* opts, void* out) {
+    return mvs_fuse_chunk_impl(device, views, n_views, opts, out, nullptr, false);
+}
+
+// `dct` (mvs_fuse_chunk_dct): weighted average without content-based weights, through the generic kernel only
+int mvs_fuse_chunk_impl(int device, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out,
+                        const DctLookup* dct, bool keep_start) {
     MvsContext* c;
     int rc = mvs_check_ready(device, &c);
     if (rc) return rc;
@@ -1399,6 +1417,8 @@ extern "C" int mvs_fuse_chunk(int device, const mvs_view_t* views, int32_t n_vie
     }
     if (opts->weights != MVS_WEIGHTS_NONE)
         return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk: unknown weights %d", opts->weights);
+    if (dct && opts->fusion != MVS_FUSE_WEIGHTED_AVERAGE)
+        return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk: DCT weights need weighted_average fusion");
 
     // stage host slabs into device scratch (slot 0)
     const size_t es = mvs_dtype_size(dtype);
@@ -1436,7 +1456,7 @@ extern "C" int mvs_fuse_chunk(int device, const mvs_view_t* views, int32_t n_vie
         prepare_translation_view(&hviews[i], opts->order, opts->fusion, opts->out_shape, es, opts->index_origin, views[i].index_offset);
         mvs_view_to_chunk_frame(&hviews[i], opts->index_origin, views[i].index_offset);
     }
-    bool use_tr = !c->force_generic;
+    bool use_tr = !c->force_generic && !dct;
     for (int i = 0; i < n_views && use_tr; ++i) use_tr = hviews[i].tr_ok != 0;
     // Float tiles with linear interpolation: scipy multiplies the second tap of every axis by its (possibly zero) weight,
     // so a NaN there poisons the sample.  Only the row kernels (weighted average) and the generic kernel read all taps;
@@ -1474,6 +1494,7 @@ extern "C" int mvs_fuse_chunk(int device, const mvs_view_t* views, int32_t n_vie
     P.tz = (int)opts->trim[0]; P.ty = (int)opts->trim[1]; P.tx = (int)opts->trim[2];
     P.cull = (const int*)((const char*)dviews + views_bytes);
     P.ablate = c->ablate;
+    P.dct = dct ? *dct : DctLookup{};
     long long nblocks = 0;
     auto set_brick_grid = [&](bool tr) {
         if (tr) {
@@ -1492,7 +1513,7 @@ extern "C" int mvs_fuse_chunk(int device, const mvs_view_t* views, int32_t n_vie
     set_brick_grid(use_tr);
     if (nblocks > 0x7fffffffLL) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "chunk too large for one launch");
 
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
+    if (!keep_start) MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     int* tr_overflow_ptr = nullptr;
     bool regions_done = false;
     if (!regions_done && use_tr && opts->fusion == MVS_FUSE_WEIGHTED_AVERAGE && (c->rows_v1 || (dtype == MVS_F32 && opts->order == 1))) {

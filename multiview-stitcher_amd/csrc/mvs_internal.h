@@ -94,6 +94,7 @@ struct MvsContext {
     bool fft_no_line = false;     // test switch: lengths of the whole-line DFT kernel run on the Bluestein kernels instead
     bool no_regions = false;      // test switch: skip the region kernel (use the column kernel)
     bool deconv_general = false;  // test switch "deconv_general": mvs_mv_deconv takes the general direct convolution even for separable kernels
+    bool dct_general = false;     // test switch "dct_general": the DCT quality pass takes its general (global scratch) path for every block size
     bool rows_v1 = false;         // opt-in: direct-load row kernels (mvs_fuse_rows.hip) for every dtype (default: float tiles only)
     // caching device allocator behind mvs_malloc / mvs_free: freed blocks are kept (size-keyed) and handed out
     // again, because hipMalloc / hipFree cost ~0.4 ms each and the registration path allocates per pair.

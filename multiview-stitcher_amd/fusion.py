@@ -24,6 +24,7 @@ import numpy as np
 
 from . import _lib, mv_deconv, mv_graph, param_utils, weights
 from .mv_deconv import PSFType, multi_view_deconvolution  # noqa: F401  (fusion.multi_view_deconvolution, fusion.PSFType)
+from .weights import content_based_dct  # noqa: F401  (fusion.content_based_dct)
 from . import spatial_image_utils as si_utils
 from .device import DeviceArray, is_device_array
 from .transformation import _as_zyx, embed3_stack, fill_view_geometry, get_pixel_affine, get_pixel_affines, shape3
@@ -73,6 +74,7 @@ BUILTIN = {
     "simple_average_fusion": simple_average_fusion,
     "content_based": content_based,
     "multi_view_deconvolution": multi_view_deconvolution,   # not a kernel mode: fuse_np's deconvolution branch
+    "content_based_dct": content_based_dct,                 # weights of fuse_np's mvs_fuse_chunk_dct branch
 }
 
 
@@ -196,7 +198,12 @@ def fuse_np(
         return _fuse_np_deconvolution(
             sims, params, out_bb, sdims, input_dtype, fusion_func_kwargs, trim_overlap_in_pixels, interpolation_order,
             full_view_bbs, spacings, blending_widths, shrink_distance, output_on_backend, out, device)
-    if fusion_func not in _FUSION_CODES or (weights_func is not None and weights_func is not content_based):
+    dct = weights_func is content_based_dct and fusion_func in _FUSION_CODES
+    if dct and _FUSION_CODES[fusion_func] != _lib.MVS_FUSE_WEIGHTED_AVERAGE:
+        dct, weights_func = False, None      # only a fusion_func with fusion_weights asks for them (_core.py:1665)
+    elif dct:
+        frame_origin, _record = None, None   # the DCT blocks are anchored at the chunk: per-chunk parameters as in the reference
+    if fusion_func not in _FUSION_CODES or (weights_func is not None and weights_func not in (content_based, content_based_dct)):
         # user callables (docs/extension_api_fusion.md): they run after the resample, so the chunk cannot be fused in one
         # kernel; the voxel work that is ours (resample, blending weights) still runs on the device
         return _fuse_np_with_callables(
@@ -204,7 +211,7 @@ def fuse_np(
             trim_overlap_in_pixels, interpolation_order, full_view_bbs, spacings, blending_widths, shrink_distance,
             output_on_backend, device)
     fusion_code = _fusion_code(fusion_func)
-    weights_code = _weights_code(weights_func)
+    weights_code = _weights_code(None if dct else weights_func)
 
     if spacings is None:
         spacings = [fvb["spacing"] for fvb in full_view_bbs] if full_view_bbs is not None else [None] * len(sims)
@@ -315,6 +322,21 @@ def fuse_np(
     opts.out_dtype = _lib.DTYPE_CODES[input_dtype]
     for k in range(3):
         opts.index_origin[k] = int(index_origin[k])
+    if dct:
+        # content_based_dct's arguments as the reference passes them (_core.py:1665-1682): output_chunksize defaults to the
+        # chunk's shape including the halo
+        dkw = dict(wk)
+        for k in ("transformed_views", "device"):
+            if k in dkw:
+                raise TypeError(f"weights_func_kwargs must not set {k!r}: fuse_np supplies it")
+        if dkw.get("output_chunksize") is None:
+            dkw["output_chunksize"] = dict(out_bb["shape"])
+        dopts = weights.dct_opts(ndim, **dkw)
+
+    def launch(dst):
+        if dct:
+            return lib.mvs_fuse_chunk_dct(device, views, n, C.byref(opts), C.byref(dopts), dst), "mvs_fuse_chunk_dct"
+        return lib.mvs_fuse_chunk(device, views, n, C.byref(opts), dst), "mvs_fuse_chunk"
 
     if out is not None or output_on_backend:
         if out is None:
@@ -322,8 +344,8 @@ def fuse_np(
         if tuple(out.shape) != tuple(res_shape) or not out.is_contiguous():
             raise ValueError("out must be a contiguous DeviceArray of the result shape")
         opts.out_mem = _lib.MVS_MEM_DEVICE
-        rc = lib.mvs_fuse_chunk(device, views, n, C.byref(opts), C.c_void_p(out.ptr))
-        _lib.check(rc, device, "mvs_fuse_chunk")
+        rc, what = launch(C.c_void_p(out.ptr))
+        _lib.check(rc, device, what)
         if weights_code and _cb_check and _cb_overflowed(device):
             # the fast content-based path lists the voxels its box-shaped mask lacks; a list that did not fit raised a flag
             # (a result left on the device is not waited for inside the call): this chunk again through the bit-faithful passes
@@ -337,8 +359,8 @@ def fuse_np(
         return out
     result = np.empty(tuple(res_shape), dtype=input_dtype)
     opts.out_mem = _lib.MVS_MEM_HOST
-    rc = lib.mvs_fuse_chunk(device, views, n, C.byref(opts), result.ctypes.data)
-    _lib.check(rc, device, "mvs_fuse_chunk")
+    rc, what = launch(result.ctypes.data)
+    _lib.check(rc, device, what)
     return result
 
 
@@ -835,6 +857,24 @@ def _replay_fuse(rec, images, transform_key, device):
     return res
 
 
+def _halo_overlap(overlap_in_pixels, sdims, funcs, output_chunksize):
+    """The halo of fuse() (_core.py:1194-1222): the requested overlap per dim, raised to every function's
+    ``required_overlap``; functions that accept ``output_chunksize`` get the requested chunk size among their kwargs."""
+    overlap_in_pixels = overlap_in_pixels or 0
+    if not isinstance(overlap_in_pixels, dict):
+        overlap_in_pixels = {d: overlap_in_pixels for d in sdims}
+    for func, kw in funcs:
+        if func is not None and hasattr(func, "required_overlap"):
+            kw = dict(kw or {})
+            if has_keyword(func, "output_chunksize") and output_chunksize is not None:
+                kw.setdefault("output_chunksize", output_chunksize)
+            cur = func.required_overlap(kw)
+            if not isinstance(cur, dict):
+                cur = {d: cur for d in sdims}
+            overlap_in_pixels = {d: max(overlap_in_pixels[d], cur[d]) for d in sdims}
+    return overlap_in_pixels
+
+
 def _fuse_once(
     images=None,
     transform_key=None,
@@ -973,17 +1013,9 @@ def _fuse_once(
     output_stack_properties["shape"] = {d: int(v) for d, v in output_stack_properties["shape"].items()}
     params = [si_utils.get_affine_from_sim(sim, transform_key) for sim in sims_]
 
-    # halo (_core.py:1194-1222)
-    overlap_in_pixels = overlap_in_pixels or 0
-    if not isinstance(overlap_in_pixels, dict):
-        overlap_in_pixels = {d: overlap_in_pixels for d in sdims}
+    overlap_in_pixels = _halo_overlap(overlap_in_pixels, sdims, [(weights_func, weights_func_kwargs), (fusion_func, fusion_func_kwargs)],
+                                      output_chunksize)
     shrink_distance = 0
-    for func, kw in [(weights_func, weights_func_kwargs), (fusion_func, fusion_func_kwargs)]:
-        if func is not None and hasattr(func, "required_overlap"):
-            cur = func.required_overlap(dict(kw or {}))
-            if not isinstance(cur, dict):
-                cur = {d: cur for d in sdims}
-            overlap_in_pixels = {d: max(overlap_in_pixels[d], cur[d]) for d in sdims}
 
     store_chunksize = dict(output_chunksize)          # the chunk grid of a Zarr output stays the requested one
     requested_chunksize = dict(output_chunksize)

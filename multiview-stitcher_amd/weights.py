@@ -137,3 +137,86 @@ def get_blending_weights(target_bb, source_bb, affine, blending_widths=None, shr
                                _lib.MVS_MEM_HOST)
     _lib.check(rc, device, "mvs_blend_weights")
     return out
+
+
+def _clamp_overlap(overlap, output_chunksize):
+    """weights._clamp_overlap (weights.py:514-524): the overlap per dim, at most the output chunk size."""
+    sdims = sorted(output_chunksize.keys())[::-1]
+    if not isinstance(overlap, dict):
+        overlap = {dim: int(overlap) for dim in sdims}
+    return {dim: min(overlap[dim], output_chunksize[dim]) for dim in sdims}
+
+
+def content_based_dct_required_overlap(kwargs):
+    """``@requires_overlap(lambda kwargs: _clamp_overlap(kwargs["dct_size"], kwargs["output_chunksize"]))`` of
+    weights.py:70-84, with the defaults merged in as misc_utils.requires_overlap does."""
+    kw = {"dct_size": 32, "output_chunksize": None, **(kwargs or {})}
+    return _clamp_overlap(kw["dct_size"], kw["output_chunksize"])
+
+
+def dct_opts(ndim, dct_size=32, exponent=1.0, otf_support_fraction=0.5, output_chunksize=None):
+    """The ``mvs_dct_opts_t`` of content_based_dct's keyword arguments (spatial dims z, y, x; 2D: y, x)."""
+    sdims = ["z", "y", "x"][-ndim:]
+    o = _lib.mvs_dct_opts_t()
+    sizes = [dct_size[d] for d in sdims] if isinstance(dct_size, dict) else [dct_size] * ndim
+    for k, v in enumerate([1] * (3 - ndim) + [int(s) for s in sizes]):
+        o.dct_size[k] = v
+    if output_chunksize is not None:
+        o.has_output_chunksize = 1
+        for k, v in enumerate([1] * (3 - ndim) + [int(output_chunksize[d]) for d in sdims]):
+            o.output_chunksize[k] = v
+    o.exponent = float(exponent)
+    if otf_support_fraction is not None:
+        o.has_otf = 1
+        o.otf_support_fraction = float(otf_support_fraction)
+    return o
+
+
+def content_based_dct(transformed_views, dct_size=32, exponent=1.0, otf_support_fraction=0.5, output_chunksize=None, device=0,
+                      return_quality=False):
+    """weights.content_based_dct (weights.py:77-290): DCT Shannon-entropy fusion weights on the device.
+
+    ``transformed_views`` (n_views, *spatial) as numpy or ``DeviceArray`` (NaN = outside a view); returns float32 weights of
+    the same shape and kind (``mvs_content_dct_weights``).  ``return_quality``: also the raw per-block qualities
+    (n_views, *blocks), before the shift by their minimum over the views.
+    """
+    from .device import DeviceArray, is_device_array
+
+    lib = _lib.init(device)
+    on_dev = is_device_array(transformed_views)
+    if on_dev:
+        views = transformed_views.on_device(device)
+        views.wait_ready(device)
+        if views.dtype != np.float32 or not views.is_contiguous():
+            views = DeviceArray.from_host(np.ascontiguousarray(views.get(), dtype=np.float32), device)
+    else:
+        views = np.ascontiguousarray(transformed_views, dtype=np.float32)
+    nv, spatial = int(views.shape[0]), tuple(int(s) for s in views.shape[1:])
+    ndim = len(spatial)
+    if ndim not in (2, 3):
+        raise ValueError("content_based_dct: transformed_views must be (n_views, y, x) or (n_views, z, y, x)")
+    opts = dct_opts(ndim, dct_size, exponent, otf_support_fraction, output_chunksize)
+    s3 = shape3(spatial)
+    sizes = [opts.dct_size[k] for k in range(3)]
+    if opts.has_output_chunksize:
+        sizes = [min(sizes[k], opts.output_chunksize[k]) for k in range(3)]
+    nblocks = tuple(max(1, -(-s3[k] // min(sizes[k], s3[k]))) for k in range(3 - ndim, 3))
+    if on_dev:
+        out = DeviceArray.empty((nv,) + spatial, np.float32, device)
+        q = DeviceArray.empty((nv,) + nblocks, np.float32, device) if return_quality else None
+        rc = lib.mvs_content_dct_weights(device, C.c_void_p(views.ptr), nv, _lib.i64x3(s3), ndim, C.byref(opts), C.c_void_p(out.ptr),
+                                         C.c_void_p(q.ptr) if q is not None else None, _lib.MVS_MEM_DEVICE)
+        _lib.check(rc, device, "mvs_content_dct_weights")
+        out.mark_written()
+        if q is not None:
+            q.mark_written()
+    else:
+        out = np.empty((nv,) + spatial, np.float32)
+        q = np.empty((nv,) + nblocks, np.float32) if return_quality else None
+        rc = lib.mvs_content_dct_weights(device, views.ctypes.data, nv, _lib.i64x3(s3), ndim, C.byref(opts), out.ctypes.data,
+                                         q.ctypes.data if q is not None else None, _lib.MVS_MEM_HOST)
+        _lib.check(rc, device, "mvs_content_dct_weights")
+    return (out, q) if return_quality else out
+
+
+content_based_dct.required_overlap = content_based_dct_required_overlap
