@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from .device import DeviceArray, is_device_array
-from .transformation import shape3
+from .transformation import shape3, view_data
 
 
 def _ptr_mem(a):
@@ -210,20 +210,16 @@ def bin_mean(data, bins, device=0, wait=True, out=None):
     dtype = np.dtype(data.dtype)
     if dtype not in _lib.DTYPE_CODES:
         raise TypeError(f"unsupported dtype {dtype}")
-    if is_device_array(data):
-        ptr, mem, strides = data.ptr, _lib.MVS_MEM_DEVICE, list(data.strides)
+    ptr, s3, st3, mem, data = view_data(data, device, wait=False)
+    if mem == _lib.MVS_MEM_DEVICE:
         if out is None:
             out = DeviceArray.empty(oshape, dtype, device)
         elif tuple(out.shape) != tuple(oshape) or out.dtype != dtype or not out.is_contiguous():
             raise ValueError("bin_mean: out must be a contiguous DeviceArray of the binned shape and the input dtype")
         optr, omem = out.ptr, _lib.MVS_MEM_DEVICE
     else:
-        data = np.ascontiguousarray(data)
-        ptr, mem, strides = data.ctypes.data, _lib.MVS_MEM_HOST, [int(np.prod(data.shape[k + 1:])) for k in range(nd)]
         out = np.empty(oshape, dtype=dtype)
         optr, omem = out.ctypes.data, _lib.MVS_MEM_HOST
-    s3 = shape3(shape)
-    st3 = strides if nd == 3 else [strides[0] * s3[1], strides[0], strides[1]]
     b3 = [1] * (3 - nd) + bins
     if not wait and mem == _lib.MVS_MEM_DEVICE:
         rc = lib.mvs_bin_mean_async(device, ptr, _lib.DTYPE_CODES[dtype], _lib.i64x3(s3), _lib.i64x3(st3), _lib.i64x3(b3), optr)

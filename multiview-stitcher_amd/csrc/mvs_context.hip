@@ -181,6 +181,79 @@ static void pool_flush(MvsContext* c) {
     c->pool_cached_bytes = 0;
 }
 
+// ---- options and counters that are one field of the context: mvs_set_option / mvs_get_counter (and the environment switches of
+// mvs_init) look the key up here; the kernels' launch code reads the fields themselves.  Whatever does more than set or read a
+// field is code in those two functions. ----
+struct MvsBoolOption { const char* key; bool MvsContext::* field; };
+static const MvsBoolOption kBoolOptions[] = {
+    {"force_generic", &MvsContext::force_generic},
+    {"no_regions", &MvsContext::no_regions},
+    {"deconv_general", &MvsContext::deconv_general},
+    {"dct_general", &MvsContext::dct_general},
+    {"rows_v1", &MvsContext::rows_v1},
+    {"cb_mask_count", &MvsContext::cb_mask_count},
+    {"cb_mask_closed_form", &MvsContext::cb_mask_closed_form},
+    {"fuse_mixed", &MvsContext::fuse_mixed},
+    {"serial_classes", &MvsContext::serial_classes},
+    {"reg_unfused", &MvsContext::reg_unfused},
+    {"ssim_two_pass", &MvsContext::ssim_two_pass},
+    {"ssim_f32", &MvsContext::ssim_f32},
+    {"ssim_prune", &MvsContext::ssim_prune},
+    {"materialize_shifts", &MvsContext::materialize_shifts},
+    {"cb_exact", &MvsContext::cb_exact},
+    {"cb_blend_generic", &MvsContext::cb_blend_generic},
+    {"cb_nosplit", &MvsContext::cb_nosplit},
+    {"cb_unpaired", &MvsContext::cb_unpaired},
+    {"fft_no_pair", &MvsContext::fft_no_pair},
+    {"fft_no_slab", &MvsContext::fft_no_slab},
+    {"fft_no_line", &MvsContext::fft_no_line},
+};
+// mvs_set_option under the context's lock; mvs_init applies the environment switches through it
+static int set_option(MvsContext* c, const char* key, int64_t value) {
+    for (const MvsBoolOption& e : kBoolOptions)
+        if (!strcmp(key, e.key)) {
+            c->*e.field = value != 0;
+            return MVS_OK;
+        }
+    if (!strcmp(key, "pool_cache_limit_mb")) {
+        std::lock_guard<std::mutex> plock(c->pool_mu);
+        c->pool_cache_limit = (size_t)std::max<int64_t>(value, 0) << 20;
+        if (c->pool_cached_bytes > c->pool_cache_limit) pool_flush(c);
+        return MVS_OK;
+    }
+    if (!strcmp(key, "cb_taps_f64")) {
+        if (value < 0 || value > 3) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_set_option: cb_taps_f64 is 0, 1, 2 or 3");
+        c->cb_taps = (int)value;
+        return MVS_OK;
+    }
+    if (!strcmp(key, "fft_slab_axes")) {
+        if (value < 0 || value > 7) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_set_option: fft_slab_axes is a mask of 3 bits");
+        c->fft_slab_axes = (int)value;
+        return MVS_OK;
+    }
+    if (!strcmp(key, "ablate")) {
+        c->ablate = (int)value;
+        return MVS_OK;
+    }
+    return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_set_option: unknown key '%s'", key);
+}
+// accumulating counters: a double (`real`) or an integer (`count`) of the context
+struct MvsCounter { const char* key; double MvsContext::* real; long long MvsContext::* count; };
+static const MvsCounter kCounters[] = {
+    {"reg_alg_bytes", &MvsContext::reg_alg_bytes, nullptr},
+    {"reg_alg_bytes_full", &MvsContext::reg_alg_bytes_full, nullptr},
+    {"reg_pairs", nullptr, &MvsContext::reg_pairs},
+    {"reg_candidates", nullptr, &MvsContext::reg_candidates},
+    {"reg_rewalks", nullptr, &MvsContext::reg_rewalks},
+    {"reg_pruned", nullptr, &MvsContext::reg_pruned},
+    {"reg_cand_volumes", &MvsContext::reg_cand_volumes, nullptr},
+    {"reg_slab_pairs", nullptr, &MvsContext::reg_slab_pairs},
+    {"cb_mask_views", nullptr, &MvsContext::cb_mask_views},
+    {"cb_mask_boxes", nullptr, &MvsContext::cb_mask_boxes},
+    {"cb_line_launches", nullptr, &MvsContext::cb_line_launches},
+    {"cb_overflows_redone", nullptr, &MvsContext::cb_overflows},
+};
+
 double mvs_rows_last_plan_ms(MvsContext* c);       // mvs_fuse_rows.hip
 double mvs_regions_last_plan_ms(MvsContext* c);    // mvs_fuse_region.hip
 double mvs_regions_class_stat(MvsContext* c, int what, int cls);   // mvs_fuse_region.hip
@@ -259,19 +332,18 @@ int mvs_init(int device) {
         if (hipMemGetInfo(&f, &t) == hipSuccess) c->pool_cache_limit = std::max(c->pool_cache_limit, t / 2);
         else (void)hipGetLastError();
     }
-    {   // A/B switch for all context lanes of a process (bench.py, tools/): MVS_SSIM_PRUNE=0 scores every candidate in full
-        const char* ev = getenv("MVS_SSIM_PRUNE");
-        if (ev && *ev) c->ssim_prune = atoi(ev) != 0;
-        ev = getenv("MVS_SSIM_F32");      // (the same for the float32 walk of the pruned search)
-        if (ev && *ev) c->ssim_f32 = atoi(ev) != 0;
-        ev = getenv("MVS_FUSE_MIXED");          // A/B switch of the one-launch fuse list (profiles/round5_fuse_mixed.txt)
-        if (ev && *ev) c->fuse_mixed = atoi(ev) != 0;
-        ev = getenv("MVS_FFT_SLAB_AXES");       // ... and of the crop orientations that take it (bit k = short axis k of (z, y, x))
-        if (ev && *ev && atoi(ev) >= 0 && atoi(ev) <= 7) c->fft_slab_axes = atoi(ev);
-        ev = getenv("MVS_FFT_NO_SLAB");         // A/B switch of the three-pass phase correlation (mvs_fft_slab.hip)
-        if (ev && *ev) c->fft_no_slab = atoi(ev) != 0;
-        ev = getenv("MVS_FFT_NO_PAIR");
-        if (ev && *ev) c->fft_no_pair = atoi(ev) != 0;
+    {   // A/B switches for all context lanes of a process (bench.py, tools/): the option of that key, for new contexts; a value the
+        // option refuses is ignored.  MVS_SSIM_PRUNE=0 scores every candidate in full, MVS_SSIM_F32=0 walks the pruned search in
+        // float64, MVS_FUSE_MIXED=1 takes the one-launch fuse list (profiles/round5_fuse_mixed.txt), MVS_FFT_NO_SLAB=1 /
+        // MVS_FFT_NO_PAIR=1 turn the three-pass phase correlation (mvs_fft_slab.hip) / its partner pairs off, MVS_FFT_SLAB_AXES
+        // picks the crop orientations that take the three passes
+        static const char* const env_switch[][2] = {{"MVS_SSIM_PRUNE", "ssim_prune"},   {"MVS_SSIM_F32", "ssim_f32"},
+                                                    {"MVS_FUSE_MIXED", "fuse_mixed"},   {"MVS_FFT_SLAB_AXES", "fft_slab_axes"},
+                                                    {"MVS_FFT_NO_SLAB", "fft_no_slab"}, {"MVS_FFT_NO_PAIR", "fft_no_pair"}};
+        for (const auto& e : env_switch) {
+            const char* ev = getenv(e[0]);
+            if (ev && *ev) (void)set_option(c, e[1], atoi(ev));
+        }
     }
     // (The side streams of the fuse launch are NOT created here but at the first large launch (mvs_ensure_aux_streams, ~70 ms once).
     // Round 6 created them at init to take that one-off out of a one-mosaic caller's first fuse(): HIP maps streams onto its hardware
@@ -280,6 +352,7 @@ int mvs_init(int device) {
     // (alternating runs on one box, profiles/round6_summary.md).  Creation order: lanes, side streams, copy stream.)
     c->ready = true;
     c->last_error.clear();
+    c->last_code = 0;
     return MVS_OK;
 }
 
@@ -358,111 +431,7 @@ int mvs_set_option(int device, const char* key, int64_t value) {
     if (rc) return rc;
     if (!key) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_set_option: NULL key");
     std::lock_guard<std::recursive_mutex> lock(c->mu);
-    if (!strcmp(key, "force_generic")) {
-        c->force_generic = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "pool_cache_limit_mb")) {
-        std::lock_guard<std::mutex> plock(c->pool_mu);
-        c->pool_cache_limit = (size_t)std::max<int64_t>(value, 0) << 20;
-        if (c->pool_cached_bytes > c->pool_cache_limit) pool_flush(c);
-        return MVS_OK;
-    }
-    if (!strcmp(key, "no_regions")) {
-        c->no_regions = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "deconv_general")) {
-        c->deconv_general = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "dct_general")) {
-        c->dct_general = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "rows_v1")) {
-        c->rows_v1 = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "cb_mask_count")) {
-        c->cb_mask_count = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "cb_mask_closed_form")) {
-        c->cb_mask_closed_form = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "fuse_mixed")) {
-        c->fuse_mixed = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "serial_classes")) {
-        c->serial_classes = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "reg_unfused")) {
-        c->reg_unfused = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "ssim_two_pass")) {
-        c->ssim_two_pass = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "ssim_f32")) {
-        c->ssim_f32 = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "ssim_prune")) {
-        c->ssim_prune = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "materialize_shifts")) {
-        c->materialize_shifts = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "cb_exact")) {
-        c->cb_exact = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "cb_blend_generic")) {
-        c->cb_blend_generic = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "cb_taps_f64")) {
-        if (value < 0 || value > 3) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_set_option: cb_taps_f64 is 0, 1, 2 or 3");
-        c->cb_taps = (int)value;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "cb_nosplit")) {
-        c->cb_nosplit = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "cb_unpaired")) {
-        c->cb_unpaired = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "fft_no_pair")) {
-        c->fft_no_pair = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "fft_slab_axes")) {
-        if (value < 0 || value > 7) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_set_option: fft_slab_axes is a mask of 3 bits");
-        c->fft_slab_axes = (int)value;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "fft_no_slab")) {
-        c->fft_no_slab = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "fft_no_line")) {
-        c->fft_no_line = value != 0;
-        return MVS_OK;
-    }
-    if (!strcmp(key, "ablate")) {
-        c->ablate = (int)value;
-        return MVS_OK;
-    }
-    return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_set_option: unknown key '%s'", key);
+    return set_option(c, key, value);
 }
 
 // Measurement counters of one context: "reg_alg_bytes" (algorithmic HBM bytes of the pairwise registrations),
@@ -474,17 +443,12 @@ int mvs_get_counter(int device, const char* key, int32_t reset, double* value_ou
     if (rc) return rc;
     if (!key || !value_out) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_get_counter: NULL argument");
     std::lock_guard<std::recursive_mutex> lock(c->mu);
-    if (!strcmp(key, "reg_alg_bytes")) { *value_out = c->reg_alg_bytes; if (reset) c->reg_alg_bytes = 0.0; return MVS_OK; }
-    if (!strcmp(key, "reg_alg_bytes_full")) { *value_out = c->reg_alg_bytes_full; if (reset) c->reg_alg_bytes_full = 0.0; return MVS_OK; }
-    if (!strcmp(key, "reg_pairs")) { *value_out = (double)c->reg_pairs; if (reset) c->reg_pairs = 0; return MVS_OK; }
-    if (!strcmp(key, "reg_candidates")) { *value_out = (double)c->reg_candidates; if (reset) c->reg_candidates = 0; return MVS_OK; }
-    if (!strcmp(key, "reg_rewalks")) { *value_out = (double)c->reg_rewalks; if (reset) c->reg_rewalks = 0; return MVS_OK; }
-    if (!strcmp(key, "reg_pruned")) { *value_out = (double)c->reg_pruned; if (reset) c->reg_pruned = 0; return MVS_OK; }
-    if (!strcmp(key, "reg_cand_volumes")) { *value_out = c->reg_cand_volumes; if (reset) c->reg_cand_volumes = 0.0; return MVS_OK; }
-    if (!strcmp(key, "reg_slab_pairs")) { *value_out = (double)c->reg_slab_pairs; if (reset) c->reg_slab_pairs = 0; return MVS_OK; }
-    if (!strcmp(key, "cb_mask_views")) { *value_out = (double)c->cb_mask_views; if (reset) c->cb_mask_views = 0; return MVS_OK; }
-    if (!strcmp(key, "cb_mask_boxes")) { *value_out = (double)c->cb_mask_boxes; if (reset) c->cb_mask_boxes = 0; return MVS_OK; }
-    if (!strcmp(key, "cb_line_launches")) { *value_out = (double)c->cb_line_launches; if (reset) c->cb_line_launches = 0; return MVS_OK; }
+    for (const MvsCounter& e : kCounters) {
+        if (strcmp(key, e.key)) continue;
+        if (e.real) { *value_out = c->*e.real; if (reset) c->*e.real = 0.0; }
+        else { *value_out = (double)(c->*e.count); if (reset) c->*e.count = 0; }
+        return MVS_OK;
+    }
     if (!strcmp(key, "cb_overflow")) {
         // chunks of the fast content-based path whose mask list overflowed: the ones a host-result call redid by itself are counted,
         // a raised flag means device-result chunks that still hold a wrong result (the caller redoes them with option cb_exact)
@@ -503,7 +467,6 @@ int mvs_get_counter(int device, const char* key, int32_t reset, double* value_ou
     if (!strcmp(key, "pool_misses")) { std::lock_guard<std::mutex> pl(c->pool_mu); *value_out = (double)c->pool_misses; if (reset) c->pool_misses = 0; return MVS_OK; }
     if (!strcmp(key, "pool_miss_bytes")) { std::lock_guard<std::mutex> pl(c->pool_mu); *value_out = c->pool_miss_bytes; if (reset) c->pool_miss_bytes = 0.0; return MVS_OK; }
     if (!strcmp(key, "pool_releases")) { std::lock_guard<std::mutex> pl(c->pool_mu); *value_out = (double)c->pool_releases; if (reset) c->pool_releases = 0; return MVS_OK; }
-    if (!strcmp(key, "cb_overflows_redone")) { *value_out = (double)c->cb_overflows; if (reset) c->cb_overflows = 0; return MVS_OK; }
     if (!strcmp(key, "fuse_plan_ms")) {
         *value_out = mvs_rows_last_plan_ms(c) + mvs_regions_last_plan_ms(c);
         return MVS_OK;

@@ -47,5 +47,6 @@ __device__ __forceinline__ float dct_lookup(const DctLookup& L, int view, double
 
 // the chunk-level fused weighted average of mvs_fuse.hip with the DCT factor (mvs_fuse_chunk_dct); `keep_start`: the caller
 // recorded the context's start event before its own kernels (last_kernel_ms then covers the whole chunk)
-int mvs_fuse_chunk_impl(int device, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out,
+// (arguments checked, context locked, device set by the entry)
+int mvs_fuse_chunk_impl(MvsContext* c, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out,
                         const DctLookup* dct, bool keep_start);

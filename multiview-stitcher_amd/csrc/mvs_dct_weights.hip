@@ -314,7 +314,6 @@ __global__ void dct_interp_kernel(DctLookup L, int n_views, int sz, int sy, int 
 }
 
 int grid_for(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 256 * 32)); }
-size_t align_up(size_t v) { return (v + 255) / 256 * 256; }
 
 // clamped block sizes, grid and branch of weights.py:165-203
 int dct_geometry(MvsContext* c, const char* who, const int64_t shape[3], int ndim, const mvs_dct_opts_t* o, DctGeom* g) {
@@ -419,75 +418,47 @@ extern "C" int mvs_content_dct_weights(int device, const float* views, int32_t n
     // work area: [stack | weights] (host data only) | Q | Qn | quality scratch
     const size_t off_st = 0, off_w = off_st + (host ? align_up(vol_bytes) : 0), off_q = off_w + (host ? align_up(vol_bytes) : 0);
     const size_t off_qn = off_q + grid_bytes, off_s = off_qn + grid_bytes, total = off_s + qs_bytes;
-    void* work = nullptr;
-    rc = mvs_malloc(device, total, &work);
+    MvsWorkArea work(c);
+    rc = work.alloc(total);
     if (rc) return rc;
-    char* W = (char*)work;
+    char* W = (char*)work.ptr;
     const float* stack = host ? (const float*)(W + off_st) : views;
     float* dw = host ? (float*)(W + off_w) : weights_out;
     float* Q = (float*)(W + off_q);
     float* Qn = (float*)(W + off_qn);
-    auto fail = [&](int code) {
-        hipStreamSynchronize(c->stream);
-        mvs_free(device, work);
-        return code;
-    };
-#define DCT_TRY(expr)                                                                                                    \
-    do {                                                                                                                 \
-        hipError_t _e = (expr);                                                                                          \
-        if (_e != hipSuccess) {                                                                                          \
-            (void)hipGetLastError();                                                                                     \
-            mvs_fail(c, _e == hipErrorOutOfMemory ? MVS_ERR_OUT_OF_MEMORY : MVS_ERR_HIP, "%s failed: %s (%s:%d)", #expr,  \
-                     hipGetErrorString(_e), __FILE__, __LINE__);                                                         \
-            return fail(c->last_code);                                                                                   \
-        }                                                                                                                \
-    } while (0)
-    if (host) DCT_TRY(hipMemcpyAsync((void*)stack, views, vol_bytes, hipMemcpyHostToDevice, c->stream));
-    DCT_TRY(hipEventRecord(c->ev_start, c->stream));
+    if (host) MVS_HIP_TRY(c, hipMemcpyAsync((void*)stack, views, vol_bytes, hipMemcpyHostToDevice, c->stream));
+    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     rc = run_quality(c, g, n_views, stack, Q, Qn, W + off_s, lds, slots, slot_floats);
-    if (rc) return fail(rc);
+    if (rc) return rc;
     hipLaunchKernelGGL(dct_interp_kernel, dim3(grid_for(S)), dim3(256), 0, c->stream, lookup_of(g, Qn), (int)n_views, g.S[0], g.S[1], g.S[2], dw);
-    DCT_TRY(hipGetLastError());
-    DCT_TRY(hipEventRecord(c->ev_stop, c->stream));
+    MVS_HIP_TRY(c, hipGetLastError());
+    MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
     c->timing_valid = true;
     const hipMemcpyKind back = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (host) DCT_TRY(hipMemcpyAsync(weights_out, dw, vol_bytes, back, c->stream));
-    if (quality_out) DCT_TRY(hipMemcpyAsync(quality_out, Q, (size_t)g.nblocks * n_views * 4, back, c->stream));
-    if (host) DCT_TRY(hipStreamSynchronize(c->stream));
-#undef DCT_TRY
-    return mvs_free(device, work);
+    if (host) MVS_HIP_TRY(c, hipMemcpyAsync(weights_out, dw, vol_bytes, back, c->stream));
+    if (quality_out) MVS_HIP_TRY(c, hipMemcpyAsync(quality_out, Q, (size_t)g.nblocks * n_views * 4, back, c->stream));
+    if (host) MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return work.release();
 }
 
 extern "C" int mvs_fuse_chunk_dct(int device, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts,
                                   const mvs_dct_opts_t* dopts, void* out) {
-    MvsContext* c0 = mvs_ctx(device);
-    if (!views || n_views < 1 || !opts || !dopts || !out) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: NULL/empty argument");
-    if (opts->ndim != 2 && opts->ndim != 3) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: ndim must be 2 or 3");
-    if (opts->order != 0 && opts->order != 1) return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_fuse_chunk_dct: interpolation order %d (only 0|1)", opts->order);
-    if (opts->fusion != MVS_FUSE_WEIGHTED_AVERAGE || opts->weights != MVS_WEIGHTS_NONE)
-        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: needs fusion weighted_average and weights none");
-    for (int k = 0; k < 3; ++k) {
-        if (opts->out_shape[k] < 1 || opts->out_shape[k] > 0x7fffffffLL || opts->trim[k] < 0 || opts->out_shape[k] - 2 * opts->trim[k] < 1)
-            return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: bad out_shape/trim on axis %d", k);
-        if (opts->index_origin[k] != 0) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: index_origin must be 0");
-    }
-    if (opts->ndim == 2 && opts->out_shape[0] != 1) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: 2D chunks need out_shape[0] == 1");
-    const long long S = (long long)opts->out_shape[0] * opts->out_shape[1] * opts->out_shape[2];
-    if (S * n_views > (1LL << 40) || S > 0x7fffffffLL) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: chunk too large");
-    for (int i = 0; i < n_views; ++i) {
-        if (!mvs_dtype_size(views[i].dtype) || views[i].dtype != views[0].dtype)
-            return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: views must share one valid dtype");
-        if (views[i].index_offset[0] || views[i].index_offset[1] || views[i].index_offset[2])
-            return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: index_offset must be 0");
-        if (views[i].mem == MVS_MEM_HOST &&
-            (views[i].stride[2] != 1 || views[i].stride[1] != views[i].shape[2] || views[i].stride[0] != views[i].shape[1] * views[i].shape[2]))
-            return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_fuse_chunk_dct: host slabs must be C-contiguous");
-    }
-
     MvsContext* c;
     int rc = mvs_check_ready(device, &c);
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> lock(c->mu);
+    rc = mvs_check_chunk_args(c, "mvs_fuse_chunk_dct", views, n_views, opts, out);
+    if (rc) return rc;
+    if (!dopts) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: NULL/empty argument");
+    if (opts->fusion != MVS_FUSE_WEIGHTED_AVERAGE || opts->weights != MVS_WEIGHTS_NONE)
+        return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: needs fusion weighted_average and weights none");
+    for (int k = 0; k < 3; ++k)
+        if (opts->index_origin[k] != 0) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: index_origin must be 0");
+    const long long S = (long long)opts->out_shape[0] * opts->out_shape[1] * opts->out_shape[2];
+    if (S * n_views > (1LL << 40) || S > 0x7fffffffLL) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: chunk too large");
+    for (int i = 0; i < n_views; ++i)
+        if (views[i].index_offset[0] || views[i].index_offset[1] || views[i].index_offset[2])
+            return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk_dct: index_offset must be 0");
     MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
     DctGeom g;
     rc = dct_geometry(c, "mvs_fuse_chunk_dct", opts->out_shape, opts->ndim, dopts, &g);
@@ -498,59 +469,40 @@ extern "C" int mvs_fuse_chunk_dct(int device, const mvs_view_t* views, int32_t n
     const size_t qs_bytes = quality_scratch_bytes(c, g, n_views, &lds, &slots, &slot_floats);
     const size_t es = mvs_dtype_size(views[0].dtype);
     size_t host_bytes = 0;
-    for (int i = 0; i < n_views; ++i)
-        if (views[i].mem == MVS_MEM_HOST) host_bytes += align_up((size_t)views[i].shape[0] * views[i].shape[1] * views[i].shape[2] * es);
+    rc = mvs_stage_views_bytes(c, views, n_views, es, &host_bytes);
+    if (rc) return rc;
     // work area: host slabs | resampled stack | Q | Qn | quality scratch
     const size_t grid_bytes = align_up((size_t)g.nblocks * n_views * 4);
     const size_t off_st = host_bytes, off_q = off_st + align_up((size_t)S * n_views * 4), off_qn = off_q + grid_bytes, off_s = off_qn + grid_bytes;
-    void* work = nullptr;
-    rc = mvs_malloc(device, off_s + qs_bytes, &work);
+    MvsWorkArea work(c);
+    rc = work.alloc(off_s + qs_bytes);
     if (rc) return rc;
-    char* W = (char*)work;
+    char* W = (char*)work.ptr;
     float* stack = (float*)(W + off_st);
     float* Q = (float*)(W + off_q);
     float* Qn = (float*)(W + off_qn);
-    auto fail = [&](int code) {
-        hipStreamSynchronize(c->stream);
-        mvs_free(device, work);
-        return code;
-    };
-#define DCT_TRY(expr)                                                                                                    \
-    do {                                                                                                                 \
-        hipError_t _e = (expr);                                                                                          \
-        if (_e != hipSuccess) {                                                                                          \
-            (void)hipGetLastError();                                                                                     \
-            mvs_fail(c, _e == hipErrorOutOfMemory ? MVS_ERR_OUT_OF_MEMORY : MVS_ERR_HIP, "%s failed: %s (%s:%d)", #expr,  \
-                     hipGetErrorString(_e), __FILE__, __LINE__);                                                         \
-            return fail(c->last_code);                                                                                   \
-        }                                                                                                                \
-    } while (0)
     // host slabs are staged once; the fuse launch reads the same device copies
     std::vector<mvs_view_t> dv(views, views + n_views);
     size_t cursor = 0;
-    for (int i = 0; i < n_views; ++i)
-        if (views[i].mem == MVS_MEM_HOST) {
-            const size_t nb = (size_t)views[i].shape[0] * views[i].shape[1] * views[i].shape[2] * es;
-            DCT_TRY(hipMemcpyAsync(W + cursor, views[i].data, nb, hipMemcpyHostToDevice, c->stream));
-            dv[i].data = W + cursor;
-            dv[i].mem = MVS_MEM_DEVICE;
-            cursor += align_up(nb);
-        }
-    DCT_TRY(hipEventRecord(c->ev_start, c->stream));
+    for (int i = 0; i < n_views; ++i) {
+        rc = mvs_stage_view(c, views[i], es, W, &cursor, &dv[i].data);
+        if (rc) return rc;
+        dv[i].mem = MVS_MEM_DEVICE;
+    }
+    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     // transformed_views (_core.py:1622-1633): the views resampled onto the whole chunk, NaN outside
     for (int i = 0; i < n_views; ++i) {
         DevView d;
         rc = mvs_fill_dev_view(c, dv[i], opts->ndim, dv[i].data, &d);
-        if (rc) return fail(rc);
+        if (rc) return rc;
         mvs_launch_resample(c, d, dv[i].dtype, opts->order, NAN, stack + (long long)i * S, opts->out_shape);
-        DCT_TRY(hipGetLastError());
+        MVS_HIP_TRY(c, hipGetLastError());
     }
     rc = run_quality(c, g, n_views, stack, Q, Qn, W + off_s, lds, slots, slot_floats);
-    if (rc) return fail(rc);
+    if (rc) return rc;
     const DctLookup L = lookup_of(g, Qn);
-    rc = mvs_fuse_chunk_impl(device, dv.data(), n_views, opts, out, &L, true);
-    if (rc) return fail(rc);
-    if (opts->out_mem != MVS_MEM_HOST && host_bytes) DCT_TRY(hipStreamSynchronize(c->stream));   // (the caller may free its slabs)
-#undef DCT_TRY
-    return mvs_free(device, work);
+    rc = mvs_fuse_chunk_impl(c, dv.data(), n_views, opts, out, &L, true);
+    if (rc) return rc;
+    if (opts->out_mem != MVS_MEM_HOST && host_bytes) MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the caller may free its slabs)
+    return work.release();
 }

@@ -377,19 +377,19 @@ extern "C" int mvs_mv_deconv(int device, const float* views, float* weights, int
     const size_t fS = (size_t)S * 4;
     size_t off_psi = 0, off_wr = off_psi + fS, off_a = off_wr + fS, off_b = off_a + (separable ? fS : 0);
     size_t off_m0 = off_b + (separable ? fS : 0);
-    size_t off_m1 = off_m0 + (opts->erosion_px > 0 ? ((size_t)S + 255) / 256 * 256 : 0);
-    size_t off_bm = off_m1 + (opts->erosion_px > 0 ? ((size_t)S + 255) / 256 * 256 : 0);
+    size_t off_m1 = off_m0 + (opts->erosion_px > 0 ? align_up((size_t)S) : 0);
+    size_t off_bm = off_m1 + (opts->erosion_px > 0 ? align_up((size_t)S) : 0);
     size_t off_pk = off_bm + init_blocks * 4;
     size_t off_tp = off_pk + 256;
-    size_t off_out = off_tp + (htaps.size() * 4 + 255) / 256 * 256;
+    size_t off_out = off_tp + align_up(htaps.size() * 4);
     const size_t out_elem = mvs_dtype_size(opts->out_dtype);
     const long long oz = nz - 2 * opts->trim[0], oy = ny - 2 * opts->trim[1], ox = nx - 2 * opts->trim[2];
     const size_t out_bytes = (size_t)(oz * oy * ox) * out_elem;
     size_t total = off_out + (out_mem == MVS_MEM_HOST ? out_bytes : 0);
-    void* work = nullptr;
-    rc = mvs_malloc(device, total, &work);
+    MvsWorkArea work(c);
+    rc = work.alloc(total);
     if (rc) return rc;
-    char* W = (char*)work;
+    char* W = (char*)work.ptr;
     float* psi = (float*)(W + off_psi);
     float* wr = (float*)(W + off_wr);
     float* pa = (float*)(W + off_a);
@@ -401,36 +401,20 @@ extern "C" int mvs_mv_deconv(int device, const float* views, float* weights, int
     float* dtaps = (float*)(W + off_tp);
     void* dout = out_mem == MVS_MEM_HOST ? (void*)(W + off_out) : out;
 
-    auto fail = [&](int code) {
-        hipStreamSynchronize(c->stream);
-        mvs_free(device, work);
-        return code;
-    };
-#define DECONV_TRY(expr)                                                                                                     \
-    do {                                                                                                                     \
-        hipError_t _e = (expr);                                                                                              \
-        if (_e != hipSuccess) {                                                                                              \
-            (void)hipGetLastError();                                                                                         \
-            mvs_fail(c, _e == hipErrorOutOfMemory ? MVS_ERR_OUT_OF_MEMORY : MVS_ERR_HIP, "%s failed: %s (%s:%d)", #expr,      \
-                     hipGetErrorString(_e), __FILE__, __LINE__);                                                             \
-            return fail(c->last_code);                                                                                       \
-        }                                                                                                                    \
-    } while (0)
-
-    DECONV_TRY(hipEventRecord(c->ev_start, c->stream));
-    DECONV_TRY(hipMemcpyAsync(dtaps, htaps.data(), htaps.size() * 4, hipMemcpyHostToDevice, c->stream));
+    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
+    MVS_HIP_TRY(c, hipMemcpyAsync(dtaps, htaps.data(), htaps.size() * 4, hipMemcpyHostToDevice, c->stream));
     const int pgrid = grid_for(S);
     if (opts->flags & MVS_DECONV_PREPARE_WEIGHTS) {
         hipLaunchKernelGGL(deconv_weights_kernel, dim3(pgrid), dim3(256), 0, c->stream, views, (float*)weights, V, S);
-        DECONV_TRY(hipGetLastError());
+        MVS_HIP_TRY(c, hipGetLastError());
     }
     const float minv = (float)opts->min_value;
     const int lambda_on = opts->lambda_reg > 0.0;
     hipLaunchKernelGGL(deconv_init_kernel, dim3(init_blocks), dim3(256), 0, c->stream, views, weights, V, S, minv, psi, bmax);
-    DECONV_TRY(hipGetLastError());
+    MVS_HIP_TRY(c, hipGetLastError());
     if (lambda_on) {
         hipLaunchKernelGGL(deconv_peak_kernel, dim3(1), dim3(256), 0, c->stream, (const float*)bmax, init_blocks, peak);
-        DECONV_TRY(hipGetLastError());
+        MVS_HIP_TRY(c, hipGetLastError());
     }
     Epi e{};
     e.psi = psi;
@@ -450,10 +434,10 @@ extern "C" int mvs_mv_deconv(int device, const float* views, float* weights, int
                 const float* t2 = dtaps + (long long)(V + v) * kvolp;
                 hipLaunchKernelGGL(deconv_conv_general<0>, ggrid, dim3(64), glds, c->stream, (const float*)psi, wr, t1, nz, ny, nx, kz, ky, kxp,
                                    az, ay, ax, 0.f, e);
-                DECONV_TRY(hipGetLastError());
+                MVS_HIP_TRY(c, hipGetLastError());
                 hipLaunchKernelGGL(deconv_conv_general<1>, ggrid, dim3(64), glds, c->stream, (const float*)wr, (float*)nullptr, t2, nz, ny, nx,
                                    kz, ky, kxp, az, ay, ax, 1.f, e);
-                DECONV_TRY(hipGetLastError());
+                MVS_HIP_TRY(c, hipGetLastError());
             } else {
                 const float* t1 = dtaps + (long long)v * ksep;
                 const float* t2 = dtaps + (long long)(V + v) * ksep;
@@ -464,7 +448,7 @@ extern "C" int mvs_mv_deconv(int device, const float* views, float* weights, int
                 hipLaunchKernelGGL((deconv_pass<1, 1, 0>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)pa, pb, t2 + kz, nz, ny, nx, ky, ay, sep_cval[2 * v], e);
                 hipLaunchKernelGGL((deconv_pass<0, 1, 2>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)pb, (float*)nullptr, t2, nz, ny, nx, kz, az,
                                    sep_cval[2 * v + 1], e);
-                DECONV_TRY(hipGetLastError());
+                MVS_HIP_TRY(c, hipGetLastError());
             }
         }
     }
@@ -476,7 +460,7 @@ extern "C" int mvs_mv_deconv(int device, const float* views, float* weights, int
             hipLaunchKernelGGL(deconv_erode_kernel, dim3(pgrid), dim3(256), 0, c->stream, (const unsigned char*)src, dst, nz, ny, nx, (int)ndim);
             std::swap(src, dst);
         }
-        DECONV_TRY(hipGetLastError());
+        MVS_HIP_TRY(c, hipGetLastError());
         mask = src;
     }
     const int ogrid = grid_for(oz * oy * ox);
@@ -490,14 +474,13 @@ extern "C" int mvs_mv_deconv(int device, const float* views, float* weights, int
     else
         hipLaunchKernelGGL(deconv_out_kernel<unsigned char>, dim3(ogrid), dim3(256), 0, c->stream, (const float*)psi, mask, ny, nx, (int)oz, (int)oy,
                            (int)ox, t0, t1, t2, (unsigned char*)dout);
-    DECONV_TRY(hipGetLastError());
-    DECONV_TRY(hipEventRecord(c->ev_stop, c->stream));
+    MVS_HIP_TRY(c, hipGetLastError());
+    MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
     c->timing_valid = true;
     if (out_mem == MVS_MEM_HOST) {
-        DECONV_TRY(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
-        DECONV_TRY(hipStreamSynchronize(c->stream));
+        MVS_HIP_TRY(c, hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
-#undef DECONV_TRY
     // the work area goes back to the pool; the pool hands it out again only to work later on this stream
-    return mvs_free(device, work);
+    return work.release();
 }

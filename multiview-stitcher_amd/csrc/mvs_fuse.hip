@@ -1349,8 +1349,6 @@ void launch_fuse_tr(const TrParams& P, int fusion, int nblocks, hipStream_t s) {
         hipLaunchKernelGGL((fuse_tr_kernel<TIn, TOut, MVS_FUSE_SIMPLE_AVERAGE>), dim3(nblocks), dim3(256), 0, s, P);
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 }  // namespace
 
 // Translation-path record of a view for callers outside this file (mvs_gauss.hip): prepare_translation_view + the chunk frame +
@@ -1373,42 +1371,70 @@ int mvs_fuse_rows(MvsContext* c, const TrView* htr, const TrView* dtr, int n_vie
 int mvs_fuse_content_based(MvsContext* c, const mvs_view_t* views, int32_t n_views,
                            const mvs_fuse_opts_t* opts, void* out);   // mvs_gauss.hip
 
-extern "C" int mvs_fuse_chunk(int device, const mvs_view_t* views, int32_t n_views,
-                              const mvs_fuse_opts_t* opts, void* out) {
-    return mvs_fuse_chunk_impl(device, views, n_views, opts, out, nullptr, false);
+// What every chunk entry requires of its arguments; `what` is the entry's name, the prefix of the messages.
+int mvs_check_chunk_args(MvsContext* c, const char* what, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, const void* out) {
+    if (!views || n_views < 1 || !opts || !out) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: NULL/empty argument", what);
+    if (opts->ndim != 2 && opts->ndim != 3) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: ndim must be 2 or 3", what);
+    if (opts->order != 0 && opts->order != 1)
+        return mvs_fail(c, MVS_ERR_UNSUPPORTED, "%s: interpolation order %d (only 0|1)", what, opts->order);
+    if (opts->fusion < 0 || opts->fusion > 2) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: unknown fusion %d", what, opts->fusion);
+    const int dtype = views[0].dtype;
+    if (!mvs_dtype_size(dtype)) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: bad dtype %d", what, dtype);
+    for (int i = 0; i < n_views; ++i)
+        if (views[i].dtype != dtype) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "%s: views must share one dtype", what);
+    if (opts->out_dtype != dtype) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "%s: out_dtype must equal the input dtype", what);
+    for (int k = 0; k < 3; ++k)
+        if (opts->trim[k] < 0 || opts->out_shape[k] - 2 * opts->trim[k] < 1 || opts->out_shape[k] > 0x7fffffffLL)
+            return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: bad out_shape/trim on axis %d", what, k);
+    if (opts->ndim == 2 && opts->out_shape[0] != 1) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: 2D chunks need out_shape[0] == 1", what);
+    return MVS_OK;
 }
 
-// `dct` (mvs_fuse_chunk_dct): weighted average without content-based weights, through the generic kernel only
-int mvs_fuse_chunk_impl(int device, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out,
-                        const DctLookup* dct, bool keep_start) {
+// Host slabs of a chunk's views go through a device area the caller supplies.  mvs_stage_views_bytes checks them and gives the
+// area's size (every slab starts on a 256-byte boundary); mvs_stage_view queues the upload of one view's slab at `area + *cursor`
+// and advances the cursor.  *dev_data is where the kernels find the view: its slab in the area, or view.data for a device view.
+int mvs_stage_views_bytes(MvsContext* c, const mvs_view_t* views, int n_views, size_t es, size_t* bytes) {
+    *bytes = 0;
+    for (int i = 0; i < n_views; ++i) {
+        const mvs_view_t& v = views[i];
+        if (v.mem != MVS_MEM_HOST) continue;
+        if (v.stride[2] != 1 || v.stride[1] != v.shape[2] || v.stride[0] != v.shape[1] * v.shape[2])
+            return mvs_fail(c, MVS_ERR_UNSUPPORTED, "host slabs must be C-contiguous");
+        *bytes += align_up((size_t)v.shape[0] * v.shape[1] * v.shape[2] * es);
+    }
+    return MVS_OK;
+}
+
+int mvs_stage_view(MvsContext* c, const mvs_view_t& v, size_t es, char* area, size_t* cursor, const void** dev_data) {
+    *dev_data = v.data;
+    if (v.mem != MVS_MEM_HOST) return MVS_OK;
+    const size_t nb = (size_t)v.shape[0] * v.shape[1] * v.shape[2] * es;
+    MVS_HIP_TRY(c, hipMemcpyAsync(area + *cursor, v.data, nb, hipMemcpyHostToDevice, c->stream));
+    *dev_data = area + *cursor;
+    *cursor += align_up(nb);
+    return MVS_OK;
+}
+
+extern "C" int mvs_fuse_chunk(int device, const mvs_view_t* views, int32_t n_views,
+                              const mvs_fuse_opts_t* opts, void* out) {
     MvsContext* c;
     int rc = mvs_check_ready(device, &c);
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> lock(c->mu);
-    if (!views || n_views < 1 || !opts || !out)
-        return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk: NULL/empty argument");
-    if (opts->ndim != 2 && opts->ndim != 3)
-        return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk: ndim must be 2 or 3");
-    if (opts->order != 0 && opts->order != 1)
-        return mvs_fail(c, MVS_ERR_UNSUPPORTED, "mvs_fuse_chunk: interpolation order %d (only 0|1)", opts->order);
-    if (opts->fusion < 0 || opts->fusion > 2)
-        return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk: unknown fusion %d", opts->fusion);
-    const int dtype = views[0].dtype;
-    if (!mvs_dtype_size(dtype)) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk: bad dtype %d", dtype);
-    for (int i = 0; i < n_views; ++i)
-        if (views[i].dtype != dtype)
-            return mvs_fail(c, MVS_ERR_UNSUPPORTED, "mvs_fuse_chunk: views must share one dtype");
-    if (opts->out_dtype != dtype)
-        return mvs_fail(c, MVS_ERR_UNSUPPORTED, "mvs_fuse_chunk: out_dtype must equal the input dtype");
-    int64_t os[3];
-    for (int k = 0; k < 3; ++k) {
-        os[k] = opts->out_shape[k] - 2 * opts->trim[k];
-        if (opts->trim[k] < 0 || os[k] < 1 || opts->out_shape[k] > 0x7fffffffLL)
-            return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk: bad out_shape/trim on axis %d", k);
-    }
-    if (opts->ndim == 2 && opts->out_shape[0] != 1)
-        return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk: 2D chunks need out_shape[0] == 1");
+    rc = mvs_check_chunk_args(c, "mvs_fuse_chunk", views, n_views, opts, out);
+    if (rc) return rc;
     MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
+    return mvs_fuse_chunk_impl(c, views, n_views, opts, out, nullptr, false);
+}
+
+// The entry has checked the arguments (mvs_check_chunk_args), holds the context's lock and has set the device.
+// `dct` (mvs_fuse_chunk_dct): weighted average without content-based weights, through the generic kernel only
+int mvs_fuse_chunk_impl(MvsContext* c, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out,
+                        const DctLookup* dct, bool keep_start) {
+    int rc;
+    const int dtype = views[0].dtype;
+    int64_t os[3];
+    for (int k = 0; k < 3; ++k) os[k] = opts->out_shape[k] - 2 * opts->trim[k];
 
     if (opts->weights == MVS_WEIGHTS_CONTENT_BASED) {
         if (opts->fusion != MVS_FUSE_WEIGHTED_AVERAGE)
@@ -1417,25 +1443,19 @@ int mvs_fuse_chunk_impl(int device, const mvs_view_t* views, int32_t n_views, co
     }
     if (opts->weights != MVS_WEIGHTS_NONE)
         return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk: unknown weights %d", opts->weights);
-    if (dct && opts->fusion != MVS_FUSE_WEIGHTED_AVERAGE)
-        return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk: DCT weights need weighted_average fusion");
 
     // stage host slabs into device scratch (slot 0)
     const size_t es = mvs_dtype_size(dtype);
     size_t host_bytes = 0;
-    for (int i = 0; i < n_views; ++i)
-        if (views[i].mem == MVS_MEM_HOST) {
-            if (views[i].stride[1] != views[i].shape[2] || views[i].stride[0] != views[i].shape[1] * views[i].shape[2])
-                return mvs_fail(c, MVS_ERR_UNSUPPORTED, "host slabs must be C-contiguous");
-            host_bytes += align_up((size_t)views[i].shape[0] * views[i].shape[1] * views[i].shape[2] * es, 256);
-        }
+    rc = mvs_stage_views_bytes(c, views, n_views, es, &host_bytes);
+    if (rc) return rc;
     char* slab_base = nullptr;
     if (host_bytes) {
         slab_base = (char*)mvs_scratch(c, 0, host_bytes);
         if (!slab_base) return mvs_alloc_failed(c);
     }
-    const size_t views_bytes = align_up(sizeof(DevView) * (size_t)n_views, 256);
-    const size_t cull_bytes = align_up(sizeof(int) * 6 * (size_t)n_views, 256);
+    const size_t views_bytes = align_up(sizeof(DevView) * (size_t)n_views);
+    const size_t cull_bytes = align_up(sizeof(int) * 6 * (size_t)n_views);
     const size_t params_bytes = views_bytes + cull_bytes + sizeof(TrView) * (size_t)n_views;
     DevView* hviews = (DevView*)mvs_pinned(c, params_bytes);
     if (!hviews) return mvs_alloc_failed(c);
@@ -1444,13 +1464,9 @@ int mvs_fuse_chunk_impl(int device, const mvs_view_t* views, int32_t n_views, co
 
     size_t cursor = 0;
     for (int i = 0; i < n_views; ++i) {
-        const void* dptr = views[i].data;
-        if (views[i].mem == MVS_MEM_HOST) {
-            size_t nb = (size_t)views[i].shape[0] * views[i].shape[1] * views[i].shape[2] * es;
-            MVS_HIP_TRY(c, hipMemcpyAsync(slab_base + cursor, views[i].data, nb, hipMemcpyHostToDevice, c->stream));
-            dptr = slab_base + cursor;
-            cursor += align_up(nb, 256);
-        }
+        const void* dptr;
+        rc = mvs_stage_view(c, views[i], es, slab_base, &cursor, &dptr);
+        if (rc) return rc;
         rc = fill_dev_view(c, views[i], opts->ndim, dptr, &hviews[i]);
         if (rc) return rc;
         prepare_translation_view(&hviews[i], opts->order, opts->fusion, opts->out_shape, es, opts->index_origin, views[i].index_offset);
@@ -1510,6 +1526,12 @@ int mvs_fuse_chunk_impl(int device, const mvs_view_t* views, int32_t n_views, co
         P.nbx = (P.ox + brick_x - 1) / brick_x;
         nblocks = (long long)P.nbz * P.nby * P.nbx;
     };
+    auto launch_generic = [&] {
+        mvs_dispatch_dtype(dtype, [&](auto tag) {
+            using E = decltype(tag);
+            launch_fuse<E, E>(P, opts->order, opts->fusion, (int)nblocks, c->stream);
+        });
+    };
     set_brick_grid(use_tr);
     if (nblocks > 0x7fffffffLL) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "chunk too large for one launch");
 
@@ -1556,17 +1578,12 @@ int mvs_fuse_chunk_impl(int device, const mvs_view_t* views, int32_t n_views, co
         if (opts->fusion == MVS_FUSE_WEIGHTED_AVERAGE) {
             hipLaunchKernelGGL(xweight_table_kernel, dim3(16, n_views), dim3(256), 0, c->stream, T.views, n_views, xtab);
         }
-        switch (dtype) {
-            case MVS_U8: launch_fuse_tr<unsigned char, unsigned char>(T, opts->fusion, (int)nblocks, c->stream); break;
-            case MVS_U16: launch_fuse_tr<unsigned short, unsigned short>(T, opts->fusion, (int)nblocks, c->stream); break;
-            default: launch_fuse_tr<float, float>(T, opts->fusion, (int)nblocks, c->stream); break;
-        }
+        mvs_dispatch_dtype(dtype, [&](auto tag) {
+            using E = decltype(tag);
+            launch_fuse_tr<E, E>(T, opts->fusion, (int)nblocks, c->stream);
+        });
     } else {
-        switch (dtype) {
-            case MVS_U8: launch_fuse<unsigned char, unsigned char>(P, opts->order, opts->fusion, (int)nblocks, c->stream); break;
-            case MVS_U16: launch_fuse<unsigned short, unsigned short>(P, opts->order, opts->fusion, (int)nblocks, c->stream); break;
-            default: launch_fuse<float, float>(P, opts->order, opts->fusion, (int)nblocks, c->stream); break;
-        }
+        launch_generic();
     }
     MVS_HIP_TRY(c, hipGetLastError());
     if (use_tr && !regions_done && n_views > 64) {
@@ -1575,18 +1592,9 @@ int mvs_fuse_chunk_impl(int device, const mvs_view_t* views, int32_t n_views, co
         MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (ovf) {
             // a column met more than 64 views: redo the chunk with the generic kernel (bricks of 4x4x64)
-            P.bz = (os[0] > 1) ? 4 : 1;
-            P.by = (os[0] > 1) ? 4 : 16;
-            P.nbz = (P.oz + P.bz - 1) / P.bz;
-            P.nby = (P.oy + P.by - 1) / P.by;
-            P.nbx = (P.ox + kBrickX - 1) / kBrickX;
-            const long long nb2 = (long long)P.nbz * P.nby * P.nbx;
-            if (nb2 > 0x7fffffffLL) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "chunk too large for one launch");
-            switch (dtype) {
-                case MVS_U8: launch_fuse<unsigned char, unsigned char>(P, opts->order, opts->fusion, (int)nb2, c->stream); break;
-                case MVS_U16: launch_fuse<unsigned short, unsigned short>(P, opts->order, opts->fusion, (int)nb2, c->stream); break;
-                default: launch_fuse<float, float>(P, opts->order, opts->fusion, (int)nb2, c->stream); break;
-            }
+            set_brick_grid(false);
+            if (nblocks > 0x7fffffffLL) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "chunk too large for one launch");
+            launch_generic();
             MVS_HIP_TRY(c, hipGetLastError());
         }
     }
@@ -1610,15 +1618,16 @@ int stage_single_view(MvsContext* c, const mvs_view_t* view, int ndim, bool need
     if (need_data) {
         size_t es = mvs_dtype_size(view->dtype);
         if (!es || !view->data) return mvs_fail(c, MVS_ERR_INVALID_ARG, "bad view dtype/data");
-        if (view->mem == MVS_MEM_HOST) {
-            if (view->stride[1] != view->shape[2] || view->stride[0] != view->shape[1] * view->shape[2])
-                return mvs_fail(c, MVS_ERR_UNSUPPORTED, "host slabs must be C-contiguous");
-            size_t nb = (size_t)view->shape[0] * view->shape[1] * view->shape[2] * es;
-            void* s = mvs_scratch(c, 0, nb);
+        size_t host_bytes = 0, cursor = 0;
+        int rc = mvs_stage_views_bytes(c, view, 1, es, &host_bytes);
+        if (rc) return rc;
+        char* s = nullptr;
+        if (host_bytes) {
+            s = (char*)mvs_scratch(c, 0, host_bytes);
             if (!s) return mvs_alloc_failed(c);
-            MVS_HIP_TRY(c, hipMemcpyAsync(s, view->data, nb, hipMemcpyHostToDevice, c->stream));
-            dptr = s;
         }
+        rc = mvs_stage_view(c, *view, es, s, &cursor, &dptr);
+        if (rc) return rc;
     }
     mvs_view_t tmp = *view;
     if (!need_data) { tmp.shape[0] = tmp.shape[1] = tmp.shape[2] = 1; tmp.stride[0] = tmp.stride[1] = tmp.stride[2] = 1; }
@@ -1774,11 +1783,10 @@ void mvs_launch_resample(MvsContext* c, const DevView& d, int dtype, int order, 
     const int nblocks = (int)std::min<long long>((n + 255) / 256, 256 * 16);
 #define MVS_RS(T, O) hipLaunchKernelGGL((resample_kernel<T, O>), dim3(nblocks), dim3(256), 0, c->stream, d, out, \
                                         (int)shape[0], (int)shape[1], (int)shape[2], cval, b0[0], b0[1], b0[2])
-    switch (dtype) {
-        case MVS_U8: if (order) MVS_RS(unsigned char, 1); else MVS_RS(unsigned char, 0); break;
-        case MVS_U16: if (order) MVS_RS(unsigned short, 1); else MVS_RS(unsigned short, 0); break;
-        default: if (order) MVS_RS(float, 1); else MVS_RS(float, 0); break;
-    }
+    mvs_dispatch_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if (order) MVS_RS(T, 1); else MVS_RS(T, 0);
+    });
 #undef MVS_RS
 }
 

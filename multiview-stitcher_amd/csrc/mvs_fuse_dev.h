@@ -29,6 +29,15 @@ struct DevView {
 };
 
 
+// ---- the prologue the chunk entries share (mvs_fuse.hip) ----
+// what every entry requires of (views, opts, out); `what` = the entry's name, the prefix of the messages
+int mvs_check_chunk_args(MvsContext* c, const char* what, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, const void* out);
+// host slabs of the views: check them and size the device area they go through (the caller's choice: scratch slot 0, or part of
+// its own work block) ...
+int mvs_stage_views_bytes(MvsContext* c, const mvs_view_t* views, int n_views, size_t es, size_t* bytes);
+// ... then, per view, queue its upload at area + *cursor; *dev_data = where the kernels read the view (v.data for a device view)
+int mvs_stage_view(MvsContext* c, const mvs_view_t& v, size_t es, char* area, size_t* cursor, const void** dev_data);
+
 int mvs_fill_dev_view(MvsContext* c, const mvs_view_t& v, int ndim, const void* dev_data, DevView* d);
 // `box0` (may be null): chunk index of the output array's first voxel -- the output is a sub-box of the chunk, evaluated with the
 // chunk's own coordinates

@@ -1272,7 +1272,7 @@ int mvs_fuse_regions(MvsContext* c, const TrView* htr, const TrView* dtr, int n_
             items.insert(items.end(), items_by_class[k].begin(), items_by_class[k].end());
         }
         if (items.empty() || items.size() > (1u << 28)) return MVS_OK;
-        rbytes = (regions.size() * sizeof(Region) + 255) / 256 * 256;
+        rbytes = align_up(regions.size() * sizeof(Region));
         const size_t ibytes = items.size() * sizeof(Item);
         char* hbuf = (char*)mvs_pinned_slot(c, 1, rbytes + ibytes + 256);   // slot 0 holds the view parameters still in flight
         if (!hbuf) return mvs_alloc_failed(c);
@@ -1314,9 +1314,10 @@ int mvs_fuse_regions(MvsContext* c, const TrView* htr, const TrView* dtr, int n_
     if (pc.mixed_count) {       // copy + one-view + two-view bricks: one launch over the space-ordered list, on the main stream
         const int cnt = pc.mixed_count;                     // = 8 L, L a multiple of 4: grid = 2 L workgroups, a multiple of 8
         const dim3 grid(cnt / 4), block(256);
-        if (dtype == MVS_U8) hipLaunchKernelGGL((fuse_region_mixed_kernel<unsigned char, unsigned char>), grid, block, 0, c->stream, P, 0, cnt);
-        else if (dtype == MVS_U16) hipLaunchKernelGGL((fuse_region_mixed_kernel<unsigned short, unsigned short>), grid, block, 0, c->stream, P, 0, cnt);
-        else hipLaunchKernelGGL((fuse_region_mixed_kernel<float, float>), grid, block, 0, c->stream, P, 0, cnt);
+        mvs_dispatch_dtype(dtype, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL((fuse_region_mixed_kernel<T, T>), grid, block, 0, c->stream, P, 0, cnt);
+        });
         item0 = cnt;
     }
     const bool time_classes = c->serial_classes && !pc.mixed_count;
@@ -1333,17 +1334,14 @@ int mvs_fuse_regions(MvsContext* c, const TrView* htr, const TrView* dtr, int n_
             side_used[side_of_class[k]] = true;
             MVS_HIP_TRY(c, hipStreamWaitEvent(kstream, c->ev_fork, 0));
         }
-        if (cnt && k == 4) {
+        if (cnt) {
             const dim3 grid(((cnt + 3) / 4 + 7) / 8 * 8), block(256);   // multiple of 8: see the XCD mapping in the kernels
-            if (dtype == MVS_U8) hipLaunchKernelGGL((copy_region_kernel<unsigned char, unsigned char>), grid, block, 0, kstream, P, item0, cnt);
-            else if (dtype == MVS_U16) hipLaunchKernelGGL((copy_region_kernel<unsigned short, unsigned short>), grid, block, 0, kstream, P, item0, cnt);
-            else hipLaunchKernelGGL((copy_region_kernel<float, float>), grid, block, 0, kstream, P, item0, cnt);
-        } else if (cnt) {
-            const dim3 grid(((cnt + 3) / 4 + 7) / 8 * 8), block(256);   // multiple of 8: see the XCD mapping in the kernels
-#define MVS_RK(T, NVC) hipLaunchKernelGGL((fuse_region_kernel<T, T, NVC>), grid, block, 0, kstream, P, item0, cnt)
-#define MVS_RKD(NVC) do { if (dtype == MVS_U8) MVS_RK(unsigned char, NVC); else if (dtype == MVS_U16) MVS_RK(unsigned short, NVC); else MVS_RK(float, NVC); } while (0)
-            if (k == 0) MVS_RKD(1); else if (k == 1) MVS_RKD(2); else if (k == 2) MVS_RKD(4); else MVS_RKD(8);
-#undef MVS_RKD
+#define MVS_RK(NVC) hipLaunchKernelGGL((fuse_region_kernel<T, T, NVC>), grid, block, 0, kstream, P, item0, cnt)
+            mvs_dispatch_dtype(dtype, [&](auto tag) {
+                using T = decltype(tag);
+                if (k == 4) hipLaunchKernelGGL((copy_region_kernel<T, T>), grid, block, 0, kstream, P, item0, cnt);
+                else if (k == 0) MVS_RK(1); else if (k == 1) MVS_RK(2); else if (k == 2) MVS_RK(4); else MVS_RK(8);
+            });
 #undef MVS_RK
         }
         item0 += cnt;

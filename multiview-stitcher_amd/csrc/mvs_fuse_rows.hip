@@ -133,8 +133,8 @@ int mvs_fuse_rows(MvsContext* c, const TrView* htr, const TrView* dtr, int n_vie
         size_t nitems = 0;
         for (int k = 0; k < 6; ++k) nitems += items_by_class[k].size();
         if (nitems == 0 || nitems > (1u << 26)) return MVS_OK;
-        const size_t sbytes = (strips.size() * sizeof(Strip) + 255) / 256 * 256;
-        const size_t cbytes = (cells.size() * sizeof(Cell) + 255) / 256 * 256;
+        const size_t sbytes = align_up(strips.size() * sizeof(Strip));
+        const size_t cbytes = align_up(cells.size() * sizeof(Cell));
         const size_t ibytes = nitems * sizeof(RowItem);
         const size_t total = sbytes + cbytes + ibytes;
         char* hbuf = (char*)mvs_pinned_slot(c, 1, total + 256);   // slot 0 holds the view parameters still in flight

@@ -800,12 +800,7 @@ int mvs_fuse_content_based(MvsContext* c, const mvs_view_t* views, int32_t n_vie
     std::vector<DevView> dvs((size_t)n_views);
     std::vector<CbBox> boxes((size_t)n_views);
     size_t host_bytes = 0;
-    for (int i = 0; i < n_views; ++i)
-        if (views[i].mem == MVS_MEM_HOST) {
-            if (views[i].stride[1] != views[i].shape[2] || views[i].stride[0] != views[i].shape[1] * views[i].shape[2])
-                return mvs_fail(c, MVS_ERR_UNSUPPORTED, "host slabs must be C-contiguous");
-            host_bytes += ((size_t)views[i].shape[0] * views[i].shape[1] * views[i].shape[2] * es + 255) / 256 * 256;
-        }
+    { const int rcs = mvs_stage_views_bytes(c, views, n_views, es, &host_bytes); if (rcs) return rcs; }
     char* slab_base = nullptr;
     if (host_bytes) {
         slab_base = (char*)mvs_scratch(c, 0, host_bytes);
@@ -815,14 +810,10 @@ int mvs_fuse_content_based(MvsContext* c, const mvs_view_t* views, int32_t n_vie
     size_t cursor = 0;
     long long pool = 0, max_box = 1;
     for (int i = 0; i < n_views; ++i) {
-        const void* dptr = views[i].data;
-        if (views[i].mem == MVS_MEM_HOST) {
-            const size_t nb = (size_t)views[i].shape[0] * views[i].shape[1] * views[i].shape[2] * es;
-            MVS_HIP_TRY(c, hipMemcpyAsync(slab_base + cursor, views[i].data, nb, hipMemcpyHostToDevice, c->stream));
-            dptr = slab_base + cursor;
-            cursor += (nb + 255) / 256 * 256;
-        }
-        int rc = mvs_fill_dev_view(c, views[i], opts->ndim, dptr, &dvs[i]);
+        const void* dptr;
+        int rc = mvs_stage_view(c, views[i], es, slab_base, &cursor, &dptr);
+        if (rc) return rc;
+        rc = mvs_fill_dev_view(c, views[i], opts->ndim, dptr, &dvs[i]);
         if (rc) return rc;
         mvs_view_to_chunk_frame(&dvs[i], opts->index_origin, views[i].index_offset);
         int lo[3], hi[3];
@@ -841,7 +832,7 @@ int mvs_fuse_content_based(MvsContext* c, const mvs_view_t* views, int32_t n_vie
     }
 
     // ---- scratch layout (slot 6): pools I, BW, F (one box per view), 6 temporaries of the largest box, filter kernels, boxes ----
-    const size_t pool_b = (size_t)pool * 4, tmp_b = ((size_t)max_box * 4 + 255) / 256 * 256;
+    const size_t pool_b = (size_t)pool * 4, tmp_b = align_up((size_t)max_box * 4);
     // paired line passes (gauss1d_pair_kernel): can every line set of every view be staged twice in 60 KiB of LDS?
     const int ndim = opts->ndim;
     int r1, r2;
@@ -891,11 +882,11 @@ int mvs_fuse_content_based(MvsContext* c, const mvs_view_t* views, int32_t n_vie
     float* T1 = (float*)((char*)T0 + tmp_b);
     float* T2 = (float*)((char*)T1 + tmp_b);
     // filter kernels, boxes and view records: ONE device block in the layout of the host staging block below (one upload per chunk)
-    char* dblock = (char*)(((uintptr_t)(base + 3 * pool_b + tmp_total) + 255) / 256 * 256);
+    char* dblock = (char*)align_up((uintptr_t)(base + 3 * pool_b + tmp_total));
     if ((w1.size() + w2.size()) * 8 > 32 * 1024) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "content_based: sigma too large");
-    const size_t wb = ((w1.size() + w2.size()) * 8 + 255) / 256 * 256, bb = ((size_t)n_views * sizeof(CbBox) + 255) / 256 * 256,
-                 vb = ((size_t)n_views * sizeof(DevView) + 255) / 256 * 256, rb = ((size_t)n_views * sizeof(CbMaskRec) + 255) / 256 * 256,
-                 ob = ((size_t)n_views * 16 + 255) / 256 * 256;
+    const size_t wb = align_up((w1.size() + w2.size()) * 8), bb = align_up((size_t)n_views * sizeof(CbBox)),
+                 vb = align_up((size_t)n_views * sizeof(DevView)), rb = align_up((size_t)n_views * sizeof(CbMaskRec)),
+                 ob = align_up((size_t)n_views * 16);
     double* dfw1 = (double*)dblock;
     double* dfw2 = dfw1 + w1.size();
     CbBox* dboxes = (CbBox*)(dblock + wb);
@@ -1106,18 +1097,13 @@ int mvs_fuse_content_based(MvsContext* c, const mvs_view_t* views, int32_t n_vie
     }
     const int gbo = grid_for(no);
     const int tz = (int)opts->trim[0], ty = (int)opts->trim[1], tx = (int)opts->trim[2];
-    if (small) {
-        switch (dtype) {
-            case MVS_U8: hipLaunchKernelGGL(cb_fuse8_kernel<unsigned char>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, bx8, n_views, tz, ty, tx, O, (unsigned char*)dout); break;
-            case MVS_U16: hipLaunchKernelGGL(cb_fuse8_kernel<unsigned short>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, bx8, n_views, tz, ty, tx, O, (unsigned short*)dout); break;
-            default: hipLaunchKernelGGL(cb_fuse8_kernel<float>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, bx8, n_views, tz, ty, tx, O, (float*)dout); break;
-        }
-    } else
-    switch (dtype) {
-        case MVS_U8: hipLaunchKernelGGL(cb_fuse_kernel<unsigned char>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, dboxes, n_views, tz, ty, tx, O, (unsigned char*)dout); break;
-        case MVS_U16: hipLaunchKernelGGL(cb_fuse_kernel<unsigned short>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, dboxes, n_views, tz, ty, tx, O, (unsigned short*)dout); break;
-        default: hipLaunchKernelGGL(cb_fuse_kernel<float>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, dboxes, n_views, tz, ty, tx, O, (float*)dout); break;
-    }
+    mvs_dispatch_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        if (small)
+            hipLaunchKernelGGL(cb_fuse8_kernel<T>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, bx8, n_views, tz, ty, tx, O, (T*)dout);
+        else
+            hipLaunchKernelGGL(cb_fuse_kernel<T>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, dboxes, n_views, tz, ty, tx, O, (T*)dout);
+    });
     MVS_HIP_TRY(c, hipGetLastError());
     MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
     c->timing_valid = true;
@@ -1161,12 +1147,7 @@ static int cb_fast_chunk(MvsContext* c, const mvs_view_t* views, int32_t n_views
     // ---- device views and their boxes inside the chunk ----
     std::vector<DevView> dvs((size_t)n_views);
     size_t host_bytes = 0;
-    for (int i = 0; i < n_views; ++i)
-        if (views[i].mem == MVS_MEM_HOST) {
-            if (views[i].stride[1] != views[i].shape[2] || views[i].stride[0] != views[i].shape[1] * views[i].shape[2])
-                return mvs_fail(c, MVS_ERR_UNSUPPORTED, "host slabs must be C-contiguous");
-            host_bytes += ((size_t)views[i].shape[0] * views[i].shape[1] * views[i].shape[2] * es + 255) / 256 * 256;
-        }
+    { const int rcs = mvs_stage_views_bytes(c, views, n_views, es, &host_bytes); if (rcs) return rcs; }
     CbFastViews VS;
     memset(&VS, 0, sizeof(VS));
     VS.nv = n_views;
@@ -1224,27 +1205,24 @@ static int cb_fast_chunk(MvsContext* c, const mvs_view_t* views, int32_t n_views
     MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     {
         size_t cursor = 0;
-        for (int i = 0; i < n_views; ++i)
-            if (views[i].mem == MVS_MEM_HOST) {
-                const size_t nb = (size_t)views[i].shape[0] * views[i].shape[1] * views[i].shape[2] * es;
-                MVS_HIP_TRY(c, hipMemcpyAsync(slab_base + cursor, views[i].data, nb, hipMemcpyHostToDevice, c->stream));
-                dvs[i].data = slab_base + cursor;
-                cursor += (nb + 255) / 256 * 256;
-            }
+        for (int i = 0; i < n_views; ++i) {
+            const int rcs = mvs_stage_view(c, views[i], es, slab_base, &cursor, &dvs[i].data);
+            if (rcs) return rcs;
+        }
     }
 
     // ---- scratch (slot 6): pools I, BW, F, T0; row records; [uploaded block: weights f64 / f32, view records, mask records]; lists; tables ----
-    const size_t pool_b = ((size_t)pool * 4 + 255) / 256 * 256;
-    const size_t rows_b = ((size_t)total_rows * 16 + 255) / 256 * 256;
+    const size_t pool_b = align_up((size_t)pool * 4);
+    const size_t rows_b = align_up((size_t)total_rows * 16);
     const size_t nw = w1.size() + w2.size();
-    const size_t wdb = (nw * 8 + 255) / 256 * 256, wfb = (nw * 4 + 255) / 256 * 256, vb = ((size_t)n_views * sizeof(DevView) + 255) / 256 * 256,
-                 rb = ((size_t)n_views * sizeof(CbFastRec) + 255) / 256 * 256;
+    const size_t wdb = align_up(nw * 8), wfb = align_up(nw * 4), vb = align_up((size_t)n_views * sizeof(DevView)),
+                 rb = align_up((size_t)n_views * sizeof(CbFastRec));
     const size_t up_b = wdb + wfb + vb + rb;
-    const size_t miss_b = (size_t)n_views * kCbMissCap * 16, tab_b = ((size_t)tab_doubles * 8 + 255) / 256 * 256;
+    const size_t miss_b = (size_t)n_views * kCbMissCap * 16, tab_b = align_up((size_t)tab_doubles * 8);
     long long max_rows = 1;
     for (int i = 0; i < n_views; ++i) max_rows = std::max(max_rows, (long long)VS.v[i].n[0] * VS.v[i].n[1]);
     const unsigned rows_grid = (unsigned)std::min<long long>((max_rows + 15) / 16, 1024);      // a workgroup: 4 wavefronts x 4 rows per sweep
-    const size_t part_b = ((size_t)n_views * rows_grid * sizeof(CbPartial) + 255) / 256 * 256;
+    const size_t part_b = align_up((size_t)n_views * rows_grid * sizeof(CbPartial));
     const size_t need = 4 * pool_b + rows_b + up_b + miss_b + tab_b + part_b + 4096;
     char* base = (char*)mvs_scratch(c, 6, need);
     if (!base) return mvs_alloc_failed(c);
@@ -1392,11 +1370,10 @@ static int cb_fast_chunk(MvsContext* c, const mvs_view_t* views, int32_t n_views
     }
     const int gbo = grid_for((no + kCbRun - 1) / kCbRun);
     const int tz = (int)opts->trim[0], ty = (int)opts->trim[1], tx = (int)opts->trim[2];
-    switch (dtype) {
-        case MVS_U8: hipLaunchKernelGGL(cb_fuse8_runs_kernel<unsigned char>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, bx8, n_views, tz, ty, tx, O, (unsigned char*)dout); break;
-        case MVS_U16: hipLaunchKernelGGL(cb_fuse8_runs_kernel<unsigned short>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, bx8, n_views, tz, ty, tx, O, (unsigned short*)dout); break;
-        default: hipLaunchKernelGGL(cb_fuse8_runs_kernel<float>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, bx8, n_views, tz, ty, tx, O, (float*)dout); break;
-    }
+    mvs_dispatch_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(cb_fuse8_runs_kernel<T>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, bx8, n_views, tz, ty, tx, O, (T*)dout);
+    });
     MVS_HIP_TRY(c, hipGetLastError());
     MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
     c->timing_valid = true;

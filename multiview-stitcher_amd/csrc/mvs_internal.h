@@ -180,11 +180,47 @@ static inline int mvs_alloc_failed(const MvsContext* c) { return c->last_code ? 
         }                                                                            \
     } while (0)
 
+// A block of mvs_malloc that a call works in.  Leaving the scope with the block still held is an error return: launches already
+// queued may touch it, so the stream is waited for before the block goes back to the pool.  The success path ends in release(),
+// which frees without waiting (the pool hands a block out again only to work later on this stream).
+struct MvsWorkArea {
+    MvsContext* c;
+    void* ptr = nullptr;
+    explicit MvsWorkArea(MvsContext* ctx) : c(ctx) {}
+    MvsWorkArea(const MvsWorkArea&) = delete;
+    MvsWorkArea& operator=(const MvsWorkArea&) = delete;
+    int alloc(size_t nbytes) { return mvs_malloc(c->device, nbytes, &ptr); }
+    int release() {
+        void* p = ptr;
+        ptr = nullptr;
+        return mvs_free(c->device, p);
+    }
+    ~MvsWorkArea() {
+        if (!ptr) return;
+        (void)hipStreamSynchronize(c->stream);
+        mvs_free(c->device, ptr);
+    }
+};
+
+// byte counts of device work areas: every part starts on a 256-byte boundary
+static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+
 static inline size_t mvs_dtype_size(int dtype) {
     switch (dtype) {
         case MVS_U8: return 1;
         case MVS_U16: return 2;
         case MVS_F32: return 4;
         default: return 0;
+    }
+}
+
+// Calls f(T{}) with T the element type of `dtype`, for launches templated on it: `[&](auto tag) { using T = decltype(tag); ... }`.
+// Callers have validated `dtype` (mvs_dtype_size); whatever is neither uint8 nor uint16 is float.
+template <typename F>
+static inline void mvs_dispatch_dtype(int dtype, F&& f) {
+    switch (dtype) {
+        case MVS_U8: f((unsigned char)0); break;
+        case MVS_U16: f((unsigned short)0); break;
+        default: f(0.f); break;
     }
 }

@@ -644,11 +644,11 @@ extern "C" int mvs_phasecorr_multi(int device, const float* fixed, const float* 
       if (la >= 0 && mvs_fft_reg_length((int)shape[la])) ga = std::max<long long>(ga, (n / shape[la] + 15) / 16);
       if (slab_axis >= 0) ga = std::max(ga, mvs_phasecorr_slab_peaks(shape, slab_axis));
   }
-  const size_t mb_red = (size_t)ga * 32, mb_z0 = mb_red, mb_res = mb_red + 256, mb_res_stride = (res_elems * sizeof(float2) + 255) / 256 * 256;
+  const size_t mb_red = (size_t)ga * 32, mb_z0 = mb_red, mb_res = mb_red + 256, mb_res_stride = align_up(res_elems * sizeof(float2));
   void *mb_host = nullptr, *mb_dev = nullptr;
   // ... | the kernel vectors of every refinement (pinned: their upload is a plain asynchronous copy, no staging through the runtime)]
   const size_t mb_k = mb_res + mb_res_stride * (size_t)n_norm;
-  const size_t mb_kbytes = upsample_factor > 1 ? ((size_t)up_U0 * (size_t)(nz + ny + nx) * sizeof(float2) + 255) / 256 * 256 : 0;
+  const size_t mb_kbytes = upsample_factor > 1 ? align_up((size_t)up_U0 * (size_t)(nz + ny + nx) * sizeof(float2)) : 0;
   rc = mvs_mailbox(c, mb_k + mb_kbytes * (size_t)n_norm, &mb_host, &mb_dev);
   if (rc) return rc;
   char* red = (char*)mb_dev;
@@ -717,7 +717,7 @@ extern "C" int mvs_phasecorr_multi(int device, const float* fixed, const float* 
   };
   std::vector<NormState> state((size_t)n_norm);
   const int up_U = (int)ceilf((float)upsample_factor * 1.5f);
-  const size_t up_kbytes = ((size_t)up_U * (size_t)(nz + ny + nx) * sizeof(float2) + 255) / 256 * 256;
+  const size_t up_kbytes = align_up((size_t)up_U * (size_t)(nz + ny + nx) * sizeof(float2));
   const size_t up_s1 = (size_t)nz * ny * up_U, up_s2 = (size_t)nz * up_U * up_U, up_s3 = (size_t)up_U * up_U * up_U;
   const size_t up_bytes = up_kbytes + (up_s1 + up_s2 + up_s3) * sizeof(float2) + 1024;
   char* up_base = nullptr;
@@ -1042,20 +1042,17 @@ static int bin_mean_impl(int device, const void* in, int32_t dtype, int32_t mem,
         if (!dout) return mvs_alloc_failed(c);
     }
     const int gb = grid_for(n);
-#define MVS_BIN(T) hipLaunchKernelGGL(bin_mean_kernel<T>, dim3(gb), dim3(256), 0, c->stream, (const T*)din, sz, sy, (T*)dout, \
-                                      o[0], o[1], o[2], (int)bin[0], (int)bin[1], (int)bin[2])
     const bool vec_u16 = dtype == MVS_U16 && bin[2] == 2 && o[2] % 4 == 0 && sy % 8 == 0 && sz % 8 == 0 && ((uintptr_t)din % 16) == 0 &&
                          ((uintptr_t)dout % 8) == 0 && bin[0] * bin[1] <= 16384;
     if (vec_u16) {
         hipLaunchKernelGGL(bin_mean_u16x2_kernel, dim3(grid_for(n / 4)), dim3(256), 0, c->stream, (const unsigned short*)din, sz, sy,
                            (unsigned short*)dout, o[0], o[1], o[2], (int)bin[0], (int)bin[1]);
     } else
-    switch (dtype) {
-        case MVS_U8: MVS_BIN(unsigned char); break;
-        case MVS_U16: MVS_BIN(unsigned short); break;
-        default: MVS_BIN(float); break;
-    }
-#undef MVS_BIN
+        mvs_dispatch_dtype(dtype, [&](auto tag) {
+            using T = decltype(tag);
+            hipLaunchKernelGGL(bin_mean_kernel<T>, dim3(gb), dim3(256), 0, c->stream, (const T*)din, sz, sy, (T*)dout, o[0], o[1], o[2],
+                               (int)bin[0], (int)bin[1], (int)bin[2]);
+        });
     MVS_HIP_TRY(c, hipGetLastError());
     if (out_mem == MVS_MEM_HOST) MVS_HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)n * es, hipMemcpyDeviceToHost, c->stream));
     if (wait) MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -1317,7 +1317,7 @@ __global__ __launch_bounds__(1024) void rank_table_kernel(const unsigned int* __
 struct DeviceBump {   // bump allocator over one scratch slot
     char* base; size_t cap, used;
     template <typename T> T* take(size_t count) {
-        const size_t bytes = (count * sizeof(T) + 255) / 256 * 256;
+        const size_t bytes = align_up(count * sizeof(T));
         if (used + bytes > cap) return nullptr;
         T* p = (T*)(base + used);
         used += bytes;
@@ -1466,8 +1466,8 @@ int mvs_score_candidates_impl(int device, const float* fixed, const float* movin
     if (!d_counter) return mvs_fail(c, MVS_ERR_HIP, "mvs_score_candidates: scratch layout");
     // results the host reads (reduction partials of the rank correlation, voxel and region statistics) are written by the kernels
     // straight into the context's mailbox (pinned host memory): no copy launches
-    const size_t mb_partial = 0, mb_vox = ((size_t)gb * 4 * sizeof(double) + 255) / 256 * 256;
-    const size_t mb_reg = mb_vox + ((size_t)(kMaxResident + 2) * sizeof(VoxStats) + 255) / 256 * 256;
+    const size_t mb_partial = 0, mb_vox = align_up((size_t)gb * 4 * sizeof(double));
+    const size_t mb_reg = mb_vox + align_up((size_t)(kMaxResident + 2) * sizeof(VoxStats));
     void *mb_host = nullptr, *mb_dev = nullptr;
     {
         const int rcm = mvs_mailbox(c, mb_reg + (size_t)kMaxResident * sizeof(RegionStats), &mb_host, &mb_dev);

@@ -27,7 +27,7 @@ from .mv_deconv import PSFType, multi_view_deconvolution  # noqa: F401  (fusion.
 from .weights import content_based_dct  # noqa: F401  (fusion.content_based_dct)
 from . import spatial_image_utils as si_utils
 from .device import DeviceArray, is_device_array
-from .transformation import _as_zyx, embed3_stack, fill_view_geometry, get_pixel_affine, get_pixel_affines, shape3
+from .transformation import _as_zyx, embed3_stack, fill_view_geometry, get_pixel_affine, get_pixel_affines, shape3, view_data
 
 BoundingBox = dict
 
@@ -105,6 +105,23 @@ def _weights_code(weights_func):
     if weights_func is content_based or weights_func == "content_based":
         return _lib.MVS_WEIGHTS_CONTENT_BASED
     raise NotImplementedError("backend='hip' supports weights_func None or content_based")
+
+
+def _view_frames(sims, spacings, full_view_bbs):
+    """``(spacings, full_view_bbs)`` of a chunk's views with the defaults filled: a slab's spacing is its whole view's, and
+    without whole-view boxes every slab is a whole view."""
+    if spacings is None:
+        spacings = [fvb["spacing"] for fvb in full_view_bbs] if full_view_bbs is not None else [None] * len(sims)
+    if full_view_bbs is None:
+        full_view_bbs = [si_utils.get_stack_properties_from_sim(s) for s in sims]
+    return spacings, full_view_bbs
+
+
+def _trim_dict(trim_overlap_in_pixels, sdims):
+    """``trim_overlap_in_pixels`` (one int, or a dict that may leave dims out) per spatial dim."""
+    if not isinstance(trim_overlap_in_pixels, dict):
+        return {d: int(trim_overlap_in_pixels) for d in sdims}
+    return {d: int(trim_overlap_in_pixels.get(d, 0)) for d in sdims}
 
 
 def _bb_dicts(bb, sdims):
@@ -213,10 +230,7 @@ def fuse_np(
     fusion_code = _fusion_code(fusion_func)
     weights_code = _weights_code(None if dct else weights_func)
 
-    if spacings is None:
-        spacings = [fvb["spacing"] for fvb in full_view_bbs] if full_view_bbs is not None else [None] * len(sims)
-    if full_view_bbs is None:
-        full_view_bbs = [si_utils.get_stack_properties_from_sim(s) for s in sims]
+    spacings, full_view_bbs = _view_frames(sims, spacings, full_view_bbs)
 
     n = len(sims)
     views = (_lib.mvs_view_t * n)()
@@ -258,24 +272,9 @@ def fuse_np(
         np.stack([_as_zyx(b["shape"], sdims) for b in fv]), sdims, blending_widths, shrink_distance)
     w_matrices, w_offsets = get_pixel_affines(p_inv, sup_origins, sup_spacings, ref_out_origin, out_spacing)
     ptrs, shapes, strides = np.zeros(n, np.uint64), np.ones((n, 3), np.int64), np.zeros((n, 3), np.int64)
-    mems = np.full(n, _lib.MVS_MEM_DEVICE, np.int32)
+    mems = np.zeros(n, np.int32)
     for i, sim in enumerate(sims):
-        data = sim.data
-        if is_device_array(data):
-            if data.dtype != input_dtype:
-                raise TypeError("all views of a chunk must share one dtype")
-            data = data.on_device(device)     # a tile resident on another GPU: peer copy, cached per (tile, device)
-            data.wait_ready(device)           # a tile still on its way (device.to_device_async): this call's stream waits for the upload
-            ptrs[i], st = data.ptr, [int(v) for v in data.strides]
-        else:
-            data = np.ascontiguousarray(data, dtype=input_dtype)
-            ptrs[i] = data.ctypes.data
-            st = [int(np.prod(data.shape[k + 1:])) for k in range(data.ndim)]   # numpy's strides of size-1 axes are arbitrary
-            mems[i] = _lib.MVS_MEM_HOST
-        s3 = shape3(data.shape)
-        if len(st) == 2:  # 2D slab: a single z plane
-            st = [st[0] * s3[1], st[0], st[1]]
-        shapes[i], strides[i] = s3, st
+        ptrs[i], shapes[i], strides[i], mems[i], data = view_data(sim.data, device, input_dtype)
         keep.append(data)
     V = _lib.mvs_view_t
     rec = np.frombuffer(views, dtype=np.uint8).reshape(n, C.sizeof(V))
@@ -301,10 +300,7 @@ def fuse_np(
     for i, table in enumerate(tables):
         edt[i, : table.size] = table.reshape(-1)
 
-    if not isinstance(trim_overlap_in_pixels, dict):
-        trim = {d: int(trim_overlap_in_pixels) for d in sdims}
-    else:
-        trim = {d: int(trim_overlap_in_pixels.get(d, 0)) for d in sdims}
+    trim = _trim_dict(trim_overlap_in_pixels, sdims)
     res_shape = [out_shape[i] - 2 * trim[d] for i, d in enumerate(sdims)]
 
     opts = _lib.mvs_fuse_opts_t()
@@ -372,8 +368,6 @@ def _fuse_np_deconvolution(sims, params, out_bb, sdims, input_dtype, fusion_func
     into two (V, *S) stacks; mvs_mv_deconv masks the weights by ~isnan and normalises them, deconvolves, trims the halo,
     applies nan_to_num and casts to the input dtype.  ``output_spacing`` is the chunk spacing unless the caller passed
     one (_core.py:1658-1662).  Only the result crosses PCIe, and only when a host result is asked for."""
-    from .transformation import fill_view_geometry
-
     lib = _lib.init(device)
     ndim = len(sdims)
     kw = dict(fusion_func_kwargs or {})
@@ -382,10 +376,7 @@ def _fuse_np_deconvolution(sims, params, out_bb, sdims, input_dtype, fusion_func
             raise TypeError(f"fusion_func_kwargs must not set {k!r}: fuse_np supplies it")
     if kw.get("output_spacing") is None:
         kw["output_spacing"] = dict(out_bb["spacing"])
-    if spacings is None:
-        spacings = [fvb["spacing"] for fvb in full_view_bbs] if full_view_bbs is not None else [None] * len(sims)
-    if full_view_bbs is None:
-        full_view_bbs = [si_utils.get_stack_properties_from_sim(s) for s in sims]
+    spacings, full_view_bbs = _view_frames(sims, spacings, full_view_bbs)
     out_shape = tuple(int(out_bb["shape"][d]) for d in sdims)
     o_origin, o_spacing = _as_zyx(out_bb["origin"], sdims), _as_zyx(out_bb["spacing"], sdims)
     n = len(sims)
@@ -401,20 +392,9 @@ def _fuse_np_deconvolution(sims, params, out_bb, sdims, input_dtype, fusion_func
         in_spacing = spacing if spacing is not None else si_utils.get_spacing_from_sim(sim)
         matrix, offset = get_pixel_affine(p_inv, si_utils.get_origin_from_sim(sim, asarray=True), _as_zyx(in_spacing, sdims),
                                           o_origin, o_spacing)
-        data = sim.data
         view = _lib.mvs_view_t()
-        if is_device_array(data):
-            data = data.on_device(device)
-            data.wait_ready(device)
-            if data.dtype not in _lib.DTYPE_CODES:
-                raise TypeError(f"unsupported dtype {data.dtype}")
-            fill_view_geometry(view, data.ptr, _lib.DTYPE_CODES[data.dtype], _lib.MVS_MEM_DEVICE, data.shape, data.strides, matrix, offset)
-        else:
-            data = np.ascontiguousarray(data)
-            if data.dtype not in _lib.DTYPE_CODES:
-                data = data.astype(np.float32)
-            fill_view_geometry(view, data.ctypes.data, _lib.DTYPE_CODES[data.dtype], _lib.MVS_MEM_HOST, data.shape,
-                               [int(np.prod(data.shape[k + 1:])) for k in range(data.ndim)], matrix, offset)
+        ptr, shape, strides, mem, data = view_data(sim.data, device)
+        fill_view_geometry(view, ptr, _lib.DTYPE_CODES[data.dtype], mem, shape, strides, matrix, offset)
         keep.append(data)
         rc = lib.mvs_resample(device, C.byref(view), s3, int(interpolation_order), float("nan"), C.c_void_p(views_t.ptr + 4 * i * S),
                               _lib.MVS_MEM_DEVICE)
@@ -424,10 +404,7 @@ def _fuse_np_deconvolution(sims, params, out_bb, sdims, input_dtype, fusion_func
                                   shrink_distance)
         rc = lib.mvs_blend_weights(device, C.byref(wview), ndim, s3, C.c_void_p(blend.ptr + 4 * i * S), _lib.MVS_MEM_DEVICE)
         _lib.check(rc, device, "mvs_blend_weights")
-    if not isinstance(trim_overlap_in_pixels, dict):
-        trim = [int(trim_overlap_in_pixels)] * ndim
-    else:
-        trim = [int(trim_overlap_in_pixels.get(d, 0)) for d in sdims]
+    trim = list(_trim_dict(trim_overlap_in_pixels, sdims).values())
     on_device = out is not None or output_on_backend
     res = mv_deconv._run(views_t, blend, ndim, kernels, kw.get("n_iterations", 10), kw.get("lambda_reg", 0.0),
                          kw.get("min_value", 1e-4), kw.get("sample_boundary_erosion_px", 0), trim, input_dtype, on_device, device,
@@ -491,10 +468,7 @@ def _fuse_np_with_callables(sims, params, output_properties, fusion_func, fusion
     weights_func_kwargs = dict(weights_func_kwargs or {})
     sdims = si_utils.get_spatial_dims_from_sim(sims[0])
     input_dtype = np.dtype(sims[0].dtype)
-    if spacings is None:
-        spacings = [fvb["spacing"] for fvb in full_view_bbs] if full_view_bbs is not None else [None] * len(sims)
-    if full_view_bbs is None:
-        full_view_bbs = [si_utils.get_stack_properties_from_sim(s) for s in sims]
+    spacings, full_view_bbs = _view_frames(sims, spacings, full_view_bbs)
     out_bb = _bb_dicts(output_properties, sdims)
 
     def host(a):
@@ -542,10 +516,7 @@ def _fuse_np_with_callables(sims, params, output_properties, fusion_func, fusion
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", category=RuntimeWarning)   # func_ignore_nan_warning (_core.py:1684-1687)
         fused = np.asarray(fusion_func(**fusion_func_kwargs))
-    if not isinstance(trim_overlap_in_pixels, dict):
-        trim = {d: int(trim_overlap_in_pixels) for d in sdims}
-    else:
-        trim = {d: int(trim_overlap_in_pixels.get(d, 0)) for d in sdims}
+    trim = _trim_dict(trim_overlap_in_pixels, sdims)
     if any(trim[d] > 0 for d in sdims):
         fused = fused[tuple(slice(trim[d], -trim[d]) if trim[d] > 0 else slice(None) for d in sdims)]
     fused = np.nan_to_num(fused).astype(input_dtype)

@@ -102,6 +102,34 @@ def shape3(shape):
     return [1] * (3 - len(shape)) + shape
 
 
+def view_data(data, device, dtype=None, wait=True):
+    """Where the C entries find a view's voxels: ``(pointer, 3D shape, 3D element strides, MVS_MEM_* code, array to keep
+    alive until the call is over)``.  A DeviceArray is used in place (``wait``: first brought to ``device`` and this lane's
+    stream made to wait for an upload still in flight); a host array is made C-contiguous, cast to ``dtype`` if one is given
+    and to float32 if its own is none of the kernels'.  2D data is a single z plane."""
+    from .device import is_device_array
+
+    if is_device_array(data):
+        if dtype is not None and data.dtype != dtype:
+            raise TypeError("all views of a chunk must share one dtype")
+        if wait:
+            data = data.on_device(device)     # a tile resident on another GPU: peer copy, cached per (tile, device)
+            data.wait_ready(device)           # a tile still on its way (device.to_device_async)
+        if data.dtype not in _lib.DTYPE_CODES:
+            raise TypeError(f"unsupported dtype {data.dtype}")
+        ptr, st, mem = data.ptr, [int(v) for v in data.strides], _lib.MVS_MEM_DEVICE
+    else:
+        data = np.ascontiguousarray(data, dtype=dtype)
+        if data.dtype not in _lib.DTYPE_CODES:
+            data = data.astype(np.float32)
+        st = [int(np.prod(data.shape[k + 1:])) for k in range(data.ndim)]   # C order; numpy's strides of size-1 axes are arbitrary
+        ptr, mem = data.ctypes.data, _lib.MVS_MEM_HOST
+    s3 = shape3(data.shape)
+    if len(st) == 2:
+        st = [st[0] * s3[1], st[0], st[1]]
+    return ptr, s3, st, mem, data
+
+
 def fill_view_geometry(view, data_ptr, dtype_code, mem, shape, strides_elems, matrix, offset):
     """Fill the data/geometry half of an ``mvs_view_t``."""
     m3, o3 = embed3(matrix, offset)
@@ -139,18 +167,8 @@ def resample_array(data, matrix, offset, output_shape, order=1, cval=0.0, device
     on_dev = is_device_array(data)
     if out_on_device is None:
         out_on_device = on_dev
-    if on_dev:
-        if data.dtype not in _lib.DTYPE_CODES:
-            raise TypeError(f"unsupported dtype {data.dtype}")
-        fill_view_geometry(view, data.ptr, _lib.DTYPE_CODES[data.dtype], _lib.MVS_MEM_DEVICE, data.shape, data.strides, matrix, offset)
-        keep = data
-    else:
-        data = np.ascontiguousarray(data)
-        if data.dtype not in _lib.DTYPE_CODES:
-            data = data.astype(np.float32)
-        strides = [int(np.prod(data.shape[k + 1:])) for k in range(data.ndim)]   # C order; size-1 axes have arbitrary numpy strides
-        fill_view_geometry(view, data.ctypes.data, _lib.DTYPE_CODES[data.dtype], _lib.MVS_MEM_HOST, data.shape, strides, matrix, offset)
-        keep = data
+    ptr, s3, st3, mem, keep = view_data(data, device, wait=False)
+    fill_view_geometry(view, ptr, _lib.DTYPE_CODES[keep.dtype], mem, s3, st3, matrix, offset)
     oshape = tuple(int(s) for s in output_shape)
     if out_on_device:
         out = DeviceArray.empty(oshape, np.float32, device)
