@@ -10,6 +10,7 @@
 //   quality = spearmanr(im0[mask], im1t[mask] - 1)                                  (scipy.stats)
 // Everything voxel-sized runs on the device; the host only sees counters, bounding boxes and sums.
 #include "mvs_internal.h"
+#include "mvs_prune_search.h"
 
 #include <cstring>
 
@@ -26,6 +27,7 @@ namespace {
 
 constexpr int kStatBlocks = 1024;    // workgroups (= partial results per candidate) of the statistics kernels
 constexpr int kMaxResident = 16;     // shifted copies of the moving image kept per batch of candidates
+static_assert(kMaxResident == kPruneMaxCand, "PruneSearch holds one batch");
 constexpr int kChunk = 8;            // outputs one thread produces along the filtered axis
 
 inline int grid_for(long long n) { return (int)std::min<long long>((n + 255) / 256, 256 * 8); }
@@ -605,12 +607,8 @@ __global__ __launch_bounds__(256) void ssim_yx_batch_kernel(YxBatch B, float* __
 // offset, so a sample costs no address arithmetic (the kernel is bound by the float64 filter arithmetic: ~300 of its ~580
 // vector instructions per plane are f64 adds / multiplies / conversions, all at 1/2 of the fp32 issue rate on gfx950).
 // A candidate is its shifted copy (dz = dy = dx = 0) or, for an integer shift, the moving crop itself read in place.
-// sel: the work items (tile x z segment, numbered x fastest) this launch walks for the candidate, as a set of residues of the
-// item number modulo 32 -- 0xffffffff: all of them; the pruned argmax search (mvs_score_candidates) scores a candidate in rounds
-// Residue r of group g (items g K .. g K + K - 1) is item g K + (r + kSelRot g) mod K: without the rotation a residue class of a crop with
-// 16 tiles per z segment (x neighbours: 256 x 256 x 51) is ONE tile row -- class 0 the row along the crop's border -- and the first
-// 1 / 32 of a candidate says little about the rest of it (a wrong leader is completed, the others are walked further than needed).
-constexpr int kSelRot = 7;
+// sel: the work items (WalkGeom, mvs_prune_search.h) this launch walks for the candidate, as a set of residues of the item number
+// modulo `selk` -- 0xffffffff: all of them; the pruned argmax search (PruneSearch) scores a candidate in rounds.
 struct FusedCand { const float* src; int dz, dy, dx; unsigned int sel; };
 struct FusedBatch { FusedCand c[kMaxResident]; };
 #ifndef MVS_SSIM_WPE_LO
@@ -626,7 +624,8 @@ __device__ __forceinline__ void ssim_fused_batch_body(const float* __restrict__ 
                                                                const float* __restrict__ ux, const float* __restrict__ uxx, int zseg,
                                                                float cov_norm, float C1, float C2, float* __restrict__ pmax,
                                                                int* __restrict__ phasnan, double* __restrict__ psum, int selk) {
-    constexpr int H = WIN / 2, pad = (WIN - 1) / 2, TY = 16, TX = 56, LY = TY + 2 * H, LX = TX + 2 * H;
+    typedef WalkGeom<WIN> G;
+    constexpr int H = G::H, pad = G::PAD, TY = G::TY, TX = G::TX, LY = TY + 2 * H, LX = TX + 2 * H;
     constexpr int NO = 4, NI = NO + 2 * H;           // outputs / inputs of one y- or x-pass item
     constexpr int NR = (LY + 3) / 4;                 // patch rows per thread: row = (tid >> 6) + 4 k, column = tid & 63
     typedef typename std::conditional<F32, float, double>::type run_t;
@@ -647,19 +646,18 @@ __device__ __forceinline__ void ssim_fused_batch_body(const float* __restrict__ 
     const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc((void*)im0, 0, (int)vol_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc((void*)C.src, 0, (int)vol_bytes, 0x00020000);
     if (cz > 0 && cy > 0 && cx > 0) {
-        const int nty = (cy + TY - 1) / TY, ntx = (cx + TX - 1) / TX, nzs = (cz + zseg - 1) / zseg;
-        const int nitems = nty * ntx * nzs;
+        const G g(S.nz, S.ny, S.nx, zseg);
+        const int nitems = g.nitems;
         const int sy = S.nx, sz = S.ny * S.nx;
         const int nsel = ((nitems + selk - 1) / selk) * nselres;             // selected items: residue k of group g is number g * nselres + k
         for (int si = blockIdx.x; si < nsel; si += gridDim.x) {
             unsigned int rest = C.sel;
             for (int k = si % nselres; k > 0; --k) rest &= rest - 1;  // (uniform: scalar work)
             const int grp = si / nselres;
-            const int item = grp * selk + (__ffs(rest) - 1 + kSelRot * grp) % selk;      // (residue rotated per group: see kSelRot)
+            const int item = G::group_first(grp, selk) + G::rotated(__ffs(rest) - 1, grp, selk);      // == G::item_of(grp, residue, selk)
             if (item >= nitems) continue;
-            const int tx = item % ntx, ty = (item / ntx) % nty, zs = item / (ntx * nty);
-            const int z0 = pad + zs * zseg, z1 = min(z0 + zseg, S.nz - pad);
-            const int y0 = pad + ty * TY, x0 = pad + tx * TX;
+            const WalkItem w = g.item(item);
+            const int z0 = w.z0, z1 = w.z1, y0 = w.y0, x0 = w.x0;
             const int gx = min(x0 - H + col, S.nx - 1);          // (clamped duplicates feed outputs that are never used)
             const bool xin = (unsigned)(gx + C.dx) < (unsigned)S.nx;
             // byte offsets of this thread's pixels inside a plane of im0 / the candidate; the plane itself is a scalar offset
@@ -824,7 +822,8 @@ void ssim_fused_batch_f32_kernel(const float* __restrict__ im0, Shape3 S, FusedB
 template <int WIN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8)))
 void ssim_fixed_walk_kernel(const float* __restrict__ im0, Shape3 S, float* __restrict__ ux, float* __restrict__ uxx, int zseg) {
-    constexpr int H = WIN / 2, pad = (WIN - 1) / 2, TY = 16, TX = 56, LY = TY + 2 * H, LX = TX + 2 * H;
+    typedef WalkGeom<WIN> G;
+    constexpr int H = G::H, pad = G::PAD, TY = G::TY, TX = G::TX, LY = TY + 2 * H, LX = TX + 2 * H;
     constexpr int NO = 4, NI = NO + 2 * H;
     constexpr int NR = (LY + 3) / 4;
     constexpr double inv = 1.0 / (double)WIN;
@@ -832,17 +831,14 @@ void ssim_fixed_walk_kernel(const float* __restrict__ im0, Shape3 S, float* __re
     __shared__ float sz_[2][LY][LX + 1];
     __shared__ float sy_[2][TY][LX + 1];
     const int tid = threadIdx.x, col = tid & 63, wrow = tid >> 6;
-    const int cz = S.nz - 2 * pad, cy = S.ny - 2 * pad, cx = S.nx - 2 * pad;
-    if (cz <= 0 || cy <= 0 || cx <= 0) return;
+    if (G::crop(S.nz) <= 0 || G::crop(S.ny) <= 0 || G::crop(S.nx) <= 0) return;
     const long long vol_bytes = (long long)S.nz * S.ny * S.nx * 4;      // < 2^31 (checked by the host)
     const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc((void*)im0, 0, (int)vol_bytes, 0x00020000);
-    const int nty = (cy + TY - 1) / TY, ntx = (cx + TX - 1) / TX, nzs = (cz + zseg - 1) / zseg;
-    const int nitems = nty * ntx * nzs;
+    const G g(S.nz, S.ny, S.nx, zseg);
     const int sy = S.nx, sz = S.ny * S.nx;
-    for (int item = blockIdx.x; item < nitems; item += gridDim.x) {
-        const int tx = item % ntx, ty = (item / ntx) % nty, zs = item / (ntx * nty);
-        const int z0 = pad + zs * zseg, z1 = min(z0 + zseg, S.nz - pad);
-        const int y0 = pad + ty * TY, x0 = pad + tx * TX;
+    for (int item = blockIdx.x; item < g.nitems; item += gridDim.x) {
+        const WalkItem w = g.item(item);
+        const int z0 = w.z0, z1 = w.z1, y0 = w.y0, x0 = w.x0;
         const int gx = min(x0 - H + col, S.nx - 1);          // (clamped duplicates feed outputs that are never used)
         int v0[NR];
 #pragma unroll
@@ -1325,6 +1321,8 @@ struct DeviceBump {   // bump allocator over one scratch slot
     }
 };
 
+typedef WalkGeom<7> Walk7;      // the fused walk exists for the 7-wide window only
+
 // The fixed image's own terms (mean of x and of x * x over the window) of a 3D pair whose SSIM region is the whole volume for
 // every candidate: z pass + y/x pass once, results in setB[2], setB[3] (shared_x of launch_ssim_passes).
 template <int WIN>
@@ -1336,9 +1334,8 @@ void launch_ssim_shared_x(hipStream_t stream, const float* im0, Shape3 S, Shape3
     P2.dst[2] = setB[3];
     if (walk && WIN == 7 && R.nz == S.nz && R.ny == S.ny && R.nx == S.nx) {
         // one launch: z walk per (y, x) tile, about one resident round of work items
-        const int tiles = ((S.ny - 6 + 15) / 16) * ((S.nx - 6 + 55) / 56), cz = S.nz - 6;
-        const int nzs = std::max(1, std::min(768 / std::max(tiles, 1), (cz + 7) / 8));
-        MVS_DUP("ssim_fixed", hipLaunchKernelGGL(ssim_fixed_walk_kernel<7>, dim3(kStatBlocks), dim3(256), 0, stream, im0, S, setB[2], setB[3], (cz + nzs - 1) / nzs));
+        MVS_DUP("ssim_fixed", hipLaunchKernelGGL(ssim_fixed_walk_kernel<7>, dim3(kStatBlocks), dim3(256), 0, stream, im0, S, setB[2], setB[3],
+                                                Walk7::zseg_for(S.nz, S.ny, S.nx, 768)));
         return;
     }
     hipLaunchKernelGGL((ssim_first_pass_kernel<WIN, false, 1>), dim3(kStatBlocks), dim3(256), 0, stream, im0, im0, S, 0, 0, 0, R, 0, P1, pmax, phasnan,
@@ -1381,6 +1378,628 @@ void launch_ssim_passes(hipStream_t stream, const float* im0, const float* im1t,
     hipLaunchKernelGGL(ssim_last_pass_kernel<WIN>, dim3(kStatBlocks), dim3(256), 0, stream, P3, R, ndim, cov_norm, C1, C2, psum);
 }
 
+// ---- mvs_score_candidates as a sequence of steps over the state of one call ---------------------------------------------------
+// In 3D the phase correlation refines to half pixels, so the candidates of a pair -- t, -t, -(t - N), -t - N per axis -- share the
+// fractional part of their shift per axis, and every candidate image is an INTEGER shift of one "fraction-only" shifted copy of the
+// moving image (same taps, weights and order: c = o + t is exact in double).  One copy per fraction class instead of one per
+// candidate; the fused SSIM walk reads it at o + floor(t) exactly as it reads the moving image itself for integer shifts.
+constexpr int kMaxCls = 4;      // fraction classes of half-pixel shifts that get ONE shifted copy shared by their candidates
+struct ClsBuf { int key; float* buf; };
+
+struct ScoreCall {
+    MvsContext* c;
+    const MvsScoreOpts* so;
+    int device;
+    // the arguments of the call
+    Shape3 S;
+    long long n;
+    int ndim, k0, region_mode, quality_for_all;
+    double data_range, im1_min;
+    const double* t_candidates;
+    double *ssim_out, *spearman_out;
+    int32_t* code_out;
+    float *im0, *im1;                       // the staged crops
+    int nres, gb;                           // candidates per batch; grid of the voxel-wise kernels
+    // scratch (layout_scratch)
+    float *im1t_buf[kMaxResident], *setA[5], *setB[5], *cand3[3 * kMaxResident];
+    ClsBuf cls[kMaxCls];
+    int n_cls;
+    void* sort_temp;
+    size_t sort_temp_bytes;
+    VoxStats* vox_partial;
+    float* pmax;
+    int* phasnan;
+    double* psum;
+    unsigned int *d_hist, *d_parts, *d_counter;      // key histograms of the rank correlation, per-workgroup packed ones; compaction counter
+    float* d_rank;
+    // results the host reads (reduction partials of the rank correlation, voxel and region statistics) are written by the kernels
+    // straight into the context's mailbox (pinned host memory): no copy launches.  Device views and host views of the same cells:
+    double* partial;
+    VoxStats* vox_out;
+    RegionStats* reg_out;
+    const double* h_partial;
+    const VoxStats* h_vox;
+    const RegionStats* h_reg;
+    // the pair (image_boxes)
+    VoxStats h_im[2];                       // valid voxels and their box: fixed, moving
+    unsigned int valid1;
+    int im0_all_finite, im1_all_finite;
+    bool on_the_fly, may_batch, shared_x;
+    float C1, C2;
+    std::vector<unsigned long long> cnts;   // jointly valid voxels per candidate
+    std::vector<int> resident;              // buffer holding the candidate's im1t, if still there
+
+    void shift_of(int ic, double t[3]) const {
+        t[0] = t[1] = t[2] = 0.0;
+        for (int k = 0; k < ndim; ++k) t[k0 + k] = t_candidates[ic * ndim + k];
+    }
+};
+
+// one batch of candidates that passed the analytic pre-test (at most nres: their shifted copies stay resident)
+struct ScoreBatch {
+    int nb;
+    const int* ics;                         // candidate numbers
+    bool batched;                           // the 7-wide whole-volume candidates of this batch share their launches
+    // phase A
+    VoxStats h_vs[kMaxResident];
+    ShiftArg shifts[kMaxResident];
+    bool otf[kMaxResident];                 // integer shift of finite crops: read in place, never materialised
+    int cls_of[kMaxResident];               // fraction class whose copy the candidate reads (-1: its own copy / the moving image)
+    // phase B
+    Shape3 Rs[kMaxResident];
+    bool scored[kMaxResident];
+    FirstBatch first;
+    YxBatch yx;
+    FusedBatch fused;
+    bool any_batched;
+    float cov_norm;
+    RegionStats h_rs[kMaxResident];
+};
+
+// The scratch request and its layout, term by term.  The terms marked (mailbox) have no take -- those results are written to the
+// mailbox -- and stay in the request as headroom, so that the size of the slot does not depend on where the results go.
+int layout_scratch(ScoreCall& sc) {
+    MvsContext* c = sc.c;
+    const size_t n = (size_t)sc.n;
+    const int nres = sc.nres, gb = sc.gb;
+    const bool may_batch = sc.may_batch;
+    const size_t stat_bytes = (size_t)(kMaxResident + 2) * kStatBlocks * (sizeof(VoxStats) + 4 + 4 + 8)      // vox_partial, pmax, phasnan, psum
+                              + (kMaxResident + 2) * 64;                                                     // (mailbox: vox_out, reg_out)
+    const size_t need = n * 4 * (10 + nres + (may_batch ? 3 * nres + kMaxCls : 0))      // setA, setB; im1t_buf; cand3, cls
+                        + 256 * (12 + 4 * nres + kMaxCls)                                // alignment of those and of the takes below
+                        + sc.sort_temp_bytes                                             // sort_temp
+                        + (size_t)gb * 32                                                // (mailbox: partial)
+                        + stat_bytes + 64 * 1024
+                        + (size_t)(kHistBinsMax + 64) * 8                                // d_hist, d_rank
+                        + (size_t)kHistParts * (kHistBinsMax / 2 + 1) * 4                // d_parts
+                        + 2048;                                                          // d_counter
+    char* base = (char*)mvs_scratch(c, 6, need);
+    if (!base) return mvs_alloc_failed(c);
+    DeviceBump B{base, need, 0};
+    for (int i = 0; i < nres; ++i) sc.im1t_buf[i] = B.take<float>(n);
+    for (int a = 0; a < 5; ++a) sc.setA[a] = B.take<float>(n);
+    for (int a = 0; a < 5; ++a) sc.setB[a] = B.take<float>(n);
+    for (int i = 0; i < (may_batch ? 3 * nres : 0); ++i) sc.cand3[i] = B.take<float>(n);
+    sc.n_cls = 0;
+    for (int k = 0; k < kMaxCls; ++k) sc.cls[k] = ClsBuf{-1, may_batch ? B.take<float>(n) : nullptr};
+    sc.sort_temp = B.take<char>(sc.sort_temp_bytes);
+    sc.vox_partial = B.take<VoxStats>((size_t)(kMaxResident + 2) * kStatBlocks);
+    sc.pmax = B.take<float>((size_t)kMaxResident * kStatBlocks);
+    sc.phasnan = B.take<int>((size_t)kMaxResident * kStatBlocks);
+    sc.psum = B.take<double>((size_t)kMaxResident * kStatBlocks);
+    sc.d_hist = B.take<unsigned int>((size_t)kHistBinsMax + 64);
+    sc.d_rank = B.take<float>((size_t)kHistBinsMax + 64);
+    sc.d_parts = B.take<unsigned int>((size_t)kHistParts * (kHistBinsMax / 2 + 1));
+    sc.d_counter = B.take<unsigned int>(64);
+    if (!sc.d_counter) return mvs_fail(c, MVS_ERR_HIP, "mvs_score_candidates: scratch layout");
+
+    const size_t mb_partial = 0, mb_vox = align_up((size_t)gb * 4 * sizeof(double));
+    const size_t mb_reg = mb_vox + align_up((size_t)(kMaxResident + 2) * sizeof(VoxStats));
+    void *mb_host = nullptr, *mb_dev = nullptr;
+    const int rcm = mvs_mailbox(c, mb_reg + (size_t)kMaxResident * sizeof(RegionStats), &mb_host, &mb_dev);
+    if (rcm) return rcm;
+    sc.partial = (double*)((char*)mb_dev + mb_partial);
+    sc.vox_out = (VoxStats*)((char*)mb_dev + mb_vox);
+    sc.reg_out = (RegionStats*)((char*)mb_dev + mb_reg);
+    sc.h_partial = (const double*)((const char*)mb_host + mb_partial);
+    sc.h_vox = (const VoxStats*)((const char*)mb_host + mb_vox);
+    sc.h_reg = (const RegionStats*)((const char*)mb_host + mb_reg);
+    return MVS_OK;
+}
+
+// valid voxels of im1 and the bboxes of both images (registration.py:400, 491)
+int image_boxes(ScoreCall& sc) {
+    MvsContext* c = sc.c;
+    const Shape3 S = sc.S;
+    if (sc.so->both_crops_finite) {
+        // the caller (mvs_register_crops) has just reduced both images and found neither NaN nor inf: every voxel is valid,
+        // the boxes are the whole volume -- no reduction, no host round trip
+        for (int k = 0; k < 2; ++k) {
+            sc.h_im[k].cnt = (unsigned long long)sc.n;
+            sc.h_im[k].bb[0] = sc.h_im[k].bb[1] = sc.h_im[k].bb[2] = 0;
+            sc.h_im[k].bb[3] = S.nz - 1; sc.h_im[k].bb[4] = S.ny - 1; sc.h_im[k].bb[5] = S.nx - 1;
+        }
+    } else {
+        hipLaunchKernelGGL(image_stats_kernel, dim3(kStatBlocks), dim3(256), 0, c->stream, sc.im0, S, sc.vox_partial);
+        hipLaunchKernelGGL(image_stats_kernel, dim3(kStatBlocks), dim3(256), 0, c->stream, sc.im1, S, sc.vox_partial + kStatBlocks);
+        hipLaunchKernelGGL(finish_voxstats_kernel, dim3(2), dim3(256), 0, c->stream, sc.vox_partial, sc.vox_out);
+        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        sc.h_im[0] = sc.h_vox[0];
+        sc.h_im[1] = sc.h_vox[1];
+    }
+    sc.valid1 = (unsigned int)(sc.h_im[1].cnt & 0xffffffffull);
+    // every voxel of the moving image finite?  (lower half: #non-NaN, upper half: #inf, see image_stats_kernel)
+    sc.im1_all_finite = ((long long)sc.valid1 == sc.n && (sc.h_im[1].cnt >> 32) == 0) ? 1 : 0;
+    sc.im0_all_finite = ((long long)(sc.h_im[0].cnt & 0xffffffffull) == sc.n && (sc.h_im[0].cnt >> 32) == 0) ? 1 : 0;
+    // Both crops finite (tiles on a common grid): the valid box of a shifted copy and with it the mask count are known
+    // without touching the volume -- x is valid iff 0 <= fl(x + t) <= n - 1 per axis -- so the reduction of phase A and its
+    // host round trip are skipped, and candidates with integer shifts are never materialised: the SSIM z pass reads the
+    // moving image at the shifted position (the winner's copy is written afterwards, for the rank correlation).
+    sc.on_the_fly = !sc.quality_for_all && sc.im0_all_finite && sc.im1_all_finite && !c->materialize_shifts;
+    return MVS_OK;
+}
+
+// analytic pre-test: upper bound of the mask count from the valid bounding boxes -- im1t can only be valid
+// where x + t lies in im1's valid box.  If even the bound fails the 10 % test the candidate is rejected
+// exactly as the reference rejects it (registration.py:503-505) without touching the volume.
+bool passes_pretest(const ScoreCall& sc, const double t[3]) {
+    const int *bb0 = sc.h_im[0].bb, *bbm = sc.h_im[1].bb;
+    const int dimv[3] = {sc.S.nz, sc.S.ny, sc.S.nx};
+    double bound = 1.0;
+    for (int k = 0; k < 3; ++k) {
+        const double lo1 = std::ceil((double)bbm[k] - t[k] - 1.0), hi1 = std::floor((double)bbm[3 + k] - t[k] + 1.0);
+        const double lo = std::max(std::max(lo1, (double)bb0[k]), 0.0);
+        const double hi = std::min(std::min(hi1, (double)bb0[3 + k]), (double)(dimv[k] - 1));
+        bound *= std::max(hi - lo + 1.0, 0.0);
+    }
+    return !(sc.valid1 == 0 || bound == 0.0 || bound / (double)sc.valid1 < 0.1);
+}
+
+// The valid box and voxel count of the copy of a finite image shifted by t: the predicate of axis_tap, evaluated on the host in
+// the same double arithmetic (first and last valid index per axis).
+VoxStats valid_box(Shape3 S, const double t[3]) {
+    const int dims[3] = {S.nz, S.ny, S.nx};
+    VoxStats vs;
+    vs.cnt = 1;
+    for (int k = 0; k < 3; ++k) {
+        auto ok = [&](long long x) { const double cc = (double)x + t[k]; return !(cc < 0.0 || cc > (double)(dims[k] - 1)); };
+        long long lo = (long long)std::ceil(-t[k]), hi = (long long)std::floor((double)(dims[k] - 1) - t[k]);
+        lo = std::min<long long>(std::max<long long>(lo, 0), dims[k]);
+        hi = std::max<long long>(std::min<long long>(hi, dims[k] - 1), -1);
+        while (lo > 0 && ok(lo - 1)) --lo;
+        while (lo < dims[k] && !ok(lo)) ++lo;
+        while (hi < dims[k] - 1 && ok(hi + 1)) ++hi;
+        while (hi >= 0 && !ok(hi)) --hi;
+        vs.bb[k] = (int)lo;
+        vs.bb[3 + k] = (int)hi;
+        vs.cnt *= (unsigned long long)std::max<long long>(hi - lo + 1, 0);
+    }
+    return vs;
+}
+
+// every component a multiple of 1/2 (and small): *H = floor and fraction bit per axis
+bool half_shift(const double t[3], HalfShift* H) {
+    int f[3], h[3];
+    for (int k = 0; k < 3; ++k) {
+        const double t2 = t[k] * 2.0;
+        if (!(std::floor(t2) == t2 && std::fabs(t[k]) < 1e6)) return false;
+        f[k] = (int)std::floor(t[k]);
+        h[k] = (t[k] != std::floor(t[k])) ? 1 : 0;
+    }
+    *H = HalfShift{f[0], f[1], f[2], h[0], h[1], h[2]};
+    return true;
+}
+
+// slot of the fraction class of a half-pixel shift (bit k of the key: axis k has the fraction 1/2), -1 when the candidate keeps a
+// copy of its own (integer shift, no slot left, mode off); *fresh: the class copy still has to be written
+int share_cls(ScoreCall& sc, const HalfShift& H, bool* fresh) {
+    *fresh = false;
+    if (!sc.may_batch || !sc.im1_all_finite || sc.c->materialize_shifts || sc.c->ssim_two_pass) return -1;
+    const int key = H.hz | (H.hy << 1) | (H.hx << 2);
+    if (key == 0) return -1;
+    for (int q = 0; q < sc.n_cls; ++q)
+        if (sc.cls[q].key == key) return q;
+    if (sc.n_cls == kMaxCls) return -1;
+    sc.cls[sc.n_cls].key = key;
+    *fresh = true;
+    return sc.n_cls++;
+}
+
+// candidate j's own shifted copy (with the statistics of phase A) into its batch buffer
+void launch_shift_copy(ScoreCall& sc, const ScoreBatch& b, int j) {
+    hipLaunchKernelGGL(shift_kernel, dim3(kStatBlocks), dim3(256), 0, sc.c->stream, sc.im1, sc.im0, sc.im1t_buf[j], sc.S, b.shifts[j].tz, b.shifts[j].ty,
+                       b.shifts[j].tx, sc.im1_all_finite, sc.vox_partial + (size_t)j * kStatBlocks);
+    sc.resident[b.ics[j]] = j;
+}
+
+// ---- phase A: shifted copies + mask counts / bboxes of the whole batch ----
+int phase_a(ScoreCall& sc, ScoreBatch& b) {
+    MvsContext* c = sc.c;
+    ShiftBatch shift_batch;
+    int n_shift_batch = 0;
+    for (int j = 0; j < kMaxResident; ++j) { b.otf[j] = false; b.cls_of[j] = -1; }
+    for (int j = 0; j < b.nb; ++j) {
+        double t[3];
+        sc.shift_of(b.ics[j], t);
+        b.shifts[j] = ShiftArg{t[0], t[1], t[2], sc.im1_all_finite};
+        if (sc.on_the_fly) {
+            b.h_vs[j] = valid_box(sc.S, t);
+            // integer shifts: one tap of weight 1 per voxel -- the z pass reads the moving image directly.  Fractional
+            // shifts keep their shifted copy (its 2-8 double-precision taps per voxel would be re-evaluated 1.75 times
+            // by the windowed z pass), but nobody waits for its statistics.
+            b.otf[j] = t[0] == std::floor(t[0]) && t[1] == std::floor(t[1]) && t[2] == std::floor(t[2]);
+            if (b.otf[j]) continue;
+            if (b.batched) {      // all fractional shifts of the batch in one launch, after this loop
+                HalfShift H;
+                const bool half = half_shift(t, &H);
+                bool fresh = false;
+                const int q = half ? share_cls(sc, H, &fresh) : -1;
+                if (q >= 0) {
+                    b.cls_of[j] = q;
+                    if (fresh)      // the class copy: the fraction-only shift, through the same launch as the other copies
+                        shift_batch.c[n_shift_batch++] = ShiftCand{sc.cls[q].buf, 0.5 * H.hz, 0.5 * H.hy, 0.5 * H.hx, 1, HalfShift{0, 0, 0, H.hz, H.hy, H.hx}};
+                    continue;
+                }
+                shift_batch.c[n_shift_batch++] = half ? ShiftCand{sc.im1t_buf[j], t[0], t[1], t[2], 1, H}
+                                                      : ShiftCand{sc.im1t_buf[j], t[0], t[1], t[2], 0, HalfShift{0, 0, 0, 0, 0, 0}};
+                sc.resident[b.ics[j]] = j;
+                continue;
+            }
+        }
+        launch_shift_copy(sc, b, j);
+    }
+    if (n_shift_batch)
+        MVS_DUP("shift", hipLaunchKernelGGL(shift_batch_kernel, dim3(kStatBlocks, n_shift_batch), dim3(256), 0, c->stream, sc.im1, sc.im0, sc.S, shift_batch, sc.im1_all_finite));
+    if (!sc.on_the_fly) {
+        hipLaunchKernelGGL(finish_voxstats_kernel, dim3(b.nb), dim3(256), 0, c->stream, sc.vox_partial, sc.vox_out);
+        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (int j = 0; j < b.nb; ++j) b.h_vs[j] = sc.h_vox[j];
+    }
+    return MVS_OK;
+}
+
+// window of a region: skimage's default 7, narrower (odd) for a region with a shorter axis; below 3 there is no SSIM
+int ssim_window(const ScoreCall& sc, Shape3 R) {
+    int min_shape = 0x7fffffff;
+    for (int k = sc.k0; k < 3; ++k) min_shape = std::min(min_shape, (&R.nz)[k]);
+    return std::min(7, min_shape - ((min_shape - 1) % 2));
+}
+
+// ---- phase B: SSIM passes of every candidate that keeps enough jointly valid voxels ----
+// A candidate with the 7-wide window over the whole volume joins the launches its batch shares (when the batch has them), one
+// on its own takes the passes of its window -- with the fixed image's shared terms when the pair has them.
+void phase_b(ScoreCall& sc, ScoreBatch& b) {
+    MvsContext* c = sc.c;
+    const Shape3 S = sc.S;
+    const int* bb0 = sc.h_im[0].bb;
+    b.any_batched = false;
+    b.cov_norm = 0.f;
+    for (int j = 0; j < kMaxResident; ++j) {
+        b.first.c[j] = FirstCand{nullptr, nullptr, nullptr, nullptr, ShiftArg{0.0, 0.0, 0.0, 0}, 0};
+        b.yx.c[j] = YxCand{nullptr, nullptr, nullptr};
+        b.fused.c[j] = FusedCand{nullptr, 0, 0, 0, 0xffffffffu};
+        b.scored[j] = false;
+        b.Rs[j] = {0, 0, 0};
+    }
+    for (int j = 0; j < b.nb; ++j) {
+        const int ic = b.ics[j];
+        const unsigned long long cnt = b.h_vs[j].cnt;
+        const int* bb1 = b.h_vs[j].bb;
+        sc.cnts[ic] = cnt;
+        if (cnt == 0 || (double)cnt / (double)sc.valid1 < 0.1) {   // registration.py:503-505
+            sc.code_out[ic] = 1;
+            continue;
+        }
+        // region slices (registration.py:509-528)
+        int lo[3], hi[3];
+        for (int k = 0; k < 3; ++k) {
+            if (sc.region_mode == 0) { lo[k] = std::min(bb0[k], bb1[k]); hi[k] = std::max(bb0[3 + k], bb1[3 + k]) + 1; }
+            else { lo[k] = std::max(bb0[k], bb1[k]); hi[k] = std::min(bb0[3 + k], bb1[3 + k]) + 1; }
+        }
+        const Shape3 R = {std::max(hi[0] - lo[0], 0), std::max(hi[1] - lo[1], 0), std::max(hi[2] - lo[2], 0)};
+        b.Rs[j] = R;
+        if ((long long)R.nz * R.ny * R.nx <= 0) continue;
+        const int win = std::max(ssim_window(sc, R), 3);   // below 3 SSIM is -1 (decode_results); the pass still yields the region statistics
+        double NP = 1.0;
+        for (int k = 0; k < sc.ndim; ++k) NP *= (double)win;
+        const float cov_norm = (float)(NP / (NP - 1.0));
+        float* pm = sc.pmax + (size_t)j * kStatBlocks;
+        int* ph = sc.phasnan + (size_t)j * kStatBlocks;
+        double* ps = sc.psum + (size_t)j * kStatBlocks;
+        const bool full = R.nz == S.nz && R.ny == S.ny && R.nx == S.nx;
+        const bool joins = b.batched && win == 7 && full;
+        if (b.cls_of[j] >= 0 && !joins) {
+            // (a candidate that reads a class copy has finite crops and a whole-volume region of 7 or more per axis: it joins.  Should
+            // that ever change, it gets its own copy like any other candidate)
+            launch_shift_copy(sc, b, j);
+            b.cls_of[j] = -1;
+        }
+        const float* second = b.otf[j] ? sc.im1 : sc.im1t_buf[j];
+        const ShiftArg* sa = b.otf[j] ? &b.shifts[j] : nullptr;
+        if (joins) {
+            float* d1 = sc.cand3[(size_t)3 * j], *d3 = sc.cand3[(size_t)3 * j + 1], *d4 = sc.cand3[(size_t)3 * j + 2];
+            const ShiftArg& T = b.shifts[j];
+            b.first.c[j] = FirstCand{second, d1, d3, d4, T, b.otf[j] ? 1 : 0};
+            b.yx.c[j] = YxCand{d1, d3, d4};
+            b.fused.c[j] = b.otf[j] ? FusedCand{sc.im1, (int)T.tz, (int)T.ty, (int)T.tx, 0xffffffffu}
+                           : b.cls_of[j] >= 0 ? FusedCand{sc.cls[b.cls_of[j]].buf, (int)std::floor(T.tz), (int)std::floor(T.ty), (int)std::floor(T.tx), 0xffffffffu}
+                                              : FusedCand{sc.im1t_buf[j], 0, 0, 0, 0xffffffffu};
+            b.any_batched = true;
+            b.cov_norm = cov_norm;
+        }
+        else if (win == 7) launch_ssim_passes<7>(c->stream, sc.im0, second, S, lo, R, sc.ndim, sc.setA, sc.setB, cov_norm, sc.C1, sc.C2, pm, ph, ps, sa, sc.shared_x && full);
+        else if (win == 5) launch_ssim_passes<5>(c->stream, sc.im0, second, S, lo, R, sc.ndim, sc.setA, sc.setB, cov_norm, sc.C1, sc.C2, pm, ph, ps, sa);
+        else launch_ssim_passes<3>(c->stream, sc.im0, second, S, lo, R, sc.ndim, sc.setA, sc.setB, cov_norm, sc.C1, sc.C2, pm, ph, ps, sa);
+        b.scored[j] = true;
+    }
+}
+
+// every batched candidate in full, one launch
+void score_full(ScoreCall& sc, ScoreBatch& b, int n_in) {
+    MvsContext* c = sc.c;
+    const Shape3 S = sc.S;
+    // ~1536 workgroups (two resident rounds of 3 per CU): 243 instead of 282 us per pair with 768 -- a workgroup spends its
+    // time waiting (two barriers and a load round trip per plane), so a second round hides more than its 6 halo planes cost
+    MVS_DUP("ssim_fused", hipLaunchKernelGGL(ssim_fused_batch_kernel<7>, dim3(kStatBlocks, b.nb), dim3(256), 0, c->stream, sc.im0, S, b.fused, sc.setB[2], sc.setB[3],
+                       Walk7::zseg_for(S.nz, S.ny, S.nx, 1536, b.nb), b.cov_norm, sc.C1, sc.C2, sc.pmax, sc.phasnan, sc.psum, 32));
+    c->reg_cand_volumes += (double)n_in;
+}
+
+// the separate z and y / x launches for the batch (test switch ssim_two_pass)
+void score_two_pass(ScoreCall& sc, ScoreBatch& b) {
+    MvsContext* c = sc.c;
+    hipLaunchKernelGGL(ssim_first_pass_batch_kernel<7>, dim3(kStatBlocks, b.nb), dim3(256), 0, c->stream, sc.im0, sc.S, b.first, sc.pmax, sc.phasnan);
+    hipLaunchKernelGGL(ssim_yx_batch_kernel<7>, dim3(kStatBlocks, b.nb), dim3(256), 0, c->stream, b.yx, sc.setB[2], sc.setB[3], sc.S, b.cov_norm, sc.C1, sc.C2, sc.psum);
+}
+
+// the environment switches of the pruned search, read once
+struct PruneEnv { int target_items, K; bool debug; };
+const PruneEnv& prune_env() {
+    static const PruneEnv env = [] {
+        const char* items = getenv("MVS_SSIM_PRUNE_ITEMS");        // work items a candidate's walk is cut into (about)
+        // residue classes of the work items (a candidate's volume is walked in K-ths): 32 (measured against 16: 2.60 instead of
+        // 2.84 candidate volumes per pair on the bench mosaic); MVS_SSIM_PRUNE_CLASSES=16 for the A/B
+        const char* classes = getenv("MVS_SSIM_PRUNE_CLASSES");
+        return PruneEnv{(items && atoi(items) > 0) ? atoi(items) : 320, (classes && atoi(classes) == 16) ? 16 : 32, getenv("MVS_PRUNE_DEBUG") != nullptr};
+    }();
+    return env;
+}
+
+// one round of the pruned search: candidate j walks the residue classes masks[j]; the sums, maxima and flags of the round land
+// in sc.h_reg
+int run_round(ScoreCall& sc, const ScoreBatch& b, const Walk7& g, int K, const unsigned int* masks, bool f32) {
+    MvsContext* c = sc.c;
+    FusedBatch fb = b.fused;
+    int maxsel = 0;
+    for (int j = 0; j < b.nb; ++j) {
+        fb.c[j].sel = masks[j];
+        if (!masks[j]) { fb.c[j].src = nullptr; continue; }
+        maxsel = std::max(maxsel, ((g.nitems + K - 1) / K) * __builtin_popcount(masks[j]));
+    }
+    const int gx = std::min(kStatBlocks, maxsel);
+    // (117 VGPRs at 3-4 waves per SIMD; forced to 5 waves it spills: pairwise 38.9 -> 43.2 ms, measured)
+    if (f32)
+        MVS_DUP("ssim_fused", hipLaunchKernelGGL(ssim_fused_batch_f32_kernel<7>, dim3(gx, b.nb), dim3(256), 0, c->stream, sc.im0, sc.S, fb, sc.setB[2], sc.setB[3], g.zseg,
+                           b.cov_norm, sc.C1, sc.C2, sc.pmax, sc.phasnan, sc.psum, K));
+    else
+        MVS_DUP("ssim_fused", hipLaunchKernelGGL(ssim_fused_batch_kernel<7>, dim3(gx, b.nb), dim3(256), 0, c->stream, sc.im0, sc.S, fb, sc.setB[2], sc.setB[3], g.zseg,
+                           b.cov_norm, sc.C1, sc.C2, sc.pmax, sc.phasnan, sc.psum, K));
+    MVS_DUP("finish", hipLaunchKernelGGL(finish_region_kernel, dim3(b.nb), dim3(256), 0, c->stream, sc.pmax, sc.phasnan, sc.psum, sc.reg_out, gx));
+    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MVS_OK;
+}
+
+// pruned arg-max search (the caller needs the arg-max candidate only: mvs_register_crops): PruneSearch (mvs_prune_search.h)
+// decides, this function walks.  Fills b.h_rs.
+int score_pruned(ScoreCall& sc, ScoreBatch& b, double slack) {
+    MvsContext* c = sc.c;
+    const Shape3 S = sc.S;
+    const PruneEnv& env = prune_env();
+    const Walk7 g(S.nz, S.ny, S.nx, Walk7::zseg_for(S.nz, S.ny, S.nx, env.target_items));
+    double vol_res[32];
+    prune_residue_volumes(g, env.K, vol_res);
+    const double Ntot = (double)g.cz * (double)g.cy * (double)g.cx;
+    bool in[kMaxResident];
+    for (int j = 0; j < kMaxResident; ++j) in[j] = b.fused.c[j].src != nullptr;
+    // float32 walk (option ssim_f32, default on) + float64 re-walk of the candidates that end within the margin of the best
+    const bool walk_f32 = c->ssim_f32;
+    PruneSearch search(b.nb, in, env.K, vol_res, Ntot, slack, walk_f32 ? kPruneMarginF32 : 0.0, sc.im1_min);
+    unsigned int masks[kMaxResident];
+    while (search.next_round(masks)) {
+        if (search.rewalk())
+            for (int j = 0; j < b.nb; ++j)
+                if (masks[j]) { c->reg_rewalks += 1; c->reg_cand_volumes += 1.0; }
+        const int rc = run_round(sc, b, g, env.K, masks, walk_f32 && !search.rewalk());
+        if (rc) return rc;
+        double sum[kMaxResident];
+        float mx[kMaxResident];
+        int hasnan[kMaxResident];
+        for (int j = 0; j < b.nb; ++j) { sum[j] = sc.h_reg[j].ssim_sum; mx[j] = sc.h_reg[j].mx; hasnan[j] = sc.h_reg[j].hasnan; }
+        search.take(sum, mx, hasnan);
+    }
+    if (env.debug) {
+        fprintf(stderr, "prune: best %.4f |", search.best_sum() / Ntot);
+        for (int j = 0; j < b.nb; ++j)
+            if (in[j]) fprintf(stderr, " %d/%d:%.3f%s", search.classes_done(j), env.K, search.mean(j), search.pruned(j) ? "x" : "");
+        fprintf(stderr, "\n");
+    }
+    for (int j = 0; j < b.nb; ++j) {
+        b.h_rs[j].mx = search.maximum(j);
+        b.h_rs[j].hasnan = search.hasnan(j);
+        b.h_rs[j].ssim_sum = search.sum(j);
+        if (in[j]) {
+            c->reg_cand_volumes += search.volume_fraction(j);
+            c->reg_pruned += search.pruned(j) ? 1 : 0;
+        }
+    }
+    return MVS_OK;
+}
+
+// the launches the batched candidates share, then the region statistics of the whole batch into b.h_rs
+int score_batch(ScoreCall& sc, ScoreBatch& b, size_t n_todo) {
+    MvsContext* c = sc.c;
+    bool have_rs = false;
+    if (b.any_batched && !c->ssim_two_pass) {
+        bool prune = sc.so->argmax_only && c->ssim_prune && n_todo <= (size_t)sc.nres;
+        int n_in = 0;
+        for (int j = 0; j < b.nb; ++j) {
+            if (b.fused.c[j].src) ++n_in;
+            else if (b.scored[j]) prune = false;          // a candidate on the separate passes: everything is scored in full
+        }
+        const double vb = sc.so->value_bound;
+        const double slack = 1e-2 * std::max(1.0, (vb / sc.data_range) * (vb / sc.data_range));
+        prune = prune && n_in >= 2 && sc.data_range > 0.0 && std::isfinite(slack) && slack <= 0.05;
+        if (!prune) score_full(sc, b, n_in);
+        else {
+            const int rc = score_pruned(sc, b, slack);
+            if (rc) return rc;
+            have_rs = true;
+        }
+    } else if (b.any_batched) {
+        score_two_pass(sc, b);
+    }
+    bool any = false;
+    for (int j = 0; j < b.nb; ++j) any = any || b.scored[j];
+    if (any && !have_rs) {
+        hipLaunchKernelGGL(finish_region_kernel, dim3(b.nb), dim3(256), 0, c->stream, sc.pmax, sc.phasnan, sc.psum, sc.reg_out, kStatBlocks);
+        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (int j = 0; j < b.nb; ++j) b.h_rs[j] = sc.h_reg[j];
+    }
+    return MVS_OK;
+}
+
+// codes and SSIM values of the batch from its region statistics
+void decode_results(ScoreCall& sc, const ScoreBatch& b) {
+    for (int j = 0; j < b.nb; ++j) {
+        const int ic = b.ics[j];
+        if (sc.code_out[ic] != 0) continue;
+        float region_nanmax = NAN;
+        int region_hasnan = 0;
+        if (b.scored[j]) {
+            region_hasnan = b.h_rs[j].hasnan;
+            region_nanmax = (b.h_rs[j].mx == -INFINITY) ? NAN : b.h_rs[j].mx;   // all-NaN region
+        }
+        // `if np.nanmax(im1t[mask_slices]) <= im1_min: continue` (Q3: nothing is appended)
+        if (region_nanmax <= (float)sc.im1_min) {
+            sc.code_out[ic] = 2;
+            continue;
+        }
+        const Shape3 R = b.Rs[j];
+        const int win = ssim_window(sc, R);
+        const float region_max = region_hasnan ? NAN : region_nanmax;   // np.max propagates NaN
+        if (win < 3 || region_max <= (float)sc.im1_min || !b.scored[j]) {
+            sc.ssim_out[ic] = -1.0;
+        } else {
+            const int pad = (win - 1) / 2;
+            double cropn = 1.0;
+            for (int k = sc.k0; k < 3; ++k) cropn *= (double)((&R.nz)[k] - 2 * pad);
+            sc.ssim_out[ic] = b.h_rs[j].ssim_sum / cropn;
+        }
+    }
+}
+
+// ---- Spearman over the jointly valid voxels of candidate ic ----
+// histogram ranks: both crops hold 16-bit integers (the caller vouches: raw_u16_keys) and are finite, every component of this
+// candidate's shift is a multiple of 1/2, and the keys fit the tables
+struct HistPlan { double t[3]; long long kx0, nbx, ky0, nby, hgb; bool fold; };
+bool hist_ranks_apply(const ScoreCall& sc, int ic, HistPlan* hp) {
+    const MvsScoreOpts& so = *sc.so;
+    sc.shift_of(ic, hp->t);
+    bool halves = true;
+    int nf = 0;
+    for (int k = 0; k < 3; ++k) {
+        halves = halves && (std::floor(hp->t[k] * 2.0) == hp->t[k] * 2.0);
+        nf += (std::floor(hp->t[k]) != hp->t[k]) ? 1 : 0;
+    }
+    // key ranges from the raw extrema of the crops (so.raw_range: min / max of the fixed and of the moving crop)
+    hp->kx0 = (long long)so.raw_range[0]; hp->nbx = (long long)so.raw_range[1] - hp->kx0 + 1;
+    hp->ky0 = (long long)so.raw_range[2] * (1 << nf); hp->nby = ((long long)so.raw_range[3] - (long long)so.raw_range[2]) * (1 << nf) + 1;
+    // < 65536 voxels per workgroup; up to kHistParts workgroups write their histograms out whole (folded by a
+    // second kernel), beyond that the non-zero counters are flushed with atomics
+    const long long hneed = (sc.n / 4 + 16382) / 16383;
+    hp->fold = hneed <= kHistParts;
+    hp->hgb = hp->fold ? std::max<long long>(hneed, std::min<long long>(kHistParts, (sc.n + 8191) / 8192)) : std::max<long long>(sc.gb, hneed);
+    return halves && so.raw_u16_keys[0] && so.raw_u16_keys[1] && so.both_crops_finite && !sc.c->materialize_shifts && hp->nbx > 0 && hp->nby > 0 &&
+           hp->nbx + hp->nby <= kHistBinsMax && hp->hgb <= 65535;
+}
+
+int spearman_hist(ScoreCall& sc, int ic, const HistPlan& hp) {
+    MvsContext* c = sc.c;
+    const MvsScoreOpts& so = *sc.so;
+    const long long kx0 = hp.kx0, nbx = hp.nbx, ky0 = hp.ky0, nby = hp.nby, hgb = hp.hgb;
+    unsigned int* d_hist = sc.d_hist;
+    float* d_rank = sc.d_rank;
+    static bool lds_attr[MVS_MAX_DEVICES] = {false};
+    if (!lds_attr[mvs_hip_device(sc.device)]) {
+        MVS_HIP_TRY(c, hipFuncSetAttribute((const void*)hist_rank_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+        lds_attr[mvs_hip_device(sc.device)] = true;
+    }
+    const size_t lds_bytes = (size_t)((nbx + nby + 1) / 2) * 4;
+    if (!hp.fold) MVS_HIP_TRY(c, hipMemsetAsync(d_hist, 0, sizeof(unsigned int) * (size_t)(nbx + nby), c->stream));
+    MVS_DUP("hist_count", hipLaunchKernelGGL(hist_rank_kernel<false>, dim3((unsigned)hgb), dim3(1024), lds_bytes, c->stream, so.raw_u16_keys[0], so.raw_u16_keys[1],
+                       sc.S, hp.t[0], hp.t[1], hp.t[2], (int)kx0, (int)nbx, (int)ky0, (int)nby, d_hist, d_hist + nbx, (const float*)nullptr,
+                       (const float*)nullptr, (double*)nullptr, hp.fold ? sc.d_parts : (unsigned int*)nullptr));
+    if (hp.fold) {
+        const int nwords = (int)((nbx + nby + 1) / 2);
+        MVS_DUP("hist_fold", hipLaunchKernelGGL(hist_fold_kernel, dim3((nwords + 63) / 64), dim3(1024), 0, c->stream, sc.d_parts, (int)hgb, nwords, (int)nbx, (int)nby,
+                           d_hist, d_hist + nbx));
+    }
+    MVS_DUP("rank_table", hipLaunchKernelGGL(rank_table_kernel, dim3(2), dim3(1024), 0, c->stream, d_hist, (int)nbx, d_rank, d_hist + nbx, (int)nby,
+                       d_rank + nbx, sc.partial));
+    MVS_DUP("hist_corr", hipLaunchKernelGGL(hist_rank_kernel<true>, dim3(sc.gb), dim3(256), 0, c->stream, so.raw_u16_keys[0], so.raw_u16_keys[1], sc.S, hp.t[0], hp.t[1],
+                       hp.t[2], (int)kx0, (int)nbx, (int)ky0, (int)nby, d_hist, d_hist + nbx, d_rank, d_rank + nbx, sc.partial + 4, (unsigned int*)nullptr));
+    MVS_HIP_TRY(c, hipGetLastError());
+    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const double* hpart = sc.h_partial;
+    double sxy = 0;
+    for (int i = 0; i < sc.gb; ++i) sxy += hpart[4 + i];
+    sc.spearman_out[ic] = sxy / std::sqrt(hpart[0] * hpart[2]);
+    return MVS_OK;
+}
+
+// sorted ranks: compaction, sort by x carrying y, ranks of x in sorted order, sort by y carrying rank(x), correlation sums in
+// y-sorted order.  im1t == nullptr: the candidate has no shifted copy of its own; it is made here (into im1t_buf[0])
+int spearman_sorted(ScoreCall& sc, int ic, const float* im1t) {
+    MvsContext* c = sc.c;
+    float* const* setA = sc.setA;
+    float* const* setB = sc.setB;
+    if (!im1t) {
+        double t[3];
+        sc.shift_of(ic, t);
+        hipLaunchKernelGGL(shift_kernel, dim3(kStatBlocks), dim3(256), 0, c->stream, sc.im1, sc.im0, sc.im1t_buf[0], sc.S, t[0], t[1], t[2], sc.im1_all_finite, sc.vox_partial);
+        std::fill(sc.resident.begin(), sc.resident.end(), -1);
+        sc.resident[ic] = 0;
+        im1t = sc.im1t_buf[0];
+    }
+    MVS_HIP_TRY(c, hipMemsetAsync(sc.d_counter, 0, 4, c->stream));
+    const float* raw0 = sc.so->raw_u16_keys[0];      // 16-bit integer keys for the fixed image when the caller vouches for them
+    hipLaunchKernelGGL(compact_kernel, dim3(sc.gb), dim3(256), 0, c->stream, sc.im0, im1t, sc.n, setA[0], setA[1], sc.d_counter, raw0);
+    const unsigned int m = (unsigned int)sc.cnts[ic];
+    const int mgb = (int)std::min<long long>(((long long)m + kRankChunk - 1) / kRankChunk, 2048);   // one chunk of sorted keys per workgroup turn
+    if (raw0) {
+        MVS_HIP_TRY(c, rocprim::radix_sort_pairs(sc.sort_temp, sc.sort_temp_bytes, (unsigned int*)setA[0], (unsigned int*)setA[2], setA[1], setA[3], (size_t)m,
+                                                0, 16, c->stream));
+        hipLaunchKernelGGL(ranks_sorted_kernel<unsigned int>, dim3(mgb), dim3(256), 0, c->stream, (const unsigned int*)setA[2], m, setA[4]);
+    } else {
+        MVS_HIP_TRY(c, rocprim::radix_sort_pairs(sc.sort_temp, sc.sort_temp_bytes, setA[0], setA[2], setA[1], setA[3], (size_t)m, 0, 32, c->stream));
+        hipLaunchKernelGGL(ranks_sorted_kernel<float>, dim3(mgb), dim3(256), 0, c->stream, setA[2], m, setA[4]);
+    }
+    MVS_HIP_TRY(c, rocprim::radix_sort_pairs(sc.sort_temp, sc.sort_temp_bytes, setA[3], setB[0], setA[4], setB[1], (size_t)m, 0, 32, c->stream));
+    hipLaunchKernelGGL(rankcorr_kernel, dim3(mgb), dim3(256), 0, c->stream, setB[0], setB[1], m, 0.5 * ((double)m + 1.0), sc.partial);
+    MVS_HIP_TRY(c, hipGetLastError());
+    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const double* hp = sc.h_partial;
+    double sxy = 0, sxx = 0, syy = 0;
+    for (int i = 0; i < mgb; ++i) { sxy += hp[i * 3]; sxx += hp[i * 3 + 1]; syy += hp[i * 3 + 2]; }
+    sc.spearman_out[ic] = sxy / std::sqrt(sxx * syy);
+    return MVS_OK;
+}
+
+int spearman_from(ScoreCall& sc, int ic, const float* im1t) {
+    HistPlan hp;
+    return hist_ranks_apply(sc, ic, &hp) ? spearman_hist(sc, ic, hp) : spearman_sorted(sc, ic, im1t);
+}
+
 }  // namespace
 
 extern "C" int mvs_score_candidates(int device, const float* fixed, const float* moving, int32_t mem, int32_t ndim,
@@ -1403,641 +2022,85 @@ int mvs_score_candidates_impl(int device, const float* fixed, const float* movin
     if (ndim != 2 && ndim != 3) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_score_candidates: ndim must be 2 or 3");
     if (ndim == 2 && shape[0] != 1) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_score_candidates: 2D needs shape[0]==1");
     MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
-    const Shape3 S = {(int)shape[0], (int)shape[1], (int)shape[2]};
-    const long long n = (long long)S.nz * S.ny * S.nx;
+    ScoreCall sc;
+    sc.c = c; sc.so = &so; sc.device = device;
+    sc.S = Shape3{(int)shape[0], (int)shape[1], (int)shape[2]};
+    const Shape3 S = sc.S;
+    const long long n = sc.n = (long long)S.nz * S.ny * S.nx;
     if (n >= (1ll << 31) - 8) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "mvs_score_candidates: volume too large");
-    const int k0 = 3 - ndim;
+    sc.ndim = ndim; sc.k0 = 3 - ndim; sc.region_mode = region_mode; sc.quality_for_all = quality_for_all;
+    sc.data_range = data_range; sc.im1_min = im1_min;
+    sc.t_candidates = t_candidates; sc.ssim_out = ssim_out; sc.spearman_out = spearman_out; sc.code_out = code_out;
 
-    float *im0, *im1;
-    rc = mvs_stage_float_volume(c, fixed, mem, n, 4, &im0);
+    rc = mvs_stage_float_volume(c, fixed, mem, n, 4, &sc.im0);
     if (rc) return rc;
-    rc = mvs_stage_float_volume(c, moving, mem, n, 5, &im1);
+    rc = mvs_stage_float_volume(c, moving, mem, n, 5, &sc.im1);
     if (rc) return rc;
 
     // Candidates that survive the analytic pre-test are evaluated in batches: all their shifted copies of the
     // moving image stay resident (one host round trip for the masks / boxes of the whole batch, a second one
     // for the SSIM sums), and the winner's copy is still there for the rank correlation.
-    const int nres = (int)std::max<long long>(1, std::min<long long>(std::min(kMaxResident, std::max(n_candidates, 1)),
-                                                                     (4ll << 30) / (n * 4)));
-    size_t sort_temp_bytes = 0;
-    MVS_HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sort_temp_bytes, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+    sc.nres = (int)std::max<long long>(1, std::min<long long>(std::min(kMaxResident, std::max(n_candidates, 1)), (4ll << 30) / (n * 4)));
+    sc.sort_temp_bytes = 0;
+    MVS_HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, sc.sort_temp_bytes, (float*)nullptr, (float*)nullptr, (float*)nullptr,
                                             (float*)nullptr, (size_t)n, 0, 32, c->stream));
     {
         size_t tb16 = 0;
         MVS_HIP_TRY(c, rocprim::radix_sort_pairs(nullptr, tb16, (unsigned int*)nullptr, (unsigned int*)nullptr, (float*)nullptr,
                                                 (float*)nullptr, (size_t)n, 0, 16, c->stream));
-        sort_temp_bytes = std::max(sort_temp_bytes, tb16);
+        sc.sort_temp_bytes = std::max(sc.sort_temp_bytes, tb16);
     }
-    const int gb = grid_for(n);
-    const size_t stat_bytes = (size_t)(kMaxResident + 2) * kStatBlocks * (sizeof(VoxStats) + 4 + 4 + 8) + (kMaxResident + 2) * 64;
+    sc.gb = grid_for(n);
     // batched launches (one z pass / one y-x pass for all candidates of a batch) keep three z-filtered arrays per candidate
-    const bool may_batch = ndim == 3 && region_mode == 0 && !quality_for_all && !c->materialize_shifts && (long long)n * 12 * nres <= (3ll << 30);
-    constexpr int kMaxCls = 4;      // fraction classes of half-pixel shifts that get ONE shifted copy shared by their candidates
-    const size_t need = (size_t)n * 4 * (10 + nres + (may_batch ? 3 * nres + kMaxCls : 0)) + 256 * (12 + 4 * nres + kMaxCls) + sort_temp_bytes + (size_t)gb * 32 + stat_bytes + 64 * 1024 + (size_t)(kHistBinsMax + 64) * 8 + (size_t)kHistParts * (kHistBinsMax / 2 + 1) * 4 + 2048;
-    char* base = (char*)mvs_scratch(c, 6, need);
-    if (!base) return mvs_alloc_failed(c);
-    DeviceBump B{base, need, 0};
-    std::vector<float*> im1t_buf(nres);
-    for (int i = 0; i < nres; ++i) im1t_buf[i] = B.take<float>(n);
-    float* setA[5]; float* setB[5];
-    for (int a = 0; a < 5; ++a) setA[a] = B.take<float>(n);
-    for (int a = 0; a < 5; ++a) setB[a] = B.take<float>(n);
-    std::vector<float*> cand3((size_t)(may_batch ? 3 * nres : 0));
-    for (float*& q : cand3) q = B.take<float>(n);
-    // In 3D the phase correlation refines to half pixels, so the candidates of a pair -- t, -t, -(t - N), -t - N per axis -- share the
-    // fractional part of their shift per axis, and every candidate image is an INTEGER shift of one "fraction-only" shifted copy of the
-    // moving image (same taps, weights and order: c = o + t is exact in double).  One copy per fraction class instead of one per
-    // candidate; the fused SSIM walk reads it at o + floor(t) exactly as it reads the moving image itself for integer shifts.
-    struct ClsBuf { int key; float* buf; } cls[kMaxCls];
-    int n_cls = 0;
-    for (int k = 0; k < kMaxCls; ++k) cls[k] = ClsBuf{-1, may_batch ? B.take<float>(n) : nullptr};
-    void* sort_temp = B.take<char>(sort_temp_bytes);
-    double* partial = B.take<double>((size_t)gb * 4);
-    VoxStats* vox_partial = B.take<VoxStats>((size_t)(kMaxResident + 2) * kStatBlocks);
-    VoxStats* vox_out = B.take<VoxStats>(kMaxResident + 2);
-    float* pmax = B.take<float>((size_t)kMaxResident * kStatBlocks);
-    int* phasnan = B.take<int>((size_t)kMaxResident * kStatBlocks);
-    double* psum = B.take<double>((size_t)kMaxResident * kStatBlocks);
-    RegionStats* reg_out = B.take<RegionStats>(kMaxResident);
-    unsigned int* d_hist = B.take<unsigned int>((size_t)kHistBinsMax + 64);     // key histograms of the rank correlation
-    float* d_rank = B.take<float>((size_t)kHistBinsMax + 64);
-    unsigned int* d_parts = B.take<unsigned int>((size_t)kHistParts * (kHistBinsMax / 2 + 1));   // per-workgroup packed histograms
-    unsigned int* d_counter = B.take<unsigned int>(64);
-    if (!d_counter) return mvs_fail(c, MVS_ERR_HIP, "mvs_score_candidates: scratch layout");
-    // results the host reads (reduction partials of the rank correlation, voxel and region statistics) are written by the kernels
-    // straight into the context's mailbox (pinned host memory): no copy launches
-    const size_t mb_partial = 0, mb_vox = align_up((size_t)gb * 4 * sizeof(double));
-    const size_t mb_reg = mb_vox + align_up((size_t)(kMaxResident + 2) * sizeof(VoxStats));
-    void *mb_host = nullptr, *mb_dev = nullptr;
-    {
-        const int rcm = mvs_mailbox(c, mb_reg + (size_t)kMaxResident * sizeof(RegionStats), &mb_host, &mb_dev);
-        if (rcm) return rcm;
-    }
-    partial = (double*)((char*)mb_dev + mb_partial);
-    vox_out = (VoxStats*)((char*)mb_dev + mb_vox);
-    reg_out = (RegionStats*)((char*)mb_dev + mb_reg);
-    const double* h_partial = (const double*)((const char*)mb_host + mb_partial);
-    const VoxStats* h_vox = (const VoxStats*)((const char*)mb_host + mb_vox);
-    const RegionStats* h_reg = (const RegionStats*)((const char*)mb_host + mb_reg);
-
-    // valid voxels of im1 and the bboxes of both images (registration.py:400, 491)
-    VoxStats h_im[2];
-    if (so.both_crops_finite) {
-        // the caller (mvs_register_crops) has just reduced both images and found neither NaN nor inf: every voxel is valid,
-        // the boxes are the whole volume -- no reduction, no host round trip
-        for (int k = 0; k < 2; ++k) {
-            h_im[k].cnt = (unsigned long long)n;
-            h_im[k].bb[0] = h_im[k].bb[1] = h_im[k].bb[2] = 0;
-            h_im[k].bb[3] = S.nz - 1; h_im[k].bb[4] = S.ny - 1; h_im[k].bb[5] = S.nx - 1;
-        }
-    } else {
-        hipLaunchKernelGGL(image_stats_kernel, dim3(kStatBlocks), dim3(256), 0, c->stream, im0, S, vox_partial);
-        hipLaunchKernelGGL(image_stats_kernel, dim3(kStatBlocks), dim3(256), 0, c->stream, im1, S, vox_partial + kStatBlocks);
-        hipLaunchKernelGGL(finish_voxstats_kernel, dim3(2), dim3(256), 0, c->stream, vox_partial, vox_out);
-        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        h_im[0] = h_vox[0];
-        h_im[1] = h_vox[1];
-    }
-    const int* bb0 = h_im[0].bb;
-    const int* bbm = h_im[1].bb;
-    const unsigned int valid1 = (unsigned int)(h_im[1].cnt & 0xffffffffull);
-    // every voxel of the moving image finite?  (lower half: #non-NaN, upper half: #inf, see image_stats_kernel)
-    const int im1_all_finite = ((long long)valid1 == n && (h_im[1].cnt >> 32) == 0) ? 1 : 0;
-    const int im0_all_finite = ((long long)(h_im[0].cnt & 0xffffffffull) == n && (h_im[0].cnt >> 32) == 0) ? 1 : 0;
-    // Both crops finite (tiles on a common grid): the valid box of a shifted copy and with it the mask count are known
-    // without touching the volume -- x is valid iff 0 <= fl(x + t) <= n - 1 per axis -- so the reduction of phase A and its
-    // host round trip are skipped, and candidates with integer shifts are never materialised: the SSIM z pass reads the
-    // moving image at the shifted position (the winner's copy is written afterwards, for the rank correlation).
-    const bool on_the_fly = !quality_for_all && im0_all_finite && im1_all_finite && !c->materialize_shifts;
+    sc.may_batch = ndim == 3 && region_mode == 0 && !quality_for_all && !c->materialize_shifts && (long long)n * 12 * sc.nres <= (3ll << 30);
+    rc = layout_scratch(sc);
+    if (rc) return rc;
+    rc = image_boxes(sc);
+    if (rc) return rc;
 
     MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    // analytic pre-test: upper bound of the mask count from the valid bounding boxes -- im1t can only be valid
-    // where x + t lies in im1's valid box.  If even the bound fails the 10 % test the candidate is rejected
-    // exactly as the reference rejects it (registration.py:503-505) without touching the volume.
     std::vector<int> todo;
     for (int ic = 0; ic < n_candidates; ++ic) {
-        double t[3] = {0.0, 0.0, 0.0};
-        for (int k = 0; k < ndim; ++k) t[k0 + k] = t_candidates[ic * ndim + k];
+        double t[3];
+        sc.shift_of(ic, t);
         ssim_out[ic] = -1.0;
         spearman_out[ic] = -1.0;
         code_out[ic] = 0;
-        double bound = 1.0;
-        const int dimv[3] = {S.nz, S.ny, S.nx};
-        for (int k = 0; k < 3; ++k) {
-            const double lo1 = std::ceil((double)bbm[k] - t[k] - 1.0), hi1 = std::floor((double)bbm[3 + k] - t[k] + 1.0);
-            const double lo = std::max(std::max(lo1, (double)bb0[k]), 0.0);
-            const double hi = std::min(std::min(hi1, (double)bb0[3 + k]), (double)(dimv[k] - 1));
-            bound *= std::max(hi - lo + 1.0, 0.0);
-        }
-        if (valid1 == 0 || bound == 0.0 || bound / (double)valid1 < 0.1) code_out[ic] = 1;
-        else todo.push_back(ic);
+        if (passes_pretest(sc, t)) todo.push_back(ic);
+        else code_out[ic] = 1;
     }
 
-    std::vector<unsigned long long> cnts((size_t)std::max(n_candidates, 1), 0ull);
-    std::vector<int> resident((size_t)std::max(n_candidates, 1), -1);   // buffer holding the candidate's im1t, if still there
+    sc.cnts.assign((size_t)std::max(n_candidates, 1), 0ull);
+    sc.resident.assign((size_t)std::max(n_candidates, 1), -1);
     const float Rf = (float)data_range;
     // (K1 * R) ** 2 with R a float32 scalar: numpy keeps this in float32
-    const float C1 = (0.01f * Rf) * (0.01f * Rf);
-    const float C2 = (0.03f * Rf) * (0.03f * Rf);
-
-    // Spearman over the jointly valid voxels of candidate ic, whose shifted image is `im1t`: compaction, sort by x
-    // carrying y, ranks of x in sorted order, sort by y carrying rank(x), correlation sums in y-sorted order
-    // im1t == nullptr: the candidate has no shifted copy of its own; it is made (into im1t_buf[0]) only if the sorting path needs it
-    auto spearman_from = [&](int ic, const float* im1t) -> int {
-        {
-            // histogram ranks: both crops hold 16-bit integers (the caller vouches: raw_u16_keys) and are finite, every
-            // component of this candidate's shift is a multiple of 1/2
-            double t[3] = {0.0, 0.0, 0.0};
-            bool halves = true;
-            for (int k = 0; k < ndim; ++k) {
-                t[k0 + k] = t_candidates[ic * ndim + k];
-                halves = halves && (std::floor(t[k0 + k] * 2.0) == t[k0 + k] * 2.0);
-            }
-            int nf = 0;
-            for (int k = 0; k < 3; ++k) nf += (std::floor(t[k]) != t[k]) ? 1 : 0;
-            // key ranges from the raw extrema of the crops (so.raw_range: min / max of the fixed and of the moving crop)
-            const long long kx0 = (long long)so.raw_range[0], nbx = (long long)so.raw_range[1] - kx0 + 1;
-            const long long ky0 = (long long)so.raw_range[2] * (1 << nf), nby = ((long long)so.raw_range[3] - (long long)so.raw_range[2]) * (1 << nf) + 1;
-            // < 65536 voxels per workgroup; up to kHistParts workgroups write their histograms out whole (folded by a
-            // second kernel), beyond that the non-zero counters are flushed with atomics
-            const long long hneed = ((long long)n / 4 + 16382) / 16383;
-            const bool fold = hneed <= kHistParts;
-            const long long hgb = fold ? std::max<long long>(hneed, std::min<long long>(kHistParts, ((long long)n + 8191) / 8192)) : std::max<long long>(gb, hneed);
-            if (halves && so.raw_u16_keys[0] && so.raw_u16_keys[1] && so.both_crops_finite && !c->materialize_shifts && nbx > 0 && nby > 0 &&
-                nbx + nby <= kHistBinsMax && hgb <= 65535) {
-                static bool lds_attr[MVS_MAX_DEVICES] = {false};
-                if (!lds_attr[mvs_hip_device(device)]) {
-                    MVS_HIP_TRY(c, hipFuncSetAttribute((const void*)hist_rank_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                    lds_attr[mvs_hip_device(device)] = true;
-                }
-                const size_t lds_bytes = (size_t)((nbx + nby + 1) / 2) * 4;
-                if (!fold) MVS_HIP_TRY(c, hipMemsetAsync(d_hist, 0, sizeof(unsigned int) * (size_t)(nbx + nby), c->stream));
-                MVS_DUP("hist_count", hipLaunchKernelGGL(hist_rank_kernel<false>, dim3((unsigned)hgb), dim3(1024), lds_bytes, c->stream, so.raw_u16_keys[0], so.raw_u16_keys[1],
-                                   S, t[0], t[1], t[2], (int)kx0, (int)nbx, (int)ky0, (int)nby, d_hist, d_hist + nbx, (const float*)nullptr,
-                                   (const float*)nullptr, (double*)nullptr, fold ? d_parts : (unsigned int*)nullptr));
-                if (fold) {
-                    const int nwords = (int)((nbx + nby + 1) / 2);
-                    MVS_DUP("hist_fold", hipLaunchKernelGGL(hist_fold_kernel, dim3((nwords + 63) / 64), dim3(1024), 0, c->stream, d_parts, (int)hgb, nwords, (int)nbx, (int)nby,
-                                       d_hist, d_hist + nbx));
-                }
-                MVS_DUP("rank_table", hipLaunchKernelGGL(rank_table_kernel, dim3(2), dim3(1024), 0, c->stream, d_hist, (int)nbx, d_rank, d_hist + nbx, (int)nby,
-                                   d_rank + nbx, partial));
-                MVS_DUP("hist_corr", hipLaunchKernelGGL(hist_rank_kernel<true>, dim3(gb), dim3(256), 0, c->stream, so.raw_u16_keys[0], so.raw_u16_keys[1], S, t[0], t[1],
-                                   t[2], (int)kx0, (int)nbx, (int)ky0, (int)nby, d_hist, d_hist + nbx, d_rank, d_rank + nbx, partial + 4, (unsigned int*)nullptr));
-                MVS_HIP_TRY(c, hipGetLastError());
-                MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-                const double* hp = h_partial;
-                double sxy = 0;
-                for (int i = 0; i < gb; ++i) sxy += hp[4 + i];
-                spearman_out[ic] = sxy / std::sqrt(hp[0] * hp[2]);
-                return MVS_OK;
-            }
-        }
-        if (!im1t) {
-            double t[3] = {0.0, 0.0, 0.0};
-            for (int k = 0; k < ndim; ++k) t[k0 + k] = t_candidates[ic * ndim + k];
-            hipLaunchKernelGGL(shift_kernel, dim3(kStatBlocks), dim3(256), 0, c->stream, im1, im0, im1t_buf[0], S, t[0], t[1], t[2], im1_all_finite, vox_partial);
-            std::fill(resident.begin(), resident.end(), -1);
-            resident[ic] = 0;
-            im1t = im1t_buf[0];
-        }
-        MVS_HIP_TRY(c, hipMemsetAsync(d_counter, 0, 4, c->stream));
-        const float* raw0 = so.raw_u16_keys[0];      // 16-bit integer keys for the fixed image when the caller vouches for them
-        hipLaunchKernelGGL(compact_kernel, dim3(gb), dim3(256), 0, c->stream, im0, im1t, n, setA[0], setA[1], d_counter, raw0);
-        const unsigned int m = (unsigned int)cnts[ic];
-        const int mgb = (int)std::min<long long>(((long long)m + kRankChunk - 1) / kRankChunk, 2048);   // one chunk of sorted keys per workgroup turn
-        if (raw0) {
-            MVS_HIP_TRY(c, rocprim::radix_sort_pairs(sort_temp, sort_temp_bytes, (unsigned int*)setA[0], (unsigned int*)setA[2], setA[1], setA[3], (size_t)m,
-                                                    0, 16, c->stream));
-            hipLaunchKernelGGL(ranks_sorted_kernel<unsigned int>, dim3(mgb), dim3(256), 0, c->stream, (const unsigned int*)setA[2], m, setA[4]);
-        } else {
-            MVS_HIP_TRY(c, rocprim::radix_sort_pairs(sort_temp, sort_temp_bytes, setA[0], setA[2], setA[1], setA[3], (size_t)m, 0, 32, c->stream));
-            hipLaunchKernelGGL(ranks_sorted_kernel<float>, dim3(mgb), dim3(256), 0, c->stream, setA[2], m, setA[4]);
-        }
-        MVS_HIP_TRY(c, rocprim::radix_sort_pairs(sort_temp, sort_temp_bytes, setA[3], setB[0], setA[4], setB[1], (size_t)m, 0, 32, c->stream));
-        hipLaunchKernelGGL(rankcorr_kernel, dim3(mgb), dim3(256), 0, c->stream, setB[0], setB[1], m, 0.5 * ((double)m + 1.0), partial);
-        MVS_HIP_TRY(c, hipGetLastError());
-        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        const double* hp = h_partial;
-        double sxy = 0, sxx = 0, syy = 0;
-        for (int i = 0; i < mgb; ++i) { sxy += hp[i * 3]; sxx += hp[i * 3 + 1]; syy += hp[i * 3 + 2]; }
-        spearman_out[ic] = sxy / std::sqrt(sxx * syy);
-        return MVS_OK;
-    };
+    sc.C1 = (0.01f * Rf) * (0.01f * Rf);
+    sc.C2 = (0.03f * Rf) * (0.03f * Rf);
 
     // 3D, fixed image finite, "union" regions: the SSIM region of every candidate is the whole volume, so the fixed image's own
     // window means (x, xx: 2 of the 5 filtered quantities) are computed once for the pair instead of once per candidate
-    bool shared_x = false;
-    if (ndim == 3 && region_mode == 0 && im0_all_finite && todo.size() >= 2 && std::min(S.nz, std::min(S.ny, S.nx)) >= 7 &&
-        !c->materialize_shifts) {
-        shared_x = true;
-        launch_ssim_shared_x<7>(c->stream, im0, S, S, setA, setB, pmax, phasnan, !c->ssim_two_pass && (long long)S.nz * S.ny * S.nx * 4 < (1ll << 31));
-    }
-    // slot of the fraction class of a shift whose components are all multiples of 1/2 (bit k of the key: axis k has the fraction
-    // 1/2), -1 when the candidate keeps a copy of its own (other fractions, integer shift, no slot left, mode off); *fresh: the
-    // class copy still has to be written
-    auto share_cls = [&](const double t[3], bool* fresh) -> int {
-        *fresh = false;
-        if (!may_batch || !im1_all_finite || c->materialize_shifts || c->ssim_two_pass) return -1;
-        int key = 0;
-        for (int k = 0; k < 3; ++k) {
-            const double t2 = t[k] * 2.0;
-            if (!(std::floor(t2) == t2 && std::fabs(t[k]) < 1e6)) return -1;
-            key |= (t[k] != std::floor(t[k])) ? (1 << k) : 0;
-        }
-        if (key == 0) return -1;
-        for (int q = 0; q < n_cls; ++q)
-            if (cls[q].key == key) return q;
-        if (n_cls == kMaxCls) return -1;
-        cls[n_cls].key = key;
-        *fresh = true;
-        return n_cls++;
-    };
-    for (size_t b0 = 0; b0 < todo.size(); b0 += (size_t)nres) {
-        const int nb = (int)std::min<size_t>((size_t)nres, todo.size() - b0);
-        std::fill(resident.begin(), resident.end(), -1);
-        // ---- phase A: shifted copies + mask counts / bboxes of the whole batch ----
-        VoxStats h_vs[kMaxResident];
-        ShiftArg shifts[kMaxResident];
-        bool otf[kMaxResident] = {};
-        int cls_of[kMaxResident];      // fraction class whose copy the candidate reads (-1: its own copy / the moving image)
-        for (int j = 0; j < kMaxResident; ++j) cls_of[j] = -1;
-        const bool batched = on_the_fly && shared_x && may_batch;
-        ShiftBatch shift_batch;
-        int n_shift_batch = 0;
-        for (int j = 0; j < nb; ++j) {
-            const int ic = todo[b0 + j];
-            double t[3] = {0.0, 0.0, 0.0};
-            for (int k = 0; k < ndim; ++k) t[k0 + k] = t_candidates[ic * ndim + k];
-            shifts[j] = ShiftArg{t[0], t[1], t[2], im1_all_finite};
-            if (on_the_fly) {
-                // the predicate of axis_tap, evaluated on the host in the same double arithmetic: first and last valid index
-                const int dims[3] = {S.nz, S.ny, S.nx};
-                unsigned long long cnt = 1;
-                for (int k = 0; k < 3; ++k) {
-                    auto ok = [&](long long x) { const double cc = (double)x + t[k]; return !(cc < 0.0 || cc > (double)(dims[k] - 1)); };
-                    long long lo = (long long)std::ceil(-t[k]), hi = (long long)std::floor((double)(dims[k] - 1) - t[k]);
-                    lo = std::min<long long>(std::max<long long>(lo, 0), dims[k]);
-                    hi = std::max<long long>(std::min<long long>(hi, dims[k] - 1), -1);
-                    while (lo > 0 && ok(lo - 1)) --lo;
-                    while (lo < dims[k] && !ok(lo)) ++lo;
-                    while (hi < dims[k] - 1 && ok(hi + 1)) ++hi;
-                    while (hi >= 0 && !ok(hi)) --hi;
-                    h_vs[j].bb[k] = (int)lo;
-                    h_vs[j].bb[3 + k] = (int)hi;
-                    cnt *= (unsigned long long)std::max<long long>(hi - lo + 1, 0);
-                }
-                h_vs[j].cnt = cnt;
-                // integer shifts: one tap of weight 1 per voxel -- the z pass reads the moving image directly.  Fractional
-                // shifts keep their shifted copy (its 2-8 double-precision taps per voxel would be re-evaluated 1.75 times
-                // by the windowed z pass), but nobody waits for its statistics.
-                otf[j] = t[0] == std::floor(t[0]) && t[1] == std::floor(t[1]) && t[2] == std::floor(t[2]);
-                if (otf[j]) continue;
-                if (batched) {
-                    bool fresh = false;
-                    const int q = share_cls(t, &fresh);
-                    if (q >= 0) {
-                        cls_of[j] = q;
-                        if (fresh) {      // the class copy: the fraction-only shift, through the same launch as the other copies
-                            const int key = cls[q].key;
-                            ShiftCand sc{cls[q].buf, 0.5 * (key & 1), 0.5 * ((key >> 1) & 1), 0.5 * ((key >> 2) & 1), 1,
-                                         HalfShift{0, 0, 0, key & 1, (key >> 1) & 1, (key >> 2) & 1}};
-                            shift_batch.c[n_shift_batch++] = sc;
-                        }
-                        continue;
-                    }
-                }
-                if (batched) {      // all fractional shifts of the batch in one launch, after this loop
-                    ShiftCand sc{im1t_buf[j], t[0], t[1], t[2], 0, HalfShift{0, 0, 0, 0, 0, 0}};
-                    if (!c->materialize_shifts) {
-                        bool half = true;
-                        int f[3], h[3];
-                        for (int k = 0; k < 3; ++k) {
-                            const double t2 = t[k] * 2.0;
-                            half = half && std::floor(t2) == t2 && std::fabs(t[k]) < 1e6;
-                            f[k] = (int)std::floor(t[k]);
-                            h[k] = (t[k] != std::floor(t[k])) ? 1 : 0;
-                        }
-                        if (half) { sc.half = 1; sc.H = HalfShift{f[0], f[1], f[2], h[0], h[1], h[2]}; }
-                    }
-                    shift_batch.c[n_shift_batch++] = sc;
-                    resident[ic] = j;
-                    continue;
-                }
-            }
-            hipLaunchKernelGGL(shift_kernel, dim3(kStatBlocks), dim3(256), 0, c->stream, im1, im0, im1t_buf[j], S, t[0], t[1], t[2],
-                               im1_all_finite, vox_partial + (size_t)j * kStatBlocks);
-            resident[ic] = j;
-        }
-        if (n_shift_batch)
-            MVS_DUP("shift", hipLaunchKernelGGL(shift_batch_kernel, dim3(kStatBlocks, n_shift_batch), dim3(256), 0, c->stream, im1, im0, S, shift_batch, im1_all_finite));
-        if (!on_the_fly) {
-            hipLaunchKernelGGL(finish_voxstats_kernel, dim3(nb), dim3(256), 0, c->stream, vox_partial, vox_out);
-            MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-            for (int j = 0; j < nb; ++j) h_vs[j] = h_vox[j];
-        }
+    sc.shared_x = ndim == 3 && region_mode == 0 && sc.im0_all_finite && todo.size() >= 2 && std::min(S.nz, std::min(S.ny, S.nx)) >= 7 &&
+                  !c->materialize_shifts;
+    if (sc.shared_x)
+        launch_ssim_shared_x<7>(c->stream, sc.im0, S, S, sc.setA, sc.setB, sc.pmax, sc.phasnan, !c->ssim_two_pass && (long long)S.nz * S.ny * S.nx * 4 < (1ll << 31));
 
-        // ---- phase B: SSIM passes of every candidate that keeps enough jointly valid voxels ----
-        Shape3 Rs[kMaxResident];
-        int wins[kMaxResident];
-        bool scored[kMaxResident];
-        FirstBatch first_batch;
-        YxBatch yx_batch;
-        FusedBatch fused_batch;
-        bool any_batched = false;
-        float batch_cov_norm = 0.f;
-        for (int j = 0; j < nb; ++j) {
-            first_batch.c[j] = FirstCand{nullptr, nullptr, nullptr, nullptr, ShiftArg{0.0, 0.0, 0.0, 0}, 0};
-            yx_batch.c[j] = YxCand{nullptr, nullptr, nullptr};
-            fused_batch.c[j] = FusedCand{nullptr, 0, 0, 0, 0xffffffffu};
-        }
-        for (int j = 0; j < nb; ++j) {
-            const int ic = todo[b0 + j];
-            const unsigned long long cnt = h_vs[j].cnt;
-            const int* bb1 = h_vs[j].bb;
-            scored[j] = false;
-            wins[j] = 0;
-            Rs[j] = {0, 0, 0};
-            cnts[ic] = cnt;
-            if (cnt == 0 || (double)cnt / (double)valid1 < 0.1) {   // registration.py:503-505
-                code_out[ic] = 1;
-                continue;
-            }
-            // region slices (registration.py:509-528)
-            int lo[3], hi[3];
-            for (int k = 0; k < 3; ++k) {
-                if (region_mode == 0) { lo[k] = std::min(bb0[k], bb1[k]); hi[k] = std::max(bb0[3 + k], bb1[3 + k]) + 1; }
-                else { lo[k] = std::max(bb0[k], bb1[k]); hi[k] = std::min(bb0[3 + k], bb1[3 + k]) + 1; }
-            }
-            const Shape3 R = {std::max(hi[0] - lo[0], 0), std::max(hi[1] - lo[1], 0), std::max(hi[2] - lo[2], 0)};
-            Rs[j] = R;
-            const long long rn = (long long)R.nz * R.ny * R.nx;
-            if (rn <= 0) continue;
-            int min_shape = 0x7fffffff;
-            for (int k = k0; k < 3; ++k) min_shape = std::min(min_shape, (&R.nz)[k]);
-            int win = std::min(7, min_shape - ((min_shape - 1) % 2));
-            if (win < 3) win = 3;   // SSIM is -1 then (decided below); the pass still yields the region statistics
-            wins[j] = win;
-            double NP = 1.0;
-            for (int k = 0; k < ndim; ++k) NP *= (double)win;
-            const float cov_norm = (float)(NP / (NP - 1.0));
-            float* pm = pmax + (size_t)j * kStatBlocks;
-            int* ph = phasnan + (size_t)j * kStatBlocks;
-            double* ps = psum + (size_t)j * kStatBlocks;
-            const float* second = otf[j] ? im1 : im1t_buf[j];
-            const ShiftArg* sa = otf[j] ? &shifts[j] : nullptr;
-            const bool full = R.nz == S.nz && R.ny == S.ny && R.nx == S.nx;
-            if (cls_of[j] >= 0 && !(batched && win == 7 && full)) {
-                // (cannot happen for a whole-volume region with a 7-wide window; keeps the single-candidate paths below whole)
-                hipLaunchKernelGGL(shift_kernel, dim3(kStatBlocks), dim3(256), 0, c->stream, im1, im0, im1t_buf[j], S, shifts[j].tz, shifts[j].ty,
-                                   shifts[j].tx, im1_all_finite, vox_partial + (size_t)j * kStatBlocks);
-                resident[ic] = j;
-                cls_of[j] = -1;
-            }
-            if (batched && win == 7 && full) {     // joins the two batched launches below
-                float* d1 = cand3[(size_t)3 * j], *d3 = cand3[(size_t)3 * j + 1], *d4 = cand3[(size_t)3 * j + 2];
-                first_batch.c[j] = FirstCand{second, d1, d3, d4, shifts[j], otf[j] ? 1 : 0};
-                yx_batch.c[j] = YxCand{d1, d3, d4};
-                fused_batch.c[j] = otf[j] ? FusedCand{im1, (int)shifts[j].tz, (int)shifts[j].ty, (int)shifts[j].tx, 0xffffffffu}
-                                   : cls_of[j] >= 0 ? FusedCand{cls[cls_of[j]].buf, (int)std::floor(shifts[j].tz), (int)std::floor(shifts[j].ty), (int)std::floor(shifts[j].tx), 0xffffffffu}
-                                                    : FusedCand{im1t_buf[j], 0, 0, 0, 0xffffffffu};
-                any_batched = true;
-                batch_cov_norm = cov_norm;
-            }
-            else if (win == 7 && shared_x && full) launch_ssim_passes<7>(c->stream, im0, second, S, lo, R, ndim, setA, setB, cov_norm, C1, C2, pm, ph, ps, sa, true);
-            else if (win == 7) launch_ssim_passes<7>(c->stream, im0, second, S, lo, R, ndim, setA, setB, cov_norm, C1, C2, pm, ph, ps, sa);
-            else if (win == 5) launch_ssim_passes<5>(c->stream, im0, second, S, lo, R, ndim, setA, setB, cov_norm, C1, C2, pm, ph, ps, sa);
-            else launch_ssim_passes<3>(c->stream, im0, second, S, lo, R, ndim, setA, setB, cov_norm, C1, C2, pm, ph, ps, sa);
-            scored[j] = true;
-        }
-        RegionStats h_rs[kMaxResident];
-        bool have_rs = false;
-        if (any_batched && !c->ssim_two_pass) {
-            const int tiles = ((S.ny - 6 + 15) / 16) * ((S.nx - 6 + 55) / 56), cz = S.nz - 6;
-            // ---- pruned argmax search (the caller needs the arg-max candidate only: mvs_register_crops) -------------------------------
-            // The SSIM of a candidate is the mean of per-voxel values S <= 1 (S = l * cs with l <= 1 by the AM-GM inequality and
-            // |cs| <= 1 by Cauchy-Schwarz; the float32 window means move a variance by at most a few 2^-23 M^2, M the largest value,
-            // against C2 = (0.03 R)^2 in the denominator: S <= 1 + slack with the slack below).  So once ONE candidate is scored
-            // completely (sum S*), a candidate with partial sum p over n of the N voxels can at best reach p + (N - n)(1 + slack); if
-            // that is below S* it cannot be the arg max, whatever the rest of its volume holds -- the reference's nanargmax picks the
-            // same candidate, and the Spearman coefficient is only ever evaluated for that one.  All candidates are walked on 1 / 32 of
-            // the work items (spread over the volume), the leader is completed, the others continue in rounds only while their bound
-            // still reaches the best complete sum (see the plan inside the loop).  On the bench mosaic the decorrelated candidates
-            // (mean 0.01-0.15 against 0.90-0.975) leave after 3/32-8/32 of their volume, the sign flips of a half-pixel axis (0.6-0.94)
-            // after 6/32-22/32: 2.6 instead of 9.2 candidate volumes per pair (profiles/round4_prune_ab.txt).
-            bool prune = so.argmax_only && c->ssim_prune && todo.size() <= (size_t)nres;
-            int n_in = 0;
-            for (int j = 0; j < nb; ++j) {
-                if (fused_batch.c[j].src) ++n_in;
-                else if (scored[j]) prune = false;          // a candidate on the separate passes: everything is scored in full
-            }
-            const double vb = so.value_bound;
-            const double slack = 1e-2 * std::max(1.0, (vb / data_range) * (vb / data_range));
-            prune = prune && n_in >= 2 && data_range > 0.0 && std::isfinite(slack) && slack <= 0.05;
-            if (!prune) {
-                // ~1536 workgroups (two resident rounds of 3 per CU): 243 instead of 282 us per pair with 768 -- a workgroup spends its
-                // time waiting (two barriers and a load round trip per plane), so a second round hides more than its 6 halo planes cost
-                const int nzs = std::max(1, std::min(1536 / std::max(tiles * nb, 1), (cz + 7) / 8));
-                MVS_DUP("ssim_fused", hipLaunchKernelGGL(ssim_fused_batch_kernel<7>, dim3(kStatBlocks, nb), dim3(256), 0, c->stream, im0, S, fused_batch, setB[2], setB[3],
-                                   (cz + nzs - 1) / nzs, batch_cov_norm, C1, C2, pmax, phasnan, psum, 32));
-                c->reg_cand_volumes += (double)n_in;
-            } else {
-                const int cy = S.ny - 6, cx = S.nx - 6, nty = (cy + 15) / 16, ntx = (cx + 55) / 56;
-                static const int target_items = [] { const char* e = getenv("MVS_SSIM_PRUNE_ITEMS"); return (e && atoi(e) > 0) ? atoi(e) : 320; }();
-                const int nzs0 = std::max(1, std::min(target_items / std::max(tiles, 1), (cz + 7) / 8));
-                const int zseg = (cz + nzs0 - 1) / nzs0, nzs = (cz + zseg - 1) / zseg, nitems = nty * ntx * nzs;
-                // residue classes of the work items (a candidate's volume is walked in K-ths): 32 (measured against 16: 2.60 instead of
-                // 2.84 candidate volumes per pair on the bench mosaic); MVS_SSIM_PRUNE_CLASSES=16 for the A/B
-                static const int K = [] { const char* e = getenv("MVS_SSIM_PRUNE_CLASSES"); return (e && atoi(e) == 16) ? 16 : 32; }();
-                const unsigned int kAll = K == 32 ? 0xffffffffu : 0xffffu;
-                double vol_res[32];                     // output voxels of the work items of every residue class (the kernel's own geometry)
-                for (int r = 0; r < 32; ++r) vol_res[r] = 0.0;
-                for (int item = 0; item < nitems; ++item) {
-                    const int tx = item % ntx, ty = (item / ntx) % nty, zs = item / (ntx * nty);
-                    const int z0 = 3 + zs * zseg, z1 = std::min(z0 + zseg, S.nz - 3);
-                    const int res = (((item % K) - kSelRot * (item / K)) % K + K) % K;      // the residue class whose member this item is (kSelRot)
-                    vol_res[res] += (double)(z1 - z0) * (double)std::min(16, cy - ty * 16) * (double)std::min(56, cx - tx * 56);
-                }
-                const double Ntot = (double)cz * (double)cy * (double)cx;
-                auto vol_of = [&](unsigned int m) { double v = 0.0; for (int r = 0; r < 32; ++r) if ((m >> r) & 1u) v += vol_res[r]; return v; };
-                double acc[kMaxResident];
-                float amx[kMaxResident];
-                int ahn[kMaxResident];
-                unsigned int done[kMaxResident], masks[kMaxResident];
-                for (int j = 0; j < kMaxResident; ++j) { acc[j] = 0.0; amx[j] = -INFINITY; ahn[j] = 0; done[j] = 0; masks[j] = 0; }
-                // float32 walk (option ssim_f32, default on) + float64 re-walk of the candidates that end within `margin` (mean SSIM) of
-                // the best: a float32 window variance is off by <= a few 1e-7 (values rescaled to [0, 1], sums restarted per segment)
-                // against C2 = 9e-4 in the denominator -- up to ~1e-3 of a voxel's value in flat regions, far less in the mean over a
-                // crop; 1e-3 of the MEAN is the margin.  Candidates are dropped only when their bound stays below the best sum by it.
-                const bool walk_f32 = c->ssim_f32;
-                const double margin = walk_f32 ? 1e-3 : 0.0;
-                bool rewalk = false;
-                auto run_round = [&]() -> int {
-                    FusedBatch fb = fused_batch;
-                    int maxsel = 0;
-                    for (int j = 0; j < nb; ++j) {
-                        fb.c[j].sel = masks[j];
-                        if (!masks[j] || !fb.c[j].src) { fb.c[j].src = nullptr; masks[j] = 0; continue; }
-                        maxsel = std::max(maxsel, ((nitems + K - 1) / K) * __builtin_popcount(masks[j]));
-                    }
-                    if (maxsel == 0) return MVS_OK;
-                    const int gx = std::min(kStatBlocks, maxsel);
-                    // (117 VGPRs at 3-4 waves per SIMD; forced to 5 waves it spills: pairwise 38.9 -> 43.2 ms, measured)
-                    if (walk_f32 && !rewalk)
-                        MVS_DUP("ssim_fused", hipLaunchKernelGGL(ssim_fused_batch_f32_kernel<7>, dim3(gx, nb), dim3(256), 0, c->stream, im0, S, fb, setB[2], setB[3], zseg,
-                                           batch_cov_norm, C1, C2, pmax, phasnan, psum, K));
-                    else
-                        MVS_DUP("ssim_fused", hipLaunchKernelGGL(ssim_fused_batch_kernel<7>, dim3(gx, nb), dim3(256), 0, c->stream, im0, S, fb, setB[2], setB[3], zseg,
-                                           batch_cov_norm, C1, C2, pmax, phasnan, psum, K));
-                    MVS_DUP("finish", hipLaunchKernelGGL(finish_region_kernel, dim3(nb), dim3(256), 0, c->stream, pmax, phasnan, psum, reg_out, gx));
-                    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-                    for (int j = 0; j < nb; ++j) {
-                        if (!masks[j]) continue;
-                        acc[j] += h_reg[j].ssim_sum;
-                        amx[j] = fmaxf(amx[j], h_reg[j].mx);
-                        ahn[j] |= h_reg[j].hasnan;
-                        done[j] |= masks[j];
-                        masks[j] = 0;
-                    }
-                    return MVS_OK;
-                };
-                for (int j = 0; j < nb; ++j) masks[j] = fused_batch.c[j].src ? 0x0001u : 0u;
-                rc = run_round();
-                if (rc) return rc;
-                // A candidate whose region maximum does not exceed im1_min is the reference's `continue` case (registration.py:530-533):
-                // it takes no part in the arg max, so its sum must never be the one the others are dropped against (against a sparse
-                // fixed image an all-background candidate can hold the highest sum).  Complete candidates know their maximum; the
-                // leader is re-elected among the open candidates when it turns out to be such a candidate.
-                auto excluded = [&](int j) { return done[j] == kAll && !((double)amx[j] > im1_min); };
-                auto mean_of = [&](int j) { return acc[j] / std::max(vol_of(done[j]), 1.0); };
-                auto elect = [&]() {
-                    int l = -1;
-                    for (int j = 0; j < nb; ++j)
-                        if (fused_batch.c[j].src && !excluded(j) && !(done[j] == kAll && !std::isfinite(acc[j])) && (l < 0 || mean_of(j) > mean_of(l))) l = j;
-                    return l;
-                };
-                int leader = elect();
-                bool pruned[kMaxResident];
-                double ub[kMaxResident];
-                for (int j = 0; j < kMaxResident; ++j) { pruned[j] = false; ub[j] = 0.0; }
-                bool have_best = false;
-                double s_best = 0.0;
-                static const bool dbg = getenv("MVS_PRUNE_DEBUG") != nullptr;
-                for (int round = 0; round < 34; ++round) {
-                    // Plan: the leader is completed; every other open candidate advances to the fraction at which its bound would
-                    // fall below the reference sum if its mean stayed what it is so far (residues are taken in rising order; the
-                    // reference is the best complete sum, before there is one the leader's extrapolated sum -- a guess that only
-                    // sizes the round: candidates are dropped against complete sums alone).
-                    if (!have_best && (leader < 0 || done[leader] == kAll)) leader = elect();      // the leader was a `continue` candidate / NaN
-                    const double s_ref = have_best ? s_best : leader >= 0 ? mean_of(leader) * Ntot : Ntot * (1.0 + slack);
-                    bool more = false;
-                    for (int j = 0; j < nb; ++j) {
-                        if (!fused_batch.c[j].src || done[j] == kAll || pruned[j]) continue;
-                        const int k_done = __builtin_popcount(done[j]);
-                        int k_to = K;
-                        if (j != leader && (double)amx[j] > im1_min) {
-                            const double mean_c = acc[j] / std::max(vol_of(done[j]), 1.0);
-                            const double den = (1.0 + slack) - mean_c;
-                            const double f = den > 0.0 ? ((1.0 + slack) - s_ref / Ntot) / den : 2.0;
-                            if (f < 1.0) k_to = std::min(K, std::max(k_done + 1, (int)std::ceil((double)K * f * 1.15 + 0.25)));
-                            if (4 * k_to >= 3 * K) k_to = K;
-                        }
-                        masks[j] = (unsigned int)((1ull << k_to) - 1ull) & ~(unsigned int)((1ull << k_done) - 1ull);
-                        more = true;
-                    }
-                    if (!more) break;
-                    rc = run_round();
-                    if (rc) return rc;
-                    for (int j = 0; j < nb; ++j)
-                        if (fused_batch.c[j].src && done[j] == kAll && !excluded(j) && std::isfinite(acc[j]) && (!have_best || acc[j] > s_best)) {
-                            s_best = acc[j];
-                            have_best = true;
-                        }
-                    for (int j = 0; j < nb; ++j) {
-                        if (!fused_batch.c[j].src || done[j] == kAll || pruned[j]) continue;
-                        // (a candidate whose samples so far do not exceed im1_min may still be the reference's `continue` case: in full)
-                        ub[j] = acc[j] + (Ntot - vol_of(done[j])) * (1.0 + slack);
-                        if ((double)amx[j] > im1_min && ub[j] < s_best - (1e-9 + margin) * Ntot) pruned[j] = true;
-                    }
-                }
-                if (walk_f32 && have_best) {
-                    // the complete candidates within the margin of the best float32 sum: with two or more of them the arg max is decided
-                    // by their float64 sums (whole volume, fresh accumulators)
-                    int near = 0;
-                    for (int j = 0; j < nb; ++j)
-                        if (fused_batch.c[j].src && done[j] == kAll && !pruned[j] && !excluded(j) && std::isfinite(acc[j]) && acc[j] >= s_best - margin * Ntot) ++near;
-                    if (near >= 2) {
-                        rewalk = true;
-                        for (int j = 0; j < nb; ++j) {
-                            const bool sel = fused_batch.c[j].src && done[j] == kAll && !pruned[j] && !excluded(j) && std::isfinite(acc[j]) && acc[j] >= s_best - margin * Ntot;
-                            masks[j] = sel ? kAll : 0u;
-                            if (sel) { acc[j] = 0.0; c->reg_rewalks += 1; c->reg_cand_volumes += 1.0; }
-                        }
-                        rc = run_round();
-                        if (rc) return rc;
-                    }
-                }
-                if (dbg) {
-                    fprintf(stderr, "prune: best %.4f |", s_best / Ntot);
-                    for (int j = 0; j < nb; ++j)
-                        if (fused_batch.c[j].src) fprintf(stderr, " %d/%d:%.3f%s", __builtin_popcount(done[j]), K, acc[j] / std::max(vol_of(done[j]), 1.0), pruned[j] ? "x" : "");
-                    fprintf(stderr, "\n");
-                }
-                for (int j = 0; j < nb; ++j) {
-                    h_rs[j].mx = amx[j];
-                    h_rs[j].hasnan = ahn[j];
-                    h_rs[j].ssim_sum = pruned[j] ? ub[j] : acc[j];        // pruned: the bound it could not exceed (< the best sum)
-                    if (fused_batch.c[j].src) {
-                        c->reg_cand_volumes += vol_of(done[j]) / Ntot;
-                        c->reg_pruned += pruned[j] ? 1 : 0;
-                    }
-                }
-                have_rs = true;
-            }
-        } else if (any_batched) {
-            hipLaunchKernelGGL(ssim_first_pass_batch_kernel<7>, dim3(kStatBlocks, nb), dim3(256), 0, c->stream, im0, S, first_batch, pmax, phasnan);
-            hipLaunchKernelGGL(ssim_yx_batch_kernel<7>, dim3(kStatBlocks, nb), dim3(256), 0, c->stream, yx_batch, setB[2], setB[3], S, batch_cov_norm, C1, C2, psum);
-        }
-        bool any = false;
-        for (int j = 0; j < nb; ++j) any = any || scored[j];
-        if (any && !have_rs) {
-            hipLaunchKernelGGL(finish_region_kernel, dim3(nb), dim3(256), 0, c->stream, pmax, phasnan, psum, reg_out, kStatBlocks);
-            MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-            for (int j = 0; j < nb; ++j) h_rs[j] = h_reg[j];
-        }
-        for (int j = 0; j < nb; ++j) {
-            const int ic = todo[b0 + j];
-            if (code_out[ic] != 0) continue;
-            float region_nanmax = NAN;
-            int region_hasnan = 0;
-            if (scored[j]) {
-                region_hasnan = h_rs[j].hasnan;
-                region_nanmax = (h_rs[j].mx == -INFINITY) ? NAN : h_rs[j].mx;   // all-NaN region
-            }
-            // `if np.nanmax(im1t[mask_slices]) <= im1_min: continue` (Q3: nothing is appended)
-            if (region_nanmax <= (float)im1_min) {
-                code_out[ic] = 2;
-                continue;
-            }
-            const Shape3 R = Rs[j];
-            int min_shape = 0x7fffffff;
-            for (int k = k0; k < 3; ++k) min_shape = std::min(min_shape, (&R.nz)[k]);
-            const int win = std::min(7, min_shape - ((min_shape - 1) % 2));
-            const float region_max = region_hasnan ? NAN : region_nanmax;   // np.max propagates NaN
-            if (win < 3 || region_max <= (float)im1_min || !scored[j]) {
-                ssim_out[ic] = -1.0;
-            } else {
-                const int pad = (win - 1) / 2;
-                double cropn = 1.0;
-                for (int k = k0; k < 3; ++k) cropn *= (double)((&R.nz)[k] - 2 * pad);
-                ssim_out[ic] = h_rs[j].ssim_sum / cropn;
-            }
-        }
+    for (size_t b0 = 0; b0 < todo.size(); b0 += (size_t)sc.nres) {
+        ScoreBatch b;
+        b.nb = (int)std::min<size_t>((size_t)sc.nres, todo.size() - b0);
+        b.ics = todo.data() + b0;
+        b.batched = sc.on_the_fly && sc.shared_x && sc.may_batch;
+        std::fill(sc.resident.begin(), sc.resident.end(), -1);
+        rc = phase_a(sc, b);
+        if (rc) return rc;
+        phase_b(sc, b);
+        rc = score_batch(sc, b, todo.size());
+        if (rc) return rc;
+        decode_results(sc, b);
         if (quality_for_all)
-            for (int j = 0; j < nb; ++j) {
-                const int ic = todo[b0 + j];
+            for (int j = 0; j < b.nb; ++j) {
+                const int ic = b.ics[j];
                 if (code_out[ic] != 0) continue;
-                rc = spearman_from(ic, im1t_buf[j]);
+                rc = spearman_from(sc, ic, sc.im1t_buf[j]);
                 if (rc) return rc;
             }
     }
@@ -2051,7 +2114,7 @@ int mvs_score_candidates_impl(int device, const float* fixed, const float* movin
         for (int ic = 0; ic < n_candidates; ++ic) {
             if (code_out[ic] != 0) continue;
             if (!(ssim_out[ic] == best)) { spearman_out[ic] = NAN; continue; }
-            rc = spearman_from(ic, resident[ic] >= 0 ? im1t_buf[resident[ic]] : (const float*)nullptr);
+            rc = spearman_from(sc, ic, sc.resident[ic] >= 0 ? sc.im1t_buf[sc.resident[ic]] : (const float*)nullptr);
             if (rc) return rc;
         }
     }

@@ -23,6 +23,7 @@ for rep in $(seq $REPS); do
     IFS='|' read -r label envs extra lib <<< "$v"
     cp "${lib:-/tmp/mvs_tree.so}" multiview-stitcher_amd/libmvs_hip.so
     env $envs timeout 600 python bench.py $ARGS $extra > gpurun_out/ab.json 2> gpurun_out/ab.err
+    rc=$?; [ $rc -eq 0 ] || { echo "$label: bench.py ended with status $rc" | tee -a $O; cp /tmp/mvs_tree.so multiview-stitcher_amd/libmvs_hip.so; exit $rc; }   # a failed run ends the job
     python - "$label" <<'PY' | tee -a $O
 import json, sys
 try:
