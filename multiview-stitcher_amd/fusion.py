@@ -11,25 +11,29 @@ the kernel arguments the way the reference derives scipy's.
 
 from __future__ import annotations
 
+import collections
+import contextlib
 import ctypes as C
-from itertools import product
-
+import functools
+import gc
+import inspect
 import os
 import shutil
-
 import threading
 import time
+import traceback
+import warnings
 
 import numpy as np
 
-from . import _lib, mv_deconv, mv_graph, param_utils, weights
+from . import _lib, msi_utils, mv_deconv, mv_graph, ngff_utils, param_utils, streaming, weights, zarr_io
+from . import device as dev_mod
 from .mv_deconv import PSFType, multi_view_deconvolution  # noqa: F401  (fusion.multi_view_deconvolution, fusion.PSFType)
 from .weights import content_based_dct  # noqa: F401  (fusion.content_based_dct)
 from . import spatial_image_utils as si_utils
 from .device import DeviceArray, is_device_array
-from .transformation import _as_zyx, embed3_stack, fill_view_geometry, get_pixel_affine, get_pixel_affines, shape3, view_data
-
-BoundingBox = dict
+from .transformation import (_as_zyx, check_interpolation_order, embed3_stack, fill_view_geometry, get_pixel_affine, get_pixel_affines,
+                             shape3, transform_sim, view_data)
 
 
 # --- built-in fusion / weight functions: markers dispatched to kernel modes ------------------
@@ -89,22 +93,10 @@ def builtin(func):
     return BUILTIN[name]
 
 
-def _fusion_code(fusion_func):
-    try:
-        return _FUSION_CODES[fusion_func]
-    except (KeyError, TypeError):
-        raise NotImplementedError(
-            "backend='hip' fuses with the built-in fusion functions (weighted_average_fusion, "
-            "max_fusion, simple_average_fusion); custom callables are not supported"
-        ) from None
-
-
-def _weights_code(weights_func):
-    if weights_func is None:
-        return _lib.MVS_WEIGHTS_NONE
-    if weights_func is content_based or weights_func == "content_based":
-        return _lib.MVS_WEIGHTS_CONTENT_BASED
-    raise NotImplementedError("backend='hip' supports weights_func None or content_based")
+def _kernel_fused(fusion_func, weights_func):
+    """Fused by the kernel modes: a block is one ``mvs_fuse_chunk`` launch (a built-in fusion function, weights None or
+    content_based), so the index frame, the block pipeline and -- without weights -- merged launch blocks and the replay apply."""
+    return fusion_func in _FUSION_CODES and (weights_func is None or weights_func is content_based)
 
 
 def _view_frames(sims, spacings, full_view_bbs):
@@ -139,18 +131,15 @@ def _cb_overflowed(device):
     return _lib.get_counter("cb_overflow", device, reset=True) > 0
 
 
-class _cb_exact:
-    """Context manager: content-based weights through the bit-faithful passes (option ``cb_exact``) on ``device``."""
-
-    def __init__(self, device):
-        self.device = device
-
-    def __enter__(self):
-        _lib.set_option("cb_exact", 1, self.device)
-
-    def __exit__(self, *exc):
-        _lib.set_option("cb_exact", 0, self.device)
-        return False
+@contextlib.contextmanager
+def _library_option(name, device):
+    """Library option ``name`` set on ``device`` for the duration.  ``cb_exact``: content-based weights through the
+    bit-faithful passes; ``serial_classes``: the class kernels of a launch stay on the lane's own stream."""
+    _lib.set_option(name, 1, device)
+    try:
+        yield
+    finally:
+        _lib.set_option(name, 0, device)
 
 
 def fuse_np(
@@ -198,54 +187,56 @@ def fuse_np(
     """
     if backend not in ("hip", None):
         raise ValueError("multiview_stitcher_amd.fusion.fuse_np only implements backend='hip'")
-    from .transformation import check_interpolation_order
-
     check_interpolation_order(interpolation_order, "interpolation_order")
     lib = _lib.init(device)
     sdims = si_utils.get_spatial_dims_from_sim(sims[0])
-    ndim = len(sdims)
-    out_bb = _bb_dicts(output_properties, sdims)
-    out_origin = _as_zyx(out_bb["origin"], sdims)
-    out_spacing = _as_zyx(out_bb["spacing"], sdims)
-    out_shape = [int(out_bb["shape"][d]) for d in sdims]
     input_dtype = np.dtype(sims[0].dtype)
     if input_dtype not in _lib.DTYPE_CODES:
         raise TypeError(f"unsupported dtype {input_dtype} (uint8/uint16/float32)")
+    spacings, full_view_bbs = _view_frames(sims, spacings, full_view_bbs)
+    chunk = _Chunk(sims, params, sdims, _bb_dicts(output_properties, sdims), input_dtype, _trim_dict(trim_overlap_in_pixels, sdims), spacings,
+                   [_bb_dicts(b, sdims) for b in full_view_bbs], int(interpolation_order), blending_widths, shrink_distance, device)
     if fusion_func is multi_view_deconvolution:
-        return _fuse_np_deconvolution(
-            sims, params, out_bb, sdims, input_dtype, fusion_func_kwargs, trim_overlap_in_pixels, interpolation_order,
-            full_view_bbs, spacings, blending_widths, shrink_distance, output_on_backend, out, device)
+        return _fuse_np_deconvolution(chunk, fusion_func_kwargs, output_on_backend, out)
     dct = weights_func is content_based_dct and fusion_func in _FUSION_CODES
     if dct and _FUSION_CODES[fusion_func] != _lib.MVS_FUSE_WEIGHTED_AVERAGE:
         dct, weights_func = False, None      # only a fusion_func with fusion_weights asks for them (_core.py:1665)
     elif dct:
         frame_origin, _record = None, None   # the DCT blocks are anchored at the chunk: per-chunk parameters as in the reference
-    if fusion_func not in _FUSION_CODES or (weights_func is not None and weights_func not in (content_based, content_based_dct)):
+    if not dct and not _kernel_fused(fusion_func, weights_func):
         # user callables (docs/extension_api_fusion.md): they run after the resample, so the chunk cannot be fused in one
         # kernel; the voxel work that is ours (resample, blending weights) still runs on the device
-        return _fuse_np_with_callables(
-            sims, params, output_properties, fusion_func, fusion_func_kwargs, weights_func, weights_func_kwargs,
-            trim_overlap_in_pixels, interpolation_order, full_view_bbs, spacings, blending_widths, shrink_distance,
-            output_on_backend, device)
-    fusion_code = _fusion_code(fusion_func)
-    weights_code = _weights_code(None if dct else weights_func)
+        return _fuse_np_with_callables(chunk, fusion_func, fusion_func_kwargs, weights_func, weights_func_kwargs, output_on_backend)
+    weights_code = _lib.MVS_WEIGHTS_CONTENT_BASED if weights_func is content_based else _lib.MVS_WEIGHTS_NONE
+    frame = _index_frame(chunk, frame_origin, _record)
+    views, ptrs, mems, keep = _view_records(chunk, frame)
+    opts, dopts = _fuse_opts(chunk, _FUSION_CODES[fusion_func], weights_code, weights_func_kwargs, frame.index_origin, dct)
+    return _launch_chunk(lib, chunk, views, opts, dopts, out, output_on_backend, weights_code and _cb_check, _record, ptrs, mems)
 
-    spacings, full_view_bbs = _view_frames(sims, spacings, full_view_bbs)
 
-    n = len(sims)
-    views = (_lib.mvs_view_t * n)()
-    keep = []
-    # the view records are computed for all views at once (stacked arrays: the per-view form of the same arithmetic costs
-    # ~70 us of interpreter time per view) and written into the ctypes array through a byte view
-    p_stack = np.stack([np.asarray(p, dtype=np.float64) for p in params])
-    p_inv = np.linalg.inv(p_stack)
-    in_spacings = np.stack([_as_zyx(sp if sp is not None else si_utils.get_spacing_from_sim(sim), sdims) for sim, sp in zip(sims, spacings)])
-    in_origins = np.stack([si_utils.get_origin_from_sim(sim, asarray=True) for sim in sims])
-    fv = [_bb_dicts(b, sdims) for b in full_view_bbs]
-    full_origins = np.stack([_as_zyx(b["origin"], sdims) for b in fv])
-    # index frame: chunk and slabs as integer shifts of parameters derived for (frame origin, whole view)
+# One fuse_np call with its arguments normalised, as the three forms (kernel modes, deconvolution, callables) receive it:
+# ``out_bb`` the chunk box incl. halo as dict-of-dicts, ``trim`` the halo to cut per spatial dim, ``spacings`` a slab's spacing or
+# None (= read it from the slab), ``full_view_bbs`` the whole views' boxes as dict-of-dicts (see ``_view_frames``).
+_Chunk = collections.namedtuple(
+    "_Chunk", "sims params sdims out_bb input_dtype trim spacings full_view_bbs order blending_widths shrink_distance device")
+
+# The index frame of one chunk (``_index_frame``): integer shifts of the chunk (``index_origin``, 3) and of every slab
+# (``index_offsets``, (n, 3)) against the origins the parameters are derived for (``out_origin``; ``in_origins`` per view); next
+# to them the stacked per-view geometry they were computed from.
+_Frame = collections.namedtuple("_Frame", "index_origin index_offsets out_origin in_origins in_spacings full_origins")
+
+
+def _index_frame(chunk, frame_origin, record):
+    """Chunk and slabs as integer index shifts of parameters derived for (frame origin, whole view) -- or, without a
+    ``frame_origin`` or with one that does not apply (an origin off the frame's grids: ``IndexFrameWarning``, attributed to
+    fuse_np's caller), no shifts and the chunk's and slabs' own origins."""
+    sdims, ndim, n = chunk.sdims, len(chunk.sdims), len(chunk.sims)
+    out_origin, out_spacing = _as_zyx(chunk.out_bb["origin"], sdims), _as_zyx(chunk.out_bb["spacing"], sdims)
+    in_spacings = np.stack([_as_zyx(sp if sp is not None else si_utils.get_spacing_from_sim(sim), sdims)
+                            for sim, sp in zip(chunk.sims, chunk.spacings)])
+    in_origins = np.stack([si_utils.get_origin_from_sim(sim, asarray=True) for sim in chunk.sims])
+    full_origins = np.stack([_as_zyx(b["origin"], sdims) for b in chunk.full_view_bbs])
     index_origin, index_offsets = np.zeros(3, np.int64), np.zeros((n, 3), np.int64)
-    ref_out_origin, ref_in_origins = out_origin, in_origins
     if frame_origin is not None:
         f_origin = _as_zyx(frame_origin, sdims)
         io_ = (out_origin - f_origin) / out_spacing
@@ -253,28 +244,36 @@ def fuse_np(
         if np.all(np.abs(io_ - np.round(io_)) < 1e-6) and np.all(np.abs(so_ - np.round(so_)) < 1e-6):
             index_origin[3 - ndim:] = np.round(io_).astype(np.int64)
             index_offsets[:, 3 - ndim:] = np.round(so_).astype(np.int64)
-            ref_out_origin, ref_in_origins = f_origin, full_origins
-        else:
-            import warnings
+            return _Frame(index_origin, index_offsets, f_origin, full_origins, in_spacings, full_origins)
+        off_c = float(np.abs(io_ - np.round(io_)).max()) if io_.size else 0.0
+        off_s = float(np.abs(so_ - np.round(so_)).max()) if so_.size else 0.0      # (a chunk without views has no slabs)
+        warnings.warn(
+            "fuse_np: frame_origin cannot be applied -- the chunk origin or a slab origin is not on the frame's grid "
+            f"(largest distance from it: chunk {off_c:.3g} px, slabs {off_s:.3g} px); the parameters of this chunk are derived per chunk, so its "
+            "voxels may differ in the last bit from the same voxels fused through another chunk, launch block or shard",
+            IndexFrameWarning, stacklevel=3)
+        if record is not None:
+            record["no_replay"] = True      # (a replayed call would not repeat the warning)
+    return _Frame(index_origin, index_offsets, out_origin, in_origins, in_spacings, full_origins)
 
-            off_c = float(np.abs(io_ - np.round(io_)).max()) if io_.size else 0.0
-            off_s = float(np.abs(so_ - np.round(so_)).max()) if so_.size else 0.0      # (a chunk without views has no slabs)
-            warnings.warn(
-                "fuse_np: frame_origin cannot be applied -- the chunk origin or a slab origin is not on the frame's grid "
-                f"(largest distance from it: chunk {off_c:.3g} px, slabs {off_s:.3g} px); the parameters of this chunk are derived per chunk, so its "
-                "voxels may differ in the last bit from the same voxels fused through another chunk, launch block or shard",
-                IndexFrameWarning, stacklevel=2)
-            if _record is not None:
-                _record["no_replay"] = True      # (a replayed call would not repeat the warning)
-    matrices, offsets = get_pixel_affines(p_inv, ref_in_origins, in_spacings, ref_out_origin, out_spacing)
+
+def _view_records(chunk, frame):
+    """The ``mvs_view_t`` array of a chunk: ``(views, data pointers, memory codes, keep-alive list)``."""
+    sdims, device, n = chunk.sdims, chunk.device, len(chunk.sims)
+    views = (_lib.mvs_view_t * n)()
+    keep = []
+    # the view records are computed for all views at once (stacked arrays: the per-view form of the same arithmetic costs
+    # ~70 us of interpreter time per view) and written into the ctypes array through a byte view
+    p_inv = np.linalg.inv(np.stack([np.asarray(p, dtype=np.float64) for p in chunk.params]))
+    out_spacing = _as_zyx(chunk.out_bb["spacing"], sdims)
+    matrices, offsets = get_pixel_affines(p_inv, frame.in_origins, frame.in_spacings, frame.out_origin, out_spacing)
     tables, sup_origins, sup_spacings = weights.blending_supports(
-        full_origins, np.stack([_as_zyx(b["spacing"], sdims) for b in fv]),
-        np.stack([_as_zyx(b["shape"], sdims) for b in fv]), sdims, blending_widths, shrink_distance)
-    w_matrices, w_offsets = get_pixel_affines(p_inv, sup_origins, sup_spacings, ref_out_origin, out_spacing)
-    ptrs, shapes, strides = np.zeros(n, np.uint64), np.ones((n, 3), np.int64), np.zeros((n, 3), np.int64)
-    mems = np.zeros(n, np.int32)
-    for i, sim in enumerate(sims):
-        ptrs[i], shapes[i], strides[i], mems[i], data = view_data(sim.data, device, input_dtype)
+        frame.full_origins, np.stack([_as_zyx(b["spacing"], sdims) for b in chunk.full_view_bbs]),
+        np.stack([_as_zyx(b["shape"], sdims) for b in chunk.full_view_bbs]), sdims, chunk.blending_widths, chunk.shrink_distance)
+    w_matrices, w_offsets = get_pixel_affines(p_inv, sup_origins, sup_spacings, frame.out_origin, out_spacing)
+    ptrs, mems, shapes, strides = np.zeros(n, np.uint64), np.zeros(n, np.int32), np.ones((n, 3), np.int64), np.zeros((n, 3), np.int64)
+    for i, sim in enumerate(chunk.sims):
+        ptrs[i], shapes[i], strides[i], mems[i], data = view_data(sim.data, device, chunk.input_dtype)
         keep.append(data)
     V = _lib.mvs_view_t
     rec = np.frombuffer(views, dtype=np.uint8).reshape(n, C.sizeof(V))
@@ -286,7 +285,7 @@ def fuse_np(
     m3, o3 = embed3_stack(matrices, offsets)
     wm3, wo3 = embed3_stack(w_matrices, w_offsets)
     field("data", np.uint64, 1)[:, 0] = ptrs
-    field("dtype", np.int32, 1)[:, 0] = _lib.DTYPE_CODES[input_dtype]
+    field("dtype", np.int32, 1)[:, 0] = _lib.DTYPE_CODES[chunk.input_dtype]
     field("mem", np.int32, 1)[:, 0] = mems
     field("shape", np.int64, 3)[:] = shapes
     field("stride", np.int64, 3)[:] = strides
@@ -294,80 +293,89 @@ def fuse_np(
     field("offset", np.float64, 3)[:] = o3
     field("w_matrix", np.float64, 9)[:] = wm3
     field("w_offset", np.float64, 3)[:] = wo3
-    field("index_offset", np.int64, 3)[:] = index_offsets
+    field("index_offset", np.int64, 3)[:] = frame.index_offsets
     edt = field("edt", np.float32, 125)
     edt[:] = 0
     for i, table in enumerate(tables):
         edt[i, : table.size] = table.reshape(-1)
+    return views, ptrs, mems, keep
 
-    trim = _trim_dict(trim_overlap_in_pixels, sdims)
-    res_shape = [out_shape[i] - 2 * trim[d] for i, d in enumerate(sdims)]
 
+def _fuse_opts(chunk, fusion_code, weights_code, weights_func_kwargs, index_origin, dct):
+    """The ``mvs_fuse_opts_t`` of a chunk (``out_mem`` is set by the launch) and, with ``dct``, its ``mvs_dct_opts_t``."""
+    sdims, ndim = chunk.sdims, len(chunk.sdims)
     opts = _lib.mvs_fuse_opts_t()
     opts.ndim = ndim
-    opts.order = int(interpolation_order)
+    opts.order = chunk.order
     opts.fusion = fusion_code
     opts.weights = weights_code
-    s3, t3 = shape3(out_shape), [0] * (3 - ndim) + [trim[d] for d in sdims]
+    s3, t3 = shape3([int(chunk.out_bb["shape"][d]) for d in sdims]), [0] * (3 - ndim) + [chunk.trim[d] for d in sdims]
     for k in range(3):
         opts.out_shape[k] = s3[k]
         opts.trim[k] = t3[k]
+        opts.index_origin[k] = int(index_origin[k])
     wk = weights_func_kwargs or {}
     opts.sigma_1 = float(wk.get("sigma_1", 5))
     opts.sigma_2 = float(wk.get("sigma_2", 11))
-    opts.out_dtype = _lib.DTYPE_CODES[input_dtype]
-    for k in range(3):
-        opts.index_origin[k] = int(index_origin[k])
-    if dct:
-        # content_based_dct's arguments as the reference passes them (_core.py:1665-1682): output_chunksize defaults to the
-        # chunk's shape including the halo
-        dkw = dict(wk)
-        for k in ("transformed_views", "device"):
-            if k in dkw:
-                raise TypeError(f"weights_func_kwargs must not set {k!r}: fuse_np supplies it")
-        if dkw.get("output_chunksize") is None:
-            dkw["output_chunksize"] = dict(out_bb["shape"])
-        dopts = weights.dct_opts(ndim, **dkw)
+    opts.out_dtype = _lib.DTYPE_CODES[chunk.input_dtype]
+    if not dct:
+        return opts, None
+    # content_based_dct's arguments as the reference passes them (_core.py:1665-1682): output_chunksize defaults to the
+    # chunk's shape including the halo
+    dkw = dict(wk)
+    for k in ("transformed_views", "device"):
+        if k in dkw:
+            raise TypeError(f"weights_func_kwargs must not set {k!r}: fuse_np supplies it")
+    if dkw.get("output_chunksize") is None:
+        dkw["output_chunksize"] = dict(chunk.out_bb["shape"])
+    return opts, weights.dct_opts(ndim, **dkw)
+
+
+def _launch_chunk(lib, chunk, views, opts, dopts, out, output_on_backend, cb_check, record, ptrs, mems):
+    """One ``mvs_fuse_chunk`` (``mvs_fuse_chunk_dct`` with ``dopts``) launch into ``out`` / a new device array / a new host
+    array.  ``cb_check``: a content-based result left on the device is checked for a mask-list overflow.  ``record``: where
+    fuse()'s geometry-keyed replay remembers a launch whose views are all resident on the device (``mems``), or None."""
+    device, n = chunk.device, len(views)
+    res_shape = [int(chunk.out_bb["shape"][d]) - 2 * chunk.trim[d] for d in chunk.sdims]
 
     def launch(dst):
-        if dct:
+        if dopts is not None:
             return lib.mvs_fuse_chunk_dct(device, views, n, C.byref(opts), C.byref(dopts), dst), "mvs_fuse_chunk_dct"
         return lib.mvs_fuse_chunk(device, views, n, C.byref(opts), dst), "mvs_fuse_chunk"
 
     if out is not None or output_on_backend:
         if out is None:
-            out = DeviceArray.empty(res_shape, input_dtype, device)
+            out = DeviceArray.empty(res_shape, chunk.input_dtype, device)
         if tuple(out.shape) != tuple(res_shape) or not out.is_contiguous():
             raise ValueError("out must be a contiguous DeviceArray of the result shape")
         opts.out_mem = _lib.MVS_MEM_DEVICE
         rc, what = launch(C.c_void_p(out.ptr))
         _lib.check(rc, device, what)
-        if weights_code and _cb_check and _cb_overflowed(device):
+        if cb_check and _cb_overflowed(device):
             # the fast content-based path lists the voxels its box-shaped mask lacks; a list that did not fit raised a flag
             # (a result left on the device is not waited for inside the call): this chunk again through the bit-faithful passes
-            with _cb_exact(device):
+            with _library_option("cb_exact", device):
                 rc = lib.mvs_fuse_chunk(device, views, n, C.byref(opts), C.c_void_p(out.ptr))
                 _lib.check(rc, device, "mvs_fuse_chunk")
         out.mark_written()
-        if _record is not None and bool(np.all(mems == _lib.MVS_MEM_DEVICE)):
-            # (fuse()'s geometry-keyed replay: the view records without their data pointers, the options, the result shape)
-            _record.update(views=bytes(views), opts=bytes(opts), n=n, res_shape=tuple(int(v) for v in res_shape), ptrs=ptrs.copy())
+        if record is not None and bool(np.all(mems == _lib.MVS_MEM_DEVICE)):
+            # (the view records without their data pointers, the options, the result shape)
+            record.update(views=bytes(views), opts=bytes(opts), n=n, res_shape=tuple(int(v) for v in res_shape), ptrs=ptrs.copy())
         return out
-    result = np.empty(tuple(res_shape), dtype=input_dtype)
+    result = np.empty(tuple(res_shape), dtype=chunk.input_dtype)
     opts.out_mem = _lib.MVS_MEM_HOST
     rc, what = launch(result.ctypes.data)
     _lib.check(rc, device, what)
     return result
 
 
-def _fuse_np_deconvolution(sims, params, out_bb, sdims, input_dtype, fusion_func_kwargs, trim_overlap_in_pixels,
-                           interpolation_order, full_view_bbs, spacings, blending_widths, shrink_distance, output_on_backend,
-                           out, device):
+def _fuse_np_deconvolution(chunk, fusion_func_kwargs, output_on_backend, out):
     """fuse_np with ``fusion_func=multi_view_deconvolution`` (_core.py:1608-1713 around mv_deconv.py:251-501), all on the
     device: every view resampled by mvs_resample (float32, NaN outside) and its blending weights by mvs_blend_weights
     into two (V, *S) stacks; mvs_mv_deconv masks the weights by ~isnan and normalises them, deconvolves, trims the halo,
     applies nan_to_num and casts to the input dtype.  ``output_spacing`` is the chunk spacing unless the caller passed
     one (_core.py:1658-1662).  Only the result crosses PCIe, and only when a host result is asked for."""
+    sims, params, sdims, out_bb, device = chunk.sims, chunk.params, chunk.sdims, chunk.out_bb, chunk.device
     lib = _lib.init(device)
     ndim = len(sdims)
     kw = dict(fusion_func_kwargs or {})
@@ -376,7 +384,6 @@ def _fuse_np_deconvolution(sims, params, out_bb, sdims, input_dtype, fusion_func
             raise TypeError(f"fusion_func_kwargs must not set {k!r}: fuse_np supplies it")
     if kw.get("output_spacing") is None:
         kw["output_spacing"] = dict(out_bb["spacing"])
-    spacings, full_view_bbs = _view_frames(sims, spacings, full_view_bbs)
     out_shape = tuple(int(out_bb["shape"][d]) for d in sdims)
     o_origin, o_spacing = _as_zyx(out_bb["origin"], sdims), _as_zyx(out_bb["spacing"], sdims)
     n = len(sims)
@@ -387,7 +394,7 @@ def _fuse_np_deconvolution(sims, params, out_bb, sdims, input_dtype, fusion_func
     blend = DeviceArray.empty((n,) + out_shape, np.float32, device)
     s3 = _lib.i64x3(shape3(out_shape))
     keep = []
-    for i, (sim, param, spacing) in enumerate(zip(sims, params, spacings)):
+    for i, (sim, param, spacing) in enumerate(zip(sims, params, chunk.spacings)):
         p_inv = np.linalg.inv(np.asarray(param, dtype=np.float64))
         in_spacing = spacing if spacing is not None else si_utils.get_spacing_from_sim(sim)
         matrix, offset = get_pixel_affine(p_inv, si_utils.get_origin_from_sim(sim, asarray=True), _as_zyx(in_spacing, sdims),
@@ -396,20 +403,19 @@ def _fuse_np_deconvolution(sims, params, out_bb, sdims, input_dtype, fusion_func
         ptr, shape, strides, mem, data = view_data(sim.data, device)
         fill_view_geometry(view, ptr, _lib.DTYPE_CODES[data.dtype], mem, shape, strides, matrix, offset)
         keep.append(data)
-        rc = lib.mvs_resample(device, C.byref(view), s3, int(interpolation_order), float("nan"), C.c_void_p(views_t.ptr + 4 * i * S),
+        rc = lib.mvs_resample(device, C.byref(view), s3, chunk.order, float("nan"), C.c_void_p(views_t.ptr + 4 * i * S),
                               _lib.MVS_MEM_DEVICE)
         _lib.check(rc, device, "mvs_resample")
         wview = _lib.mvs_view_t()
-        weights.fill_view_weights(wview, _bb_dicts(full_view_bbs[i], sdims), param, o_origin, o_spacing, blending_widths,
-                                  shrink_distance)
+        weights.fill_view_weights(wview, chunk.full_view_bbs[i], param, o_origin, o_spacing, chunk.blending_widths,
+                                  chunk.shrink_distance)
         rc = lib.mvs_blend_weights(device, C.byref(wview), ndim, s3, C.c_void_p(blend.ptr + 4 * i * S), _lib.MVS_MEM_DEVICE)
         _lib.check(rc, device, "mvs_blend_weights")
-    trim = list(_trim_dict(trim_overlap_in_pixels, sdims).values())
+    trim = list(chunk.trim.values())
     on_device = out is not None or output_on_backend
     res = mv_deconv._run(views_t, blend, ndim, kernels, kw.get("n_iterations", 10), kw.get("lambda_reg", 0.0),
-                         kw.get("min_value", 1e-4), kw.get("sample_boundary_erosion_px", 0), trim, input_dtype, on_device, device,
+                         kw.get("min_value", 1e-4), kw.get("sample_boundary_erosion_px", 0), trim, chunk.input_dtype, on_device, device,
                          prepare_weights=True, out=out)
-    del keep
     return res
 
 
@@ -443,50 +449,40 @@ _HOST_FUSION = {weighted_average_fusion: _host_weighted_average_fusion, max_fusi
 
 def has_keyword(func, keyword):
     """misc_utils.has_keyword (misc_utils.py:69-80): does ``func`` accept ``keyword``?"""
-    import inspect
-
     try:
         return keyword in inspect.signature(func).parameters
     except (TypeError, ValueError):
         return False
 
 
-def _fuse_np_with_callables(sims, params, output_properties, fusion_func, fusion_func_kwargs, weights_func,
-                            weights_func_kwargs, trim_overlap_in_pixels, interpolation_order, full_view_bbs, spacings,
-                            blending_widths, shrink_distance, output_on_backend, device):
+def _fuse_np_with_callables(chunk, fusion_func, fusion_func_kwargs, weights_func, weights_func_kwargs, output_on_backend):
     """fuse_np for user-supplied ``fusion_func`` / ``weights_func`` callables (_core.py:1608-1733): every view is
     resampled with mvs_resample (float32, NaN outside), blending weights come from mvs_blend_weights and are
     normalised like weights.normalize_weights (weights.py:325-345); the callables then receive host float32
     arrays exactly as in the reference (``transformed_views`` (V, *S), ``blending_weights``, ``fusion_weights``,
     ``params``, ``output_spacing`` / ``output_chunksize`` when they ask for them)."""
-    from .transformation import transform_sim
-
+    sims, params, sdims, out_bb, device = chunk.sims, chunk.params, chunk.sdims, chunk.out_bb, chunk.device
     # A custom weights_func with one of the built-in fusion functions (the documented extension case, _core.py:1663-1690):
     # the built-ins are kernel modes here, so their host form takes over behind the user's weights.
     fusion_func = _HOST_FUSION.get(fusion_func, fusion_func) if not isinstance(fusion_func, str) else _HOST_FUSION[BUILTIN[fusion_func + "_fusion"]]
     fusion_func_kwargs = dict(fusion_func_kwargs or {})
     weights_func_kwargs = dict(weights_func_kwargs or {})
-    sdims = si_utils.get_spatial_dims_from_sim(sims[0])
-    input_dtype = np.dtype(sims[0].dtype)
-    spacings, full_view_bbs = _view_frames(sims, spacings, full_view_bbs)
-    out_bb = _bb_dicts(output_properties, sdims)
 
     def host(a):
         return a.get() if is_device_array(a) else np.asarray(a)
 
     views_t = np.stack([
         host(transform_sim(sim, np.linalg.inv(np.asarray(param, dtype=np.float64)), output_stack_properties=out_bb,
-                           input_spacing=spacing, order=interpolation_order, cval=np.nan, device=device,
+                           input_spacing=spacing, order=chunk.order, cval=np.nan, device=device,
                            allow_noop=False).data).astype(np.float32, copy=False)
-        for sim, param, spacing in zip(sims, params, spacings)
+        for sim, param, spacing in zip(sims, params, chunk.spacings)
     ])
     needs_blending = has_keyword(fusion_func, "blending_weights") or (
         weights_func is not None and has_keyword(weights_func, "blending_weights"))
     blend = None
     if needs_blending:
         blend = np.stack([
-            weights.get_blending_weights(out_bb, _bb_dicts(full_view_bbs[i], sdims), params[i], blending_widths,
-                                         shrink_distance, device)
+            weights.get_blending_weights(out_bb, chunk.full_view_bbs[i], params[i], chunk.blending_widths, chunk.shrink_distance, device)
             for i in range(len(sims))
         ])
         blend = blend * ~np.isnan(views_t)
@@ -511,15 +507,13 @@ def _fuse_np_with_callables(sims, params, output_properties, fusion_func, fusion
         if has_keyword(weights_func, "output_chunksize") and "output_chunksize" not in weights_func_kwargs:
             weights_func_kwargs["output_chunksize"] = out_bb["shape"]
         fusion_func_kwargs["fusion_weights"] = weights_func(**weights_func_kwargs)
-    import warnings
-
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", category=RuntimeWarning)   # func_ignore_nan_warning (_core.py:1684-1687)
         fused = np.asarray(fusion_func(**fusion_func_kwargs))
-    trim = _trim_dict(trim_overlap_in_pixels, sdims)
+    trim = chunk.trim
     if any(trim[d] > 0 for d in sdims):
         fused = fused[tuple(slice(trim[d], -trim[d]) if trim[d] > 0 else slice(None) for d in sdims)]
-    fused = np.nan_to_num(fused).astype(input_dtype)
+    fused = np.nan_to_num(fused).astype(chunk.input_dtype)
     if output_on_backend:
         return DeviceArray.from_host(np.ascontiguousarray(fused), device)
     return fused
@@ -684,11 +678,6 @@ class IndexFrameWarning(RuntimeWarning):
     """fuse_np was given a frame_origin it could not apply (an origin off the frame's grid)."""
 
 
-def _is_device_memory_error(exc):
-    """Out of device memory, by the library's error CODE (MVS_ERR_OUT_OF_MEMORY <- hipErrorOutOfMemory), not by message text."""
-    return isinstance(exc, _lib.DeviceMemoryError)
-
-
 # --- chunk -> view-slab plan (_core.py:354-722): computed by the library ---------------------------------
 _PLAN_ENTRY = np.dtype([("block", "<i8", (3,)), ("view", "<i4"), ("planewise", "<i4"), ("lo", "<i8", (3,)), ("n", "<i8", (3,))])
 
@@ -768,8 +757,6 @@ def _replay_key(images, transform_key, fusion_func, device, *args):
     """Everything fuse()'s host work depends on for device-resident plain images, as a hashable -- or None when the call is not
     of that kind.  Per image: the spatial dims, first / second coordinate and length of every axis (origin, spacing, shape as
     the stack-property getters read them), the transform under ``transform_key``, dtype, strides and device of the tile."""
-    from . import msi_utils
-
     try:
         first = images[0]
         if msi_utils.is_msim(first) or fusion_func not in _FUSION_CODES:
@@ -846,6 +833,37 @@ def _halo_overlap(overlap_in_pixels, sdims, funcs, output_chunksize):
     return overlap_in_pixels
 
 
+class _FuseCall:
+    """The state of one ``_fuse_once`` call; every step below reads and fills it.  The arguments of ``fuse()`` under their own
+    names (``images`` with the ``sims`` alias resolved; ``batch_options`` / ``zarr_options`` as dicts once parsed), and:
+
+    replay_key, record   key of the geometry-keyed replay, and the dict fuse_np records its launch in (None: not eligible)
+    views                ``list(images)``, plain SpatialImages
+    dtype                dtype of the views and of the result
+    sdims, nsdims        spatial / non-spatial dims of the views
+    ns_shape, n_fields   sizes of the non-spatial dims = the grid of (c, t) fields, and their number
+    osp                  the output stack (origin, spacing, shape) as dict-of-dicts
+    params, views_bb     per view: the affine under ``transform_key`` (may be t-stacked), the stack properties
+    halo                 overlap per spatial dim a block is fused with (``_halo_overlap``)
+    chunksize            the requested chunk size per spatial dim: the chunk grid of a Zarr output
+    streamed             blocks pass through host memory one by one (Zarr in or out, large host arrays)
+    block_size           size of a launch block: ``chunksize``, or whole multiples of it (``merge_chunks``)
+    norm_chunks          per spatial axis the extents of the blocks in the result (with the halo when it is not trimmed)
+    result_shape         spatial shape of the result: the output stack's, or the assembly of the untrimmed blocks
+    blocks               per launch block ``block_index`` (its grid index), ``bb_halo`` (its box with the halo: what fuse_np
+                         fuses) and ``window`` (the slices of the result it covers)
+    zarr_out             the open output array (None without ``output_zarr_url``)
+    ome_zarr             the output is level 0 of an NGFF image of version ``ngff_version``: the epilogue adds the pyramid
+    result, dev_full     the host / the device result for all fields (None: the result is elsewhere)
+    plans                per time point ``(affines, entries)``, see ``_plan_for``
+    """
+
+    def __init__(self, **arguments):
+        self.__dict__.update(arguments)
+        self.replay_key = self.record = self.zarr_out = self.result = self.dev_full = None
+        self.ome_zarr, self.plans = False, {}
+
+
 def _fuse_once(
     images=None,
     transform_key=None,
@@ -905,399 +923,400 @@ def _fuse_once(
         raise TypeError("fuse() got both 'images' and deprecated 'sims'. Use only 'images'.")
     if not images:
         raise ValueError("images must contain at least one image.")
-    # Device-resident tiles fused into one device-resident launch block: everything the interpreter derives for the call -- output
-    # stack, chunk plan, slab windows, the view records of mvs_fuse_chunk -- is a function of the views' geometry and the
-    # arguments, not of the voxels.  It is derived once per geometry and replayed with the current data pointers afterwards
-    # (a register + fuse loop over time points or channels of one mosaic pays the ~2 ms of host work once).
-    fast_key, record = None, None
-    if (_REPLAY[0] and output_on_backend and output_zarr_url is None and not batch_options and chunk_filter is None and merge_chunks
-            and weights_func is None and not fusion_func_kwargs and not weights_func_kwargs and not zarr_options and backend in ("hip", None)):
-        fast_key = _replay_key(images, transform_key, fusion_func, device, output_spacing, output_stack_mode, output_origin, output_shape,
-                               output_stack_properties, output_chunksize, overlap_in_pixels, trim_overlap, interpolation_order,
-                               blending_widths, frame_origin)
-        if fast_key is not None:
-            with _REPLAY_LOCK:
-                hit = _REPLAY_MEMO.get(fast_key)
-            if hit is not None:
-                return _replay_fuse(hit, images, transform_key, device)
-            record = {}
+    call = _FuseCall(
+        images=images, transform_key=transform_key, fusion_func=fusion_func, fusion_func_kwargs=fusion_func_kwargs, weights_func=weights_func,
+        weights_func_kwargs=weights_func_kwargs, output_spacing=output_spacing, output_stack_mode=output_stack_mode, output_origin=output_origin,
+        output_shape=output_shape, output_stack_properties=output_stack_properties, output_chunksize=output_chunksize,
+        overlap_in_pixels=overlap_in_pixels, trim_overlap=trim_overlap, interpolation_order=interpolation_order, blending_widths=blending_widths,
+        output_zarr_url=output_zarr_url, zarr_options=zarr_options, batch_options=batch_options, backend=backend,
+        output_on_backend=output_on_backend, device=device, chunk_filter=chunk_filter, merge_chunks=merge_chunks, frame_origin=frame_origin)
+    hit = _replay_lookup(call)
+    if hit is not None:
+        return _replay_fuse(hit, images, transform_key, device)
     if output_zarr_url is not None and output_on_backend:
         raise ValueError("output_zarr_url streams chunks to disk; it cannot be combined with output_on_backend")
     if backend not in ("hip", None):
         raise ValueError("multiview_stitcher_amd.fusion.fuse only implements backend='hip'")
-    from . import msi_utils
-
     is_ms = [msi_utils.is_msim(im) for im in images]
     if any(is_ms) and not all(is_ms):
         raise ValueError("All input images must be of the same kind: either all SpatialImages or all MultiscaleSpatialImages.")
     if all(is_ms):
-        # MultiscaleSpatialImages in, a multiscale result out (fusion/_core.py:939-1064): scale0 defines the finest output
-        # geometry; every output level is FUSED from the coarsest input level that is still fine enough for it (not
-        # downsampled from the level above); a Zarr output is one level fused from the matching input level.
-        msims = list(images)
-        common = dict(transform_key=transform_key, fusion_func=fusion_func, fusion_func_kwargs=fusion_func_kwargs,
-                      weights_func=weights_func, weights_func_kwargs=weights_func_kwargs, output_stack_mode=output_stack_mode,
-                      output_chunksize=output_chunksize, overlap_in_pixels=overlap_in_pixels, trim_overlap=trim_overlap,
-                      interpolation_order=interpolation_order, blending_widths=blending_widths, backend=backend, device=device,
-                      chunk_filter=chunk_filter, merge_chunks=merge_chunks)
-        scale0 = [msi_utils.get_sim_from_msim(m, scale="scale0") for m in msims]
-        sdims0 = si_utils.get_spatial_dims_from_sim(scale0[0])
-        osp0 = _bb_dicts(process_output_stack_properties(scale0, output_spacing, output_origin, output_shape, output_stack_properties,
-                                                         output_stack_mode, transform_key), sdims0)
+        return _fuse_multiscale(call)
+    _output_geometry(call)
+    _launch_blocks(call)
+    _chunk_grid(call)
+    _check_batch_options(call)
+    _open_zarr_output(call)
+    _allocate_result(call)
+    if call.batch_options:
+        _fuse_batches(call)
+    else:
+        for ns_index in np.ndindex(*call.ns_shape) if call.ns_shape else [()]:
+            _fuse_field(call, ns_index)
+    _record_replay(call)
+    return _wrap_result(call)
 
-        def level_sims(spacing):
-            return [msi_utils.get_sim_from_msim(m, scale="scale%d" % msi_utils.get_res_level_from_spacing(m, spacing)) for m in msims]
 
-        if output_zarr_url is not None:
-            fused = fuse(images=level_sims(osp0["spacing"]), output_stack_properties=osp0, output_zarr_url=output_zarr_url,
-                               zarr_options=zarr_options, batch_options=batch_options, frame_origin=frame_origin, **common)
-            if (zarr_options or {}).get("ome_zarr", False) and chunk_filter is None:
-                from . import ngff_utils
+def _replay_lookup(call):
+    """Device-resident tiles fused into one device-resident launch block: everything the interpreter derives for the call --
+    output stack, chunk plan, slab windows, the view records of mvs_fuse_chunk -- is a function of the views' geometry and the
+    arguments, not of the voxels.  It is derived once per geometry and replayed with the current data pointers afterwards
+    (a register + fuse loop over time points or channels of one mosaic pays the ~2 ms of host work once).  Returns the
+    remembered derivation, or None after setting ``replay_key`` / ``record`` when this call may make one."""
+    if not (_REPLAY[0] and call.output_on_backend and call.output_zarr_url is None and not call.batch_options and call.chunk_filter is None
+            and call.merge_chunks and call.weights_func is None and not call.fusion_func_kwargs and not call.weights_func_kwargs
+            and not call.zarr_options and call.backend in ("hip", None)):
+        return None
+    call.replay_key = _replay_key(
+        call.images, call.transform_key, call.fusion_func, call.device, call.output_spacing, call.output_stack_mode, call.output_origin,
+        call.output_shape, call.output_stack_properties, call.output_chunksize, call.overlap_in_pixels, call.trim_overlap,
+        call.interpolation_order, call.blending_widths, call.frame_origin)
+    if call.replay_key is None:
+        return None
+    with _REPLAY_LOCK:
+        hit = _REPLAY_MEMO.get(call.replay_key)
+    if hit is None:
+        call.record = {}
+    return hit
 
-                return ngff_utils.read_msim_from_ome_zarr(output_zarr_url, transform_key=transform_key if transform_key is not None
-                                                          else si_utils.DEFAULT_TRANSFORM_KEY)
-            return msi_utils.get_msim_from_sim(fused, scale_factors=[])
-        shapes, _, abs_factors = msi_utils.calc_resolution_levels({d: int(osp0["shape"][d]) for d in sdims0})
-        fused_levels = []
-        for shape, f in zip(shapes, abs_factors):
-            props = {"shape": dict(shape), "spacing": {d: osp0["spacing"][d] * f[d] for d in sdims0},
-                     # centre-of-pixel convention of downsampled levels (as in the OME-Zarr pyramid)
-                     "origin": {d: osp0["origin"][d] + (f[d] - 1) * osp0["spacing"][d] / 2 for d in sdims0}}
-            # (a caller's frame_origin refers to the scale0 grid: a coarser level's grid is displaced by (f - 1) * spacing / 2
-            # against it, so the level keeps its own frame = its own stack origin)
-            level0 = all(int(f[d]) == 1 for d in sdims0)
-            fused_levels.append(fuse(images=level_sims(props["spacing"]), output_stack_properties=props,
-                                           output_on_backend=output_on_backend, frame_origin=frame_origin if level0 else None, **common))
-        return msi_utils.get_msim_from_sims(fused_levels)
-    sims_ = list(images)
 
-    from .transformation import check_interpolation_order
+def _fuse_multiscale(call):
+    """MultiscaleSpatialImages in, a multiscale result out (fusion/_core.py:939-1064): scale0 defines the finest output
+    geometry; every output level is FUSED (one ``fuse`` call) from the coarsest input level that is still fine enough for it
+    (not downsampled from the level above); a Zarr output is one level fused from the matching input level."""
+    common = {k: getattr(call, k) for k in (
+        "transform_key", "fusion_func", "fusion_func_kwargs", "weights_func", "weights_func_kwargs", "output_stack_mode", "output_chunksize",
+        "overlap_in_pixels", "trim_overlap", "interpolation_order", "blending_widths", "backend", "device", "chunk_filter", "merge_chunks")}
+    scale0 = [msi_utils.get_sim_from_msim(m, scale="scale0") for m in call.images]
+    sdims0 = si_utils.get_spatial_dims_from_sim(scale0[0])
+    osp0 = _bb_dicts(process_output_stack_properties(scale0, call.output_spacing, call.output_origin, call.output_shape,
+                                                     call.output_stack_properties, call.output_stack_mode, call.transform_key), sdims0)
 
-    check_interpolation_order(interpolation_order, "interpolation_order")
-    output_chunksize = process_output_chunksize(sims_, output_chunksize)
-    output_stack_properties = process_output_stack_properties(
-        sims_, output_spacing, output_origin, output_shape, output_stack_properties, output_stack_mode, transform_key
-    )
-    sdims = si_utils.get_spatial_dims_from_sim(sims_[0])
-    nsdims = si_utils.get_nonspatial_dims_from_sim(sims_[0])
-    output_stack_properties = _bb_dicts(output_stack_properties, sdims)
-    output_stack_properties["shape"] = {d: int(v) for d, v in output_stack_properties["shape"].items()}
-    params = [si_utils.get_affine_from_sim(sim, transform_key) for sim in sims_]
+    def level_sims(spacing):
+        return [msi_utils.get_sim_from_msim(m, scale="scale%d" % msi_utils.get_res_level_from_spacing(m, spacing)) for m in call.images]
 
-    overlap_in_pixels = _halo_overlap(overlap_in_pixels, sdims, [(weights_func, weights_func_kwargs), (fusion_func, fusion_func_kwargs)],
-                                      output_chunksize)
-    shrink_distance = 0
+    if call.output_zarr_url is not None:
+        fused = fuse(images=level_sims(osp0["spacing"]), output_stack_properties=osp0, output_zarr_url=call.output_zarr_url,
+                     zarr_options=call.zarr_options, batch_options=call.batch_options, frame_origin=call.frame_origin, **common)
+        if (call.zarr_options or {}).get("ome_zarr", False) and call.chunk_filter is None:
+            return ngff_utils.read_msim_from_ome_zarr(
+                call.output_zarr_url, transform_key=call.transform_key if call.transform_key is not None else si_utils.DEFAULT_TRANSFORM_KEY)
+        return msi_utils.get_msim_from_sim(fused, scale_factors=[])
+    shapes, _, abs_factors = msi_utils.calc_resolution_levels({d: int(osp0["shape"][d]) for d in sdims0})
+    fused_levels = []
+    for shape, f in zip(shapes, abs_factors):
+        props = {"shape": dict(shape), "spacing": {d: osp0["spacing"][d] * f[d] for d in sdims0},
+                 # centre-of-pixel convention of downsampled levels (as in the OME-Zarr pyramid)
+                 "origin": {d: osp0["origin"][d] + (f[d] - 1) * osp0["spacing"][d] / 2 for d in sdims0}}
+        # (a caller's frame_origin refers to the scale0 grid: a coarser level's grid is displaced by (f - 1) * spacing / 2
+        # against it, so the level keeps its own frame = its own stack origin)
+        level0 = all(int(f[d]) == 1 for d in sdims0)
+        fused_levels.append(fuse(images=level_sims(props["spacing"]), output_stack_properties=props,
+                                 output_on_backend=call.output_on_backend, frame_origin=call.frame_origin if level0 else None, **common))
+    return msi_utils.get_msim_from_sims(fused_levels)
 
-    store_chunksize = dict(output_chunksize)          # the chunk grid of a Zarr output stays the requested one
-    requested_chunksize = dict(output_chunksize)
-    merged = False
-    streamed = output_zarr_url is not None or any(type(s_.data).__name__ in ("ZarrArray", "ZarrView") for s_ in sims_)
-    if not streamed and _HOST_STREAM[0] and _STREAM_PIPELINE[0] and not output_on_backend and not batch_options and chunk_filter is None \
-            and fusion_func in _FUSION_CODES and (weights_func is None or weights_func is content_based) \
-            and all(isinstance(s_.data, np.ndarray) or is_device_array(s_.data) for s_ in sims_) \
-            and sum(int(np.prod(s_.data.shape)) * np.dtype(s_.dtype).itemsize for s_ in sims_) >= _HOST_STREAM_MIN_BYTES \
+
+def _output_geometry(call):
+    """The output stack, the dims, per view the affine and the box, the halo."""
+    call.views = list(call.images)
+    check_interpolation_order(call.interpolation_order, "interpolation_order")
+    call.chunksize = process_output_chunksize(call.views, call.output_chunksize)
+    osp = process_output_stack_properties(call.views, call.output_spacing, call.output_origin, call.output_shape,
+                                          call.output_stack_properties, call.output_stack_mode, call.transform_key)
+    call.sdims = si_utils.get_spatial_dims_from_sim(call.views[0])
+    call.nsdims = si_utils.get_nonspatial_dims_from_sim(call.views[0])
+    call.osp = _bb_dicts(osp, call.sdims)
+    call.osp["shape"] = {d: int(v) for d, v in call.osp["shape"].items()}
+    call.params = [si_utils.get_affine_from_sim(sim, call.transform_key) for sim in call.views]
+    call.halo = _halo_overlap(call.overlap_in_pixels, call.sdims,
+                              [(call.weights_func, call.weights_func_kwargs), (call.fusion_func, call.fusion_func_kwargs)], call.chunksize)
+    call.views_bb = [si_utils.get_stack_properties_from_sim(sim) for sim in call.views]
+    call.ns_shape = tuple(call.views[0].sizes[d] for d in call.nsdims)
+    call.dtype = np.dtype(call.views[0].dtype)
+
+
+def _launch_blocks(call):
+    """Whether the call is streamed, and the size of its launch blocks."""
+    kernel_fused = _kernel_fused(call.fusion_func, call.weights_func)
+    single_blocks = bool(call.batch_options) or call.chunk_filter is not None      # (both address single chunks)
+    call.streamed = call.output_zarr_url is not None or any(type(s.data).__name__ in ("ZarrArray", "ZarrView") for s in call.views)
+    if not call.streamed and _HOST_STREAM[0] and _STREAM_PIPELINE[0] and not call.output_on_backend and not single_blocks and kernel_fused \
+            and all(isinstance(s.data, np.ndarray) or is_device_array(s.data) for s in call.views) \
+            and sum(int(np.prod(s.data.shape)) * np.dtype(s.dtype).itemsize for s in call.views) >= _HOST_STREAM_MIN_BYTES \
             and _lib.device_count() > 0:
         # plain host arrays (or resident tiles) in, host array out -- what a user of the reference calls: launch blocks of <= 1 GiB through the block
         # pipeline (slabs copied into pinned staging buffers by the I/O pool, asynchronous transfers under the launch blocks, results
         # copied out by the pool) instead of ONE launch block whose views mvs_fuse_chunk uploads from pageable memory, fuses and
         # downloads one after the other: the north star 0.98 -> 0.41 s (2.26 -> 1.03 s for the first call of a process); resident tiles
         # with a host result 0.64 -> 0.24 s
-        streamed = True
-    if (merge_chunks and not batch_options and chunk_filter is None
-            and weights_func is None and fusion_func in _FUSION_CODES and not any(overlap_in_pixels[d] for d in sdims)
-            and not ("z" in sdims and int(output_chunksize["z"]) == 1 and output_stack_properties["shape"]["z"] > 1)):
+        call.streamed = True
+    call.block_size = call.chunksize
+    if (call.merge_chunks and not single_blocks and kernel_fused and call.weights_func is None and not any(call.halo[d] for d in call.sdims)
+            and not ("z" in call.sdims and int(call.chunksize["z"]) == 1 and call.osp["shape"]["z"] > 1)):
         # streamed inputs / outputs pass through host memory block by block: a smaller budget per launch block
-        itemsize = np.dtype(sims_[0].dtype).itemsize
-        budget = _launch_budget(sims_, output_stack_properties["shape"], sdims, itemsize, device,
-                                MAX_STREAM_BYTES if streamed else MAX_LAUNCH_BYTES)
-        output_chunksize = _merged_chunksize(output_chunksize, output_stack_properties["shape"], sdims, itemsize, budget)
-        merged = any(int(output_chunksize[d]) != int(requested_chunksize[d]) for d in sdims)
+        budget = _launch_budget(call.views, call.osp["shape"], call.sdims, call.dtype.itemsize, call.device,
+                                MAX_STREAM_BYTES if call.streamed else MAX_LAUNCH_BYTES)
+        call.block_size = _merged_chunksize(call.chunksize, call.osp["shape"], call.sdims, call.dtype.itemsize, budget)
 
-    chunk_bbs, block_indices = mv_graph.get_chunk_bbs(output_stack_properties, output_chunksize)
-    chunk_bbs_ov = [
-        cb
-        | {"origin": {d: cb["origin"][d] - overlap_in_pixels[d] * output_stack_properties["spacing"][d] for d in sdims}}
-        | {"shape": {d: cb["shape"][d] + 2 * overlap_in_pixels[d] for d in sdims}}
-        for cb in chunk_bbs
-    ]
-    chunk_bbs_res = chunk_bbs if trim_overlap else chunk_bbs_ov
-    views_bb = [si_utils.get_stack_properties_from_sim(sim) for sim in sims_]
-    norm_chunks = mv_graph.normalize_chunks([output_chunksize[d] for d in sdims], [output_stack_properties["shape"][d] for d in sdims])
-    untrimmed = (not trim_overlap) and any(overlap_in_pixels[d] for d in sdims)
-    if untrimmed:
+
+def _chunk_grid(call):
+    """The launch blocks (``blocks``), and the shape of the result they tile."""
+    sdims, halo, osp = call.sdims, call.halo, call.osp
+    chunk_bbs, block_indices = mv_graph.get_chunk_bbs(osp, call.block_size)
+    call.norm_chunks = mv_graph.normalize_chunks([call.block_size[d] for d in sdims], [osp["shape"][d] for d in sdims])
+    call.result_shape = tuple(osp["shape"][d] for d in sdims)
+    if (not call.trim_overlap) and any(halo[d] for d in sdims):
         # trim_overlap=False (_core.py:1252-1254, 1687-1711): every chunk keeps its halo and the result is the block
         # assembly of the untrimmed chunks side by side (da.block of chunks of shape chunk + 2 * halo), i.e. an array
         # that is larger than the output stack by 2 * halo per chunk and axis
-        if output_zarr_url is not None:
+        if call.output_zarr_url is not None:
             raise NotImplementedError("trim_overlap=False assembles untrimmed chunks in memory; it cannot stream to a Zarr store")
-        norm_chunks = [tuple(int(c) + 2 * int(overlap_in_pixels[d]) for c in cs_) for cs_, d in zip(norm_chunks, sdims)]
-    block_offsets = [np.cumsum((0,) + c[:-1]) for c in norm_chunks]
+        call.norm_chunks = [tuple(int(n) + 2 * int(halo[d]) for n in cs_) for cs_, d in zip(call.norm_chunks, sdims)]
+        call.result_shape = tuple(int(sum(n)) for n in call.norm_chunks)
+    offsets = [np.cumsum((0,) + n[:-1]) for n in call.norm_chunks]
+    call.blocks = [
+        {"block_index": tuple(bi),
+         "bb_halo": cb | {"origin": {d: cb["origin"][d] - halo[d] * osp["spacing"][d] for d in sdims}}
+                       | {"shape": {d: cb["shape"][d] + 2 * halo[d] for d in sdims}},
+         "window": tuple(slice(int(offsets[i][b]), int(offsets[i][b]) + int(call.norm_chunks[i][b])) for i, b in enumerate(bi))}
+        for cb, bi in zip(chunk_bbs, block_indices)]
 
-    out_shape_sp = tuple(int(sum(c)) for c in norm_chunks) if untrimmed else tuple(output_stack_properties["shape"][d] for d in sdims)
-    ns_shape = tuple(sims_[0].sizes[d] for d in nsdims)
-    dtype = np.dtype(sims_[0].dtype)
-    on_device = output_on_backend
-    zarr_out = None
-    if output_zarr_url is not None:
-        # streaming output (_core.py:1068-1171, 2044-2156): every fused chunk goes straight into its region of a Zarr v2
-        # array, the mosaic never exists in host memory; with ome_zarr=True the array is level "0" of an NGFF image
-        from . import ngff_utils, zarr_io
 
-        zarr_options = dict(zarr_options or {})
-        ome_zarr = bool(zarr_options.get("ome_zarr", False))
-        ngff_version = zarr_options.get("ngff_version", "0.4")
-        create_kw = dict(zarr_options.get("zarr_array_creation_kwargs") or {})
-        if create_kw.get("chunks") is not None:
-            # the store's chunk grid: full rank (c, t, spatial) or spatial dims only, as write_sim_to_ome_zarr takes it.  Every
-            # fused block is written into its region, so the fuse chunk grid must be made of whole store chunks.
-            req = [int(v) for v in create_kw["chunks"]]
-            if len(req) == len(nsdims) + len(sdims):
-                req = req[len(nsdims):]
-            if len(req) != len(sdims) or min(req) < 1:
-                raise ValueError(f"zarr_array_creation_kwargs['chunks'] {create_kw['chunks']} does not match dims {list(nsdims) + list(sdims)}")
-            for d, c in zip(sdims, req):
-                if int(requested_chunksize[d]) % c and int(requested_chunksize[d]) < int(output_stack_properties["shape"][d]):
-                    raise ValueError(f"store chunks {req} do not tile the fuse chunks {[int(requested_chunksize[d_]) for d_ in sdims]}")
-            store_chunksize = dict(zip(sdims, req))
-        create_kw.pop("chunks", None)
-        if ome_zarr_requested := bool(zarr_options.get("ome_zarr", False)):
-            want_fmt = 3 if str(zarr_options.get("ngff_version", "0.4")) == "0.5" else 2
-            if int(create_kw.get("zarr_format", want_fmt)) != want_fmt:
-                raise ValueError(f"zarr_format {create_kw['zarr_format']} conflicts with NGFF {zarr_options.get('ngff_version', '0.4')} "
-                                 f"(which stores Zarr v{want_fmt} arrays)")
-        if zarr_options.get("overwrite", True) and os.path.exists(output_zarr_url) and chunk_filter is None:
-            shutil.rmtree(output_zarr_url)
-        if ome_zarr:
-            create_kw = ngff_utils.update_zarr_array_creation_kwargs_for_ngff_version(ngff_version, create_kw)
-            zarr_io.create_group(output_zarr_url, **ngff_utils.zarr_group_creation_kwargs_for_ngff_version(ngff_version))
-            if create_kw.get("zarr_format") == 3:
-                create_kw.setdefault("dimension_names", list(nsdims) + list(sdims))
-        store_url = os.path.join(output_zarr_url, "0") if ome_zarr else output_zarr_url
-        if zarr_io.array_exists(store_url):
-            zarr_out = zarr_io.ZarrArray.open(store_url)      # a farm worker joining an array another worker created
-        else:
-            zarr_out = zarr_io.ZarrArray.create(
-                store_url, ns_shape + out_shape_sp, (1,) * len(ns_shape) + tuple(store_chunksize[d] for d in sdims), dtype,
-                **create_kw)
-    result = None if (on_device or zarr_out is not None) else np.zeros(ns_shape + out_shape_sp, dtype=dtype)
-    # output_on_backend: one device array for all (c, t) fields (_core.py:1275-1306 loops the fields); every field is fused
-    # into its own contiguous sub-array.  A single field keeps the spatial dims only, as before.
-    n_fields = int(np.prod(ns_shape)) if ns_shape else 1
-    dev_full = DeviceArray.empty((ns_shape if n_fields > 1 else ()) + out_shape_sp, dtype, device) if on_device else None
-
-    # batch_options (_core.py:1068-1141, 2044-2156): with a Zarr output the reference hands batches of block ids to
-    # batch_func(fuse_chunk, block_ids, **batch_func_kwargs); fuse_chunk(block_id) fuses one block and writes its region
-    batch_options = dict(batch_options or {})
-    unknown = set(batch_options) - {"batch_func", "n_batch", "batch_func_kwargs"}
+def _check_batch_options(call):
+    """batch_options (_core.py:1068-1141, 2044-2156): with a Zarr output the reference hands batches of block ids to
+    batch_func(fuse_chunk, block_ids, **batch_func_kwargs); fuse_chunk(block_id) fuses one block and writes its region."""
+    call.batch_options = dict(call.batch_options or {})
+    unknown = set(call.batch_options) - {"batch_func", "n_batch", "batch_func_kwargs"}
     if unknown:
         raise TypeError(f"unknown batch_options keys {sorted(unknown)}")
-    if batch_options and output_zarr_url is None:
+    if call.batch_options and call.output_zarr_url is None:
         raise ValueError("batch_options drive the block-wise Zarr output of fuse(); pass output_zarr_url as well")
-    if batch_options and chunk_filter is not None:
+    if call.batch_options and call.chunk_filter is not None:
         raise ValueError("batch_options and chunk_filter both select blocks; use one of them")
 
-    plan_cache = {}
 
-    def plan_for(it):
-        """(affines of time point ``it``, plan): ``plan["per_chunk_entries"]`` lists, in block order, the chunks with their
-        boxes, the contributing views and the index window of each view (``mvs_fuse_plan``)."""
-        key = it if any(np.asarray(p).ndim == 3 for p in params) else 0
-        if key not in plan_cache:
-            sparams = [param_utils.select_time(p, it) for p in params]
-            by_block, info = _plan_chunks(sparams, views_bb, output_stack_properties, output_chunksize, overlap_in_pixels,
-                                          interpolation_order, sdims)
-            entries = []
-            for cbb, cbb_ov, cbb_res, block_index in zip(chunk_bbs, chunk_bbs_ov, chunk_bbs_res, block_indices):
-                planewise, chunk_views = by_block.get(tuple(int(b) for b in block_index), (False, []))
-                entries.append({"views": chunk_views, "output_bb": cbb, "output_bb_overlap": cbb_ov, "output_bb_result": cbb_res,
-                                "fuse_planewise": planewise, "block_index": tuple(block_index)})
-            plan_cache[key] = (sparams, dict(info, per_chunk_entries=entries, sparams=sparams))
-        return plan_cache[key]
+def _open_zarr_output(call):
+    """Streaming output (_core.py:1068-1171, 2044-2156): every fused block goes straight into its region of a Zarr array
+    (``zarr_out``), the mosaic never exists in host memory; with ome_zarr=True the array is level "0" of an NGFF image.  All
+    checks come before the store is touched."""
+    if call.output_zarr_url is None:
+        return
+    sdims, nsdims = call.sdims, call.nsdims
+    call.zarr_options = dict(call.zarr_options or {})
+    call.ome_zarr = bool(call.zarr_options.get("ome_zarr", False))
+    call.ngff_version = call.zarr_options.get("ngff_version", "0.4")
+    create_kw = dict(call.zarr_options.get("zarr_array_creation_kwargs") or {})
+    store_chunksize = call.chunksize          # the chunk grid of a Zarr output stays the requested one
+    if create_kw.get("chunks") is not None:
+        # the store's chunk grid: full rank (c, t, spatial) or spatial dims only, as write_sim_to_ome_zarr takes it.  Every
+        # fused block is written into its region, so the fuse chunk grid must be made of whole store chunks.
+        req = [int(v) for v in create_kw["chunks"]]
+        if len(req) == len(nsdims) + len(sdims):
+            req = req[len(nsdims):]
+        if len(req) != len(sdims) or min(req) < 1:
+            raise ValueError(f"zarr_array_creation_kwargs['chunks'] {create_kw['chunks']} does not match dims {list(nsdims) + list(sdims)}")
+        for d, n in zip(sdims, req):
+            if int(call.chunksize[d]) % n and int(call.chunksize[d]) < int(call.osp["shape"][d]):
+                raise ValueError(f"store chunks {req} do not tile the fuse chunks {[int(call.chunksize[d_]) for d_ in sdims]}")
+        store_chunksize = dict(zip(sdims, req))
+    create_kw.pop("chunks", None)
+    if call.ome_zarr:
+        want_fmt = 3 if str(call.ngff_version) == "0.5" else 2
+        if int(create_kw.get("zarr_format", want_fmt)) != want_fmt:
+            raise ValueError(f"zarr_format {create_kw['zarr_format']} conflicts with NGFF {call.ngff_version} "
+                             f"(which stores Zarr v{want_fmt} arrays)")
+    if call.zarr_options.get("overwrite", True) and os.path.exists(call.output_zarr_url) and call.chunk_filter is None:
+        shutil.rmtree(call.output_zarr_url)
+    if call.ome_zarr:
+        create_kw = ngff_utils.update_zarr_array_creation_kwargs_for_ngff_version(call.ngff_version, create_kw)
+        zarr_io.create_group(call.output_zarr_url, **ngff_utils.zarr_group_creation_kwargs_for_ngff_version(call.ngff_version))
+        if create_kw.get("zarr_format") == 3:
+            create_kw.setdefault("dimension_names", list(nsdims) + list(sdims))
+    store_url = os.path.join(call.output_zarr_url, "0") if call.ome_zarr else call.output_zarr_url
+    if zarr_io.array_exists(store_url):
+        call.zarr_out = zarr_io.ZarrArray.open(store_url)      # a farm worker joining an array another worker created
+    else:
+        call.zarr_out = zarr_io.ZarrArray.create(
+            store_url, call.ns_shape + call.result_shape, (1,) * len(call.ns_shape) + tuple(store_chunksize[d] for d in sdims), call.dtype,
+            **create_kw)
 
-    def chunk_call(ns_index, entry, dev):
-        """fuse_np arguments of one (field, block) and its window in the result."""
-        ns_sel = {d: int(i) for d, i in zip(nsdims, ns_index)}
-        sparams, _ = plan_for(ns_sel.get("t", 0))
-        bi = entry["block_index"]
-        cbb_ov = entry["output_bb_overlap"]
-        slabs = [sims_[iv].isel(dict(ns_sel, **{d: slice(a, a + m) for d, a, m in zip(sdims, lo, n)})) for iv, lo, n in entry["views"]]
-        idxs = [iv for iv, _, _ in entry["views"]]
-        if entry["fuse_planewise"]:
-            slabs = [s.isel({"z": 0}) for s in slabs]
-            tmp_params = [sparams[iv][1:, 1:] for iv in idxs]
-            cbb_use = mv_graph.project_bb_along_dim(cbb_ov, "z")
-            fvb = [mv_graph.project_bb_along_dim(views_bb[iv], "z") for iv in idxs]
+
+def _allocate_result(call):
+    """The host result, or with output_on_backend one device array for all (c, t) fields (_core.py:1275-1306 loops the
+    fields): every field is fused into its own contiguous sub-array; a single field keeps the spatial dims only."""
+    call.n_fields = int(np.prod(call.ns_shape)) if call.ns_shape else 1
+    if call.output_on_backend:
+        call.dev_full = DeviceArray.empty((call.ns_shape if call.n_fields > 1 else ()) + call.result_shape, call.dtype, call.device)
+    elif call.zarr_out is None:
+        call.result = np.zeros(call.ns_shape + call.result_shape, dtype=call.dtype)
+
+
+def _plan_for(call, it):
+    """(affines of time point ``it``, entries): by grid index and in block order, every launch block with the contributing
+    views and the index window of each (``views``: [(iview, lo, n)], from ``mvs_fuse_plan``) and ``fuse_planewise``."""
+    key = it if any(np.asarray(p).ndim == 3 for p in call.params) else 0
+    if key not in call.plans:
+        sparams = [param_utils.select_time(p, it) for p in call.params]
+        by_block, _ = _plan_chunks(sparams, call.views_bb, call.osp, call.block_size, call.halo, call.interpolation_order, call.sdims)
+        entries = {}
+        for block in call.blocks:
+            planewise, views = by_block.get(block["block_index"], (False, []))
+            entries[block["block_index"]] = dict(block, views=views, fuse_planewise=planewise)
+        call.plans[key] = (sparams, entries)
+    return call.plans[key]
+
+
+def _chunk_call(call, ns_index, entry, device):
+    """fuse_np arguments of one (field, block)."""
+    ns_sel = {d: int(i) for d, i in zip(call.nsdims, ns_index)}
+    sparams, _ = _plan_for(call, ns_sel.get("t", 0))
+    slabs = [call.views[iv].isel(dict(ns_sel, **{d: slice(a, a + m) for d, a, m in zip(call.sdims, lo, n)})) for iv, lo, n in entry["views"]]
+    idxs = [iv for iv, _, _ in entry["views"]]
+    params, cbb, fvb = [sparams[iv] for iv in idxs], entry["bb_halo"], [call.views_bb[iv] for iv in idxs]
+    if entry["fuse_planewise"]:      # (one z plane on the views' z grid: a 2D chunk)
+        slabs, params = [s.isel({"z": 0}) for s in slabs], [p[1:, 1:] for p in params]
+        cbb, fvb = mv_graph.project_bb_along_dim(cbb, "z"), [mv_graph.project_bb_along_dim(b, "z") for b in fvb]
+    kwargs = dict(
+        sims=slabs, params=params, output_properties=cbb, fusion_func=call.fusion_func, fusion_func_kwargs=call.fusion_func_kwargs,
+        weights_func=call.weights_func, weights_func_kwargs=call.weights_func_kwargs,
+        trim_overlap_in_pixels=(call.halo if call.trim_overlap else 0), interpolation_order=call.interpolation_order, full_view_bbs=fvb,
+        blending_widths=call.blending_widths, shrink_distance=0, backend="hip", device=device, _cb_check=False)
+    if _kernel_fused(call.fusion_func, call.weights_func):
+        origin = call.frame_origin if call.frame_origin is not None else call.osp["origin"]
+        kwargs["frame_origin"] = {d: origin[d] for d in cbb["origin"]}
+        if call.record is not None and not entry["fuse_planewise"]:
+            kwargs["_record"] = call.record
+            call.record["calls"] = call.record.get("calls", 0) + 1
+            call.record["view_index"] = idxs
+    return kwargs
+
+
+def _deliver(call, ns_index, entry, chunk, pipelined=False):
+    """A fused host block into its region of the Zarr output or its window of the host result (``pipelined``: called by the
+    block pipeline's writer, which copies and writes through the I/O pool).  A plane-wise block gets its plane axis back."""
+    if entry["fuse_planewise"]:
+        chunk = chunk[np.newaxis]
+    if call.zarr_out is not None:
+        start, data = list(ns_index) + [s.start for s in entry["window"]], chunk.reshape((1,) * len(ns_index) + chunk.shape)
+        if pipelined:
+            streaming.write_region(call.zarr_out, start, data)
         else:
-            tmp_params = [sparams[iv] for iv in idxs]
-            cbb_use = cbb_ov
-            fvb = [views_bb[iv] for iv in idxs]
-        sl = tuple(
-            slice(int(block_offsets[i][bi[i]]), int(block_offsets[i][bi[i]]) + int(entry["output_bb_result"]["shape"][d]))
-            for i, d in enumerate(sdims)
-        )
-        kwargs = dict(
-            sims=slabs, params=tmp_params, output_properties=cbb_use, fusion_func=fusion_func,
-            fusion_func_kwargs=fusion_func_kwargs, weights_func=weights_func,
-            weights_func_kwargs=weights_func_kwargs,
-            trim_overlap_in_pixels=(overlap_in_pixels if trim_overlap else 0),
-            interpolation_order=interpolation_order, full_view_bbs=fvb, blending_widths=blending_widths,
-            shrink_distance=shrink_distance, backend="hip", device=dev, _cb_check=False,
-        )
-        if fusion_func in _FUSION_CODES and (weights_func is None or weights_func is content_based):
-            fo_ = frame_origin if frame_origin is not None else output_stack_properties["origin"]
-            kwargs["frame_origin"] = {d: fo_[d] for d in cbb_use["origin"]}
-            if record is not None and not entry["fuse_planewise"]:
-                kwargs["_record"] = record
-                record["calls"] = record.get("calls", 0) + 1
-                record["view_index"] = idxs
-        return kwargs, sl
-
-    if batch_options:
-        # ---- block-wise Zarr output driven by batch_func ----
-        nblocks = tuple(ns_shape) + tuple(len(c) for c in norm_chunks)
-        by_block_cache = {}
-
-        def fuse_chunk(block_id, device=device):
-            """Fuse block ``block_id`` (index into the chunk grid of the output array, non-spatial axes first) and write
-            it into its region of the output store; ``device`` lets a batch function place blocks on several GPUs."""
-            block_id = tuple(int(b) for b in block_id)
-            ns_index, bi = block_id[: len(ns_shape)], block_id[len(ns_shape):]
-            _, plan_t = plan_for({d: i for d, i in zip(nsdims, ns_index)}.get("t", 0))
-            by_block = by_block_cache.setdefault(id(plan_t), {tuple(e["block_index"]): e for e in plan_t["per_chunk_entries"]})
-            entry = by_block[bi]
-            if not entry["views"]:
-                return None      # the store's fill value (0) stands for blocks without contributing views
-            kwargs, sl = chunk_call(ns_index, entry, device)
-            chunk = np.asarray(fuse_np(**kwargs))
-            if entry["fuse_planewise"]:
-                chunk = chunk[np.newaxis]
-            zarr_out.write(list(ns_index) + [s_.start for s_ in sl], chunk.reshape((1,) * len(ns_index) + chunk.shape))
-            return None
-
-        batch_func = batch_options.get("batch_func")
-        n_batch = int(batch_options.get("n_batch", 1))
-        batch_func_kwargs = dict(batch_options.get("batch_func_kwargs") or {})
-        block_iter = iter(np.ndindex(*nblocks))
-        while True:
-            batch = [b for _, b in zip(range(n_batch), block_iter)]
-            if not batch:
-                break
-            if batch_func is None:
-                for block_id in batch:
-                    fuse_chunk(block_id)
-            else:
-                batch_func(fuse_chunk, batch, **batch_func_kwargs)
+            call.zarr_out.write(start, data)
+    elif pipelined:
+        streaming.parallel_copy(call.result[tuple(ns_index) + entry["window"]], chunk, kind="write")
+    elif chunk.shape == call.result.shape:
+        call.result = chunk           # one launch block and one field: the fused array is the result
     else:
-      for ns_index in np.ndindex(*ns_shape) if ns_shape else [()]:
-        ns_sel = {d: int(i) for d, i in zip(nsdims, ns_index)}
-        _, plan = plan_for(ns_sel.get("t", 0))
-        dev_out = None
-        if on_device:
-            dev_out = dev_full[tuple(int(i) for i in ns_index)] if n_fields > 1 else dev_full
-            entries = plan["per_chunk_entries"]
-            # one chunk that is actually fused over the whole array writes every voxel; in every other case (several chunks,
-            # a chunk without views, a chunk the filter rejects) untouched voxels must read 0 like the host result
-            single = (len(entries) == 1 and bool(entries[0]["views"])
-                      and (chunk_filter is None or chunk_filter(entries[0]["block_index"])))
-            if not single:
-                dev_out.fill_zero()
-        # tiles read from Zarr stores and / or a result that leaves the device block by block: read-ahead, asynchronous transfers
-        # and write-behind around the launch blocks (streaming.BlockPipeline) -- the same fuse_np calls in the same order
-        pipe = None
-        if streamed and _STREAM_PIPELINE[0] and not on_device and fusion_func in _FUSION_CODES and (weights_func is None or weights_func is content_based) \
-                and _lib.device_count() > 0:
-            from .streaming import BlockPipeline
+        call.result[tuple(ns_index) + entry["window"]] = chunk
 
-            pipe = BlockPipeline(fuse_np, device)
-        try:
-            for entry in plan["per_chunk_entries"]:
-                bi = entry["block_index"]
-                if chunk_filter is not None and not chunk_filter(bi):
-                    continue
-                if not entry["views"]:
-                    continue
-                kwargs, sl = chunk_call(ns_index, entry, device)
-                if pipe is not None:
-                    def sink(chunk, entry=entry, sl=sl, ns_index=ns_index):
-                        if entry["fuse_planewise"]:
-                            chunk = chunk[np.newaxis]
-                        if zarr_out is not None:
-                            from .streaming import write_region
 
-                            write_region(zarr_out, list(ns_index) + [s_.start for s_ in sl], chunk.reshape((1,) * len(ns_index) + chunk.shape))
-                        else:
-                            from .streaming import parallel_copy
+def _fuse_batches(call):
+    """Block-wise Zarr output driven by ``batch_func``: batches of ``n_batch`` block ids in ``np.ndindex`` order."""
+    def fuse_chunk(block_id, device=call.device):
+        """Fuse block ``block_id`` (index into the chunk grid of the output array, non-spatial axes first) and write
+        it into its region of the output store; ``device`` lets a batch function place blocks on several GPUs."""
+        block_id, n_ns = tuple(int(b) for b in block_id), len(call.ns_shape)
+        ns_index = block_id[:n_ns]
+        entry = _plan_for(call, dict(zip(call.nsdims, ns_index)).get("t", 0))[1][block_id[n_ns:]]
+        if entry["views"]:      # (the store's fill value (0) stands for blocks without contributing views)
+            _deliver(call, ns_index, entry, np.asarray(fuse_np(**_chunk_call(call, ns_index, entry, device))))
 
-                            parallel_copy(result[tuple(ns_index) + sl], chunk, kind="write")
-                    kwargs.pop("device", None)
-                    tiling = None
-                    if zarr_out is not None and not entry["fuse_planewise"] and _STREAM_TILES[0]:
-                        tiling = (zarr_out, list(ns_index) + [s_.start for s_ in sl])
-                    pipe.submit(dict(kwargs, device=device), sink, tiling)
-                    continue
-                if on_device and single:
-                    # (a plane-wise entry is fused with 2D parameters: hand it the one plane of the 3D result)
-                    fuse_np(out=dev_out[0] if entry["fuse_planewise"] else dev_out, **kwargs)
-                elif on_device:
-                    # chunked workflow with a device-resident mosaic: every chunk is fused on the device and copied into
-                    # its window of the mosaic device-to-device (stream-ordered, no host round trip)
-                    chunk = fuse_np(output_on_backend=True, **kwargs)
-                    chunk.copy_into(dev_out, [s_.start for s_ in sl])
-                else:
-                    chunk = np.asarray(fuse_np(**kwargs))
-                    if entry["fuse_planewise"]:
-                        chunk = chunk[np.newaxis]
-                    if zarr_out is not None:
-                        zarr_out.write(list(ns_index) + [s_.start for s_ in sl], chunk.reshape((1,) * len(ns_index) + chunk.shape))
-                    elif chunk.shape == result.shape:
-                        result = chunk           # one launch block and one field: the fused array is the result
-                    else:
-                        result[tuple(ns_index) + sl] = chunk
-        except BaseException:
+    batch_func = call.batch_options.get("batch_func") or (lambda func, block_ids, **_: [func(b) for b in block_ids])
+    n_batch = int(call.batch_options.get("n_batch", 1))
+    block_iter = iter(np.ndindex(*(tuple(call.ns_shape) + tuple(len(n) for n in call.norm_chunks))))
+    while True:
+        batch = [b for _, b in zip(range(n_batch), block_iter)]
+        if not batch:
+            break
+        batch_func(fuse_chunk, batch, **(call.batch_options.get("batch_func_kwargs") or {}))
+
+
+def _fuse_field(call, ns_index):
+    """All blocks of one (c, t) field.  A block is fused in one of three ways: submitted to the block pipeline, into the
+    device result, or on the host."""
+    entries = list(_plan_for(call, dict(zip(call.nsdims, (int(i) for i in ns_index))).get("t", 0))[1].values())
+
+    def selected(entry):      # (blocks the filter rejects and blocks without contributing views are not fused)
+        return (call.chunk_filter is None or call.chunk_filter(entry["block_index"])) and bool(entry["views"])
+
+    if call.dev_full is not None:
+        dev_out = call.dev_full[tuple(int(i) for i in ns_index)] if call.n_fields > 1 else call.dev_full
+        # one block that is actually fused over the whole array writes every voxel; in every other case (several blocks,
+        # a block without views, a block the filter rejects) untouched voxels must read 0 like the host result
+        single = len(entries) == 1 and bool(entries[0]["views"]) and selected(entries[0])
+        if not single:
+            dev_out.fill_zero()
+    # tiles read from Zarr stores and / or a result that leaves the device block by block: read-ahead, asynchronous transfers
+    # and write-behind around the launch blocks (streaming.BlockPipeline) -- the same fuse_np calls in the same order
+    pipelined = (call.streamed and _STREAM_PIPELINE[0] and call.dev_full is None and _kernel_fused(call.fusion_func, call.weights_func)
+                 and _lib.device_count() > 0)
+    pipe = streaming.BlockPipeline(fuse_np, call.device) if pipelined else None
+    try:
+        for entry in entries:
+            if not selected(entry):
+                continue
+            kwargs = _chunk_call(call, ns_index, entry, call.device)
             if pipe is not None:
-                pipe.abort()      # (queued reads are dropped, the stage threads end; the error of the block that failed goes up)
-            raise
+                tiled = call.zarr_out is not None and not entry["fuse_planewise"] and _STREAM_TILES[0]
+                tiling = (call.zarr_out, list(ns_index) + [s.start for s in entry["window"]]) if tiled else None
+                pipe.submit(kwargs, functools.partial(_deliver, call, ns_index, entry, pipelined=True), tiling)
+            elif call.dev_full is None:
+                _deliver(call, ns_index, entry, np.asarray(fuse_np(**kwargs)))
+            elif single:
+                # (a plane-wise entry is fused with 2D parameters: hand it the one plane of the 3D result)
+                fuse_np(out=dev_out[0] if entry["fuse_planewise"] else dev_out, **kwargs)
+            else:
+                # chunked workflow with a device-resident mosaic: every block is fused on the device and copied into
+                # its window of the mosaic device-to-device (stream-ordered, no host round trip)
+                fuse_np(output_on_backend=True, **kwargs).copy_into(dev_out, [s.start for s in entry["window"]])
+    except BaseException:
         if pipe is not None:
-            pipe.finish()
-    if on_device:
-        dev_full.mark_written()
-        data = dev_full
-        dims = (list(nsdims) if n_fields > 1 else []) + list(sdims)
-        if record is not None and record.get("calls") == 1 and "views" in record and not record.get("no_replay") and not nsdims and n_fields == 1 \
-                and tuple(dev_full.shape) == record["res_shape"]:
-            # one launch block wrote the whole result: replayable.  Slab pointers are remembered as offsets into their tiles.
-            base = np.array([images[iv].data.ptr for iv in record["view_index"]], dtype=np.uint64)      # (all device-resident: fuse_np recorded)
-            entry = dict(record, byte_offsets=(record["ptrs"] - base).astype(np.uint64), dims=tuple(dims),
-                         spacing=dict(output_stack_properties["spacing"]), origin=dict(output_stack_properties["origin"]),
-                         dtype=np.dtype(images[0].dtype), ndim=len(sdims))
-            with _REPLAY_LOCK:
-                while len(_REPLAY_MEMO) >= _REPLAY_CAP:
-                    _REPLAY_MEMO.pop(next(iter(_REPLAY_MEMO)), None)      # (oldest first: dicts keep insertion order)
-                _REPLAY_MEMO[fast_key] = entry
+            pipe.abort()      # (queued reads are dropped, the stage threads end; the error of the block that failed goes up)
+        raise
+    if pipe is not None:
+        pipe.finish()
+
+
+def _record_replay(call):
+    """One launch block wrote the whole device result: remember its derivation under ``replay_key``.  Slab pointers are
+    remembered as offsets into their tiles."""
+    record = call.record
+    if not (record is not None and record.get("calls") == 1 and "views" in record and not record.get("no_replay") and not call.nsdims
+            and call.n_fields == 1 and tuple(call.dev_full.shape) == record["res_shape"]):
+        return
+    base = np.array([call.images[iv].data.ptr for iv in record["view_index"]], dtype=np.uint64)      # (all device-resident: fuse_np recorded)
+    entry = dict(record, byte_offsets=(record["ptrs"] - base).astype(np.uint64), dims=tuple(call.sdims),
+                 spacing=dict(call.osp["spacing"]), origin=dict(call.osp["origin"]), dtype=np.dtype(call.images[0].dtype), ndim=len(call.sdims))
+    with _REPLAY_LOCK:
+        while len(_REPLAY_MEMO) >= _REPLAY_CAP:
+            _REPLAY_MEMO.pop(next(iter(_REPLAY_MEMO)), None)      # (oldest first: dicts keep insertion order)
+        _REPLAY_MEMO[call.replay_key] = entry
+
+
+def _wrap_result(call):
+    """The result as a SpatialImage with identity affine under ``transform_key``; for an OME-Zarr output the pyramid levels
+    and multiscales metadata around the level-0 array the blocks were written into (_core.py:1160-1171)."""
+    dims = list(call.nsdims) + list(call.sdims)
+    if call.dev_full is not None:
+        call.dev_full.mark_written()
+        data, dims = call.dev_full, (dims if call.n_fields > 1 else list(call.sdims))
     else:
-        data = result if zarr_out is None else zarr_out[...]
-        dims = list(nsdims) + list(sdims)
+        data = call.result if call.zarr_out is None else call.zarr_out[...]
     res = si_utils.to_spatial_image(
-        data, dims=dims, scale=output_stack_properties["spacing"], translation=output_stack_properties["origin"],
-        c_coords=sims_[0].coords.get("c") if "c" in dims else None,
-        t_coords=sims_[0].coords.get("t") if "t" in dims else None,
+        data, dims=dims, scale=call.osp["spacing"], translation=call.osp["origin"],
+        c_coords=call.views[0].coords.get("c") if "c" in dims else None,
+        t_coords=call.views[0].coords.get("t") if "t" in dims else None,
     )
-    si_utils.set_sim_affine(res, param_utils.identity_transform(len(sdims)), transform_key)
-    if zarr_out is not None and ome_zarr and chunk_filter is None:
-        # pyramid levels + multiscales metadata around the level-0 array written above (_core.py:1160-1171)
-        res = ngff_utils.write_sim_to_ome_zarr(res, output_zarr_url, overwrite=False, ngff_version=ngff_version,
-                                               zarr_array_creation_kwargs=zarr_options.get("zarr_array_creation_kwargs"),
-                                               device=device)
+    si_utils.set_sim_affine(res, param_utils.identity_transform(len(call.sdims)), call.transform_key)
+    if call.zarr_out is not None and call.ome_zarr and call.chunk_filter is None:
+        res = ngff_utils.write_sim_to_ome_zarr(res, call.output_zarr_url, overwrite=False, ngff_version=call.ngff_version,
+                                               zarr_array_creation_kwargs=call.zarr_options.get("zarr_array_creation_kwargs"),
+                                               device=call.device)
     return res
 
 
 def fuse(*args, **kwargs):
-    import inspect
-    import traceback
-    import warnings
-
     bound = inspect.signature(_fuse_once).bind(*args, **kwargs)      # wherever merge_chunks was passed, it can be overridden
-    failure = None
     try:
         res = _fuse_once(*bound.args, **bound.kwargs)
         if bound.arguments.get("weights_func") is content_based and bound.arguments.get("output_on_backend"):
@@ -1305,7 +1324,7 @@ def fuse(*args, **kwargs):
             # in any of them shows here, and the mosaic is fused again through the bit-faithful passes
             dev_ = bound.arguments.get("device", 0)
             if _cb_overflowed(dev_):
-                with _cb_exact(dev_):
+                with _library_option("cb_exact", dev_):
                     res = _fuse_once(*bound.args, **bound.kwargs)
         return res
     except _lib.DeviceMemoryError as exc:
@@ -1317,8 +1336,6 @@ def fuse(*args, **kwargs):
         # the retry must not run inside this handler: the traceback keeps the failed attempt's frames -- and with them the
         # mosaic-sized device buffer, staged peer copies and keep lists -- alive on a device that has just run out of memory
         traceback.clear_frames(exc.__traceback__)
-    import gc
-
     gc.collect()
     warnings.warn(f"fuse(): a merged launch block did not fit the device ({failure}); falling back to the requested "
                   "output_chunksize", RuntimeWarning, stacklevel=2)
@@ -1341,8 +1358,6 @@ def fuse_to_host(images, transform_key=None, n_slabs=8, out=None, device=0, retu
     instead of a new one.  ``return_timeline``: also return [(fuse done, download done)] per slab in ms since the first slab's
     launch block was queued (timed tickets) -- the overlap test reads it.  Remaining keyword arguments: those of ``fuse()``
     (single field images: spatial dims only)."""
-    from . import device as dev_mod
-
     for bad in ("output_zarr_url", "batch_options", "output_on_backend", "chunk_filter", "sims"):
         if fuse_kwargs.get(bad):
             raise TypeError(f"fuse_to_host does not take {bad}")
@@ -1359,8 +1374,7 @@ def fuse_to_host(images, transform_key=None, n_slabs=8, out=None, device=0, retu
         out = dev_mod.pinned_empty(shape, dtype)
     elif tuple(out.shape) != shape or out.dtype != dtype or not out.flags.c_contiguous or not dev_mod.is_pinned(out):
         raise ValueError(f"out must be a pinned C-contiguous {dtype} array of shape {shape}")
-    d0 = sdims[0]
-    n0 = shape[0]
+    d0, n0 = sdims[0], shape[0]
     n_slabs = max(1, min(int(n_slabs), n0))
     cuts = np.linspace(0, n0, n_slabs + 1).round().astype(int)
     fuse_kwargs.setdefault("frame_origin", dict(osp["origin"]))
@@ -1373,38 +1387,24 @@ def fuse_to_host(images, transform_key=None, n_slabs=8, out=None, device=0, retu
     # fused when slab k's download was through, in most runs for some slabs, in one run of ten for all of them, once 377 ms late
     # (A/B on one box, profiles/round6_summary.md 4).  A slab is 1/8 of a mosaic; forking saves it ~0.1 ms.  (The other half of the
     # same symptom: parameter blocks uploaded by a copy engine queued behind the downloads -- csrc/mvs_context.hip: mvs_upload_small.)
-    serial_slabs = True
-    if serial_slabs:
-        _lib.set_option("serial_classes", 1, device)
-    try:
-        return _fuse_to_host_slabs(images, transform_key, n_slabs, cuts, osp, d0, out, device, return_timeline, fuse_kwargs, sdims, t_start, h_start,
-                                   pending, timeline, host_ms)
-    finally:
-        if serial_slabs:
-            _lib.set_option("serial_classes", 0, device)
-
-
-def _fuse_to_host_slabs(images, transform_key, n_slabs, cuts, osp, d0, out, device, return_timeline, fuse_kwargs, sdims, t_start, h_start, pending,
-                        timeline, host_ms):
-    from . import device as dev_mod
-
-    for k in range(n_slabs):
-        a, b = int(cuts[k]), int(cuts[k + 1])
-        if b <= a:
-            continue
-        sub = {"origin": dict(osp["origin"], **{d0: osp["origin"][d0] + a * osp["spacing"][d0]}), "spacing": dict(osp["spacing"]),
-               "shape": dict(osp["shape"], **{d0: b - a})}
-        h0 = time.perf_counter()
-        fused = fuse(images, transform_key=transform_key, output_stack_properties=sub, output_on_backend=True, device=device, **fuse_kwargs)
-        host_ms.append(((h0 - h_start) * 1e3, (time.perf_counter() - h_start) * 1e3))
-        t_fused = dev_mod.mark(device)
-        t_down = fused.data.download_async(out[a:b], after=t_fused)
-        pending.append((fused, t_fused, t_down))      # (the slab stays alive until its download has passed)
-    for fused, t_fused, t_down in pending:
-        dev_mod.ticket_sync(t_down)
-        if return_timeline:
-            timeline.append((dev_mod.ticket_elapsed_ms(t_start, t_fused), dev_mod.ticket_elapsed_ms(t_start, t_down)))
-    res = si_utils.to_spatial_image(out, dims=list(sdims), scale=osp["spacing"], translation=osp["origin"])
-    si_utils.set_sim_affine(res, param_utils.identity_transform(len(sdims)), transform_key)
+    with _library_option("serial_classes", device):
+        for k in range(n_slabs):
+            a, b = int(cuts[k]), int(cuts[k + 1])
+            if b <= a:
+                continue
+            sub = {"origin": dict(osp["origin"], **{d0: osp["origin"][d0] + a * osp["spacing"][d0]}), "spacing": dict(osp["spacing"]),
+                   "shape": dict(osp["shape"], **{d0: b - a})}
+            h0 = time.perf_counter()
+            fused = fuse(images, transform_key=transform_key, output_stack_properties=sub, output_on_backend=True, device=device, **fuse_kwargs)
+            host_ms.append(((h0 - h_start) * 1e3, (time.perf_counter() - h_start) * 1e3))
+            t_fused = dev_mod.mark(device)
+            t_down = fused.data.download_async(out[a:b], after=t_fused)
+            pending.append((fused, t_fused, t_down))      # (the slab stays alive until its download has passed)
+        for fused, t_fused, t_down in pending:
+            dev_mod.ticket_sync(t_down)
+            if return_timeline:
+                timeline.append((dev_mod.ticket_elapsed_ms(t_start, t_fused), dev_mod.ticket_elapsed_ms(t_start, t_down)))
+        res = si_utils.to_spatial_image(out, dims=list(sdims), scale=osp["spacing"], translation=osp["origin"])
+        si_utils.set_sim_affine(res, param_utils.identity_transform(len(sdims)), transform_key)
     fuse_to_host.last_host_ms = host_ms          # (measurement: where the host was while the slabs were queued)
     return (res, timeline) if return_timeline else res

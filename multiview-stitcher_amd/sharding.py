@@ -22,6 +22,8 @@ once:
 
 from __future__ import annotations
 
+import warnings
+
 import numpy as np
 
 
@@ -290,9 +292,10 @@ def _gather_results_impl(self, payload, n_edges):
 ShardedPairExecutor._gather_results = _gather_results_impl
 
 
-def fuse_shard(sims, rank, world_size, transform_key, output_stack_properties=None, **fuse_kwargs):
-    """Fuse this rank's sub-box of the mosaic (fusion.fuse on ``output_stack_properties`` = the rank's part of the global
-    output stack).  Returns (fused sub-image, sub-box); the union over ranks is fusion.fuse of the whole mosaic."""
+def _fuse_sub_box(fuse_func, sims, rank, world_size, transform_key, output_stack_properties, fuse_kwargs):
+    """``fuse_func`` (fusion.fuse or fusion.fuse_to_host) on ``output_stack_properties`` = rank ``rank``'s part of the global
+    output stack, in the index frame of the WHOLE mosaic: every rank derives the views' parameters for the same origin and only
+    shifts integer indices, so the union of the sub-boxes equals the single-GPU mosaic voxel for voxel.  Returns (result, sub-box)."""
     from . import fusion
     from . import spatial_image_utils as si_utils
 
@@ -305,41 +308,25 @@ def fuse_shard(sims, rank, world_size, transform_key, output_stack_properties=No
     boxes, _ = output_subboxes(osp, world_size, sdims)
     box = boxes[rank]
     sub = {k: box[k] for k in ("origin", "spacing", "shape")}
-    # the index frame of the WHOLE mosaic: every rank derives the views' parameters for the same origin and only shifts
-    # integer indices, so the union of the sub-boxes equals the single-GPU mosaic voxel for voxel
     fuse_kwargs.setdefault("frame_origin", dict(osp["origin"]))
-    import warnings
-
     with warnings.catch_warnings():
-        # a frame that cannot be applied would silently void the union-equals-mosaic guarantee of this function
+        # a frame that cannot be applied would silently void the union-equals-mosaic guarantee of these functions
         warnings.simplefilter("error", fusion.IndexFrameWarning)
-        fused = fusion.fuse(list(sims), transform_key=transform_key, output_stack_properties=sub, **fuse_kwargs)
+        fused = getattr(fusion, fuse_func)(list(sims), transform_key=transform_key, output_stack_properties=sub, **fuse_kwargs)
     return fused, box
+
+
+def fuse_shard(sims, rank, world_size, transform_key, output_stack_properties=None, **fuse_kwargs):
+    """Fuse this rank's sub-box of the mosaic (fusion.fuse on the rank's part of the global output stack).  Returns
+    (fused sub-image, sub-box); the union over ranks is fusion.fuse of the whole mosaic."""
+    return _fuse_sub_box("fuse", sims, rank, world_size, transform_key, output_stack_properties, fuse_kwargs)
 
 
 def fuse_shard_to_host(sims, rank, world_size, transform_key, output_stack_properties=None, **fuse_kwargs):
     """``fuse_shard`` with the rank's sub-box ending in pinned host memory: ``fusion.fuse_to_host`` on the rank's part of the global
-    output stack (z slabs of the sub-box, every slab's download under the next slab's fuse), in the index frame of the whole mosaic.
-    Returns (fused sub-image or (sub-image, timeline) with ``return_timeline``, sub-box)."""
-    from . import fusion
-    from . import spatial_image_utils as si_utils
-
-    sdims = si_utils.get_spatial_dims_from_sim(sims[0])
-    if output_stack_properties is None:
-        output_stack_properties = fusion.process_output_stack_properties(
-            list(sims), fuse_kwargs.pop("output_spacing", None), fuse_kwargs.pop("output_origin", None),
-            fuse_kwargs.pop("output_shape", None), None, fuse_kwargs.pop("output_stack_mode", "union"), transform_key)
-    osp = fusion._bb_dicts(output_stack_properties, sdims)
-    boxes, _ = output_subboxes(osp, world_size, sdims)
-    box = boxes[rank]
-    sub = {k: box[k] for k in ("origin", "spacing", "shape")}
-    fuse_kwargs.setdefault("frame_origin", dict(osp["origin"]))
-    import warnings
-
-    with warnings.catch_warnings():
-        warnings.simplefilter("error", fusion.IndexFrameWarning)
-        fused = fusion.fuse_to_host(list(sims), transform_key=transform_key, output_stack_properties=sub, **fuse_kwargs)
-    return fused, box
+    output stack (z slabs of the sub-box, every slab's download under the next slab's fuse).  Returns (fused sub-image or
+    (sub-image, timeline) with ``return_timeline``, sub-box)."""
+    return _fuse_sub_box("fuse_to_host", sims, rank, world_size, transform_key, output_stack_properties, fuse_kwargs)
 
 
 def exchange_halo(torch, dist, tiles, owners, needs, rank, world_size, device, via_host=False):
