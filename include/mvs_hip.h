@@ -519,6 +519,22 @@ int mvs_resolve_translations(int32_t ndim, int32_t n_views, int32_t n_edges, con
                              int32_t reference_view, int32_t max_iter, double rel_tol, double abs_tol, double* translations_out,
                              double* edge_rms_out, double* mean_hist, double* max_hist, int32_t* n_iter_out, int32_t* ref_out);
 
+/* Normal equations of one Gauss-Newton step of the intensity registration (registration.affine_registration) over two
+ * same-shape C-contiguous float32 crops (NaN = outside), both in `mem`.  matrix (3x3 row-major, z,y,x) and offset hold the
+ * centred pose: fixed voxel x samples moving at p = c + t + A (x - c), c = (shape - 1) / 2.  ndim 2: shape = (1, ny, nx) and
+ * only the lower right 2x2 of matrix and the last two entries of offset are read.  Per voxel (arithmetic and operation order:
+ * csrc/mvs_affine_reg_dev.h): p in double, split into floor and a float32 fraction; the sample counts iff F(x) is finite, all
+ * 2^ndim taps lie inside moving and all are finite; then in float32 the bi/trilinear value v, the analytic gradient g of the
+ * interpolant, r = gain v + bias - F and J = gain g (x) [x - c, 1] (parameters: the rows of [A | t], P = ndim (ndim + 1)).
+ * out (MVS_AFFINE_NEQ_LEN doubles, packed for the given ndim, the rest zero): J^T J as a full P x P matrix, J^T r (P),
+ * sum r^2, the valid count, then sum v, sum F, sum v F, sum v^2, sum F^2.  Threads sum runs of 32 samples in float32,
+ * everything above in double, in a fixed order: equal inputs give equal bits.  Runs on the context lane of `device`. */
+#define MVS_AFFINE_NEQ_LEN (12 * 12 + 12 + 7)
+int mvs_affine_normal_eq(int device, const float* fixed, const float* moving, int32_t mem,
+                         int32_t ndim, const int64_t shape[3],
+                         const double matrix[9], const double offset[3],
+                         double gain, double bias, double* out);
+
 #ifdef __cplusplus
 }
 #endif

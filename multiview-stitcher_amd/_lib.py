@@ -20,6 +20,7 @@ MVS_U8, MVS_U16, MVS_F32 = 0, 1, 2
 MVS_MEM_HOST, MVS_MEM_DEVICE = 0, 1
 MVS_FUSE_WEIGHTED_AVERAGE, MVS_FUSE_MAX, MVS_FUSE_SIMPLE_AVERAGE = 0, 1, 2
 MVS_WEIGHTS_NONE, MVS_WEIGHTS_CONTENT_BASED = 0, 1
+MVS_AFFINE_NEQ_LEN = 12 * 12 + 12 + 7
 
 DTYPE_CODES = {np.dtype(np.uint8): MVS_U8, np.dtype(np.uint16): MVS_U16, np.dtype(np.float32): MVS_F32}
 CODE_DTYPES = {v: k for k, v in DTYPE_CODES.items()}
@@ -221,6 +222,11 @@ SIGNATURES = {
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double),
          C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
          C.POINTER(C.c_int32)],
+    ),
+    "mvs_affine_normal_eq": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double),
+         C.c_double, C.c_double, C.POINTER(C.c_double)],
     ),
 }
 

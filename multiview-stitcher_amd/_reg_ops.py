@@ -231,3 +231,33 @@ def bin_mean(data, bins, device=0, wait=True, out=None):
     if is_device_array(out):
         out.mark_written()
     return out
+
+
+def affine_normal_equations(fixed, moving, A, t, gain=1.0, bias=0.0, device=0):
+    """Normal equations of one Gauss-Newton step of the intensity registration (mvs_affine_normal_eq).  ``fixed`` / ``moving``:
+    same-shape float32 crops (NaN = outside), both numpy or both contiguous DeviceArrays; ``(A, t)``: the centred pose, fixed
+    voxel x samples moving at ``c + t + A (x - c)``.  Returns (H (P, P), b (P,), sum r^2, n valid, (sum v, sum F, sum vF,
+    sum v^2, sum F^2)) with P = ndim (ndim + 1) and the parameters ordered as the rows of ``[A | t]``."""
+    lib = _lib.init(device)
+    shape = tuple(int(s) for s in fixed.shape)
+    if tuple(moving.shape) != shape:
+        raise ValueError("crops must have the same shape")
+    ndim = len(shape)
+    p0, m0, k0 = _ptr_mem(fixed)
+    p1, m1, k1 = _ptr_mem(moving)
+    if m0 != m1:
+        raise TypeError("both crops must live on the same side (host or device)")
+    A3 = np.eye(3)
+    A3[3 - ndim:, 3 - ndim:] = np.asarray(A, dtype=np.float64).reshape(ndim, ndim)
+    t3 = np.zeros(3)
+    t3[3 - ndim:] = np.asarray(t, dtype=np.float64).reshape(ndim)
+    out = np.empty(_lib.MVS_AFFINE_NEQ_LEN, dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    rc = lib.mvs_affine_normal_eq(device, p0, p1, m0, ndim, _lib.i64x3(shape3(shape)), A3.ctypes.data_as(dp), t3.ctypes.data_as(dp),
+                                  float(gain), float(bias), out.ctypes.data_as(dp))
+    _lib.check(rc, device, "mvs_affine_normal_eq")
+    P = ndim * (ndim + 1)
+    H = out[:P * P].reshape(P, P).copy()
+    b = out[P * P:P * P + P].copy()
+    rest = out[P * P + P:P * P + P + 7]
+    return H, b, float(rest[0]), float(rest[1]), tuple(float(v) for v in rest[2:7])

@@ -153,6 +153,29 @@ def phase_correlation_registration(fixed_data, moving_data, disambiguate_region_
     return reg_result
 
 
+def affine_registration(fixed_data, moving_data, transform_type="rigid", shrink_factors=(2, 1), max_iterations=(30, 20), tolerance=1e-3,
+                        initial_affine="phase_correlation", fit_intensity=True, device=0, return_debug=False):
+    """Rigid / affine intensity registration of two same-shape overlap crops (float32, NaN = outside the view): a drop-in
+    ``pairwise_reg_func`` in the seat of the reference's ``registration_ANTsPy`` (registration.py:2774-2922).
+
+    Gauss-Newton on the squared residual ``gain * moving(p(x)) + bias - fixed(x)`` (order-1 interpolation and its analytic
+    gradient), coarse to fine over ``shrink_factors`` with at most ``max_iterations`` steps per level; a level ends when no
+    crop corner moves by ``tolerance`` (full-resolution px) any more.  ``transform_type``: "translation", "rigid",
+    "similarity" or "affine".  ``initial_affine``: "phase_correlation" (the translation ``phase_correlation_registration``
+    finds), "identity" or an (ndim + 1)^2 matrix.  ``fit_intensity``: gain and bias follow the least-squares fit of the
+    previous iteration's samples (else 1, 0).  Every iteration is one ``mvs_affine_normal_eq`` launch over the level's crop;
+    the model algebra runs on the host in float64 (``_affine_reg``).
+
+    Returns ``{"affine_matrix": fixed px -> moving px, "quality": masked Spearman coefficient of the aligned crops}``;
+    ``return_debug`` adds ``"debug": {"history": [{level, msd, n, gain, bias, step}, ...], "initial_affine"}``.  Warns and
+    returns the initial pose with quality NaN when fewer than 4 valid samples per model parameter remain or the projected
+    normal equations are not positive definite."""
+    from . import _affine_reg
+
+    return _affine_reg.affine_registration(fixed_data, moving_data, transform_type, shrink_factors, max_iterations, tolerance,
+                                           initial_affine, fit_intensity, device, return_debug)
+
+
 def get_optimal_registration_binning(sim1, sim2, max_total_pixels_per_stack=400**3, overlap_tolerance=None):
     """registration.get_optimal_registration_binning (registration.py:114-191): +1 steps (not doublings) on
     the axis with the smallest current spacing (z alone, or x and y together) until the larger of the two
