@@ -535,6 +535,43 @@ int mvs_affine_normal_eq(int device, const float* fixed, const float* moving, in
                          const double matrix[9], const double offset[3],
                          double gain, double bias, double* out);
 
+/* Bead detection (detection.log_detect), first half: the Laplacian-of-Gaussian response of a C-contiguous 2-D / 3-D image (uint8,
+ * uint16 or float32, in `mem`; ndim 2: shape = (1, ny, nx)).  response (device memory, float32, the image's shape) becomes
+ *   -scipy.ndimage.gaussian_laplace(image as float32, sigma, mode="reflect") * scale.
+ * The host supplies the filter taps (scipy's _gaussian_kernel1d): radius[k] per axis (z, y, x; the z entry is ignored in 2D), and
+ * taps0 / taps2 = the order-0 / order-2 tables of the image's axes one after the other, 2 radius + 1 float64 values each.  ndim
+ * line passes carry two volumes (x: G I and G'' I; y: G A and G'' A + G B; z: the sum): float64 accumulation over the float64
+ * taps in scipy's order, float32 stores after each pass.  The line ends reflect as scipy's do, also when the radius exceeds the
+ * axis length and on an axis of one sample.  A radius above MVS_LOG_MAX_RADIUS returns MVS_ERR_UNSUPPORTED.
+ * taps2 == NULL: response becomes scipy.ndimage.gaussian_filter(image as float32, sigma) instead (scale is not used).
+ * *max_out (optional) = the maximum of response (NaN ignored) over the slices [max_range[0], max_range[1]) of the image's first
+ * axis (max_range == NULL: all of it); per-workgroup maxima and a second small launch, no atomics.  Work area: ndim float32
+ * volumes (one for smoothing) plus the image when it comes from the host.  Waits for the result; runs on the lane of `device`.
+ * Both detection entry points return MVS_ERR_UNSUPPORTED for an axis above 2^24 or a volume above MVS_DETECT_MAX_VOXELS, and this
+ * one also when a pass would need 2^24 workgroups or more (a tile is 64 x columns by 16 rows or 32 positions, so volumes with very
+ * short rows reach that first). */
+#define MVS_LOG_MAX_RADIUS 40
+#define MVS_DETECT_MAX_VOXELS ((int64_t)1 << 34)
+int mvs_log_response(int device, const void* image, int32_t dtype, int32_t mem, int32_t ndim, const int64_t shape[3],
+                     const int32_t radius[3], const double* taps0, const double* taps2, double scale,
+                     const int64_t* max_range, float* response, float* max_out);
+
+/* Bead detection, second half: the voxels of a float32 device volume where
+ *   r == maximum of r over the box window[] (odd sizes; z, y, x; mode "reflect"),  r > threshold  and  r > 0
+ * hold (a NaN fails every comparison).  With sample != NULL (a device volume of sample_dtype and the same shape) a voxel also
+ * needs  min of sample over its box sample_window[] < bound;  a window of size n at position i covers [i - n/2, i - n/2 + n - 1]
+ * (even sizes allowed, as in scipy.ndimage.minimum_filter), and the minimum is evaluated at the remaining candidates only.  A
+ * float32 sample is compared with (float)bound, an integer one exactly.  *count_out = the exact number of detections;
+ * coords_out (host memory, capacity x 3 int32: z, y, x) receives min(count, capacity) of them in NO defined order (one integer
+ * atomicAdd per wave appends them): sort for a deterministic list.  Window sizes go up to MVS_MAXIMA_MAX_WINDOW: every
+ * output of a running maximum reads its whole window again, so a pass costs `window` loads per voxel (7 for a bead of 6 voxels;
+ * the largest window log_detect derives under MVS_LOG_MAX_RADIUS is 37), and the box minimum costs the product of its sizes per
+ * candidate.  Work area: ndim - 1 float32 volumes and the list.  Waits for the result; runs on the lane of `device`. */
+#define MVS_MAXIMA_MAX_WINDOW 127
+int mvs_local_maxima(int device, const float* response, int32_t ndim, const int64_t shape[3], const int32_t window[3],
+                     float threshold, const void* sample, int32_t sample_dtype, const int32_t sample_window[3], double bound,
+                     int32_t* coords_out, int64_t capacity, int64_t* count_out);
+
 #ifdef __cplusplus
 }
 #endif
