@@ -318,7 +318,8 @@ int mvs_rescale_intensity(int device, const float* in, int32_t mem, int64_t n, f
                           float* min_out, float* max_out, int64_t* nvalid_out);
 
 /* Block-mean binning of one view == sim.coarsen(bins, boundary="trim").mean().astype(dtype)
- * (registration.py:1732-1741): out shape = shape // bin, mean in double, cast like astype. */
+ * (registration.py:1732-1741): out shape = shape // bin; the mean is sum / count in double (a true division, as numpy's: a
+ * block whose sum is a multiple of its count gives exactly that integer for every count), cast like astype. */
 int mvs_bin_mean(int device, const void* in, int32_t dtype, int32_t mem, const int64_t shape[3],
                  const int64_t stride[3], const int64_t bin[3], void* out, int32_t out_mem);
 

@@ -23,6 +23,7 @@
 // NI_GeometricTransform does; interpolation and accumulation are float32.
 #include "mvs_internal.h"
 #include "mvs_fuse_dev.h"
+#include "mvs_bin_dev.h"
 #include "mvs_dct_dev.h"
 #include "mvs_fuse_tr.h"
 
@@ -1063,7 +1064,7 @@ __global__ __launch_bounds__(256) void crop_int_kernel(const TIn* __restrict__ d
 
 // The same crop taken from the RAW tile with the registration binning applied on the fly (round 5): output voxel (z, y, x) is the
 // binned sample (z + tz, y + ty, x + tx) of the window -- the truncated block mean of its bz x by x bx raw voxels, exactly
-// bin_mean_kernel's arithmetic (integer sum, times 1 / (bz by bx) in double, cast to the tile's type) -- or `cval` outside the
+// bin_mean_kernel's arithmetic (integer sum / count bz by bx in double, cast to the tile's type: mvs_bin_dev.h) -- or `cval` outside the
 // window's nz x ny x nx binned samples.  `data` = first raw voxel of the window.  A pair then reads only the slab of each tile its
 // overlap needs (15 GB per north-star mosaic instead of binning all 17 GB of tiles and reading the binned windows back), and no
 // binned copy of a tile exists.  bx == 2: a thread makes 8 outputs of a row from two 16-byte loads per raw row.
@@ -1075,7 +1076,7 @@ __global__ __launch_bounds__(1024) void crop_bin_kernel(const TIn* __restrict__ 
     typedef unsigned int u32x4_t __attribute__((ext_vector_type(4), aligned(4)));
     const int gpr = (ox + 7) / 8;
     const long long ngroups = (long long)oz * oy * gpr;
-    const double inv = 1.0 / ((double)bz * by * bx);
+    const double count = (double)bz * by * bx;
     // the 4-byte / 16-byte loads of the bx == 2 branches read PAIRS of 16-bit samples: every pair must start on a 4-byte boundary
     // (window base and both strides; a tile of odd width has odd strides) -- otherwise the generic branch
     const bool pairs_aligned = (((unsigned long long)data & 3ull) == 0ull) && ((stride_z & 1ll) == 0ll) && ((stride_y & 1ll) == 0ll);
@@ -1107,7 +1108,7 @@ __global__ __launch_bounds__(1024) void crop_bin_kernel(const TIn* __restrict__ 
                     for (int k = 0; k < 4; ++k) { acc[k] += (a[k] & 0xffffu) + (a[k] >> 16); acc[4 + k] += (b[k] & 0xffffu) + (b[k] >> 16); }
                 }
 #pragma unroll
-            for (int k = 0; k < 8; ++k) { v[k] = (float)(TIn)((double)acc[k] * inv); in[k] = true; }
+            for (int k = 0; k < 8; ++k) { v[k] = (float)mvs_bin::mean_cast<TIn>(acc[k], count); in[k] = true; }
         } else if (sizeof(TIn) == 2 && bx == 2 && pairs_aligned) {
             // a group that hangs over the crop or the window (the narrow crops of x neighbours end in one): one 4-byte load per
             // output and raw row instead of the generic double-precision loops
@@ -1121,7 +1122,7 @@ __global__ __launch_bounds__(1024) void crop_bin_kernel(const TIn* __restrict__ 
                         const unsigned int w = *reinterpret_cast<const unsigned int*>(p + (long long)dz * stride_z + (long long)dy * stride_y + (long long)j * 2);
                         acc += (w & 0xffffu) + (w >> 16);
                     }
-                v[j] = (float)(TIn)((double)acc * inv);
+                v[j] = (float)mvs_bin::mean_cast<TIn>(acc, count);
             }
         } else {
             for (int j = 0; j < 8; ++j) {
@@ -1134,7 +1135,7 @@ __global__ __launch_bounds__(1024) void crop_bin_kernel(const TIn* __restrict__ 
                         const TIn* r = p + (long long)dz * stride_z + (long long)dy * stride_y + (long long)j * bx;
                         for (int dx = 0; dx < bx; ++dx) acc += (double)r[dx];
                     }
-                v[j] = (float)(TIn)(acc * inv);
+                v[j] = (float)mvs_bin::mean_cast<TIn>(acc, count);
             }
         }
         if (xg + 8 <= ox) {

@@ -10,6 +10,7 @@
 // mvs_rescale_intensity == skimage.exposure.rescale_intensity(im, in_range=(nanmin, nanmax),
 // out_range=(0,1)) (registration.py:381-389).
 #include "mvs_fft.h"
+#include "mvs_bin_dev.h"
 
 #include <rocprim/warp/warp_reduce.hpp>
 
@@ -882,7 +883,7 @@ template <typename T>
 __global__ void bin_mean_kernel(const T* __restrict__ in, long long sz, long long sy, T* __restrict__ out, int oz, int oy, int ox,
                                 int bz, int by, int bx) {
     const long long n = (long long)oz * oy * ox;
-    const double inv = 1.0 / ((double)bz * by * bx);
+    const double count = (double)bz * by * bx;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const int x = (int)(i % ox);
         const long long t = i / ox;
@@ -893,8 +894,7 @@ __global__ void bin_mean_kernel(const T* __restrict__ in, long long sz, long lon
                 const T* row = in + (long long)(z * bz + dz) * sz + (long long)(y * by + dy) * sy + (long long)x * bx;
                 for (int dx = 0; dx < bx; ++dx) acc += (double)row[dx];
             }
-        const double m = acc * inv;
-        out[i] = (T)m;   // astype: truncation for integer dtypes
+        out[i] = mvs_bin::mean_cast<T>(acc, count);   // sum / count in double; astype: truncation for integer dtypes
     }
 }
 // uint16, bin 2 along x, rows 16-byte aligned: a thread produces 4 consecutive outputs of a row from one 16-byte load per
@@ -904,7 +904,7 @@ __global__ __launch_bounds__(256) void bin_mean_u16x2_kernel(const unsigned shor
                                                              unsigned short* __restrict__ out, int oz, int oy, int ox, int bz, int by) {
     const int gx = ox >> 2;                                   // groups of 4 outputs per row (ox % 4 == 0)
     const long long ngroups = (long long)oz * oy * gx;
-    const double inv = 1.0 / ((double)bz * by * 2);
+    const double count = (double)bz * by * 2;
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (long long)gridDim.x * blockDim.x) {
         const int xg = (int)(g % gx);
@@ -919,7 +919,7 @@ __global__ __launch_bounds__(256) void bin_mean_u16x2_kernel(const unsigned shor
             }
         unsigned short r[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = (unsigned short)((double)acc[k] * inv);   // astype: truncation
+        for (int k = 0; k < 4; ++k) r[k] = mvs_bin::mean_cast<unsigned short>(acc[k], count);   // astype: truncation
         *reinterpret_cast<uint2*>(out + ((long long)z * oy + y) * ox + (long long)xg * 4) =
             make_uint2((unsigned int)r[0] | ((unsigned int)r[1] << 16), (unsigned int)r[2] | ((unsigned int)r[3] << 16));
     }
@@ -935,7 +935,7 @@ __global__ __launch_bounds__(256) void bin_mean_u16x2_batch_kernel(BinBatch B, l
     unsigned short* __restrict__ out = B.out[blockIdx.y];
     const int gx = ox >> 2;
     const long long ngroups = (long long)oz * oy * gx;
-    const double inv = 1.0 / ((double)bz * by * 2);
+    const double count = (double)bz * by * 2;
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (long long)gridDim.x * blockDim.x) {
         const int xg = (int)(g % gx);
@@ -950,7 +950,7 @@ __global__ __launch_bounds__(256) void bin_mean_u16x2_batch_kernel(BinBatch B, l
             }
         unsigned short r[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = (unsigned short)((double)acc[k] * inv);   // astype: truncation
+        for (int k = 0; k < 4; ++k) r[k] = mvs_bin::mean_cast<unsigned short>(acc[k], count);   // astype: truncation
         *reinterpret_cast<uint2*>(out + ((long long)z * oy + y) * ox + (long long)xg * 4) =
             make_uint2((unsigned int)r[0] | ((unsigned int)r[1] << 16), (unsigned int)r[2] | ((unsigned int)r[3] << 16));
     }

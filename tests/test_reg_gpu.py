@@ -446,7 +446,8 @@ def test_histogram_ranks_on_binned_integer_tiles_match_oracle(hip_device, shape,
                                         ((6, 24, 40), (2, 2, 1)), ((64, 96), (2, 2)), ((10, 16, 24), (2, 3, 4))])
 def test_bin_mean_matches_numpy(hip_device, shape, bins):
     """coarsen(bins, boundary="trim").mean().astype(dtype) (registration.py:1732-1741): the vectorised uint16 kernel (bin 2 along x,
-    aligned rows) and the generic one against numpy, host and device (strided window) inputs."""
+    aligned rows) and the generic one against numpy on random data, host input and its contiguous device copy (strided and
+    misaligned device windows, the batch entry point and the edges of the kernel choice: tests/test_bin_mean_gpu.py)."""
     from multiview_stitcher_amd import _reg_ops
     from multiview_stitcher_amd.device import DeviceArray
 
