@@ -248,6 +248,9 @@ static const MvsCounter kCounters[] = {
     {"reg_pruned", nullptr, &MvsContext::reg_pruned},
     {"reg_cand_volumes", &MvsContext::reg_cand_volumes, nullptr},
     {"reg_slab_pairs", nullptr, &MvsContext::reg_slab_pairs},
+    {"reg_rank_hist", nullptr, &MvsContext::reg_rank_hist},
+    {"reg_rank_sort16", nullptr, &MvsContext::reg_rank_sort16},
+    {"reg_rank_sort32", nullptr, &MvsContext::reg_rank_sort32},
     {"cb_mask_views", nullptr, &MvsContext::cb_mask_views},
     {"cb_mask_boxes", nullptr, &MvsContext::cb_mask_boxes},
     {"cb_line_launches", nullptr, &MvsContext::cb_line_launches},

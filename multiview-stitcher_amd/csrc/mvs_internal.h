@@ -41,6 +41,8 @@ struct MvsContext {
     double reg_alg_bytes_full = 0.0;   // the same model with every scored candidate counted whole (what the reference's formulation moves)
     long long reg_pairs = 0, reg_candidates = 0, reg_pruned = 0;   // reg_pruned: candidates the pruned arg-max search left unfinished
     long long reg_slab_pairs = 0;      // phase correlations that took the three-pass form (mvs_fft_slab.hip)
+    // rank correlations by route (mvs_score.hip): key histograms, sorts on 16-bit integer keys, sorts on float keys
+    long long reg_rank_hist = 0, reg_rank_sort16 = 0, reg_rank_sort32 = 0;
     double reg_cand_volumes = 0.0;     // candidate volumes the SSIM walk actually went through (a pruned candidate counts its fraction)
     // the class kernels of one fuse launch run on side streams next to the main one (fork / join by events)
     hipStream_t aux_stream[4] = {nullptr, nullptr, nullptr, nullptr};

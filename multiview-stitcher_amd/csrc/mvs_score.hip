@@ -11,6 +11,7 @@
 // Everything voxel-sized runs on the device; the host only sees counters, bounding boxes and sums.
 #include "mvs_internal.h"
 #include "mvs_prune_search.h"
+#include "mvs_rank_plan.h"
 
 #include <cstring>
 
@@ -30,7 +31,7 @@ constexpr int kMaxResident = 16;     // shifted copies of the moving image kept 
 static_assert(kMaxResident == kPruneMaxCand, "PruneSearch holds one batch");
 constexpr int kChunk = 8;            // outputs one thread produces along the filtered axis
 
-inline int grid_for(long long n) { return (int)std::min<long long>((n + 255) / 256, 256 * 8); }
+inline int grid_for(long long n) { return mvs_rank_plan::score_grid(n); }
 
 struct Shape3 { int nz, ny, nx; };
 
@@ -943,9 +944,17 @@ __global__ __launch_bounds__(256) void finish_region_kernel(const float* __restr
 // workgroup reserves its output range with ONE atomic (the order of the pairs is irrelevant to a rank correlation).
 // raw0 != nullptr: the fixed image's sort key is its integer-valued original (< 65536) stored as uint32 -- same order and
 // ties as the rescaled value (the rescaling is strictly increasing and one-to-one on integers), a 2-pass radix sort instead of 4.
+// KEYSUM (integer-valued finite crops, a shift in multiples of 1/2: the histogram route's case when its tables do not fit): the
+// moving image's sort key is the sum of the raw taps with a non-zero weight (shifted_keysum, an integer below 2^19: exact as a
+// float) -- the order and the ties of the exactly interpolated value, as the histogram route ranks them.  The float32 value
+// im1t holds is that value computed from ROUNDED rescaled taps: equal sums a + b == c + d can come out one ulp apart.
+__device__ __forceinline__ int shifted_keysum(const float* __restrict__ raw1, int sy, int sz, const AxisTap& Z, const AxisTap& Y,
+                                              const AxisTap& X);
+template <bool KEYSUM>
 __global__ __launch_bounds__(256) void compact_kernel(const float* __restrict__ im0, const float* __restrict__ im1t, long long n,
                                                       float* __restrict__ kx, float* __restrict__ ky,
-                                                      unsigned int* __restrict__ counter, const float* __restrict__ raw0) {
+                                                      unsigned int* __restrict__ counter, const float* __restrict__ raw0,
+                                                      const float* __restrict__ raw1, Shape3 S, double tz, double ty, double tx) {
     constexpr int K = 8;
     __shared__ unsigned int s_wave[4];
     __shared__ unsigned int s_base;
@@ -980,7 +989,13 @@ __global__ __launch_bounds__(256) void compact_kernel(const float* __restrict__ 
             if (a[k] == a[k] && b[k] == b[k]) {
                 if (raw0) reinterpret_cast<unsigned int*>(kx)[p] = (unsigned int)raw0[i0 + k];
                 else kx[p] = a[k];
-                ky[p] = b[k] - 1.0f;
+                if (KEYSUM) {
+                    const unsigned int i = (unsigned int)(i0 + k);
+                    const int x = (int)(i % (unsigned int)S.nx);
+                    const unsigned int r = i / (unsigned int)S.nx;
+                    ky[p] = (float)shifted_keysum(raw1, S.nx, S.ny * S.nx, axis_tap((int)(r / (unsigned int)S.ny), tz, S.nz),
+                                                  axis_tap((int)(r % (unsigned int)S.ny), ty, S.ny), axis_tap(x, tx, S.nx));
+                } else ky[p] = b[k] - 1.0f;
                 ++p;
             }
         __syncthreads();
@@ -1141,7 +1156,7 @@ __global__ __launch_bounds__(256) void rankcorr_kernel(const float* __restrict__
 // compaction, two multi-pass radix sorts and the run-length rank kernels.  Ties and order are those of the exact
 // interpolated values; the float32 values scipy ranks are those values rounded once, distinct wherever the exact ones are
 // (spacing >= 2^-3 / range against 2^-24 relative), so the rank vectors coincide.
-constexpr int kHistParts = 256;           // workgroups whose private histograms are written out and folded (more: atomic flush)
+using mvs_rank_plan::kHistParts;          // workgroups whose private histograms are written out and folded (mvs_rank_plan.h)
 constexpr int kHistBinsMax = 48 * 1024;      // x + y bins a workgroup's private histogram can hold (16-bit counters in 96 KiB of LDS)
 __device__ __forceinline__ int shifted_keysum(const float* __restrict__ raw1, int sy, int sz, const AxisTap& Z, const AxisTap& Y,
                                               const AxisTap& X) {
@@ -1175,10 +1190,10 @@ __global__ __launch_bounds__(CORR ? 256 : 1024) void hist_rank_kernel(const floa
         __syncthreads();
     }
     double sxy = 0.0;
-    // contiguous range of 4-voxel groups per workgroup (at most 16383 groups = 65532 voxels: the counters cannot overflow)
-    const unsigned int ngroups = (n + 3) / 4;
-    const unsigned int per = (ngroups + gridDim.x - 1) / gridDim.x;
-    const unsigned int g0 = blockIdx.x * per, g1 = min(g0 + per, ngroups);
+    // contiguous range of 4-voxel groups per workgroup (mvs_rank_plan.h; the counting pass is launched by hist_launch with at
+    // most 16383 groups = 65532 voxels per workgroup, which the 16-bit counters hold even when all of them share one key)
+    unsigned int g0, g1;
+    mvs_rank_plan::hist_range(n, gridDim.x, blockIdx.x, &g0, &g1);
     for (unsigned int g = g0 + threadIdx.x; g < g1; g += blockDim.x) {
         const unsigned int i0 = g * 4;
         int x = (int)(i0 % (unsigned int)S.nx);
@@ -1901,7 +1916,7 @@ void decode_results(ScoreCall& sc, const ScoreBatch& b) {
 // ---- Spearman over the jointly valid voxels of candidate ic ----
 // histogram ranks: both crops hold 16-bit integers (the caller vouches: raw_u16_keys) and are finite, every component of this
 // candidate's shift is a multiple of 1/2, and the keys fit the tables
-struct HistPlan { double t[3]; long long kx0, nbx, ky0, nby, hgb; bool fold; };
+struct HistPlan { double t[3]; long long kx0, nbx, ky0, nby, hgb; bool fold, exact_keys; };
 bool hist_ranks_apply(const ScoreCall& sc, int ic, HistPlan* hp) {
     const MvsScoreOpts& so = *sc.so;
     sc.shift_of(ic, hp->t);
@@ -1914,19 +1929,22 @@ bool hist_ranks_apply(const ScoreCall& sc, int ic, HistPlan* hp) {
     // key ranges from the raw extrema of the crops (so.raw_range: min / max of the fixed and of the moving crop)
     hp->kx0 = (long long)so.raw_range[0]; hp->nbx = (long long)so.raw_range[1] - hp->kx0 + 1;
     hp->ky0 = (long long)so.raw_range[2] * (1 << nf); hp->nby = ((long long)so.raw_range[3] - (long long)so.raw_range[2]) * (1 << nf) + 1;
-    // < 65536 voxels per workgroup; up to kHistParts workgroups write their histograms out whole (folded by a
-    // second kernel), beyond that the non-zero counters are flushed with atomics
-    const long long hneed = (sc.n / 4 + 16382) / 16383;
-    hp->fold = hneed <= kHistParts;
-    hp->hgb = hp->fold ? std::max<long long>(hneed, std::min<long long>(kHistParts, (sc.n + 8191) / 8192)) : std::max<long long>(sc.gb, hneed);
-    return halves && so.raw_u16_keys[0] && so.raw_u16_keys[1] && so.both_crops_finite && !sc.c->materialize_shifts && hp->nbx > 0 && hp->nby > 0 &&
-           hp->nbx + hp->nby <= kHistBinsMax && hp->hgb <= 65535;
+    // at most 65532 voxels per workgroup; up to kHistParts workgroups write their histograms out whole (folded by a
+    // second kernel), beyond that the non-zero counters are flushed with atomics (mvs_rank_plan.h)
+    const mvs_rank_plan::HistLaunch hl = mvs_rank_plan::hist_launch(sc.n, sc.gb);
+    hp->fold = hl.fold;
+    hp->hgb = hl.hgb;
+    // exact_keys: the keys are exact integers; the tables must fit as well (else: sorts on the same keys, spearman_sorted)
+    hp->exact_keys = halves && so.raw_u16_keys[0] && so.raw_u16_keys[1] && so.both_crops_finite && !sc.c->materialize_shifts && hp->nbx > 0 &&
+                     hp->nby > 0;
+    return hp->exact_keys && hp->nbx + hp->nby <= kHistBinsMax && hl.ok;
 }
 
 int spearman_hist(ScoreCall& sc, int ic, const HistPlan& hp) {
     MvsContext* c = sc.c;
     const MvsScoreOpts& so = *sc.so;
     const long long kx0 = hp.kx0, nbx = hp.nbx, ky0 = hp.ky0, nby = hp.nby, hgb = hp.hgb;
+    c->reg_rank_hist += 1;
     unsigned int* d_hist = sc.d_hist;
     float* d_rank = sc.d_rank;
     static bool lds_attr[MVS_MAX_DEVICES] = {false};
@@ -1958,8 +1976,9 @@ int spearman_hist(ScoreCall& sc, int ic, const HistPlan& hp) {
 }
 
 // sorted ranks: compaction, sort by x carrying y, ranks of x in sorted order, sort by y carrying rank(x), correlation sums in
-// y-sorted order.  im1t == nullptr: the candidate has no shifted copy of its own; it is made here (into im1t_buf[0])
-int spearman_sorted(ScoreCall& sc, int ic, const float* im1t) {
+// y-sorted order.  im1t == nullptr: the candidate has no shifted copy of its own; it is made here (into im1t_buf[0]).
+// exact_t != nullptr (HistPlan::exact_keys): the moving image is ranked by its exact integer keys under that shift
+int spearman_sorted(ScoreCall& sc, int ic, const float* im1t, const double* exact_t) {
     MvsContext* c = sc.c;
     float* const* setA = sc.setA;
     float* const* setB = sc.setB;
@@ -1973,7 +1992,13 @@ int spearman_sorted(ScoreCall& sc, int ic, const float* im1t) {
     }
     MVS_HIP_TRY(c, hipMemsetAsync(sc.d_counter, 0, 4, c->stream));
     const float* raw0 = sc.so->raw_u16_keys[0];      // 16-bit integer keys for the fixed image when the caller vouches for them
-    hipLaunchKernelGGL(compact_kernel, dim3(sc.gb), dim3(256), 0, c->stream, sc.im0, im1t, sc.n, setA[0], setA[1], sc.d_counter, raw0);
+    (raw0 ? c->reg_rank_sort16 : c->reg_rank_sort32) += 1;
+    if (exact_t)
+        hipLaunchKernelGGL(compact_kernel<true>, dim3(sc.gb), dim3(256), 0, c->stream, sc.im0, im1t, sc.n, setA[0], setA[1], sc.d_counter, raw0,
+                           sc.so->raw_u16_keys[1], sc.S, exact_t[0], exact_t[1], exact_t[2]);
+    else
+        hipLaunchKernelGGL(compact_kernel<false>, dim3(sc.gb), dim3(256), 0, c->stream, sc.im0, im1t, sc.n, setA[0], setA[1], sc.d_counter, raw0,
+                           (const float*)nullptr, sc.S, 0.0, 0.0, 0.0);
     const unsigned int m = (unsigned int)sc.cnts[ic];
     const int mgb = (int)std::min<long long>(((long long)m + kRankChunk - 1) / kRankChunk, 2048);   // one chunk of sorted keys per workgroup turn
     if (raw0) {
@@ -1997,7 +2022,7 @@ int spearman_sorted(ScoreCall& sc, int ic, const float* im1t) {
 
 int spearman_from(ScoreCall& sc, int ic, const float* im1t) {
     HistPlan hp;
-    return hist_ranks_apply(sc, ic, &hp) ? spearman_hist(sc, ic, hp) : spearman_sorted(sc, ic, im1t);
+    return hist_ranks_apply(sc, ic, &hp) ? spearman_hist(sc, ic, hp) : spearman_sorted(sc, ic, im1t, hp.exact_keys ? hp.t : nullptr);
 }
 
 }  // namespace

@@ -379,8 +379,15 @@ def test_packed_inverse_transform_finds_the_same_peaks(hip_device):
 
 def test_register_crops_shortcuts_for_finite_crops_change_nothing(hip_device):
     """Finite crops take every shortcut of mvs_register_crops (packed inverse transform, no image statistics pass, analytic
-    valid boxes, on-the-fly integer shifts); "materialize_shifts" switches all of them off.  Same translation, same quality."""
+    valid boxes, on-the-fly integer shifts); "materialize_shifts" switches all of them off.  Same translation, same quality.
+    Host crops are ranked by float sorts whatever they hold (counter "reg_rank_sort32": the library learns that a crop holds
+    16-bit integers only from the statistics pass of device-resident crops), so the integer cases run a third time on
+    DeviceArray crops: the finite ones through the key histograms ("reg_rank_hist"), the one with NaNs through the sorts on
+    16-bit keys ("reg_rank_sort16") -- the same translation, the same rank vectors."""
     from multiview_stitcher_amd import _lib, _reg_ops
+    from multiview_stitcher_amd.device import DeviceArray
+
+    routes = ("hist", "sort16", "sort32")
 
     cases = [((24, 40, 36), (2, -3, 4), 2, False), ((51, 64, 48), (-1, 2, 3), 2, False), ((96, 80), (5, -7), 10, False),
              # integer-valued crops (uint16 tiles on the fixed grid): 16-bit rank keys for the fixed image; the last one with NaNs
@@ -396,15 +403,27 @@ def test_register_crops_shortcuts_for_finite_crops_change_nothing(hip_device):
         for flag in (1, 0):
             _lib.set_option("materialize_shifts", flag)
             try:
+                for r in routes:
+                    _lib.get_counter("reg_rank_" + r, reset=True)
                 res.append(_reg_ops.register_crops(a, b, up))
+                assert [_lib.get_counter("reg_rank_" + r, reset=True) for r in routes] == [0.0, 0.0, 1.0]
             finally:
                 _lib.set_option("materialize_shifts", 0)
         (t0, q0, st0, nc0), (t1, q1, st1, nc1) = res
         assert st0 == st1 == 0 and nc0 == nc1
+        if integer:
+            for r in routes:
+                _lib.get_counter("reg_rank_" + r, reset=True)
+            td, qd, std, ncd = _reg_ops.register_crops(DeviceArray.from_host(a), DeviceArray.from_host(b), up)
+            taken = [_lib.get_counter("reg_rank_" + r, reset=True) for r in routes]
+            assert taken == ([1.0, 0.0, 0.0] if integer is True else [0.0, 1.0, 0.0]), taken
+            assert std == 0 and ncd == nc1
+            np.testing.assert_array_equal(td, t1)
+            assert qd == pytest.approx(q1, rel=1e-10)
         np.testing.assert_array_equal(t0, t1)
         if integer is True:
-            # finite integer-valued crops + a shift in multiples of 1/2: the default path ranks by key histograms, the plain
-            # one by radix sorts -- the same rank vectors, sums taken in a different order
+            # finite integer-valued crops + a shift in multiples of 1/2: the device-resident run ranks by key histograms, the
+            # host runs by radix sorts -- the same rank vectors, sums taken in a different order
             assert q0 == pytest.approx(q1, rel=1e-10)
             want = ro.phase_correlation_registration(a, b)
             np.testing.assert_array_equal(want["affine_matrix"][:-1, -1], t1)
@@ -416,9 +435,15 @@ def test_register_crops_shortcuts_for_finite_crops_change_nothing(hip_device):
 @pytest.mark.parametrize("shape,bins,jit", [((48, 80, 64), (2, 2, 2), (1, -3, 2)), ((40, 64, 96), (2, 2, 2), (3, 1, -1)), ((64, 96), (1, 1), (2, -5))])
 def test_histogram_ranks_on_binned_integer_tiles_match_oracle(hip_device, shape, bins, jit):
     """uint16 tiles binned by 2 (registration.py:1732-1741: block mean cast back to uint16) and shifted by odd pixel counts:
-    the true shift is a half-integer on the binned grid, the winning candidate's moving crop is interpolated with weights
-    1/2, and the Spearman coefficient comes from key histograms.  Translation equal to the oracle's, quality within 1e-6."""
-    from multiview_stitcher_amd import _reg_ops
+    the true shift is a half-integer on the binned grid and the winning candidate's moving crop is interpolated with weights
+    1/2.  Translation equal to the oracle's, quality within 1e-6 -- for the host arrays, which the library ranks by float
+    sorts (counter "reg_rank_sort32"), and for the same pair on the device, where the statistics pass finds 16-bit integers
+    and the Spearman coefficient comes from key histograms ("reg_rank_hist": the 3D cases) or, for the 2D case's shift in tenths
+    of a pixel, from sorts on the fixed crop's 16-bit keys ("reg_rank_sort16")."""
+    from multiview_stitcher_amd import _lib, _reg_ops
+    from multiview_stitcher_amd.device import DeviceArray
+
+    routes = ("hist", "sort16", "sort32")
 
     rng = np.random.default_rng(7)
     ndim = len(shape)
@@ -433,13 +458,27 @@ def test_histogram_ranks_on_binned_integer_tiles_match_oracle(hip_device, shape,
         return v.astype(np.uint16).astype(np.float32)
 
     a, b = binned((0,) * ndim), binned(jit)
+    for r in routes:
+        _lib.get_counter("reg_rank_" + r, reset=True)
     t, q, st, nc = _reg_ops.register_crops(a, b, 2 if ndim == 3 else 10)
+    assert [_lib.get_counter("reg_rank_" + r, reset=True) for r in routes] == [0.0, 0.0, 1.0]
     want = ro.phase_correlation_registration(a, b)
     assert st == 0
     np.testing.assert_array_equal(t, want["affine_matrix"][:-1, -1])
     if ndim == 3:
         assert np.any(np.abs(t * 2 % 2) == 1)          # a genuinely half-integer component
     assert abs(q - want["quality"]) < 1e-6
+    # device-resident: both crops are finite 16-bit integers and at most 3 * 4001 bins fit the tables.  3D: the two-fold refinement
+    # gives a shift in multiples of 1/2 -> key histograms.  2D: the ten-fold refinement gives tenths of a pixel (-1.9 for the shift
+    # by 2) -> sorts, on the fixed crop's 16-bit keys
+    halves = bool(np.all(t * 2 == np.floor(t * 2)))
+    assert halves == (ndim == 3)
+    td, qd, std, ncd = _reg_ops.register_crops(DeviceArray.from_host(a), DeviceArray.from_host(b), 2 if ndim == 3 else 10)
+    taken = [_lib.get_counter("reg_rank_" + r, reset=True) for r in routes]
+    assert taken == ([1.0, 0.0, 0.0] if halves else [0.0, 1.0, 0.0]), taken
+    assert std == 0 and ncd == nc
+    np.testing.assert_array_equal(td, t)
+    assert abs(qd - want["quality"]) < 1e-6
 
 
 @pytest.mark.parametrize("shape,bins", [((16, 64, 128), (2, 2, 2)), ((9, 33, 64), (1, 2, 2)), ((12, 20, 72), (3, 1, 2)), ((8, 30, 50), (2, 2, 2)),
