@@ -108,7 +108,8 @@ const char* mvs_last_error(int device);
 int mvs_set_stream(int device, void* hip_stream);
 int mvs_synchronize(int device);
 /* Tuning / test switches. "force_generic" = 1: mvs_fuse_chunk never takes the translation fast
- * path (both paths must agree; tests compare them).  "no_regions" = 1: skip the region kernels. "deconv_general" = 1: mvs_mv_deconv
+ * path (both paths must agree; tests compare them).  "no_regions" = 1: skip the region kernels (the column kernel fuses
+ * instead; tests compare it with the oracle).  "deconv_general" = 1: mvs_mv_deconv
  * convolves through the general direct path even when separable factors are passed (tests compare both paths).  "dct_general" = 1:
  * the DCT quality pass of mvs_fuse_chunk_dct / mvs_content_dct_weights takes its general path (tests compare both paths).
  * "pool_cache_limit_mb": bytes (MiB) mvs_free may keep cached for later mvs_malloc calls
@@ -159,8 +160,13 @@ int mvs_set_option(int device, const char* key, int64_t value);
  * boxes, 1 NV = 2, 2 NV <= 4, 3 NV <= 8, 4 copy): "fuse_class_in_vox_<k>" (voxels x views of the class's boxes),
  * "fuse_class_out_vox_<k>", and "fuse_class_ms_<k>" = the class kernel's own duration when that launch ran with option
  * "serial_classes" = 1 (-1 otherwise).  "pool_misses" / "pool_miss_bytes" / "pool_releases": hipMalloc calls (and their bytes) that
- * mvs_malloc could not serve from its cache, blocks mvs_free handed back to the runtime.  reset != 0 clears an accumulating
- * counter after reading. */
+ * mvs_malloc could not serve from its cache, blocks mvs_free handed back to the runtime.  "fuse_rows_chunks" / "fuse_region_chunks" /
+ * "fuse_column_chunks" / "fuse_generic_chunks": chunks of mvs_fuse_chunk by the kernel family that fused them (row kernels, region
+ * kernels, column kernel, generic kernel; one count per family a call launched: a chunk that the column kernel gave up on because a
+ * column met more than 64 views, and that the generic kernel redid, counts in both; content-based and DCT-weighted chunks count in
+ * none).  With option "no_regions" = 1 a weighted-average chunk goes to the column kernel, which by default takes it only when the
+ * region planner declines (more than 8 views on a cell, too many cells or regions); tests assert the family they were built for.
+ * reset != 0 clears an accumulating counter after reading. */
 int mvs_get_counter(int device, const char* key, int32_t reset, double* value_out);
 /* Device time (ms, hipEvent) spent in the kernels of the most recent compute
  * call on this device; blocks until that work has finished. */

@@ -255,6 +255,10 @@ static const MvsCounter kCounters[] = {
     {"cb_mask_boxes", nullptr, &MvsContext::cb_mask_boxes},
     {"cb_line_launches", nullptr, &MvsContext::cb_line_launches},
     {"cb_overflows_redone", nullptr, &MvsContext::cb_overflows},
+    {"fuse_rows_chunks", nullptr, &MvsContext::fuse_rows_chunks},
+    {"fuse_region_chunks", nullptr, &MvsContext::fuse_region_chunks},
+    {"fuse_column_chunks", nullptr, &MvsContext::fuse_column_chunks},
+    {"fuse_generic_chunks", nullptr, &MvsContext::fuse_generic_chunks},
 };
 
 double mvs_rows_last_plan_ms(MvsContext* c);       // mvs_fuse_rows.hip

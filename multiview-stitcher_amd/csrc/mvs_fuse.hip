@@ -1546,6 +1546,7 @@ int mvs_fuse_chunk_impl(MvsContext* c, const mvs_view_t* views, int32_t n_views,
         rc = mvs_fuse_rows(c, htr, (const TrView*)((const char*)dviews + views_bytes + cull_bytes), n_views, dtype, dout, os,
                            opts->trim, &regions_done);
         if (rc) return rc;
+        if (regions_done) c->fuse_rows_chunks += 1;
     }
     if (!regions_done && nan_exact && use_tr) {   // float tiles the row kernels could not take: generic kernel
         use_tr = false;
@@ -1556,9 +1557,10 @@ int mvs_fuse_chunk_impl(MvsContext* c, const mvs_view_t* views, int32_t n_views,
         rc = mvs_fuse_regions(c, htr, (const TrView*)((const char*)dviews + views_bytes + cull_bytes), n_views, dtype, dout, os,
                               opts->trim, &regions_done);
         if (rc) return rc;
+        if (regions_done) c->fuse_region_chunks += 1;
     }
     if (regions_done) {
-        // fused by the region kernel
+        // fused by the row or region kernels
     } else if (use_tr) {
         TrParams T;
         T.views = (const TrView*)((const char*)dviews + views_bytes + cull_bytes);
@@ -1583,8 +1585,10 @@ int mvs_fuse_chunk_impl(MvsContext* c, const mvs_view_t* views, int32_t n_views,
             using E = decltype(tag);
             launch_fuse_tr<E, E>(T, opts->fusion, (int)nblocks, c->stream);
         });
+        c->fuse_column_chunks += 1;
     } else {
         launch_generic();
+        c->fuse_generic_chunks += 1;
     }
     MVS_HIP_TRY(c, hipGetLastError());
     if (use_tr && !regions_done && n_views > 64) {
@@ -1596,6 +1600,7 @@ int mvs_fuse_chunk_impl(MvsContext* c, const mvs_view_t* views, int32_t n_views,
             set_brick_grid(false);
             if (nblocks > 0x7fffffffLL) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "chunk too large for one launch");
             launch_generic();
+            c->fuse_generic_chunks += 1;
             MVS_HIP_TRY(c, hipGetLastError());
         }
     }

@@ -3,63 +3,28 @@ import numpy as np
 import pytest
 
 from oracle import fuse_oracle as fo
-from tests.helpers import (assert_fused_close, bb_to_dicts, reference_noise_floor, sim_to_view, squeeze_field,
-                           union_bb)
+from tests.helpers import grid_case as _grid_case, run_both as _run_both
+from tests.helpers import assert_fused_close, bb_to_dicts, sim_to_view, squeeze_field, union_bb
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(params=["fast", "generic", "rows"], autouse=True)
+@pytest.fixture(params=["fast", "generic", "rows", "column"], autouse=True)
 def kernel_path(request, hip_device):
     """Every parity case runs through each kernel family: the default translation fast path (region kernels; float
-    tiles: row kernels), the generic affine kernel forced, and the direct-load row kernels for every dtype -- all must match
-    the oracle."""
+    tiles: row kernels), the generic affine kernel forced, the direct-load row kernels for every dtype, and the column
+    kernel (option "no_regions": what fuses when the region planner declines a chunk) -- all must match the oracle.
+    float32 tiles at order 1 go to the row kernels by design whatever the switch (only they and the generic kernel read
+    the zero-weight taps scipy reads), so on "column" those cases repeat the default path."""
     from multiview_stitcher_amd import _lib
 
     _lib.set_option("force_generic", 1 if request.param == "generic" else 0)
     _lib.set_option("rows_v1", 1 if request.param == "rows" else 0)
+    _lib.set_option("no_regions", 1 if request.param == "column" else 0)
     yield request.param
     _lib.set_option("force_generic", 0)
     _lib.set_option("rows_v1", 0)
-
-
-def _grid_case(ndim, dtype, tiles, tile_shape, overlap, frac_shift, seed=0, spacing=None):
-    from multiview_stitcher_amd import sample_data, spatial_image_utils as si
-
-    sims, jit, _ = sample_data.generate_tiled_dataset(
-        ndim=ndim, tile_shape=tile_shape, tiles=tiles, overlap=overlap, dtype=dtype, seed=seed, spacing=spacing
-    )
-    sims = [squeeze_field(s) for s in sims]
-    rng = np.random.default_rng(seed + 7)
-    params = []
-    for s in sims:
-        p = np.eye(ndim + 1)
-        if frac_shift:
-            p[:ndim, ndim] = rng.uniform(-2, 2, ndim)
-        params.append(p)
-    return sims, params
-
-
-def _run_both(sims, params, out_bb, **kw):
-    from multiview_stitcher_amd import fusion, spatial_image_utils as si
-
-    sdims = si.get_spatial_dims_from_sim(sims[0])
-    views, bbs = zip(*[sim_to_view(s) for s in sims])
-    okw = dict(kw)
-    fusion_name = okw.pop("fusion", "weighted_average")
-    want, want_f, dbg = fo.fuse_np(list(views), params, out_bb, fusion=fusion_name, full_view_bbs=list(bbs),
-                                   return_debug=True, **okw)
-    floor = reference_noise_floor(dbg, want_f)
-    ffunc = {"weighted_average": fusion.weighted_average_fusion, "max": fusion.max_fusion,
-             "simple_average": fusion.simple_average_fusion}[fusion_name]
-    got = fusion.fuse_np(
-        list(sims), params, bb_to_dicts(out_bb, sdims), fusion_func=ffunc,
-        full_view_bbs=[bb_to_dicts(b, sdims) for b in bbs],
-        interpolation_order=kw.get("interpolation_order", 1),
-        trim_overlap_in_pixels=kw.get("trim_overlap_in_pixels", 0),
-        blending_widths=kw.get("blending_widths"),
-    )
-    return got, want, (want_f, floor)
+    _lib.set_option("no_regions", 0)
 
 
 @pytest.mark.parametrize("dtype", [np.uint16, np.float32, np.uint8])
@@ -495,7 +460,7 @@ def test_fuse_content_based_chunked_workflow(hip_device, kernel_path):
 
 def test_more_than_64_views_on_one_column_falls_back(hip_device, kernel_path):
     """The fast kernel lists at most 64 views per column; a chunk where more overlap is redone generically."""
-    from multiview_stitcher_amd import fusion, spatial_image_utils as si
+    from multiview_stitcher_amd import _lib, fusion, spatial_image_utils as si
 
     rng = np.random.default_rng(0)
     sims, params = [], []
@@ -508,8 +473,13 @@ def test_more_than_64_views_on_one_column_falls_back(hip_device, kernel_path):
         params.append(p)
     _, bbs = zip(*[sim_to_view(s) for s in sims])
     out_bb = union_bb(bbs, params, np.ones(2))
+    for key in ("fuse_column_chunks", "fuse_generic_chunks"):
+        _lib.get_counter(key, reset=True)
     got, want, want_f = _run_both(sims, params, out_bb)
     assert_fused_close(got, want, want_f[0], noise_floor=want_f[1])
+    if kernel_path == "fast":
+        # the column kernel ran, raised its overflow flag, and the generic kernel redid the chunk
+        assert _lib.get_counter("fuse_column_chunks") >= 1 and _lib.get_counter("fuse_generic_chunks") >= 1
 
 
 def test_user_callables_get_device_resampled_views(hip_device):
