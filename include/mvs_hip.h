@@ -543,6 +543,38 @@ int mvs_affine_normal_eq(int device, const float* fixed, const float* moving, in
                          const double matrix[9], const double offset[3],
                          double gain, double bias, double* out);
 
+/* Mattes mutual information of the same warped crop pair (registration.affine_registration, metric="mattes").  Crops, mem,
+ * ndim, shape, matrix, offset, the warp and the rule for a valid sample: as mvs_affine_normal_eq.  n_bins = B in 8..64.  Per valid
+ * sample, in float32 (arithmetic and operation order: csrc/mvs_affine_mi_dev.h): the fixed bin a = clamp(floor((F - f_lo) *
+ * f_scale + 0.5), 0, B - 1); the moving coordinate u = clamp((v - m_lo) * m_scale + 1.5, 1.5, B - 2.5) with its four taps
+ * b_k = floor(u) - 1 + k; the cubic B-spline window beta3(u - b_k).  The caller passes f_scale = (B - 1) / (f_hi - f_lo) and
+ * m_scale = (B - 4) / (m_hi - m_lo) for the finite ranges of the two crops (mvs_finite_range).
+ *
+ * mvs_affine_joint_hist: hist_out[a * B + b_k] += (int64)(beta3(u - b_k) * 2^20 + 0.5) over all valid samples (B * B values, host
+ * memory), *n_valid_out = their number.  The weights are integers, so the sums do not depend on their order: the kernel adds with
+ * integer atomics (LDS, then global) and equal inputs still give equal bits.
+ *
+ * mvs_affine_mi_gradient: table (B * B float32, host memory: L[a][b]); per valid sample w = sum_k beta3'(u - b_k) * L[a][b_k] in
+ * float32 in k order.  out (MVS_AFFINE_MI_GRAD_LEN doubles, packed for the given ndim, the rest zero): sum w g_j (x - c)_i and
+ * sum w g_j in the order of the rows of [A | t] (P = ndim (ndim + 1) values, the monomials of J^T r of mvs_affine_normal_eq), then
+ * the valid count.  Threads sum runs of 32 samples in float32, everything above in double, in a fixed order, no floating-point
+ * atomics: equal inputs give equal bits.  Both wait for their result and run on the context lane of `device`. */
+#define MVS_AFFINE_MI_GRAD_LEN (12 + 1)
+int mvs_affine_joint_hist(int device, const float* fixed, const float* moving, int32_t mem,
+                          int32_t ndim, const int64_t shape[3],
+                          const double matrix[9], const double offset[3],
+                          int32_t n_bins, float f_lo, float f_scale, float m_lo, float m_scale,
+                          int64_t* hist_out, int64_t* n_valid_out);
+int mvs_affine_mi_gradient(int device, const float* fixed, const float* moving, int32_t mem,
+                           int32_t ndim, const int64_t shape[3],
+                           const double matrix[9], const double offset[3],
+                           int32_t n_bins, float f_lo, float f_scale, float m_lo, float m_scale,
+                           const float* table, double* out);
+
+/* Minimum, maximum and number of the finite values (neither NaN nor +-inf) of n float32 values in `mem`; NaN, NaN, 0 when there
+ * is none.  Per-block partials, finished on the host.  Waits for the result; runs on the context lane of `device`. */
+int mvs_finite_range(int device, const float* data, int32_t mem, int64_t n, float* min_out, float* max_out, int64_t* n_finite_out);
+
 /* Bead detection (detection.log_detect), first half: the Laplacian-of-Gaussian response of a C-contiguous 2-D / 3-D image (uint8,
  * uint16 or float32, in `mem`; ndim 2: shape = (1, ny, nx)).  response (device memory, float32, the image's shape) becomes
  *   -scipy.ndimage.gaussian_laplace(image as float32, sigma, mode="reflect") * scale.

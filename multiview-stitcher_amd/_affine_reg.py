@@ -3,6 +3,10 @@
 The voxel-sized work of an iteration -- warping the moving crop, the residual and the normal equations -- is one library
 call (``mvs_affine_normal_eq``); what stays here is the model algebra on at most 12 parameters, in float64.
 
+``metric="mattes"`` maximises the Mattes mutual information instead (``optimise_mi``): per iteration one joint histogram
+(``mvs_affine_joint_hist``) per tried step length and one gradient reduction (``mvs_affine_mi_gradient``); the histogram
+algebra -- probabilities, the metric, the table of logarithms -- is B x B float64 work on the host.
+
 Pose convention: ``(A, t)`` is centred and in full-resolution pixels, fixed voxel ``x`` samples moving at
 ``p = c + t + A (x - c)`` with ``c = (shape - 1) / 2``.  Parameters of the normal equations: the rows of ``[A | t]``.
 """
@@ -14,6 +18,9 @@ import warnings
 import numpy as np
 
 MODELS = ("translation", "rigid", "similarity", "affine")
+METRICS = ("ssd", "mattes")
+MIN_BINS, MAX_BINS = 8, 64
+MIN_ALPHA = 2.0 ** -10          # the backtracking search of the mattes loop gives up below this step length (level voxels)
 
 
 def rotation_generators(ndim):
@@ -171,15 +178,99 @@ def optimise(normal_equations, levels, shape, model, A, t, max_iterations, toler
     return A, t, history
 
 
+def mutual_information(hist):
+    """From a joint histogram (rows: fixed bin, columns: moving bin), in float64: (MI = sum_{P>0} P log(P / (pF pM)), the
+    table L = log(P / pM) where P > 0 else 0, the symmetric uncertainty 2 MI / (H_F + H_M))."""
+    P = np.asarray(hist, dtype=np.float64)
+    P = P / P.sum()
+    pF, pM = P.sum(axis=1), P.sum(axis=0)
+    pos = P > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        table = np.where(pos, np.log(P / pM[None, :]), 0.0)
+        mi = float(np.sum(np.where(pos, P * np.log(P / (pF[:, None] * pM[None, :])), 0.0)))
+        entropy = -(np.sum(np.where(pF > 0, pF * np.log(pF), 0.0)) + np.sum(np.where(pM > 0, pM * np.log(pM), 0.0)))
+    return mi, table, (2.0 * mi / float(entropy) if entropy > 0 else np.nan)
+
+
+def bin_ranges(f_lo, f_hi, m_lo, m_hi, n_bins):
+    """(f_lo, f_scale, m_lo, m_scale) of the kernels, as float32; raises ``Refused`` when a crop has no spread."""
+    if not (f_hi > f_lo and m_hi > m_lo):
+        raise Refused("a crop is constant or has no finite value")
+    return (np.float32(f_lo), np.float32((n_bins - 1) / (float(f_hi) - float(f_lo))),
+            np.float32(m_lo), np.float32((n_bins - 4) / (float(m_hi) - float(m_lo))))
+
+
+def optimise_mi(metric, gradient, preconditioner, levels, shape, model, A, t, max_iterations, tolerance):
+    """The coarse-to-fine loop of ``metric="mattes"`` (ascent).  ``metric(level_index, A, t_b)`` returns (MI, table, n valid) of
+    a pose, ``gradient(level_index, A, t_b, table)`` d MI / d theta (theta: the rows of ``[A | t]``) and
+    ``preconditioner(level_index, A, t_b)`` the J^T J of the squared-residual metric at gain 1, bias 0; it is taken once per
+    level, at the level's first pose.  Per iteration: the direction ``(B^T H B)^-1 B^T g`` scaled to one level voxel of corner
+    displacement, then a backtracking search on the step length alpha, from ``min(1, 2 * previous alpha)`` down to
+    ``MIN_ALPHA``, for a pose of larger MI (one ``metric`` call per trial).  A level ends when no alpha is found, when the
+    accepted step moves no corner by ``tolerance`` or at its cap.  Returns (A, t, history)."""
+    ndim = len(shape)
+    nq = n_model_params(model, ndim)
+    history = []
+    for li, (b, cap) in enumerate(zip(levels, max_iterations)):
+        t_b = to_level(A, t, shape, b)
+        mi, table, n = metric(li, A, t_b)
+        if n < 4 * nq:
+            raise Refused(f"{int(n)} valid samples for {nq} parameters")
+        H = preconditioner(li, A, t_b)
+        alpha = 0.5
+        for _ in range(int(cap)):
+            t_b = to_level(A, t, shape, b)
+            g = gradient(li, A, t_b, table)
+            B = model_jacobian(model, A)
+            try:
+                L = np.linalg.cholesky(B.T @ H @ B)
+            except np.linalg.LinAlgError:
+                raise Refused("the preconditioner is not positive definite") from None
+            s = np.linalg.solve(L.T, np.linalg.solve(L, B.T @ g))
+
+            def moved(q):
+                A1, t1_b = apply_update(model, A, t_b, q)
+                return A1, from_level(A1, t1_b, shape, b)
+
+            d1 = corner_displacement(A, t, *moved(s), shape)
+            if not (d1 > 0.0 and np.isfinite(d1)):
+                break
+            s = s * (b / d1)
+            alpha = min(1.0, 2.0 * alpha)
+            found = None
+            while alpha >= MIN_ALPHA:
+                A1, t1 = moved(alpha * s)
+                trial = metric(li, A1, to_level(A1, t1, shape, b))
+                if trial[2] >= 4 * nq and trial[0] > mi:
+                    found = trial
+                    break
+                alpha /= 2.0
+            if found is None:
+                history.append({"level": li, "mi": mi, "n": int(n), "alpha": 0.0, "step": 0.0})
+                break
+            step = corner_displacement(A, t, A1, t1, shape)
+            history.append({"level": li, "mi": mi, "n": int(n), "alpha": alpha, "step": step})
+            A, t = A1, t1
+            mi, table, n = found
+            if step < tolerance:
+                break
+    return A, t, history
+
+
 def affine_registration(fixed_data, moving_data, transform_type="rigid", shrink_factors=(2, 1), max_iterations=(30, 20), tolerance=1e-3,
-                        initial_affine="phase_correlation", fit_intensity=True, device=0, return_debug=False):
+                        initial_affine="phase_correlation", fit_intensity=True, device=0, return_debug=False, metric="ssd", n_bins=32):
     """See ``registration.affine_registration``."""
+    if metric not in METRICS:
+        raise ValueError(f"metric must be one of {METRICS}")
+    if not (isinstance(n_bins, (int, np.integer)) and MIN_BINS <= n_bins <= MAX_BINS):
+        raise ValueError(f"n_bins must be an integer in {MIN_BINS}..{MAX_BINS}")
+    if transform_type not in MODELS:
+        raise ValueError(f"transform_type must be one of {MODELS}")
+
     from . import _reg_ops, registration
     from .device import DeviceArray, is_device_array
     from .transformation import resample_array
 
-    if transform_type not in MODELS:
-        raise ValueError(f"transform_type must be one of {MODELS}")
     if len(shrink_factors) != len(max_iterations):
         raise ValueError("shrink_factors and max_iterations must have the same length")
     F = registration._as_array(fixed_data)
@@ -235,7 +326,35 @@ def affine_registration(fixed_data, moving_data, transform_type="rigid", shrink_
     def normal_equations(li, A, t_b, gain, bias):
         return _reg_ops.affine_normal_equations(crops[li][0], crops[li][1], A, t_b, gain, bias, device)
 
+    n_bins = int(n_bins)
+    ranges = {}
+
+    def level_ranges(F_l, M_l):
+        f_lo, f_hi, _ = _reg_ops.finite_range(F_l, device)
+        m_lo, m_hi, _ = _reg_ops.finite_range(M_l, device)
+        return bin_ranges(f_lo, f_hi, m_lo, m_hi, n_bins)
+
+    def mi_metric(li, A, t_b):
+        if li not in ranges:
+            ranges[li] = level_ranges(*crops[li])
+        hist, n = _reg_ops.affine_joint_hist(crops[li][0], crops[li][1], A, t_b, n_bins, ranges[li], device)
+        if n == 0:
+            return -np.inf, None, 0
+        mi, table, _ = mutual_information(hist)
+        return mi, table, n
+
+    def mi_gradient(li, A, t_b, table):
+        sums, n = _reg_ops.affine_mi_gradient(crops[li][0], crops[li][1], A, t_b, n_bins, ranges[li], table, device)
+        return (float(ranges[li][3]) / n) * sums
+
     try:
+        if metric == "mattes":
+            A, t, history = optimise_mi(mi_metric, mi_gradient, lambda li, A, t_b: normal_equations(li, A, t_b, 1.0, 0.0)[0], levels,
+                                        shape, transform_type, A0, t0, caps, tolerance)
+            # quality: the symmetric uncertainty 2 MI / (H_F + H_M) of the full-resolution histogram at the result, in [0, 1]
+            # (a rank correlation means nothing across a relation that is not monotone)
+            hist, n = _reg_ops.affine_joint_hist(F, M, A, t, n_bins, level_ranges(F, M), device)
+            return result(A, t, mutual_information(hist)[2] if n > 0 else np.nan, history)
         A, t, history = optimise(normal_equations, levels, shape, transform_type, A0, t0, caps, tolerance, fit_intensity)
     except Refused as e:
         warnings.warn(f"affine_registration: {e}; returning the initial pose.", UserWarning, stacklevel=3)

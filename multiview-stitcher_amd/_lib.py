@@ -21,6 +21,7 @@ MVS_MEM_HOST, MVS_MEM_DEVICE = 0, 1
 MVS_FUSE_WEIGHTED_AVERAGE, MVS_FUSE_MAX, MVS_FUSE_SIMPLE_AVERAGE = 0, 1, 2
 MVS_WEIGHTS_NONE, MVS_WEIGHTS_CONTENT_BASED = 0, 1
 MVS_AFFINE_NEQ_LEN = 12 * 12 + 12 + 7
+MVS_AFFINE_MI_GRAD_LEN = 12 + 1
 MVS_LOG_MAX_RADIUS = 40
 
 DTYPE_CODES = {np.dtype(np.uint8): MVS_U8, np.dtype(np.uint16): MVS_U16, np.dtype(np.float32): MVS_F32}
@@ -229,6 +230,17 @@ SIGNATURES = {
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double),
          C.c_double, C.c_double, C.POINTER(C.c_double)],
     ),
+    "mvs_affine_joint_hist": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double),
+         C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    ),
+    "mvs_affine_mi_gradient": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double),
+         C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_double)],
+    ),
+    "mvs_finite_range": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
     "mvs_log_response": (
         C.c_int,
         [C.c_int, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double),

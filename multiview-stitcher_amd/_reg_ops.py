@@ -261,3 +261,60 @@ def affine_normal_equations(fixed, moving, A, t, gain=1.0, bias=0.0, device=0):
     b = out[P * P:P * P + P].copy()
     rest = out[P * P + P:P * P + P + 7]
     return H, b, float(rest[0]), float(rest[1]), tuple(float(v) for v in rest[2:7])
+
+
+def finite_range(a, device=0):
+    """(minimum, maximum, count) of the finite values of a float32 crop (mvs_finite_range); NaN, NaN, 0 when it has none."""
+    lib = _lib.init(device)
+    ptr, mem, keep = _ptr_mem(a)
+    mn, mx, nv = C.c_float(), C.c_float(), C.c_int64()
+    rc = lib.mvs_finite_range(device, ptr, mem, int(np.prod(a.shape)), C.byref(mn), C.byref(mx), C.byref(nv))
+    _lib.check(rc, device, "mvs_finite_range")
+    return float(mn.value), float(mx.value), int(nv.value)
+
+
+def _mi_geometry(fixed, moving, A, t):
+    shape = tuple(int(s) for s in fixed.shape)
+    if tuple(moving.shape) != shape:
+        raise ValueError("crops must have the same shape")
+    ndim = len(shape)
+    p0, m0, k0 = _ptr_mem(fixed)
+    p1, m1, k1 = _ptr_mem(moving)
+    if m0 != m1:
+        raise TypeError("both crops must live on the same side (host or device)")
+    A3 = np.eye(3)
+    A3[3 - ndim:, 3 - ndim:] = np.asarray(A, dtype=np.float64).reshape(ndim, ndim)
+    t3 = np.zeros(3)
+    t3[3 - ndim:] = np.asarray(t, dtype=np.float64).reshape(ndim)
+    dp = C.POINTER(C.c_double)
+    return (p0, p1, m0, ndim, _lib.i64x3(shape3(shape)), A3.ctypes.data_as(dp), t3.ctypes.data_as(dp)), (k0, k1, A3, t3)
+
+
+def affine_joint_hist(fixed, moving, A, t, n_bins, ranges, device=0):
+    """Joint histogram of the Mattes metric over the warped crop pair (mvs_affine_joint_hist).  Crops and pose as
+    ``affine_normal_equations``; ``ranges`` = (f_lo, f_scale, m_lo, m_scale).  Returns (hist (B, B) int64: rows = fixed bin,
+    columns = moving bin, in units of 2^-20 sample; n valid)."""
+    lib = _lib.init(device)
+    geom, keep = _mi_geometry(fixed, moving, A, t)
+    hist = np.empty((int(n_bins), int(n_bins)), dtype=np.int64)
+    n = C.c_int64()
+    rc = lib.mvs_affine_joint_hist(device, *geom, int(n_bins), *[float(v) for v in ranges], hist.ctypes.data_as(C.POINTER(C.c_int64)),
+                                   C.byref(n))
+    _lib.check(rc, device, "mvs_affine_joint_hist")
+    return hist, int(n.value)
+
+
+def affine_mi_gradient(fixed, moving, A, t, n_bins, ranges, table, device=0):
+    """Gradient sums of the Mattes metric (mvs_affine_mi_gradient); ``table``: (B, B) L[a][b], passed as float32.  Returns
+    (sums (P,) in the order of the rows of ``[A | t]``, n valid); d MI / d theta = (m_scale / n) * sums."""
+    lib = _lib.init(device)
+    geom, keep = _mi_geometry(fixed, moving, A, t)
+    tab = np.ascontiguousarray(table, dtype=np.float32)
+    if tab.shape != (int(n_bins), int(n_bins)):
+        raise ValueError("table must be n_bins x n_bins")
+    out = np.empty(_lib.MVS_AFFINE_MI_GRAD_LEN, dtype=np.float64)
+    rc = lib.mvs_affine_mi_gradient(device, *geom, int(n_bins), *[float(v) for v in ranges], tab.ctypes.data_as(C.POINTER(C.c_float)),
+                                    out.ctypes.data_as(C.POINTER(C.c_double)))
+    _lib.check(rc, device, "mvs_affine_mi_gradient")
+    P = geom[3] * (geom[3] + 1)
+    return out[:P].copy(), int(out[P])

@@ -154,7 +154,7 @@ def phase_correlation_registration(fixed_data, moving_data, disambiguate_region_
 
 
 def affine_registration(fixed_data, moving_data, transform_type="rigid", shrink_factors=(2, 1), max_iterations=(30, 20), tolerance=1e-3,
-                        initial_affine="phase_correlation", fit_intensity=True, device=0, return_debug=False):
+                        initial_affine="phase_correlation", fit_intensity=True, device=0, return_debug=False, metric="ssd", n_bins=32):
     """Rigid / affine intensity registration of two same-shape overlap crops (float32, NaN = outside the view): a drop-in
     ``pairwise_reg_func`` in the seat of the reference's ``registration_ANTsPy`` (registration.py:2774-2922).
 
@@ -169,11 +169,20 @@ def affine_registration(fixed_data, moving_data, transform_type="rigid", shrink_
     Returns ``{"affine_matrix": fixed px -> moving px, "quality": masked Spearman coefficient of the aligned crops}``;
     ``return_debug`` adds ``"debug": {"history": [{level, msd, n, gain, bias, step}, ...], "initial_affine"}``.  Warns and
     returns the initial pose with quality NaN when fewer than 4 valid samples per model parameter remain or the projected
-    normal equations are not positive definite."""
+    normal equations are not positive definite.
+
+    ``metric="mattes"`` maximises the Mattes mutual information of the two crops instead (``n_bins`` bins per axis, 8..64; an
+    order-0 window on the fixed values, a cubic B-spline window on the moving ones): for crops whose intensities are not
+    linearly related, such as opposite views or two channels.  Preconditioned gradient ascent with a backtracking step
+    length; per iteration one ``mvs_affine_mi_gradient`` launch and one ``mvs_affine_joint_hist`` launch per tried step.
+    ``fit_intensity`` is not used, and the phase-correlation start assumes related intensities too: where it cannot be trusted
+    pass ``initial_affine="identity"`` (or a matrix).  ``quality`` is then the symmetric uncertainty ``2 MI / (H_F + H_M)`` of the final
+    full-resolution histogram, in [0, 1], and the history rows are ``{level, mi, n, alpha, step}``.  It also warns and returns
+    the initial pose when a crop is constant."""
     from . import _affine_reg
 
     return _affine_reg.affine_registration(fixed_data, moving_data, transform_type, shrink_factors, max_iterations, tolerance,
-                                           initial_affine, fit_intensity, device, return_debug)
+                                           initial_affine, fit_intensity, device, return_debug, metric, n_bins)
 
 
 def get_optimal_registration_binning(sim1, sim2, max_total_pixels_per_stack=400**3, overlap_tolerance=None):
