@@ -612,6 +612,44 @@ int mvs_local_maxima(int device, const float* response, int32_t ndim, const int6
                      float threshold, const void* sample, int32_t sample_dtype, const int32_t sample_window[3], double bound,
                      int32_t* coords_out, int64_t capacity, int64_t* count_out);
 
+/* Registration quality metrics (metrics.tile_pair_image_metrics): the sample moments of a fixed and a moving tile over the
+ * overlap grid of one directed pair, for up to MVS_PAIR_MAX_CANDIDATES candidate transforms of the moving tile in one pass.
+ *   fixed->matrix / offset        grid index -> fixed pixel
+ *   cand_matrix[k] / cand_offset[k]   grid index -> moving pixel under candidate k (9 + 3 doubles, the layout of mvs_view_t;
+ *                                 the matrix / offset of `moving` itself are not read)
+ *   halfspaces                    n_halfspaces rows (a_z, a_y, a_x, b) in GRID INDEX coordinates (0 .. MVS_PAIR_MAX_HALFSPACES rows)
+ * The views are uint8, uint16 or float32 and share one dtype (else MVS_ERR_UNSUPPORTED), in host or device memory, possibly
+ * strided windows (stride[2] == 1); host slabs are C-contiguous and staged as by mvs_resample.  ndim 2: grid_shape[0] == 1 and
+ * shape[0] == 1 of both views.
+ * Per grid voxel (z, y, x), all coordinate arithmetic in double without contraction:
+ *   1. mask:   ((a_z z + a_y y) + a_x x) + b <= 0 for every halfspace (none given: every voxel passes);
+ *   2. fixed sample: c = ((z m0 + y m1) + x m2) + offset per axis; in bounds iff 0 <= c <= n - 1 on every axis; the bi / trilinear
+ *      sample of mvs_resample (order 1: float32 weights and taps, all taps read, so a NaN tap -- also one of weight 0 -- makes the
+ *      sample NaN); computed once and used for every candidate;
+ *   3. moving sample: the same under candidate k;
+ *   4. the pair (f, m_k) counts for candidate k iff the mask holds, both samples are in bounds and both are finite.
+ * out (host memory) receives n_candidates rows of MVS_PAIR_MOMENTS_LEN doubles
+ *   n, mean_f, mean_m, M2_f = sum (f - mean_f)^2, M2_m = sum (m - mean_m)^2, C_fm = sum (f - mean_f)(m - mean_m)
+ * over the counted pairs (n == 0: all six are 0).  Row k belongs to candidate k: callers keep the reference's order, the list
+ * candidate_keys of metrics.py:550-555 (the query transform keys as given, or the single key "transform").  A candidate's row does
+ * not depend on which other candidates share the launch.
+ * Reduction: every thread takes one voxel per step of a grid-stride loop and keeps, per candidate, an integer count and float64
+ * sums of the samples SHIFTED by its first counted pair (no raw sum of squares: a 16-bit tile at 60000 +- 3 keeps its variance,
+ * a constant tile sampled without interpolation rounding has M2 == 0 exactly), turns them into a record (n, means, M2s, C) and
+ * records are merged pairwise with the update of Chan, Golub and LeVeque in a fixed tree: the lanes of a wave by shuffles, the
+ * waves of a workgroup through LDS, one record per workgroup in scratch, and a second launch (one wave per candidate: each lane
+ * folds a run of consecutive records in index order, then the lanes merge).  No floating-point atomics and no completion
+ * counters; the launch has min(ceil(voxels / MVS_PAIR_BLOCK_VOXELS), MVS_PAIR_MAX_BLOCKS) workgroups, a function of the voxel
+ * count only, so equal inputs give equal bits.  Waits for the result; runs on the lane of `device`. */
+#define MVS_PAIR_MOMENTS_LEN 6
+#define MVS_PAIR_MAX_CANDIDATES 8
+#define MVS_PAIR_MAX_HALFSPACES 16
+#define MVS_PAIR_BLOCK_VOXELS 256
+#define MVS_PAIR_MAX_BLOCKS 2048
+int mvs_pair_moments(int device, const mvs_view_t* fixed, const mvs_view_t* moving, int32_t n_candidates,
+                     const double* cand_matrix, const double* cand_offset, int32_t ndim, const int64_t grid_shape[3],
+                     const double* halfspaces, int32_t n_halfspaces, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,3 +7,12 @@ for gfx950 behind the C ABI of ``include/mvs_hip.h``).  There is no CPU
 fallback: every compute entry point raises if the HIP library is missing."""
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # ``multiview_stitcher_amd.metrics`` without an explicit submodule import (loaded at first use: it binds the HIP library)
+    if name == "metrics":
+        import importlib
+
+        return importlib.import_module(__name__ + ".metrics")
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -23,6 +23,11 @@ MVS_WEIGHTS_NONE, MVS_WEIGHTS_CONTENT_BASED = 0, 1
 MVS_AFFINE_NEQ_LEN = 12 * 12 + 12 + 7
 MVS_AFFINE_MI_GRAD_LEN = 12 + 1
 MVS_LOG_MAX_RADIUS = 40
+MVS_PAIR_MOMENTS_LEN = 6          # n, mean_f, mean_m, M2_f, M2_m, C_fm
+MVS_PAIR_MAX_CANDIDATES = 8
+MVS_PAIR_MAX_HALFSPACES = 16
+MVS_PAIR_BLOCK_VOXELS = 256
+MVS_PAIR_MAX_BLOCKS = 2048
 
 DTYPE_CODES = {np.dtype(np.uint8): MVS_U8, np.dtype(np.uint16): MVS_U16, np.dtype(np.float32): MVS_F32}
 CODE_DTYPES = {v: k for k, v in DTYPE_CODES.items()}
@@ -250,6 +255,11 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_float, C.c_void_p, C.c_int32,
          C.POINTER(C.c_int32), C.c_double, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64)],
+    ),
+    "mvs_pair_moments": (
+        C.c_int,
+        [C.c_int, C.POINTER(mvs_view_t), C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32,
+         C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double)],
     ),
 }
 
