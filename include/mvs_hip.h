@@ -650,6 +650,44 @@ int mvs_pair_moments(int device, const mvs_view_t* fixed, const mvs_view_t* movi
                      const double* cand_matrix, const double* cand_offset, int32_t ndim, const int64_t grid_shape[3],
                      const double* halfspaces, int32_t n_halfspaces, double* out);
 
+/* Marker-based (bead) registration, registration.registration_marker_based (registration.py:595-1379): the three device entry
+ * points below; thresholds, the ratio test, sampling, the model fits, ranking and the ICP bookkeeping are host work.  All
+ * arithmetic on coordinates and distances is float64 without contraction; a distance is sqrt(sum_d (a_d - b_d)^2), summed over the
+ * DIFFERENCES in axis order (world coordinates at 1e6 with sub-pixel differences keep their digits).  All three wait for their
+ * result and run on the context lane of `device`.
+ *
+ * mvs_knn: brute-force k nearest neighbours, in the seat of the reference's cKDTree(...).query calls (registration.py:619, 662-664,
+ * 743-746, 1095-1097).  ref: n_ref rows of dim float64, query: n_query rows, each C-contiguous in host or device memory (ref_mem /
+ * query_mem); the same pointer for both (a set against itself) is staged once.  idx_out / dist_out (host memory, n_query x k):
+ * the k nearest reference rows of every query, ascending by distance, equal distances by ascending reference index; with
+ * k > n_ref the tail is index -1 and distance +inf.  A NaN distance never enters the list.  1 <= dim <= MVS_KNN_MAX_DIM (the
+ * descriptor length C(num_neighbors + 1, 2) at num_neighbors = 5) and 1 <= k <= MVS_KNN_MAX_K, else MVS_ERR_UNSUPPORTED; at most
+ * 2^30 rows per set.  One query per thread with its coordinates and its sorted top-k in registers (dim 1, 2, 3, 6, 10 and k 1, 2,
+ * 8, 16 are compiled forms, other values take the next larger); reference rows pass through LDS in tiles of 256, component-major. */
+#define MVS_KNN_MAX_DIM 15
+#define MVS_KNN_MAX_K 16
+int mvs_knn(int device, const double* ref, int32_t ref_mem, int64_t n_ref, const double* query, int32_t query_mem, int64_t n_query,
+            int32_t dim, int32_t k, int32_t* idx_out, double* dist_out);
+
+/* The geometric descriptors of registration.py:666-690.  points: n_points x ndim float64 (ndim 2 or 3) in points_mem; neighbors
+ * (host memory): n_points x required int32, required = num_neighbors + redundancy -- each point's nearest OTHER points.  For point
+ * p and subset s of its neighbours -- the C = C(required, num_neighbors) subsets in itertools.combinations order -- row p * C + s
+ * of out (out_mem; n_points * C rows of num_neighbors (num_neighbors + 1) / 2 float64) is the ascending vector of all pairwise
+ * distances among the point and the subset.  One thread per row; a fixed compare-exchange sequence sorts.  A neighbour index
+ * outside [0, n_points) makes its rows NaN.  num_neighbors above MVS_MARKER_MAX_NEIGHBORS or required above MVS_KNN_MAX_K - 2
+ * (the neighbourhood query takes required + 2): MVS_ERR_UNSUPPORTED. */
+#define MVS_MARKER_MAX_NEIGHBORS 5
+int mvs_marker_descriptors(int device, const double* points, int32_t points_mem, int64_t n_points, int32_t ndim,
+                           const int32_t* neighbors, int32_t num_neighbors, int32_t redundancy, double* out, int32_t out_mem);
+
+/* The scoring step of the RANSAC loop (registration.py:867-871, 958-969) for all hypotheses at once.  affines: n_hypotheses
+ * row-major (ndim + 1)^2 fixed -> moving matrices; fixed / moving: n_corr x ndim candidate correspondences (all host memory).
+ * count_out[h] = number of correspondences with || A_h f + t_h - m || <= max_error, sum_out[h] = the sum of those residuals (host
+ * memory).  One wave per hypothesis: lane l adds correspondences l, l + 64, ... in order, the lanes are folded by a fixed shuffle
+ * tree -- no floating-point atomics, equal inputs give equal bits. */
+int mvs_marker_score(int device, const double* affines, int32_t n_hypotheses, const double* fixed, const double* moving,
+                     int64_t n_corr, int32_t ndim, double max_error, int32_t* count_out, double* sum_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,10 @@ MVS_PAIR_MAX_CANDIDATES = 8
 MVS_PAIR_MAX_HALFSPACES = 16
 MVS_PAIR_BLOCK_VOXELS = 256
 MVS_PAIR_MAX_BLOCKS = 2048
+MVS_KNN_MAX_DIM = 15
+MVS_KNN_MAX_K = 16
+MVS_MARKER_MAX_NEIGHBORS = 5
+ERR_UNSUPPORTED = -4            # MVS_ERR_UNSUPPORTED
 
 DTYPE_CODES = {np.dtype(np.uint8): MVS_U8, np.dtype(np.uint16): MVS_U16, np.dtype(np.float32): MVS_F32}
 CODE_DTYPES = {v: k for k, v in DTYPE_CODES.items()}
@@ -260,6 +264,20 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.POINTER(mvs_view_t), C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32,
          C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double)],
+    ),
+    "mvs_knn": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+         C.POINTER(C.c_double)],
+    ),
+    "mvs_marker_descriptors": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_void_p, C.c_int32],
+    ),
+    "mvs_marker_score": (
+        C.c_int,
+        [C.c_int, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.c_int32, C.c_double,
+         C.POINTER(C.c_int32), C.POINTER(C.c_double)],
     ),
 }
 

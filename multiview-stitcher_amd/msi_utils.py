@@ -21,6 +21,8 @@ class MultiscaleSpatialImage:
     def __init__(self, sims, transforms=None):
         self.scales = {f"scale{i}": s for i, s in enumerate(sims)}
         self.transforms = transforms if transforms is not None else {}
+        # named point sets (set_point_set), shared by all scales: physical coordinates do not depend on the level
+        self.point_sets = dict(sims[0].attrs.get("point_sets", {})) if sims else {}
 
     def keys(self):
         return list(self.scales.keys())
@@ -102,7 +104,29 @@ def get_sim_from_msim(msim, scale="scale0"):
     """msi_utils.get_sim_from_msim (msi_utils.py:351-370): the sim at ``scale`` with all transforms."""
     sim = msim[scale].copy()
     sim.attrs["transforms"] = dict(msim.transforms)
+    if getattr(msim, "point_sets", None):
+        sim.attrs["point_sets"] = dict(msim.point_sets)
     return sim
+
+
+def set_point_set(msim, points, points_key="beads"):
+    """msi_utils.set_point_set (msi_utils.py:527-563): attach the (n, ndim) float64
+    array ``points`` -- physical coordinates in the image's own frame, columns in the order of the spatial dims, e.g. the
+    result of ``detection.detect_beads`` -- to the multiscale image under ``points_key``.  ``get_sim_from_msim`` hands the
+    point sets on to the image of every scale."""
+    si_utils.set_point_set(msim["scale0"], points, points_key)
+    stored = msim["scale0"].attrs["point_sets"][points_key]
+    msim.point_sets = dict(getattr(msim, "point_sets", {}), **{points_key: stored})
+    for s in msim.scales.values():
+        s.attrs["point_sets"] = dict(s.attrs.get("point_sets", {}), **{points_key: stored})
+    return msim
+
+
+def get_point_set(msim, points_key="beads"):
+    """msi_utils.get_point_set (msi_utils.py:566-593): the (n, ndim) point set stored under ``points_key`` (KeyError when there is none)."""
+    if points_key not in getattr(msim, "point_sets", {}):
+        raise KeyError(f"Point set {points_key!r} not found in msim.")
+    return msim.point_sets[points_key]
 
 
 def get_res_level_from_spacing(msim, spacing):

@@ -185,6 +185,53 @@ def affine_registration(fixed_data, moving_data, transform_type="rigid", shrink_
                                            initial_affine, fit_intensity, device, return_debug, metric, n_bins)
 
 
+def registration_marker_based(fixed_points, moving_points, transform_type="rigid", num_neighbors=3, redundancy=1, descriptor_ratio=3.0,
+                              descriptor_distance_threshold=None, descriptor_threshold_scale=1.0, ransac_max_error=5.0,
+                              ransac_min_inlier_ratio=0.1, ransac_min_inlier_factor=3.0, ransac_num_iterations=1000, icp=False,
+                              icp_max_error=None, icp_num_iterations=50, icp_tolerance=1e-6, random_state=0, fail_on_error=True, device=0):
+    """Marker-based registration of two point sets (registration.registration_marker_based, registration.py:1165-1379; after
+    BigStitcher's RGLDM bead matching): local geometric descriptors of ``fixed_points`` and ``moving_points`` ((n, ndim) arrays,
+    ndim 2 or 3) are matched, inconsistent matches are removed by RANSAC, and the result is ``{"affine_matrix": fixed ->
+    moving, "quality"}``.  A ``pairwise_reg_func`` for ``register``: it takes the ``fixed_points`` / ``moving_points`` that
+    ``register_pair_of_msims`` reads from the views' point sets (``msi_utils.set_point_set``, e.g. what
+    ``detection.detect_beads`` returns).
+
+    Parameters and defaults are the reference's.  ``transform_type``: "translation", "rigid" or "affine".  Every point gets
+    one descriptor per ``num_neighbors``-subset of its ``num_neighbors + redundancy`` nearest points: the sorted distances
+    among the point and the subset.  A fixed descriptor proposes a correspondence when its nearest moving descriptor is closer
+    than ``descriptor_distance_threshold`` (None: the median nearest-neighbour distance of the points times
+    sqrt(descriptor length) times ``descriptor_threshold_scale``) and ``descriptor_ratio`` times closer than the nearest
+    descriptor of any other moving point.  RANSAC fits minimal samples of the proposals (all combinations when there are at
+    most ``ransac_num_iterations``, else that many draws from ``np.random.default_rng(random_state)``), counts the proposals
+    within ``ransac_max_error``, refits on the best model's inliers and fails below ``ransac_min_inlier_ratio`` or
+    ``round(minimal sample size * ransac_min_inlier_factor)`` inliers.  ``icp``: nearest-neighbour ICP refinement within
+    ``icp_max_error`` (None: ``ransac_max_error``), at most ``icp_num_iterations`` iterations, until the matrix changes by
+    at most ``icp_tolerance`` (Frobenius).  ``fail_on_error``: raise ValueError on failure, else warn and return identity with
+    ``quality = nan``.
+
+    The nearest-neighbour queries (mvs_knn), the descriptor vectors (mvs_marker_descriptors) and the scoring of all RANSAC
+    hypotheses (mvs_marker_score) run on ``device``; arguments are validated before the device is touched.  The kernels
+    take ``num_neighbors <= 5`` and at most 15 descriptors per point; beyond that NotImplementedError names the parameter.
+    ``rigid`` is Umeyama's fit without scale, ``affine`` the least-squares estimator of ``param_resolution``."""
+    from . import _marker_reg
+
+    return _marker_reg.registration_marker_based(
+        fixed_points, moving_points, fail_on_error=fail_on_error, transform_type=transform_type, num_neighbors=num_neighbors,
+        redundancy=redundancy, descriptor_ratio=descriptor_ratio, descriptor_distance_threshold=descriptor_distance_threshold,
+        descriptor_threshold_scale=descriptor_threshold_scale, ransac_max_error=ransac_max_error,
+        ransac_min_inlier_ratio=ransac_min_inlier_ratio, ransac_min_inlier_factor=ransac_min_inlier_factor,
+        ransac_num_iterations=ransac_num_iterations, icp=icp, icp_max_error=icp_max_error, icp_num_iterations=icp_num_iterations,
+        icp_tolerance=icp_tolerance, random_state=random_state, device=device)
+
+
+def _marker_registration_details(fixed_points, moving_points, **kwargs):
+    """``registration_marker_based`` with its intermediate results (tests, tools): the result dict plus ``candidate_pairs``,
+    ``inlier_mask`` and ``descriptor_distance_threshold``; raises ValueError on every failure."""
+    from . import _marker_reg
+
+    return _marker_reg.register_details(fixed_points, moving_points, **kwargs)
+
+
 def get_optimal_registration_binning(sim1, sim2, max_total_pixels_per_stack=400**3, overlap_tolerance=None):
     """registration.get_optimal_registration_binning (registration.py:114-191): +1 steps (not doublings) on
     the axis with the smallest current spacing (z alone, or x and y together) until the larger of the two
@@ -989,16 +1036,56 @@ def _select_registration_level(msim1, msim2, registration_binning, reg_res_level
     return level(0, scale_key), level(1, scale_key), remaining
 
 
+def _has_keyword(func, keyword):
+    """misc_utils.has_keyword: does ``func`` accept ``keyword``?"""
+    import inspect
+
+    try:
+        return keyword in inspect.signature(func).parameters
+    except (TypeError, ValueError):
+        return False
+
+
+def _is_point_aware(pairwise_reg_func):
+    """registration.py:1814-1839: a function that takes ``fixed_points`` and ``moving_points`` gets the views' point sets; one
+    that takes only one of the two is refused."""
+    has = [_has_keyword(pairwise_reg_func, k) for k in ("fixed_points", "moving_points")]
+    if any(has) and not all(has):
+        raise ValueError("Point-aware pairwise registration functions must accept both 'fixed_points' and 'moving_points'.")
+    return all(has)
+
+
+def _points_for_registration(sim, points_key, sdims, affine, window=None):
+    """registration.py:568-592, 1862-1887: the view's point set ``points_key`` -- restricted to the closed ``window``
+    ({dim: slice}) when there is one -- without rows that hold a non-finite coordinate, mapped by the view's ``affine``."""
+    from . import spatial_image_utils as si_utils
+    from .transformation import transform_pts
+
+    points = np.asarray(si_utils.get_point_set(sim, points_key), dtype=np.float64)
+    if window is not None:
+        points = si_utils.point_set_sel_coords(points, sdims, window)
+    points = points[np.all(np.isfinite(points), axis=1)]
+    return points if points.size == 0 else transform_pts(points, affine)
+
+
 def register_pair_of_msims(msim1, msim2, transform_key, registration_binning=None, overlap_tolerance=None,
                            pairwise_reg_func=phase_correlation_registration, pairwise_reg_func_kwargs=None, device=0,
-                           _bin_cache=None, reg_res_level=None, overlap_bbox="closed_form"):
+                           _bin_cache=None, reg_res_level=None, overlap_bbox="closed_form", points_key="beads", prefilter_markers=False):
     """registration.register_pair_of_msims (registration.py:1547-2058) for pixel-space registration functions
     (the form the reference's phase correlation has): returns {"transform", "quality", "bbox"}.  ``reg_res_level`` /
-    ``registration_binning`` pick the pyramid level of multiscale inputs as the reference does (registration.py:1639-1717)."""
+    ``registration_binning`` pick the pyramid level of multiscale inputs as the reference does (registration.py:1639-1717).
+
+    A ``pairwise_reg_func`` that accepts ``fixed_points`` and ``moving_points`` (``registration_marker_based``) takes the
+    reference's point branch instead (registration.py:1839-1924, 2029-2030): it is called with the point sets ``points_key`` of
+    the two views, each mapped by its view's affine at ``transform_key``, and what it returns is the physical transform.
+    ``prefilter_markers`` first restricts every view's points to its overlap window (the closed interval of the crop
+    selection: lower - 1e-6 - spacing ... upper + 1e-6 + spacing per dim, in the view's own frame).  Image crops are passed
+    only to a function that also takes ``fixed_data`` / ``moving_data``."""
     from . import msi_utils
     from . import spatial_image_utils as si_utils
 
     pairwise_reg_func_kwargs = dict(pairwise_reg_func_kwargs or {})
+    point_aware = _is_point_aware(pairwise_reg_func)
     sim1, sim2, registration_binning = _select_registration_level(msim1, msim2, registration_binning, reg_res_level)
     for s_ in (sim1, sim2):
         if is_device_array(s_.data):
@@ -1054,12 +1141,33 @@ def register_pair_of_msims(msim1, msim2, transform_key, registration_binning=Non
                 ov, closed_form = ov_ref, False
     lowers, uppers = ov["lowers"], ov["uppers"]
     tol = 1e-6
-    reg_sims_b = [
-        si_utils.sim_sel_coords(
-            sim, {d: slice(lowers[i][k] - tol - spacings[i][d], uppers[i][k] + tol + spacings[i][d]) for k, d in enumerate(sdims)}
-        )
-        for i, sim in enumerate(reg_sims_b)
-    ]
+    windows = [{d: slice(lowers[i][k] - tol - spacings[i][d], uppers[i][k] + tol + spacings[i][d]) for k, d in enumerate(sdims)}
+               for i in range(2)]
+    if point_aware:
+        # registration.py:1839-1924: the function works in the space of transform_key
+        affines = [param_utils.select_time(si_utils.get_affine_from_sim(s_, transform_key), 0) for s_ in (sim1, sim2)]
+        kw = dict(pairwise_reg_func_kwargs)
+        for name, s_, a_, w_ in zip(("fixed", "moving"), (sim1, sim2), affines, windows):
+            kw[f"{name}_points"] = _points_for_registration(s_, points_key, sdims, a_, w_ if prefilter_markers else None)
+        takes_data = [_has_keyword(pairwise_reg_func, k) for k in ("fixed_data", "moving_data")]
+        if any(takes_data) and not all(takes_data):
+            raise ValueError("Image-aware pairwise registration functions must accept both 'fixed_data' and 'moving_data'.")
+        crops = [si_utils.sim_sel_coords(s_, w_) for s_, w_ in zip(reg_sims_b, windows)] if all(takes_data) or any(
+            _has_keyword(pairwise_reg_func, f"{n}_{q}") for n in ("fixed", "moving") for q in ("origin", "spacing")) else None
+        for name, k in (("fixed", 0), ("moving", 1)):
+            if _has_keyword(pairwise_reg_func, f"{name}_origin"):
+                kw[f"{name}_origin"] = si_utils.get_origin_from_sim(crops[k])
+            if _has_keyword(pairwise_reg_func, f"{name}_spacing"):
+                kw[f"{name}_spacing"] = si_utils.get_spacing_from_sim(crops[k])
+        if _has_keyword(pairwise_reg_func, "initial_affine"):
+            kw["initial_affine"] = np.matmul(np.linalg.inv(affines[1]), affines[0])
+        res = dispatch_pairwise_reg_func(pairwise_reg_func, fixed_data=crops[0].data if all(takes_data) else None,
+                                         moving_data=crops[1].data if all(takes_data) else None, skip_constant_check=True, device=device, **kw)
+        ovp = _get_overlap_bboxes(sim1, sim2, transform_key, transform_key, overlap_tolerance, closed_form=closed_form)
+        return {"transform": np.asarray(res["affine_matrix"], dtype=np.float64),
+                "quality": float(res["quality"]) if res["quality"] is not None else np.nan,
+                "bbox": np.array([ovp["lowers"][0], ovp["uppers"][0]])}
+    reg_sims_b = [si_utils.sim_sel_coords(sim, windows[i]) for i, sim in enumerate(reg_sims_b)]
     fixed, moving = sims_to_intrinsic_coord_system(reg_sims_b[0], reg_sims_b[1], transform_key, (lowers, uppers), device)
     res = dispatch_pairwise_reg_func(pairwise_reg_func, fixed_data=fixed, moving_data=moving, device=device,
                                      **pairwise_reg_func_kwargs)
@@ -1151,9 +1259,10 @@ def _prebin_views(sims, registration_binning, device, cache):
 def compute_pairwise_registrations(msims, edges, transform_key, registration_binning=None, overlap_tolerance=0.0,
                                    pairwise_reg_func=phase_correlation_registration, pairwise_reg_func_kwargs=None,
                                    pairwise_executor=None, device=0, host_threads=None, _bin_cache=None, reg_res_level=None,
-                                   overlap_bbox="closed_form"):
+                                   overlap_bbox="closed_form", points_key="beads", prefilter_markers=False):
     """registration.compute_pairwise_registrations (registration.py:2622-2714): either hand all edges to a
-    user ``pairwise_executor(msims, edges, register_kwargs)`` or loop over them on one device."""
+    user ``pairwise_executor(msims, edges, register_kwargs)`` or loop over them on one device.  ``points_key`` /
+    ``prefilter_markers`` go to ``register_pair_of_msims`` (point-aware registration functions)."""
     register_kwargs = dict(transform_key=transform_key, registration_binning=registration_binning,
                            overlap_tolerance=overlap_tolerance, pairwise_reg_func=pairwise_reg_func,
                            pairwise_reg_func_kwargs=pairwise_reg_func_kwargs)
@@ -1161,6 +1270,10 @@ def compute_pairwise_registrations(msims, edges, transform_key, registration_bin
         register_kwargs["reg_res_level"] = reg_res_level
     if overlap_bbox != "closed_form":
         register_kwargs["overlap_bbox"] = overlap_bbox
+    if points_key != "beads":
+        register_kwargs["points_key"] = points_key
+    if prefilter_markers:
+        register_kwargs["prefilter_markers"] = True
     if pairwise_executor is not None:
         results = pairwise_executor(msims, list(edges), register_kwargs)
         if len(results) != len(edges):
@@ -1346,12 +1459,16 @@ def register(msims, transform_key=None, reg_channel_index=None, reg_channel=None
              pre_reg_pruning_method_kwargs=None,
              post_registration_do_quality_filter=False, post_registration_quality_threshold=0.2, pairs=None,
              n_parallel_pairwise_regs=None, pairwise_executor=None, return_dict=False, device=0, reg_res_level=None,
-             overlap_bbox="closed_form"):
+             overlap_bbox="closed_form", points_key="beads", prefilter_markers=False):
     """Register views to a common coordinate system (registration.register, registration.py:2227-2620).
 
     ``reg_res_level`` / ``registration_binning`` select the pyramid level of multiscale inputs per pair exactly as the
     reference does (registration.py:1639-1717, 2236, 2525): a level alone, a level plus the remaining binning, or -- by
     default -- the lowest level that divides the (optimal) binning.  The overlap graph is always built on scale0.
+
+    ``points_key`` / ``prefilter_markers``: for a ``pairwise_reg_func`` that takes ``fixed_points`` / ``moving_points``
+    (``registration_marker_based``): which point set of the views it gets (``msi_utils.set_point_set``) and whether the points
+    are first restricted to the pair's overlap (see ``register_pair_of_msims``).
 
     Flow as in the reference: (1) overlap graph, (2) pairwise registrations of the selected edges,
     (3) groupwise resolution, (4) write ``new_transform_key`` (rebased on ``transform_key``).
@@ -1466,6 +1583,7 @@ def register(msims, transform_key=None, reg_channel_index=None, reg_channel=None
                 pairwise_reg_func_kwargs, pairwise_executor, device,
                 host_threads=n_parallel_pairwise_regs,
                 _bin_cache=bin_cache, reg_res_level=reg_res_level, overlap_bbox=overlap_bbox,
+                points_key=points_key, prefilter_markers=prefilter_markers,
             )
         finally:
             if prebin is not None:

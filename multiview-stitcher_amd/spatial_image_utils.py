@@ -281,9 +281,59 @@ def get_center_of_sim(sim, transform_key=None):
     return center
 
 
+def set_point_set(sim, points, points_key="beads"):
+    """spatial_image_utils.set_point_set (spatial_image_utils.py:1083-1123): attach a named point set to ``sim``
+    (``sim.attrs["point_sets"][points_key]``).  A point set is an (n, ndim) float64 array whose columns follow the spatial dims
+    of the image, in the image's own physical frame (no transform applied) -- what ``detection.detect_beads`` returns."""
+    ndim = get_ndim_from_sim(sim)
+    points = np.array(points, dtype=np.float64, copy=True)
+    if points.size == 0:
+        points = points.reshape(0, ndim)
+    if points.ndim != 2 or points.shape[1] != ndim:
+        raise ValueError(f"A point set must have shape (n_points, {ndim}) for this image, got {points.shape}.")
+    # (a new dict: shallow copies of the image share the old one)
+    point_sets = dict(sim.attrs.get("point_sets", {}))
+    point_sets[points_key] = points
+    sim.attrs["point_sets"] = point_sets
+    return sim
+
+
+def get_point_set(sim, points_key="beads"):
+    """spatial_image_utils.get_point_set (spatial_image_utils.py:1126-1148): the (n, ndim) array stored under ``points_key``."""
+    if "point_sets" not in sim.attrs or points_key not in sim.attrs["point_sets"]:
+        raise KeyError(f"Point set {points_key!r} not found in sim.")
+    return sim.attrs["point_sets"][points_key]
+
+
+def point_set_sel_coords(points, sdims, sel_dict):
+    """spatial_image_utils.point_set_sel_coords (spatial_image_utils.py:1151-1231) for (n, ndim) arrays: the points inside
+    the CLOSED interval of every spatial selector (a slice: its start and stop; coordinate values: their minimum and maximum;
+    no values: no point)."""
+    points = np.asarray(points, dtype=np.float64)
+    mask = np.ones(len(points), dtype=bool)
+    for col, dim in enumerate(sdims):
+        if dim not in sel_dict:
+            continue
+        sel = sel_dict[dim]
+        if isinstance(sel, slice):
+            lower = -np.inf if sel.start is None else float(sel.start)
+            upper = np.inf if sel.stop is None else float(sel.stop)
+        else:
+            values = np.atleast_1d(np.asarray(sel, dtype=float))
+            if values.size == 0:
+                mask[:] = False
+                continue
+            lower, upper = float(values.min()), float(values.max())
+        mask &= (points[:, col] >= lower) & (points[:, col] <= upper)
+    return points[mask]
+
+
 def sim_sel_coords(sim, sel_dict):
-    """spatial_image_utils.sim_sel_coords (spatial_image_utils.py:1278-1300)."""
+    """spatial_image_utils.sim_sel_coords (spatial_image_utils.py:1278-1300); point sets follow the spatial selection."""
     ssim = sim.sel(sel_dict)
+    if "point_sets" in sim.attrs:
+        sdims = get_spatial_dims_from_sim(sim)
+        ssim.attrs["point_sets"] = {k: point_set_sel_coords(v, sdims, sel_dict) for k, v in sim.attrs["point_sets"].items()}
     if "t" in sel_dict and not isinstance(sel_dict["t"], slice):
         it = int(np.nonzero(sim.coords["t"] == sel_dict["t"])[0][0])
         ssim.attrs["transforms"] = {
