@@ -233,12 +233,9 @@ def bin_mean(data, bins, device=0, wait=True, out=None):
     return out
 
 
-def affine_normal_equations(fixed, moving, A, t, gain=1.0, bias=0.0, device=0):
-    """Normal equations of one Gauss-Newton step of the intensity registration (mvs_affine_normal_eq).  ``fixed`` / ``moving``:
-    same-shape float32 crops (NaN = outside), both numpy or both contiguous DeviceArrays; ``(A, t)``: the centred pose, fixed
-    voxel x samples moving at ``c + t + A (x - c)``.  Returns (H (P, P), b (P,), sum r^2, n valid, (sum v, sum F, sum vF,
-    sum v^2, sum F^2)) with P = ndim (ndim + 1) and the parameters ordered as the rows of ``[A | t]``."""
-    lib = _lib.init(device)
+def _pose_geometry(fixed, moving, A, t):
+    """The arguments the affine entry points share -- crop pointers, mem, ndim, shape, the pose ``(A, t)`` embedded into 3 x 3 / 3
+    -- and the objects that keep them alive during the call."""
     shape = tuple(int(s) for s in fixed.shape)
     if tuple(moving.shape) != shape:
         raise ValueError("crops must have the same shape")
@@ -251,10 +248,20 @@ def affine_normal_equations(fixed, moving, A, t, gain=1.0, bias=0.0, device=0):
     A3[3 - ndim:, 3 - ndim:] = np.asarray(A, dtype=np.float64).reshape(ndim, ndim)
     t3 = np.zeros(3)
     t3[3 - ndim:] = np.asarray(t, dtype=np.float64).reshape(ndim)
-    out = np.empty(_lib.MVS_AFFINE_NEQ_LEN, dtype=np.float64)
     dp = C.POINTER(C.c_double)
-    rc = lib.mvs_affine_normal_eq(device, p0, p1, m0, ndim, _lib.i64x3(shape3(shape)), A3.ctypes.data_as(dp), t3.ctypes.data_as(dp),
-                                  float(gain), float(bias), out.ctypes.data_as(dp))
+    return (p0, p1, m0, ndim, _lib.i64x3(shape3(shape)), A3.ctypes.data_as(dp), t3.ctypes.data_as(dp)), (k0, k1, A3, t3)
+
+
+def affine_normal_equations(fixed, moving, A, t, gain=1.0, bias=0.0, device=0):
+    """Normal equations of one Gauss-Newton step of the intensity registration (mvs_affine_normal_eq).  ``fixed`` / ``moving``:
+    same-shape float32 crops (NaN = outside), both numpy or both contiguous DeviceArrays; ``(A, t)``: the centred pose, fixed
+    voxel x samples moving at ``c + t + A (x - c)``.  Returns (H (P, P), b (P,), sum r^2, n valid, (sum v, sum F, sum vF,
+    sum v^2, sum F^2)) with P = ndim (ndim + 1) and the parameters ordered as the rows of ``[A | t]``."""
+    lib = _lib.init(device)
+    geom, keep = _pose_geometry(fixed, moving, A, t)
+    ndim = geom[3]
+    out = np.empty(_lib.MVS_AFFINE_NEQ_LEN, dtype=np.float64)
+    rc = lib.mvs_affine_normal_eq(device, *geom, float(gain), float(bias), out.ctypes.data_as(C.POINTER(C.c_double)))
     _lib.check(rc, device, "mvs_affine_normal_eq")
     P = ndim * (ndim + 1)
     H = out[:P * P].reshape(P, P).copy()
@@ -273,29 +280,12 @@ def finite_range(a, device=0):
     return float(mn.value), float(mx.value), int(nv.value)
 
 
-def _mi_geometry(fixed, moving, A, t):
-    shape = tuple(int(s) for s in fixed.shape)
-    if tuple(moving.shape) != shape:
-        raise ValueError("crops must have the same shape")
-    ndim = len(shape)
-    p0, m0, k0 = _ptr_mem(fixed)
-    p1, m1, k1 = _ptr_mem(moving)
-    if m0 != m1:
-        raise TypeError("both crops must live on the same side (host or device)")
-    A3 = np.eye(3)
-    A3[3 - ndim:, 3 - ndim:] = np.asarray(A, dtype=np.float64).reshape(ndim, ndim)
-    t3 = np.zeros(3)
-    t3[3 - ndim:] = np.asarray(t, dtype=np.float64).reshape(ndim)
-    dp = C.POINTER(C.c_double)
-    return (p0, p1, m0, ndim, _lib.i64x3(shape3(shape)), A3.ctypes.data_as(dp), t3.ctypes.data_as(dp)), (k0, k1, A3, t3)
-
-
 def affine_joint_hist(fixed, moving, A, t, n_bins, ranges, device=0):
     """Joint histogram of the Mattes metric over the warped crop pair (mvs_affine_joint_hist).  Crops and pose as
     ``affine_normal_equations``; ``ranges`` = (f_lo, f_scale, m_lo, m_scale).  Returns (hist (B, B) int64: rows = fixed bin,
     columns = moving bin, in units of 2^-20 sample; n valid)."""
     lib = _lib.init(device)
-    geom, keep = _mi_geometry(fixed, moving, A, t)
+    geom, keep = _pose_geometry(fixed, moving, A, t)
     hist = np.empty((int(n_bins), int(n_bins)), dtype=np.int64)
     n = C.c_int64()
     rc = lib.mvs_affine_joint_hist(device, *geom, int(n_bins), *[float(v) for v in ranges], hist.ctypes.data_as(C.POINTER(C.c_int64)),
@@ -308,7 +298,7 @@ def affine_mi_gradient(fixed, moving, A, t, n_bins, ranges, table, device=0):
     """Gradient sums of the Mattes metric (mvs_affine_mi_gradient); ``table``: (B, B) L[a][b], passed as float32.  Returns
     (sums (P,) in the order of the rows of ``[A | t]``, n valid); d MI / d theta = (m_scale / n) * sums."""
     lib = _lib.init(device)
-    geom, keep = _mi_geometry(fixed, moving, A, t)
+    geom, keep = _pose_geometry(fixed, moving, A, t)
     tab = np.ascontiguousarray(table, dtype=np.float32)
     if tab.shape != (int(n_bins), int(n_bins)):
         raise ValueError("table must be n_bins x n_bins")

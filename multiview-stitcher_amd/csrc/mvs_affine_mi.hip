@@ -3,8 +3,8 @@
 // (mvs_finite_range).  Contracts: include/mvs_hip.h.  Per-sample arithmetic: mvs_affine_reg_dev.h (warp, validity) and
 // mvs_affine_mi_dev.h (bins, windows, weights).
 //
-// Both walks have the geometry of affine_neq_kernel (mvs_affine_reg.hip): a block is 4 waves over 64 consecutive x columns, a
-// thread keeps its x (and the block its z) and walks MI_RUN rows.
+// Both kernels take the walk of mvs_affine_walk_dev.h, shared with affine_neq_kernel (mvs_affine_reg.hip): a block is 4 waves
+// over 64 consecutive x columns, a thread keeps its x (and the block its z) and walks mvs_aw::RUN rows.
 //
 // Histogram.  The weights are integers (2^20 per sample, spread over four moving bins), so a sum is the same in every order
 // and atomics keep the result bit-reproducible.  A block adds into LDS copies of the B x B table with 64-bit LDS atomics and
@@ -18,103 +18,35 @@
 #include <algorithm>
 
 #include "mvs_affine_mi_dev.h"
-#include "mvs_affine_reg_dev.h"
-#include "mvs_internal.h"
-
-int mvs_stage_float_volume(MvsContext* c, const float* src, int32_t mem, long long n, int slot, float** dptr);   // mvs_reg.hip
+#include "mvs_affine_walk.h"
 
 namespace {
 
-constexpr int MI_WAVES = 4;      // waves of a block: wave w takes rows y0 + w, y0 + w + 4, ...
-constexpr int MI_RUN = 32;       // rows per thread: the length of a float32 run sum
+using mvs_aw::WAVES;
+using mvs_aw::wave_sum;
 
-struct MiParams {
-    const float* fixed;
-    const float* moving;
-    long long n[3];      // z, y, x (z = 1 in 2D)
-    double A[9];         // 3x3, row-major (z, y, x); 2D uses the lower right 2x2
-    double o[3];         // c + t
-    double c[3];
+struct MiParams : mvs_aw::Walk {
     float f_lo, f_scale, m_lo, m_scale;
     int B;               // bins per axis
     int copies, stride;  // histogram only: LDS copies and the distance between them in entries
-    int nxb, nyc;        // blocks along x and y
 };
-
-// The samples of one thread's run: f(fixed value, moving value, gradient, y - c_y as float) for every valid one.
-template <int ND, typename F>
-__device__ __forceinline__ void walk_run(const MiParams& P, long long z, int yc, int wave, long long x, double dzd, double dxd, F&& f) {
-    const long long ny = P.n[1], nx = P.n[2];
-    if (x >= nx) return;
-    // the products of the coordinate that do not change along the run (each rounds on its own, as in coord2 / coord3)
-    double az[3], ax[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        az[k] = P.A[k * 3 + 0] * dzd;
-        ax[k] = P.A[k * 3 + 2] * dxd;
-    }
-    const long long y0 = (long long)yc * (MI_WAVES * MI_RUN) + wave;
-    const float* __restrict__ frow = P.fixed + (z * ny + y0) * nx + x;
-    for (int i = 0; i < MI_RUN; ++i, frow += MI_WAVES * nx) {
-        const long long y = y0 + (long long)i * MI_WAVES;
-        if (y >= ny) break;
-        const float fv = *frow;
-        if (!mvs_ar::finite_f(fv)) continue;
-        const double dyd = (double)y - P.c[1];
-        float v, g[ND];
-        if constexpr (ND == 3) {
-            long long iz, iy, ix;
-            float fz, fy, fx;
-            if (!mvs_ar::split(((az[0] + P.A[1] * dyd) + ax[0]) + P.o[0], P.n[0], &iz, &fz)) continue;
-            if (!mvs_ar::split(((az[1] + P.A[4] * dyd) + ax[1]) + P.o[1], ny, &iy, &fy)) continue;
-            if (!mvs_ar::split(((az[2] + P.A[7] * dyd) + ax[2]) + P.o[2], nx, &ix, &fx)) continue;
-            const float* __restrict__ m = P.moving + (iz * ny + iy) * nx + ix;
-            const long long sz = ny * nx;
-            const float taps[8] = {m[0], m[1], m[nx], m[nx + 1], m[sz], m[sz + 1], m[sz + nx], m[sz + nx + 1]};
-            if (!mvs_ar::sample3(taps, fz, fy, fx, &v, g)) continue;
-        } else {
-            long long iy, ix;
-            float fy, fx;
-            if (!mvs_ar::split((P.A[4] * dyd + ax[1]) + P.o[1], ny, &iy, &fy)) continue;
-            if (!mvs_ar::split((P.A[7] * dyd + ax[2]) + P.o[2], nx, &ix, &fx)) continue;
-            const float* __restrict__ m = P.moving + iy * nx + ix;
-            const float taps[4] = {m[0], m[1], m[nx], m[nx + 1]};
-            if (!mvs_ar::sample2(taps, fy, fx, &v, g)) continue;
-        }
-        f(fv, v, g, (float)dyd);
-    }
-}
-
-struct BlockPos {
-    int xb, yc;
-    long long z;
-};
-__device__ __forceinline__ BlockPos block_pos(const MiParams& P) {
-    long long b = blockIdx.x;
-    BlockPos r;
-    r.xb = (int)(b % P.nxb);
-    b /= P.nxb;
-    r.yc = (int)(b % P.nyc);
-    r.z = b / P.nyc;
-    return r;
-}
 
 // hist: B * B entries [a][b], then the valid count; zeroed before the launch
 template <int ND>
-__global__ __launch_bounds__(MI_WAVES * 64) void mi_hist_kernel(MiParams P, unsigned long long* __restrict__ hist) {
+__global__ __launch_bounds__(WAVES * 64) void mi_hist_kernel(MiParams P, unsigned long long* __restrict__ hist) {
     extern __shared__ unsigned long long lds[];      // copies * stride entries
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int B = P.B, nb2 = B * B;
-    for (int i = threadIdx.x; i < P.copies * P.stride; i += MI_WAVES * 64) lds[i] = 0ull;
+    for (int i = threadIdx.x; i < P.copies * P.stride; i += WAVES * 64) lds[i] = 0ull;
     __syncthreads();
 
-    const BlockPos bp = block_pos(P);
+    const mvs_aw::BlockPos bp = mvs_aw::block_pos(P, blockIdx.x);
     const long long x = (long long)bp.xb * 64 + lane;
     const double dxd = (double)x - P.c[2];
     const double dzd = ND == 3 ? (double)bp.z - P.c[0] : 0.0;
     unsigned long long* mine = lds + (lane & (P.copies - 1)) * P.stride;
     int n = 0;
-    walk_run<ND>(P, bp.z, bp.yc, wave, x, dzd, dxd, [&](float fv, float v, const float*, float) {
+    mvs_aw::walk_run<ND>(P, bp.z, bp.yc, wave, x, dzd, dxd, [&](float fv, float v, const float*, float) {
         const int a = mvs_mi::fixed_bin(fv, P.f_lo, P.f_scale, B);
         long long q[4];
         const int b0 = mvs_mi::hist_weights(mvs_mi::moving_coord(v, P.m_lo, P.m_scale, B), q);
@@ -126,7 +58,7 @@ __global__ __launch_bounds__(MI_WAVES * 64) void mi_hist_kernel(MiParams P, unsi
     });
     __syncthreads();
 
-    for (int i = threadIdx.x; i < nb2; i += MI_WAVES * 64) {
+    for (int i = threadIdx.x; i < nb2; i += WAVES * 64) {
         unsigned long long s = 0ull;
         for (int cpy = 0; cpy < P.copies; ++cpy) s += lds[cpy * P.stride + i];
         if (s != 0ull) atomicAdd(&hist[i], s);
@@ -136,12 +68,6 @@ __global__ __launch_bounds__(MI_WAVES * 64) void mi_hist_kernel(MiParams P, unsi
     if (lane == 0 && n != 0) atomicAdd(&hist[nb2], (unsigned long long)n);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-
 template <int ND>
 struct GradLayout {
     static constexpr int NV = ND * 3 + 1;             // values a thread hands to the block reduction
@@ -149,23 +75,23 @@ struct GradLayout {
 };
 
 template <int ND>
-__global__ __launch_bounds__(MI_WAVES * 64) void mi_grad_kernel(MiParams P, const float* __restrict__ table, double* __restrict__ partials) {
+__global__ __launch_bounds__(WAVES * 64) void mi_grad_kernel(MiParams P, const float* __restrict__ table, double* __restrict__ partials) {
     using L = GradLayout<ND>;
     __shared__ float tab[mvs_mi::MAX_BINS * mvs_mi::MAX_BINS];
-    __shared__ double red[MI_WAVES][L::NV];
+    __shared__ double red[WAVES][L::NV];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int B = P.B;
-    for (int i = threadIdx.x; i < B * B; i += MI_WAVES * 64) tab[i] = table[i];
+    for (int i = threadIdx.x; i < B * B; i += WAVES * 64) tab[i] = table[i];
     __syncthreads();
 
-    const BlockPos bp = block_pos(P);
+    const mvs_aw::BlockPos bp = mvs_aw::block_pos(P, blockIdx.x);
     const long long x = (long long)bp.xb * 64 + lane;
     const double dxd = (double)x - P.c[2];
     const double dzd = ND == 3 ? (double)bp.z - P.c[0] : 0.0;
     float R0[ND], R1[ND], s_n = 0.f;
 #pragma unroll
     for (int k = 0; k < ND; ++k) R0[k] = R1[k] = 0.f;
-    walk_run<ND>(P, bp.z, bp.yc, wave, x, dzd, dxd, [&](float fv, float v, const float* g, float dy) {
+    mvs_aw::walk_run<ND>(P, bp.z, bp.yc, wave, x, dzd, dxd, [&](float fv, float v, const float* g, float dy) {
         const int a = mvs_mi::fixed_bin(fv, P.f_lo, P.f_scale, B);
         const float w = mvs_mi::gradient_weight(mvs_mi::moving_coord(v, P.m_lo, P.m_scale, B), tab + a * B);
 #pragma unroll
@@ -208,22 +134,6 @@ __global__ __launch_bounds__(MI_WAVES * 64) void mi_grad_kernel(MiParams P, cons
     }
 }
 
-// out[j] = sum over the blocks of partials[b][j]: thread t takes b = t, t + 256, ... in order, then a fixed tree in LDS
-// (the scheme of affine_neq_sum_kernel)
-__global__ __launch_bounds__(256) void mi_grad_sum_kernel(const double* __restrict__ partials, long long nblocks, int nout, double* __restrict__ out) {
-    __shared__ double s[256];
-    const int j = blockIdx.x;
-    double acc = 0.0;
-    for (long long b = threadIdx.x; b < nblocks; b += 256) acc += partials[(size_t)b * nout + j];
-    s[threadIdx.x] = acc;
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {
-        if ((int)threadIdx.x < half) s[threadIdx.x] += s[threadIdx.x + half];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[j] = s[0];
-}
-
 // minimum, maximum and count of the finite values, per block: part[b] = (min, max), cnt[b]
 __global__ __launch_bounds__(256) void finite_range_kernel(const float* __restrict__ a, long long n, float2* __restrict__ part,
                                                            long long* __restrict__ cnt) {
@@ -262,16 +172,15 @@ __global__ __launch_bounds__(256) void finite_range_kernel(const float* __restri
     }
 }
 
-// Argument checks and the launch geometry the two metric entries share.  *c is the locked context's; the caller holds its lock.
-int mi_setup(MvsContext* c, const char* who, const float* fixed, const float* moving, int32_t mem, int32_t ndim, const int64_t shape[3],
-             const double matrix[9], const double offset[3], int32_t n_bins, float f_lo, float f_scale, float m_lo, float m_scale, MiParams* P,
-             long long* nblocks) {
-    for (int k = 0; k < 3; ++k) {
-        P->n[k] = shape[k];
-        P->c[k] = (double)(shape[k] - 1) / 2.0;
-        P->o[k] = P->c[k] + offset[k];
-    }
-    for (int k = 0; k < 9; ++k) P->A[k] = matrix[k];
+// The checks and the parameter block the two metric entries share.  mi_setup: *c is the locked context's.
+int mi_check_args(MvsContext* c0, const char* who, const void* fixed, const void* moving, int32_t mem, int32_t ndim, const int64_t* shape,
+                  const double* matrix, const double* offset, int32_t n_bins, const void* out0, const void* out1) {
+    if (n_bins < mvs_mi::MIN_BINS || n_bins > mvs_mi::MAX_BINS) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: n_bins must be in 8..64", who);
+    return affine_check_args(c0, who, fixed, moving, mem, ndim, shape, matrix, offset, out0, out1);
+}
+
+int mi_setup(MvsContext* c, const char* who, const float* fixed, const float* moving, int32_t mem, const int64_t shape[3], const double matrix[9],
+             const double offset[3], int32_t n_bins, float f_lo, float f_scale, float m_lo, float m_scale, MiParams* P, long long* nblocks) {
     P->f_lo = f_lo;
     P->f_scale = f_scale;
     P->m_lo = m_lo;
@@ -279,33 +188,7 @@ int mi_setup(MvsContext* c, const char* who, const float* fixed, const float* mo
     P->B = n_bins;
     P->copies = n_bins <= 16 ? 16 : (n_bins <= 32 ? 4 : 1);
     P->stride = n_bins * n_bins + (P->copies > 1 ? 1 : 0);
-    P->nxb = (int)((shape[2] + 63) / 64);
-    P->nyc = (int)((shape[1] + MI_WAVES * MI_RUN - 1) / (MI_WAVES * MI_RUN));
-    *nblocks = (long long)P->nxb * P->nyc * shape[0];
-    if (*nblocks > 0x7fffffffll) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "%s: crop too large", who);
-    const long long n = (long long)shape[0] * shape[1] * shape[2];
-    float *dF, *dM;
-    int rc = mvs_stage_float_volume(c, fixed, mem, n, 4, &dF);
-    if (rc) return rc;
-    rc = mvs_stage_float_volume(c, moving, mem, n, 5, &dM);
-    if (rc) return rc;
-    P->fixed = dF;
-    P->moving = dM;
-    return MVS_OK;
-}
-
-int mi_check_args(MvsContext* c0, const char* who, const void* fixed, const void* moving, int32_t mem, int32_t ndim, const int64_t* shape,
-                  const double* matrix, const double* offset, int32_t n_bins, const void* out0, const void* out1) {
-    if (ndim != 2 && ndim != 3) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: ndim must be 2 or 3", who);
-    if (!fixed || !moving || !shape || !matrix || !offset || !out0 || !out1) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: NULL argument", who);
-    if (mem != MVS_MEM_HOST && mem != MVS_MEM_DEVICE) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: bad mem", who);
-    if (n_bins < mvs_mi::MIN_BINS || n_bins > mvs_mi::MAX_BINS) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: n_bins must be in 8..64", who);
-    for (int k = 0; k < 3; ++k)
-        if (shape[k] < 1 || (k < 3 - ndim && shape[k] != 1))
-            return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: shape must be positive (and 1 along z in 2D)", who);
-    for (int k = 0; k < 3; ++k)
-        if (shape[k] > (1 << 24)) return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "%s: axis longer than 2^24", who);
-    return MVS_OK;
+    return affine_walk_setup(c, who, fixed, moving, mem, shape, matrix, offset, P, nblocks);
 }
 
 }  // namespace
@@ -323,7 +206,7 @@ extern "C" int mvs_affine_joint_hist(int device, const float* fixed, const float
     MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
     MiParams P;
     long long nblocks;
-    rc = mi_setup(c, who, fixed, moving, mem, ndim, shape, matrix, offset, n_bins, f_lo, f_scale, m_lo, m_scale, &P, &nblocks);
+    rc = mi_setup(c, who, fixed, moving, mem, shape, matrix, offset, n_bins, f_lo, f_scale, m_lo, m_scale, &P, &nblocks);
     if (rc) return rc;
 
     const size_t nent = (size_t)n_bins * n_bins + 1;
@@ -334,8 +217,8 @@ extern "C" int mvs_affine_joint_hist(int device, const float* fixed, const float
     if (rc) return rc;
     MVS_HIP_TRY(c, hipMemsetAsync(dhist, 0, nent * 8, c->stream));
     const size_t lds_bytes = (size_t)P.copies * P.stride * 8;
-    if (ndim == 3) hipLaunchKernelGGL(mi_hist_kernel<3>, dim3((unsigned)nblocks), dim3(MI_WAVES * 64), lds_bytes, c->stream, P, dhist);
-    else hipLaunchKernelGGL(mi_hist_kernel<2>, dim3((unsigned)nblocks), dim3(MI_WAVES * 64), lds_bytes, c->stream, P, dhist);
+    if (ndim == 3) hipLaunchKernelGGL(mi_hist_kernel<3>, dim3((unsigned)nblocks), dim3(WAVES * 64), lds_bytes, c->stream, P, dhist);
+    else hipLaunchKernelGGL(mi_hist_kernel<2>, dim3((unsigned)nblocks), dim3(WAVES * 64), lds_bytes, c->stream, P, dhist);
     MVS_HIP_TRY(c, hipGetLastError());
     MVS_HIP_TRY(c, hipMemcpyAsync(mb_host, dhist, nent * 8, hipMemcpyDeviceToHost, c->stream));
     MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -358,7 +241,7 @@ extern "C" int mvs_affine_mi_gradient(int device, const float* fixed, const floa
     MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
     MiParams P;
     long long nblocks;
-    rc = mi_setup(c, who, fixed, moving, mem, ndim, shape, matrix, offset, n_bins, f_lo, f_scale, m_lo, m_scale, &P, &nblocks);
+    rc = mi_setup(c, who, fixed, moving, mem, shape, matrix, offset, n_bins, f_lo, f_scale, m_lo, m_scale, &P, &nblocks);
     if (rc) return rc;
 
     const int nout = ndim == 3 ? GradLayout<3>::NOUT : GradLayout<2>::NOUT;
@@ -371,10 +254,10 @@ extern "C" int mvs_affine_mi_gradient(int device, const float* fixed, const floa
     rc = mvs_mailbox(c, (size_t)nout * sizeof(double), &mb_host, &mb_dev);
     if (rc) return rc;
     MVS_HIP_TRY(c, hipMemcpyAsync(dtab, table, (size_t)n_bins * n_bins * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (ndim == 3) hipLaunchKernelGGL(mi_grad_kernel<3>, dim3((unsigned)nblocks), dim3(MI_WAVES * 64), 0, c->stream, P, dtab, partials);
-    else hipLaunchKernelGGL(mi_grad_kernel<2>, dim3((unsigned)nblocks), dim3(MI_WAVES * 64), 0, c->stream, P, dtab, partials);
+    if (ndim == 3) hipLaunchKernelGGL(mi_grad_kernel<3>, dim3((unsigned)nblocks), dim3(WAVES * 64), 0, c->stream, P, dtab, partials);
+    else hipLaunchKernelGGL(mi_grad_kernel<2>, dim3((unsigned)nblocks), dim3(WAVES * 64), 0, c->stream, P, dtab, partials);
     MVS_HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(mi_grad_sum_kernel, dim3(nout), dim3(256), 0, c->stream, partials, nblocks, nout, (double*)mb_dev);
+    hipLaunchKernelGGL(mvs_aw::rows_sum_kernel, dim3(nout), dim3(256), 0, c->stream, partials, nblocks, nout, (double*)mb_dev);
     MVS_HIP_TRY(c, hipGetLastError());
     MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < MVS_AFFINE_MI_GRAD_LEN; ++i) out[i] = i < nout ? ((const double*)mb_host)[i] : 0.0;

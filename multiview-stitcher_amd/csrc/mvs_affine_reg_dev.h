@@ -1,7 +1,8 @@
 // mvs_affine_reg_dev.h -- the per-sample arithmetic of the Gauss-Newton intensity registration (mvs_affine_normal_eq).
-// Host/device: the kernel of mvs_affine_reg.hip and tests/native/affine_reg_host_test.cpp compile the same functions, and
-// tests/affine_reg_oracle.py restates them in numpy (float32 mode) operation by operation.  The build uses -ffp-contract=off:
-// every * and + below rounds on its own, in the order written.
+// Host/device: the walk of mvs_affine_walk_dev.h (every kernel of affine_registration) and
+// tests/native/affine_reg_host_test.cpp compile the same functions, and tests/affine_reg_oracle.py restates them in numpy
+// (float32 mode) operation by operation.  The build uses -ffp-contract=off: every * and + below rounds on its own, in the
+// order written.
 //
 // One sample of the fixed grid at voxel x (centre c = (shape - 1) / 2, pose [A | t]):
 //   coordinate  p_k = ((A[k][0] * d_0 + A[k][1] * d_1) + A[k][2] * d_2) + o_k      double; d = x - c, o_k = c_k + t_k

@@ -21,7 +21,6 @@
 #include <cstdlib>
 #include <vector>
 
-int mvs_stage_float_volume(MvsContext* c, const float* src, int32_t mem, long long n, int slot, float** dptr);   // mvs_reg.hip
 int mvs_device_nanminmax(MvsContext* c, const float* d_in, long long n, float* mn, float* mx, long long* nvalid);   // mvs_reg.hip
 
 namespace {

@@ -59,10 +59,11 @@ def _neq_errors(got, want):
 
 @pytest.mark.parametrize("mem", ["host", "device"])
 @pytest.mark.parametrize("ipose", [0, 1], ids=["identity", "affine"])
-@pytest.mark.parametrize("shape", [(40, 48), (5, 6, 7), (21, 37, 44), (3, 4, 130)], ids=str)
+@pytest.mark.parametrize("shape", [(40, 48), (5, 6, 7), (21, 37, 44), (3, 4, 130), (130, 33), (3, 129, 65)], ids=str)
 def test_normal_equations_match_the_oracle(hip_device, shape, ipose, mem):
     """Valid count: exact.  Every sum: within 8x the deviation of the restatement's float32 mode from its float64 mode on the
-    same input (floor 16 eps32) -- the margin covers the kernel's float32 run sums of 32 samples and its summation tree."""
+    same input (floor 16 eps32) -- the margin covers the kernel's float32 run sums of 32 samples and its summation tree.  The last
+    two shapes have two chunks of rows with a partial second one; (3, 129, 65) also a second block of columns with one live lane."""
     from multiview_stitcher_amd import _reg_ops
     from multiview_stitcher_amd.device import DeviceArray
 

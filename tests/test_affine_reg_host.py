@@ -94,6 +94,44 @@ def test_header_samples_equal_the_oracle_float32_mode_bit_for_bit(tmp_path):
             assert np.float64(want).view(np.uint64) == vals[2 * nd + 1:].view(np.uint64)[0]
 
 
+WALK_SHAPES = [(1, 1), (5, 63), (5, 64), (5, 65), (127, 3), (128, 3), (129, 3), (257, 130), (3, 4, 130), (2, 129, 65)]
+
+
+def test_walk_visits_every_valid_voxel_once_with_the_loop_values(tmp_path):
+    """csrc/mvs_affine_walk_dev.h on the host: block_pos and walk_run called for every block, wave and lane reach exactly the
+    voxels a plain loop over the crop finds valid, each once, with the loop's v, g and dy bit for bit.  The shapes are the
+    smallest that reach every edge of the mapping: one voxel, 63 / 64 / 65 columns, 127 / 128 / 129 rows, three y chunks by three
+    x blocks with partial last ones, and the same in 3D."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
+        pytest.skip("hipcc not available")
+    exe = tmp_path / "affine_walk_host_test"
+    cmd = [hipcc, "-O1", "-std=c++17", "-ffp-contract=off", "--offload-arch=gfx950", "-I", os.path.join(ROOT, "multiview-stitcher_amd", "csrc"),
+           os.path.join(ROOT, "tests", "native", "affine_walk_host_test.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=900)
+    print(r.stdout)
+    lines = r.stdout.strip().splitlines()
+    rows = [[int(t) for t in ln.split()[1:]] for ln in lines if ln.startswith("W ")]
+    assert len(rows) == 2 * len(WALK_SHAPES)
+    seen = set()
+    for nd, nz, ny, nx, ipose, blocks, valid, visited, twice, missing, extra, differ in rows:
+        shape = (nz, ny, nx)[3 - nd:]
+        seen.add((shape, ipose))
+        assert blocks == nz * -(-ny // 128) * -(-nx // 64), (shape, blocks)
+        assert twice == 0, (shape, ipose, twice)
+        assert missing == 0 and extra == 0 and visited == valid, (shape, ipose, valid, visited, missing, extra)
+        assert differ == 0, (shape, ipose, differ)
+        # not vacuous: a crop of one voxel has no interpolation cell; at the identity the cells clear of the last voxel of each axis
+        # and of the NaN border take part unless one of their 1 + 2^ndim values is among the 2 % NaN voxels (17 % of them in 3D)
+        cells = (nz - 1 if nd == 3 else 1) * (ny - (3 if ny >= 8 else 1)) * (nx - (3 if nx >= 8 else 1))
+        assert valid > 0 or shape == (1, 1), (shape, ipose)
+        assert ipose == 1 or cells // 2 <= valid <= cells, (shape, valid, cells)
+    assert seen == {(s, p) for s in WALK_SHAPES for p in (0, 1)}
+    assert r.returncode == 0 and lines[-1] == "done"
+
+
 @pytest.mark.parametrize("ndim", [2, 3])
 @pytest.mark.parametrize("model", ao.MODELS)
 def test_model_jacobian_is_the_derivative_of_the_update(model, ndim):
