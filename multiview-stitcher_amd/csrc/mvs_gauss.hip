@@ -20,6 +20,7 @@
 // at every voxel of the box, the sums the reference forms over the whole chunk line (same taps, same order: the taps that
 // are skipped are exact zeros).  A chunk of a tile grid sees one view nearly whole and up to seven by a corner or a face:
 // 1.3 chunk volumes of filter work instead of 8 on the 2x2x2 probe.
+#include "mvs_cb_plan.h"
 #include "mvs_fuse_dev.h"
 #include "mvs_fuse_tr.h"
 
@@ -34,9 +35,6 @@ namespace {
 inline int grid_for(long long n) { return (int)std::min<long long>((n + 255) / 256, 256 * 16); }
 
 struct Shape3 { int nz, ny, nx; };
-
-struct CbBox { int lo[3], n[3]; long long off; };      // box of a view inside the chunk; off: its first float in the I / BW / F pools
-static_assert(sizeof(CbBox) == 32, "CbBox layout");
 
 __device__ __forceinline__ long long box_index(const CbBox& B, int z, int y, int x) {
     const int bz = z - B.lo[0], by = y - B.lo[1], bx = x - B.lo[2];
@@ -73,8 +71,6 @@ __global__ void mask_normalize_kernel(float* __restrict__ bw, const float* __res
 // The same for chunks seen by at most 8 views (every tile grid): the view loop is unrolled, a view's pool index is worked out once
 // per voxel in 32-bit arithmetic and kept in a register, and the masked weight is written once, already normalised (the general
 // kernel stores it, re-reads it and divides in place: 20 instead of 12 bytes per view and voxel).
-struct CbBox32 { int lo[3], n[3], off; };
-struct CbBoxes8 { CbBox32 b[8]; };
 __device__ __forceinline__ int box_index32(const CbBox32& B, int z, int y, int x) {
     const int bz = z - B.lo[0], by = y - B.lo[1], bx = x - B.lo[2];
     if ((unsigned)bz >= (unsigned)B.n[0] || (unsigned)by >= (unsigned)B.n[1] || (unsigned)bx >= (unsigned)B.n[2]) return -1;
@@ -274,9 +270,6 @@ __global__ __launch_bounds__(256) void gauss1d_kernel(const float* __restrict__ 
 // index arithmetic, no reflection and no global load per tap (the tap-by-tap kernel above spends its time there: the
 // sigma = 11 filter has 89 taps).  Same accumulation order, same rounding.  LDS layout [pos + radius][line], line
 // pitch T + 1 (odd) so that both access directions are bank-conflict free.
-constexpr int kGaussK = 8;      // outputs per thread of the LDS line filters
-struct GaussLines { long long n_lines; int len; long long stride; long long inner; long long outer_stride; int T; int b0, full; };
-
 __global__ __launch_bounds__(256) void gauss1d_lds_kernel(const float* __restrict__ src, float* __restrict__ dst, GaussLines L, int radius,
                                                           const double* __restrict__ fw, int pos_fastest) {
     extern __shared__ float sl[];
@@ -384,7 +377,6 @@ __global__ __launch_bounds__(256) void gauss1d_lds_kernel(const float* __restric
 //   * half of the launches (6 instead of 12 line passes per view) and the second staging of every line set.
 // Same arithmetic as gauss1d_lds_kernel per quantity (scipy's order, double accumulation, float32 result per axis, the
 // constant-tile short cut per quantity).
-enum { SRC_AB = 0, SRC_PREP = 1, SRC_VMASK = 2, DST_AB = 0, DST_SQ = 1, DST_F = 2 };
 struct PairIO {
     const float* a; const float* b;        // SRC_AB: value / mask lines; SRC_VMASK: a = value lines
     const float* im; const float* bw;      // resampled view and normalised blending weight (SRC_PREP / SRC_VMASK / DST_SQ / DST_F)
@@ -410,7 +402,7 @@ template <int SRC, int DST, bool SPLIT>
 __global__ __launch_bounds__(256) void gauss1d_pair_kernel(PairIO P, GaussLines L, int radius, const double* __restrict__ fw, int pos_fastest) {
     static_assert(!SPLIT || DST == DST_AB, "split passes store both quantities as they are");
     extern __shared__ float sl[];
-    // T is a power of two (host: pair_T / split_T), so (line, position) come out of shifts and masks; the lines' first elements
+    // T is a power of two (host: cb_pair_T / cb_split_T), so (line, position) come out of shifts and masks; the lines' first elements
     // are worked out once per workgroup (one 64-bit division per LINE instead of two per staged and stored SAMPLE)
     constexpr int NQ = SPLIT ? 1 : 2;
     const int qs = SPLIT ? (int)blockIdx.y : 0;       // SPLIT: the quantity of this workgroup
@@ -758,636 +750,395 @@ __global__ __launch_bounds__(256) void cb_fuse8_kernel(const float* __restrict__
     }
 }
 
-// scipy.ndimage._filters._gaussian_kernel1d(sigma, 0, radius), radius = int(truncate * sigma + 0.5)
-void gaussian_kernel(double sigma, int* radius_out, std::vector<double>* w) {
-    const int radius = (int)(4.0 * sigma + 0.5);
-    w->resize(2 * radius + 1);
-    const double sigma2 = sigma * sigma;
-    double sum = 0.0;
-    for (int k = -radius; k <= radius; ++k) {
-        const double v = exp(-0.5 / sigma2 * (double)k * (double)k);
-        (*w)[k + radius] = v;
-        sum += v;
-    }
-    for (auto& v : *w) v /= sum;
-    *radius_out = radius;
-}
-
 #include "mvs_gauss_fast.inc"
 
-}  // namespace
+static_assert(sizeof(CbMaskRec) == 32 && sizeof(CbFastRec) == 64 && sizeof(CbPartial) == 32, "record sizes of cb_layout");
+// ---- one content-based chunk: the call's arguments, its plan (mvs_cb_plan.h), the scratch pointers and what the steps derive.  The
+// steps below launch on the context's stream in the order they are called; the two paths are sequences of them. ----
+struct CbCall {
+    MvsContext* c; const mvs_view_t* views; int n_views; const mvs_fuse_opts_t* opts; void* out;
+    bool fast;                                      // the path the steps serve (set by cb_geometry)
+    int dtype, ndim, cs[3], r1, r2;
+    size_t es, host_bytes;
+    Shape3 S, O; long long n, no;                   // the chunk with its halo, the trimmed result
+    std::vector<double> w1, w2;                     // taps of both filters
+    std::vector<DevView> dvs; std::vector<TrView> trv; bool tr_all;
+    std::vector<CbBox> boxes; CbPool pool; CbBoxes8 bx8;
+    CbFastViews VS; int Tsel[3][2][8];              // fast
+    bool paired, small, mask_tables; std::vector<long long> table_off; long long table_floats;      // exact
+    float *I, *BW, *F, *tmp; size_t tmp_b;          // pools; temporaries (exact: 5 / 6 of tmp_b bytes, fast: the pool T0)
+    char* dblock; size_t up_bytes, rec_bytes;       // the uploaded block and what lies in it (ffw: fast, dboxes / dtable_off: exact)
+    double *dfw1, *dfw2; float *ffw1, *ffw2; CbBox* dboxes; DevView* dviews_dev; char* drecs; long long* dtable_off;
+    float* dtables; int4 *rows, *dmiss; double* dtabs; CbPartial* dpart; unsigned rows_grid;      // mask tables (exact), mask scan (fast)
+};
 
-static int cb_fast_chunk(MvsContext* c, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out, bool* taken);
+void cb_begin(CbCall& K, MvsContext* c, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out) {
+    K.c = c; K.views = views; K.n_views = n_views; K.opts = opts; K.out = out;
+    K.dtype = views[0].dtype; K.es = mvs_dtype_size(K.dtype); K.ndim = opts->ndim;
+    for (int k = 0; k < 3; ++k) K.cs[k] = (int)opts->out_shape[k];
+    K.S = {K.cs[0], K.cs[1], K.cs[2]};
+    K.O = {(int)(K.cs[0] - 2 * opts->trim[0]), (int)(K.cs[1] - 2 * opts->trim[1]), (int)(K.cs[2] - 2 * opts->trim[2])};
+    K.n = (long long)K.S.nz * K.S.ny * K.S.nx; K.no = (long long)K.O.nz * K.O.ny * K.O.nx;
+    gaussian_taps((double)opts->sigma_1, &K.r1, &K.w1); gaussian_taps((double)opts->sigma_2, &K.r2, &K.w2);
+}
 
-int mvs_fuse_content_based(MvsContext* c, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out) {
-    if (opts->order != 0 && opts->order != 1) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "content_based: order 0|1 only");
-    if (!c->cb_exact) {      // the default: mask from a box + list, one quantity per pass, float32 taps (mvs_gauss_fast.inc)
-        bool taken = false;
-        const int rc = cb_fast_chunk(c, views, n_views, opts, out, &taken);
-        if (rc || taken) return rc;
-    }
-    const int dtype = views[0].dtype;
-    const size_t es = mvs_dtype_size(dtype);
-    const int64_t* cs = opts->out_shape;
-    const Shape3 S = {(int)cs[0], (int)cs[1], (int)cs[2]};
-    const long long n = (long long)S.nz * S.ny * S.nx;
-    int64_t os[3];
-    for (int k = 0; k < 3; ++k) os[k] = cs[k] - 2 * opts->trim[k];
-    const Shape3 O = {(int)os[0], (int)os[1], (int)os[2]};
-    const long long no = (long long)O.nz * O.ny * O.nx;
-
-    // ---- device views and their boxes inside the chunk ----
-    std::vector<DevView> dvs((size_t)n_views);
-    std::vector<CbBox> boxes((size_t)n_views);
-    size_t host_bytes = 0;
-    { const int rcs = mvs_stage_views_bytes(c, views, n_views, es, &host_bytes); if (rcs) return rcs; }
-    char* slab_base = nullptr;
-    if (host_bytes) {
-        slab_base = (char*)mvs_scratch(c, 0, host_bytes);
-        if (!slab_base) return mvs_alloc_failed(c);
-    }
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    size_t cursor = 0;
-    long long pool = 0, max_box = 1;
-    for (int i = 0; i < n_views; ++i) {
-        const void* dptr;
-        int rc = mvs_stage_view(c, views[i], es, slab_base, &cursor, &dptr);
-        if (rc) return rc;
-        rc = mvs_fill_dev_view(c, views[i], opts->ndim, dptr, &dvs[i]);
-        if (rc) return rc;
-        mvs_view_to_chunk_frame(&dvs[i], opts->index_origin, views[i].index_offset);
-        int lo[3], hi[3];
-        mvs_view_chunk_box(dvs[i], cs, lo, hi);
-        CbBox& B = boxes[i];
-        long long bv = 1;
-        for (int k = 0; k < 3; ++k) {
-            B.lo[k] = lo[k];
-            B.n[k] = std::max(hi[k] - lo[k] + 1, 0);
-            bv *= B.n[k];
-        }
-        if (bv == 0) { B.n[0] = B.n[1] = B.n[2] = 0; }
-        B.off = pool;
-        pool += (bv + 63) / 64 * 64;
-        max_box = std::max(max_box, bv);
-    }
-
-    // ---- scratch layout (slot 6): pools I, BW, F (one box per view), 6 temporaries of the largest box, filter kernels, boxes ----
-    const size_t pool_b = (size_t)pool * 4, tmp_b = align_up((size_t)max_box * 4);
-    // paired line passes (gauss1d_pair_kernel): can every line set of every view be staged twice in 60 KiB of LDS?
-    const int ndim = opts->ndim;
-    int r1, r2;
-    std::vector<double> w1, w2;
-    gaussian_kernel((double)opts->sigma_1, &r1, &w1);
-    gaussian_kernel((double)opts->sigma_2, &r2, &w2);
-    auto pair_T = [&](int len, int radius, int axis) {      // lines per workgroup of a paired pass, 0: does not fit
-        const size_t span = (size_t)len + 2 * (size_t)radius;
-        int T = (axis == 2) ? 8 : 16;
-        while (T > 1 && span * (T + 1) * 8 > 60 * 1024) T >>= 1;
-        if (span * (T + 1) * 8 > 60 * 1024 || (axis != 2 && T < 4)) return 0;
-        return T;
-    };
-    auto split_T = [&](int len, int radius) {         // lines per workgroup of a split pass (one quantity in LDS), 0: does not fit
-        const size_t span = (size_t)len + 2 * (size_t)radius;
-        int T = 32;      // (8 / 16 / 32 measured: 30.9 / 28.5 / 28.1 ms per probe call)
-        while (T > 1 && span * (T + 1) * 4 > 60 * 1024) T >>= 1;
-        return (span * (T + 1) * 4 > 60 * 1024 || T < 8) ? 0 : T;
-    };
-    bool paired = !c->cb_unpaired;
-    for (int i = 0; i < n_views && paired; ++i)
-        for (int axis = 3 - ndim; axis < 3; ++axis)
-            if (boxes[i].n[axis] > 0 && (!pair_T(boxes[i].n[axis], r1, axis) || !pair_T(boxes[i].n[axis], r2, axis))) paired = false;
-    // temporaries of the largest box, shared by the views: 5 arrays on the paired path, 6 on the separate-pass path
-    const size_t tmp_total = (paired ? 5 : 6) * tmp_b;
-    // mask records + table offsets (uploaded with the block below) and the mask tables B(z, y) of every view and filter
-    const bool mask_tables = paired && n_views <= 8 && pool < (1ll << 31) && c->cb_mask_closed_form;
-    std::vector<long long> table_off((size_t)n_views * 2, 0);
-    long long table_floats = 0;
-    if (mask_tables)
-        for (int i = 0; i < n_views; ++i)
-            for (int f = 0; f < 2; ++f) {
-                table_off[(size_t)i * 2 + f] = table_floats;
-                table_floats += ((long long)boxes[i].n[0] * boxes[i].n[1] + 63) / 64 * 64;
-            }
-    const size_t need = 3 * pool_b + tmp_total + 64 * 1024 + (size_t)n_views * (sizeof(CbBox) + sizeof(DevView) + sizeof(CbMaskRec) + 16) + 4096 +
-                        (size_t)table_floats * 4;
-    char* base = (char*)mvs_scratch(c, 6, need);
-    if (!base) return mvs_alloc_failed(c);
-    float* I = (float*)base;
-    float* BW = (float*)(base + pool_b);
-    float* F = (float*)(base + 2 * pool_b);
-    float* A = (float*)(base + 3 * pool_b);
-    float* V0 = (float*)((char*)A + tmp_b);
-    float* M = (float*)((char*)V0 + tmp_b);
-    float* T0 = (float*)((char*)M + tmp_b);
-    float* T1 = (float*)((char*)T0 + tmp_b);
-    float* T2 = (float*)((char*)T1 + tmp_b);
-    // filter kernels, boxes and view records: ONE device block in the layout of the host staging block below (one upload per chunk)
-    char* dblock = (char*)align_up((uintptr_t)(base + 3 * pool_b + tmp_total));
-    if ((w1.size() + w2.size()) * 8 > 32 * 1024) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "content_based: sigma too large");
-    const size_t wb = align_up((w1.size() + w2.size()) * 8), bb = align_up((size_t)n_views * sizeof(CbBox)),
-                 vb = align_up((size_t)n_views * sizeof(DevView)), rb = align_up((size_t)n_views * sizeof(CbMaskRec)),
-                 ob = align_up((size_t)n_views * 16);
-    double* dfw1 = (double*)dblock;
-    double* dfw2 = dfw1 + w1.size();
-    CbBox* dboxes = (CbBox*)(dblock + wb);
-    DevView* dviews_dev = (DevView*)(dblock + wb + bb);      // the views' records for the batched box launches
-    CbMaskRec* drecs = (CbMaskRec*)(dblock + wb + bb + vb);
-    long long* dtable_off = (long long*)(dblock + wb + bb + vb + rb);
-    float* dtables = (float*)(dblock + wb + bb + vb + rb + ob);
-    // The block travels through the context's pinned staging slot (waited for before it is refilled: mvs_pinned_slot /
-    // mvs_pinned_mark), so the call does not have to wait for its own work: with the result on the device it returns as soon as
-    // everything is queued, and the host prepares the next chunk while this one is filtered (the probe spent ~0.4 ms per chunk idle)
-    {
-        char* hp = (char*)mvs_pinned_slot(c, 0, wb + bb + vb + rb + ob + 64);
-        if (!hp) return mvs_alloc_failed(c);
-        memcpy(hp, w1.data(), w1.size() * 8);
-        memcpy(hp + w1.size() * 8, w2.data(), w2.size() * 8);
-        memcpy(hp + wb, boxes.data(), (size_t)n_views * sizeof(CbBox));
-        memcpy(hp + wb + bb, &dvs[0], (size_t)n_views * sizeof(DevView));
-        for (int i = 0; i < n_views; ++i) {      // empty records: count 0, inverted bounding box
-            CbMaskRec r;
-            r.cnt = 0;
-            for (int k = 0; k < 3; ++k) { r.lo[k] = 0x7fffffff; r.hi[k] = -1; }
-            memcpy(hp + wb + bb + vb + (size_t)i * sizeof(CbMaskRec), &r, sizeof(r));
-        }
-        memcpy(hp + wb + bb + vb + rb, table_off.data(), (size_t)n_views * 16);
-        { const int rcu = mvs_upload_small(c, dblock, hp, wb + bb + vb + rb + ob); if (rcu) return rcu; }
-        mvs_pinned_mark(c, 0);
-    }
-
-    {   // resampled views and blend weights on the views' boxes: two launches for all views of the chunk (<= 8 views)
-        std::vector<float*> res_out(n_views), blend_out(n_views);
-        std::vector<int64_t> shp((size_t)n_views * 3);
-        std::vector<int> b0((size_t)n_views * 3);
-        for (int i = 0; i < n_views; ++i) {
-            const CbBox& B = boxes[i];
-            res_out[i] = I + B.off;
-            blend_out[i] = BW + B.off;
-            for (int k = 0; k < 3; ++k) { shp[(size_t)i * 3 + k] = B.n[k]; b0[(size_t)i * 3 + k] = B.lo[k]; }
-        }
-        mvs_launch_boxes_batch(c, &dvs[0], dviews_dev, n_views, dtype, opts->order, NAN, res_out.data(), blend_out.data(),
-                               (const int64_t (*)[3])shp.data(), (const int (*)[3])b0.data());
-    }
-    const int gb = grid_for(n);
-    // <= 8 views and a pool below 2^31 floats: boxes as a kernel argument, 32-bit indices kept in registers
-    const bool small = n_views <= 8 && pool < (1ll << 31);
-    CbBoxes8 bx8;
-    memset(&bx8, 0, sizeof(bx8));
-    if (small)
-        for (int i = 0; i < n_views; ++i) {
-            for (int k = 0; k < 3; ++k) { bx8.b[i].lo[k] = boxes[i].lo[k]; bx8.b[i].n[k] = boxes[i].n[k]; }
-            bx8.b[i].off = (int)boxes[i].off;
-        }
-    if (small) hipLaunchKernelGGL(mask_normalize8_kernel, dim3(gb), dim3(256), 0, c->stream, BW, I, bx8, n_views, S, 0);
-    else hipLaunchKernelGGL(mask_normalize_kernel, dim3(gb), dim3(256), 0, c->stream, BW, I, dboxes, n_views, S);
-
-    if (mask_tables) {      // is every view's valid mask a box?  (device-side: record + tables, no host round trip)
-        long long max_bv = 1;
-        int max_nz = 1;
-        for (int i = 0; i < n_views; ++i) {
-            max_bv = std::max(max_bv, (long long)boxes[i].n[0] * boxes[i].n[1] * boxes[i].n[2]);
-            max_nz = std::max(max_nz, boxes[i].n[0]);
-        }
-        hipLaunchKernelGGL(cb_mask_bbox_kernel, dim3((unsigned)std::min<long long>((max_bv + 2047) / 2048, 512), n_views), dim3(256), 0, c->stream,
-                           I, BW, bx8, drecs);
-        hipLaunchKernelGGL(cb_mask_table_kernel, dim3(max_nz, n_views, 2), dim3(256), 0, c->stream, drecs, bx8, S, ndim, r1, dfw1, r2, dfw2,
-                           dtables, dtable_off);
-        if (c->cb_mask_count) {      // test switch: read the records back and count the views whose mask was found to be a box
-            std::vector<CbMaskRec> hrec((size_t)n_views);
-            MVS_HIP_TRY(c, hipMemcpyAsync(hrec.data(), drecs, (size_t)n_views * sizeof(CbMaskRec), hipMemcpyDeviceToHost, c->stream));
-            MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-            for (const CbMaskRec& r : hrec) {
-                const unsigned long long vol = r.cnt ? (unsigned long long)(r.hi[0] - r.lo[0] + 1) * (unsigned long long)(r.hi[1] - r.lo[1] + 1) *
-                                                       (unsigned long long)(r.hi[2] - r.lo[2] + 1) : 0ull;
-                c->cb_mask_views += 1;
-                c->cb_mask_boxes += (r.cnt && vol == r.cnt) ? 1 : 0;
-                if (getenv("MVS_CB_DEBUG")) {
-                    const CbBox& Bd = boxes[(size_t)(&r - hrec.data())];
-                    fprintf(stderr, "[cb mask] view box lo %d %d %d n %d %d %d: valid %llu, bbox %d..%d %d..%d %d..%d (volume %llu)\n", Bd.lo[0], Bd.lo[1], Bd.lo[2],
-                            Bd.n[0], Bd.n[1], Bd.n[2], r.cnt, r.lo[0], r.hi[0], r.lo[1], r.hi[1], r.lo[2], r.hi[2], vol);
-                }
-            }
-        }
-    }
-
-    auto gauss = [&](const float* src, float* dst, const CbBox& B, int radius, const double* fw) {
-        // scipy filters axis 0, 1, 2 in turn; a 2D chunk has no z axis
-        const Shape3 Sb = {B.n[0], B.n[1], B.n[2]};
-        const long long bn = (long long)B.n[0] * B.n[1] * B.n[2];
-        const int gbb = grid_for(bn);
-        const float* cur = src;
-        float* tmp[2] = {T1, T2};
-        int pass = 0;
-        for (int axis = 3 - ndim; axis < 3; ++axis, ++pass) {
-            float* d = (axis == 2) ? dst : tmp[pass & 1];
-            // LDS-staged lines when a useful tile of them fits into 64 KiB; else the tap-by-tap kernel
-            GaussLines L;
-            const long long nz = Sb.nz, ny = Sb.ny, nx = Sb.nx;
-            if (axis == 2) { L.len = Sb.nx; L.stride = 1; L.n_lines = nz * ny; L.inner = 1; L.outer_stride = nx; }
-            else if (axis == 1) { L.len = Sb.ny; L.stride = nx; L.n_lines = nz * nx; L.inner = nx; L.outer_stride = ny * nx; }
-            else { L.len = Sb.nz; L.stride = ny * nx; L.n_lines = ny * nx; L.inner = ny * nx; L.outer_stride = 0; }
-            L.b0 = B.lo[axis];
-            L.full = (&S.nz)[axis];
-            const int span = L.len + 2 * radius;
-            int T = (axis == 2) ? 8 : 32;
-            while (T > 1 && (size_t)span * (T + 1) * 4 > 60 * 1024) T >>= 1;
-            if ((size_t)span * (T + 1) * 4 <= 60 * 1024 && (axis == 2 || T >= 8)) {
-                L.T = T;
-                const size_t lds = (size_t)span * (T + 1) * 4;
-                const long long nb = (L.n_lines + T - 1) / T;
-                hipLaunchKernelGGL(gauss1d_lds_kernel, dim3((unsigned)nb), dim3(256), lds, c->stream, cur, d, L, radius, fw, axis == 2 ? 1 : 0);
-            } else {
-                hipLaunchKernelGGL(gauss1d_kernel, dim3(gbb), dim3(256), 0, c->stream, cur, d, Sb, axis, radius, fw, L.b0, L.full);
-            }
-            cur = d;
-        }
-    };
-    // ---- paired path: per view 2 x ndim launches, one view after the other on the context's stream.  (Round 4 first ran the
-    // views' chains side by side on the side streams -- 27.0 ms per probe call against 27.5 serial; once the call stopped waiting
-    // for its own work (below) the serial form took 23.4 ms and the forked one 32-33: consecutive chunks overlap on ONE stream by
-    // themselves, and the fork / join events between low-priority side streams only got in their way.) ----
-    if (paired) {
-        std::vector<int> order;
-        for (int v = 0; v < n_views; ++v)
-            if ((long long)boxes[v].n[0] * boxes[v].n[1] * boxes[v].n[2] > 0) order.push_back(v);
-        float* TP5 = A;      // 5 temporaries of the largest box, shared by the views
-        for (size_t oi = 0; oi < order.size(); ++oi) {
-            const int v = order[oi];
-            const CbBox& B = boxes[v];
-            hipStream_t st = c->stream;
-            float* t[5];
-            for (int k = 0; k < 5; ++k) t[k] = (float*)((char*)TP5 + (size_t)k * tmp_b);
-            const float* Iv = I + B.off;
-            const float* Bv = BW + B.off;
-            for (int f = 0; f < 2; ++f) {
-                const int radius = f ? r2 : r1;
-                const double* fw = f ? dfw2 : dfw1;
-                const float *ina = nullptr, *inb = nullptr;
-                int pass = 0;
-                for (int axis = 3 - ndim; axis < 3; ++axis, ++pass) {
-                    const bool firstp = axis == 3 - ndim, lastp = axis == 2;
-                    PairIO P;
-                    P.im = Iv; P.bw = Bv;
-                    P.a = firstp ? (f ? t[4] : nullptr) : ina;
-                    P.b = firstp ? nullptr : inb;
-                    P.src = firstp ? (f ? SRC_VMASK : SRC_PREP) : SRC_AB;
-                    P.dst = lastp ? (f ? DST_F : DST_SQ) : DST_AB;
-                    P.oa = lastp ? (f ? F + B.off : t[4]) : t[2 * (pass & 1)];
-                    P.ob = lastp ? nullptr : t[2 * (pass & 1) + 1];
-                    P.rec = mask_tables ? drecs + v : nullptr;
-                    P.mtab = mask_tables ? dtables + table_off[(size_t)v * 2 + f] : nullptr;
-                    GaussLines L;
-                    const long long nz = B.n[0], ny = B.n[1], nx = B.n[2];
-                    if (axis == 2) { L.len = B.n[2]; L.stride = 1; L.n_lines = nz * ny; L.inner = 1; L.outer_stride = nx; }
-                    else if (axis == 1) { L.len = B.n[1]; L.stride = nx; L.n_lines = nz * nx; L.inner = nx; L.outer_stride = ny * nx; }
-                    else { L.len = B.n[0]; L.stride = ny * nx; L.n_lines = ny * nx; L.inner = ny * nx; L.outer_stride = 0; }
-                    L.b0 = B.lo[axis];
-                    L.full = (&S.nz)[axis];
-                    // passes along y / z that only hand both quantities on: one quantity per workgroup, twice the lines (128-byte pieces)
-                    const int Ts = (P.dst == DST_AB && axis != 2 && !c->cb_nosplit) ? split_T(L.len, radius) : 0;
-                    const bool split = Ts > 0;
-                    L.T = split ? Ts : pair_T(L.len, radius, axis);
-                    const size_t lds = (size_t)(L.len + 2 * radius + kGaussK) * (L.T + 1) * (split ? 4 : 8);
-                    const long long nb = (L.n_lines + L.T - 1) / L.T;
-                    const dim3 g((unsigned)nb, split ? 2 : 1), b(256);
-                    const int pf = axis == 2 ? 1 : 0;
-#define MVS_PAIR(S_, D_, SP_) hipLaunchKernelGGL((gauss1d_pair_kernel<S_, D_, SP_>), g, b, lds, st, P, L, radius, fw, pf)
-                    if (split) {
-                        if (P.src == SRC_PREP) MVS_PAIR(SRC_PREP, DST_AB, true);
-                        else if (P.src == SRC_VMASK) MVS_PAIR(SRC_VMASK, DST_AB, true);
-                        else MVS_PAIR(SRC_AB, DST_AB, true);
-                    }
-                    else if (P.src == SRC_PREP && P.dst == DST_AB) MVS_PAIR(SRC_PREP, DST_AB, false);
-                    else if (P.src == SRC_PREP && P.dst == DST_SQ) MVS_PAIR(SRC_PREP, DST_SQ, false);
-                    else if (P.src == SRC_VMASK && P.dst == DST_AB) MVS_PAIR(SRC_VMASK, DST_AB, false);
-                    else if (P.src == SRC_VMASK && P.dst == DST_F) MVS_PAIR(SRC_VMASK, DST_F, false);
-                    else if (P.src == SRC_AB && P.dst == DST_AB) MVS_PAIR(SRC_AB, DST_AB, false);
-                    else if (P.src == SRC_AB && P.dst == DST_SQ) MVS_PAIR(SRC_AB, DST_SQ, false);
-                    else MVS_PAIR(SRC_AB, DST_F, false);
-#undef MVS_PAIR
-                    ina = P.oa; inb = P.ob;
-                }
-            }
-        }
-        MVS_HIP_TRY(c, hipGetLastError());
-    }
-    for (int v = 0; v < n_views && !paired; ++v) {
-        const CbBox& B = boxes[v];
-        const long long bn = (long long)B.n[0] * B.n[1] * B.n[2];
-        if (bn == 0) continue;
-        const int gbb = grid_for(bn);
-        const float* Iv = I + B.off;
-        const float* Bv = BW + B.off;
-        float* Fv = F + B.off;
-        hipLaunchKernelGGL(prep_kernel, dim3(gbb), dim3(256), 0, c->stream, Iv, Bv, bn, A, V0, M);
-        gauss(V0, T0, B, r1, dfw1);           // VV  (T0)
-        gauss(M, Fv, B, r1, dfw1);            // WW  (Fv used as temporary)
-        hipLaunchKernelGGL(ng_finish_sq_kernel, dim3(gbb), dim3(256), 0, c->stream, T0, Fv, A, bn, V0);   // V0 <- (A - Z)^2, NaN -> 0
-        gauss(V0, T0, B, r2, dfw2);           // VV2 (T0)
-        gauss(M, V0, B, r2, dfw2);            // WW2 (V0)
-        hipLaunchKernelGGL(ng_finish_kernel, dim3(gbb), dim3(256), 0, c->stream, T0, V0, A, bn, Fv);
-    }
-    MVS_HIP_TRY(c, hipGetLastError());
-
-    const size_t out_bytes = (size_t)no * es;
-    void* dout = out;
-    if (opts->out_mem == MVS_MEM_HOST) {
-        dout = mvs_scratch(c, 1, out_bytes);
-        if (!dout) return mvs_alloc_failed(c);
-    }
-    const int gbo = grid_for(no);
-    const int tz = (int)opts->trim[0], ty = (int)opts->trim[1], tx = (int)opts->trim[2];
-    mvs_dispatch_dtype(dtype, [&](auto tag) {
-        using T = decltype(tag);
-        if (small)
-            hipLaunchKernelGGL(cb_fuse8_kernel<T>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, bx8, n_views, tz, ty, tx, O, (T*)dout);
-        else
-            hipLaunchKernelGGL(cb_fuse_kernel<T>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, dboxes, n_views, tz, ty, tx, O, (T*)dout);
-    });
-    MVS_HIP_TRY(c, hipGetLastError());
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->timing_valid = true;
-    if (opts->out_mem == MVS_MEM_HOST) {
-        MVS_HIP_TRY(c, hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
-        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else if (host_bytes) {
-        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));      // host slabs were staged through scratch that the next call may overwrite
+// Device views in the chunk's frame and their boxes inside the chunk.  No side effect: nothing is queued, and the views' data pointers
+// stay the call's until cb_stage_views (the geometry does not depend on them).  fast: the views also get their translation-path
+// records; one without the closed-form blend weight sends all of them through the generic blend launch.
+int cb_geometry(CbCall& K, bool fast) {
+    K.fast = fast;
+    { const int rc = mvs_stage_views_bytes(K.c, K.views, K.n_views, K.es, &K.host_bytes); if (rc) return rc; }
+    K.dvs.resize((size_t)K.n_views); K.boxes.resize((size_t)K.n_views);
+    if (fast) K.trv.resize((size_t)K.n_views);
+    K.tr_all = fast && !K.c->cb_blend_generic;
+    K.pool = CbPool(); K.VS = CbFastViews{}; K.VS.nv = K.n_views;
+    for (int i = 0; i < K.n_views; ++i) {
+        { const int rc = mvs_fill_dev_view(K.c, K.views[i], K.ndim, K.views[i].data, &K.dvs[i]); if (rc) return rc; }
+        if (!fast) mvs_view_to_chunk_frame(&K.dvs[i], K.opts->index_origin, K.views[i].index_offset);
+        else if (!mvs_prepare_tr_view(&K.dvs[i], K.opts->order, K.opts->out_shape, K.es, K.opts->index_origin, K.views[i].index_offset, &K.trv[i])) K.tr_all = false;
+        int lo[3], hi[3], row0, tab0;
+        mvs_view_chunk_box(K.dvs[i], K.opts->out_shape, lo, hi);
+        const CbBox& B = K.boxes[i];
+        cb_box_add(&K.pool, lo, hi, &K.boxes[i], &row0, &tab0);
+        if (fast) K.VS.v[i] = CbFastView{(int)B.off, {B.n[0], B.n[1], B.n[2]}, {B.lo[0], B.lo[1], B.lo[2]}, row0, tab0, 0, 0, 0, 0, 0, 0};
     }
     return MVS_OK;
 }
 
-// ---- the fast path of one chunk (kernels: mvs_gauss_fast.inc).  *taken = false: this chunk is not its kind (more than 8 views, a
-// rotated / scaled view, a chunk axis shorter than a filter radius, a line that does not fit LDS, or -- host results only, where the
-// call waits anyway -- a mask list that overflowed) and the caller runs the bit-faithful passes. ----
-static int cb_fast_chunk(MvsContext* c, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out, bool* taken) {
-    *taken = false;
-    if (n_views > 8 || n_views < 1) return MVS_OK;
-    const int dtype = views[0].dtype;
-    const size_t es = mvs_dtype_size(dtype);
-    const int64_t* cs = opts->out_shape;
-    const Shape3 S = {(int)cs[0], (int)cs[1], (int)cs[2]};
-    const long long n = (long long)S.nz * S.ny * S.nx;
-    const int ndim = opts->ndim;
-    int64_t os[3];
-    for (int k = 0; k < 3; ++k) os[k] = cs[k] - 2 * opts->trim[k];
-    const Shape3 O = {(int)os[0], (int)os[1], (int)os[2]};
-    const long long no = (long long)O.nz * O.ny * O.nx;
-    int r1, r2;
-    std::vector<double> w1, w2;
-    gaussian_kernel((double)opts->sigma_1, &r1, &w1);
-    gaussian_kernel((double)opts->sigma_2, &r2, &w2);
-    for (int axis = 3 - ndim; axis < 3; ++axis)
-        if (cs[axis] < std::max(r1, r2)) return MVS_OK;      // (further images of a voxel under the reflection would be in reach)
-    static const double I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    for (int i = 0; i < n_views; ++i)
-        for (int k = 0; k < 9; ++k)
-            if (views[i].matrix[k] != I9[k]) return MVS_OK;
-    if (std::max(r1, r2) > kCbMaxRadius) return MVS_OK;
-
-    // ---- device views and their boxes inside the chunk ----
-    std::vector<DevView> dvs((size_t)n_views);
-    size_t host_bytes = 0;
-    { const int rcs = mvs_stage_views_bytes(c, views, n_views, es, &host_bytes); if (rcs) return rcs; }
-    CbFastViews VS;
-    memset(&VS, 0, sizeof(VS));
-    VS.nv = n_views;
-    long long pool = 0, total_rows = 0, tab_doubles = 0;
-    std::vector<TrView> trv((size_t)n_views);
-    bool tr_all = !c->cb_blend_generic;
-    {
-        for (int i = 0; i < n_views; ++i) {
-            // (slab pointers of host views are filled in below, once the scratch exists; the geometry does not depend on them)
-            int rc = mvs_fill_dev_view(c, views[i], ndim, views[i].data, &dvs[i]);
-            if (rc) return rc;
-            // (also moves the view into the chunk's frame; a view without the closed-form blend weight: the generic blend launch)
-            if (!mvs_prepare_tr_view(&dvs[i], opts->order, cs, es, opts->index_origin, views[i].index_offset, &trv[i])) tr_all = false;
-            int lo[3], hi[3];
-            mvs_view_chunk_box(dvs[i], cs, lo, hi);
-            CbFastView& B = VS.v[i];
-            long long bv = 1;
-            for (int k = 0; k < 3; ++k) {
-                B.lo[k] = lo[k];
-                B.n[k] = std::max(hi[k] - lo[k] + 1, 0);
-                bv *= B.n[k];
-            }
-            if (bv == 0) { B.n[0] = B.n[1] = B.n[2] = 0; }
-            if (pool + bv >= (1ll << 31)) return MVS_OK;
-            B.off = (int)pool;
-            pool += (bv + 63) / 64 * 64;
-            B.row0 = (int)total_rows;
-            total_rows += (long long)B.n[0] * B.n[1];
-            B.tab0 = (int)tab_doubles;
-            tab_doubles += 2ll * (B.n[0] + B.n[1] + B.n[2]);
-        }
-    }
-    // lines per workgroup of every (axis, filter, view): 0 = a line does not fit -> not this path
-    int Tsel[3][2][8];
-    int xt_lo = 8, xt_hi = 32, dbg = 0;
-    if (const char* e = getenv("MVS_CBF_XT")) { xt_lo = xt_hi = atoi(e); }
-    if (const char* e = getenv("MVS_CBF_DBG")) dbg = atoi(e);
-    for (int axis = 3 - ndim; axis < 3; ++axis)
-        for (int f = 0; f < 2; ++f)
-            for (int i = 0; i < n_views; ++i) {
-                const int len = VS.v[i].n[axis];
-                Tsel[axis][f][i] = len > 0 ? cb_fast_T(len, f ? r2 : r1, axis == 2 ? xt_lo : 32, axis == 2 ? xt_hi : 64, axis == 2) : 8;
-                if (!Tsel[axis][f][i]) return MVS_OK;
-            }
+// Host slabs go through scratch slot 0; ev_start opens the call's timing in front of the first upload.
+int cb_stage_views(CbCall& K) {
+    MvsContext* c = K.c;
     char* slab_base = nullptr;
-    if (host_bytes) {
-        slab_base = (char*)mvs_scratch(c, 0, host_bytes);
-        if (!slab_base) return mvs_alloc_failed(c);
-    }
-    if (!c->cb_flag_host) {
+    if (K.host_bytes && !(slab_base = (char*)mvs_scratch(c, 0, K.host_bytes))) return mvs_alloc_failed(c);
+    if (K.fast && !c->cb_flag_host) {      // the word the device raises when a view's mask list overflows
         MVS_HIP_TRY(c, hipHostMalloc((void**)&c->cb_flag_host, 64, hipHostMallocMapped));
         MVS_HIP_TRY(c, hipHostGetDevicePointer((void**)&c->cb_flag_dev, c->cb_flag_host, 0));
         *c->cb_flag_host = 0;
     }
     MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    {
-        size_t cursor = 0;
-        for (int i = 0; i < n_views; ++i) {
-            const int rcs = mvs_stage_view(c, views[i], es, slab_base, &cursor, &dvs[i].data);
-            if (rcs) return rcs;
-        }
-    }
+    size_t cursor = 0;
+    int rc = MVS_OK;
+    for (int i = 0; i < K.n_views && !rc; ++i) rc = mvs_stage_view(c, K.views[i], K.es, slab_base, &cursor, &K.dvs[i].data);
+    return rc;
+}
 
-    // ---- scratch (slot 6): pools I, BW, F, T0; row records; [uploaded block: weights f64 / f32, view records, mask records]; lists; tables ----
-    const size_t pool_b = align_up((size_t)pool * 4);
-    const size_t rows_b = align_up((size_t)total_rows * 16);
-    const size_t nw = w1.size() + w2.size();
-    const size_t wdb = align_up(nw * 8), wfb = align_up(nw * 4), vb = align_up((size_t)n_views * sizeof(DevView)),
-                 rb = align_up((size_t)n_views * sizeof(CbFastRec));
-    const size_t up_b = wdb + wfb + vb + rb;
-    const size_t miss_b = (size_t)n_views * kCbMissCap * 16, tab_b = align_up((size_t)tab_doubles * 8);
-    long long max_rows = 1;
-    for (int i = 0; i < n_views; ++i) max_rows = std::max(max_rows, (long long)VS.v[i].n[0] * VS.v[i].n[1]);
-    const unsigned rows_grid = (unsigned)std::min<long long>((max_rows + 15) / 16, 1024);      // a workgroup: 4 wavefronts x 4 rows per sweep
-    const size_t part_b = align_up((size_t)n_views * rows_grid * sizeof(CbPartial));
-    const size_t need = 4 * pool_b + rows_b + up_b + miss_b + tab_b + part_b + 4096;
-    char* base = (char*)mvs_scratch(c, 6, need);
-    if (!base) return mvs_alloc_failed(c);
-    float* I = (float*)base;
-    float* BW = (float*)(base + pool_b);
-    float* F = (float*)(base + 2 * pool_b);
-    float* T0 = (float*)(base + 3 * pool_b);
-    int4* rows = (int4*)(base + 4 * pool_b);
-    char* dblock = base + 4 * pool_b + rows_b;
-    double* dfw1 = (double*)dblock;
-    double* dfw2 = dfw1 + w1.size();
-    float* ffw1 = (float*)(dblock + wdb);
-    float* ffw2 = ffw1 + w1.size();
-    DevView* dviews_dev = (DevView*)(dblock + wdb + wfb);
-    CbFastRec* drecs = (CbFastRec*)(dblock + wdb + wfb + vb);
-    int4* dmiss = (int4*)(dblock + up_b);
-    double* dtabs = (double*)(dblock + up_b + miss_b);
-    CbPartial* dpart = (CbPartial*)(dblock + up_b + miss_b + tab_b);
-    {
-        char* hp = (char*)mvs_pinned_slot(c, 0, up_b + 64);
-        if (!hp) return mvs_alloc_failed(c);
-        memcpy(hp, w1.data(), w1.size() * 8);
-        memcpy(hp + w1.size() * 8, w2.data(), w2.size() * 8);
-        float* hf = (float*)(hp + wdb);
-        for (size_t k = 0; k < w1.size(); ++k) hf[k] = (float)w1[k];
-        for (size_t k = 0; k < w2.size(); ++k) hf[w1.size() + k] = (float)w2[k];
-        memcpy(hp + wdb + wfb, &dvs[0], (size_t)n_views * sizeof(DevView));
-        for (int i = 0; i < n_views; ++i) {
-            CbFastRec r;
-            memset(&r, 0, sizeof(r));
-            for (int k = 0; k < 3; ++k) { r.lo[k] = 0x7fffffff; r.hi[k] = -1; }
-            memcpy(hp + wdb + wfb + vb + (size_t)i * sizeof(CbFastRec), &r, sizeof(r));
-        }
-        { const int rcu = mvs_upload_small(c, dblock, hp, up_b); if (rcu) return rcu; }
-        mvs_pinned_mark(c, 0);
+// Taps, boxes, view records, empty mask records (count 0, inverted bounding box) and table offsets: ONE device block in the layout of
+// the host staging block.  It travels through the context's pinned staging slot (waited for before it is refilled), so the call does not
+// wait for its own work: with the result on the device it returns as soon as everything is queued, and the host prepares the next chunk
+// while this one is filtered (the probe spent ~0.4 ms per chunk idle).  mvs_pinned_mark FOLLOWS the upload: the slot is busy until it has run.
+int cb_upload_block(CbCall& K) {
+    char* hp = (char*)mvs_pinned_slot(K.c, 0, K.up_bytes + 64);
+    if (!hp) return mvs_alloc_failed(K.c);
+    auto at = [&](const void* dev) { return hp + ((const char*)dev - K.dblock); };
+    memcpy(at(K.dfw1), K.w1.data(), K.w1.size() * 8); memcpy(at(K.dfw2), K.w2.data(), K.w2.size() * 8);
+    for (size_t k = 0; k < K.w1.size() && K.fast; ++k) ((float*)at(K.ffw1))[k] = (float)K.w1[k];
+    for (size_t k = 0; k < K.w2.size() && K.fast; ++k) ((float*)at(K.ffw2))[k] = (float)K.w2[k];
+    if (!K.fast) memcpy(at(K.dboxes), K.boxes.data(), (size_t)K.n_views * sizeof(CbBox));
+    memcpy(at(K.dviews_dev), &K.dvs[0], (size_t)K.n_views * sizeof(DevView));
+    const CbMaskRec empty = {0ull, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {-1, -1, -1}};      // (CbFastRec begins with the same fields)
+    for (int i = 0; i < K.n_views; ++i) {
+        memset(at(K.drecs) + (size_t)i * K.rec_bytes, 0, K.rec_bytes);
+        memcpy(at(K.drecs) + (size_t)i * K.rec_bytes, &empty, sizeof(empty));
     }
+    if (!K.fast) memcpy(at(K.dtable_off), K.table_off.data(), (size_t)K.n_views * 16);
+    { const int rc = mvs_upload_small(K.c, K.dblock, hp, K.up_bytes); if (rc) return rc; }
+    mvs_pinned_mark(K.c, 0);
+    return MVS_OK;
+}
 
-    {   // resampled views and blend weights on the views' boxes: two launches for all views of the chunk
-        std::vector<float*> res_out(n_views), blend_out(n_views);
-        std::vector<int64_t> shp((size_t)n_views * 3);
-        std::vector<int> b0((size_t)n_views * 3);
-        for (int i = 0; i < n_views; ++i) {
-            const CbFastView& B = VS.v[i];
-            res_out[i] = I + B.off;
-            blend_out[i] = BW + B.off;
-            for (int k = 0; k < 3; ++k) { shp[(size_t)i * 3 + k] = B.n[k]; b0[(size_t)i * 3 + k] = B.lo[k]; }
-        }
-        mvs_launch_boxes_batch(c, &dvs[0], dviews_dev, n_views, dtype, opts->order, NAN, res_out.data(), blend_out.data(),
-                               (const int64_t (*)[3])shp.data(), (const int (*)[3])b0.data(), tr_all ? trv.data() : nullptr);
+// Resampled views and blend weights on the views' boxes (two launches for all views of a chunk of <= 8), then bw *= ~isnan(view),
+// normalised over the views
+void cb_resample_blend_normalize(CbCall& K) {
+    MvsContext* c = K.c;
+    const size_t nv = (size_t)K.n_views;
+    std::vector<float*> outs(2 * nv); std::vector<int64_t> shp(3 * nv); std::vector<int> b0(3 * nv);
+    for (size_t i = 0; i < nv; ++i) {
+        const CbBox& B = K.boxes[i];
+        outs[i] = K.I + B.off; outs[nv + i] = K.BW + B.off;
+        for (int k = 0; k < 3; ++k) { shp[i * 3 + k] = B.n[k]; b0[i * 3 + k] = B.lo[k]; }
     }
-    CbBoxes8 bx8;
-    memset(&bx8, 0, sizeof(bx8));
-    for (int i = 0; i < n_views; ++i) {
-        for (int k = 0; k < 3; ++k) { bx8.b[i].lo[k] = VS.v[i].lo[k]; bx8.b[i].n[k] = VS.v[i].n[k]; }
-        bx8.b[i].off = VS.v[i].off;
-    }
-    hipLaunchKernelGGL(cb_normalize8_runs_kernel, dim3(grid_for((n + kCbRun - 1) / kCbRun)), dim3(256), 0, c->stream, BW, I, bx8, n_views, S);
-    // ---- the valid mask of every view: bounding box + listed voxels; tables of the box under both filters ----
-    hipLaunchKernelGGL(cb_rows_kernel, dim3(rows_grid, n_views), dim3(256), 0, c->stream, I, VS, rows, dpart);
-    hipLaunchKernelGGL(cb_rec_reduce_kernel, dim3(n_views), dim3(256), 0, c->stream, dpart, (int)rows_grid, drecs);
-    hipLaunchKernelGGL(cb_missing_kernel, dim3((unsigned)std::min<long long>((max_rows + 255) / 256, 1024), n_views), dim3(256), 0, c->stream, I, VS, rows, drecs, dmiss,
-                       c->cb_flag_dev);
-    hipLaunchKernelGGL(cb_sort_missing_kernel, dim3(n_views), dim3(kCbMissCap), 0, c->stream, drecs, dmiss);
-    hipLaunchKernelGGL(cb_tables_kernel, dim3(3, n_views, 2), dim3(256), 0, c->stream, VS, drecs, S, ndim, r1, dfw1, r2, dfw2, dtabs);
-    MVS_HIP_TRY(c, hipGetLastError());
-    if (c->cb_mask_count) {      // test / profiling switch: the views' records (how many voxels their masks lack inside the bounding box)
-        std::vector<CbFastRec> hrec((size_t)n_views);
-        MVS_HIP_TRY(c, hipMemcpyAsync(hrec.data(), drecs, (size_t)n_views * sizeof(CbFastRec), hipMemcpyDeviceToHost, c->stream));
-        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (int i = 0; i < n_views; ++i) {
-            c->cb_mask_views += 1;
-            c->cb_mask_boxes += hrec[i].nmiss;      // (fast path: the sum of the list lengths)
-            if (getenv("MVS_CB_DEBUG"))
-                fprintf(stderr, "[cb fast] view box lo %d %d %d n %d %d %d: valid %llu, bbox %d..%d %d..%d %d..%d, listed %d\n", VS.v[i].lo[0], VS.v[i].lo[1],
-                        VS.v[i].lo[2], VS.v[i].n[0], VS.v[i].n[1], VS.v[i].n[2], hrec[i].cnt, hrec[i].lo[0], hrec[i].hi[0], hrec[i].lo[1], hrec[i].hi[1],
-                        hrec[i].lo[2], hrec[i].hi[2], hrec[i].nmiss);
-        }
-    }
+    mvs_launch_boxes_batch(c, &K.dvs[0], K.dviews_dev, K.n_views, K.dtype, K.opts->order, NAN, outs.data(), outs.data() + nv,
+                           (const int64_t (*)[3])shp.data(), (const int (*)[3])b0.data(), K.tr_all ? K.trv.data() : nullptr);
+    K.bx8 = CbBoxes8{};
+    if (K.small) cb_boxes8(K.boxes.data(), K.n_views, &K.bx8);
+    if (K.fast) hipLaunchKernelGGL(cb_normalize8_runs_kernel, dim3(grid_for((K.n + kCbRun - 1) / kCbRun)), dim3(256), 0, c->stream, K.BW, K.I, K.bx8, K.n_views, K.S);
+    else if (K.small) hipLaunchKernelGGL(mask_normalize8_kernel, dim3(grid_for(K.n)), dim3(256), 0, c->stream, K.BW, K.I, K.bx8, K.n_views, K.S, 0);
+    else hipLaunchKernelGGL(mask_normalize_kernel, dim3(grid_for(K.n)), dim3(256), 0, c->stream, K.BW, K.I, K.dboxes, K.n_views, K.S);
+}
 
-    // ---- 2 * ndim line passes, each ONE launch over all views: I -> T0 -> F -> (squared deviation) T0 -> F -> T0 -> F (3D) ----
-    int pass = 0;
-    for (int f = 0; f < 2; ++f)
-        for (int axis = 3 - ndim; axis < 3; ++axis, ++pass) {
-            // accumulators (option cb_taps_f64): 1 (default) = float64 for both filters, 0 = float32 for both, 2 / 3 = float64 for the
-            // first / second filter only.  C3 at size, one-count flips of the fused uint16 voxels against the oracle (all of them at
-            // truncation boundaries, none beyond the 1e-4 bar): 0.04 % (1; the bit-faithful passes: 0.04 %), 0.10 % (3), 0.21 % (2),
-            // 0.22 % (0) -- the noise of float32 taps enters through the second filter, whose result IS the weight; the probe takes
-            // 11.8 ms with 0 and 12.4 ms with 1 (the passes are bound by memory and latency, not by the taps)
-            const bool f64 = c->cb_taps == 1 || (c->cb_taps == 2 && f == 0) || (c->cb_taps == 3 && f == 1);
-            const bool firstp = axis == 3 - ndim, lastp = axis == 2;
-            CbLineArgs A;
-            A.src = (pass == 0) ? I : ((pass & 1) ? T0 : F);
-            A.dst = (pass & 1) ? F : T0;
-            A.I = I;
-            A.axis = axis; A.radius = f ? r2 : r1; A.ndim = ndim; A.filt = f;
-            A.S = S;
-            A.fwf = f ? ffw2 : ffw1; A.fwd = f ? dfw2 : dfw1;
-            A.tabs = dtabs; A.recs = drecs; A.miss = dmiss; A.dbg = dbg;
-            CbFastViews B = VS;
-            int nb = 0;
-            size_t lds = 0;
-            for (int i = 0; i < n_views; ++i) {
-                CbFastView& V = B.v[i];
-                V.T = Tsel[axis][f][i];
-                V.blk0 = nb;
-                V.zr0 = 0; V.nzr = V.n[0]; V.yr0 = 0; V.nyr = V.n[1];
-                long long bn = (long long)V.n[0] * V.n[1] * V.n[2];
-                // the weight F of a view is read on the TRIMMED chunk only: a view that does not reach it (a sliver of a neighbour in the
-                // halo) is not filtered at all, and the last pass works on the rows inside it
-                int tl[3], th[3];
-                bool reaches = bn > 0;
-                for (int k = 0; k < 3; ++k) {
-                    tl[k] = std::max(V.lo[k], (int)opts->trim[k]) - V.lo[k];
-                    th[k] = std::min(V.lo[k] + V.n[k], (int)(cs[k] - opts->trim[k])) - V.lo[k];
-                    if (th[k] <= tl[k]) reaches = false;
-                }
-                if (!reaches) { V.nzr = V.nyr = 0; continue; }
-                if (lastp && f == 1) {
-                    V.zr0 = tl[0]; V.nzr = th[0] - tl[0]; V.yr0 = tl[1]; V.nyr = th[1] - tl[1];
-                    bn = (long long)V.nzr * V.nyr * V.n[2];
-                }
-                const long long n_lines = bn / V.n[axis];
-                nb += (int)((n_lines + V.T - 1) / V.T);
-                lds = std::max(lds, cb_fast_lds(V.n[axis], A.radius, V.T, axis == 2));
-            }
-            if (nb == 0) continue;
-            const int src = (pass == 0) ? CBS_NAN0 : CBS_PLAIN;
-            const int dst = lastp ? (f ? CBD_F : CBD_SQ) : CBD_PLAIN;
-            (void)firstp;
-#define MVS_CBL(S_, D_, PF_) do { if (f64) hipLaunchKernelGGL((cb_line_kernel<S_, D_, double, PF_>), dim3(nb), dim3(256), lds, c->stream, A, B); \
-                                  else hipLaunchKernelGGL((cb_line_kernel<S_, D_, float, PF_>), dim3(nb), dim3(256), lds, c->stream, A, B); } while (0)
-            if (!lastp) { if (src == CBS_NAN0) MVS_CBL(CBS_NAN0, CBD_PLAIN, false); else MVS_CBL(CBS_PLAIN, CBD_PLAIN, false); }
-            else if (dst == CBD_SQ) MVS_CBL(CBS_PLAIN, CBD_SQ, true);
-            else MVS_CBL(CBS_PLAIN, CBD_F, true);
-#undef MVS_CBL
-            c->cb_line_launches += 1;
-        }
-    MVS_HIP_TRY(c, hipGetLastError());
-
-    const size_t out_bytes = (size_t)no * es;
-    void* dout = out;
-    if (opts->out_mem == MVS_MEM_HOST) {
-        dout = mvs_scratch(c, 1, out_bytes);
-        if (!dout) return mvs_alloc_failed(c);
+// Test / profiling switch cb_mask_count: read the views' mask records back.  exact: count the views whose mask was found to be a box;
+// fast: sum the list lengths (how many voxels the masks lack inside their bounding boxes).  MVS_CB_DEBUG=1 prints every record.
+int cb_mask_report(CbCall& K) {
+    MvsContext* c = K.c;
+    std::vector<char> hrec((size_t)K.n_views * K.rec_bytes);
+    MVS_HIP_TRY(c, hipMemcpyAsync(hrec.data(), K.drecs, hrec.size(), hipMemcpyDeviceToHost, c->stream));
+    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < K.n_views; ++i) {
+        CbFastRec r = CbFastRec();
+        memcpy(&r, hrec.data() + (size_t)i * K.rec_bytes, K.rec_bytes);
+        const unsigned long long vol = r.cnt ? (unsigned long long)(r.hi[0] - r.lo[0] + 1) * (unsigned long long)(r.hi[1] - r.lo[1] + 1) *
+                                               (unsigned long long)(r.hi[2] - r.lo[2] + 1) : 0ull;
+        c->cb_mask_views += 1;
+        c->cb_mask_boxes += K.fast ? r.nmiss : ((r.cnt && vol == r.cnt) ? 1 : 0);
+        if (!getenv("MVS_CB_DEBUG")) continue;
+        const CbBox& B = K.boxes[(size_t)i];
+        fprintf(stderr, "[cb %s] view box lo %d %d %d n %d %d %d: valid %llu, bbox %d..%d %d..%d %d..%d", K.fast ? "fast" : "mask", B.lo[0], B.lo[1], B.lo[2],
+                B.n[0], B.n[1], B.n[2], r.cnt, r.lo[0], r.hi[0], r.lo[1], r.hi[1], r.lo[2], r.hi[2]);
+        if (K.fast) fprintf(stderr, ", listed %d\n", r.nmiss);
+        else fprintf(stderr, " (volume %llu)\n", vol);
     }
-    const int gbo = grid_for((no + kCbRun - 1) / kCbRun);
-    const int tz = (int)opts->trim[0], ty = (int)opts->trim[1], tx = (int)opts->trim[2];
-    mvs_dispatch_dtype(dtype, [&](auto tag) {
+    return MVS_OK;
+}
+
+// normalise F over views, A = bw * Fn, normalise A, out = sum I * A; trimmed, cast.  ev_stop closes the call's timing behind the fuse kernel.  A host
+// result is copied back and waited for; a device result is not waited for unless host slabs were staged through scratch the next call may overwrite.
+int cb_epilogue(CbCall& K) {
+    MvsContext* c = K.c;
+    const size_t out_bytes = (size_t)K.no * K.es;
+    const bool to_host = K.opts->out_mem == MVS_MEM_HOST;
+    void* dout = K.out;
+    if (to_host && !(dout = mvs_scratch(c, 1, out_bytes))) return mvs_alloc_failed(c);
+    const int tz = (int)K.opts->trim[0], ty = (int)K.opts->trim[1], tx = (int)K.opts->trim[2];
+    mvs_dispatch_dtype(K.dtype, [&](auto tag) {
         using T = decltype(tag);
-        hipLaunchKernelGGL(cb_fuse8_runs_kernel<T>, dim3(gbo), dim3(256), 0, c->stream, I, BW, F, bx8, n_views, tz, ty, tx, O, (T*)dout);
+        if (K.fast)
+            hipLaunchKernelGGL(cb_fuse8_runs_kernel<T>, dim3(grid_for((K.no + kCbRun - 1) / kCbRun)), dim3(256), 0, c->stream, K.I, K.BW, K.F, K.bx8, K.n_views, tz, ty, tx,
+                               K.O, (T*)dout);
+        else if (K.small)
+            hipLaunchKernelGGL(cb_fuse8_kernel<T>, dim3(grid_for(K.no)), dim3(256), 0, c->stream, K.I, K.BW, K.F, K.bx8, K.n_views, tz, ty, tx, K.O, (T*)dout);
+        else
+            hipLaunchKernelGGL(cb_fuse_kernel<T>, dim3(grid_for(K.no)), dim3(256), 0, c->stream, K.I, K.BW, K.F, K.dboxes, K.n_views, tz, ty, tx, K.O, (T*)dout);
     });
     MVS_HIP_TRY(c, hipGetLastError());
     MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
     c->timing_valid = true;
-    *taken = true;
-    if (opts->out_mem == MVS_MEM_HOST) {
-        MVS_HIP_TRY(c, hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
-        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (*c->cb_flag_host) {      // a mask list overflowed: this chunk again, through the bit-faithful passes (the caller falls through)
-            *c->cb_flag_host = 0;
-            c->cb_overflows += 1;
-            *taken = false;
+    if (to_host) MVS_HIP_TRY(c, hipMemcpyAsync(K.out, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (to_host || K.host_bytes) MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MVS_OK;
+}
+
+// Scratch slot 6 (layout: cb_layout): the pools, the uploaded block and what follows it, as pointers
+int cb_scratch(CbCall& K) {
+    const size_t n_taps = K.w1.size() + K.w2.size();
+    const CbLayout Y = cb_layout(K.fast, K.pool, K.n_views, K.paired, n_taps, sizeof(DevView), K.table_floats);
+    char* base = (char*)mvs_scratch(K.c, 6, Y.need);
+    if (!base) return mvs_alloc_failed(K.c);
+    if (!K.fast && n_taps * 8 > 32 * 1024) return mvs_fail(K.c, MVS_ERR_UNSUPPORTED, "content_based: sigma too large");
+    auto at = [&](int section) { return base + Y.off[section]; };
+    K.I = (float*)at(CS_I); K.BW = (float*)at(CS_BW); K.F = (float*)at(CS_F); K.tmp = (float*)at(CS_TMP); K.tmp_b = Y.tmp_b;
+    K.dblock = at(CS_UP0); K.up_bytes = Y.off[CS_UP1] - Y.off[CS_UP0];
+    K.dfw1 = (double*)at(CS_TAPS64); K.dfw2 = K.dfw1 + K.w1.size(); K.ffw1 = (float*)at(CS_TAPS32); K.ffw2 = K.ffw1 + K.w1.size();
+    K.dboxes = (CbBox*)at(CS_BOXES); K.dviews_dev = (DevView*)at(CS_VIEWS);      // (the views' records for the batched box launches)
+    K.drecs = at(CS_RECS); K.rec_bytes = K.fast ? sizeof(CbFastRec) : sizeof(CbMaskRec);
+    K.dtable_off = (long long*)at(CS_TOFF); K.dtables = (float*)at(CS_TABLES); K.dtabs = (double*)at(CS_TABLES);
+    K.rows = (int4*)at(CS_ROWS); K.dmiss = (int4*)at(CS_MISS); K.dpart = (CbPartial*)at(CS_PART);
+    return MVS_OK;
+}
+
+// ---- steps of the exact path ----
+// which passes the chunk takes and where the mask tables B(z, y) of every (view, filter) lie
+void cb_exact_plan(CbCall& K) {
+    K.paired = cb_paired(K.boxes.data(), K.n_views, K.ndim, K.r1, K.r2, K.c->cb_unpaired);
+    K.small = cb_small(K.n_views, K.pool.floats);
+    K.mask_tables = cb_mask_tables(K.paired, K.n_views, K.pool.floats, K.c->cb_mask_closed_form);
+    K.table_off.assign((size_t)K.n_views * 2, 0); K.table_floats = 0;
+    for (int i = 0; i < K.n_views * 2 && K.mask_tables; ++i) {
+        K.table_off[(size_t)i] = K.table_floats;
+        K.table_floats += ((long long)K.boxes[i / 2].n[0] * K.boxes[i / 2].n[1] + 63) / 64 * 64;
+    }
+}
+
+// is every view's valid mask a box?  (device-side: record + tables, no host round trip)
+void cb_exact_mask_tables(CbCall& K) {
+    int max_nz = 1;
+    for (const CbBox& B : K.boxes) max_nz = std::max(max_nz, B.n[0]);
+    hipLaunchKernelGGL(cb_mask_bbox_kernel, dim3((unsigned)std::min<long long>((K.pool.max_box + 2047) / 2048, 512), K.n_views), dim3(256), 0, K.c->stream,
+                       K.I, K.BW, K.bx8, (CbMaskRec*)K.drecs);
+    hipLaunchKernelGGL(cb_mask_table_kernel, dim3(max_nz, K.n_views, 2), dim3(256), 0, K.c->stream, (const CbMaskRec*)K.drecs, K.bx8, K.S, K.ndim, K.r1, K.dfw1,
+                       K.r2, K.dfw2, K.dtables, K.dtable_off);
+}
+
+// the instantiations of gauss1d_pair_kernel the schedule reaches, [split][src][dst] (a split pass hands both quantities on: DST_AB only)
+#define MVS_PAIR(S_, D_, SP_) gauss1d_pair_kernel<S_, D_, SP_>
+void (*const kPairKernels[2][3][3])(PairIO, GaussLines, int, const double*, int) = {
+    {{MVS_PAIR(SRC_AB, DST_AB, false), MVS_PAIR(SRC_AB, DST_SQ, false), MVS_PAIR(SRC_AB, DST_F, false)},
+     {MVS_PAIR(SRC_PREP, DST_AB, false), MVS_PAIR(SRC_PREP, DST_SQ, false), nullptr},
+     {MVS_PAIR(SRC_VMASK, DST_AB, false), nullptr, MVS_PAIR(SRC_VMASK, DST_F, false)}},
+    {{MVS_PAIR(SRC_AB, DST_AB, true), nullptr, nullptr}, {MVS_PAIR(SRC_PREP, DST_AB, true), nullptr, nullptr}, {MVS_PAIR(SRC_VMASK, DST_AB, true), nullptr, nullptr}}};
+#undef MVS_PAIR
+
+// paired passes (gauss1d_pair_kernel; schedule: cb_pair_schedule): per view 2 x ndim launches, one view after the other on the
+// context's stream -- consecutive chunks overlap on ONE stream by themselves (docs/DESIGN_history.md: the forked form)
+int cb_exact_paired_passes(CbCall& K) {
+    float* t[5];      // 5 temporaries of the largest box, shared by the views
+    for (int k = 0; k < 5; ++k) t[k] = (float*)((char*)K.tmp + (size_t)k * K.tmp_b);
+    for (int v = 0; v < K.n_views; ++v) {
+        const CbBox& B = K.boxes[v];
+        if ((long long)B.n[0] * B.n[1] * B.n[2] == 0) continue;
+        auto buf = [&](int b) -> float* { return b == kCbBufF ? K.F + B.off : (b >= 0 && b < 5) ? t[b] : nullptr; };
+        CbPairPass passes[6];
+        const int np = cb_pair_schedule(K.ndim, B.n, K.r1, K.r2, K.c->cb_nosplit, passes);
+        for (int i = 0; i < np; ++i) {
+            const CbPairPass& p = passes[i];
+            const int f = p.filt, radius = f ? K.r2 : K.r1, pf = p.axis == 2 ? 1 : 0;
+            const double* fw = f ? K.dfw2 : K.dfw1;
+            PairIO P;
+            P.im = K.I + B.off; P.bw = K.BW + B.off; P.src = p.src; P.dst = p.dst;
+            P.a = buf(p.in_a); P.b = buf(p.in_b); P.oa = buf(p.out_a); P.ob = buf(p.out_b);
+            P.rec = K.mask_tables ? (const CbMaskRec*)K.drecs + v : nullptr;
+            P.mtab = K.mask_tables ? K.dtables + K.table_off[(size_t)v * 2 + f] : nullptr;
+            GaussLines L = cb_lines(B.n, B.lo, K.cs, p.axis);
+            L.T = p.T;
+            const dim3 g((unsigned)((L.n_lines + L.T - 1) / L.T), p.split ? 2 : 1), b(256);
+            hipLaunchKernelGGL(kPairKernels[p.split ? 1 : 0][p.src][p.dst], g, b, p.lds, K.c->stream, P, L, radius, fw, pf);
         }
-    } else if (host_bytes) {
-        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));      // host slabs were staged through scratch that the next call may overwrite
+    }
+    MVS_HIP_TRY(K.c, hipGetLastError());
+    return MVS_OK;
+}
+
+// one Gaussian of one array of a box (separate passes): LDS-staged lines when a useful tile of them fits, else the tap-by-tap kernel
+void cb_gauss_separate(CbCall& K, const float* src, float* dst, const CbBox& B, int radius, const double* fw) {
+    const Shape3 Sb = {B.n[0], B.n[1], B.n[2]};
+    const int gbb = grid_for((long long)B.n[0] * B.n[1] * B.n[2]);
+    float* const tmp[2] = {(float*)((char*)K.tmp + 4 * K.tmp_b), (float*)((char*)K.tmp + 5 * K.tmp_b)};      // T1, T2
+    const float* cur = src;
+    for (int axis = 3 - K.ndim, pass = 0; axis < 3; ++axis, ++pass) {
+        float* d = (axis == 2) ? dst : tmp[pass & 1];
+        GaussLines L = cb_lines(B.n, B.lo, K.cs, axis);
+        L.T = cb_single_T(L.len, radius, axis);
+        if (L.T)
+            hipLaunchKernelGGL(gauss1d_lds_kernel, dim3((unsigned)((L.n_lines + L.T - 1) / L.T)), dim3(256), cb_single_lds(L.len, radius, L.T), K.c->stream, cur, d, L,
+                               radius, fw, axis == 2 ? 1 : 0);
+        else hipLaunchKernelGGL(gauss1d_kernel, dim3(gbb), dim3(256), 0, K.c->stream, cur, d, Sb, axis, radius, fw, L.b0, L.full);
+        cur = d;
+    }
+}
+
+// separate value / mask passes (option cb_unpaired, or a line no paired tile fits): temporaries A, V0, M, T0 (+ T1, T2 of cb_gauss_separate)
+void cb_exact_separate_passes(CbCall& K) {
+    float *A = K.tmp, *V0 = (float*)((char*)A + K.tmp_b), *M = (float*)((char*)A + 2 * K.tmp_b), *T0 = (float*)((char*)A + 3 * K.tmp_b);
+    for (int v = 0; v < K.n_views; ++v) {
+        const CbBox& B = K.boxes[v];
+        const long long bn = (long long)B.n[0] * B.n[1] * B.n[2];
+        if (bn == 0) continue;
+        const int gbb = grid_for(bn);
+        float* Fv = K.F + B.off;
+        hipLaunchKernelGGL(prep_kernel, dim3(gbb), dim3(256), 0, K.c->stream, K.I + B.off, K.BW + B.off, bn, A, V0, M);
+        cb_gauss_separate(K, V0, T0, B, K.r1, K.dfw1);           // VV  (T0)
+        cb_gauss_separate(K, M, Fv, B, K.r1, K.dfw1);            // WW  (Fv used as temporary)
+        hipLaunchKernelGGL(ng_finish_sq_kernel, dim3(gbb), dim3(256), 0, K.c->stream, T0, Fv, A, bn, V0);   // V0 <- (A - Z)^2, NaN -> 0
+        cb_gauss_separate(K, V0, T0, B, K.r2, K.dfw2);           // VV2 (T0)
+        cb_gauss_separate(K, M, V0, B, K.r2, K.dfw2);            // WW2 (V0)
+        hipLaunchKernelGGL(ng_finish_kernel, dim3(gbb), dim3(256), 0, K.c->stream, T0, V0, A, bn, Fv);
+    }
+}
+
+int cb_exact_path(CbCall& K) {
+    int rc = cb_geometry(K, false);
+    if (!rc) rc = cb_stage_views(K);
+    if (!rc) { cb_exact_plan(K); rc = cb_scratch(K); }
+    if (!rc) rc = cb_upload_block(K);
+    if (rc) return rc;
+    cb_resample_blend_normalize(K);
+    if (K.mask_tables) {
+        cb_exact_mask_tables(K);
+        if (K.c->cb_mask_count) { rc = cb_mask_report(K); if (rc) return rc; }
+    }
+    if (K.paired) { rc = cb_exact_paired_passes(K); if (rc) return rc; }
+    else cb_exact_separate_passes(K);
+    MVS_HIP_TRY(K.c, hipGetLastError());
+    return cb_epilogue(K);
+}
+
+// ---- steps of the fast path (kernels: mvs_gauss_fast.inc) ----
+// the valid mask of every view: bounding box + listed voxels (sorted); tables of the box under both filters
+int cb_fast_mask_scan(CbCall& K) {
+    MvsContext* c = K.c;
+    CbFastRec* drecs = (CbFastRec*)K.drecs;
+    hipLaunchKernelGGL(cb_rows_kernel, dim3(K.rows_grid, K.n_views), dim3(256), 0, c->stream, K.I, K.VS, K.rows, K.dpart);
+    hipLaunchKernelGGL(cb_rec_reduce_kernel, dim3(K.n_views), dim3(256), 0, c->stream, K.dpart, (int)K.rows_grid, drecs);
+    hipLaunchKernelGGL(cb_missing_kernel, dim3((unsigned)std::min<long long>((K.pool.max_rows + 255) / 256, 1024), K.n_views), dim3(256), 0, c->stream, K.I, K.VS, K.rows,
+                       drecs, K.dmiss, c->cb_flag_dev);
+    hipLaunchKernelGGL(cb_sort_missing_kernel, dim3(K.n_views), dim3(kCbMissCap), 0, c->stream, drecs, K.dmiss);
+    hipLaunchKernelGGL(cb_tables_kernel, dim3(3, K.n_views, 2), dim3(256), 0, c->stream, K.VS, drecs, K.S, K.ndim, K.r1, K.dfw1, K.r2, K.dfw2, K.dtabs);
+    MVS_HIP_TRY(c, hipGetLastError());
+    return MVS_OK;
+}
+
+// 2 * ndim line passes, each ONE launch over all views (schedule: cb_fast_schedule)
+int cb_fast_line_passes(CbCall& K) {
+    MvsContext* c = K.c;
+    CbFastPass passes[6];
+    const int np = cb_fast_schedule(K.VS, K.ndim, K.cs, K.opts->trim, K.r1, K.r2, K.Tsel, passes);
+    float* const pools[3] = {K.I, K.tmp, K.F};      // kCbBufI, kCbBufT0, kCbBufFast
+    for (int i = 0; i < np; ++i) {
+        const CbFastPass& p = passes[i];
+        if (p.nb == 0) continue;
+        const int f = p.filt;
+        // accumulators (option cb_taps_f64): 1 (default) = float64 for both filters, 0 = float32 for both, 2 / 3 = float64 for the first / second
+        // filter only.  C3 at size, one-count flips of the fused uint16 voxels against the oracle (all of them at truncation boundaries, none
+        // beyond the 1e-4 bar): 0.04 % (1; the bit-faithful passes: 0.04 %), 0.10 % (3), 0.21 % (2), 0.22 % (0) -- the noise of float32 taps
+        // enters through the second filter, whose result IS the weight; the probe takes 11.8 ms with 0 and 12.4 ms with 1 (memory and latency)
+        const bool f64 = c->cb_taps == 1 || (c->cb_taps == 2 && f == 0) || (c->cb_taps == 3 && f == 1);
+        CbLineArgs A;
+        A.src = pools[p.src_buf]; A.dst = pools[p.dst_buf]; A.I = K.I; A.S = K.S;
+        A.axis = p.axis; A.radius = p.radius; A.ndim = K.ndim; A.filt = f;
+        A.fwf = f ? K.ffw2 : K.ffw1; A.fwd = f ? K.dfw2 : K.dfw1; A.tabs = K.dtabs; A.recs = (const CbFastRec*)K.drecs; A.miss = K.dmiss;
+#define MVS_CBL(S_, D_, PF_) do { if (f64) hipLaunchKernelGGL((cb_line_kernel<S_, D_, double, PF_>), dim3(p.nb), dim3(256), p.lds, c->stream, A, p.views); \
+                                  else hipLaunchKernelGGL((cb_line_kernel<S_, D_, float, PF_>), dim3(p.nb), dim3(256), p.lds, c->stream, A, p.views); } while (0)
+        if (p.dst == CBD_PLAIN) { if (p.src == CBS_NAN0) MVS_CBL(CBS_NAN0, CBD_PLAIN, false); else MVS_CBL(CBS_PLAIN, CBD_PLAIN, false); }
+        else if (p.dst == CBD_SQ) MVS_CBL(CBS_PLAIN, CBD_SQ, true);
+        else MVS_CBL(CBS_PLAIN, CBD_F, true);
+#undef MVS_CBL
+        c->cb_line_launches += 1;
+    }
+    MVS_HIP_TRY(c, hipGetLastError());
+    return MVS_OK;
+}
+
+// The default path: mask from a box + list, one quantity per pass, all views in one launch.  *taken = false: this chunk is not its kind
+// (cb_fast_accepts_chunk / _boxes: more than 8 views, a rotated / scaled view, a chunk axis shorter than a filter radius, a line that
+// does not fit LDS) and the caller runs the bit-faithful passes.  It declines BEFORE any side effect: no scratch is taken, no upload is
+// queued, ev_start is not recorded.
+int cb_fast_path(CbCall& K, bool* taken) {
+    MvsContext* c = K.c;
+    *taken = false;
+    bool identity = true;
+    for (int i = 0; i < K.n_views && identity; ++i) identity = cb_is_identity(K.views[i].matrix);
+    if (cb_fast_accepts_chunk(K.n_views, K.ndim, K.cs, K.r1, K.r2, identity) != kCbTaken) return MVS_OK;
+    int rc = cb_geometry(K, true);
+    if (rc || cb_fast_accepts_boxes(K.pool, K.boxes.data(), K.n_views, K.ndim, K.r1, K.r2, K.Tsel) != kCbTaken) return rc;
+    K.small = true; K.paired = false; K.table_floats = 0; K.rows_grid = cb_rows_grid(K.pool.max_rows);
+    rc = cb_stage_views(K);
+    if (!rc) rc = cb_scratch(K);
+    if (!rc) rc = cb_upload_block(K);
+    if (rc) return rc;
+    cb_resample_blend_normalize(K);
+    rc = cb_fast_mask_scan(K);
+    if (!rc && c->cb_mask_count) rc = cb_mask_report(K);
+    if (!rc) rc = cb_fast_line_passes(K);
+    if (!rc) rc = cb_epilogue(K);
+    if (rc) return rc;
+    *taken = true;
+    // A mask list that overflowed raised the flag.  A host result has been waited for: the flag is read here and the caller redoes this
+    // chunk through the bit-faithful passes.  A device result is not waited for: the Python side checks the flag (counter cb_overflow).
+    if (K.opts->out_mem == MVS_MEM_HOST && *c->cb_flag_host) {
+        *c->cb_flag_host = 0; c->cb_overflows += 1; *taken = false;
     }
     return MVS_OK;
+}
+
+}  // namespace
+
+int mvs_fuse_content_based(MvsContext* c, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out) {
+    if (opts->order != 0 && opts->order != 1) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "content_based: order 0|1 only");
+    CbCall K;
+    cb_begin(K, c, views, n_views, opts, out);
+    if (!c->cb_exact) {
+        bool taken = false;
+        const int rc = cb_fast_path(K, &taken);
+        if (rc || taken) return rc;
+    }
+    return cb_exact_path(K);
 }

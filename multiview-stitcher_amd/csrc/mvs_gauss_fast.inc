@@ -20,14 +20,8 @@
 //
 // Reference: weights.py:22-74 (content_based), :293-322 (nan_gaussian_filter), :325-345 (normalize_weights); fusion/_core.py:1199-1220.
 
-constexpr int kCbNearCap = 256;       // listed voxels one workgroup of a last pass handles in its compact form
-constexpr int kCbMissCap = 512;       // listed voxels per view; more -> flag, exact path
 struct CbFastRec { unsigned long long cnt; int lo[3]; int hi[3]; int nmiss; int pad[7]; };      // lo / hi: box-local bounding box of the valid voxels
 static_assert(sizeof(CbFastRec) == 64, "CbFastRec layout");
-// zr0 / nzr / yr0 / nyr: the rows (z, y) of the box a pass along x works on (the last pass of the second filter: only the rows
-// inside the trimmed chunk are ever read); nzr == 0: the view takes no part in the launch
-struct CbFastView { int off; int n[3]; int lo[3]; int row0; int tab0; int T; int blk0; int zr0, nzr, yr0, nyr; };
-struct CbFastViews { CbFastView v[8]; int nv; };
 
 // ---- valid voxels per row (one wavefront per group of 4 rows, their loads in flight together), per-workgroup partial records of
 // the view's count and bounding box (no atomics: a few thousand of them on one cache line cost more than the scan itself);
@@ -237,10 +231,8 @@ __device__ __forceinline__ float cb_axis_weight_lds(int p, int s, int b0, int fu
     w += (a2 <= radius) ? sfw[radius - min(a2, radius)] : 0.f;
     return w;
 }
-constexpr int kCbMaxRadius = 127;     // radii of the fast path (sigma <= 31): the weights of a last pass sit in static LDS
 
 // ---- the line filter of ONE quantity, all views of the chunk in one launch ----
-enum { CBS_PLAIN = 0, CBS_NAN0 = 1, CBD_PLAIN = 0, CBD_SQ = 1, CBD_F = 2 };
 typedef float cb_f4u_t __attribute__((ext_vector_type(4), aligned(4)));      // 16-byte access at 4-byte alignment (rows of odd length)
 struct CbLineArgs {
     const float* src; float* dst; const float* I;      // pools (a view's box at + off)
@@ -248,7 +240,6 @@ struct CbLineArgs {
     Shape3 S;                                          // the chunk (reflection)
     const float* fwf; const double* fwd;               // the filter's 2 radius + 1 weights
     const double* tabs; const CbFastRec* recs; const int4* miss;
-    int dbg;      // profiling builds: bit 0 = ignore the listed voxels
 };
 #ifndef MVS_CBF_PREFETCH
 #define MVS_CBF_PREFETCH 1      // the view's 8 samples of the last pass are requested before the taps, not after them
@@ -259,14 +250,6 @@ struct CbLineArgs {
 #ifndef MVS_CBF_NB
 #define MVS_CBF_NB 8
 #endif
-
-// LDS layouts.  Lines along z / y (PF = false): [position][line], pitch T + 1 -- a wavefront's lanes are adjacent LINES (adjacent x in
-// memory), staging, filter reads and stores are all conflict-free / coalesced.  Lines along x (PF = true): a wavefront's lanes must
-// be adjacent 8-sample BLOCKS of one line, or every 32-byte piece of the pass's global reads and writes lands in another row; their
-// window samples are 8 positions apart, so a line is stored de-interleaved by 8 -- position p at (p & 7) * S8 + (p >> 3), S8 = 4 mod 8
-// -- which makes both the staging (lanes = consecutive positions) and the filter reads (lanes = consecutive blocks) conflict-free.
-__host__ __device__ __forceinline__ int cb_pf_S8(int rows) { int s = (rows + 7) / 8 + 1; s += (12 - (s & 7)) & 7; return s; }      // rows = len + 2 radius + K
-__host__ __device__ __forceinline__ int cb_pf_LP(int rows) { return 8 * cb_pf_S8(rows) + 11; }
 
 template <int SRC, int DST, typename ACC, bool PF>
 __global__ __launch_bounds__(256) void cb_line_kernel(CbLineArgs A, CbFastViews B) {
@@ -354,7 +337,7 @@ __global__ __launch_bounds__(256) void cb_line_kernel(CbLineArgs A, CbFastViews 
         }
     }
     if constexpr (DST != CBD_PLAIN) {
-        nm = (A.dbg & 1) ? 0 : min(nm, kCbMissCap);
+        nm = min(nm, kCbMissCap);
         if (nm > 0) {
             const int ra = (int)(l0 / V.nyr), rb = (int)((l0 + nl - 1) / V.nyr);
             const int za = V.zr0 + ra, zb = V.zr0 + rb;
@@ -388,7 +371,6 @@ __global__ __launch_bounds__(256) void cb_line_kernel(CbLineArgs A, CbFastViews 
                 int tot = 0;
                 for (int wd = 0; wd < nw; ++wd) tot += __popc(s_nearmask[wd]);
                 s_nn = (tot > kCbNear || (len + K - 1) / K > kCbBlkMax) ? kCbNear + 1 : tot;
-                if (A.dbg & 4) s_nn = 0;
             }
             if (threadIdx.x < 32 * NW) s_lmask[threadIdx.x] = 0ull;
             for (int i = threadIdx.x; i < ((len + K - 1) / K) * NW && i < kCbBlkMax * NW; i += blockDim.x) s_emask[i] = 0ull;
@@ -526,7 +508,7 @@ __global__ __launch_bounds__(256) void cb_line_kernel(CbLineArgs A, CbFastViews 
             float corr[K];      // (the bumps are <= 1e-2 of WW: their float32 sum is exact to 1e-9 of it)
 #pragma unroll
             for (int k = 0; k < K; ++k) corr[k] = 0.f;
-            const int nn = (A.dbg & 2) ? 0 : s_nn;
+            const int nn = s_nn;
             if (nn > 0 && nn <= kCbNear) {
                 for (int half = 0; half < NW; ++half) {
                 unsigned long long bits = s_lmask[line * NW + half] & s_emask[blk * NW + half];
@@ -603,7 +585,6 @@ __global__ __launch_bounds__(256) void cb_line_kernel(CbLineArgs A, CbFastViews 
 
 // ---- mask_normalize8_kernel / cb_fuse8_kernel of the exact path spend their time testing 8 boxes per voxel (~150 instructions for 12
 // bytes); here a thread owns R consecutive voxels of a row: the z / y tests and the row's index are worked out once per view and run ----
-constexpr int kCbRun = 4;
 __global__ __launch_bounds__(256) void cb_normalize8_runs_kernel(float* __restrict__ bw, float* __restrict__ im, CbBoxes8 BX, int nviews, Shape3 S) {
     const int runs_x = (S.nx + kCbRun - 1) / kCbRun;
     const long long nruns = (long long)S.nz * S.ny * runs_x;
@@ -725,25 +706,4 @@ __global__ __launch_bounds__(256) void cb_fuse8_runs_kernel(const float* __restr
                 out[o + r] = cast_cb<TOut>(q);
             }
     }
-}
-
-// lines per workgroup of a pass over lines of `len` samples: the power of two (from `lo` to `hi`) that leaves the fewest idle thread
-// slots in the filter loop (T * ceil(len / K) items on 256 threads) and fits the LDS budget; ties go to the larger T
-static size_t cb_fast_lds(int len, int radius, int T, bool pf) {
-    const int rows = len + 2 * radius + kGaussK;
-    return pf ? (size_t)T * cb_pf_LP(rows) * 4 + (size_t)kCbNearCap * T * 4 : (size_t)rows * (T + 1) * 4;
-}
-static int cb_fast_T(int len, int radius, int lo, int hi, bool pf) {
-    const int nblk = (len + kGaussK - 1) / kGaussK;
-    int best = 0;
-    double best_eff = -1.0;
-    for (int T = lo; T <= hi; T <<= 1) {
-        if (cb_fast_lds(len, radius, T, pf) > 60 * 1024) break;
-        const int items = T * nblk;
-        const double eff = (double)items / (double)(((items + 255) / 256) * 256);
-        // ties: lines along z / y take the larger T (longer contiguous pieces per row), lines along x the smaller one (less LDS per
-        // workgroup, more of them per CU: 16.4 -> 13.5 ms per probe call)
-        if (pf ? eff > best_eff + 1e-9 : eff >= best_eff - 1e-9) { best_eff = eff; best = T; }
-    }
-    return best;
 }

@@ -445,6 +445,36 @@ def test_content_based_fast_path_against_oracle_and_exact_passes(hip_device, cas
             _assert_cb_float_close(got[ok], ref[ok])
 
 
+@pytest.mark.parametrize("case", ["nine_views", "long_x"])
+def test_content_based_fallback_branches_against_oracle(hip_device, case, kernel_path):
+    """Two branches of the content-based steps that no tile-grid case above reaches, each one chunk against the oracle at the bar
+    of ``test_fuse_content_based_weights``.  ``nine_views``: a 3 x 3 grid seen whole -- more than 8 views, so the fast path
+    declines, the boxes do not travel as a kernel argument and ``mask_normalize_kernel`` / ``cb_fuse_kernel`` run.  ``long_x``:
+    x lines of 8200 samples, longer than any LDS tile holds (7680 - 2 r) -- no path stages them, the passes are the separate
+    ones without any option set and the x pass is the tap-by-tap ``gauss1d_kernel``."""
+    from multiview_stitcher_amd import _lib, fusion, spatial_image_utils as si
+
+    if kernel_path != "fast":
+        pytest.skip("content-based weights have a single implementation")
+    if case == "nine_views":
+        sims, params = _grid_case(2, np.float32, (3, 3), (40, 44), (12, 14), True, seed=51)
+    else:
+        sims, params = _grid_case(2, np.float32, (2, 1), (40, 8200), (12, 0), True, seed=52)
+    sig, halo = {"sigma_1": 2.0, "sigma_2": 4.0}, 8
+    sdims = si.get_spatial_dims_from_sim(sims[0])
+    views, bbs = zip(*[sim_to_view(s) for s in sims])
+    out_bb = union_bb(bbs, params, np.ones(2))
+    want = fo.fuse_np(list(views), params, out_bb, full_view_bbs=list(bbs), weights="content_based", weights_kwargs=sig,
+                      trim_overlap_in_pixels=halo)
+    _lib.get_counter("cb_line_launches", reset=True)
+    got = fusion.fuse_np(list(sims), params, bb_to_dicts(out_bb, sdims), weights_func=fusion.content_based,
+                         weights_func_kwargs=sig, full_view_bbs=[bb_to_dicts(b, sdims) for b in bbs],
+                         trim_overlap_in_pixels=halo)
+    assert _lib.get_counter("cb_line_launches", reset=True) == 0      # the fast path declined the chunk
+    assert got.shape == want.shape and len(sims) == (9 if case == "nine_views" else 2)
+    _assert_cb_float_close(got, want)
+
+
 def test_fuse_content_based_chunked_workflow(hip_device, kernel_path):
     """fusion.fuse(weights_func=content_based): halo = 2*sigma_2 from required_overlap, chunks trimmed (T/test_fusion.py:845-896)."""
     from multiview_stitcher_amd import fusion, sample_data
