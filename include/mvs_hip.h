@@ -688,6 +688,35 @@ int mvs_marker_descriptors(int device, const double* points, int32_t points_mem,
 int mvs_marker_score(int device, const double* affines, int32_t n_hypotheses, const double* fixed, const double* moving,
                      int64_t n_corr, int32_t ndim, double max_error, int32_t* count_out, double* sum_out);
 
+/* PSF extraction from beads (mv_deconv.extract_psf): the average of the background-subtracted, unit-sum windows around the beads of
+ * one view, on the OUTPUT grid -- what mvs_mv_deconv takes as that view's forward kernel.  The reference has no counterpart; its
+ * model, BigStitcher / multiview-reconstruction, measures the PSFs from the beads of the registration.
+ *   view            uint8 / uint16 / float32, host (C-contiguous, staged as by mvs_resample) or device (stride[2] == 1); only
+ *                   data / dtype / mem / shape / stride are read.  ndim 2: shape[0] == 1
+ *   centers         host, n_beads x 3 (z, y, x; z = 0 in 2D): the beads in view pixel coordinates
+ *   window_matrix   M, 3 x 3 row-major (2D: embedded like every matrix of this ABI): window offset o, in output-grid voxels, ->
+ *                   view pixels; the window of a bead at c is c + M o for o in prod [-radius[k], radius[k]], x fastest
+ *   radius          per axis, 1 .. MVS_PSF_MAX_RADIUS (the z entry is ignored in 2D)
+ * Per bead, in double unless stated otherwise and without contraction:
+ *   1. sample: s(o) = the view at ((M_k0 o_z + M_k1 o_y) + M_k2 o_x) + c_k, the linear sample of mvs_resample (float32).  A sample
+ *      that is out of bounds (not 0 <= coordinate <= n - 1 on every axis) or NaN gives the bead status 1 (outside);
+ *   2. background: bg = mean of s over the shell (|o_k| == radius[k] on some axis); e(o) = max(s(o) - bg, 0); sum e not a positive
+ *      finite number: status 2 (empty);
+ *   3. refine_iterations (0 .. 64) times: c += M (sum o e(o) / sum e), then 1-2 again at the new centre;
+ *   4. u(o) = e(o) / sum e, kept as float32.
+ * psf_out (host, the window's samples, x fastest) = (sum of u over the beads of status 0, in ascending bead index, float64) / their
+ * number, as float32; all zero when no bead has status 0 (not an error: status_out says why).  stats_out[b] = (bg, sum e, the
+ * Pearson correlation of u_b with psf_out over the window); NaN where a bead did not get that far.  centers_out[b] = the centre
+ * the bead was last sampled at.  Every sum has a fixed order (a thread's strided samples in order, the lanes of a wave by shuffles,
+ * the waves in order) and there are no floating-point atomics: equal inputs give equal bits.  The beads go through the kernels in
+ * batches whose rows (window x 4 bytes per bead) fit a scratch budget; mvs_set_option "psf_batch" = n fixes the batch (0, the
+ * default: automatic), and the result does not depend on it (with more than one batch the windows are gathered a second time for
+ * the correlations).  Waits for the result; runs on the context lane of `device`. */
+#define MVS_PSF_MAX_RADIUS 31
+int mvs_psf_extract(int device, const mvs_view_t* view, int32_t ndim, const double* centers, int64_t n_beads,
+                    const double window_matrix[9], const int32_t radius[3], int32_t refine_iterations, double* centers_out,
+                    int32_t* status_out, float* stats_out, float* psf_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,7 @@ MVS_PAIR_MAX_BLOCKS = 2048
 MVS_KNN_MAX_DIM = 15
 MVS_KNN_MAX_K = 16
 MVS_MARKER_MAX_NEIGHBORS = 5
+MVS_PSF_MAX_RADIUS = 31
 ERR_UNSUPPORTED = -4            # MVS_ERR_UNSUPPORTED
 
 DTYPE_CODES = {np.dtype(np.uint8): MVS_U8, np.dtype(np.uint16): MVS_U16, np.dtype(np.float32): MVS_F32}
@@ -278,6 +279,11 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64, C.c_int32, C.c_double,
          C.POINTER(C.c_int32), C.POINTER(C.c_double)],
+    ),
+    "mvs_psf_extract": (
+        C.c_int,
+        [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32),
+         C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)],
     ),
 }
 

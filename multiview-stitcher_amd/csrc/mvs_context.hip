@@ -231,6 +231,11 @@ static int set_option(MvsContext* c, const char* key, int64_t value) {
         c->fft_slab_axes = (int)value;
         return MVS_OK;
     }
+    if (!strcmp(key, "psf_batch")) {
+        if (value < 0) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_set_option: psf_batch is 0 (automatic) or a number of beads");
+        c->psf_batch = value;
+        return MVS_OK;
+    }
     if (!strcmp(key, "ablate")) {
         c->ablate = (int)value;
         return MVS_OK;

@@ -100,6 +100,7 @@ struct MvsContext {
     long long fuse_rows_chunks = 0, fuse_region_chunks = 0, fuse_column_chunks = 0, fuse_generic_chunks = 0;
     bool deconv_general = false;  // test switch "deconv_general": mvs_mv_deconv takes the general direct convolution even for separable kernels
     bool dct_general = false;     // test switch "dct_general": the DCT quality pass takes its general (global scratch) path for every block size
+    long long psf_batch = 0;      // option "psf_batch": beads per launch of mvs_psf_extract (0: sized to a scratch budget); the result does not depend on it
     bool rows_v1 = false;         // opt-in: direct-load row kernels (mvs_fuse_rows.hip) for every dtype (default: float tiles only)
     // caching device allocator behind mvs_malloc / mvs_free: freed blocks are kept (size-keyed) and handed out
     // again, because hipMalloc / hipFree cost ~0.4 ms each and the registration path allocates per pair.

@@ -254,6 +254,139 @@ def multi_view_deconvolution(
     return res.astype(in_dtype, copy=False)
 
 
+# ---- PSFs measured from beads --------------------------------------------------------------------------------------------------
+_PSF_STATUS = {0: "used", 1: "outside", 2: "empty"}
+
+
+def _psf_extents(psf_shape, sdims):
+    """The window's extent per spatial dim: odd, 3 .. KERNEL_LIMIT (else ``ValueError``)."""
+    if isinstance(psf_shape, dict):
+        if sorted(psf_shape) != sorted(sdims):
+            raise ValueError(f"psf_shape must have one entry per spatial dim {sdims}")
+        shape = [psf_shape[d] for d in sdims]
+    else:
+        shape = list(np.atleast_1d(psf_shape))
+        if len(shape) != len(sdims):
+            raise ValueError(f"psf_shape must have one entry per spatial dim {sdims}")
+    for n in shape:
+        if int(n) != n or int(n) % 2 == 0 or not 3 <= int(n) <= KERNEL_LIMIT:
+            raise ValueError(f"psf_shape {tuple(shape)}: every extent must be odd and in 3..{KERNEL_LIMIT}")
+    return tuple(int(n) for n in shape)
+
+
+def extract_psf(sim, points, psf_shape, affine=None, output_spacing=None, refine_iterations=1, min_correlation=None,
+                max_beads=None, device=0, return_info=False):
+    """The PSF of one view, measured from its beads on the OUTPUT grid of a fusion: the average of the background-subtracted,
+    unit-sum windows around the beads (mvs_psf_extract, csrc/mvs_psf.hip), normalised to sum 1 -- one entry of ``psfs`` of
+    ``multi_view_deconvolution``.
+
+    ``sim``: the view (2-D / 3-D uint8 / uint16 / float32; numpy- or ``DeviceArray``-backed; the first field of its non-spatial
+    dims); ``points``: (n, ndim) physical bead positions in the view's own frame, as ``detection.detect_beads`` returns them;
+    ``psf_shape``: odd extents in 3..63, a tuple or a dict per dim; ``affine``: the view -> world affine (default identity; only
+    its linear part enters; singular: ``ValueError``); ``output_spacing``: the fused grid's spacing (dict or sequence; default
+    the view's own).  A window offset ``o`` in output voxels is sampled at ``c + M o`` in view pixels,
+    ``M = diag(1 / spacing) L^-1 diag(output_spacing)``.
+
+    Beads whose windows hold another bead's centre are dropped (``too_close``), then the first ``max_beads`` remain.  Per bead
+    the background is the mean over the window's shell, the centre is refined ``refine_iterations`` times by the centroid of the
+    background-subtracted window, and a bead whose window leaves the view is ``outside``, one with no signal ``empty``.  With
+    ``min_correlation`` the beads whose Pearson correlation with the average is lower are dropped (``low_correlation``) and the
+    rest averaged again at their refined centres.  No bead left: ``ValueError``.
+
+    Returns the float32 PSF of ``psf_shape``; with ``return_info`` also a dict: ``centers`` (physical, refined), ``status`` (per
+    given bead: ``used`` / ``outside`` / ``empty`` / ``too_close`` / ``low_correlation`` / ``skipped`` (beyond ``max_beads``)),
+    ``background``, ``ncc`` (NaN where not computed), ``n_used``."""
+    from . import _psf_ops, msi_utils, param_utils
+    from . import spatial_image_utils as si_utils
+
+    if msi_utils.is_msim(sim):
+        sim = msi_utils.get_sim_from_msim(sim, scale="scale0")
+    sim = si_utils.get_sim_field(sim)
+    sdims = si_utils.get_spatial_dims_from_sim(sim)
+    ndim = len(sdims)
+    shape = _psf_extents(psf_shape, sdims)
+    radius = [(n - 1) // 2 for n in shape]
+    points = np.asarray(points, dtype=np.float64)
+    if points.ndim != 2 or points.shape[1] != ndim:
+        raise ValueError(f"points must have shape (n_points, {ndim}) for this image, got {points.shape}")
+    spacing = si_utils.get_spacing_from_sim(sim, asarray=True)
+    origin = si_utils.get_origin_from_sim(sim, asarray=True)
+    full = np.eye(ndim + 1) if affine is None else param_utils.select_time(affine, 0)
+    if full.shape != (ndim + 1, ndim + 1):
+        raise ValueError(f"affine must be {ndim + 1} x {ndim + 1}")
+    if output_spacing is None:
+        out_sp = spacing
+    elif isinstance(output_spacing, dict):
+        out_sp = np.array([float(output_spacing[d]) for d in sdims])
+    else:
+        out_sp = np.asarray(output_spacing, dtype=np.float64)
+    matrix = _psf_ops.window_matrix(spacing, full[:ndim, :ndim], out_sp)
+    if min_correlation is not None and not -1.0 <= float(min_correlation) <= 1.0:
+        raise ValueError("min_correlation is a correlation coefficient in [-1, 1]")
+
+    n = len(points)
+    centers = (points - origin) / spacing
+    status = np.array(["used"] * n, dtype=object)
+    status[_psf_ops.too_close(centers, matrix, radius)] = "too_close"
+    sel = np.nonzero(status == "used")[0]
+    if max_beads is not None:
+        status[sel[int(max_beads):]] = "skipped"
+        sel = sel[:int(max_beads)]
+    if len(sel) == 0:
+        raise ValueError("extract_psf: no bead is left after the separation rule")
+    background = np.full(n, np.nan)
+    ncc = np.full(n, np.nan)
+    psf, c_out, codes, stats = _psf_ops.psf_extract(sim.data, centers[sel], matrix, radius, refine_iterations, device)
+    centers = centers.copy()
+    centers[sel] = c_out
+    for code, name in _PSF_STATUS.items():
+        status[sel[codes == code]] = name
+    background[sel], ncc[sel] = stats[:, 0], stats[:, 2]
+    used = sel[codes == 0]
+    if len(used) and min_correlation is not None:
+        low = used[~(ncc[used] >= float(min_correlation))]
+        if len(low):
+            status[low] = "low_correlation"
+            used = used[ncc[used] >= float(min_correlation)]
+            if len(used):
+                psf, _, codes2, stats2 = _psf_ops.psf_extract(sim.data, centers[used], matrix, radius, 0, device)
+                for code, name in _PSF_STATUS.items():
+                    status[used[codes2 == code]] = name
+                background[used], ncc[used] = stats2[:, 0], stats2[:, 2]
+                used = used[codes2 == 0]
+    if len(used) == 0:
+        counts = {k: int(np.sum(status == k)) for k in sorted(set(status))}
+        raise ValueError(f"extract_psf: no usable bead ({counts})")
+    psf = _norm(psf)
+    if not return_info:
+        return psf
+    return psf, {"centers": origin + centers * spacing, "status": [str(v) for v in status], "background": background, "ncc": ncc,
+                 "n_used": int(len(used))}
+
+
+def extract_psfs(msims, transform_key, psf_shape, points_key="beads", output_spacing=None, **kw):
+    """One measured PSF per view, for ``fuse(..., fusion_func=multi_view_deconvolution, fusion_func_kwargs={"psfs": psfs})``.
+
+    ``msims``: the views with their beads attached (``msi_utils.set_point_set`` under ``points_key``) and registered under
+    ``transform_key`` (its affine at the first time point is used).  ``output_spacing`` (dict per dim): the fused grid's spacing;
+    default: the spacing ``fusion.process_output_stack_properties`` gives these views, i.e. that of a default ``fuse()``.
+    Remaining keywords go to ``extract_psf``."""
+    from . import fusion, msi_utils
+    from . import spatial_image_utils as si_utils
+
+    if kw.get("return_info"):
+        raise TypeError("extract_psfs returns the PSFs only; call extract_psf per view for the per-bead information")
+    sims = [msi_utils.get_sim_from_msim(m, scale="scale0") if msi_utils.is_msim(m) else m for m in msims]
+    if output_spacing is None:
+        output_spacing = fusion.process_output_stack_properties(sims, transform_key=transform_key)["spacing"]
+    psfs = []
+    for msim, sim in zip(msims, sims):
+        points = msi_utils.get_point_set(msim, points_key) if msi_utils.is_msim(msim) else si_utils.get_point_set(sim, points_key)
+        psfs.append(extract_psf(sim, points, psf_shape, affine=si_utils.get_affine_from_sim(sim, transform_key),
+                                output_spacing=output_spacing, **kw))
+    return psfs
+
+
 def _required_overlap(func_kwargs):
     """Chunk halo for the deconvolution (mv_deconv.py:504-527): half the estimated PSF's largest extent when
     ``output_spacing`` is among the kwargs, else 4 (the 1.5-pixel default PSF of 9 pixels)."""
