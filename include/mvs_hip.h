@@ -156,7 +156,9 @@ int mvs_set_option(int device, const char* key, int64_t value);
  * (candidate volumes the SSIM passes went through), "reg_slab_pairs" (phase correlations that ran in three passes: crops with one
  * short and two power-of-two axes; option "fft_no_slab" switches that form off), "reg_rank_hist" / "reg_rank_sort16" / "reg_rank_sort32" (Spearman coefficients
  * computed from key histograms, from sorts on the fixed crop's 16-bit integer keys, from sorts on float keys), "fuse_plan_ms" = host time the last mvs_fuse_chunk spent decomposing the chunk
- * (0 when the plan cached for the same geometry was reused).  Per class k of the last region-kernel launch (0 one-view rim
+ * (0 when the plan cached for the same geometry was reused), "fuse_region_bricks" = items (bricks) of the last region-kernel launch,
+ * the padding items of the "fuse_mixed" list excluded, "fuse_region_forked" = 1 if that launch ran its class kernels on the side
+ * streams (4096 items or more and option "serial_classes" off), else 0.  Per class k of the last region-kernel launch (0 one-view rim
  * boxes, 1 NV = 2, 2 NV <= 4, 3 NV <= 8, 4 copy): "fuse_class_in_vox_<k>" (voxels x views of the class's boxes),
  * "fuse_class_out_vox_<k>", and "fuse_class_ms_<k>" = the class kernel's own duration when that launch ran with option
  * "serial_classes" = 1 (-1 otherwise).  "pool_misses" / "pool_miss_bytes" / "pool_releases": hipMalloc calls (and their bytes) that

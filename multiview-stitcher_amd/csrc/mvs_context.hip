@@ -269,6 +269,7 @@ static const MvsCounter kCounters[] = {
 double mvs_rows_last_plan_ms(MvsContext* c);       // mvs_fuse_rows.hip
 double mvs_regions_last_plan_ms(MvsContext* c);    // mvs_fuse_region.hip
 double mvs_regions_class_stat(MvsContext* c, int what, int cls);   // mvs_fuse_region.hip
+double mvs_regions_launch_stat(MvsContext* c, int what);           // mvs_fuse_region.hip
 
 extern "C" {
 
@@ -483,6 +484,10 @@ int mvs_get_counter(int device, const char* key, int32_t reset, double* value_ou
         *value_out = mvs_rows_last_plan_ms(c) + mvs_regions_last_plan_ms(c);
         return MVS_OK;
     }
+    // the last region-kernel launch of this context: its bricks (the padding items of the "fuse_mixed" list do not count) and
+    // whether its class kernels forked onto the side streams
+    if (!strcmp(key, "fuse_region_bricks")) { *value_out = mvs_regions_launch_stat(c, 0); return MVS_OK; }
+    if (!strcmp(key, "fuse_region_forked")) { *value_out = mvs_regions_launch_stat(c, 1); return MVS_OK; }
     // per-class figures of the last region-kernel launch of this context, <k> = 0 (one-view rim boxes), 1 (NV = 2), 2 (NV <= 4),
     // 3 (NV <= 8), 4 (copy): "fuse_class_in_vox_<k>" / "fuse_class_out_vox_<k>" = input voxel reads (sum over the class's boxes of
     // voxels x views) and output voxels of the class; "fuse_class_ms_<k>" = the class kernel's own duration, measured only by a

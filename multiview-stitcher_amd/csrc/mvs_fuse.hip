@@ -1320,6 +1320,8 @@ int mvs_fuse_regions(MvsContext* c, const TrView* htr, const TrView* dtr, int n_
 
 int mvs_fuse_rows(MvsContext* c, const TrView* htr, const TrView* dtr, int n_views, int dtype, void* dout, const int64_t os[3],
                   const int64_t trim[3], bool* done);      // mvs_fuse_rows.hip
+void mvs_rows_clear_plan_ms(MvsContext* c);                // mvs_fuse_rows.hip
+void mvs_regions_clear_plan_ms(MvsContext* c);             // mvs_fuse_region.hip
 
 int mvs_fuse_content_based(MvsContext* c, const mvs_view_t* views, int32_t n_views,
                            const mvs_fuse_opts_t* opts, void* out);   // mvs_gauss.hip
@@ -1491,6 +1493,9 @@ int mvs_fuse_chunk_impl(MvsContext* c, const mvs_view_t* views, int32_t n_views,
     if (!keep_start) MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     int* tr_overflow_ptr = nullptr;
     bool regions_done = false;
+    // counter "fuse_plan_ms" speaks of THIS chunk: a family that does not plan it must not leave the time of an earlier chunk behind
+    mvs_rows_clear_plan_ms(c);
+    mvs_regions_clear_plan_ms(c);
     if (!regions_done && use_tr && opts->fusion == MVS_FUSE_WEIGHTED_AVERAGE && (c->rows_v1 || (dtype == MVS_F32 && opts->order == 1))) {
         // direct-load row-owning kernels.  Float tiles take them by default: they read both taps of every axis even at
         // integer offsets, so a NaN next to a tap poisons the sample exactly as scipy's zero-weight multiply does

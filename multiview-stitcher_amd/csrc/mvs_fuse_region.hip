@@ -15,6 +15,7 @@
 //                                      row-uniform nodes (G1, dG) evaluated once per plane by 32 lanes
 // The unrolled NV = 1, 2, 4 instantiations keep all per-view constants in scalar registers.
 #include "mvs_fuse_tr.h"
+#include "mvs_region_plan.h"   // Region, Item, kRB / kRV / kMaxRV, axis_breakpoints, mvs_region_plan
 
 #include <algorithm>
 #include <chrono>
@@ -25,22 +26,7 @@
 
 namespace {
 
-constexpr int kRB = 4;       // planes per brick
 constexpr int kRG = 8;       // 4-row groups per brick
-constexpr int kRV = 8;       // voxels per lane
-constexpr int kMaxRV = 8;    // views per region handled here
-
-struct Region {
-    int z0, z1, y0, y1, x0, x1;   // chunk-index box, end exclusive
-    int nviews;
-    int allone_mask;              // bits 0-7: view ids[v] has blend weight 1 everywhere in the box; bit 15: every view is in
-                                  // bounds with a strictly positive weight everywhere (plain weighted sums suffice);
-                                  // bits 16-31: view ids[v] covers the box only partially (per-voxel bounds test)
-    int ids[kMaxRV];
-};
-static_assert(sizeof(Region) == 64, "Region layout");
-
-struct Item { int region_bx, by_bz; };   // region | bx << 16 ; by | bz << 16
 
 struct RegionParams {
     const TrView* views;
@@ -790,7 +776,7 @@ __device__ __forceinline__ void copy_brick_item(const RegionParams& P, const Ite
         const int zc = z0b + p;
         if (zc >= z1) break;
         const int vo_p = ((zc + ioz) * sz + ioy * sy + (xl + iox)) * ES;   // + row * sy * ES
-        if (!anyfrac && lxb >= 4) {
+        if (lxb >= 4) {      // (fractional offsets have returned above)
           for (int gb = 0; gb < L.NG; gb += kRG) {
             if (y0b + L.RG * gb >= y1) break;
             unsigned int raw[kRG][9];
@@ -829,40 +815,22 @@ __device__ __forceinline__ void copy_brick_item(const RegionParams& P, const Ite
             }
           }
         } else {
-            const float ux = 1.f - wx, uy = 1.f - wy, uz = 1.f - wz;
+            // thin boxes (fewer than 8 row groups): one tap row per row group.  (Offsets are whole pixels here, so the other three
+            // taps of the stencil weigh 0 -- and must not be touched: 0 x NaN of a float tile's neighbour voxel is NaN.)
 #pragma unroll 2
             for (int g = 0; g < L.NG; ++g) {
                 const int yc = y0b + L.RG * g + r;
                 if (y0b + L.RG * g >= y1) break;
                 const int yl = min(yc, y1 - 1);
                 const int v0 = vo_p + yl * sy * ES;
-                unsigned int w00[9], w01[9], w10[9], w11[9];
-                Row8<TIn, true>::load(rsrc, v0, w00);
-                Row8<TIn, true>::load(rsrc, v0 + sy * ES, w01);
-                Row8<TIn, true>::load(rsrc, v0 + sz * ES, w10);
-                Row8<TIn, true>::load(rsrc, v0 + (sz + sy) * ES, w11);
-                float e00[9], e01[9], e10[9], e11[9];
-                Row8<TIn, true>::decode(w00, e00);
-                Row8<TIn, true>::decode(w01, e01);
-                Row8<TIn, true>::decode(w10, e10);
-                Row8<TIn, true>::decode(w11, e11);
-                const int olast = v0 + (sz + sy) * ES;
-                if (__any(v0 < 0 || olast + WB > nbytes)) {
-                    const int o1 = v0 + sy * ES, o2 = v0 + sz * ES;
-                    if (__any((v0 < 0 && v0 + WB > 0) || (v0 < nbytes && v0 + WB > nbytes))) row8_refetch<TIn>(rsrc, v0, e00, strip);
-                    if (__any((o1 < 0 && o1 + WB > 0) || (o1 < nbytes && o1 + WB > nbytes))) row8_refetch<TIn>(rsrc, o1, e01, strip);
-                    if (__any((o2 < 0 && o2 + WB > 0) || (o2 < nbytes && o2 + WB > nbytes))) row8_refetch<TIn>(rsrc, o2, e10, strip);
-                    if (__any((olast < 0 && olast + WB > 0) || (olast < nbytes && olast + WB > nbytes))) row8_refetch<TIn>(rsrc, olast, e11, strip);
-                }
+                unsigned int w00[9];
+                Row8<TIn, false>::load(rsrc, v0, w00);
+                float e00[9];
+                Row8<TIn, false>::decode(w00, e00);
+                if (__any((v0 < 0 && v0 + WB > 0) || (v0 < nbytes && v0 + WB > nbytes))) row8_refetch<TIn>(rsrc, v0, e00, strip);
                 float q[kRV];
 #pragma unroll
-                for (int j = 0; j < kRV; ++j) {
-                    const float a00 = fmaf(e00[j + 1], wx, e00[j] * ux), a01 = fmaf(e01[j + 1], wx, e01[j] * ux);
-                    const float a10 = fmaf(e10[j + 1], wx, e10[j] * ux), a11 = fmaf(e11[j + 1], wx, e11[j] * ux);
-                    const float s0 = fmaf(a10, wz, a00 * uz), s1 = fmaf(a11, wz, a01 * uz);
-                    const float vv = fmaf(s1, wy, s0 * uy);
-                    q[j] = (vv == vv) ? vv : 0.f;
-                }
+                for (int j = 0; j < kRV; ++j) q[j] = (e00[j] == e00[j]) ? e00[j] : 0.f;   // nan_to_num (float tiles)
                 if (yc < y1 && nvalid_x > 0)
                     store8<TOut>(out + ((long long)(zc - P.tz) * P.oy + (yc - P.ty)) * (long long)P.ox + (xq - P.tx), q, nvalid_x);
             }
@@ -970,6 +938,8 @@ struct PlanCache {
     bool valid = false;
     int mixed_count = 0;      // option "fuse_mixed": the padded, space-ordered list of the copy / one-view / two-view bricks (stored first)
     bool mixed = false;
+    int bricks = 0;           // items without the padding of the mixed list (counter "fuse_region_bricks")
+    bool forked = false;      // the last launch used the side streams (counter "fuse_region_forked")
     double class_in_vox[5] = {0, 0, 0, 0, 0};    // sum over the class's boxes of voxels x views (input voxel reads the class cannot avoid)
     double class_out_vox[5] = {0, 0, 0, 0, 0};   // voxels of the class's boxes
     // measurement (counters "fuse_class_ms_<k>"): with option serial_classes the class kernels of a launch run one after the other
@@ -986,73 +956,16 @@ unsigned long long fnv1a(const void* p, size_t n, unsigned long long h) {
     return h;
 }
 
-// Break points of one axis.  View borders that lie within `tol` of each other (tiles of one grid row/column after
-// registration differ by a few pixels) are clustered: a cluster of lower borders contributes its minimum, a cluster
-// of upper borders (hi + 1) its maximum, so the sliver between the clustered borders falls into the overlap cell,
-// where the affected views are flagged "partial", and the single-view interior cells keep full coverage.
-void axis_breakpoints(const TrView* htr, int n_views, int d, int t, int o, std::vector<int>* out) {
-    // kinds: 0 lower border (cluster -> min), 1 upper border + 1 (-> max),
-    //        2 end of the lower ramp zone (-> max), 3 start of the upper ramp zone (-> min)
-    std::vector<std::pair<int, int>> ev;
-    auto clampi = [&](int v) { return std::min(std::max(v, t), t + o); };
-    for (int v = 0; v < n_views; ++v) {
-        const int lo = htr[v].lo[d], hi = htr[v].hi[d];
-        if (lo > hi) continue;
-        ev.push_back({clampi(lo), 0});
-        ev.push_back({clampi(hi + 1), 1});
-        // A thin shell next to every border: inside it the blend weight of the view can round to 0 (the reference
-        // outputs 0 there even for a single view, weights.py:502-507); outside it a voxel seen by ONE view is simply
-        // the resampled value whatever the weight is, so single-view boxes off the shell need no weights at all.
-        // Along x a 4-voxel sliver costs a whole cache line per row and view, so the shell is only cut where it matters:
-        // next to a border that no other view covers (the rim of the mosaic).  Inside an overlap the box simply is not
-        // flagged "positive" if a weight can vanish there (it cannot, away from the edges of the view).
-        const int shell = 4;
-        bool cut_lo = true, cut_hi = true;
-        if (d == 2) {
-            for (int w = 0; w < n_views; ++w) {
-                if (w == v || htr[w].lo[2] > htr[w].hi[2]) continue;
-                const bool touches = htr[w].lo[0] <= htr[v].hi[0] && htr[w].hi[0] >= htr[v].lo[0] && htr[w].lo[1] <= htr[v].hi[1] &&
-                                     htr[w].hi[1] >= htr[v].lo[1];
-                if (!touches) continue;
-                if (htr[w].lo[2] <= lo - 8 && htr[w].hi[2] >= lo + shell + 8) cut_lo = false;
-                if (htr[w].lo[2] <= hi - shell - 8 && htr[w].hi[2] >= hi + 8) cut_hi = false;
-            }
-        }
-        if (2 * shell + 8 < hi - lo + 1) {
-            if (cut_lo) ev.push_back({clampi(lo + shell), 2});
-            if (cut_hi) ev.push_back({clampi(hi + 1 - shell), 3});
-        }
-    }
-    const int tol = 16;
-    out->clear();
-    out->push_back(t);
-    for (int kind_group = 0; kind_group < 2; ++kind_group) {
-        // borders and shell ends are clustered separately so that a shell end never merges with a border
-        std::vector<std::pair<int, int>> e2;
-        for (auto& e : ev)
-            if (e.second / 2 == kind_group) e2.push_back(e);
-        std::sort(e2.begin(), e2.end());
-        size_t i = 0;
-        while (i < e2.size()) {
-            size_t j = i;
-            bool want_min = false, want_max = false;
-            while (j < e2.size() && e2[j].first - e2[i].first <= tol) {
-                // lower borders and the starts of upper shells cluster to their minimum, the rest to the maximum
-                if (e2[j].second == 0 || e2[j].second == 3) want_min = true; else want_max = true;
-                ++j;
-            }
-            if (want_min) out->push_back(e2[i].first);
-            if (want_max) out->push_back(e2[j - 1].first);
-            i = j;
-        }
-    }
-    out->push_back(t + o);
-    std::sort(out->begin(), out->end());
-    out->erase(std::unique(out->begin(), out->end()), out->end());
-}
 }  // namespace
 
 double mvs_regions_last_plan_ms(MvsContext* c) { return g_region_plan_ms[mvs_ctx_index(c->device)]; }
+void mvs_regions_clear_plan_ms(MvsContext* c) { g_region_plan_ms[mvs_ctx_index(c->device)] = 0.0; }
+
+// what = 0: bricks of the last launch (padding items excluded), 1: whether that launch forked onto the side streams
+double mvs_regions_launch_stat(MvsContext* c, int what) {
+    const PlanCache& pc = g_plan[mvs_ctx_index(c->device)];
+    return what == 0 ? (double)pc.bricks : (pc.forked ? 1.0 : 0.0);
+}
 
 // what = 0: input voxel reads, 1: output voxels, 2: kernel ms of class `cls` in the last launch (-1: that launch was not a serial one)
 double mvs_regions_class_stat(MvsContext* c, int what, int cls) {
@@ -1090,116 +1003,10 @@ int mvs_fuse_regions(MvsContext* c, const TrView* htr, const TrView* dtr, int n_
         nitems = pc.nitems;
         rbytes = pc.rbytes;
     } else {
-        std::vector<int> pts[3];
-        for (int d = 0; d < 3; ++d) axis_breakpoints(htr, n_views, d, t[d], o[d], &pts[d]);
-        const size_t ncell = (pts[0].size() - 1) * (pts[1].size() - 1) * (pts[2].size() - 1);
-        if (ncell == 0 || ncell > 60000) return MVS_OK;
-        std::vector<Region> regions;
-        std::vector<Item> items_by_class[5];
-        double in_vox[5] = {0, 0, 0, 0, 0}, out_vox[5] = {0, 0, 0, 0, 0};
-        regions.reserve(ncell);
-        std::vector<int> zviews, yviews;
-        struct SlabRegion { int rid, nbx, bytes_per_item; };
-        std::vector<SlabRegion> slab;              // the mixed-class regions of the current (z, y) slab, in x order
-        std::vector<Item> mixed_items;
-        std::vector<int> mixed_work;
-        for (size_t iz = 0; iz + 1 < pts[0].size(); ++iz) {
-            zviews.clear();
-            for (int v = 0; v < n_views; ++v)
-                if (htr[v].lo[0] < pts[0][iz + 1] && htr[v].hi[0] >= pts[0][iz] && htr[v].lo[1] <= htr[v].hi[1] && htr[v].lo[2] <= htr[v].hi[2]) zviews.push_back(v);
-            for (size_t iy = 0; iy + 1 < pts[1].size(); ++iy) {
-                slab.clear();
-                yviews.clear();
-                for (int v : zviews)
-                    if (htr[v].lo[1] < pts[1][iy + 1] && htr[v].hi[1] >= pts[1][iy]) yviews.push_back(v);
-                for (size_t ix = 0; ix + 1 < pts[2].size(); ++ix) {
-                    Region R;
-                    memset(&R, 0, sizeof(R));
-                    R.z0 = pts[0][iz]; R.z1 = pts[0][iz + 1];
-                    R.y0 = pts[1][iy]; R.y1 = pts[1][iy + 1];
-                    R.x0 = pts[2][ix]; R.x1 = pts[2][ix + 1];
-                    int nv = 0;
-                    bool positive_full = false, all_positive = true;
-                    for (int v : yviews) {
-                        if (!(htr[v].lo[2] < R.x1 && htr[v].hi[2] >= R.x0)) continue;   // does not touch the box
-                        if (nv == kMaxRV) return MVS_OK;                              // too many views: column kernel
-                        const bool full = htr[v].lo[0] <= R.z0 && htr[v].hi[0] >= R.z1 - 1 && htr[v].lo[1] <= R.y0 &&
-                                          htr[v].hi[1] >= R.y1 - 1 && htr[v].lo[2] <= R.x0 && htr[v].hi[2] >= R.x1 - 1;
-                        // the profile is concave, so its minimum over the box sits at one of the 8 corners
-                        float wmin = INFINITY;
-                        for (int k = 0; k < 8; ++k) {
-                            const int z = (k & 4) ? R.z1 - 1 : R.z0, y = (k & 2) ? R.y1 - 1 : R.y0, x = (k & 1) ? R.x1 - 1 : R.x0;
-                            wmin = fminf(wmin, tr_weight_profile(htr[v], z, y, x));
-                        }
-                        const bool unit = full && wmin >= 1.f;          // weight exactly 1 everywhere
-                        // weight > 0 everywhere: the float32 ramp (cos(pi (1 - W)) + 1) / 2 only vanishes when the cosine
-                        // rounds to -1, i.e. W < 7.8e-5; at W = 3e-4 the cosine is 7 ulp away from -1
-                        if (full && wmin >= 3e-4f) positive_full = true;
-                        else all_positive = false;
-                        if (unit) R.allone_mask |= 1 << nv;
-                        if (!full) R.allone_mask |= 1 << (16 + nv);
-                        R.ids[nv++] = v;
-                    }
-                    if (nv > 0 && all_positive) R.allone_mask |= 1 << 15;
-                    // profiling only (WRONG results): every view counts as a full unit view, i.e. every brick takes the plain-average
-                    // path -- the floor of what the weight evaluation can be brought down to
-                    // (compiled only into profiling builds -- make CXXFLAGS+=-DMVS_PROFILING_ABLATIONS, tools/fuse_floor.sh: a stray
-                    // environment variable must not be able to corrupt the shipped path's output)
-#ifdef MVS_PROFILING_ABLATIONS
-                    static const bool ablate_unit = getenv("MVS_FUSE_ALL_UNIT") != nullptr;
-                    if (ablate_unit) R.allone_mask = ((1 << nv) - 1) | (1 << 15);
-#endif
-                    // brick width: 16 voxels for thin boxes, 512 (one full tile row per load instruction: the longest
-                    // contiguous runs, 4.0 instead of 3.0 TB/s on the copy class) for wide copy-class boxes, else 128
-                    int lxb = (R.x1 - R.x0 <= 32) ? 1 : 4;
-                    if (nv == 1 && positive_full && R.x1 - R.x0 > 160) lxb = 6;
-                    // overlap zones along x (about 100 voxels wide): 64-voxel bricks, so that each brick holds only ONE of the
-                    // zone's two ramp ends and the other view classifies as "unit" (measured best of 16/32/64/128)
-                    if (nv >= 2 && R.x1 - R.x0 > 32 && R.x1 - R.x0 <= 136) lxb = 3;
-                    // (measured, round 4: 256- / 512-voxel bricks for the wide NV >= 2 boxes -- the copy class's layout -- lose:
-                    // launch 10.06 -> 10.3 / 11.2 ms; every wavefront then spans a ramp end and takes the per-voxel weights)
-                    const bool copy_class = (nv == 1) && positive_full;   // one full view with positive weight everywhere
-                    const int cls = copy_class ? 4 : nv <= 1 ? 0 : nv == 2 ? 1 : nv <= 4 ? 2 : 3;
-                    R.nviews = nv | (lxb << 8) | (cls << 12);
-                    {
-                        const double vox = (double)(R.z1 - R.z0) * (double)(R.y1 - R.y0) * (double)(R.x1 - R.x0);
-                        in_vox[cls] += vox * nv;
-                        out_vox[cls] += vox;
-                    }
-                    const int rid = (int)regions.size();
-                    if (rid >= 65535) return MVS_OK;                     // (0xffff marks a padding item)
-                    regions.push_back(R);
-                    const int bxw = kRV << lxb;
-                    const int nbz = (R.z1 - R.z0 + kRB - 1) / kRB, nby = (R.y1 - R.y0 + 31) / 32, nbx = (R.x1 - R.x0 + bxw - 1) / bxw;
-                    if (nbz >= 65536 || nby >= 65536 || nbx >= 65536) return MVS_OK;
-                    if (mixed_mode && (cls == 4 || cls <= 1)) {         // joins the space-ordered list of this slab (below)
-                        slab.push_back(SlabRegion{rid, nbx, std::min(bxw, R.x1 - R.x0) * (std::max(nv, 1) + 1)});
-                        continue;
-                    }
-                    std::vector<Item>& dst = items_by_class[cls];
-                    // x fastest, then z, then y: bricks that are neighbours along x share the cache lines at their common
-                    // edge, neighbours along z share a whole plane when the offsets are fractional; both reuses then happen
-                    // within a few bricks, i.e. inside the L2 of the XCD that owns this stretch of the list
-                    for (int by = 0; by < nby; ++by)
-                        for (int bz = 0; bz < nbz; ++bz)
-                            for (int bx = 0; bx < nbx; ++bx) dst.push_back({rid | (bx << 16), by | (bz << 16)});
-                }
-                if (!slab.empty()) {
-                    // one (z, y) slab of the cell grid: its regions share the z / y extents and the brick grid; y block, then z
-                    // block, then ALL regions along x -- so the bricks of a row of the mosaic are neighbours in the list whatever
-                    // their class
-                    const int z0s = pts[0][iz], z1s = pts[0][iz + 1], y0s = pts[1][iy], y1s = pts[1][iy + 1];
-                    const int nbz = (z1s - z0s + kRB - 1) / kRB, nby = (y1s - y0s + 31) / 32;
-                    for (int by = 0; by < nby; ++by)
-                        for (int bz = 0; bz < nbz; ++bz)
-                            for (const SlabRegion& sr : slab)
-                                for (int bx = 0; bx < sr.nbx; ++bx) {
-                                    mixed_items.push_back({sr.rid | (bx << 16), by | (bz << 16)});
-                                    mixed_work.push_back(sr.bytes_per_item);
-                                }
-                }
-            }
-        }
+        RegionPlan plan;
+        mvs_region_plan(htr, n_views, t, o, mixed_mode != 0, &plan);
+        if (plan.declined) return MVS_OK;
+        const std::vector<Region>& regions = plan.regions;
         if (getenv("MVS_PLAN_STATS")) {
             double vox[6][2] = {{0}};
             for (const Region& R : regions) {
@@ -1235,43 +1042,18 @@ int mvs_fuse_regions(MvsContext* c, const TrView* htr, const TrView* dtr, int n_
             fprintf(stderr, "[mvs plan] regions %zu; Mvox (ramp / all-unit): nv0 %.1f/%.1f nv1 %.1f/%.1f nv2 %.1f/%.1f nv3-4 %.1f/%.1f nv5+ %.1f/%.1f; bricks",
                     regions.size(), vox[0][0] / 1e6, vox[0][1] / 1e6, vox[1][0] / 1e6, vox[1][1] / 1e6, vox[2][0] / 1e6, vox[2][1] / 1e6,
                     vox[3][0] / 1e6, vox[3][1] / 1e6, vox[4][0] / 1e6, vox[4][1] / 1e6);
-            for (int k = 0; k < 5; ++k) fprintf(stderr, " %zu", items_by_class[k].size());
+            for (int k = 0; k < 5; ++k) fprintf(stderr, " %d", plan.class_count[k]);
             fprintf(stderr, "\n");
         }
-        std::vector<Item> items;
+        const std::vector<Item>& items = plan.items;
         pc.mixed = mixed_mode != 0;
-        pc.mixed_count = 0;
-        if (!mixed_items.empty()) {
-            // eight stretches of equal WORK (bytes moved), one per XCD (see the workgroup -> item mapping of the kernels), padded to
-            // one length with no-op items
-            long long total = 0;
-            for (int w : mixed_work) total += w;
-            size_t cut[9];
-            cut[0] = 0;
-            long long acc = 0;
-            size_t i = 0;
-            for (int k = 1; k <= 8; ++k) {
-                const long long target = total * k / 8;
-                while (i < mixed_items.size() && acc < target) acc += mixed_work[i++];
-                cut[k] = k == 8 ? mixed_items.size() : i;
-            }
-            size_t longest = 0;
-            for (int k = 0; k < 8; ++k) longest = std::max(longest, cut[k + 1] - cut[k]);
-            const size_t L = (longest + 3) / 4 * 4;
-            items.reserve(8 * L);
-            for (int k = 0; k < 8; ++k) {
-                items.insert(items.end(), mixed_items.begin() + (long)cut[k], mixed_items.begin() + (long)cut[k + 1]);
-                items.resize((size_t)(k + 1) * L, Item{0xffff, 0});
-            }
-            pc.mixed_count = (int)items.size();
-        }
+        pc.mixed_count = plan.mixed_count;
+        pc.bricks = plan.bricks;
         for (int k = 0; k < 5; ++k) {
-            pc.class_count[k] = (int)items_by_class[k].size();
-            pc.class_in_vox[k] = in_vox[k];
-            pc.class_out_vox[k] = out_vox[k];
-            items.insert(items.end(), items_by_class[k].begin(), items_by_class[k].end());
+            pc.class_count[k] = plan.class_count[k];
+            pc.class_in_vox[k] = plan.class_in_vox[k];
+            pc.class_out_vox[k] = plan.class_out_vox[k];
         }
-        if (items.empty() || items.size() > (1u << 28)) return MVS_OK;
         rbytes = align_up(regions.size() * sizeof(Region));
         const size_t ibytes = items.size() * sizeof(Item);
         char* hbuf = (char*)mvs_pinned_slot(c, 1, rbytes + ibytes + 256);   // slot 0 holds the view parameters still in flight
@@ -1302,6 +1084,7 @@ int mvs_fuse_regions(MvsContext* c, const TrView* htr, const TrView* dtr, int n_
     // NV = 4 / 8 classes by their weight arithmetic): they run side by side -- NV = 2, the largest, on the main stream, the
     // others on side streams that start after everything queued so far (fork event) and are waited for at the end (join).
     const bool fork = !c->serial_classes && nitems >= 4096;   // small chunks: five event round trips cost more than the overlap gains
+    pc.forked = fork;
     if (fork) {      // side streams: created once per context (tens of ms: outside the timed section)
         const int rca = mvs_ensure_aux_streams(c);
         if (rca) return rca;

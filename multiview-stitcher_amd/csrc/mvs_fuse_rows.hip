@@ -29,6 +29,7 @@ double g_last_plan_ms[MVS_MAX_DEVICES * MVS_MAX_LANES];
 }  // namespace
 
 double mvs_rows_last_plan_ms(MvsContext* c) { return g_last_plan_ms[mvs_ctx_index(c->device)]; }
+void mvs_rows_clear_plan_ms(MvsContext* c) { g_last_plan_ms[mvs_ctx_index(c->device)] = 0.0; }
 
 // Returns MVS_OK and sets *done = true when the chunk was fused by the row kernels; *done = false means the caller
 // must use another path (more than kMaxCV views on one cell, or too many cells / items).

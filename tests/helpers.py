@@ -159,3 +159,49 @@ def assert_fused_close(got, want, want_float=None, rtol=1e-4, data_range=None, m
     stats = fused_close_stats(got, want, want_float, rtol, data_range, max_bad_frac, noise_floor)
     assert stats["beyond_plain_bar"] <= max_floor_frac * stats["voxels"], stats
     return stats
+
+
+def white_noise(rng, shape, dtype):
+    """Independent white noise over the whole range of ``dtype``: uint16 0..65535, uint8 0..255, float32 in [0, 1)."""
+    dtype = np.dtype(dtype)
+    if dtype.kind == "f":
+        return rng.random(shape, dtype=np.float32)
+    return rng.integers(0, int(np.iinfo(dtype).max) + 1, size=shape, dtype=dtype)
+
+
+def placed_tiles(dtype, shape, origins, seed=0):
+    """Squeezed sims of ``shape`` with their first voxels at the integer ``origins`` (unit spacing), every one filled with white
+    noise of its own (``white_noise``): two views that share a voxel differ by a third of the range on average, so a wrong blend
+    weight moves the output by whole counts.  The parameters come separately (``shift_params``)."""
+    from multiview_stitcher_amd import spatial_image_utils as si
+
+    ndim = len(shape)
+    sdims = ["z", "y", "x"][-ndim:]
+    rng = np.random.default_rng(seed)
+    sims = []
+    for origin in origins:
+        sim = si.get_sim_from_array(white_noise(rng, tuple(shape), dtype), dims=sdims, scale=dict(zip(sdims, [1.0] * ndim)),
+                                    translation=dict(zip(sdims, [float(v) for v in origin])))
+        sims.append(squeeze_field(sim))
+    return sims
+
+
+def stair_tiles(dtype, shape, n, step, seed=0):
+    """A "stair" of ``n`` tiles (``placed_tiles``): tile ``i`` at origin ``i * step``."""
+    return placed_tiles(dtype, shape, [tuple(i * int(s) for s in step) for i in range(n)], seed)
+
+
+def grid_origins(tiles, shape, overlap):
+    """Origins of a regular grid of ``tiles`` tiles of ``shape`` whose neighbours share ``overlap`` voxels."""
+    return [tuple(int(i) * (int(n) - int(o)) for i, n, o in zip(idx, shape, overlap)) for idx in np.ndindex(*tiles)]
+
+
+def shift_params(ndim, shifts=None, n=None):
+    """One translation matrix per view: identity (``shifts`` None, ``n`` of them) or a shift by ``shifts[i]``."""
+    params = []
+    for i in range(len(shifts) if shifts is not None else n):
+        p = np.eye(ndim + 1)
+        if shifts is not None:
+            p[:ndim, ndim] = shifts[i]
+        params.append(p)
+    return params
