@@ -719,6 +719,60 @@ int mvs_psf_extract(int device, const mvs_view_t* view, int32_t ndim, const doub
                     const double window_matrix[9], const int32_t radius[3], int32_t refine_iterations, double* centers_out,
                     int32_t* status_out, float* stats_out, float* psf_out);
 
+/* Tile intensity harmonisation (intensity.fit_maps / apply_maps): remove brightness steps between tiles (bleaching, light-sheet
+ * side, detector offset, exposure) before fusion.  The reference has no counterpart.  Every view carries a grid of cells[] =
+ * (gz, gy, gx) cells (2D: gz == 1), 1 .. MVS_INTENSITY_MAX_CELLS per axis, with a gain a and an offset b per cell.
+ * THE CELL RULE, along an axis of n pixels with g cells (pixel centres at integer coordinates): the continuous coordinate c
+ * belongs to cell clamp(floor((c + 0.5) * g / n), 0, g - 1), evaluated in double, the product before the quotient; the centre of
+ * cell k is at (k + 0.5) * n / g - 0.5.
+ *
+ * mvs_intensity_pair_moments: the moments of mvs_pair_moments, split by the cells of both tiles.  fixed->matrix / offset and
+ * moving->matrix / offset map a grid index to a pixel of the respective tile; halfspaces, dtypes (uint8 / uint16 / float32, one
+ * for both views, else MVS_ERR_UNSUPPORTED), host / device memory and strided windows are as in mvs_pair_moments.  A record is a
+ * box of the grid, lo[k] <= index[k] < lo[k] + n[k] (z, y, x; 2D: lo[0] == 0, n[0] == 1), plus one cell of each tile.  A voxel of
+ * the box counts for the record iff
+ *   - it passes steps 1-4 of mvs_pair_moments (mask, both samples in bounds and finite; the same device code), and
+ *   - the cell rule puts its fixed pixel coordinate in cell_f and its moving pixel coordinate in cell_m on every axis.
+ * Boxes therefore only need to be conservative: a sample belongs to exactly one (cell_f, cell_m) whatever boxes the host chose.
+ * out (host memory) receives n_records rows of MVS_PAIR_MOMENTS_LEN doubles, (n, mean_f, mean_m, M2_f, M2_m, C_fm) of the
+ * counted pairs (all six 0 when n == 0).  1 <= n_records <= MVS_INTENSITY_MAX_RECORDS; callers batch above that.
+ * Launches: one for all records of the call -- record r owns min(max(ceil(voxels_r / MVS_INTENSITY_BLOCK_VOXELS), 1),
+ * MVS_INTENSITY_MAX_BLOCKS) consecutive workgroups, a function of its own voxel count only; a prefix table built on the host maps
+ * a workgroup to its record -- and a second one that folds each record's workgroup results.  Reduction as in mvs_pair_moments:
+ * per thread an integer count and float64 sums shifted by its first counted pair, then the update of Chan, Golub and LeVeque in a
+ * fixed tree (lanes by shuffles, waves through LDS, a record's workgroups in index order: each lane of one wave folds a run of
+ * ceil(blocks / 64) consecutive ones, then the lanes merge).  No floating-point atomics and no completion counters; a record's
+ * row does not depend on which other records share the call, and equal inputs give equal bits.  Waits for the result. */
+#define MVS_INTENSITY_MAX_CELLS 16
+#define MVS_INTENSITY_MAX_RECORDS 1024
+#define MVS_INTENSITY_BLOCK_VOXELS 256
+#define MVS_INTENSITY_MAX_BLOCKS 1024
+typedef struct {
+    int64_t lo[3], n[3];          /* box of the grid */
+    int32_t cell_f[3], cell_m[3]; /* the cell of the fixed / moving tile */
+} mvs_intensity_record_t;
+int mvs_intensity_pair_moments(int device, const mvs_view_t* fixed, const mvs_view_t* moving, int32_t ndim, const int32_t cells_f[3],
+                               const int32_t cells_m[3], const double* halfspaces, int32_t n_halfspaces,
+                               const mvs_intensity_record_t* records, int32_t n_records, double* out);
+
+/* mvs_intensity_apply: out(p) = a(p) * view(p) + b(p) for every voxel of a tile.  Only data / dtype / mem / shape / stride of
+ * `view` are read (uint8 / uint16 / float32; host C-contiguous, or device with stride[2] == 1).  coeff (host): (gz, gy, gx, 2)
+ * float32, (a, b) per cell.  tables (host): for the axes z, y, x in turn, shape[k] int32 followed by shape[k] float32 -- per pixel
+ * index the lower cell i of the two it lies between and the weight t of cell i + 1; the caller derives both in double from the
+ * cell rule (coordinate clamped to the first and last cell centre; an axis with one cell: i = 0, t = 0), so the kernel divides
+ * nothing.  The upper cell is min(i + 1, g - 1).
+ * Arithmetic: float32 without contraction, lerp(u, v, t) = u + t * (v - u).  Per row (z, y) the gx coefficient pairs are
+ * interpolated along z, then along y: lerp(lerp(c[z0][y0], c[z1][y0], tz), lerp(c[z0][y1], c[z1][y1], tz), ty); per voxel
+ * a = lerp(a[x0], a[x1], tx), b likewise, then y = a * (float)I + b.  A float32 output stores y (a NaN input stays NaN); an
+ * integer output stores rintf(y) (half to even) saturated to the type's range, a NaN as 0.
+ * out: C-contiguous, shape of the view, in out_mem; out_dtype is the view's dtype or float32 (else MVS_ERR_UNSUPPORTED).  out may
+ * be view->data itself for a contiguous device array with out_dtype == dtype (in place: every voxel is read once, by the lane that
+ * writes it, before it is written).  One wave per row: the row's coefficient pairs in LDS, then 16-byte loads / stores per lane
+ * along x (on the wider of the two element types) with a scalar head up to the row's first aligned element and a scalar tail; a
+ * row whose input and output alignments differ goes element by element.  Waits for the result; runs on the lane of `device`. */
+int mvs_intensity_apply(int device, const mvs_view_t* view, int32_t ndim, const int32_t cells[3], const float* coeff, const void* tables,
+                        void* out, int32_t out_dtype, int32_t out_mem);
+
 #ifdef __cplusplus
 }
 #endif

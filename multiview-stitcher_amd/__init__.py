@@ -10,9 +10,9 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # ``multiview_stitcher_amd.metrics`` without an explicit submodule import (loaded at first use: it binds the HIP library)
-    if name == "metrics":
+    # ``multiview_stitcher_amd.metrics`` / ``.intensity`` without an explicit submodule import (loaded at first use: they bind the HIP library)
+    if name in ("metrics", "intensity"):
         import importlib
 
-        return importlib.import_module(__name__ + ".metrics")
+        return importlib.import_module(__name__ + "." + name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

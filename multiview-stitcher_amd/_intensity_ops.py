@@ -1,0 +1,140 @@
+"""Thin array-level wrappers of the intensity harmonisation entry points of libmvs_hip.so (mvs_intensity_pair_moments,
+mvs_intensity_apply) and the host form of the cell rule they share with the planner and the solver of ``intensity.py``."""
+
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .transformation import fill_view_geometry, shape3, view_data
+
+
+# ---- the cell rule (include/mvs_hip.h) ------------------------------------------------------------------------------------------
+def cell_index(c, g, n):
+    """Cell of the continuous pixel coordinate(s) ``c`` along an axis of ``n`` pixels with ``g`` cells:
+    ``clamp(floor((c + 0.5) * g / n), 0, g - 1)`` in float64, the product before the quotient."""
+    k = np.floor((np.asarray(c, dtype=np.float64) + 0.5) * float(g) / float(n))
+    return np.clip(k, 0, g - 1).astype(np.int64)
+
+
+def cell_centres(g, n):
+    """Pixel coordinates of the centres of the ``g`` cells of an axis of ``n`` pixels: ``(k + 0.5) * n / g - 0.5``."""
+    return (np.arange(g, dtype=np.float64) + 0.5) * float(n) / float(g) - 0.5
+
+
+def axis_table(n, g):
+    """What mvs_intensity_apply reads per pixel index of one axis: ``(lower cell int32[n], weight float32[n])``.  The pixel
+    coordinate is clamped to the first and last cell centre; with ``u`` its position in units of the centre spacing, the lower cell
+    is ``min(floor(u), g - 2)`` and the weight of the cell above it ``u - lower``, both derived in float64.  ``g == 1``: cell 0,
+    weight 0."""
+    if g == 1:
+        return np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float32)
+    ctr = cell_centres(g, n)
+    p = np.clip(np.arange(n, dtype=np.float64), ctr[0], ctr[-1])
+    u = (p - ctr[0]) / (float(n) / float(g))
+    lower = np.clip(np.floor(u), 0, g - 2)
+    return lower.astype(np.int32), (u - lower).astype(np.float32)
+
+
+def _view(data, matrix, offset, device):
+    view = _lib.mvs_view_t()
+    ptr, s3, st3, mem, keep = view_data(data, device)
+    fill_view_geometry(view, ptr, _lib.DTYPE_CODES[np.dtype(keep.dtype)], mem, s3, st3, matrix, offset)
+    return view, keep
+
+
+def _i32x3(vals, ndim, fill):
+    vals = [int(v) for v in vals]
+    if len(vals) != ndim:
+        raise ValueError(f"expected {ndim} values, got {len(vals)}")
+    return (C.c_int32 * 3)(*([fill] * (3 - ndim) + vals))
+
+
+def cell_pair_moments(fixed, moving, fixed_affine, moving_affine, cells_f, cells_m, records, halfspaces=None, device=0, batch=None):
+    """Moments of the sample pairs of two tiles per record (mvs_intensity_pair_moments): an ``(R, 6)`` float64 array with the rows
+    ``(n, mean_f, mean_m, M2_f, M2_m, C_fm)``.
+
+    ``fixed`` / ``moving``: 2-D / 3-D tiles of one dtype, numpy arrays or ``DeviceArray`` windows; ``fixed_affine`` /
+    ``moving_affine = (matrix, offset)`` map a grid index to a pixel of the tile; ``cells_f`` / ``cells_m``: cells per axis.
+    ``records``: int64 array ``(R, 4, ndim)`` with the rows ``lo, n, cell_f, cell_m`` (``intensity.plan_records``).  ``halfspaces``
+    as in ``_metric_ops.pair_moments``.  Records go to the device in groups of ``batch`` (default and at most
+    MVS_INTENSITY_MAX_RECORDS); a record's row does not depend on its group."""
+    lib = _lib.init(device)
+    records = np.asarray(records, dtype=np.int64)
+    ndim = len(cells_f)
+    if ndim not in (2, 3) or records.ndim != 3 or records.shape[1:] != (4, ndim):
+        raise ValueError("cell_pair_moments needs 2-D or 3-D cells and records of shape (R, 4, ndim)")
+    batch = _lib.MVS_INTENSITY_MAX_RECORDS if batch is None else int(batch)
+    if not 1 <= batch <= _lib.MVS_INTENSITY_MAX_RECORDS:
+        raise ValueError(f"batch must be 1..{_lib.MVS_INTENSITY_MAX_RECORDS}")
+    fview, keep_f = _view(fixed, fixed_affine[0], fixed_affine[1], device)
+    mview, keep_m = _view(moving, moving_affine[0], moving_affine[1], device)
+    hs = np.zeros((0, ndim + 1)) if halfspaces is None else np.asarray(halfspaces, dtype=np.float64).reshape(-1, ndim + 1)
+    if len(hs) > _lib.MVS_PAIR_MAX_HALFSPACES:
+        raise ValueError(f"at most {_lib.MVS_PAIR_MAX_HALFSPACES} halfspaces")
+    hs3 = np.zeros((len(hs), 4))
+    hs3[:, 3 - ndim:] = hs                       # 2-D: a_z = 0
+    cf, cm = _i32x3(cells_f, ndim, 1), _i32x3(cells_m, ndim, 1)
+    out = np.zeros((len(records), _lib.MVS_PAIR_MOMENTS_LEN))
+    dp = C.POINTER(C.c_double)
+    k = 3 - ndim
+    for r0 in range(0, len(records), batch):
+        group = records[r0:r0 + batch]
+        recs = (_lib.mvs_intensity_record_t * len(group))()
+        for rec, row in zip(recs, group):
+            rec.lo[:] = [0] * k + row[0].tolist()
+            rec.n[:] = [1] * k + row[1].tolist()
+            rec.cell_f[:] = [0] * k + row[2].tolist()
+            rec.cell_m[:] = [0] * k + row[3].tolist()
+        res = np.zeros((len(group), _lib.MVS_PAIR_MOMENTS_LEN))
+        rc = lib.mvs_intensity_pair_moments(device, C.byref(fview), C.byref(mview), ndim, cf, cm, hs3.ctypes.data_as(dp) if len(hs3) else None,
+                                            len(hs3), recs, len(group), res.ctypes.data_as(dp))
+        _lib.check(rc, device, "mvs_intensity_pair_moments")
+        out[r0:r0 + len(group)] = res
+    del keep_f, keep_m
+    return out
+
+
+def apply_map(data, coeff, out=None, out_dtype=None, device=0):
+    """``a(p) * data + b(p)`` for one 2-D / 3-D tile (mvs_intensity_apply).  ``coeff``: float32 ``cells + (2,)``, gain and offset
+    per cell, interpolated multilinearly between the cell centres.  ``data``: numpy array or (possibly strided) ``DeviceArray``;
+    the result is of the same kind, of ``out_dtype`` (the input's dtype, the default, or float32).  ``out``: where the result goes
+    -- a contiguous array of the data's shape and ``out_dtype``; ``out is data`` corrects a contiguous array in place."""
+    from .device import DeviceArray, is_device_array
+
+    lib = _lib.init(device)
+    coeff = np.ascontiguousarray(coeff, dtype=np.float32)
+    ndim = coeff.ndim - 1
+    if ndim not in (2, 3) or coeff.shape[-1] != 2 or len(data.shape) != ndim:
+        raise ValueError("apply_map needs a 2-D or 3-D tile and coefficients of shape cells + (2,)")
+    cells = coeff.shape[:-1]
+    on_dev = is_device_array(data)
+    in_dtype = np.dtype(data.dtype)
+    if in_dtype not in _lib.DTYPE_CODES:
+        raise TypeError(f"unsupported dtype {in_dtype} (uint8 / uint16 / float32)")
+    out_dtype = in_dtype if out_dtype is None else np.dtype(out_dtype)
+    if out_dtype not in (in_dtype, np.dtype(np.float32)):
+        raise TypeError(f"out_dtype must be the input's dtype or float32, not {out_dtype}")
+    shape = tuple(int(s) for s in data.shape)
+    if out is None:
+        out = DeviceArray.empty(shape, out_dtype, device) if on_dev else np.empty(shape, dtype=out_dtype)
+    if is_device_array(out) != on_dev or tuple(out.shape) != shape or np.dtype(out.dtype) != out_dtype:
+        raise ValueError("out must be of the data's kind and shape and of out_dtype")
+    if not (out.is_contiguous() if on_dev else out.flags.c_contiguous):
+        raise ValueError("out must be contiguous")
+    view, keep = _view(data, np.eye(ndim), np.zeros(ndim), device)
+    tables = np.concatenate([part.view(np.uint8) for n, g in zip(shape3(shape), shape3(cells)) for part in axis_table(n, g)])
+    if on_dev:
+        out.wait_ready(device)
+        out_ptr, out_mem = out.ptr, _lib.MVS_MEM_DEVICE
+    else:
+        out_ptr, out_mem = out.ctypes.data, _lib.MVS_MEM_HOST
+    rc = lib.mvs_intensity_apply(device, C.byref(view), ndim, _i32x3(cells, ndim, 1), coeff.ctypes.data_as(C.POINTER(C.c_float)),
+                                 C.c_void_p(tables.ctypes.data), C.c_void_p(out_ptr), _lib.DTYPE_CODES[out_dtype], out_mem)
+    _lib.check(rc, device, "mvs_intensity_apply")
+    if on_dev:
+        out.mark_written()
+    del keep
+    return out

@@ -32,6 +32,10 @@ MVS_KNN_MAX_DIM = 15
 MVS_KNN_MAX_K = 16
 MVS_MARKER_MAX_NEIGHBORS = 5
 MVS_PSF_MAX_RADIUS = 31
+MVS_INTENSITY_MAX_CELLS = 16
+MVS_INTENSITY_MAX_RECORDS = 1024
+MVS_INTENSITY_BLOCK_VOXELS = 256
+MVS_INTENSITY_MAX_BLOCKS = 1024
 ERR_UNSUPPORTED = -4            # MVS_ERR_UNSUPPORTED
 
 DTYPE_CODES = {np.dtype(np.uint8): MVS_U8, np.dtype(np.uint16): MVS_U16, np.dtype(np.float32): MVS_F32}
@@ -105,6 +109,15 @@ class mvs_pair_job_t(C.Structure):
         ("wait_ticket", C.c_uint64 * 2),
         ("bin", C.c_int32 * 3),
         ("flags", C.c_int32),
+    ]
+
+
+class mvs_intensity_record_t(C.Structure):
+    _fields_ = [
+        ("lo", C.c_int64 * 3),
+        ("n", C.c_int64 * 3),
+        ("cell_f", C.c_int32 * 3),
+        ("cell_m", C.c_int32 * 3),
     ]
 
 
@@ -284,6 +297,15 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_int32),
          C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)],
+    ),
+    "mvs_intensity_pair_moments": (
+        C.c_int,
+        [C.c_int, C.POINTER(mvs_view_t), C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
+         C.c_int32, C.POINTER(mvs_intensity_record_t), C.c_int32, C.POINTER(C.c_double)],
+    ),
+    "mvs_intensity_apply": (
+        C.c_int,
+        [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32],
     ),
 }
 

@@ -12,8 +12,7 @@
 // no floating-point atomics, no completion counters, and a grid that depends on the voxel count only.
 #include "mvs_internal.h"
 #include "mvs_fuse_dev.h"
-#include "mvs_sample_dev.h"
-#include "mvs_pair_metrics_dev.h"
+#include "mvs_pair_voxel_dev.h"
 
 #include <algorithm>
 #include <cmath>
@@ -37,24 +36,6 @@ struct PairArgs {
 };
 static_assert(sizeof(PairArgs) <= 4096, "kernel arguments");
 
-__device__ __forceinline__ PairMoments shfl_down_moments(const PairMoments& r, int off) {
-    PairMoments o;
-    o.n = __shfl_down(r.n, off, 64);
-    o.mean_f = __shfl_down(r.mean_f, off, 64);
-    o.mean_m = __shfl_down(r.mean_m, off, 64);
-    o.m2_f = __shfl_down(r.m2_f, off, 64);
-    o.m2_m = __shfl_down(r.m2_m, off, 64);
-    o.c_fm = __shfl_down(r.c_fm, off, 64);
-    return o;
-}
-
-// lane 0 gets the moments of the whole wave: at every step a lane is the left operand and the lane `off` above it the right one
-__device__ __forceinline__ PairMoments wave_merge(PairMoments r) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) r = pair_moments_merge(r, shfl_down_moments(r, off));
-    return r;
-}
-
 template <typename T, int KMAX>
 __global__ __launch_bounds__(kPairBlockThreads) void pair_moments_kernel(PairArgs P) {
     PairSums acc[KMAX];
@@ -68,26 +49,18 @@ __global__ __launch_bounds__(kPairBlockThreads) void pair_moments_kernel(PairArg
         const int y = (int)(t % P.gy);
         const int z = (int)(t / P.gy);
         const double pz = (double)z, py = (double)y, px = (double)x;
-        bool inside = true;
-        for (int h = 0; h < P.n_hs; ++h) inside = inside && (((P.hs[h][0] * pz + P.hs[h][1] * py) + P.hs[h][2] * px) + P.hs[h][3] <= 0.0);
-        if (!inside) continue;
-        const DevView& F = P.fixed;
-        const double fz = ((pz * F.m[0] + py * F.m[1]) + px * F.m[2]) + F.off[0];
-        const double fy = ((pz * F.m[3] + py * F.m[4]) + px * F.m[5]) + F.off[1];
-        const double fx = ((pz * F.m[6] + py * F.m[7]) + px * F.m[8]) + F.off[2];
-        if (!view_in_bounds(F, fz, fy, fx)) continue;
-        const float f = sample_view<T, 1>(F, fz, fy, fx);
-        if (!isfinite(f)) continue;
+        if (!pair_mask_holds(P.hs, P.n_hs, pz, py, px)) continue;
+        double fz, fy, fx;
+        pair_grid_to_pixel(P.fixed.m, P.fixed.off, pz, py, px, fz, fy, fx);
+        float f;
+        if (!pair_sample_finite<T>(P.fixed, fz, fy, fx, &f)) continue;
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) {
             if (k >= P.n_cand) continue;
-            const double* m = P.cm[k];
-            const double cz = ((pz * m[0] + py * m[1]) + px * m[2]) + P.co[k][0];
-            const double cy = ((pz * m[3] + py * m[4]) + px * m[5]) + P.co[k][1];
-            const double cx = ((pz * m[6] + py * m[7]) + px * m[8]) + P.co[k][2];
-            if (!view_in_bounds(P.moving, cz, cy, cx)) continue;
-            const float v = sample_view<T, 1>(P.moving, cz, cy, cx);
-            if (isfinite(v)) pair_sums_add(acc[k], f, v);
+            double cz, cy, cx;
+            pair_grid_to_pixel(P.cm[k], P.co[k], pz, py, px, cz, cy, cx);
+            float v;
+            if (pair_sample_finite<T>(P.moving, cz, cy, cx, &v)) pair_sums_add(acc[k], f, v);
         }
     }
 

@@ -1,0 +1,48 @@
+// mvs_pair_voxel_dev.h -- internal, device only: what the kernels that reduce sample pairs over an overlap grid share
+// (mvs_pair_metrics.hip, mvs_intensity.hip): the per-voxel rule of mvs_pair_moments (halfspace mask, grid index -> pixel, in-bounds
+// test, linear float32 sample, finite test) and the wave step of the fixed merge tree.  One copy, so that a voxel counted by
+// either kernel is the same voxel with the same bits.
+#pragma once
+#include "mvs_sample_dev.h"
+#include "mvs_pair_metrics_dev.h"
+
+// step 1: ((a_z z + a_y y) + a_x x) + b <= 0 for every row of `hs`
+__device__ __forceinline__ bool pair_mask_holds(const double (*hs)[4], int n_hs, double pz, double py, double px) {
+    bool inside = true;
+    for (int h = 0; h < n_hs; ++h) inside = inside && (((hs[h][0] * pz + hs[h][1] * py) + hs[h][2] * px) + hs[h][3] <= 0.0);
+    return inside;
+}
+
+// grid index -> pixel: c = ((z m0 + y m1) + x m2) + offset per axis (`m`: 9 doubles row-major, `off`: 3)
+__device__ __forceinline__ void pair_grid_to_pixel(const double* m, const double* off, double pz, double py, double px, double& cz, double& cy,
+                                                   double& cx) {
+    cz = ((pz * m[0] + py * m[1]) + px * m[2]) + off[0];
+    cy = ((pz * m[3] + py * m[4]) + px * m[5]) + off[1];
+    cx = ((pz * m[6] + py * m[7]) + px * m[8]) + off[2];
+}
+
+// steps 2-4 for one tile at an in-bounds-tested coordinate: false when the coordinate is out of bounds or the sample is not finite
+template <typename T>
+__device__ __forceinline__ bool pair_sample_finite(const DevView& V, double cz, double cy, double cx, float* v) {
+    if (!view_in_bounds(V, cz, cy, cx)) return false;
+    *v = sample_view<T, 1>(V, cz, cy, cx);
+    return isfinite(*v);
+}
+
+__device__ __forceinline__ PairMoments shfl_down_moments(const PairMoments& r, int off) {
+    PairMoments o;
+    o.n = __shfl_down(r.n, off, 64);
+    o.mean_f = __shfl_down(r.mean_f, off, 64);
+    o.mean_m = __shfl_down(r.mean_m, off, 64);
+    o.m2_f = __shfl_down(r.m2_f, off, 64);
+    o.m2_m = __shfl_down(r.m2_m, off, 64);
+    o.c_fm = __shfl_down(r.c_fm, off, 64);
+    return o;
+}
+
+// lane 0 gets the moments of the whole wave: at every step a lane is the left operand and the lane `off` above it the right one
+__device__ __forceinline__ PairMoments wave_merge(PairMoments r) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) r = pair_moments_merge(r, shfl_down_moments(r, off));
+    return r;
+}
