@@ -773,6 +773,48 @@ int mvs_intensity_pair_moments(int device, const mvs_view_t* fixed, const mvs_vi
 int mvs_intensity_apply(int device, const mvs_view_t* view, int32_t ndim, const int32_t cells[3], const float* coeff, const void* tables,
                         void* out, int32_t out_dtype, int32_t out_mem);
 
+/* Shading (flat-field) correction (intensity.estimate_shading / apply_shading): remove the vignetting and uneven illumination that
+ * every tile of an acquisition shares.  The reference has no counterpart.  The profile is estimated from a per-pixel order
+ * statistic over the stack of all tiles and planes (mvs_stack_quantiles), smoothed and normalised on the host, and applied as a
+ * per-pixel gain / offset plane (mvs_plane_apply).
+ *
+ * mvs_stack_quantiles: 1 <= n_views <= MVS_STACK_MAX_VIEWS tiles of one dtype (uint8 / uint16 / float32) and one (H, W) =
+ * (shape[1], shape[2]); shape[0] may differ per view (2D: 1).  Only data / dtype / mem / shape / stride are read; stride[2] == 1,
+ * stride[0] and stride[1] are arbitrary (windows, every k-th plane); host or device memory per view.  Anything else:
+ * MVS_ERR_UNSUPPORTED.
+ * THE SAMPLE SET of pixel (y, x) is view_v(z, y, x) over all v, z.  A float32 NaN is not a sample; +-inf are; -0 counts as +0.
+ * n(y, x), the number of samples, goes to count_out (host, H x W int32); more than 2^31 - 1 planes in all are refused.
+ * THE RANK RULE: out (host, n_q x H x W float32; 1 <= n_q <= MVS_STACK_MAX_QUANTILES, 0 <= q[j] <= 1) receives in out[j][y][x]
+ * the sample of ascending 0-based rank floor((double)(n - 1) * q[j]), NaN where n == 0: numpy's quantile(..., method="lower")
+ * (nanquantile for float32).  The result is a selection: exact, independent of the order of the views, of how planes are shared
+ * among waves and workgroups and of host / device / window inputs; equal inputs give equal bits.
+ * Algorithm (csrc/mvs_stack_select.h): most-significant-digit radix select with 8-bit digits on an order-preserving unsigned key
+ * (the value itself for integers: 1 / 2 digits; for float32 the sign-flipped bit pattern, -0 first mapped to +0: 4 digits).  A
+ * workgroup owns a strip of 128 bytes of one row (128 / 64 / 32 pixels; the last strip of a row may be shorter) for all samples
+ * and keeps the strip's 256 bins per pixel as 32-bit counters in LDS (128 / 64 / 32 KiB; they cannot overflow); there are no
+ * histograms in global memory.  Half a wave loads one plane's 128 bytes, 4 bytes per lane (element by element where the row is
+ * not 4-byte aligned), and the 32 half waves of a workgroup take different planes of a device-side table of the views.  The top
+ * digit is counted once for all quantiles, every further digit once per quantile over the samples that share the pixel's prefix:
+ * the stack is read 1 + n_q * (digits - 1) times.  Integer LDS atomics only; no floating-point atomics.
+ * Host views are packed into one device block of their total size for the duration of the call (pageable uploads at the rate
+ * of the link, row by row for strided host windows): callers that ask more than once keep their tiles resident.
+ * Waits for the result; runs on the context lane of `device`. */
+#define MVS_STACK_MAX_VIEWS 4096
+#define MVS_STACK_MAX_QUANTILES 4
+int mvs_stack_quantiles(int device, const mvs_view_t* views, int32_t n_views, int32_t ndim, const double* q, int32_t n_q, float* out,
+                        int32_t* count_out);
+
+/* mvs_plane_apply: out(z, y, x) = a(y, x) * (float)view(z, y, x) + b(y, x).  view, out, out_dtype, out_mem, the float32
+ * arithmetic without contraction, the rounding of integer outputs (rintf, saturated, a NaN stored as 0; a float32 output keeps
+ * NaN) and in-place use are exactly those of mvs_intensity_apply.  coeff: (H, W, 2) float32, (a, b) per pixel, in coeff_mem =
+ * host (uploaded by the call) or device memory (used in place: callers that correct many tiles upload once).
+ * A wave takes one row y and a slab of planes; a lane keeps the coefficient pairs of its consecutive pixels in registers and walks
+ * z, so the coefficient plane is read once per slab and not once per voxel.  16-byte loads / stores along x (on the wider of the
+ * two element types) with a scalar head up to the row's first aligned element and a scalar tail; a row whose input and output
+ * alignments differ, or change from plane to plane, goes pixel by pixel.  Waits for the result; runs on the lane of `device`. */
+int mvs_plane_apply(int device, const mvs_view_t* view, int32_t ndim, const float* coeff, int32_t coeff_mem, void* out, int32_t out_dtype,
+                    int32_t out_mem);
+
 #ifdef __cplusplus
 }
 #endif

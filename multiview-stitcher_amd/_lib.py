@@ -36,6 +36,8 @@ MVS_INTENSITY_MAX_CELLS = 16
 MVS_INTENSITY_MAX_RECORDS = 1024
 MVS_INTENSITY_BLOCK_VOXELS = 256
 MVS_INTENSITY_MAX_BLOCKS = 1024
+MVS_STACK_MAX_VIEWS = 4096
+MVS_STACK_MAX_QUANTILES = 4
 ERR_UNSUPPORTED = -4            # MVS_ERR_UNSUPPORTED
 
 DTYPE_CODES = {np.dtype(np.uint8): MVS_U8, np.dtype(np.uint16): MVS_U16, np.dtype(np.float32): MVS_F32}
@@ -306,6 +308,14 @@ SIGNATURES = {
     "mvs_intensity_apply": (
         C.c_int,
         [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32],
+    ),
+    "mvs_stack_quantiles": (
+        C.c_int,
+        [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)],
+    ),
+    "mvs_plane_apply": (
+        C.c_int,
+        [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32],
     ),
 }
 

@@ -11,13 +11,17 @@ at ``(k + 0.5) * n / g - 0.5`` (``_intensity_ops.cell_index`` / ``cell_centres``
 ``a, b`` as constant per cell; the correction ``I' = a(p) I + b(p)`` interpolates them multilinearly between the cell centres.
 
 The voxel work runs in two kernels (csrc/mvs_intensity.hip): mvs_intensity_pair_moments reduces the overlap of a pair to six
-moments per pair of cells, mvs_intensity_apply corrects a tile.  The planner and the solver below are host algebra in float64."""
+moments per pair of cells, mvs_intensity_apply corrects a tile.  The planner and the solver below are host algebra in float64.
+
+``estimate_shading`` / ``apply_shading`` remove what the overlaps cannot show: the shading every tile shares (vignetting, uneven
+illumination).  The per-pixel order statistics of the stack of all tiles come from mvs_stack_quantiles, the correction runs in
+mvs_plane_apply (csrc/mvs_shading.hip); the smoothing and normalisation between the two are host algebra in float64."""
 
 from __future__ import annotations
 
 import numpy as np
 
-from . import _intensity_ops, metrics, msi_utils, mv_graph
+from . import _intensity_ops, _shading_ops, metrics, msi_utils, mv_graph
 from . import spatial_image_utils as si_utils
 from ._intensity_ops import axis_table, cell_centres, cell_index  # noqa: F401  (part of this module's interface)
 from .transformation import get_pixel_affine
@@ -298,12 +302,14 @@ def fit_maps(msims, transform_key, cells=1, pairs=None, step=1, channel_index=0,
     return solve_maps(per_view, records, lambda_identity, lambda_smooth, min_samples, reference_view, normalize, return_info)
 
 
-def _apply_sim(sim, vmap, out_dtype, inplace, device):
+def _apply_sim(sim, vmap, out_dtype, inplace, device, apply_one=_intensity_ops.apply_map, who="apply_maps"):
+    """One spatial image through ``apply_one(data, coeff, out=, out_dtype=, device=)``, leading c / t dims looped; ``vmap``: the
+    coefficients, or a dict of them per channel coordinate."""
     from .device import DeviceArray, is_device_array
 
     lead = [d for d in sim.dims if d in ("c", "t")]
     if list(sim.dims[:len(lead)]) != lead:
-        raise ValueError("apply_maps needs the c / t dims in front of the spatial ones")
+        raise ValueError(f"{who} needs the c / t dims in front of the spatial ones")
     data = sim.data
     on_dev = is_device_array(data)
     dtype = np.dtype(data.dtype) if out_dtype is None else np.dtype(out_dtype)
@@ -318,28 +324,17 @@ def _apply_sim(sim, vmap, out_dtype, inplace, device):
             coeff = vmap[sim.coords["c"][idx[lead.index("c")]].item() if "c" in lead else next(iter(vmap))]
         else:
             coeff = vmap
-        _intensity_ops.apply_map(data[idx] if idx else data, coeff, out=out[idx] if idx else out, out_dtype=dtype, device=device)
+        apply_one(data[idx] if idx else data, coeff, out=out[idx] if idx else out, out_dtype=dtype, device=device)
     return sim if inplace else sim.copy(data=out)
 
 
-def apply_maps(msims, maps, out_dtype=None, inplace=False, device=0):
-    """``I' = a(p) I + b(p)`` for every view (mvs_intensity_apply): images of the kind given -- multiscale or spatial, host or
-    resident -- with all attributes, transforms and coordinates carried over.
-
-    ``maps``: per view one array ``cells + (2,)`` (``fit_maps``), applied to all channels and time points, or a dict of such
-    arrays per channel coordinate.  ``out_dtype``: the view's dtype (default; integer results are rounded half to even and
-    saturated) or float32.  ``inplace=True`` overwrites the views' (contiguous) arrays.  Leading ``c`` / ``t`` dims are looped.
-
-    Of a multiscale image only scale0 goes through the kernel.  The further levels of a host-backed image are rebuilt from the
-    corrected scale0 by ``msi_utils.get_msim_from_sim`` with the factors of the given pyramid; a resident image keeps scale0
-    only (the pyramid helper averages on the host)."""
+def _apply_views(msims, per_view, out_dtype, inplace, device, apply_one=_intensity_ops.apply_map, who="apply_maps"):
+    """Every view through ``_apply_sim`` with its own coefficients; multiscale images are rebuilt around the corrected scale0."""
     from .device import is_device_array
 
-    if len(maps) != len(msims):
-        raise ValueError("one map per view")
     out = []
-    for image, vmap in zip(msims, maps):
-        sim = _apply_sim(_as_sim(image), vmap, out_dtype, inplace, device)
+    for image, vmap in zip(msims, per_view):
+        sim = _apply_sim(_as_sim(image), vmap, out_dtype, inplace, device, apply_one, who)
         if not msi_utils.is_msim(image):
             out.append(sim)
             continue
@@ -355,3 +350,169 @@ def apply_maps(msims, maps, out_dtype=None, inplace=False, device=0):
         res.point_sets = dict(getattr(image, "point_sets", {}))
         out.append(res)
     return out
+
+
+def apply_maps(msims, maps, out_dtype=None, inplace=False, device=0):
+    """``I' = a(p) I + b(p)`` for every view (mvs_intensity_apply): images of the kind given -- multiscale or spatial, host or
+    resident -- with all attributes, transforms and coordinates carried over.
+
+    ``maps``: per view one array ``cells + (2,)`` (``fit_maps``), applied to all channels and time points, or a dict of such
+    arrays per channel coordinate.  ``out_dtype``: the view's dtype (default; integer results are rounded half to even and
+    saturated) or float32.  ``inplace=True`` overwrites the views' (contiguous) arrays.  Leading ``c`` / ``t`` dims are looped.
+
+    Of a multiscale image only scale0 goes through the kernel.  The further levels of a host-backed image are rebuilt from the
+    corrected scale0 by ``msi_utils.get_msim_from_sim`` with the factors of the given pyramid; a resident image keeps scale0
+    only (the pyramid helper averages on the host)."""
+    if len(maps) != len(msims):
+        raise ValueError("one map per view")
+    return _apply_views(msims, maps, out_dtype, inplace, device)
+
+
+# ---- shading (flat-field) correction ---------------------------------------------------------------------------------------------
+# fit_maps sees only the overlaps, so it cannot remove what every tile shares: the vignetting and uneven illumination of the one
+# objective and camera, which leave a lattice across a fused mosaic.  The retrospective estimate of that profile is a per-pixel
+# order statistic over the stack of all tiles and planes (mvs_stack_quantiles), smoothed and normalised to mean 1 on the host;
+# the correction I' = (I - D) / F + mean(D) is one gain and one offset per pixel (mvs_plane_apply).  The reference has no
+# counterpart; BigStitcher's flat-field correction, MIST and BaSiC are the model (BaSiC's low-rank fit is out of scope).
+# The median of a pixel sees the background only where the sample is sparse: ``quantile`` is the knob.
+SHADING_FIT_ROWS = 256            # rows of the design matrix of the polynomial fit that are built at a time
+
+
+def _unit_coordinates(n):
+    return np.zeros(1) if n == 1 else np.linspace(-1.0, 1.0, n)
+
+
+def _legendre_smooth(plane, valid, degree):
+    """Least squares fit of ``plane`` on ``valid`` by the products ``P_i(y) P_j(x)``, ``i + j <= degree``, of Legendre polynomials
+    in coordinates scaled to [-1, 1], evaluated on all pixels."""
+    from numpy.polynomial import legendre
+
+    h, w = plane.shape
+    vy, vx = legendre.legvander(_unit_coordinates(h), degree), legendre.legvander(_unit_coordinates(w), degree)
+    terms = [(i, j) for i in range(degree + 1) for j in range(degree + 1 - i)]
+    if int(valid.sum()) < len(terms):
+        raise ValueError(f"shading: {int(valid.sum())} usable pixels cannot carry a polynomial of {len(terms)} terms")
+    ti, tj = np.array([t[0] for t in terms]), np.array([t[1] for t in terms])
+    ata, atb = np.zeros((len(terms), len(terms))), np.zeros(len(terms))
+    for y0 in range(0, h, SHADING_FIT_ROWS):
+        rows = slice(y0, min(y0 + SHADING_FIT_ROWS, h))
+        a = (vy[rows][:, None, ti] * vx[None, :, tj])[valid[rows]]
+        ata += a.T @ a
+        atb += a.T @ plane[rows][valid[rows]]
+    coef = np.linalg.lstsq(ata, atb, rcond=None)[0]
+    cmat = np.zeros((degree + 1, degree + 1))
+    cmat[ti, tj] = coef
+    return vy @ cmat @ vx.T
+
+
+def _smooth_plane(plane, valid, degree, sigma):
+    """``plane`` (float64) smoothed over its ``valid`` pixels and filled in on the others: polynomial (``degree``), NaN-aware
+    normalised Gaussian (``sigma``, mode="nearest"), or as it is with the mean of the valid pixels elsewhere."""
+    if not valid.any():
+        raise ValueError("shading: no pixel has enough samples")
+    if degree is not None and sigma is not None:
+        raise ValueError("shading: give degree or sigma, not both")
+    if degree is not None:
+        return _legendre_smooth(np.where(valid, plane, 0.0), valid, int(degree))
+    if sigma is not None:
+        from scipy import ndimage
+
+        num = ndimage.gaussian_filter(np.where(valid, plane, 0.0), sigma, mode="nearest")
+        den = ndimage.gaussian_filter(valid.astype(np.float64), sigma, mode="nearest")
+        ok = den > 1e-12
+        res = np.where(ok, num / np.where(ok, den, 1.0), 0.0)
+        return np.where(ok, res, res[ok].mean())
+    return np.where(valid, plane, plane[valid].mean())
+
+
+def shading_from_planes(planes, counts, darkfield=None, degree=4, sigma=None, min_samples=8, min_flat=0.1):
+    """The shading model from the order statistics of ``_shading_ops.stack_quantiles``.  Host only, float64.
+
+    ``R = planes[-1] - D``.  ``darkfield``: ``None`` (D = 0), a scalar or an ``(H, W)`` array the caller measured, or
+    ``"quantile"``: the smoothed ``planes[0]`` (``estimate_shading(dark_quantile=...)``).  Pixels with ``counts < min_samples`` or a
+    non-finite R are left out of the fit.  Smoothing: ``degree`` -- least squares on the products of Legendre polynomials of total
+    degree <= ``degree`` in coordinates scaled to [-1, 1] (the default: a Gaussian biases a paraboloid by more than 10 % at the tile
+    border); ``sigma`` (with ``degree=None``) -- a NaN-aware normalised Gaussian, mode="nearest"; neither -- the raw plane.  Then
+    ``F /= mean(F)`` and ``F = max(F, min_flat)``.
+
+    Returns ``{"flatfield": F, "darkfield": D, "offset": mean(D)}``: float32 ``(H, W)`` arrays and a float."""
+    planes = np.asarray(planes, dtype=np.float64)
+    counts = np.asarray(counts)
+    if planes.ndim != 3 or counts.shape != planes.shape[1:]:
+        raise ValueError("shading_from_planes needs planes (n_q, H, W) and counts (H, W)")
+    enough = counts >= int(min_samples)
+    if isinstance(darkfield, str):
+        if darkfield != "quantile" or len(planes) < 2:
+            raise ValueError('darkfield="quantile" needs two planes: the dark and the bright quantile')
+        dark = _smooth_plane(planes[0], enough & np.isfinite(planes[0]), degree, sigma)
+    elif darkfield is None:
+        dark = np.zeros(planes.shape[1:])
+    else:
+        dark = np.broadcast_to(np.asarray(darkfield, dtype=np.float64), planes.shape[1:]).copy()
+    with np.errstate(invalid="ignore"):
+        raw = planes[-1] - dark
+    flat = _smooth_plane(raw, enough & np.isfinite(raw), degree, sigma)
+    flat = flat / flat.mean()
+    flat = np.maximum(flat, float(min_flat))
+    return {"flatfield": flat.astype(np.float32), "darkfield": dark.astype(np.float32), "offset": float(dark.mean())}
+
+
+def shading_coefficients(shading):
+    """The ``(H, W, 2)`` float32 gain / offset plane of a shading model for ``_shading_ops.apply_plane``: ``a = 1 / F``,
+    ``b = offset - D / F``, derived in float64, so that ``I' = (I - D) / F + offset``."""
+    flat = np.asarray(shading["flatfield"], dtype=np.float64)
+    dark = np.broadcast_to(np.asarray(shading["darkfield"], dtype=np.float64), flat.shape)
+    return np.stack([1.0 / flat, float(shading["offset"]) - dark / flat], axis=-1).astype(np.float32)
+
+
+def _shading_tiles(msims, channel_index, plane_step):
+    """The tiles of the stack: channel ``channel_index`` of every view and time point, every ``plane_step``-th plane by stride."""
+    tiles = []
+    for image in msims:
+        sim = _as_sim(image)
+        lead = [d for d in sim.dims if d in ("c", "t")]
+        if list(sim.dims[:len(lead)]) != lead:
+            raise ValueError("estimate_shading needs the c / t dims in front of the spatial ones")
+        data = sim.data
+        for idx in np.ndindex(*[1 if d == "c" else n for d, n in zip(lead, data.shape)]):
+            idx = tuple(channel_index if d == "c" else i for d, i in zip(lead, idx))
+            tiles.append(_shading_ops.every_kth_plane(data[idx] if idx else data, plane_step))
+    return tiles
+
+
+def estimate_shading(msims, channel_index=0, quantile=0.5, dark_quantile=None, plane_step=1, darkfield=None, degree=4, sigma=None,
+                     min_samples=8, min_flat=0.1, device=0, return_info=False):
+    """The shading all tiles of an acquisition share, for ``apply_shading``: ``{"flatfield", "darkfield", "offset"}``.
+
+    ``msims``: multiscale or spatial images of one tile shape and dtype, numpy- or ``DeviceArray``-backed (resident tiles are read
+    in place).  Channel ``channel_index`` of every view and time point and every ``plane_step``-th plane (by stride, no copy) form
+    the stack; per pixel of the tile the sample of quantile ``quantile`` -- and of ``dark_quantile``, when given, as the dark field
+    -- is selected on the device (mvs_stack_quantiles: exact, numpy's ``method="lower"``, NaNs left out) and handed to
+    ``shading_from_planes`` with ``darkfield``, ``degree``, ``sigma``, ``min_samples`` and ``min_flat``.
+
+    The estimate assumes that over the stack every pixel sees the same distribution of content: many tiles, and a ``quantile`` that
+    lands on comparable structure everywhere (the median sees the background only where the sample is sparse).
+
+    ``return_info=True``: also ``{"planes", "counts", "q"}``, the raw order statistics."""
+    tiles = _shading_tiles(msims, channel_index, plane_step)
+    q = [float(quantile)] if dark_quantile is None else [float(dark_quantile), float(quantile)]
+    planes, counts = _shading_ops.stack_quantiles(tiles, q, device)
+    shading = shading_from_planes(planes, counts, "quantile" if dark_quantile is not None else darkfield, degree, sigma, min_samples, min_flat)
+    return (shading, {"planes": planes, "counts": counts, "q": q}) if return_info else shading
+
+
+def apply_shading(msims, shading, out_dtype=None, inplace=False, device=0):
+    """``I' = (I - D) / F + mean(D)`` for every view (mvs_plane_apply), with the conventions of ``apply_maps``: images of the kind
+    given -- multiscale or spatial, host or resident -- leading ``c`` / ``t`` dims looped, ``out_dtype`` the view's dtype (rounded
+    half to even and saturated) or float32, ``inplace=True`` overwriting contiguous arrays, the pyramid of a host-backed multiscale
+    image rebuilt from the corrected scale0.
+
+    ``shading``: one model (``estimate_shading``) for all channels, or a dict of models per channel coordinate.  The coefficient
+    plane of a model is derived once (``shading_coefficients``) and uploaded once for all views of the call."""
+    from .device import DeviceArray
+
+    def resident(model):
+        return DeviceArray.from_host(shading_coefficients(model), device)
+
+    coeff = resident(shading) if "flatfield" in shading else {k: resident(m) for k, m in shading.items()}
+    return _apply_views(msims, [coeff] * len(msims), out_dtype, inplace, device, _shading_ops.apply_plane, "apply_shading")
