@@ -4,19 +4,9 @@ import pytest
 from scipy import ndimage
 
 from oracle import reg_oracle as ro
+from tests.helpers import _check_scores, _pair
 
 pytestmark = pytest.mark.gpu
-
-
-def _pair(shape, shift, seed=0, sigma=1.0, noise=0.0):
-    rng = np.random.default_rng(seed)
-    pad = 12
-    big = ndimage.gaussian_filter(rng.random(tuple(s + 2 * pad for s in shape)), sigma).astype(np.float32)
-    a = np.ascontiguousarray(big[tuple(slice(pad, pad + s) for s in shape)])
-    b = np.ascontiguousarray(big[tuple(slice(pad + d, pad + d + s) for d, s in zip(shift, shape))])
-    if noise:
-        b = b + noise * rng.standard_normal(shape).astype(np.float32)
-    return a, b
 
 
 # power-of-two, odd, prime and mixed sizes: the transform length is the overlap shape itself
@@ -72,39 +62,6 @@ def test_rescale_intensity(hip_device, shape):
     assert mn == np.nanmin(im) and mx == np.nanmax(im) and nv == np.sum(~np.isnan(im))
     np.testing.assert_array_equal(np.isnan(got), np.isnan(want))
     np.testing.assert_allclose(got[~np.isnan(got)], want[~np.isnan(want)], rtol=0, atol=1.2e-7)
-
-
-def _check_scores(a, b, t_cands, region_mode):
-    """mvs_score_candidates against the oracle's candidate loop on rescaled inputs."""
-    from multiview_stitcher_amd import _reg_ops
-
-    im0, im1 = ro.rescale_intensity_01(a), ro.rescale_intensity_01(b)
-    im0nm = np.isnan(im0)
-    data_range = np.nanmax([im0, im1]) - np.nanmin([im0, im1])
-    im1_min = np.nanmin(im1)
-    valid1 = np.sum(~np.isnan(im1))
-    im0_bb = ro.get_bb_from_nanmask(~im0nm)
-    ssim, spear, codes = _reg_ops.score_candidates(im0, im1, t_cands, region_mode, data_range, im1_min)
-    for i, t in enumerate(t_cands):
-        code, s, q = ro.score_candidate(im0, im1, im0nm, t, valid1, region_mode, data_range, im1_min, im0_bb)
-        assert codes[i] == code, (i, t, codes[i], code)
-        if code == 0:
-            assert abs(ssim[i] - s) <= 2e-5 * max(abs(s), 1e-3), (i, t, ssim[i], s)
-            assert abs(spear[i] - q) <= 1e-5, (i, t, spear[i], q)
-        elif code == 1:
-            assert ssim[i] == -1 and spear[i] == -1
-    # quality_for_all=False: same SSIM / codes; Spearman only for the best-SSIM candidate(s), NaN for the rest
-    ssim2, spear2, codes2 = _reg_ops.score_candidates(im0, im1, t_cands, region_mode, data_range, im1_min, quality_for_all=False)
-    np.testing.assert_array_equal(codes2, codes)
-    np.testing.assert_array_equal(ssim2, ssim)
-    listed = [i for i in range(len(codes)) if codes[i] != 2]
-    if listed:
-        best = np.nanmax([ssim[i] for i in listed])
-        for i in listed:
-            if ssim[i] == best or codes[i] == 1:
-                assert spear2[i] == spear[i], (i, spear2[i], spear[i])
-            else:
-                assert np.isnan(spear2[i])
 
 
 @pytest.mark.parametrize("shape,shift", [((60, 104), (3, -5)), ((24, 40, 36), (2, -3, 4)), ((1, 50, 64), (0, 4, 2))])
