@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .transformation import fill_view_geometry, shape3, view_data
+from .transformation import shape3, tile_view
 
 
 # ---- the cell rule (include/mvs_hip.h) ------------------------------------------------------------------------------------------
@@ -38,13 +38,6 @@ def axis_table(n, g):
     return lower.astype(np.int32), (u - lower).astype(np.float32)
 
 
-def _view(data, matrix, offset, device):
-    view = _lib.mvs_view_t()
-    ptr, s3, st3, mem, keep = view_data(data, device)
-    fill_view_geometry(view, ptr, _lib.DTYPE_CODES[np.dtype(keep.dtype)], mem, s3, st3, matrix, offset)
-    return view, keep
-
-
 def _i32x3(vals, ndim, fill):
     vals = [int(v) for v in vals]
     if len(vals) != ndim:
@@ -69,8 +62,8 @@ def cell_pair_moments(fixed, moving, fixed_affine, moving_affine, cells_f, cells
     batch = _lib.MVS_INTENSITY_MAX_RECORDS if batch is None else int(batch)
     if not 1 <= batch <= _lib.MVS_INTENSITY_MAX_RECORDS:
         raise ValueError(f"batch must be 1..{_lib.MVS_INTENSITY_MAX_RECORDS}")
-    fview, keep_f = _view(fixed, fixed_affine[0], fixed_affine[1], device)
-    mview, keep_m = _view(moving, moving_affine[0], moving_affine[1], device)
+    fview, keep_f = tile_view(fixed, fixed_affine[0], fixed_affine[1], device)
+    mview, keep_m = tile_view(moving, moving_affine[0], moving_affine[1], device)
     hs = np.zeros((0, ndim + 1)) if halfspaces is None else np.asarray(halfspaces, dtype=np.float64).reshape(-1, ndim + 1)
     if len(hs) > _lib.MVS_PAIR_MAX_HALFSPACES:
         raise ValueError(f"at most {_lib.MVS_PAIR_MAX_HALFSPACES} halfspaces")
@@ -97,19 +90,13 @@ def cell_pair_moments(fixed, moving, fixed_affine, moving_affine, cells_f, cells
     return out
 
 
-def apply_map(data, coeff, out=None, out_dtype=None, device=0):
-    """``a(p) * data + b(p)`` for one 2-D / 3-D tile (mvs_intensity_apply).  ``coeff``: float32 ``cells + (2,)``, gain and offset
-    per cell, interpolated multilinearly between the cell centres.  ``data``: numpy array or (possibly strided) ``DeviceArray``;
-    the result is of the same kind, of ``out_dtype`` (the input's dtype, the default, or float32).  ``out``: where the result goes
-    -- a contiguous array of the data's shape and ``out_dtype``; ``out is data`` corrects a contiguous array in place."""
+def apply_to_tile(name, data, out, out_dtype, device, call):
+    """What ``apply_map`` and ``_shading_ops.apply_plane`` share: the result is of the data's kind and of ``out_dtype`` (the input's
+    dtype, the default, or float32); ``out`` (allocated when None) is a contiguous array of the data's kind and shape and of
+    ``out_dtype``.  ``call(view, out_ptr, out_dtype_code, out_mem)`` runs entry point ``name`` and returns its code."""
     from .device import DeviceArray, is_device_array
 
-    lib = _lib.init(device)
-    coeff = np.ascontiguousarray(coeff, dtype=np.float32)
-    ndim = coeff.ndim - 1
-    if ndim not in (2, 3) or coeff.shape[-1] != 2 or len(data.shape) != ndim:
-        raise ValueError("apply_map needs a 2-D or 3-D tile and coefficients of shape cells + (2,)")
-    cells = coeff.shape[:-1]
+    ndim = len(data.shape)
     on_dev = is_device_array(data)
     in_dtype = np.dtype(data.dtype)
     if in_dtype not in _lib.DTYPE_CODES:
@@ -124,17 +111,30 @@ def apply_map(data, coeff, out=None, out_dtype=None, device=0):
         raise ValueError("out must be of the data's kind and shape and of out_dtype")
     if not (out.is_contiguous() if on_dev else out.flags.c_contiguous):
         raise ValueError("out must be contiguous")
-    view, keep = _view(data, np.eye(ndim), np.zeros(ndim), device)
-    tables = np.concatenate([part.view(np.uint8) for n, g in zip(shape3(shape), shape3(cells)) for part in axis_table(n, g)])
+    view, keep = tile_view(data, np.eye(ndim), np.zeros(ndim), device)
     if on_dev:
         out.wait_ready(device)
         out_ptr, out_mem = out.ptr, _lib.MVS_MEM_DEVICE
     else:
         out_ptr, out_mem = out.ctypes.data, _lib.MVS_MEM_HOST
-    rc = lib.mvs_intensity_apply(device, C.byref(view), ndim, _i32x3(cells, ndim, 1), coeff.ctypes.data_as(C.POINTER(C.c_float)),
-                                 C.c_void_p(tables.ctypes.data), C.c_void_p(out_ptr), _lib.DTYPE_CODES[out_dtype], out_mem)
-    _lib.check(rc, device, "mvs_intensity_apply")
+    _lib.check(call(C.byref(view), C.c_void_p(out_ptr), _lib.DTYPE_CODES[out_dtype], out_mem), device, name)
     if on_dev:
         out.mark_written()
     del keep
     return out
+
+
+def apply_map(data, coeff, out=None, out_dtype=None, device=0):
+    """``a(p) * data + b(p)`` for one 2-D / 3-D tile (mvs_intensity_apply).  ``coeff``: float32 ``cells + (2,)``, gain and offset
+    per cell, interpolated multilinearly between the cell centres.  ``data``: numpy array or (possibly strided) ``DeviceArray``;
+    the result is of the same kind, of ``out_dtype`` (the input's dtype, the default, or float32).  ``out``: where the result goes
+    -- a contiguous array of the data's shape and ``out_dtype``; ``out is data`` corrects a contiguous array in place."""
+    lib = _lib.init(device)
+    coeff = np.ascontiguousarray(coeff, dtype=np.float32)
+    ndim = coeff.ndim - 1
+    if ndim not in (2, 3) or coeff.shape[-1] != 2 or len(data.shape) != ndim:
+        raise ValueError("apply_map needs a 2-D or 3-D tile and coefficients of shape cells + (2,)")
+    cells = coeff.shape[:-1]
+    tables = np.concatenate([part.view(np.uint8) for n, g in zip(shape3(data.shape), shape3(cells)) for part in axis_table(n, g)])
+    return apply_to_tile("mvs_intensity_apply", data, out, out_dtype, device, lambda view, out_ptr, out_code, out_mem: lib.mvs_intensity_apply(
+        device, view, ndim, _i32x3(cells, ndim, 1), coeff.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(tables.ctypes.data), out_ptr, out_code, out_mem))

@@ -9,14 +9,7 @@ import math
 import numpy as np
 
 from . import _lib
-from .transformation import embed3, fill_view_geometry, shape3, view_data
-
-
-def _view(data, matrix, offset, device):
-    view = _lib.mvs_view_t()
-    ptr, s3, st3, mem, keep = view_data(data, device)
-    fill_view_geometry(view, ptr, _lib.DTYPE_CODES[np.dtype(keep.dtype)], mem, s3, st3, matrix, offset)
-    return view, keep
+from .transformation import embed3, shape3, tile_view
 
 
 def pair_moments(fixed, moving, fixed_affine, cand_affines, grid_shape, halfspaces=None, device=0):
@@ -33,8 +26,8 @@ def pair_moments(fixed, moving, fixed_affine, cand_affines, grid_shape, halfspac
     ndim = len(grid_shape)
     if ndim not in (2, 3):
         raise ValueError("pair_moments needs a 2-D or 3-D grid")
-    fview, keep_f = _view(fixed, fixed_affine[0], fixed_affine[1], device)
-    mview, keep_m = _view(moving, np.eye(ndim), np.zeros(ndim), device)
+    fview, keep_f = tile_view(fixed, fixed_affine[0], fixed_affine[1], device)
+    mview, keep_m = tile_view(moving, np.eye(ndim), np.zeros(ndim), device)
     hs = np.zeros((0, ndim + 1)) if halfspaces is None else np.asarray(halfspaces, dtype=np.float64).reshape(-1, ndim + 1)
     if len(hs) > _lib.MVS_PAIR_MAX_HALFSPACES:
         raise ValueError(f"at most {_lib.MVS_PAIR_MAX_HALFSPACES} halfspaces")

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .transformation import view_data
+from .transformation import tile_view
 
 STATUS_USED, STATUS_OUTSIDE, STATUS_EMPTY = 0, 1, 2      # status_out of mvs_psf_extract
 
@@ -61,11 +61,7 @@ def psf_extract(data, centers, matrix, radius, refine_iterations=1, device=0):
     if len(radius) != ndim or min(radius) < 1 or max(radius) > _lib.MVS_PSF_MAX_RADIUS:
         raise ValueError(f"one radius per axis in 1..{_lib.MVS_PSF_MAX_RADIUS}")
     n, k = len(centers), 3 - ndim
-    view = _lib.mvs_view_t()
-    ptr, s3, st3, mem, keep = view_data(data, device)
-    view.data, view.dtype, view.mem = ptr, _lib.DTYPE_CODES[np.dtype(keep.dtype)], mem
-    view.shape[:] = s3
-    view.stride[:] = st3
+    view, keep = tile_view(data, np.eye(ndim), np.zeros(ndim), device)
     c3 = np.zeros((n, 3))
     c3[:, k:] = centers
     m3 = np.eye(3)

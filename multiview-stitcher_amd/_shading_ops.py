@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._intensity_ops import _view
+from ._intensity_ops import apply_to_tile
 from .transformation import fill_view_geometry, shape3, view_data
 
 
@@ -100,7 +100,7 @@ def apply_plane(data, coeff, out=None, out_dtype=None, device=0):
     per pixel, a numpy array or a contiguous ``DeviceArray`` (callers that correct many tiles upload it once).  ``data``, ``out``
     and ``out_dtype`` as in ``_intensity_ops.apply_map``: the result is of the data's kind, of the input's dtype (the default) or
     float32; ``out is data`` corrects a contiguous array in place."""
-    from .device import DeviceArray, is_device_array
+    from .device import is_device_array
 
     lib = _lib.init(device)
     ndim = len(data.shape)
@@ -114,29 +114,5 @@ def apply_plane(data, coeff, out=None, out_dtype=None, device=0):
         coeff_ptr, coeff_mem = coeff.ctypes.data, _lib.MVS_MEM_HOST
     if ndim not in (2, 3) or tuple(coeff.shape) != tuple(int(s) for s in data.shape[-2:]) + (2,):
         raise ValueError("apply_plane needs a 2-D or 3-D tile and coefficients of shape (H, W, 2)")
-    on_dev = is_device_array(data)
-    in_dtype = np.dtype(data.dtype)
-    if in_dtype not in _lib.DTYPE_CODES:
-        raise TypeError(f"unsupported dtype {in_dtype} (uint8 / uint16 / float32)")
-    out_dtype = in_dtype if out_dtype is None else np.dtype(out_dtype)
-    if out_dtype not in (in_dtype, np.dtype(np.float32)):
-        raise TypeError(f"out_dtype must be the input's dtype or float32, not {out_dtype}")
-    shape = tuple(int(s) for s in data.shape)
-    if out is None:
-        out = DeviceArray.empty(shape, out_dtype, device) if on_dev else np.empty(shape, dtype=out_dtype)
-    if is_device_array(out) != on_dev or tuple(out.shape) != shape or np.dtype(out.dtype) != out_dtype:
-        raise ValueError("out must be of the data's kind and shape and of out_dtype")
-    if not (out.is_contiguous() if on_dev else out.flags.c_contiguous):
-        raise ValueError("out must be contiguous")
-    view, keep = _view(data, np.eye(ndim), np.zeros(ndim), device)
-    if on_dev:
-        out.wait_ready(device)
-        out_ptr, out_mem = out.ptr, _lib.MVS_MEM_DEVICE
-    else:
-        out_ptr, out_mem = out.ctypes.data, _lib.MVS_MEM_HOST
-    rc = lib.mvs_plane_apply(device, C.byref(view), ndim, C.c_void_p(coeff_ptr), coeff_mem, C.c_void_p(out_ptr), _lib.DTYPE_CODES[out_dtype], out_mem)
-    _lib.check(rc, device, "mvs_plane_apply")
-    if on_dev:
-        out.mark_written()
-    del keep
-    return out
+    return apply_to_tile("mvs_plane_apply", data, out, out_dtype, device, lambda view, out_ptr, out_code, out_mem: lib.mvs_plane_apply(
+        device, view, ndim, C.c_void_p(coeff_ptr), coeff_mem, out_ptr, out_code, out_mem))

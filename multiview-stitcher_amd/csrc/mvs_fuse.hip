@@ -1370,6 +1370,40 @@ int mvs_stage_view(MvsContext* c, const mvs_view_t& v, size_t es, char* area, si
     return MVS_OK;
 }
 
+int mvs_check_tile_view(MvsContext* c, const char* what, const mvs_view_t* v, int ndim) {
+    if (!v->data) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: view without data", what);
+    if (v->mem != MVS_MEM_HOST && v->mem != MVS_MEM_DEVICE) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: bad mem", what);
+    if (!mvs_dtype_size(v->dtype)) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "%s: dtype %d (uint8 / uint16 / float32)", what, v->dtype);
+    if (ndim == 2 && v->shape[0] != 1) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: 2D views have shape[0] == 1", what);
+    return MVS_OK;
+}
+
+int mvs_stage_tile_views(MvsContext* c, const mvs_view_t* const* views, int n, int ndim, const void** dev_data, DevView* const* dviews) {
+    size_t total = 0, cursor = 0;
+    for (int i = 0; i < n; ++i) {
+        size_t bytes = 0;
+        const int rc = mvs_stage_views_bytes(c, views[i], 1, mvs_dtype_size(views[i]->dtype), &bytes);
+        if (rc) return rc;
+        total += bytes;
+    }
+    char* area = nullptr;
+    if (total) {
+        area = (char*)mvs_scratch(c, 0, total);
+        if (!area) return mvs_alloc_failed(c);
+    }
+    for (int i = 0; i < n; ++i) {
+        const void* dptr;
+        int rc = mvs_stage_view(c, *views[i], mvs_dtype_size(views[i]->dtype), area, &cursor, &dptr);
+        if (rc) return rc;
+        if (dev_data) dev_data[i] = dptr;
+        if (!dviews) continue;
+        rc = fill_dev_view(c, *views[i], ndim, dptr, dviews[i]);
+        if (rc) return rc;
+        dviews[i]->tr_ok = 0;
+    }
+    return MVS_OK;
+}
+
 extern "C" int mvs_fuse_chunk(int device, const mvs_view_t* views, int32_t n_views,
                               const mvs_fuse_opts_t* opts, void* out) {
     MvsContext* c;
@@ -1577,24 +1611,14 @@ int mvs_fuse_chunk_impl(MvsContext* c, const mvs_view_t* views, int32_t n_views,
 namespace {
 // shared host-side helper of mvs_resample / mvs_blend_weights
 int stage_single_view(MvsContext* c, const mvs_view_t* view, int ndim, bool need_data, DevView* d) {
-    const void* dptr = view->data;
     if (need_data) {
-        size_t es = mvs_dtype_size(view->dtype);
-        if (!es || !view->data) return mvs_fail(c, MVS_ERR_INVALID_ARG, "bad view dtype/data");
-        size_t host_bytes = 0, cursor = 0;
-        int rc = mvs_stage_views_bytes(c, view, 1, es, &host_bytes);
-        if (rc) return rc;
-        char* s = nullptr;
-        if (host_bytes) {
-            s = (char*)mvs_scratch(c, 0, host_bytes);
-            if (!s) return mvs_alloc_failed(c);
-        }
-        rc = mvs_stage_view(c, *view, es, s, &cursor, &dptr);
-        if (rc) return rc;
+        if (!mvs_dtype_size(view->dtype) || !view->data) return mvs_fail(c, MVS_ERR_INVALID_ARG, "bad view dtype/data");
+        return mvs_stage_tile_views(c, &view, 1, ndim, nullptr, &d);
     }
     mvs_view_t tmp = *view;
-    if (!need_data) { tmp.shape[0] = tmp.shape[1] = tmp.shape[2] = 1; tmp.stride[0] = tmp.stride[1] = tmp.stride[2] = 1; }
-    return fill_dev_view(c, tmp, ndim, dptr, d);
+    tmp.shape[0] = tmp.shape[1] = tmp.shape[2] = 1;
+    tmp.stride[0] = tmp.stride[1] = tmp.stride[2] = 1;
+    return fill_dev_view(c, tmp, ndim, view->data, d);
 }
 }  // namespace
 

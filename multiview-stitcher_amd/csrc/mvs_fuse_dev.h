@@ -39,6 +39,15 @@ int mvs_stage_views_bytes(MvsContext* c, const mvs_view_t* views, int n_views, s
 int mvs_stage_view(MvsContext* c, const mvs_view_t& v, size_t es, char* area, size_t* cursor, const void** dev_data);
 
 int mvs_fill_dev_view(MvsContext* c, const mvs_view_t& v, int ndim, const void* dev_data, DevView* d);
+
+// ---- the prologue of the entries that take one or two whole tiles (metrics, PSF extraction, intensity, shading, mvs_resample) ----
+// what they require of a tile: data, a known mem and dtype, one plane in 2D; `what` = the entry's name.  Needs no device: `c` may
+// be the context of mvs_ctx(device) before mvs_check_ready.
+int mvs_check_tile_view(MvsContext* c, const char* what, const mvs_view_t* v, int ndim);
+// the n (1 or 2) checked tiles through scratch slot 0: sizes the slot and queues the uploads of the host tiles.  Where the kernels
+// read tile i goes to dev_data[i] and, with mvs_fill_dev_view and no translation path, into *dviews[i]; either array may be NULL.
+int mvs_stage_tile_views(MvsContext* c, const mvs_view_t* const* views, int n, int ndim, const void** dev_data, DevView* const* dviews);
+
 // `box0` (may be null): chunk index of the output array's first voxel -- the output is a sub-box of the chunk, evaluated with the
 // chunk's own coordinates
 void mvs_launch_resample(MvsContext* c, const DevView& d, int dtype, int order, float cval, float* out, const int64_t shape[3], const int* box0 = nullptr,

@@ -11,6 +11,7 @@
 #include "mvs_fuse_dev.h"
 #include "mvs_pair_voxel_dev.h"
 #include "mvs_intensity_dev.h"
+#include "mvs_tile_apply.h"
 
 #include <algorithm>
 #include <cmath>
@@ -106,26 +107,14 @@ constexpr int kApplyThreads = 256;                  // four waves, one row each 
 constexpr int kApplyRows = kApplyThreads / 64;
 constexpr int kApplyMaxBlocks = 16384;
 
-struct ApplyArgs {
-    const void* in;
-    void* out;
-    long long in_sz, in_sy;                         // elements; the output is C-contiguous
-    int nz, ny, nx;
-    int gz, gy, gx;
+// (gz, gy, gx come last on purpose: placed right after TileApplyArgs, 4 bytes later than they once were, the same kernels compile
+// to up to 49 more VGPRs and lose up to three occupancy steps -- profiles/tile_apply_ab.txt, section 2)
+struct ApplyArgs : TileApplyArgs {
     const float* coeff;                             // (gz, gy, gx, 2)
     const int* cell[3];                             // per axis and pixel: lower cell index ...
     const float* frac[3];                           // ... and interpolation weight
+    int gz, gy, gx;
 };
-
-template <typename T, int V>
-struct alignas(V * sizeof(T)) ApplyVec {
-    T v[V];
-};
-
-template <typename TOut> __device__ __forceinline__ TOut apply_store(float y);
-template <> __device__ __forceinline__ float apply_store<float>(float y) { return y; }
-template <> __device__ __forceinline__ unsigned char apply_store<unsigned char>(float y) { return (unsigned char)intensity_saturate(y, 255.f); }
-template <> __device__ __forceinline__ unsigned short apply_store<unsigned short>(float y) { return (unsigned short)intensity_saturate(y, 65535.f); }
 
 template <typename TIn, typename TOut>
 __device__ __forceinline__ TOut apply_voxel(const ApplyArgs& P, const float2* ab, int x, TIn raw) {
@@ -134,7 +123,7 @@ __device__ __forceinline__ TOut apply_voxel(const ApplyArgs& P, const float2* ab
     const float t = P.frac[2][x];
     const float2 c0 = ab[i], c1 = ab[i1];
     const float a = intensity_lerp(c0.x, c1.x, t), b = intensity_lerp(c0.y, c1.y, t);
-    return apply_store<TOut>(a * (float)raw + b);
+    return tile_store<TOut>(a * (float)raw + b);
 }
 
 // A wave takes one row (z, y) at a time.  Its first gx lanes interpolate the row's coefficient pairs along z, then y, into LDS; then
@@ -149,8 +138,8 @@ __global__ __launch_bounds__(kApplyThreads) void intensity_apply_kernel(ApplyArg
     const long long rows = (long long)P.nz * P.ny;
     const TIn* in = (const TIn*)P.in;
     TOut* out = (TOut*)P.out;
-    using VIn = ApplyVec<TIn, V>;
-    using VOut = ApplyVec<TOut, V>;
+    using VIn = TileVec<TIn, V>;
+    using VOut = TileVec<TOut, V>;
     for (long long base = (long long)blockIdx.x * kApplyRows; base < rows; base += (long long)gridDim.x * kApplyRows) {
         const long long row = base + wave;
         const bool live = row < rows;
@@ -173,10 +162,8 @@ __global__ __launch_bounds__(kApplyThreads) void intensity_apply_kernel(ApplyArg
         const float2* ab = row_ab[wave];
         const TIn* src = in + (long long)z * P.in_sz + (long long)y * P.in_sy;
         TOut* dst = out + row * P.nx;
-        const unsigned long long mis = (unsigned long long)src % (V * sizeof(TIn));
-        int head = mis ? (int)((V * sizeof(TIn) - mis) / sizeof(TIn)) : 0;
-        if (head > P.nx || mis % sizeof(TIn) || (unsigned long long)(dst + head) % (V * sizeof(TOut))) head = P.nx;
-        const int nvec = (P.nx - head) / V, tail = head + nvec * V;
+        const TileRowSplit split = tile_row_split((unsigned long long)src, (unsigned long long)dst, P.nx, sizeof(TIn), sizeof(TOut), V, true);
+        const int head = split.head, nvec = split.nvec, tail = split.tail;
         for (int x = lane; x < head; x += 64) dst[x] = apply_voxel<TIn, TOut>(P, ab, x, src[x]);
         for (int j = lane; j < nvec; j += 64) {
             const int x0 = head + j * V;
@@ -192,16 +179,7 @@ __global__ __launch_bounds__(kApplyThreads) void intensity_apply_kernel(ApplyArg
 
 template <typename TIn, typename TOut>
 void launch_apply(const ApplyArgs& P, int nblocks, hipStream_t s) {
-    constexpr int V = 16 / (sizeof(TIn) > sizeof(TOut) ? sizeof(TIn) : sizeof(TOut));
-    hipLaunchKernelGGL((intensity_apply_kernel<TIn, TOut, V>), dim3(nblocks), dim3(kApplyThreads), 0, s, P);
-}
-
-int check_view(MvsContext* c, const char* what, const mvs_view_t* v, int ndim) {
-    if (!v->data) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: view without data", what);
-    if (v->mem != MVS_MEM_HOST && v->mem != MVS_MEM_DEVICE) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: bad mem", what);
-    if (!mvs_dtype_size(v->dtype)) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "%s: dtype %d (uint8 / uint16 / float32)", what, v->dtype);
-    if (ndim == 2 && v->shape[0] != 1) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: 2D views have shape[0] == 1", what);
-    return MVS_OK;
+    hipLaunchKernelGGL((intensity_apply_kernel<TIn, TOut, tile_vec_len<TIn, TOut>()>), dim3(nblocks), dim3(kApplyThreads), 0, s, P);
 }
 
 int check_cells(MvsContext* c, const char* what, const int32_t cells[3], int ndim) {
@@ -226,8 +204,8 @@ extern "C" int mvs_intensity_pair_moments(int device, const mvs_view_t* fixed, c
         return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: n_records must be 1..%d", what, MVS_INTENSITY_MAX_RECORDS);
     int rc = check_cells(c0, what, cells_f, ndim);
     if (!rc) rc = check_cells(c0, what, cells_m, ndim);
-    if (!rc) rc = check_view(c0, what, fixed, ndim);
-    if (!rc) rc = check_view(c0, what, moving, ndim);
+    if (!rc) rc = mvs_check_tile_view(c0, what, fixed, ndim);
+    if (!rc) rc = mvs_check_tile_view(c0, what, moving, ndim);
     if (rc) return rc;
     if (fixed->dtype != moving->dtype)
         return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "%s: the views must share one dtype (%d and %d given)", what, fixed->dtype, moving->dtype);
@@ -250,29 +228,11 @@ extern "C" int mvs_intensity_pair_moments(int device, const mvs_view_t* fixed, c
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
 
-    // host slabs go through scratch slot 0, as in mvs_pair_moments
-    const mvs_view_t* both[2] = {fixed, moving};
-    const size_t es = mvs_dtype_size(fixed->dtype);
-    size_t bytes[2] = {0, 0}, cursor = 0;
-    for (int i = 0; i < 2; ++i) {
-        rc = mvs_stage_views_bytes(c, both[i], 1, es, &bytes[i]);
-        if (rc) return rc;
-    }
-    char* area = nullptr;
-    if (bytes[0] + bytes[1]) {
-        area = (char*)mvs_scratch(c, 0, bytes[0] + bytes[1]);
-        if (!area) return mvs_alloc_failed(c);
-    }
     IntensityArgs P;
+    const mvs_view_t* both[2] = {fixed, moving};
     DevView* dv[2] = {&P.fixed, &P.moving};
-    for (int i = 0; i < 2; ++i) {
-        const void* dptr;
-        rc = mvs_stage_view(c, *both[i], es, area, &cursor, &dptr);
-        if (rc) return rc;
-        rc = mvs_fill_dev_view(c, *both[i], ndim, dptr, dv[i]);
-        if (rc) return rc;
-        dv[i]->tr_ok = 0;
-    }
+    rc = mvs_stage_tile_views(c, both, 2, ndim, nullptr, dv);
+    if (rc) return rc;
     if (n_halfspaces) memcpy(P.hs, halfspaces, sizeof(double) * 4 * n_halfspaces);
     P.n_hs = n_halfspaces;
     P.n_records = n_records;
@@ -315,77 +275,34 @@ extern "C" int mvs_intensity_apply(int device, const mvs_view_t* view, int32_t n
     const char* what = "mvs_intensity_apply";
     MvsContext* c0 = mvs_ctx(device);
     if (!view || !cells || !coeff || !tables || !out) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: NULL argument", what);
-    if (ndim != 2 && ndim != 3) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: ndim must be 2 or 3", what);
     int rc = check_cells(c0, what, cells, ndim);
-    if (!rc) rc = check_view(c0, what, view, ndim);
     if (rc) return rc;
-    if (out_mem != MVS_MEM_HOST && out_mem != MVS_MEM_DEVICE) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: bad out_mem", what);
-    if (out_dtype != view->dtype && out_dtype != MVS_F32)
-        return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "%s: out_dtype must be the input's dtype or float32 (%d -> %d given)", what, view->dtype, out_dtype);
-    for (int k = 0; k < 3; ++k)
-        if (view->shape[k] < 1 || view->shape[k] > 0x7fffffffLL) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: view shape[%d] out of range", what, k);
-    if (view->mem == MVS_MEM_DEVICE && view->stride[2] != 1) return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "%s: view stride along x must be 1", what);
-    const bool in_place = view->mem == MVS_MEM_DEVICE && out_mem == MVS_MEM_DEVICE && out == view->data;
-    if (in_place && (out_dtype != view->dtype || view->stride[1] != view->shape[2] || view->stride[0] != view->shape[1] * view->shape[2]))
-        return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "%s: in place needs a contiguous array and out_dtype == dtype", what);
-    MvsContext* c;
-    rc = mvs_check_ready(device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
-
-    const size_t es = mvs_dtype_size(view->dtype), es_out = mvs_dtype_size(out_dtype);
-    const size_t n = (size_t)view->shape[0] * view->shape[1] * view->shape[2];
-    size_t view_bytes = 0, cursor = 0;
-    rc = mvs_stage_views_bytes(c, view, 1, es, &view_bytes);
-    if (rc) return rc;
-    char* area = nullptr;
-    if (view_bytes) {
-        area = (char*)mvs_scratch(c, 0, view_bytes);
-        if (!area) return mvs_alloc_failed(c);
-    }
-    const void* dptr;
-    rc = mvs_stage_view(c, *view, es, area, &cursor, &dptr);
-    if (rc) return rc;
-
     ApplyArgs P;
-    P.in = dptr;
-    P.in_sz = view->mem == MVS_MEM_HOST ? view->shape[1] * view->shape[2] : view->stride[0];
-    P.in_sy = view->mem == MVS_MEM_HOST ? view->shape[2] : view->stride[1];
-    P.nz = (int)view->shape[0]; P.ny = (int)view->shape[1]; P.nx = (int)view->shape[2];
-    P.gz = cells[0]; P.gy = cells[1]; P.gx = cells[2];
-    P.out = out;
-    if (out_mem == MVS_MEM_HOST) {
-        P.out = mvs_scratch(c, 1, n * es_out);
-        if (!P.out) return mvs_alloc_failed(c);
-    }
-    // coefficients and tables: scratch slot 2 (tables: per axis z, y, x the int32 lower cell of every pixel, then its float32 weight)
-    const size_t coeff_bytes = sizeof(float) * 2 * (size_t)cells[0] * cells[1] * cells[2];
-    const size_t table_bytes = 8 * ((size_t)P.nz + P.ny + P.nx);
-    char* small = (char*)mvs_scratch(c, 2, align_up(coeff_bytes) + table_bytes);
-    if (!small) return mvs_alloc_failed(c);
-    MVS_HIP_TRY(c, hipMemcpyAsync(small, coeff, coeff_bytes, hipMemcpyHostToDevice, c->stream));
-    MVS_HIP_TRY(c, hipMemcpyAsync(small + align_up(coeff_bytes), tables, table_bytes, hipMemcpyHostToDevice, c->stream));
-    P.coeff = (const float*)small;
-    char* t = small + align_up(coeff_bytes);
-    for (int k = 0; k < 3; ++k) {
-        P.cell[k] = (const int*)t;
-        P.frac[k] = (const float*)(t + 4 * (size_t)view->shape[k]);
-        t += 8 * (size_t)view->shape[k];
-    }
-
-    const long long rows = (long long)P.nz * P.ny;
-    const int nblocks = (int)std::min<long long>((rows + kApplyRows - 1) / kApplyRows, kApplyMaxBlocks);
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    mvs_dispatch_dtype(view->dtype, [&](auto tag) {
-        using T = decltype(tag);
-        if (out_dtype == view->dtype) launch_apply<T, T>(P, nblocks, c->stream);
-        else launch_apply<T, float>(P, nblocks, c->stream);
+    int nblocks = 0;
+    hipStream_t stream = nullptr;
+    auto prepare = [&](MvsContext* c, const TileApplyArgs& A) -> int {
+        stream = c->stream;
+        static_cast<TileApplyArgs&>(P) = A;
+        P.gz = cells[0]; P.gy = cells[1]; P.gx = cells[2];
+        // coefficients and tables: scratch slot 2 (tables: per axis z, y, x the int32 lower cell of every pixel, then its float32 weight)
+        const size_t coeff_bytes = sizeof(float) * 2 * (size_t)cells[0] * cells[1] * cells[2];
+        const size_t table_bytes = 8 * ((size_t)P.nz + P.ny + P.nx);
+        char* small = (char*)mvs_scratch(c, 2, align_up(coeff_bytes) + table_bytes);
+        if (!small) return mvs_alloc_failed(c);
+        MVS_HIP_TRY(c, hipMemcpyAsync(small, coeff, coeff_bytes, hipMemcpyHostToDevice, c->stream));
+        MVS_HIP_TRY(c, hipMemcpyAsync(small + align_up(coeff_bytes), tables, table_bytes, hipMemcpyHostToDevice, c->stream));
+        P.coeff = (const float*)small;
+        char* t = small + align_up(coeff_bytes);
+        for (int k = 0; k < 3; ++k) {
+            P.cell[k] = (const int*)t;
+            P.frac[k] = (const float*)(t + 4 * (size_t)view->shape[k]);
+            t += 8 * (size_t)view->shape[k];
+        }
+        const long long rows = (long long)P.nz * P.ny;
+        nblocks = (int)std::min<long long>((rows + kApplyRows - 1) / kApplyRows, kApplyMaxBlocks);
+        return MVS_OK;
+    };
+    return mvs_tile_apply(device, what, view, ndim, out, out_dtype, out_mem, prepare, [&](auto tin, auto tout) {
+        launch_apply<decltype(tin), decltype(tout)>(P, nblocks, stream);
     });
-    MVS_HIP_TRY(c, hipGetLastError());
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->timing_valid = true;
-    if (out_mem == MVS_MEM_HOST) MVS_HIP_TRY(c, hipMemcpyAsync(out, P.out, n * es_out, hipMemcpyDeviceToHost, c->stream));
-    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return MVS_OK;
 }

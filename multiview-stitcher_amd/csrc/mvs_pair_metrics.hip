@@ -119,10 +119,8 @@ extern "C" int mvs_pair_moments(int device, const mvs_view_t* fixed, const mvs_v
             return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_pair_moments: grid_shape must be positive (and 1 along z in 2D)");
     const mvs_view_t* both[2] = {fixed, moving};
     for (const mvs_view_t* v : both) {
-        if (!v->data) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_pair_moments: view without data");
-        if (v->mem != MVS_MEM_HOST && v->mem != MVS_MEM_DEVICE) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_pair_moments: bad mem");
-        if (!mvs_dtype_size(v->dtype)) return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_pair_moments: dtype %d (uint8 / uint16 / float32)", v->dtype);
-        if (ndim == 2 && v->shape[0] != 1) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_pair_moments: 2D views have shape[0] == 1");
+        const int rc = mvs_check_tile_view(c0, "mvs_pair_moments", v, ndim);
+        if (rc) return rc;
     }
     if (fixed->dtype != moving->dtype)
         return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_pair_moments: the views must share one dtype (%d and %d given)", fixed->dtype, moving->dtype);
@@ -132,28 +130,10 @@ extern "C" int mvs_pair_moments(int device, const mvs_view_t* fixed, const mvs_v
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
 
-    // host slabs go through scratch slot 0, as in mvs_resample
-    const size_t es = mvs_dtype_size(fixed->dtype);
-    size_t bytes[2] = {0, 0}, cursor = 0;
-    for (int i = 0; i < 2; ++i) {
-        rc = mvs_stage_views_bytes(c, both[i], 1, es, &bytes[i]);
-        if (rc) return rc;
-    }
-    char* area = nullptr;
-    if (bytes[0] + bytes[1]) {
-        area = (char*)mvs_scratch(c, 0, bytes[0] + bytes[1]);
-        if (!area) return mvs_alloc_failed(c);
-    }
     PairArgs P;
     DevView* dv[2] = {&P.fixed, &P.moving};
-    for (int i = 0; i < 2; ++i) {
-        const void* dptr;
-        rc = mvs_stage_view(c, *both[i], es, area, &cursor, &dptr);
-        if (rc) return rc;
-        rc = mvs_fill_dev_view(c, *both[i], ndim, dptr, dv[i]);
-        if (rc) return rc;
-        dv[i]->tr_ok = 0;
-    }
+    rc = mvs_stage_tile_views(c, both, 2, ndim, nullptr, dv);
+    if (rc) return rc;
     memcpy(P.cm, cand_matrix, sizeof(double) * 9 * n_candidates);
     memcpy(P.co, cand_offset, sizeof(double) * 3 * n_candidates);
     if (n_halfspaces) memcpy(P.hs, halfspaces, sizeof(double) * 4 * n_halfspaces);

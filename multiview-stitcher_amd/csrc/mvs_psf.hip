@@ -194,10 +194,8 @@ extern "C" int mvs_psf_extract(int device, const mvs_view_t* view, int32_t ndim,
     if (!view || !centers || !window_matrix || !radius || !centers_out || !status_out || !stats_out || !psf_out)
         return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_psf_extract: NULL argument");
     if (ndim != 2 && ndim != 3) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_psf_extract: ndim must be 2 or 3");
-    if (!view->data) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_psf_extract: view without data");
-    if (view->mem != MVS_MEM_HOST && view->mem != MVS_MEM_DEVICE) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_psf_extract: bad mem");
-    if (!mvs_dtype_size(view->dtype)) return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_psf_extract: dtype %d (uint8 / uint16 / float32)", view->dtype);
-    if (ndim == 2 && view->shape[0] != 1) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_psf_extract: 2D views have shape[0] == 1");
+    int rc = mvs_check_tile_view(c0, "mvs_psf_extract", view, ndim);
+    if (rc) return rc;
     for (int k = 3 - ndim; k < 3; ++k)
         if (radius[k] < 1 || radius[k] > MVS_PSF_MAX_RADIUS)
             return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_psf_extract: radius[%d] = %d, must be 1..%d", k, (int)radius[k], MVS_PSF_MAX_RADIUS);
@@ -206,28 +204,15 @@ extern "C" int mvs_psf_extract(int device, const mvs_view_t* view, int32_t ndim,
     for (int k = 0; k < 9; ++k)
         if (!std::isfinite(window_matrix[k])) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_psf_extract: window_matrix is not finite");
     MvsContext* c;
-    int rc = mvs_check_ready(device, &c);
+    rc = mvs_check_ready(device, &c);
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> lock(c->mu);
     MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
 
     PsfArgs P;
-    // a host view goes through scratch slot 0, as in mvs_resample
-    const size_t es = mvs_dtype_size(view->dtype);
-    size_t view_bytes = 0, cursor = 0;
-    rc = mvs_stage_views_bytes(c, view, 1, es, &view_bytes);
+    DevView* dv = &P.view;
+    rc = mvs_stage_tile_views(c, &view, 1, ndim, nullptr, &dv);
     if (rc) return rc;
-    char* area = nullptr;
-    if (view_bytes) {
-        area = (char*)mvs_scratch(c, 0, view_bytes);
-        if (!area) return mvs_alloc_failed(c);
-    }
-    const void* dptr;
-    rc = mvs_stage_view(c, *view, es, area, &cursor, &dptr);
-    if (rc) return rc;
-    rc = mvs_fill_dev_view(c, *view, ndim, dptr, &P.view);
-    if (rc) return rc;
-    P.view.tr_ok = 0;
 
     memcpy(P.m, window_matrix, sizeof(P.m));
     P.first_axis = 3 - ndim;

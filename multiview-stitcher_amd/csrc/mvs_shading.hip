@@ -12,6 +12,7 @@
 #include "mvs_fuse_dev.h"
 #include "mvs_intensity_dev.h"
 #include "mvs_stack_select.h"
+#include "mvs_tile_apply.h"
 
 #include <algorithm>
 #include <cmath>
@@ -175,24 +176,10 @@ constexpr int kPlaneRows = kPlaneThreads / 64;
 constexpr int kPlaneBatch = 4;                              // planes a lane has loaded before it stores them
 constexpr long long kPlaneTargetRows = 8192;               // (row, z slab) items wanted at least, so that short stacks of rows still fill the device
 
-struct PlaneArgs {
-    const void* in;
-    void* out;
-    long long in_sz, in_sy;                                 // elements; the output is C-contiguous
-    int nz, ny, nx;
+struct PlaneArgs : TileApplyArgs {
     int slab, n_slabs;                                      // planes per z slab; slabs
     const float2* coeff;                                    // (ny, nx): (a, b)
 };
-
-template <typename T, int V>
-struct alignas(V * sizeof(T)) PlaneVec {
-    T v[V];
-};
-
-template <typename TOut> __device__ __forceinline__ TOut plane_store(float y);
-template <> __device__ __forceinline__ float plane_store<float>(float y) { return y; }
-template <> __device__ __forceinline__ unsigned char plane_store<unsigned char>(float y) { return (unsigned char)intensity_saturate(y, 255.f); }
-template <> __device__ __forceinline__ unsigned short plane_store<unsigned short>(float y) { return (unsigned short)intensity_saturate(y, 65535.f); }
 
 // one pixel column x of row y through the planes [z0, z1)
 template <typename TIn, typename TOut>
@@ -200,7 +187,7 @@ __device__ __forceinline__ void plane_column(const PlaneArgs& P, const TIn* src,
     const float2 c = P.coeff[x];
     for (int z = z0; z < z1; ++z) {
         const TIn raw = src[(long long)(z - z0) * P.in_sz + x];
-        dst[(long long)(z - z0) * out_sz + x] = plane_store<TOut>(c.x * (float)raw + c.y);
+        dst[(long long)(z - z0) * out_sz + x] = tile_store<TOut>(c.x * (float)raw + c.y);
     }
 }
 
@@ -213,21 +200,19 @@ __global__ __launch_bounds__(kPlaneThreads) void plane_apply_kernel(PlaneArgs P)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long items = (long long)P.ny * P.n_slabs;
     const long long out_sz = (long long)P.ny * P.nx;
-    using VIn = PlaneVec<TIn, V>;
-    using VOut = PlaneVec<TOut, V>;
+    using VIn = TileVec<TIn, V>;
+    using VOut = TileVec<TOut, V>;
     PlaneArgs Q = P;
     for (long long item = (long long)blockIdx.x * kPlaneRows + wave; item < items; item += (long long)gridDim.x * kPlaneRows) {
         const int y = (int)(item % P.ny), z0 = (int)(item / P.ny) * P.slab, z1 = min(z0 + P.slab, P.nz);
         const TIn* src = (const TIn*)P.in + (long long)z0 * P.in_sz + (long long)y * P.in_sy;
         TOut* dst = (TOut*)P.out + (long long)z0 * out_sz + (long long)y * P.nx;
         Q.coeff = P.coeff + (long long)y * P.nx;
-        const unsigned long long mis = (unsigned long long)src % (V * sizeof(TIn));
-        int head = mis ? (int)((V * sizeof(TIn) - mis) / sizeof(TIn)) : 0;
         // (planes keep the row's alignment iff the plane pitches are multiples of the vectors)
         const bool pitches = z1 - z0 == 1 || (!((P.in_sz * (long long)sizeof(TIn)) % (long long)(V * sizeof(TIn))) &&
                                               !((out_sz * (long long)sizeof(TOut)) % (long long)(V * sizeof(TOut))));
-        if (head > P.nx || mis % sizeof(TIn) || (unsigned long long)(dst + head) % (V * sizeof(TOut)) || !pitches) head = P.nx;
-        const int nvec = (P.nx - head) / V, tail = head + nvec * V;
+        const TileRowSplit split = tile_row_split((unsigned long long)src, (unsigned long long)dst, P.nx, sizeof(TIn), sizeof(TOut), V, pitches);
+        const int head = split.head, nvec = split.nvec, tail = split.tail;
         for (int x = lane; x < head; x += 64) plane_column<TIn, TOut>(Q, src, dst, x, z0, z1, out_sz);
         for (int j = lane; j < nvec; j += 64) {
             const int x0 = head + j * V;
@@ -244,7 +229,7 @@ __global__ __launch_bounds__(kPlaneThreads) void plane_apply_kernel(PlaneArgs P)
                     if (z + u >= z1) continue;
                     VOut vo;
 #pragma unroll
-                    for (int k = 0; k < V; ++k) vo.v[k] = plane_store<TOut>(c[k].x * (float)vi[u].v[k] + c[k].y);
+                    for (int k = 0; k < V; ++k) vo.v[k] = tile_store<TOut>(c[k].x * (float)vi[u].v[k] + c[k].y);
                     *(VOut*)(dst + (long long)(z + u - z0) * out_sz + x0) = vo;
                 }
             }
@@ -255,8 +240,7 @@ __global__ __launch_bounds__(kPlaneThreads) void plane_apply_kernel(PlaneArgs P)
 
 template <typename TIn, typename TOut>
 void launch_plane_apply(const PlaneArgs& P, int nblocks, hipStream_t s) {
-    constexpr int V = 16 / (sizeof(TIn) > sizeof(TOut) ? sizeof(TIn) : sizeof(TOut));
-    hipLaunchKernelGGL((plane_apply_kernel<TIn, TOut, V>), dim3(nblocks), dim3(kPlaneThreads), 0, s, P);
+    hipLaunchKernelGGL((plane_apply_kernel<TIn, TOut, tile_vec_len<TIn, TOut>()>), dim3(nblocks), dim3(kPlaneThreads), 0, s, P);
 }
 
 }  // namespace
@@ -378,77 +362,31 @@ extern "C" int mvs_plane_apply(int device, const mvs_view_t* view, int32_t ndim,
     const char* what = "mvs_plane_apply";
     MvsContext* c0 = mvs_ctx(device);
     if (!view || !coeff || !out) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: NULL argument", what);
-    if (ndim != 2 && ndim != 3) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: ndim must be 2 or 3", what);
-    if (!view->data) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: view without data", what);
-    if (view->mem != MVS_MEM_HOST && view->mem != MVS_MEM_DEVICE) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: bad mem", what);
-    if (!mvs_dtype_size(view->dtype)) return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "%s: dtype %d (uint8 / uint16 / float32)", what, view->dtype);
-    if (ndim == 2 && view->shape[0] != 1) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: 2D views have shape[0] == 1", what);
-    if ((out_mem != MVS_MEM_HOST && out_mem != MVS_MEM_DEVICE) || (coeff_mem != MVS_MEM_HOST && coeff_mem != MVS_MEM_DEVICE))
-        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: bad out_mem / coeff_mem", what);
-    if (out_dtype != view->dtype && out_dtype != MVS_F32)
-        return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "%s: out_dtype must be the input's dtype or float32 (%d -> %d given)", what, view->dtype, out_dtype);
-    for (int k = 0; k < 3; ++k)
-        if (view->shape[k] < 1 || view->shape[k] > 0x7fffffffLL) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: view shape[%d] out of range", what, k);
-    if (view->mem == MVS_MEM_DEVICE && view->stride[2] != 1) return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "%s: view stride along x must be 1", what);
-    const bool in_place = view->mem == MVS_MEM_DEVICE && out_mem == MVS_MEM_DEVICE && out == view->data;
-    if (in_place && (out_dtype != view->dtype || view->stride[1] != view->shape[2] || view->stride[0] != view->shape[1] * view->shape[2]))
-        return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "%s: in place needs a contiguous array and out_dtype == dtype", what);
-    MvsContext* c;
-    int rc = mvs_check_ready(device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
-
-    const size_t es = mvs_dtype_size(view->dtype), es_out = mvs_dtype_size(out_dtype);
-    const size_t n = (size_t)view->shape[0] * view->shape[1] * view->shape[2];
-    size_t view_bytes = 0, cursor = 0;
-    rc = mvs_stage_views_bytes(c, view, 1, es, &view_bytes);
-    if (rc) return rc;
-    char* area = nullptr;
-    if (view_bytes) {
-        area = (char*)mvs_scratch(c, 0, view_bytes);
-        if (!area) return mvs_alloc_failed(c);
-    }
-    const void* dptr;
-    rc = mvs_stage_view(c, *view, es, area, &cursor, &dptr);
-    if (rc) return rc;
-
+    if (coeff_mem != MVS_MEM_HOST && coeff_mem != MVS_MEM_DEVICE) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: bad coeff_mem", what);
     PlaneArgs P;
-    P.in = dptr;
-    P.in_sz = view->mem == MVS_MEM_HOST ? view->shape[1] * view->shape[2] : view->stride[0];
-    P.in_sy = view->mem == MVS_MEM_HOST ? view->shape[2] : view->stride[1];
-    P.nz = (int)view->shape[0]; P.ny = (int)view->shape[1]; P.nx = (int)view->shape[2];
-    P.out = out;
-    if (out_mem == MVS_MEM_HOST) {
-        P.out = mvs_scratch(c, 1, n * es_out);
-        if (!P.out) return mvs_alloc_failed(c);
-    }
-    P.coeff = (const float2*)coeff;
-    if (coeff_mem == MVS_MEM_HOST) {
-        const size_t coeff_bytes = sizeof(float) * 2 * (size_t)P.ny * P.nx;
-        void* cd = mvs_scratch(c, 2, coeff_bytes);
-        if (!cd) return mvs_alloc_failed(c);
-        MVS_HIP_TRY(c, hipMemcpyAsync(cd, coeff, coeff_bytes, hipMemcpyHostToDevice, c->stream));
-        P.coeff = (const float2*)cd;
-    }
-    // z slabs: as few as give kPlaneTargetRows (row, slab) items, so that a lane's coefficients serve as many planes as possible
-    const long long want = (kPlaneTargetRows + P.ny - 1) / P.ny;
-    P.n_slabs = (int)std::max<long long>(1, std::min<long long>(P.nz, want));
-    P.slab = (P.nz + P.n_slabs - 1) / P.n_slabs;
-    P.n_slabs = (P.nz + P.slab - 1) / P.slab;
-
-    const long long items = (long long)P.ny * P.n_slabs;
-    const int nblocks = (int)std::min<long long>((items + kPlaneRows - 1) / kPlaneRows, 1 << 20);
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    mvs_dispatch_dtype(view->dtype, [&](auto tag) {
-        using T = decltype(tag);
-        if (out_dtype == view->dtype) launch_plane_apply<T, T>(P, nblocks, c->stream);
-        else launch_plane_apply<T, float>(P, nblocks, c->stream);
+    int nblocks = 0;
+    hipStream_t stream = nullptr;
+    auto prepare = [&](MvsContext* c, const TileApplyArgs& A) -> int {
+        stream = c->stream;
+        static_cast<TileApplyArgs&>(P) = A;
+        P.coeff = (const float2*)coeff;
+        if (coeff_mem == MVS_MEM_HOST) {
+            const size_t coeff_bytes = sizeof(float) * 2 * (size_t)P.ny * P.nx;
+            void* cd = mvs_scratch(c, 2, coeff_bytes);
+            if (!cd) return mvs_alloc_failed(c);
+            MVS_HIP_TRY(c, hipMemcpyAsync(cd, coeff, coeff_bytes, hipMemcpyHostToDevice, c->stream));
+            P.coeff = (const float2*)cd;
+        }
+        // z slabs: as few as give kPlaneTargetRows (row, slab) items, so that a lane's coefficients serve as many planes as possible
+        const long long want = (kPlaneTargetRows + P.ny - 1) / P.ny;
+        P.n_slabs = (int)std::max<long long>(1, std::min<long long>(P.nz, want));
+        P.slab = (P.nz + P.n_slabs - 1) / P.n_slabs;
+        P.n_slabs = (P.nz + P.slab - 1) / P.slab;
+        const long long items = (long long)P.ny * P.n_slabs;
+        nblocks = (int)std::min<long long>((items + kPlaneRows - 1) / kPlaneRows, 1 << 20);
+        return MVS_OK;
+    };
+    return mvs_tile_apply(device, what, view, ndim, out, out_dtype, out_mem, prepare, [&](auto tin, auto tout) {
+        launch_plane_apply<decltype(tin), decltype(tout)>(P, nblocks, stream);
     });
-    MVS_HIP_TRY(c, hipGetLastError());
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->timing_valid = true;
-    if (out_mem == MVS_MEM_HOST) MVS_HIP_TRY(c, hipMemcpyAsync(out, P.out, n * es_out, hipMemcpyDeviceToHost, c->stream));
-    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return MVS_OK;
 }

@@ -146,6 +146,15 @@ def fill_view_geometry(view, data_ptr, dtype_code, mem, shape, strides_elems, ma
     view.matrix[:] = m3.reshape(-1).tolist()
 
 
+def tile_view(data, matrix, offset, device):
+    """``(mvs_view_t, array to keep alive)`` of one whole tile for the entry points that take tiles (metrics, PSF extraction,
+    intensity, shading): ``view_data`` and ``fill_view_geometry`` with the tile's own dtype."""
+    view = _lib.mvs_view_t()
+    ptr, s3, st3, mem, keep = view_data(data, device)
+    fill_view_geometry(view, ptr, _lib.DTYPE_CODES[np.dtype(keep.dtype)], mem, s3, st3, matrix, offset)
+    return view, keep
+
+
 def check_interpolation_order(order, name):
     """The reference forwards ``order`` to scipy.ndimage.affine_transform unchanged (transformation.py:85-94,
     fusion/_core.py:797, 1627); the HIP resampler has nearest (0) and bi / trilinear (1) taps only.  Higher spline orders

@@ -252,3 +252,29 @@ def _check_scores(a, b, t_cands, region_mode):
                 assert spear2[i] == spear[i], (i, spear2[i], spear[i])
             else:
                 assert np.isnan(spear2[i])
+
+
+# ---- what the apply tests of test_intensity_gpu.py and test_shading_gpu.py share ----
+def apply_input(shape, dtype, seed):
+    rng = np.random.default_rng(seed)
+    if dtype == np.float32:
+        x = (rng.random(shape) * 200 - 50).astype(np.float32)
+        x.ravel()[::7] = np.nan
+        return x
+    hi = np.iinfo(dtype).max
+    x = rng.integers(0, hi + 1, size=shape).astype(dtype)
+    x.ravel()[::5] = hi
+    x.ravel()[1::5] = 0
+    return x
+
+
+def apply_coeff(cells, dtype, seed):
+    """Gains 0.4 .. 1.9 and offsets on both sides of zero, large enough to saturate integer outputs at both ends; ``cells``: the
+    shape of the coefficient grid (cells per axis, or the pixels of a plane)."""
+    rng = np.random.default_rng(seed)
+    span = 1.0 if dtype == np.float32 else float(np.iinfo(dtype).max)
+    return np.stack([rng.random(cells) * 1.5 + 0.4, (rng.random(cells) - 0.5) * 0.8 * span], axis=-1).astype(np.float32)
+
+
+def same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()

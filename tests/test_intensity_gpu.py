@@ -13,7 +13,7 @@ from multiview_stitcher_amd import _intensity_ops, _lib, _metric_ops, fusion, in
 from multiview_stitcher_amd.device import DeviceArray, to_device
 from tests import intensity_oracle as io
 from tests import metrics_oracle as mo
-from tests.helpers import assert_fused_close
+from tests.helpers import apply_coeff, apply_input, assert_fused_close, same_bits
 from tests.intensity_helpers import DTYPES, mosaic, pair_case
 
 pytestmark = pytest.mark.gpu
@@ -164,30 +164,6 @@ def test_a_record_without_counted_samples_gives_zeros(hip_device):
 
 
 # ---- apply --------------------------------------------------------------------------------------------------------------------------
-def apply_input(shape, dtype, seed):
-    rng = np.random.default_rng(seed)
-    if dtype == np.float32:
-        x = (rng.random(shape) * 200 - 50).astype(np.float32)
-        x.ravel()[::7] = np.nan
-        return x
-    hi = np.iinfo(dtype).max
-    x = rng.integers(0, hi + 1, size=shape).astype(dtype)
-    x.ravel()[::5] = hi
-    x.ravel()[1::5] = 0
-    return x
-
-
-def apply_coeff(cells, dtype, seed):
-    """Gains 0.4 .. 1.9 and offsets on both sides of zero, large enough to saturate integer outputs at both ends."""
-    rng = np.random.default_rng(seed)
-    span = 1.0 if dtype == np.float32 else float(np.iinfo(dtype).max)
-    return np.stack([rng.random(cells) * 1.5 + 0.4, (rng.random(cells) - 0.5) * 0.8 * span], axis=-1).astype(np.float32)
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
-
-
 APPLY_CASES = [
     # shape, cells: row lengths 5, 8, 13, 67; one cell on some axes; as many cells as pixels
     ((6, 5), (2, 5)), ((9, 8), (1, 3)), ((7, 13), (7, 1)), ((5, 67), (3, 16)),

@@ -14,6 +14,7 @@ import pytest
 from multiview_stitcher_amd import _shading_ops, intensity, msi_utils
 from multiview_stitcher_amd.device import DeviceArray, to_device
 from tests import shading_oracle as so
+from tests.helpers import apply_coeff, apply_input, same_bits
 from tests.shading_helpers import CASES, RECOVERY_CAP, oracle_planes, planted_case, recovery_error
 
 pytestmark = pytest.mark.gpu
@@ -46,8 +47,8 @@ def assert_selects_like_the_oracle(tiles, q=Q5, got=None):
     return planes, counts
 
 
-def same_bits(a, b):
-    return all(x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes() for x, y in zip(a, b))
+def same_planes(a, b):
+    return all(same_bits(x, y) for x, y in zip(a, b))
 
 
 # ---- quantiles against the oracle ----------------------------------------------------------------------------------------------------
@@ -135,10 +136,10 @@ def test_view_order_and_memory_do_not_change_the_bits(hip_device, dtype_name):
     tiles = bits_case(dtype_name)
     q = (0.02, 0.5, 0.73)
     first = assert_selects_like_the_oracle(tiles, q)
-    assert same_bits(first, _shading_ops.stack_quantiles(tiles[::-1], q))
+    assert same_planes(first, _shading_ops.stack_quantiles(tiles[::-1], q))
     resident = [DeviceArray.from_host(t) for t in tiles]
-    assert same_bits(first, _shading_ops.stack_quantiles(resident, q))
-    assert same_bits(first, _shading_ops.stack_quantiles([resident[0], tiles[1], resident[2], tiles[3]], q))
+    assert same_planes(first, _shading_ops.stack_quantiles(resident, q))
+    assert same_planes(first, _shading_ops.stack_quantiles([resident[0], tiles[1], resident[2], tiles[3]], q))
     # windows at x offset 3 / y offset 1 of larger arrays: rows that are not 4-byte aligned for uint8 / uint16
     big = [np.full((t.shape[0] + 1, t.shape[1] + 2, t.shape[2] + 5), 9, t.dtype) for t in tiles]
     win = (slice(None, -1), slice(1, 6), slice(3, 73))
@@ -146,10 +147,10 @@ def test_view_order_and_memory_do_not_change_the_bits(hip_device, dtype_name):
         b[win] = t
     dev_windows = [DeviceArray.from_host(b)[win] for b in big]
     assert not dev_windows[0].is_contiguous()
-    assert same_bits(first, _shading_ops.stack_quantiles(dev_windows, q))
+    assert same_planes(first, _shading_ops.stack_quantiles(dev_windows, q))
     host_windows = [b[win] for b in big]
     assert not host_windows[0].flags.c_contiguous
-    assert same_bits(first, _shading_ops.stack_quantiles(host_windows, q))
+    assert same_planes(first, _shading_ops.stack_quantiles(host_windows, q))
 
 
 @pytest.mark.parametrize("dtype_name", ["u16", "f32"])
@@ -157,10 +158,10 @@ def test_every_second_plane_by_stride(hip_device, dtype_name):
     tiles = bits_case(dtype_name)
     copied = [np.ascontiguousarray(t[::2]) for t in tiles]
     want = assert_selects_like_the_oracle(copied, (0.5,))
-    assert same_bits(want, _shading_ops.stack_quantiles([_shading_ops.every_kth_plane(t, 2) for t in tiles], 0.5))
+    assert same_planes(want, _shading_ops.stack_quantiles([_shading_ops.every_kth_plane(t, 2) for t in tiles], 0.5))
     resident = [_shading_ops.every_kth_plane(DeviceArray.from_host(t), 2) for t in tiles]
     assert [r.shape for r in resident] == [c.shape for c in copied]
-    assert same_bits(want, _shading_ops.stack_quantiles(resident, 0.5))
+    assert same_planes(want, _shading_ops.stack_quantiles(resident, 0.5))
 
 
 def test_bad_stacks_are_refused(hip_device):
@@ -176,30 +177,6 @@ def test_bad_stacks_are_refused(hip_device):
 
 
 # ---- apply -----------------------------------------------------------------------------------------------------------------------------
-def apply_input(shape, dtype, seed):
-    rng = np.random.default_rng(seed)
-    if dtype == np.float32:
-        x = (rng.random(shape) * 200 - 50).astype(np.float32)
-        x.ravel()[::7] = np.nan
-        return x
-    hi = np.iinfo(dtype).max
-    x = rng.integers(0, hi + 1, size=shape).astype(dtype)
-    x.ravel()[::5] = hi
-    x.ravel()[1::5] = 0
-    return x
-
-
-def apply_coeff(plane_shape, dtype, seed):
-    """Gains 0.4 .. 1.9 and offsets on both sides of zero, large enough to saturate integer outputs at both ends."""
-    rng = np.random.default_rng(seed)
-    span = 1.0 if dtype == np.float32 else float(np.iinfo(dtype).max)
-    return np.stack([rng.random(plane_shape) * 1.5 + 0.4, (rng.random(plane_shape) - 0.5) * 0.8 * span], axis=-1).astype(np.float32)
-
-
-def bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
-
-
 APPLY_SHAPES = [
     # rows of 5, 8, 13, 67; 2-D, z = 1, 2, 9
     (6, 5), (9, 8), (7, 13), (5, 67), (1, 6, 5), (2, 3, 8), (9, 4, 13), (9, 5, 67), (2, 7, 64),
@@ -223,17 +200,17 @@ def test_apply_matches_the_float32_restatement(hip_device, shape, dtype_name):
         host = _shading_ops.apply_plane(x, coeff, out_dtype=out_dtype)
         dev = _shading_ops.apply_plane(DeviceArray.from_host(x), coeff, out_dtype=out_dtype)
         assert isinstance(host, np.ndarray) and isinstance(dev, DeviceArray)
-        assert bits(host, want), (out_dtype, np.argwhere(host != want)[:5])
-        assert bits(dev.get(), want)
+        assert same_bits(host, want), (out_dtype, np.argwhere(host != want)[:5])
+        assert same_bits(dev.get(), want)
         # coefficients from device memory, for host and resident tiles
-        assert bits(_shading_ops.apply_plane(x, coeff_dev, out_dtype=out_dtype), want)
-        assert bits(_shading_ops.apply_plane(DeviceArray.from_host(x), coeff_dev, out_dtype=out_dtype).get(), want)
+        assert same_bits(_shading_ops.apply_plane(x, coeff_dev, out_dtype=out_dtype), want)
+        assert same_bits(_shading_ops.apply_plane(DeviceArray.from_host(x), coeff_dev, out_dtype=out_dtype).get(), want)
     # in place equals out of place, on the device and on the host
     d = DeviceArray.from_host(x)
-    assert _shading_ops.apply_plane(d, coeff_dev, out=d) is d and bits(d.get(), so.apply(x, coeff))
+    assert _shading_ops.apply_plane(d, coeff_dev, out=d) is d and same_bits(d.get(), so.apply(x, coeff))
     h = x.copy()
     _shading_ops.apply_plane(h, coeff, out=h)
-    assert bits(h, so.apply(x, coeff))
+    assert same_bits(h, so.apply(x, coeff))
 
 
 @pytest.mark.parametrize("dtype_name", list(DTYPES))
@@ -246,7 +223,7 @@ def test_apply_reads_a_window_at_an_odd_offset(hip_device, dtype_name):
     assert not window.is_contiguous()
     for out_dtype in dict.fromkeys([dtype, np.float32]):
         got = _shading_ops.apply_plane(window, coeff, out_dtype=out_dtype)
-        assert got.is_contiguous() and bits(got.get(), so.apply(np.ascontiguousarray(big[win]), coeff, out_dtype))
+        assert got.is_contiguous() and same_bits(got.get(), so.apply(np.ascontiguousarray(big[win]), coeff, out_dtype))
 
 
 def test_apply_rounds_ties_to_even_and_keeps_nan(hip_device):
@@ -289,7 +266,7 @@ def test_a_planted_profile_is_estimated_and_removed(hip_device, name, dtype_name
     for msims in (case["msims"], resident_msims(case["msims"])):
         got, info = intensity.estimate_shading(msims, darkfield=case["dark"], return_info=True)
         assert np.array_equal(info["planes"], planes) and np.array_equal(info["counts"], counts)
-        assert bits(got["flatfield"], want["flatfield"]) and bits(got["darkfield"], want["darkfield"]) and got["offset"] == want["offset"]
+        assert same_bits(got["flatfield"], want["flatfield"]) and same_bits(got["darkfield"], want["darkfield"]) and got["offset"] == want["offset"]
         corrected = intensity.apply_shading(msims, got, out_dtype=None)
         assert all(msi_utils.is_msim(c) for c in corrected)
         worst = raw_worst = 0.0
@@ -322,4 +299,4 @@ def test_shading_per_channel_in_place_and_every_second_plane(hip_device):
         assert sim.data is msi_utils.get_sim_from_msim(r).data
         for ch, key in enumerate("ab"):
             lead = tuple(ch if d == "c" else 0 for d in sim.dims[:2])
-            assert bits(sim.data[lead].get(), so.apply(t[ch], so.coefficients(models[key])))
+            assert same_bits(sim.data[lead].get(), so.apply(t[ch], so.coefficients(models[key])))
