@@ -8,6 +8,8 @@
 
 from __future__ import annotations
 
+import collections
+import ctypes as C
 import logging
 import os
 import warnings
@@ -49,6 +51,11 @@ def _enumerate_candidates(shift_candidates, shape, ndim):
     return t_candidates
 
 
+def _default_upsample_factor(ndim):
+    """``upsample_factor`` of the phase correlation when the caller gives none (registration.py:410-411)."""
+    return 10 if ndim == 2 else 2
+
+
 def phase_correlation_registration(fixed_data, moving_data, disambiguate_region_mode=None, device=0,
                                    return_debug=False, _constant_check=False, **skimage_phase_corr_kwargs):
     """Translation between two same-shape overlap crops (float32, NaN = outside the view).
@@ -67,7 +74,7 @@ def phase_correlation_registration(fixed_data, moving_data, disambiguate_region_
     if not return_debug and set(skimage_phase_corr_kwargs) <= {"upsample_factor"}:
         # the whole function as one library call (same steps, same quirks); the Python flow below stays for the debug
         # outputs and for callers that pass other phase_cross_correlation keywords
-        uf = skimage_phase_corr_kwargs.get("upsample_factor", 10 if ndim == 2 else 2)
+        uf = skimage_phase_corr_kwargs.get("upsample_factor", _default_upsample_factor(ndim))
         t, quality, status, _ = _reg_ops.register_crops(im0, im1, uf, disambiguate_region_mode, _constant_check, device)
         if status == 2:
             warnings.warn(
@@ -97,7 +104,7 @@ def phase_correlation_registration(fixed_data, moving_data, disambiguate_region_
     if disambiguate_region_mode is None:
         disambiguate_region_mode = "intersection" if has_nan else "union"
     if "upsample_factor" not in skimage_phase_corr_kwargs:
-        skimage_phase_corr_kwargs["upsample_factor"] = 10 if ndim == 2 else 2
+        skimage_phase_corr_kwargs["upsample_factor"] = _default_upsample_factor(ndim)
     upsample_factor = skimage_phase_corr_kwargs["upsample_factor"]
 
     # strategy of the reference: phase correlation with and without normalisation, the candidate with
@@ -329,6 +336,24 @@ def si_utils_extend(stack_props, extend_by):
     return sp
 
 
+def _normalise_tolerance(overlap_tolerance, sdims):
+    """``overlap_tolerance`` (None, one number, or a dict that may leave dims out) as {dim: float} over ``sdims``."""
+    if overlap_tolerance is None:
+        return {d: 0.0 for d in sdims}
+    if isinstance(overlap_tolerance, (int, float)):
+        return {d: float(overlap_tolerance) for d in sdims}
+    return {d: float(overlap_tolerance.get(d, 0.0)) for d in sdims}
+
+
+def _binned_coords(coords, b):
+    """Coordinates of an axis binned by ``b`` (``coarsen(boundary="trim").mean()``, registration.py:1732-1741): the mean of
+    every group of ``b`` samples -- the sum divided by b, as numpy's mean does it -- a trailing group that is not full dropped.
+    ``coords``: one axis (L,) or the same axis of several views stacked (views, L): one reduction for all of them (the same
+    additions per element as view by view)."""
+    m = coords.shape[-1] // b
+    return np.add.reduce(coords[..., : m * b].reshape(coords.shape[:-1] + (m, b)), axis=-1) / b
+
+
 def _bin_sim(sim, binning, device, wait=True, out=None):
     """sim.coarsen(binning, boundary="trim").mean().astype(dtype) incl. the coarsened coordinates
     (registration.py:1732-1741)."""
@@ -341,10 +366,7 @@ def _bin_sim(sim, binning, device, wait=True, out=None):
     if is_device_array(sim.data):
         sim.data.wait_ready(device)      # (an upload still in flight: this lane's stream waits for it)
     data = _reg_ops.bin_mean(sim.data, bins, device, wait=wait) if out is None else _reg_ops.bin_mean(sim.data, bins, device, wait=wait, out=out)
-    coords = {}
-    for d, b, n in zip(sdims, bins, data.shape):
-        c = sim.coords[d][: n * b].reshape(n, b).mean(axis=1)
-        coords[d] = c
+    coords = {d: _binned_coords(np.asarray(sim.coords[d]), b) for d, b in zip(sdims, bins)}
     out = si_utils.SpatialImage(data, sdims, coords, {"transforms": dict(sim.attrs.get("transforms", {}))})
     return out
 
@@ -633,7 +655,7 @@ def _lean_register_pair(g1b, g2b, g1, g2, sdims, tol, upsample_factor, transform
         raise ValueError("views do not overlap")
     n = len(sdims)
     slabs = [g.sim.data[tuple(slice(a, b) for a, b in plan["windows"][i])] for i, g in enumerate((g1b, g2b))]
-    uf = (10 if n == 2 else 2) if upsample_factor is None else upsample_factor
+    uf = _default_upsample_factor(n) if upsample_factor is None else upsample_factor
     if all(is_device_array(d) and d.dtype in _lib.DTYPE_CODES for d in slabs):
         # resample both crops + register them: one library call, no crop allocation, no wait in between
         t, quality, status, _ = _reg_ops.register_views(slabs[0], plan["matrix_diag"][0], plan["offset"][0], slabs[1], plan["matrix_diag"][1],
@@ -711,6 +733,323 @@ def _pair_results_from_plan(ts, qualities, statuses, out_origin, out_spacing, ou
     return [{"transform": affine_phys[k], "quality": float(quality[k]), "bbox": np.array([lo_world[k], up_world[k]])} for k in range(ne)]
 
 
+# ---- the batched pair path, step by step (_register_pairs_batched below is the driver).  Everything but _run_pair_jobs, and
+# the binned copies _crop_sources makes when the crops cannot come from the raw tiles, is host code that runs without a device:
+# tests/test_pair_batch.py (plans, results), tests/test_pair_batch_steps.py (the other steps, the driver around a stand-in run) ----
+class _PairBatch:
+    """What the steps share about one covered call (filled by _batch_coverage): the arguments the steps read, the used views
+    (``used``: their indices into ``sims``, sorted) with their geometry in that order, and the pairs as indices into ``used``."""
+
+    __slots__ = ("sims", "edges", "transform_key", "registration_binning", "overlap_tolerance", "device", "used", "sdims", "n", "dtype",
+                 "binning", "bins", "do_bin", "tol", "geoms", "geoms_b", "pairs")
+
+
+def _upload_order(sims, edges):
+    """The order in which the pairs run while tiles are still on their way to the device (device.to_device_async uploads them in
+    list order): by the later tile of each pair, as indices into ``edges``.  None: as given (nothing in flight, or already so)."""
+    if not any(is_device_array(getattr(sims[v], "data", None)) and sims[v].data.ready_ticket for e in edges for v in e):
+        return None
+    order = sorted(range(len(edges)), key=[max(e) for e in edges].__getitem__)
+    return None if order == list(range(len(edges))) else order
+
+
+def _in_edge_order(part, index, n_edges):
+    """``part[k]`` is the result of edge ``index[k]``: the list over all ``n_edges`` edges (None where ``index`` names none)."""
+    res = [None] * n_edges
+    for k, r in zip(index, part):
+        res[k] = r
+    return res
+
+
+def _pair_geometry(sims, transform_key, bins):
+    """_TileGeom of every view as it is and as the registration binning ``bins`` leaves it (coordinates only -- _bin_sim's -- without
+    touching a voxel).  Views of one shape: one reduction per axis for all of them (host time)."""
+    geoms = [_TileGeom(s, transform_key) for s in sims]
+    if max(bins) == 1:
+        return geoms, geoms
+    if all(g.shape == geoms[0].shape for g in geoms):
+        stacked = [_binned_coords(np.stack([g.coords[k] for g in geoms]), b) for k, b in enumerate(bins)]
+        coords = [[st[i] for st in stacked] for i in range(len(geoms))]
+    else:
+        coords = [[_binned_coords(g.coords[k], b) for k, b in enumerate(bins)] for g in geoms]
+    return geoms, [_TileGeom(s, transform_key, like=g, coords=c) for s, g, c in zip(sims, geoms, coords)]
+
+
+def _batch_coverage(sims, edges, transform_key, registration_binning, overlap_tolerance, device):
+    """The _PairBatch of a call the batched path covers, or None: plain device-resident images (no pyramids, spatial dims only) of
+    one supported dtype on ``device`` whose rows are contiguous, transforms that are pure translations, one binning for all pairs
+    that leaves at least one sample per axis.  Decided on the host, before any library call."""
+    from . import msi_utils
+    from . import spatial_image_utils as si_utils
+
+    if not edges or any(msi_utils.is_msim(m) for m in sims):
+        return None
+    b = _PairBatch()
+    b.sims, b.edges, b.transform_key, b.device = sims, edges, transform_key, device
+    b.registration_binning, b.overlap_tolerance = registration_binning, overlap_tolerance
+    b.used = used = sorted({v for e in edges for v in e})
+    first = sims[used[0]]
+    b.sdims = sdims = si_utils.get_spatial_dims_from_sim(first)
+    b.n = len(sdims)
+    b.dtype = first.data.dtype
+    for v in used:
+        s_ = sims[v]
+        if list(s_.dims) != list(sdims) or not is_device_array(s_.data) or s_.data.dtype != b.dtype or s_.data.dtype not in _lib.DTYPE_CODES:
+            return None
+    if registration_binning is None:
+        shape0, sp0 = si_utils.get_shape_from_sim(first), si_utils.get_spacing_from_sim(first)
+        if any(si_utils.get_shape_from_sim(sims[v]) != shape0 or si_utils.get_spacing_from_sim(sims[v]) != sp0 for v in used[1:]):
+            return None                  # the optimal binning would differ between pairs
+        b.binning = get_optimal_registration_binning(sims[edges[0][0]], sims[edges[0][1]])
+    else:
+        b.binning = dict(registration_binning)
+    b.do_bin = max(b.binning.values()) > 1
+    b.bins = [int(b.binning.get(d, 1)) for d in sdims]
+    tol = _normalise_tolerance(overlap_tolerance, sdims)
+    b.tol = [tol[d] for d in sdims]
+    if not all((sims[v].data.device & 0xff) == (device & 0xff) and sims[v].data.strides[-1] == 1 for v in used):
+        return None
+    if any(len(sims[v].coords[d]) // bb < 1 for v in used for d, bb in zip(sdims, b.bins)):
+        return None                      # a binned axis without a sample
+    b.geoms, b.geoms_b = _pair_geometry([sims[v] for v in used], transform_key, b.bins)
+    if any(g.t is None for g in b.geoms):
+        return None
+    slot = {v: i for i, v in enumerate(used)}
+    b.pairs = np.array([[slot[i], slot[j]] for i, j in edges], dtype=np.int32).reshape(len(edges), 2)
+    return b
+
+
+def _as_ptr(a, ctype):
+    return a.ctypes.data_as(C.POINTER(ctype))
+
+
+_PairPlans = collections.namedtuple("_PairPlans", "windows out_origin out_spacing out_shape matrix_diag offset status")
+
+
+def _plan_pairs(geoms, pairs, tol):
+    """The binding of mvs_plan_pairs (host code; the arithmetic of _lean_pair_plan): crop windows (pairs, 2, 3, 2), output grid and
+    pixel affines (diagonal and offset, (pairs, 2, 3)) of the ``pairs`` (index pairs into ``geoms``), axes in the first ``n`` slots;
+    ``status`` 1: the views do not overlap.  None when the library declines the call."""
+    n, nv = len(geoms[0].sdims), len(geoms)
+    pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    ne = len(pr)
+    cptr = (C.c_void_p * (nv * n))(*[g.coords[k].__array_interface__["data"][0] for g in geoms for k in range(n)])
+    clen = np.array([len(g.coords[k]) for g in geoms for k in range(n)], dtype=np.int64)
+    tr = np.array([g.t for g in geoms], dtype=np.float64).reshape(nv, n)
+    tolv = np.array(tol, dtype=np.float64)
+    p = _PairPlans(np.zeros((ne, 2, 3, 2), dtype=np.int64), np.zeros((ne, 3)), np.zeros((ne, 3)), np.ones((ne, 3), dtype=np.int64),
+                   np.zeros((ne, 2, 3)), np.zeros((ne, 2, 3)), np.zeros(ne, dtype=np.int32))
+    rc = _lib.load().mvs_plan_pairs(n, nv, cptr, _as_ptr(clen, C.c_int64), _as_ptr(tr, C.c_double), _as_ptr(tolv, C.c_double), ne,
+                                    _as_ptr(pr, C.c_int32), _as_ptr(p.windows, C.c_int64), _as_ptr(p.out_origin, C.c_double),
+                                    _as_ptr(p.out_spacing, C.c_double), _as_ptr(p.out_shape, C.c_int64), _as_ptr(p.matrix_diag, C.c_double),
+                                    _as_ptr(p.offset, C.c_double), _as_ptr(p.status, C.c_int32))
+    return None if rc != 0 else p
+
+
+def _world_boxes(geoms, pairs, tol):
+    """_lean_overlap(..., to_intrinsic=False) of all ``pairs`` (index pairs into ``geoms``: the UNBINNED views) at once: the lower
+    and upper corner of every overlap box in world coordinates, (pairs, n) each."""
+    n = len(geoms[0].sdims)
+    pr = np.asarray(pairs).reshape(-1, 2)
+    tolv = np.array(tol, dtype=np.float64)
+    o = np.array([g.origin for g in geoms], dtype=np.float64).reshape(-1, n)
+    sp = np.array([g.spacing for g in geoms], dtype=np.float64).reshape(-1, n)
+    shp = np.array([g.shape for g in geoms], dtype=np.int64).reshape(-1, n)
+    tw = np.array([g.t for g in geoms], dtype=np.float64).reshape(-1, n)
+    shp = shp + np.ceil(2 * tolv / sp).astype(np.int64)
+    o = o - tolv
+    lo_v = o + tw
+    hi_v = ((shp - 1) * 1.0 * sp + o) + tw
+    lo = np.maximum(lo_v[pr[:, 0]], lo_v[pr[:, 1]])
+    hi = np.minimum(hi_v[pr[:, 0]], hi_v[pr[:, 1]])
+    return lo, 1.0 * (hi - lo) + lo
+
+
+def _crops_from_raw_tiles(dtype, do_bin, plans, n):
+    """Binned integer tiles whose crops are whole-pixel translations (every regular mosaic): the crops come straight from the RAW
+    tiles, the binning applied inside the crop kernel (job.bin) -- no binned copy of a tile is ever made, a pair reads only the slabs
+    its overlap needs."""
+    return bool(do_bin and _raw_crops_enabled[0] and dtype in (np.dtype(np.uint8), np.dtype(np.uint16))
+                and np.all(plans.matrix_diag[:, :, :n] == 1.0) and np.all(plans.offset[:, :, :n] == np.floor(plans.offset[:, :, :n])))
+
+
+def _crop_sources(b, plans, cache):
+    """Where the crops of the batch come from: ``(arrays, tickets, raw_crops, prebin_lane)`` -- per used view the DeviceArray the
+    windows index and the ticket a pair's lane waits for before it reads it; whether these are the raw tiles with the binning left
+    to the crop kernel (_crops_from_raw_tiles); the lane the binning was queued on, to be waited for after the pairs (or None).
+    Otherwise binned tiles serve, pre-binned in groups with stream tickets (_prebin_views).  Counts the pairs in
+    ``cache.raw_crops``.  None: a binned copy is not what the plans assume, the caller takes the per-pair path."""
+    import functools
+
+    sims, used, device = b.sims, b.used, b.device
+    raw_crops = _crops_from_raw_tiles(b.dtype, b.do_bin, plans, b.n)
+    prebin_lane = None
+    if raw_crops or not b.do_bin:
+        arrays = [sims[v].data for v in used]
+        # tiles still on their way to the device (device.to_device_async): a pair's lane waits for the uploads of ITS two tiles
+        tickets = [a.ready_ticket for a in arrays]
+    else:
+        bkey = tuple(sorted(b.binning.items()))
+        if all(cache.ticket_of((id(sims[v].data), bkey)) is None and (id(sims[v].data), bkey) not in cache._items for v in used):
+            # (queues the binning of all views on the last context lane; None: not a regular mosaic, the views are binned one by one below)
+            prebin_lane = _prebin_views([sims[v] for v in used], b.binning, device, cache)
+        arrays, tickets = [], []
+        for v, g in zip(used, b.geoms_b):
+            s_ = sims[v]
+            key = (id(s_.data), bkey)
+            b_ = cache.get_or_compute(key, functools.partial(_bin_sim, s_, b.binning, device), keep=s_.data)
+            tickets.append(cache.ticket_of(key) or 0)
+            if (b_.data.device & 0xff) != (device & 0xff) or b_.data.strides[-1] != 1 or [len(b_.coords[d]) for d in b.sdims] != g.shape:
+                return None
+            arrays.append(b_.data)
+    cache.raw_crops = len(b.edges) if raw_crops else 0
+    return arrays, tickets, raw_crops, prebin_lane
+
+
+def _fill_pair_jobs(plans, pairs, n, base, strides, itemsize, dtype_code, tickets, bin_scale=None, timed=False):
+    """One mvs_pair_job_t per pair: its two crop windows as mvs_view_t (strided windows into the arrays at ``base``, one pointer,
+    one row of ``strides`` (in elements) and one ticket per view; ``pairs`` index them) and the output grid.  ``bin_scale``: the bins
+    per axis when the arrays are raw tiles (window indices of the binned grid times the bin; job.bin), None when the windows index
+    the arrays as they are.  ``timed``: every pair leaves a timed ticket of its last kernel (flags).  Plain numpy, no library."""
+    ne = len(pairs)
+    jobs = (_lib.mvs_pair_job_t * ne)()
+    ja = np.frombuffer(jobs, dtype=_JOB_DTYPE)
+    k0 = 3 - n
+    base, tk = np.asarray(base, dtype=np.uint64), np.asarray(tickets, dtype=np.uint64)
+    strides = np.asarray(strides, dtype=np.int64).reshape(-1, n)
+    scale = np.array([1] * n if bin_scale is None else bin_scale, dtype=np.int64)      # binned index -> index of the source array
+    for i, name in enumerate(("fixed", "moving")):
+        f = ja[name]
+        vi = pairs[:, i]
+        a, b = plans.windows[:, i, :n, 0] * scale, plans.windows[:, i, :n, 1] * scale
+        st = strides[vi]
+        f["data"] = base[vi] + (np.sum(a * st, axis=1) * itemsize).astype(np.uint64)
+        f["dtype"] = dtype_code
+        f["mem"] = _lib.MVS_MEM_DEVICE
+        f["shape"][:, :k0] = 1
+        f["shape"][:, k0:] = b - a
+        if n == 3:
+            f["stride"][:] = st
+        else:       # a 2D slab is one z plane
+            f["stride"][:, 0] = st[:, 0] * (b - a)[:, 0]
+            f["stride"][:, 1:] = st
+        f["matrix"][:] = 0.0
+        f["matrix"][:, [0, 4, 8]] = 1.0
+        f["matrix"][:, [(k0 + k) * 4 for k in range(n)]] = plans.matrix_diag[:, i, :n]
+        f["offset"][:] = 0.0
+        f["offset"][:, k0:] = plans.offset[:, i, :n]
+        ja["wait_ticket"][:, i] = tk[vi]
+    ja["out_shape"][:, :k0] = 1
+    ja["out_shape"][:, k0:] = plans.out_shape[:, :n]
+    if bin_scale is not None:
+        ja["bin"][:, :k0] = 1
+        ja["bin"][:, k0:] = scale
+    if timed:
+        ja["flags"][:] = 1
+    return jobs
+
+
+def _run_pair_jobs(jobs, edges, n, upsample_factor, n_lanes, device, prebin_lane=None):
+    """mvs_register_pairs on ``n_lanes`` context lanes driven by native threads -- the one step of the batched path that needs the
+    GPU: ``(shifts (pairs, n), qualities, statuses)`` as mvs_register_views reports them per pair.  ``prebin_lane``: waited for
+    when the pairs are done or have failed.  Fills ``_pair_timeline``."""
+    ne = len(jobs)
+    t3, q = np.zeros((ne, 3)), np.zeros(ne)
+    status, ncand, rcs = np.zeros(ne, dtype=np.int32), np.zeros(ne, dtype=np.int32), np.zeros(ne, dtype=np.int32)
+    lib = _lib.init(device & 0xff)
+    try:
+        rc = lib.mvs_register_pairs(device & 0xff, ne, jobs, n, int(upsample_factor), -1, 1, int(n_lanes), _as_ptr(t3, C.c_double),
+                                    _as_ptr(q, C.c_double), _as_ptr(status, C.c_int32), _as_ptr(ncand, C.c_int32), _as_ptr(rcs, C.c_int32))
+    finally:
+        if prebin_lane is not None:
+            _lib.synchronize(prebin_lane)      # (done long ago unless a pair failed: nothing stays queued on the caller's tiles)
+    _lib.check(rc, device & 0xff, "mvs_register_pairs")
+    if _pair_timeline is not None:
+        done = np.frombuffer(jobs, dtype=_JOB_DTYPE)["wait_ticket"]
+        _pair_timeline.extend((tuple(edges[e]), int(done[e, 0])) for e in range(ne))
+    return t3[:, 3 - n:], q, status
+
+
+def _register_planned_pairs(b, plans, pairwise_reg_func_kwargs, n_lanes, cache):
+    """Crop sources -> jobs -> mvs_register_pairs -> the result dicts of all pairs (None: not covered after all)."""
+    src = _crop_sources(b, plans, cache)
+    if src is None:
+        return None
+    arrays, tickets, raw_crops, prebin_lane = src
+    n = b.n
+    jobs = _fill_pair_jobs(plans, b.pairs, n, [a.ptr for a in arrays], [a.strides for a in arrays], b.dtype.itemsize, _lib.DTYPE_CODES[b.dtype],
+                           tickets, b.bins if raw_crops else None, _pair_timeline is not None)
+    upsample_factor = (pairwise_reg_func_kwargs or {}).get("upsample_factor")
+    uf = _default_upsample_factor(n) if upsample_factor is None else upsample_factor
+    ts, q, status = _run_pair_jobs(jobs, b.edges, n, uf, n_lanes, b.device, prebin_lane)
+    # ---- overlap boxes in world coordinates (_lean_overlap on the UNBINNED views) and the physical affines ----
+    lo, up = _world_boxes(b.geoms, b.pairs, b.tol)
+    fixed_aff = np.array([g.affine for g in b.geoms_b], dtype=np.float64)[b.pairs[:, 0]]
+    return _pair_results_from_plan(ts, q, status, plans.out_origin[:, :n], plans.out_spacing[:, :n], plans.out_shape[:, :n], fixed_aff, lo, up)
+
+
+class _KnifeQuestion:
+    """The crop-length question of one batch (_knife_question): its memo key; ``odd``: the remembered answer (indices of the pairs
+    whose reference crop is one sample shorter) or None while ``thread`` is still finding it out, into ``box``."""
+
+    __slots__ = ("key", "odd", "thread", "box")
+
+
+def _ask_reference_crops(box, geoms, pairs, tol, shapes):
+    """(body of the helper thread) ``box["odd"]``: the pairs whose reference crop differs; ``box["error"]``: what was raised."""
+    try:
+        box["odd"] = [e for e, (i, j) in enumerate(pairs) if _reference_crop_differs(geoms[i], geoms[j], tol, shapes[e])]
+    except BaseException as exc:      # noqa: BLE001 - handed to the caller's thread by _knife_answer
+        box["error"] = exc
+
+
+def _knife_question(geoms_b, pairs, tol, out_shapes):
+    """Which pairs have a reference crop that is one sample shorter (see _reference_crop_differs)?  They take the
+    overlap_bbox="reference" path one by one; the others stay in the batch.  One memo entry per MOSAIC geometry: a list of pair
+    indices, looked up with a few hundred bytes."""
+    q = _KnifeQuestion()
+    q.key = ("mosaic", len(geoms_b[0].sdims), pairs.tobytes(), np.array(tol, dtype=np.float64).tobytes(),
+             np.array([[g.t, g.origin, g.spacing, g.shape] for g in geoms_b], dtype=np.float64).tobytes())
+    q.thread = q.box = None
+    with _KNIFE_LOCK:
+        q.odd = _KNIFE_MEMO.get(q.key)
+    if q.odd is None:
+        # a geometry seen for the first time: the question costs ~2 ms of scipy per pair on the host (GIL-bound), the pairs
+        # themselves ~0.3 ms each on the GPU -- so it is asked on a thread of its own WHILE all pairs are registered with the
+        # closed-form crops (mvs_register_pairs releases the interpreter lock), and the pairs it names, if any, are registered
+        # again through the reference's sequence afterwards: the result is the reference's crop for every pair either way.
+        q.box = {}
+        q.thread = threading.Thread(target=_ask_reference_crops, args=(q.box, geoms_b, pairs.tolist(), tol, out_shapes.copy()),
+                                    name="mvs-crop-length", daemon=True)
+        q.thread.start()
+    return q
+
+
+def _knife_answer(q):
+    """(first call of a geometry) wait for the crop-length answers and remember them; the pairs they name."""
+    q.thread.join()
+    if "error" in q.box:
+        raise q.box["error"]
+    with _KNIFE_LOCK:
+        _KNIFE_MEMO[q.key] = q.box["odd"]
+    return q.box["odd"]
+
+
+def _redo_reference_pairs(b, res, odd, pairwise_reg_func_kwargs, cache, raw_before=None):
+    """The pairs ``odd`` of ``res`` registered the reference's way (overlap_bbox="reference"), one by one, and counted in
+    ``cache.reference_pairs``.  ``raw_before``: ``cache.raw_crops`` before a batched run that registered them too -- those
+    closed-form results are discarded, so they leave that count."""
+    cache.reference_pairs = len(odd)
+    if raw_before is not None and cache.raw_crops > raw_before:
+        cache.raw_crops = max(raw_before, cache.raw_crops - len(odd))
+    for e in odd:
+        i, j = b.edges[e]
+        res[e] = register_pair_of_msims(b.sims[i], b.sims[j], b.transform_key, registration_binning=b.registration_binning,
+                                        overlap_tolerance=b.overlap_tolerance, pairwise_reg_func_kwargs=pairwise_reg_func_kwargs,
+                                        device=b.device, _bin_cache=cache, overlap_bbox="reference")
+    return res
+
+
 def _register_pairs_batched(sims, edges, transform_key, registration_binning, overlap_tolerance, pairwise_reg_func_kwargs, device,
                             n_lanes, cache, knife_check=True):
     """compute_pairwise_registrations for the common case in two library calls: plain device-resident images of one dtype whose
@@ -719,268 +1058,40 @@ def _register_pairs_batched(sims, edges, transform_key, registration_binning, ov
     driven by native threads; the interpreter only assembles the inputs and turns the pixel shifts into physical affines
     (stacked matmuls).  Returns the list of result dicts, or None when the case is not covered (the caller then takes the
     per-pair path).  Same plans, same kernels, same results as _lean_register_pair (tests/test_pair_batch.py, -m gpu tests)."""
-    import ctypes as C
-
-    from . import msi_utils
-    from . import spatial_image_utils as si_utils
-
-    if not edges or any(msi_utils.is_msim(m) for m in sims):
+    again = (transform_key, registration_binning, overlap_tolerance, pairwise_reg_func_kwargs, device, n_lanes, cache)
+    order = _upload_order(sims, edges)
+    if order is not None:
+        # uploads in flight: the pairs in the order in which their later tile lands, results back in edge order
+        part = _register_pairs_batched(sims, [edges[k] for k in order], *again, knife_check=knife_check)
+        return None if part is None else _in_edge_order(part, order, len(edges))
+    b = _batch_coverage(sims, edges, transform_key, registration_binning, overlap_tolerance, device)
+    if b is None:
         return None
-    if any(is_device_array(sims[v].data) and sims[v].data.ready_ticket for e in edges for v in e):
-        # uploads in flight (in list order): the pairs in the order in which their later tile lands, results back in edge order
-        order = sorted(range(len(edges)), key=lambda k: max(edges[k]))
-        if order != list(range(len(edges))):
-            part = _register_pairs_batched(sims, [edges[k] for k in order], transform_key, registration_binning, overlap_tolerance,
-                                           pairwise_reg_func_kwargs, device, n_lanes, cache, knife_check=knife_check)
-            if part is None:
-                return None
-            res = [None] * len(edges)
-            for k, r in zip(order, part):
-                res[k] = r
-            return res
-    used = sorted({v for e in edges for v in e})
-    sdims = si_utils.get_spatial_dims_from_sim(sims[used[0]])
-    n = len(sdims)
-    first = sims[used[0]]
-    for v in used:
-        s_ = sims[v]
-        if list(s_.dims) != list(sdims) or not is_device_array(s_.data) or s_.data.dtype != first.data.dtype or s_.data.dtype not in _lib.DTYPE_CODES:
-            return None
-    if registration_binning is None:
-        shape0, sp0 = si_utils.get_shape_from_sim(first), si_utils.get_spacing_from_sim(first)
-        if any(si_utils.get_shape_from_sim(sims[v]) != shape0 or si_utils.get_spacing_from_sim(sims[v]) != sp0 for v in used[1:]):
-            return None                  # the optimal binning would differ between pairs
-        binning = get_optimal_registration_binning(sims[edges[0][0]], sims[edges[0][1]])
-    else:
-        binning = dict(registration_binning)
-    if overlap_tolerance is None:
-        tol = [0.0] * n
-    elif isinstance(overlap_tolerance, (int, float)):
-        tol = [float(overlap_tolerance)] * n
-    else:
-        tol = [float(overlap_tolerance.get(d, 0.0)) for d in sdims]
-    bkey = tuple(sorted(binning.items()))
-    do_bin = max(binning.values()) > 1
-    bins = [int(binning.get(d, 1)) for d in sdims]
-    dev_ok = all((sims[v].data.device & 0xff) == (device & 0xff) and sims[v].data.strides[-1] == 1 for v in used)
-    if not dev_ok:
+    plans = _plan_pairs(b.geoms_b, b.pairs, b.tol)
+    if plans is None:
         return None
-    # ---- geometry: the views as they are and as the registration binning leaves them (coordinates only: means of groups of b
-    # samples, the sum divided by b as numpy's mean does it -- _bin_sim's coordinates -- without touching a voxel) ----
-    geoms, geoms_b = {}, {}
-    for v in used:
-        geoms[v] = _TileGeom(sims[v], transform_key)
-        if geoms[v].t is None:
-            return None
-    if do_bin:
-        same_len = all(geoms[v].shape == geoms[used[0]].shape for v in used)
-        if same_len:
-            stacked = []
-            for k, b in enumerate(bins):
-                m = geoms[used[0]].shape[k] // b
-                st = np.stack([geoms[v].coords[k][: m * b] for v in used])
-                stacked.append(np.ascontiguousarray(np.add.reduce(st.reshape(len(used), m, b), axis=2) / b))
-            for i, v in enumerate(used):
-                geoms_b[v] = _TileGeom(sims[v], transform_key, like=geoms[v], coords=[stacked[k][i] for k in range(n)])
-        else:
-            for v in used:
-                cs = []
-                for k, b in enumerate(bins):
-                    m = geoms[v].shape[k] // b
-                    cs.append(np.ascontiguousarray(np.add.reduce(geoms[v].coords[k][: m * b].reshape(m, b), axis=1) / b))
-                geoms_b[v] = _TileGeom(sims[v], transform_key, like=geoms[v], coords=cs)
-        if any(min(g.shape) < 1 for g in geoms_b.values()):
-            return None
-    else:
-        geoms_b = geoms
-    slot = {v: i for i, v in enumerate(used)}
-    nv, ne = len(used), len(edges)
-    # ---- plans of all pairs (mvs_plan_pairs: the arithmetic of _lean_pair_plan) ----
-    cptr = (C.c_void_p * (nv * n))(*[geoms_b[v].coords[k].__array_interface__["data"][0] for v in used for k in range(n)])
-    clen = np.array([len(geoms_b[v].coords[k]) for v in used for k in range(n)], dtype=np.int64)
-    tr = np.array([geoms_b[v].t for v in used], dtype=np.float64).reshape(nv, n)
-    tolv = np.array(tol, dtype=np.float64)
-    pr = np.array([[slot[a], slot[b]] for a, b in edges], dtype=np.int32).reshape(ne, 2)
-    windows = np.zeros((ne, 2, 3, 2), dtype=np.int64)
-    out_origin, out_spacing = np.zeros((ne, 3)), np.zeros((ne, 3))
-    out_shape = np.ones((ne, 3), dtype=np.int64)
-    mdiag, offs = np.zeros((ne, 2, 3)), np.zeros((ne, 2, 3))
-    pstat = np.zeros(ne, dtype=np.int32)
-    ptr = lambda a, ty: a.ctypes.data_as(C.POINTER(ty))
-    lib = _lib.init(device & 0xff)
-    rc = lib.mvs_plan_pairs(n, nv, cptr, ptr(clen, C.c_int64), ptr(tr, C.c_double), ptr(tolv, C.c_double), ne, ptr(pr, C.c_int32),
-                            ptr(windows, C.c_int64), ptr(out_origin, C.c_double), ptr(out_spacing, C.c_double), ptr(out_shape, C.c_int64),
-                            ptr(mdiag, C.c_double), ptr(offs, C.c_double), ptr(pstat, C.c_int32))
-    if rc != 0:
-        return None
-    if np.any(pstat != 0):
+    if np.any(plans.status != 0):
         raise ValueError("views do not overlap")
-    knife_thread = None
-    if knife_check and _KNIFE_CHECK[0]:
-        # pairs whose reference crop is one sample shorter (see _reference_crop_differs) take the overlap_bbox="reference" path one by
-        # one; the others stay here.  One memo entry per MOSAIC geometry: a list of pair indices, looked up with a few hundred bytes.
-        mkey = ("mosaic", n, tr.tobytes(), clen.tobytes(), pr.tobytes(), tolv.tobytes(),
-                np.array([[geoms_b[v].coords[k][0], geoms_b[v].spacing[k]] for v in used for k in range(n)]).tobytes())
-        with _KNIFE_LOCK:
-            odd = _KNIFE_MEMO.get(mkey)
-        if odd is None:
-            # a geometry seen for the first time: the question costs ~2 ms of scipy per pair on the host (GIL-bound), the pairs
-            # themselves ~0.3 ms each on the GPU -- so it is asked on a thread of its own WHILE all pairs are registered with the
-            # closed-form crops below (mvs_register_pairs releases the interpreter lock), and the pairs it names, if any, are
-            # registered again through the reference's sequence afterwards: the result is the reference's crop for every pair either way.
-            knife_box = {}
-
-            def ask(box=knife_box, shapes=out_shape[:, :n].copy()):
-                try:
-                    box["odd"] = [e for e in range(ne) if _reference_crop_differs(geoms_b[edges[e][0]], geoms_b[edges[e][1]], tol, shapes[e])]
-                except BaseException as exc:      # noqa: BLE001 - handed to the caller's thread below
-                    box["error"] = exc
-
-            knife_thread = threading.Thread(target=ask, name="mvs-crop-length", daemon=True)
-            knife_thread.start()
-        elif odd:
-            cache.reference_pairs = len(odd)
-            odd_set = set(odd)
-            keep = [e for e in range(ne) if e not in odd_set]
-            res = [None] * ne
-            if keep:
-                part = _register_pairs_batched(sims, [edges[e] for e in keep], transform_key, registration_binning, overlap_tolerance,
-                                               pairwise_reg_func_kwargs, device, n_lanes, cache, knife_check=False)
-                if part is None:
-                    return None
-                for e, r in zip(keep, part):
-                    res[e] = r
-            for e in odd:
-                i, j = edges[e]
-                res[e] = register_pair_of_msims(sims[i], sims[j], transform_key, registration_binning=registration_binning,
-                                                overlap_tolerance=overlap_tolerance, pairwise_reg_func_kwargs=pairwise_reg_func_kwargs,
-                                                device=device, _bin_cache=cache, overlap_bbox="reference")
-            return res
-
-    def knife_fixup(res):
-        """(first call of a geometry) wait for the crop-length answers, remember them, redo the pairs they name the reference's way."""
-        if knife_thread is None:
-            return res
-        knife_thread.join()
-        if "error" in knife_box:
-            raise knife_box["error"]
-        odd_ = knife_box["odd"]
-        with _KNIFE_LOCK:
-            _KNIFE_MEMO[mkey] = odd_
-        if res is None:
+    knife = _knife_question(b.geoms_b, b.pairs, b.tol, plans.out_shape[:, :b.n]) if knife_check and _KNIFE_CHECK[0] else None
+    if knife is not None and knife.odd:
+        # a geometry seen before, with pairs on the knife edge: the others as a batch of their own, those the reference's way
+        keep = sorted(set(range(len(edges))) - set(knife.odd))
+        part = _register_pairs_batched(sims, [edges[e] for e in keep], *again, knife_check=False) if keep else []
+        if part is None:
             return None
-        if odd_:
-            cache.reference_pairs = len(odd_)
-            if raw_before is not None and cache.raw_crops > raw_before:
-                cache.raw_crops = max(raw_before, cache.raw_crops - len(odd_))      # (their closed-form results are discarded)
-            for e in odd_:
-                i, j = edges[e]
-                res[e] = register_pair_of_msims(sims[i], sims[j], transform_key, registration_binning=registration_binning,
-                                                overlap_tolerance=overlap_tolerance, pairwise_reg_func_kwargs=pairwise_reg_func_kwargs,
-                                                device=device, _bin_cache=cache, overlap_bbox="reference")
-        return res
-
-    def _register_planned_pairs():
-        """Jobs of all planned pairs -> mvs_register_pairs -> result dicts (None: not covered, the caller takes the per-pair path)."""
-        # ---- where the crops come from.  Binned integer tiles whose crops are whole-pixel translations (every regular mosaic): straight
-        # from the RAW tiles, the binning applied inside the crop kernel (job.bin) -- no binned copy of a tile is ever made, a pair reads
-        # only the slabs its overlap needs.  Otherwise from binned tiles (pre-binned in groups with stream tickets, see _prebin_views). ----
-        raw_crops = (do_bin and _raw_crops_enabled[0] and first.data.dtype in (np.dtype(np.uint8), np.dtype(np.uint16))
-                     and bool(np.all(mdiag[:, :, :n] == 1.0)) and bool(np.all(offs[:, :, :n] == np.floor(offs[:, :, :n]))))
-        tickets = {v: 0 for v in used}
-        prebin_lane = None
-        if raw_crops or not do_bin:
-            source = {v: sims[v].data for v in used}
-            # tiles still on their way to the device (device.to_device_async): a pair's lane waits for the uploads of ITS two tiles
-            tickets = {v: source[v].ready_ticket for v in used}
-        else:
-            if all(cache.ticket_of((id(sims[v].data), bkey)) is None and (id(sims[v].data), bkey) not in cache._items for v in used):
-                # (queues the binning of all views on the last context lane; None: not a regular mosaic, the views are binned one by one below)
-                prebin_lane = _prebin_views([sims[v] for v in used], binning, device, cache)
-            source = {}
-            for v in used:
-                s_ = sims[v]
-                key = (id(s_.data), bkey)
-                b_ = cache.get_or_compute(key, lambda s_=s_: _bin_sim(s_, binning, device), keep=s_.data)
-                tickets[v] = cache.ticket_of(key) or 0
-                if (b_.data.device & 0xff) != (device & 0xff) or b_.data.strides[-1] != 1 or [len(b_.coords[d]) for d in sdims] != geoms_b[v].shape:
-                    return None
-                source[v] = b_.data
-        cache.raw_crops = ne if raw_crops else 0
-        # ---- jobs: the two crop windows of every pair as mvs_view_t (strided windows into the tiles) ----
-        jobs = (_lib.mvs_pair_job_t * ne)()
-        ja = np.frombuffer(jobs, dtype=_JOB_DTYPE)
-        k0 = 3 - n
-        base = np.array([source[v].ptr for v in used], dtype=np.uint64)
-        strides = np.array([[int(x) for x in source[v].strides] for v in used], dtype=np.int64).reshape(nv, n)
-        item = first.data.dtype.itemsize
-        code = _lib.DTYPE_CODES[first.data.dtype]
-        tk = np.array([tickets[v] for v in used], dtype=np.uint64)
-        scale = np.array(bins if raw_crops else [1] * n, dtype=np.int64)      # binned index -> index of the source array
-        for i, name in enumerate(("fixed", "moving")):
-            f = ja[name]
-            vi = pr[:, i]
-            a, b = windows[:, i, :n, 0] * scale, windows[:, i, :n, 1] * scale
-            st = strides[vi]
-            f["data"] = base[vi] + (np.sum(a * st, axis=1) * item).astype(np.uint64)
-            f["dtype"] = code
-            f["mem"] = _lib.MVS_MEM_DEVICE
-            f["shape"][:, :k0] = 1
-            f["shape"][:, k0:] = b - a
-            if n == 3:
-                f["stride"][:] = st
-            else:       # a 2D slab is one z plane
-                f["stride"][:, 0] = st[:, 0] * (b - a)[:, 0]
-                f["stride"][:, 1:] = st
-            f["matrix"][:] = 0.0
-            f["matrix"][:, [0, 4, 8]] = 1.0
-            f["matrix"][:, [(k0 + k) * 4 for k in range(n)]] = mdiag[:, i, :n]
-            f["offset"][:] = 0.0
-            f["offset"][:, k0:] = offs[:, i, :n]
-            ja["wait_ticket"][:, i] = tk[vi]
-        ja["out_shape"][:, :k0] = 1
-        ja["out_shape"][:, k0:] = out_shape[:, :n]
-        if raw_crops:
-            ja["bin"][:, :k0] = 1
-            ja["bin"][:, k0:] = scale
-        if _pair_timeline is not None:
-            ja["flags"][:] = 1       # every pair leaves a timed ticket of its last kernel (read below)
-        upsample_factor = (pairwise_reg_func_kwargs or {}).get("upsample_factor")
-        uf = (10 if n == 2 else 2) if upsample_factor is None else upsample_factor
-        t3, q = np.zeros((ne, 3)), np.zeros(ne)
-        status, ncand, rcs = np.zeros(ne, dtype=np.int32), np.zeros(ne, dtype=np.int32), np.zeros(ne, dtype=np.int32)
-        try:
-            rc = lib.mvs_register_pairs(device & 0xff, ne, jobs, n, int(uf), -1, 1, int(n_lanes), ptr(t3, C.c_double), ptr(q, C.c_double),
-                                        ptr(status, C.c_int32), ptr(ncand, C.c_int32), ptr(rcs, C.c_int32))
-        finally:
-            if prebin_lane is not None:
-                _lib.synchronize(prebin_lane)      # (done long ago unless a pair failed: nothing stays queued on the caller's tiles)
-        _lib.check(rc, device & 0xff, "mvs_register_pairs")
-        if _pair_timeline is not None:
-            _pair_timeline.extend((tuple(edges[e]), int(ja["wait_ticket"][e, 0])) for e in range(ne))
-        # ---- overlap boxes in world coordinates (_lean_overlap on the UNBINNED views) and the physical affines ----
-        o = np.array([geoms[v].origin for v in used], dtype=np.float64).reshape(nv, n)
-        sp = np.array([geoms[v].spacing for v in used], dtype=np.float64).reshape(nv, n)
-        shp = np.array([geoms[v].shape for v in used], dtype=np.int64).reshape(nv, n)
-        tw = np.array([geoms[v].t for v in used], dtype=np.float64).reshape(nv, n)
-        shp = shp + np.ceil(2 * tolv / sp).astype(np.int64)
-        o = o - tolv
-        lo_v = o + tw
-        hi_v = ((shp - 1) * 1.0 * sp + o) + tw
-        lo = np.maximum(lo_v[pr[:, 0]], lo_v[pr[:, 1]])
-        hi = np.minimum(hi_v[pr[:, 0]], hi_v[pr[:, 1]])
-        up = 1.0 * (hi - lo) + lo
-        fixed_aff = np.array([geoms_b[v].affine for v in used], dtype=np.float64)[pr[:, 0]]
-        return _pair_results_from_plan(t3[:, k0:], q, status, out_origin[:, :n], out_spacing[:, :n], out_shape[:, :n], fixed_aff, lo, up)
-
+        return _redo_reference_pairs(b, _in_edge_order(part, keep, len(edges)), knife.odd, pairwise_reg_func_kwargs, cache)
+    asked = knife is not None and knife.thread is not None
     raw_before = getattr(cache, "raw_crops", None)
     try:
-        res_all = _register_planned_pairs()
+        res = _register_planned_pairs(b, plans, pairwise_reg_func_kwargs, n_lanes, cache)
     except BaseException:
-        if knife_thread is not None:
-            knife_thread.join()
+        if asked:
+            knife.thread.join()
         raise
-    return knife_fixup(res_all)
+    odd = _knife_answer(knife) if asked else []
+    if res is None or not odd:
+        return res
+    return _redo_reference_pairs(b, res, odd, pairwise_reg_func_kwargs, cache, raw_before)
 
 
 def _geom_of(sim, transform_key, cache):
@@ -1092,12 +1203,7 @@ def register_pair_of_msims(msim1, msim2, transform_key, registration_binning=Non
             s_.data.wait_ready(device)       # (tiles uploaded with device.to_device_async: this lane's stream waits for them)
     sdims = si_utils.get_spatial_dims_from_sim(sim1)
     ndim = len(sdims)
-    if overlap_tolerance is None:
-        overlap_tolerance = {d: 0.0 for d in sdims}
-    elif isinstance(overlap_tolerance, (int, float)):
-        overlap_tolerance = {d: float(overlap_tolerance) for d in sdims}
-    else:
-        overlap_tolerance = {d: float(overlap_tolerance.get(d, 0.0)) for d in sdims}
+    overlap_tolerance = _normalise_tolerance(overlap_tolerance, sdims)
 
     def binned(sim):
         if max(registration_binning.values()) <= 1:
@@ -1183,10 +1289,9 @@ def register_pair_of_msims(msim1, msim2, transform_key, registration_binning=Non
 def _prebin_views(sims, registration_binning, device, cache):
     """Queues the binning of all views of a regular mosaic (one shape, one spacing: every pair asks for the same binning)
     on the last context lane and puts the results into ``cache``; returns that lane's device id (to be synchronised before
-    the pairs start) or None when there is nothing to do.  register() calls this before it builds the overlap graph, so
-    the GPU bins the tiles while the interpreter builds and prunes the graph.  (A helper thread doing the same through
-    the blocking call starves on the GIL: measured.)"""
-    import threading
+    the pairs have run) or None when there is nothing to do.  The batched pair path calls this when the crops cannot come from
+    the raw tiles (_crop_sources): the tiles are binned in groups, and a pair starts when the groups of its two tiles are done.
+    (A helper thread doing the same through the blocking call starves on the GIL: measured.)"""
     from . import spatial_image_utils as si_utils
     from .device import is_device_array
 
@@ -1225,12 +1330,8 @@ def _prebin_views(sims, registration_binning, device, cache):
     st3 = st if nd == 3 else [st[0] * shape[0], st[0], st[1]]
     s3, b3, st3 = _lib.i64x3(shape3(shape)), _lib.i64x3([1] * (3 - nd) + bins), _lib.i64x3(st3)
     code = _lib.DTYPE_CODES[dtype]
-    # the coarsened coordinates of _bin_sim (mean of each group of b: the sum divided by b, as numpy's mean does it), all views
-    # of an axis in one reduction (the same additions per element as view by view)
-    all_coords = {}
-    for d, b, n in zip(sdims, bins, oshape):
-        stack = np.stack([np.asarray(s.coords[d])[: n * b] for s in sims])
-        all_coords[d] = np.add.reduce(stack.reshape(len(sims), n, b), axis=2) / b
+    # the coarsened coordinates of _bin_sim, all views of an axis in one reduction
+    all_coords = {d: _binned_coords(np.stack([np.asarray(s.coords[d]) for s in sims]), b) for d, b in zip(sdims, bins)}
     # the tiles are binned in groups (one library call and one ticket each): a pair starts as soon as the groups of its two
     # tiles are done, while the later groups are still being binned (mvs_event_record / mvs_event_wait, no host wait)
     n_v = len(sims)
@@ -1524,12 +1625,9 @@ def register(msims, transform_key=None, reg_channel_index=None, reg_channel=None
         levels_reg = [[channel_of(msi_utils.get_sim_from_msim(m, scale=k)) for k in msi_utils.get_sorted_scale_keys(m)]
                       if msi_utils.is_msim(m) else [channel_of(m)] for m in msims]
 
-    # tiles of a regular mosaic are binned while the graph is built (the GPU would idle otherwise)
     # (binned copies of the tiles are only made when the batched pair path cannot take its crops from the raw tiles: it then
-    # queues the binning of all views itself, in groups with stream tickets -- see _register_pairs_batched / _prebin_views)
-    bin_cache, prebin = None, None
-    if pairwise_executor is None and nt == 1 and not multiscale:
-        bin_cache = _BinCache()
+    # queues the binning of all views itself, in groups with stream tickets -- see _crop_sources / _prebin_views)
+    bin_cache = _BinCache() if pairwise_executor is None and nt == 1 and not multiscale else None
 
     # (1) graph
     sps = [si_utils.get_stack_properties_from_sim(s) for s in sims_reg]
@@ -1538,21 +1636,14 @@ def register(msims, transform_key=None, reg_channel_index=None, reg_channel=None
     tol = overlap_tolerance
     if tol is not None and not isinstance(tol, dict):
         tol = {d: float(tol) for d in sps[0]["spacing"]}
-    try:
-        views = [dict(sp, transform=a) for sp, a in zip(sps, affs)]
-        # axis-aligned views + the default pruning: graph, overlap volumes and pruning in one library call (host code)
-        edges = mv_graph.registration_edges_native(views, tol, pairs, pre_registration_pruning_method, pre_reg_pruning_method_kwargs) \
-            if _native_graph[0] else None
-        if edges is None:
-            g_views = mv_graph.build_view_adjacency_graph(views, overlap_tolerance=tol, pairs=pairs)
-            g_views = mv_graph.prune_view_adjacency_graph(g_views, pre_registration_pruning_method, pre_reg_pruning_method_kwargs)
-            edges = [tuple(sorted(e)) for e in g_views.edges()]
-    except BaseException:
-        if prebin is not None:
-            _lib.synchronize(prebin)     # graph building raised: nothing stays queued on tiles the caller may free
-        raise
-    # (no wait here: every lane that reads a binned tile makes its stream wait for the tile's ticket, see register_pair_of_msims;
-    # the pre-binning lane is the last context lane, a pair worker that reuses it queues behind the binning anyway)
+    views = [dict(sp, transform=a) for sp, a in zip(sps, affs)]
+    # axis-aligned views + the default pruning: graph, overlap volumes and pruning in one library call (host code)
+    edges = mv_graph.registration_edges_native(views, tol, pairs, pre_registration_pruning_method, pre_reg_pruning_method_kwargs) \
+        if _native_graph[0] else None
+    if edges is None:
+        g_views = mv_graph.build_view_adjacency_graph(views, overlap_tolerance=tol, pairs=pairs)
+        g_views = mv_graph.prune_view_adjacency_graph(g_views, pre_registration_pruning_method, pre_reg_pruning_method_kwargs)
+        edges = [tuple(sorted(e)) for e in g_views.edges()]
 
     # (2) pairwise registrations per time point
     params_t, all_results, resolution_info = [], [], []
@@ -1577,19 +1668,13 @@ def register(msims, transform_key=None, reg_channel_index=None, reg_channel=None
                 fields.append(msi_utils.MultiscaleSpatialImage(fl, fl[0].attrs["transforms"]))
         else:
             fields = [field_of(s) for s in sims_reg]
-        try:
-            results = compute_pairwise_registrations(
-                fields, edges, transform_key, registration_binning, overlap_tolerance, pairwise_reg_func,
-                pairwise_reg_func_kwargs, pairwise_executor, device,
-                host_threads=n_parallel_pairwise_regs,
-                _bin_cache=bin_cache, reg_res_level=reg_res_level, overlap_bbox=overlap_bbox,
-                points_key=points_key, prefilter_markers=prefilter_markers,
-            )
-        finally:
-            if prebin is not None:
-                # (done long ago unless a tile took part in no pair or a pair raised: nothing stays queued on the caller's tiles)
-                _lib.synchronize(prebin)
-                prebin = None
+        results = compute_pairwise_registrations(
+            fields, edges, transform_key, registration_binning, overlap_tolerance, pairwise_reg_func,
+            pairwise_reg_func_kwargs, pairwise_executor, device,
+            host_threads=n_parallel_pairwise_regs,
+            _bin_cache=bin_cache, reg_res_level=reg_res_level, overlap_bbox=overlap_bbox,
+            points_key=points_key, prefilter_markers=prefilter_markers,
+        )
         keep = list(range(len(edges)))
         if post_registration_do_quality_filter:
             # mv_graph.filter_edges removes edges with quality < threshold only: a NaN quality (constant overlap ->

@@ -1,14 +1,13 @@
 """CPU tests of the batched pair path (registration._register_pairs_batched): the plans mvs_plan_pairs derives for all pairs of
-a mosaic equal registration._lean_pair_plan pair by pair, bit for bit (windows, output grid, pixel affines: the arguments
-of the crop kernels), and the stacked post-processing (_pair_results_from_plan) returns the very result dicts of
-_lean_register_pair -- for random non-dyadic origins / spacings, binned coordinates, tolerances, 2D and 3D.  The library calls
-that need a GPU are covered by tests/test_register_fuse_gpu.py (batched == per-pair results on the device)."""
-import ctypes as C
-
+a mosaic (registration._plan_pairs) equal registration._lean_pair_plan pair by pair, bit for bit (windows, output grid, pixel
+affines: the arguments of the crop kernels), and the stacked post-processing (_world_boxes, _pair_results_from_plan) returns the
+very result dicts of _lean_register_pair -- for random non-dyadic origins / spacings, binned coordinates, tolerances, 2D and 3D.
+The driver's other steps are tested in tests/test_pair_batch_steps.py; the library calls that need a GPU are covered by
+tests/test_register_fuse_gpu.py (batched == per-pair results on the device)."""
 import numpy as np
 import pytest
 
-from multiview_stitcher_amd import _lib, _reg_ops, registration, transformation
+from multiview_stitcher_amd import _reg_ops, registration, transformation
 from multiview_stitcher_amd import spatial_image_utils as si
 
 
@@ -36,27 +35,6 @@ def _views(rng, ndim, n_views, binned):
     return sims, sdims
 
 
-def _plan_native(geoms, pairs, tol):
-    n = len(geoms[0].sdims)
-    nv, ne = len(geoms), len(pairs)
-    cptr = (C.c_void_p * (nv * n))(*[g.coords[k].ctypes.data for g in geoms for k in range(n)])
-    clen = np.array([len(g.coords[k]) for g in geoms for k in range(n)], dtype=np.int64)
-    tr = np.array([g.t for g in geoms], dtype=np.float64).reshape(nv, n)
-    tolv = np.array(tol, dtype=np.float64)
-    pr = np.array(pairs, dtype=np.int32).reshape(ne, 2)
-    windows = np.zeros((ne, 2, 3, 2), dtype=np.int64)
-    oo, osp = np.zeros((ne, 3)), np.zeros((ne, 3))
-    osh = np.ones((ne, 3), dtype=np.int64)
-    md, of = np.zeros((ne, 2, 3)), np.zeros((ne, 2, 3))
-    st = np.zeros(ne, dtype=np.int32)
-    ptr = lambda a, ty: a.ctypes.data_as(C.POINTER(ty))
-    rc = _lib.load().mvs_plan_pairs(n, nv, cptr, ptr(clen, C.c_int64), ptr(tr, C.c_double), ptr(tolv, C.c_double), ne, ptr(pr, C.c_int32),
-                                    ptr(windows, C.c_int64), ptr(oo, C.c_double), ptr(osp, C.c_double), ptr(osh, C.c_int64), ptr(md, C.c_double),
-                                    ptr(of, C.c_double), ptr(st, C.c_int32))
-    assert rc == 0
-    return windows, oo, osp, osh, md, of, st
-
-
 @pytest.mark.parametrize("ndim", [2, 3])
 @pytest.mark.parametrize("binned", [False, True])
 def test_native_plans_equal_the_python_plans(ndim, binned):
@@ -67,7 +45,7 @@ def test_native_plans_equal_the_python_plans(ndim, binned):
         geoms = [registration._TileGeom(s, "k") for s in sims]
         pairs = [(a, b) for a in range(5) for b in range(5) if a != b]
         tol = [float(v) for v in rng.choice([0.0, 0.0, 1.5], ndim)]
-        windows, oo, osp, osh, md, of, st = _plan_native(geoms, pairs, tol)
+        windows, oo, osp, osh, md, of, st = registration._plan_pairs(geoms, pairs, tol)
         for p, (a, b) in enumerate(pairs):
             want = registration._lean_pair_plan(geoms[a], geoms[b], tol)
             if want is None:
@@ -106,7 +84,7 @@ def test_stacked_post_processing_equals_the_per_pair_results(monkeypatch, ndim):
         pairs = [(a, b) for a in range(4) for b in range(4) if a != b and registration._lean_pair_plan(geoms[a], geoms[b], tol) is not None]
         if not pairs:
             continue
-        windows, oo, osp, osh, md, of, st = _plan_native(geoms, pairs, tol)
+        windows, oo, osp, osh, md, of, st = registration._plan_pairs(geoms, pairs, tol)
         ts = rng.integers(-6, 7, (len(pairs), ndim)) * 0.5
         qs = rng.uniform(0.1, 1.0, len(pairs))
         status = np.where(rng.random(len(pairs)) < 0.2, 2, 0).astype(np.int32)
@@ -115,15 +93,8 @@ def test_stacked_post_processing_equals_the_per_pair_results(monkeypatch, ndim):
             shifts.update(t=ts[p], q=float(qs[p]), status=int(status[p]))
             with pytest.warns(UserWarning) if status[p] == 2 else _nullcontext():
                 want.append(registration._lean_register_pair(geoms[a], geoms[b], geoms[a], geoms[b], sdims, tol, None, "k", 0))
-        o = np.array([g.origin for g in geoms]) - np.array(tol)
-        sp = np.array([g.spacing for g in geoms])
-        shp = np.array([g.shape for g in geoms]) + np.ceil(2 * np.array(tol) / sp).astype(np.int64)
-        tw = np.array([g.t for g in geoms])
-        lo_v, hi_v = o + tw, ((shp - 1) * 1.0 * sp + o) + tw
-        pr = np.array(pairs)
-        lo = np.maximum(lo_v[pr[:, 0]], lo_v[pr[:, 1]])
-        up = 1.0 * (np.minimum(hi_v[pr[:, 0]], hi_v[pr[:, 1]]) - lo) + lo
-        fixed_aff = np.array([g.affine for g in geoms])[pr[:, 0]]
+        lo, up = registration._world_boxes(geoms, pairs, tol)
+        fixed_aff = np.array([g.affine for g in geoms])[np.array(pairs)[:, 0]]
         import warnings
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
