@@ -1,5 +1,5 @@
 // mvs_bin_dev.h -- the one definition of a block mean's arithmetic (bin_mean_kernel, bin_mean_u16x2_kernel,
-// bin_mean_u16x2_batch_kernel in mvs_reg.hip; the three branches of crop_bin_kernel in mvs_fuse.hip), host/device: the kernels and
+// bin_mean_u16x2_batch_kernel in mvs_bin.hip; the three branches of crop_bin_kernel in mvs_fuse.hip), host/device: the kernels and
 // tests/native/bin_mean_host_test.cpp compile the same function.
 //
 //   mean_cast    sum / count in double, cast to T like numpy's astype (truncation for the integer types) ==

@@ -266,11 +266,6 @@ static const MvsCounter kCounters[] = {
     {"fuse_generic_chunks", nullptr, &MvsContext::fuse_generic_chunks},
 };
 
-double mvs_rows_last_plan_ms(MvsContext* c);       // mvs_fuse_rows.hip
-double mvs_regions_last_plan_ms(MvsContext* c);    // mvs_fuse_region.hip
-double mvs_regions_class_stat(MvsContext* c, int what, int cls);   // mvs_fuse_region.hip
-double mvs_regions_launch_stat(MvsContext* c, int what);           // mvs_fuse_region.hip
-
 extern "C" {
 
 const char* mvs_version(void) { return "mvs_hip 0.1 (gfx950)"; }

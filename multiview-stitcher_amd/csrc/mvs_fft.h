@@ -1,6 +1,7 @@
 // mvs_fft.h -- internal: batched complex64 FFT used by the registration kernels.
 #pragma once
 #include "mvs_internal.h"
+#include "mvs_phasecorr_plan.h"
 
 // Optional fusions at the two ends of a 3D transform (taken only when the pass in question runs on the register kernels; *used tells):
 //   re_src / im_src: the first pass reads the real and imaginary parts from two float arrays of the transform's shape instead of
@@ -25,21 +26,21 @@ struct MvsFftFuse {
     bool src_used = false;   // out
 };
 int mvs_fft3_c2c(MvsContext* c, float2* data, const int64_t shape[3], bool inverse, MvsFftFuse* fuse = nullptr);
-// The three-pass form for crops with one short axis (mvs_fft_slab.hip): which axis is the short one (-1: not of that kind), the
-// number of per-workgroup peak entries its last pass writes, and the passes themselves.
-int mvs_phasecorr_slab_axis(const MvsContext* c, const int64_t shape[3]);
-int mvs_phasecorr_slab_peaks(const int64_t shape[3], int short_axis);
+// the test switches of a context that the phase correlation's plan (mvs_phasecorr_plan.h) depends on
+inline mvs_phasecorr_plan::Switches mvs_phasecorr_switches(const MvsContext* c) {
+    mvs_phasecorr_plan::Switches sw;
+    sw.reg_unfused = c->reg_unfused; sw.materialize_shifts = c->materialize_shifts;
+    sw.fft_no_slab = c->fft_no_slab; sw.fft_no_line = c->fft_no_line; sw.fft_no_pair = c->fft_no_pair;
+    sw.fft_slab_axes = c->fft_slab_axes;
+    return sw;
+}
+// The three-pass form for crops with one short axis (mvs_fft_slab.hip; which crops take it and how many per-workgroup peak entries
+// its last pass writes: mvs_phasecorr_plan::slab_axis, slab_peaks).
 int mvs_phasecorr_slab(MvsContext* c, const float* a, const float* b, float2* Z, float2* CC, float2* P2, float2* dc, const int64_t shape[3],
                        int short_axis, int sel_a, int sel_b, float* const peak_val[2], long long* const peak_idx[2], float2* z0_out);
-bool mvs_fft_reg_length(int n);      // does a line of n samples run on the kernels that carry the fusions?
 
-// ---- the cross-power arithmetic of the phase correlation, shared by xpower_packed_kernel (mvs_reg.hip) and the fused first pass ----
-// channel scales of the packed pair of correlations (exact powers of two, see xpower_packed_kernel)
-__device__ __forceinline__ void mvs_xpower_scales(float2 z0, long long n, float* scale_phase, float* scale_plain) {
-    const float dc = fabsf(z0.x * z0.y);           // sum(a) * sum(b): the DC term of the plain cross power
-    *scale_plain = (dc > 0.f && dc < INFINITY) ? ldexpf(1.f, -ilogbf(dc)) : 1.f;
-    *scale_phase = ldexpf(1.f, -ilogbf((float)n));
-}
+// ---- the cross-power arithmetic of the phase correlation, shared by xpower_packed_kernel (mvs_reg.hip) and the fused first pass
+// (the channel scales: mvs_xpower_scales, mvs_phasecorr_plan.h) ----
 // z = Z(k), m = Z(-k): p = A conj(B), p1 = p / max(|p|, 100 eps); returns the input of the inverse transform
 // (sel_b < 0: one correlation, sel_a picks p1 / p; else sa pa + i sb pb with the channel scales)
 __device__ __forceinline__ float2 mvs_xpower_value(float2 z, float2 m, int sel_a, int sel_b, float scale_phase, float scale_plain,

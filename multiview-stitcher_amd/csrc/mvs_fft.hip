@@ -647,102 +647,101 @@ int mvs_fft_twiddles(MvsContext* c, int n, const float2** tw) {
     return MVS_OK;
 }
 
-// In-place 3D (or 2D when shape[0]==1) complex64 FFT of a C-contiguous (nz,ny,nx) array on c->stream.
-// inverse: unnormalised conjugate transform (the caller applies 1/N where it matters).
-// does a line of n samples run on the register kernels (which carry the MvsFftFuse options)?
-bool mvs_fft_reg_length(int n) {
-    if (n < 2) return false;
-    if (mvs_dft_line_length(n)) return true;
-    if ((n & (n - 1)) == 0) return n == 64 || n == 128 || n == 256;
-    int M = 1;
-    while (M < 2 * n - 1) M <<= 1;
-    return M >= 64 && M <= 256;
+namespace {
+
+// a pass on the LDS kernel (pass.kind == kLds)
+int launch_lds_pass(MvsContext* c, const FftArgs& A, bool bluestein) {
+    const size_t lds = (2ull * A.lpb * A.M + A.M / 2 + 1) * sizeof(float2);   // two line buffers + the twiddles
+    const long long nblocks = (A.n_lines + A.lpb - 1) / A.lpb;
+    if (bluestein) {
+        MVS_HIP_TRY(c, hipFuncSetAttribute((const void*)fft_lines_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(fft_lines_kernel<true>, dim3((unsigned)nblocks), dim3(256), lds, c->stream, A);
+    } else {
+        MVS_HIP_TRY(c, hipFuncSetAttribute((const void*)fft_lines_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(fft_lines_kernel<false>, dim3((unsigned)nblocks), dim3(256), lds, c->stream, A);
+    }
+    MVS_HIP_TRY(c, hipGetLastError());
+    return MVS_OK;
 }
 
+// a pass on the register kernels, with the fusions at the two ends of the transform (MvsFftFuse)
+int launch_reg_pass(MvsContext* c, FftArgs A, const mvs_phasecorr_plan::Pass& pass, int axis, int first_axis, int last_axis, const int64_t shape[3], MvsFftFuse* fuse) {
+    namespace pcp = mvs_phasecorr_plan;
+    const int n = A.n;
+    const bool first = axis == first_axis, last = axis == last_axis;
+    unsigned grid = (unsigned)pass.grid;
+    if (fuse && first && fuse->re_src && fuse->im_src) {
+        A.re_src = fuse->re_src;
+        A.im_src = fuse->im_src;
+        fuse->src_used = true;
+    }
+    if (fuse && first && axis == 2 && A.inverse && fuse->xp_src && fuse->xp_p2) {
+        A.xp_src = fuse->xp_src; A.xp_p2 = fuse->xp_p2;
+        A.xp_ny = (int)shape[1]; A.xp_nz = (int)shape[0];
+        A.xp_sel_a = fuse->xp_sel_a; A.xp_sel_b = fuse->xp_sel_b;
+        fuse->xp_used = true;
+        if (pcp::xp_pairs(pass, c->fft_no_pair)) {      // partner lines side by side (fft_reg2_kernel)
+            A.xp_pair = 1;
+            grid = (unsigned)pcp::xp_pair_grid(pass, shape[0], shape[1]);
+        }
+    }
+    if (fuse && last && fuse->peak_val[0] && (long long)grid <= fuse->peak_cap) {
+        for (int k = 0; k < 2; ++k) { A.peak_val[k] = fuse->peak_val[k]; A.peak_idx[k] = fuse->peak_idx[k]; }
+        fuse->n_peak = (int)grid;
+    }
+    if (pass.kind == pcp::kLine) {
+        // short composite lines: the whole line in the registers of one thread (mvs_dft_small.h)
+        if (!(n <= 44 ? mvs_launch_dft_line_lo(c, A, grid) : mvs_launch_dft_line_hi(c, A, grid))) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "FFT: no whole-line kernel for n = %d", n);
+    } else if (pass.kind == pcp::kRegPow2) {
+        // short power-of-two lines: two register transforms around one LDS exchange
+        if (n == 256) hipLaunchKernelGGL((fft_reg2_kernel<16, 16>), dim3(grid), dim3(256), 0, c->stream, A);
+        else if (n == 128) hipLaunchKernelGGL((fft_reg2_kernel<16, 8>), dim3(grid), dim3(256), 0, c->stream, A);
+        else hipLaunchKernelGGL((fft_reg2_kernel<8, 8>), dim3(grid), dim3(256), 0, c->stream, A);
+    } else {
+        // ... and Bluestein lines of up to 128 samples
+        if (pass.M == 256) hipLaunchKernelGGL((bluestein_reg_kernel<16, 16>), dim3(grid), dim3(256), 0, c->stream, A);
+        else if (pass.M == 128) hipLaunchKernelGGL((bluestein_reg_kernel<16, 8>), dim3(grid), dim3(256), 0, c->stream, A);
+        else hipLaunchKernelGGL((bluestein_reg_kernel<8, 8>), dim3(grid), dim3(256), 0, c->stream, A);
+    }
+    MVS_HIP_TRY(c, hipGetLastError());
+    return MVS_OK;
+}
+
+}  // namespace
+
+// In-place 3D (or 2D when shape[0]==1) complex64 FFT of a C-contiguous (nz,ny,nx) array on c->stream.
+// inverse: unnormalised conjugate transform (the caller applies 1/N where it matters).
+// Which kernel family a pass runs on, its lines per workgroup and its grid: mvs_phasecorr_plan::line_pass (the phase correlation
+// plans its fusions with the same rule).
 int mvs_fft3_c2c(MvsContext* c, float2* data, const int64_t shape[3], bool inverse, MvsFftFuse* fuse) {
+    namespace pcp = mvs_phasecorr_plan;
     const long long nz = shape[0], ny = shape[1], nx = shape[2];
-    int first_axis = -1, last_axis = -1;
-    for (int axis = 2; axis >= 0; --axis)
-        if (shape[axis] > 1) { if (first_axis < 0) first_axis = axis; last_axis = axis; }
+    int first_axis, last_axis;
+    pcp::transformed_axes(shape, &first_axis, &last_axis);
     if (fuse) { fuse->n_peak = 0; fuse->src_used = false; fuse->xp_used = false; }
     for (int axis = 2; axis >= 0; --axis) {
         const int n = (int)shape[axis];
         if (n == 1) continue;
-        const bool pow2n = (n & (n - 1)) == 0;
-        if (n > 4096 || (!pow2n && n > 2048)) {      // beyond the LDS core (Bluestein of n > 2048 needs M = 8192 points per line)
-            int rcb;
-            if (axis == 2) rcb = fft_axis_big(c, data, n, nz * ny, 1, 1, nx, inverse);
-            else if (axis == 1) rcb = fft_axis_big(c, data, n, nz * nx, nx, nx, ny * nx, inverse);
-            else rcb = fft_axis_big(c, data, n, ny * nx, ny * nx, ny * nx, 0, inverse);
+        FftArgs A;
+        A.data = data;
+        if (axis == 2) { A.stride = 1; A.n_lines = nz * ny; A.inner = 1; A.outer_stride = nx; }
+        else if (axis == 1) { A.stride = nx; A.n_lines = nz * nx; A.inner = nx; A.outer_stride = ny * nx; }
+        else { A.stride = ny * nx; A.n_lines = ny * nx; A.inner = ny * nx; A.outer_stride = 0; }
+        const pcp::Pass pass = pcp::line_pass(n, A.n_lines, axis == 2, c->fft_no_line);
+        if (pass.kind == pcp::kFourStep) {
+            const int rcb = fft_axis_big(c, data, n, A.n_lines, A.stride, A.inner, A.outer_stride, inverse);
             if (rcb) return rcb;
             continue;
         }
         FftPlan p;
         int rc = get_plan(c, n, &p);
         if (rc) return rc;
-        FftArgs A;
-        A.data = data;
         A.n = n; A.M = p.M; A.log2M = p.log2M;
         A.inverse = inverse ? 1 : 0;
         A.tw = p.tw; A.chirp = p.chirp; A.bfft = p.bfft;
-        if (axis == 2) { A.stride = 1; A.n_lines = nz * ny; A.inner = 1; A.outer_stride = nx; }
-        else if (axis == 1) { A.stride = nx; A.n_lines = nz * nx; A.inner = nx; A.outer_stride = ny * nx; }
-        else { A.stride = ny * nx; A.n_lines = ny * nx; A.inner = ny * nx; A.outer_stride = 0; }
-        // lines per workgroup (measured on 51 x 256 x 256: 8 beats 4 and 16 for both kinds of pass; LDS 33 KB -> 4 workgroups / CU)
-        int lpb = std::max(1, std::min(8, 4096 / p.M));
-        if (axis == 2) lpb = std::max(1, std::min(8, 2048 / p.M));
-        A.lpb = lpb;
-        const size_t lds = (2ull * lpb * p.M + p.M / 2 + 1) * sizeof(float2);   // two line buffers + the twiddles
-        const long long nblocks = (A.n_lines + lpb - 1) / lpb;
-        const bool reg_pow2 = !p.bluestein && (n == 64 || n == 128 || n == 256);
-        const bool reg_blue = p.bluestein && p.M <= 256 && p.M >= 64;
-        const bool reg_line = mvs_dft_line_length(n) && !c->fft_no_line;
-        if (reg_pow2 || reg_blue || reg_line) {
-            const int lpw = reg_line ? 64 : ((reg_pow2 && n == 64) || (reg_blue && p.M == 64)) ? 32 : 16;      // lines per workgroup
-            unsigned grid = (unsigned)((A.n_lines + lpw - 1) / lpw);
-            // the fusions at the two ends of the transform (MvsFftFuse)
-            if (fuse && axis == first_axis && fuse->re_src && fuse->im_src) {
-                A.re_src = fuse->re_src;
-                A.im_src = fuse->im_src;
-                fuse->src_used = true;
-            }
-            if (fuse && axis == first_axis && axis == 2 && inverse && fuse->xp_src && fuse->xp_p2) {
-                A.xp_src = fuse->xp_src; A.xp_p2 = fuse->xp_p2;
-                A.xp_ny = (int)ny; A.xp_nz = (int)nz;
-                A.xp_sel_a = fuse->xp_sel_a; A.xp_sel_b = fuse->xp_sel_b;
-                fuse->xp_used = true;
-                if (reg_pow2 && lpw % 2 == 0 && !c->fft_no_pair) {      // partner lines side by side (fft_reg2_kernel)
-                    const long long h = ny / 2 + 1, ncanon = h + ((nz - 1) / 2) * ny + ((nz % 2 == 0) ? h : 0);
-                    A.xp_pair = 1;
-                    grid = (unsigned)((ncanon + lpw / 2 - 1) / (lpw / 2));
-                }
-            }
-            if (fuse && axis == last_axis && fuse->peak_val[0] && (long long)grid <= fuse->peak_cap) {
-                for (int k = 0; k < 2; ++k) { A.peak_val[k] = fuse->peak_val[k]; A.peak_idx[k] = fuse->peak_idx[k]; }
-                fuse->n_peak = (int)grid;
-            }
-            if (reg_line) {
-                // short composite lines: the whole line in the registers of one thread (mvs_dft_small.h)
-                if (!(n <= 44 ? mvs_launch_dft_line_lo(c, A, grid) : mvs_launch_dft_line_hi(c, A, grid))) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "FFT: no whole-line kernel for n = %d", n);
-            } else if (reg_pow2) {
-                // short power-of-two lines: two register transforms around one LDS exchange
-                if (n == 256) hipLaunchKernelGGL((fft_reg2_kernel<16, 16>), dim3(grid), dim3(256), 0, c->stream, A);
-                else if (n == 128) hipLaunchKernelGGL((fft_reg2_kernel<16, 8>), dim3(grid), dim3(256), 0, c->stream, A);
-                else hipLaunchKernelGGL((fft_reg2_kernel<8, 8>), dim3(grid), dim3(256), 0, c->stream, A);
-            } else {
-                // ... and Bluestein lines of up to 128 samples
-                if (p.M == 256) hipLaunchKernelGGL((bluestein_reg_kernel<16, 16>), dim3(grid), dim3(256), 0, c->stream, A);
-                else if (p.M == 128) hipLaunchKernelGGL((bluestein_reg_kernel<16, 8>), dim3(grid), dim3(256), 0, c->stream, A);
-                else hipLaunchKernelGGL((bluestein_reg_kernel<8, 8>), dim3(grid), dim3(256), 0, c->stream, A);
-            }
-        } else if (p.bluestein) {
-            MVS_HIP_TRY(c, hipFuncSetAttribute((const void*)fft_lines_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(fft_lines_kernel<true>, dim3((unsigned)nblocks), dim3(256), lds, c->stream, A);
-        } else {
-            MVS_HIP_TRY(c, hipFuncSetAttribute((const void*)fft_lines_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(fft_lines_kernel<false>, dim3((unsigned)nblocks), dim3(256), lds, c->stream, A);
-        }
-        MVS_HIP_TRY(c, hipGetLastError());
+        A.lpb = pcp::lds_lines_per_wg(p.M, axis == 2);
+        rc = pass.fused() ? launch_reg_pass(c, A, pass, axis, first_axis, last_axis, shape, fuse) : launch_lds_pass(c, A, p.bluestein);
+        if (rc) return rc;
     }
     return MVS_OK;
 }

@@ -109,13 +109,7 @@ struct LongArgs {
 };
 int mvs_fft_twiddles(MvsContext* c, int n, const float2** tw);
 
-// lengths the whole-line kernel is built for: non-powers of two from 17 to 64 whose prime factors are <= 19 (mvs_dft_small.h)
-constexpr bool mvs_dft_line_length(int n) {
-    if (n < 17 || n > 64 || (n & (n - 1)) == 0) return false;
-    for (int p = 2; p <= 19; ++p)
-        while (n % p == 0) n /= p;
-    return n == 1;
-}
+// (the lengths the whole-line kernel is built for: mvs_dft_line_length, mvs_phasecorr_plan.h)
 // launches dft_line_kernel<A.n> on c->stream (grid workgroups of 64 lines); false: no kernel for this length
 bool mvs_launch_dft_line_lo(MvsContext* c, const FftArgs& A, unsigned grid);     // 17 <= n <= 44
 bool mvs_launch_dft_line_hi(MvsContext* c, const FftArgs& A, unsigned grid);     // 45 <= n <= 64

@@ -125,24 +125,7 @@ __global__ __launch_bounds__(256) void long_xp_kernel(LongArgs A) {
     }
 }
 
-bool slab_long_length(int64_t n) { return n == 64 || n == 128 || n == 256; }
-
 }  // namespace
-
-// which axis is the short one (-1: the crop is not of the slab kind)
-int mvs_phasecorr_slab_axis(const MvsContext* c, const int64_t shape[3]) {
-    if (c->fft_no_slab || c->fft_no_line || c->reg_unfused) return -1;
-    int as = -1;
-    for (int k = 0; k < 3; ++k) {
-        if (slab_long_length(shape[k])) continue;
-        if (shape[k] > 64 || !mvs_dft_line_length((int)shape[k]) || as >= 0) return -1;
-        as = k;
-    }
-    if (as >= 0 && !((c->fft_slab_axes >> as) & 1)) return -1;
-    return as;
-}
-// workgroups of the last pass (= entries of the peak arrays the caller must provide)
-int mvs_phasecorr_slab_peaks(const int64_t shape[3], int short_axis) { return (int)(short_axis == 0 ? shape[1] : shape[0]); }
 
 // a, b: the two real crops; Z, CC, P2: complex work volumes of the crop's shape; dc: >= 256 complex values of scratch.
 // On return: P2 = plain cross power (natural layout), peak_val / peak_idx [2][n_peak] the per-workgroup peaks of the two packed

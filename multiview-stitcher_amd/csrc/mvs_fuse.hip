@@ -1315,17 +1315,6 @@ bool mvs_prepare_tr_view(DevView* d, int order, const int64_t chunk_shape[3], si
     return true;
 }
 
-int mvs_fuse_regions(MvsContext* c, const TrView* htr, const TrView* dtr, int n_views, int dtype, void* dout, const int64_t os[3],
-                     const int64_t trim[3], bool* done);   // mvs_fuse_region.hip
-
-int mvs_fuse_rows(MvsContext* c, const TrView* htr, const TrView* dtr, int n_views, int dtype, void* dout, const int64_t os[3],
-                  const int64_t trim[3], bool* done);      // mvs_fuse_rows.hip
-void mvs_rows_clear_plan_ms(MvsContext* c);                // mvs_fuse_rows.hip
-void mvs_regions_clear_plan_ms(MvsContext* c);             // mvs_fuse_region.hip
-
-int mvs_fuse_content_based(MvsContext* c, const mvs_view_t* views, int32_t n_views,
-                           const mvs_fuse_opts_t* opts, void* out);   // mvs_gauss.hip
-
 // What every chunk entry requires of its arguments; `what` is the entry's name, the prefix of the messages.
 int mvs_check_chunk_args(MvsContext* c, const char* what, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, const void* out) {
     if (!views || n_views < 1 || !opts || !out) return mvs_fail(c, MVS_ERR_INVALID_ARG, "%s: NULL/empty argument", what);

@@ -61,5 +61,10 @@ void mvs_launch_boxes_batch(MvsContext* c, const DevView* hviews, const DevView*
                             const TrView* tr = nullptr);
 bool mvs_prepare_tr_view(DevView* d, int order, const int64_t chunk_shape[3], size_t elem_size, const int64_t org[3], const int64_t ioff[3],
                          TrView* out);
+// the translation-path kernel families of a chunk (mvs_fuse_region.hip, mvs_fuse_rows.hip); *done: the family took the chunk
+int mvs_fuse_regions(MvsContext* c, const TrView* htr, const TrView* dtr, int n_views, int dtype, void* dout, const int64_t os[3],
+                     const int64_t trim[3], bool* done);
+int mvs_fuse_rows(MvsContext* c, const TrView* htr, const TrView* dtr, int n_views, int dtype, void* dout, const int64_t os[3],
+                  const int64_t trim[3], bool* done);
 void mvs_view_chunk_box(const DevView& d, const int64_t shape[3], int lo[3], int hi[3]);
 void mvs_view_to_chunk_frame(DevView* d, const int64_t org[3], const int64_t ioff[3]);

@@ -123,9 +123,6 @@ struct MvsScoreOpts {
     const float* raw_u16_keys[2] = {nullptr, nullptr};   // integer-valued originals of the two crops (16-bit rank keys), or NULL
     float raw_range[4] = {0.f, 0.f, 0.f, 0.f};           // with raw_u16_keys: min, max of the fixed crop, min, max of the moving crop
 };
-// min / max / #valid partials the integer crop kernel leaves while it writes a crop (mvs_register_views -> mvs_resample_impl ->
-// mvs_rescale_pair_device): per-block partials in the layout of nanminmax_pair_kernel, `nb` blocks per image, image k at
-// base + k * nb * 16; done[k] is set by the launch that actually wrote them; gen = the mailbox generation they were parked in
 // Profiling builds only (-DMVS_PROFILING_ABLATIONS): a kernel whose tag is listed in the environment variable MVS_DUP_KERNELS is
 // launched twice (idempotent launches only: the second one rewrites the same results).  The difference in the pair loop's wall time
 // is that kernel's marginal cost among the concurrent context lanes -- which its duration alone in a trace does not tell.
@@ -135,6 +132,9 @@ bool mvs_dup_kernel(const char* tag);
 #else
 #define MVS_DUP(tag, ...) do { __VA_ARGS__; } while (0)
 #endif
+// min / max / #valid partials the integer crop kernel leaves while it writes a crop (mvs_register_views -> mvs_resample_impl ->
+// mvs_rescale_pair_device): per-block partials in the layout of nanminmax_pair_kernel, `nb` blocks per image, image k at
+// base + k * nb * 16; done[k] is set by the launch that actually wrote them; gen = the mailbox generation they were parked in
 struct MvsCropStats {
     char* base = nullptr;
     int nb = 0;
@@ -173,7 +173,23 @@ int mvs_ensure_aux_streams(MvsContext* c);
 int mvs_upload_from_mapped(MvsContext* c, void* dst_dev, const void* src_mapped_dev, size_t nbytes);
 // mvs_reg.hip: n floats of host or device memory as a device pointer (host data is copied into scratch slot `slot`)
 int mvs_stage_float_volume(MvsContext* c, const float* src, int32_t mem, long long n, int slot, float** dptr);
+// mvs_reg.hip: nanmin / nanmax / number of valid voxels of n device floats (one host round trip) ...
+int mvs_device_nanminmax(MvsContext* c, const float* d_in, long long n, float* mn, float* mx, long long* nvalid);
+// ... and the intensity normalisation of both crops of a pair with one round trip (parked: partials the crop kernels have left already)
+int mvs_rescale_pair_device(MvsContext* c, const float* in0, const float* in1, long long n, float* out0, float* out1,
+                            float mn[2], float mx[2], long long nvalid[2], long long n_not_u16[2], const MvsCropStats* parked);
 int mvs_upload_small(MvsContext* c, void* dst_dev, const void* src_pinned, size_t nbytes);   // parameter blocks out of a pinned staging slot: by a kernel, not a copy engine
+
+// mvs_fuse_rows.hip / mvs_fuse_region.hip: forget the plan time of the context's last chunk (mvs_fuse.hip clears both before it plans one)
+void mvs_rows_clear_plan_ms(MvsContext* c);
+void mvs_regions_clear_plan_ms(MvsContext* c);
+// ... and what the counters report of them (mvs_context.hip)
+double mvs_rows_last_plan_ms(MvsContext* c);
+double mvs_regions_last_plan_ms(MvsContext* c);
+double mvs_regions_class_stat(MvsContext* c, int what, int cls);
+double mvs_regions_launch_stat(MvsContext* c, int what);
+// mvs_gauss.hip: a chunk fused with content-based weights
+int mvs_fuse_content_based(MvsContext* c, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out);
 
 // the code of the failure mvs_scratch / mvs_pinned recorded when they returned NULL (MVS_ERR_OUT_OF_MEMORY or MVS_ERR_HIP)
 static inline int mvs_alloc_failed(const MvsContext* c) { return c->last_code ? c->last_code : MVS_ERR_HIP; }

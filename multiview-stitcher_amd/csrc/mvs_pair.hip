@@ -11,9 +11,6 @@
 // that mirror for the debug outputs and for custom keyword arguments.
 #include "mvs_internal.h"
 
-int mvs_rescale_pair_device(MvsContext* c, const float* in0, const float* in1, long long n, float* out0, float* out1,
-                            float mn[2], float mx[2], long long nvalid[2], long long n_not_u16[2], const MvsCropStats* parked);   // mvs_reg.hip
-
 #include <algorithm>
 #include <cmath>
 #include <vector>

@@ -10,7 +10,6 @@
 // mvs_rescale_intensity == skimage.exposure.rescale_intensity(im, in_range=(nanmin, nanmax),
 // out_range=(0,1)) (registration.py:381-389).
 #include "mvs_fft.h"
-#include "mvs_bin_dev.h"
 
 #include <rocprim/warp/warp_reduce.hpp>
 
@@ -226,7 +225,7 @@ __global__ __launch_bounds__(256) void updft_x2_kernel(const float2* __restrict_
 // 256 x 256 x 51 crop, 39 us this way).  Stage 3 (updft_mid_kernel over z) folds the chunks
 // (kdiv: the chunks of a plane share its kernel sample).  The sums run in a different order than in the separate stages (y before x): equal to them to
 // float32 rounding, the refined shifts -- multiples of 1 / upsample -- agree (tests/test_reg_gpu.py).
-constexpr int kYxChunksMax = 64, kYxRows = 64;      // rows of a chunk, 16 per wavefront (measured 8 ... 128 rows: 60.6, 42.7, 33.9, 33.0, 38.2 us for stages 1-3)
+// (rows of a chunk: kYxRows, at most kYxChunksMax chunks -- mvs_phasecorr_plan.h)
 struct UpdftYX { const float2* Kx[2]; const float2* Ky[2]; float2* out[2]; int phase[2]; };
 template <int U>
 __global__ __launch_bounds__(256) void updft_yx2_kernel(const float2* __restrict__ P2, UpdftYX q, int nz, int ny, int nx, int rows_per_chunk, int nchunks) {
@@ -425,17 +424,29 @@ __global__ void rescale_pair_kernel(PairPtrs P, long long n) {
     }
 }
 
-inline int grid_for(long long n) { return (int)std::min<long long>((n + 255) / 256, 256 * 8); }
+inline int grid_for(long long n) { return mvs_phasecorr_plan::voxel_grid(n); }
 
 // a few bytes of device memory into the host-resident mailbox
 __global__ void peek_kernel(const unsigned int* __restrict__ src, unsigned int* __restrict__ dst, int nwords) {
     for (int i = threadIdx.x; i < nwords; i += blockDim.x) dst[i] = src[i];
 }
 
-// fftfreq(n, d)[x] as numpy defines it
-inline double fftfreq(int n, double d, int x) {
-    const int half = (n - 1) / 2 + 1;
-    return (double)(x < half ? x : x - n) / ((double)n * d);
+// min / max / counts over the per-block partials of nanminmax_kernel and nanminmax_pair_kernel: [float min[nb] | float max[nb] |
+// long long count[nb]]; the upper half of a count holds the valid voxels that are not 16-bit integers
+struct MinMaxCount { float mn, mx; long long nvalid, n_not_u16; };
+MinMaxCount fold_minmax_partials(const char* part, int nb) {
+    const float* hmin = (const float*)part;
+    const float* hmax = hmin + nb;
+    const long long* hval = (const long long*)(part + (size_t)nb * 8);
+    float a = INFINITY, b = -INFINITY;
+    long long v = 0;
+    for (int i = 0; i < nb; ++i) { a = std::min(a, hmin[i]); b = std::max(b, hmax[i]); v += hval[i]; }
+    MinMaxCount r;
+    r.n_not_u16 = v >> 32;
+    r.nvalid = v & 0xffffffffll;
+    if (r.nvalid == 0) { a = NAN; b = NAN; }
+    r.mn = a; r.mx = b;
+    return r;
 }
 
 }  // namespace
@@ -452,15 +463,8 @@ int mvs_device_nanminmax(MvsContext* c, const float* d_in, long long n, float* m
     std::vector<char> h((size_t)nb * 16);
     MVS_HIP_TRY(c, hipMemcpyAsync(h.data(), scratch, h.size(), hipMemcpyDeviceToHost, c->stream));
     MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const float* hmin = (const float*)h.data();
-    const float* hmax = hmin + nb;
-    const long long* hval = (const long long*)(h.data() + (size_t)nb * 8);
-    float a = INFINITY, b = -INFINITY;
-    long long v = 0;
-    for (int i = 0; i < nb; ++i) { a = std::min(a, hmin[i]); b = std::max(b, hmax[i]); v += hval[i]; }
-    v &= 0xffffffffll;      // the upper half counts voxels that are not 16-bit integers (used by mvs_rescale_pair_device only)
-    if (v == 0) { a = NAN; b = NAN; }
-    *mn = a; *mx = b; *nvalid = v;
+    const MinMaxCount r = fold_minmax_partials(h.data(), nb);
+    *mn = r.mn; *mx = r.mx; *nvalid = r.nvalid;
     return MVS_OK;
 }
 
@@ -483,18 +487,10 @@ int mvs_rescale_pair_device(MvsContext* c, const float* in0, const float* in1, l
     MVS_HIP_TRY(c, hipGetLastError());
     MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int k = 0; k < 2; ++k) {
-        const char* part = (const char*)mb_host + (size_t)k * nb * 16;
-        const float* hmin = (const float*)part;
-        const float* hmax = hmin + nb;
-        const long long* hval = (const long long*)(part + (size_t)nb * 8);
-        float a = INFINITY, b = -INFINITY;
-        long long v = 0;
-        for (int i = 0; i < nb; ++i) { a = std::min(a, hmin[i]); b = std::max(b, hmax[i]); v += hval[i]; }
-        n_not_u16[k] = v >> 32;
-        v &= 0xffffffffll;
-        if (v == 0) { a = NAN; b = NAN; }
-        mn[k] = a; mx[k] = b; nvalid[k] = v;
-        PP.lo[k] = a; PP.hi[k] = b; PP.degenerate[k] = a == b ? 1 : 0;
+        const MinMaxCount r = fold_minmax_partials((const char*)mb_host + (size_t)k * nb * 16, nb);
+        n_not_u16[k] = r.n_not_u16;
+        mn[k] = r.mn; mx[k] = r.mx; nvalid[k] = r.nvalid;
+        PP.lo[k] = r.mn; PP.hi[k] = r.mx; PP.degenerate[k] = r.mn == r.mx ? 1 : 0;
     }
     MVS_DUP("rescale", hipLaunchKernelGGL(rescale_pair_kernel, dim3(nb, 2), dim3(256), 0, c->stream, PP, n));
     MVS_HIP_TRY(c, hipGetLastError());
@@ -574,14 +570,43 @@ extern "C" int mvs_phasecorr(int device, const float* fixed, const float* moving
                                peak_index_out, peak_abs_out);
 }
 
-extern "C" int mvs_phasecorr_multi(int device, const float* fixed, const float* moving, int32_t mem, int32_t ndim,
-                                   const int64_t shape[3], const int32_t* normalizations, int32_t n_norm,
-                                   int32_t upsample_factor, double* shifts_out, int64_t* peak_indices_out,
-                                   float* peak_abs_out_all) {
-    MvsContext* c;
-    int rc = mvs_check_ready(device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
+// ---- mvs_phasecorr_multi: the steps, in the order the exported function at the end runs them ----
+// Every decision (route, fusions, peak counts) and every offset (mailbox, refinement scratch) comes from mvs_phasecorr_plan.h.
+namespace {
+namespace pcp = mvs_phasecorr_plan;
+
+struct NormRefine {      // one normalisation: its shift so far and where its refinement works
+    float shift[3] = {0.f, 0.f, 0.f};
+    size_t nout = 0;                // complex values of the result
+    const float2* P = nullptr;      // the cross power it refines
+    float2 *dk = nullptr, *o1 = nullptr, *o2 = nullptr, *o3 = nullptr;      // kernel vectors, outputs of the three stages
+    size_t koff[3] = {0, 0, 0};     // the kernel of axis k starts at dk + koff[k]
+};
+struct Phasecorr {
+    MvsContext* c = nullptr;
+    int ndim = 0, n_norm = 0, upsample = 1;
+    const int64_t* shape = nullptr;
+    const int32_t* norms = nullptr;
+    long long n = 0;
+    int nz = 0, ny = 0, nx = 0;
+    pcp::Plan plan;
+    pcp::Mailbox mb;
+    pcp::Scratch up;
+    float *da = nullptr, *db = nullptr;
+    // complex work volumes: Z (ONE forward transform of a + i b carries both spectra), P1 / P2 (cross power with and without phase
+    // normalisation, kept for the upsampled DFT), CC (inverse transform; both correlations in one transform on the packed routes)
+    float2 *Z = nullptr, *P1 = nullptr, *P2 = nullptr, *CC = nullptr;
+    char *mb_host = nullptr, *mb_dev = nullptr, *up_base = nullptr;
+    float packed_scale[2] = {1.f, 1.f};
+    std::vector<NormRefine> norm;
+    int sel(int ch) const { return norms[ch] ? 1 : 0; }
+    float* peak_val(int ch) const { return (float*)(mb_dev + mb.peak_val(ch)); }
+    long long* peak_idx(int ch) const { return (long long*)(mb_dev + mb.peak_idx(ch)); }
+    float2* z0_dev() const { return (float2*)(mb_dev + mb.z0); }
+};
+
+int validate_and_stage(Phasecorr& s, MvsContext* c, int device, const float* fixed, const float* moving, int32_t mem, int32_t ndim,
+                       const int64_t shape[3], const int32_t* normalizations, int32_t n_norm, int32_t upsample_factor, const double* shifts_out) {
     if (!fixed || !moving || !shape || !shifts_out || !normalizations || n_norm < 1)
         return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_phasecorr: NULL argument");
     if (ndim != 2 && ndim != 3) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_phasecorr: ndim must be 2 or 3");
@@ -590,471 +615,252 @@ extern "C" int mvs_phasecorr_multi(int device, const float* fixed, const float* 
         if (shape[k] < 1) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_phasecorr: bad shape");
     if (ndim == 2 && shape[0] != 1) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_phasecorr: 2D needs shape[0]==1");
     MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
-    const long long n = (long long)shape[0] * shape[1] * shape[2];
-    const int nz = (int)shape[0], ny = (int)shape[1], nx = (int)shape[2];
-
-    float *da, *db;
-    rc = mvs_stage_float_volume(c, fixed, mem, n, 4, &da);
+    s.c = c; s.ndim = ndim; s.n_norm = n_norm; s.upsample = upsample_factor; s.shape = shape; s.norms = normalizations;
+    s.nz = (int)shape[0]; s.ny = (int)shape[1]; s.nx = (int)shape[2];
+    s.n = (long long)shape[0] * shape[1] * shape[2];
+    s.plan = pcp::plan(ndim, shape, normalizations, n_norm, upsample_factor, mvs_phasecorr_switches(c));
+    s.mb = pcp::mailbox(s.plan, ndim, shape, n_norm);
+    s.up = pcp::scratch(s.plan, shape, n_norm);
+    s.norm.resize((size_t)n_norm);
+    int rc = mvs_stage_float_volume(c, fixed, mem, s.n, 4, &s.da);
     if (rc) return rc;
-    rc = mvs_stage_float_volume(c, moving, mem, n, 5, &db);
+    rc = mvs_stage_float_volume(c, moving, mem, s.n, 5, &s.db);
     if (rc) return rc;
-    // complex work volumes: Z (ONE forward transform of a + i b carries both spectra), P1 / P2 (cross power with and
-    // without phase normalisation, kept for the upsampled DFT), CC (inverse transform; both correlations in one transform
-    // when two normalisations are asked for)
-    float2* Z = (float2*)mvs_scratch(c, 6, (size_t)n * 8 * 4);
-    if (!Z) return mvs_alloc_failed(c);
-    float2* P1 = Z + n;
-    float2* P2 = P1 + n;
-    float2* CC = P2 + n;
-
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    const int gb = grid_for(n);
-    // first / last transformed axis (the transform runs x, y, z; axes of length 1 are skipped)
-    int first_axis = -1, last_axis = -1;
-    for (int axis = 2; axis >= 0; --axis)
-        if (shape[axis] > 1) { if (first_axis < 0) first_axis = axis; last_axis = axis; }
-    // crops with one short axis and two power-of-two axes, two normalisations, small refinement: three passes in all
-    // (mvs_fft_slab.hip) -- the forward transform happens there, together with the cross power and the inverse transform
-    const int slab_axis = (ndim == 3 && n_norm == 2 && (normalizations[0] != 0) != (normalizations[1] != 0) && !c->materialize_shifts &&
-                           (int)ceilf((float)upsample_factor * 1.5f) <= 4)
-                              ? mvs_phasecorr_slab_axis(c, shape) : -1;
-    if (slab_axis >= 0) {
-        rc = MVS_OK;
-    } else if (first_axis >= 0 && mvs_fft_reg_length((int)shape[first_axis]) && !c->reg_unfused) {
-        MvsFftFuse ff;      // the first pass reads a and b themselves: no packed copy is written and read back
-        ff.re_src = da;
-        ff.im_src = db;
-        rc = mvs_fft3_c2c(c, Z, shape, false, &ff);
-    } else {
-        hipLaunchKernelGGL(pack_pair_kernel, dim3(gb), dim3(256), 0, c->stream, da, db, Z, n);
-        rc = mvs_fft3_c2c(c, Z, shape, false);
-    }
-    if (rc) return rc;
-  // Two different normalisations: both correlations come out of ONE inverse transform (real and imaginary channel, see
-  // xpower_packed_kernel) and one host round trip; otherwise one complex transform per normalisation.
-  const bool packed = n_norm == 2 && (normalizations[0] != 0) != (normalizations[1] != 0) && !c->materialize_shifts;
-  // mailbox (host memory written by the kernels): [peak partials gb * 32 | z0 | refinement results of every normalisation]
-  const int up_U0 = (int)ceilf((float)upsample_factor * 1.5f);
-  const size_t res_elems = upsample_factor > 1 ? (ndim == 3 ? (size_t)up_U0 * up_U0 * up_U0 : (size_t)up_U0 * up_U0) : 0;
-  // blocks of the peak searches (one host-memory write each): 512 for the stand-alone kernel, or the workgroups of the inverse
-  // transform's last pass when that pass does the search itself (16 or 32 lines each)
-  int ga = std::min(gb, 512);
-  {
-      int la = -1;
-      for (int axis = 2; axis >= 0; --axis) if (shape[axis] > 1) la = axis;
-      if (la >= 0 && mvs_fft_reg_length((int)shape[la])) ga = std::max<long long>(ga, (n / shape[la] + 15) / 16);
-      if (slab_axis >= 0) ga = std::max(ga, mvs_phasecorr_slab_peaks(shape, slab_axis));
-  }
-  const size_t mb_red = (size_t)ga * 32, mb_z0 = mb_red, mb_res = mb_red + 256, mb_res_stride = align_up(res_elems * sizeof(float2));
-  void *mb_host = nullptr, *mb_dev = nullptr;
-  // ... | the kernel vectors of every refinement (pinned: their upload is a plain asynchronous copy, no staging through the runtime)]
-  const size_t mb_k = mb_res + mb_res_stride * (size_t)n_norm;
-  const size_t mb_kbytes = upsample_factor > 1 ? align_up((size_t)up_U0 * (size_t)(nz + ny + nx) * sizeof(float2)) : 0;
-  rc = mvs_mailbox(c, mb_k + mb_kbytes * (size_t)n_norm, &mb_host, &mb_dev);
-  if (rc) return rc;
-  char* red = (char*)mb_dev;
-  const char* hred = (const char*)mb_host;
-  float packed_scale[2] = {1.f, 1.f};
-  int n_red_packed = ga;
-  // ... and when its first pass (along x) runs on them and the refinement is small, the cross power is formed inside that pass
-  // (MvsFftFuse::xp_src) and both refinements' first stage read it in one launch (updft_x2_kernel): the combined spectrum and the
-  // phase-normalised cross power are never stored.
-  const bool fuse_xp = slab_axis >= 0 || (packed && first_axis == 2 && mvs_fft_reg_length((int)nx) && up_U0 <= 4 && !c->reg_unfused);
-  // ... and in 3D (refinement of 3 samples per axis: upsample factor 2) the first TWO stages of both refinements are one pass
-  // over it (updft_yx2_kernel): a lane sums its columns over the rows of a chunk before anything is reduced across lanes
-  const bool fuse_yx = fuse_xp && ndim == 3 && up_U0 == 3 && nx <= 256 && ny >= 4;
-  const int yx_chunks = fuse_yx ? std::max(1, std::min(kYxChunksMax, ((int)ny + kYxRows - 1) / kYxRows)) : 1;
-  if (packed && slab_axis >= 0) {
-    float* pv[2] = {(float*)red, (float*)(red + (size_t)ga * 16)};
-    long long* pi[2] = {(long long*)(red + (size_t)ga * 8), (long long*)(red + (size_t)ga * 24)};
-    rc = mvs_phasecorr_slab(c, da, db, Z, CC, P2, P1 /* scratch: the slabs' DC terms */, shape, slab_axis, normalizations[0] ? 1 : 0,
-                            normalizations[1] ? 1 : 0, pv, pi, (float2*)((char*)mb_dev + mb_z0));
-    if (rc) return rc;
-    n_red_packed = mvs_phasecorr_slab_peaks(shape, slab_axis);
-    c->reg_slab_pairs += 1;
-    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const float2 z0 = *(const float2*)((const char*)mb_host + mb_z0);
-    const float dc = std::fabs(z0.x * z0.y);
-    const float s_plain = (dc > 0.f && dc < INFINITY) ? std::ldexp(1.f, -std::ilogb(dc)) : 1.f;
-    const float s_phase = std::ldexp(1.f, -std::ilogb((float)n));
-    for (int ch = 0; ch < 2; ++ch) packed_scale[ch] = normalizations[ch] ? s_phase : s_plain;
-  } else if (packed) {
-    if (!fuse_xp)
-        hipLaunchKernelGGL(xpower_packed_kernel, dim3(gb), dim3(256), 0, c->stream, Z, P1, P2, CC, nz, ny, nx, normalizations[0] ? 1 : 0,
-                           normalizations[1] ? 1 : 0);
-    // the correlation volume is only ever searched for its two peaks: when the last pass of the inverse transform runs on the
-    // register kernels it reduces its output to per-workgroup maxima instead of storing it (no 27 MB written and read back)
-    MvsFftFuse fp;
-    if (last_axis >= 0 && mvs_fft_reg_length((int)shape[last_axis]) && !c->reg_unfused) {
-        fp.peak_val[0] = (float*)red; fp.peak_idx[0] = (long long*)(red + (size_t)ga * 8);
-        fp.peak_val[1] = (float*)(red + (size_t)ga * 16); fp.peak_idx[1] = (long long*)(red + (size_t)ga * 24);
-        fp.peak_cap = ga;
-    }
-    if (fuse_xp) { fp.xp_src = Z; fp.xp_p2 = P2; fp.xp_sel_a = normalizations[0] ? 1 : 0; fp.xp_sel_b = normalizations[1] ? 1 : 0; }
-    rc = mvs_fft3_c2c(c, CC, shape, true, &fp);
-    if (rc) return rc;
-    if (fuse_xp && !fp.xp_used) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "phase correlation: the fused cross-power pass was not taken");
-    if (fp.n_peak > 0) {
-        n_red_packed = fp.n_peak;
-        hipLaunchKernelGGL(peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned int*)Z, (unsigned int*)((char*)mb_dev + mb_z0), 2);
-    } else {
-        hipLaunchKernelGGL(argmax_abs2_kernel, dim3(ga), dim3(256), 0, c->stream, CC, n, (float*)red, (long long*)(red + (size_t)ga * 8),
-                           (float*)(red + (size_t)ga * 16), (long long*)(red + (size_t)ga * 24), Z, (float2*)((char*)mb_dev + mb_z0));
-    }
-    MVS_HIP_TRY(c, hipGetLastError());
-    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const float2 z0 = *(const float2*)((const char*)mb_host + mb_z0);
-    // the channel scales of xpower_packed_kernel (exact powers of two), to report the peak height unscaled
-    const float dc = std::fabs(z0.x * z0.y);
-    const float s_plain = (dc > 0.f && dc < INFINITY) ? std::ldexp(1.f, -std::ilogb(dc)) : 1.f;
-    const float s_phase = std::ldexp(1.f, -std::ilogb((float)n));
-    for (int ch = 0; ch < 2; ++ch) packed_scale[ch] = normalizations[ch] ? s_phase : s_plain;
-  }
-  // Per normalisation: integer peak -> upsampled DFT around it.  The refinements of all normalisations are queued before
-  // the host waits once for their results (phase 2 below).
-  struct NormState {
-      float shift[3]; size_t nout = 0;
-      const float2* P = nullptr; float2 *dk = nullptr, *o1 = nullptr, *o2 = nullptr, *o3 = nullptr; size_t koff[3] = {0, 0, 0};
-  };
-  std::vector<NormState> state((size_t)n_norm);
-  const int up_U = (int)ceilf((float)upsample_factor * 1.5f);
-  const size_t up_kbytes = align_up((size_t)up_U * (size_t)(nz + ny + nx) * sizeof(float2));
-  const size_t up_s1 = (size_t)nz * ny * up_U, up_s2 = (size_t)nz * up_U * up_U, up_s3 = (size_t)up_U * up_U * up_U;
-  const size_t up_bytes = up_kbytes + (up_s1 + up_s2 + up_s3) * sizeof(float2) + 1024;
-  char* up_base = nullptr;
-  if (upsample_factor > 1) {
-      up_base = (char*)mvs_scratch(c, 7, up_bytes * (size_t)n_norm);
-      if (!up_base) return mvs_alloc_failed(c);
-  }
-  for (int inorm = 0; inorm < n_norm; ++inorm) {
-    const int normalization = normalizations[inorm];
-    int64_t* peak_index_out = peak_indices_out ? peak_indices_out + 3 * inorm : nullptr;
-    float* peak_abs_out = peak_abs_out_all ? peak_abs_out_all + inorm : nullptr;
-    const float2* P = normalization ? P1 : P2;
-    const char* hpart = hred + (packed ? (size_t)inorm * ga * 16 : 0);
-    const int n_part = packed ? n_red_packed : ga;
-    if (!packed) {
-        hipLaunchKernelGGL(xpower_packed_kernel, dim3(gb), dim3(256), 0, c->stream, Z, P1, P2, CC, nz, ny, nx, normalization ? 1 : 0, -1);
-        rc = mvs_fft3_c2c(c, CC, shape, true);   // cc (unnormalised inverse: argmax is scale invariant)
-        if (rc) return rc;
-        hipLaunchKernelGGL(argmax_abs_kernel<0>, dim3(ga), dim3(256), 0, c->stream, CC, n, (float*)red, (long long*)(red + (size_t)ga * 8));
-        MVS_HIP_TRY(c, hipGetLastError());
-        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    float best = -1.f;
-    long long bi = 0;
-    {
-        const float* hv = (const float*)hpart;
-        const long long* hi = (const long long*)(hpart + (size_t)ga * 8);
-        for (int i = 0; i < n_part; ++i)
-            if (hv[i] > best || (hv[i] == best && hi[i] < bi)) { best = hv[i]; bi = hi[i]; }
-    }
-    if (packed) best /= packed_scale[inorm];
-    const long long pz = bi / ((long long)ny * nx), py = (bi / nx) % ny, px = bi % nx;
-    const long long peak[3] = {pz, py, px};
-    if (peak_index_out) { peak_index_out[0] = pz; peak_index_out[1] = py; peak_index_out[2] = px; }
-    if (peak_abs_out) *peak_abs_out = best / (float)n;   // ifftn's 1/N
-
-    // ---- signed shift, float32 arithmetic like skimage ----
-    float (&shift)[3] = state[inorm].shift;
-    for (int k = 0; k < 3; ++k) {
-        shift[k] = (float)peak[k];
-        const float mid = truncf((float)shape[k] / 2.f);   // np.fix(axis_size / 2)
-        if (shift[k] > mid) shift[k] -= (float)shape[k];
-    }
-    if (upsample_factor > 1) {
-        const float uf = (float)upsample_factor;
-        const int U = (int)ceilf(uf * 1.5f);
-        const float dftshift = truncf((float)U / 2.f);
-        float offs[3];
-        for (int k = 0; k < 3; ++k) {
-            shift[k] = nearbyintf(shift[k] * uf) / uf;            // np.round: half to even
-            offs[k] = dftshift - shift[k] * uf;
-        }
-        // kernels exp(-2 pi i (a - off) * fftfreq(n, uf)[x]) computed in double, cast to complex64
-        const int k0 = (ndim == 3) ? 0 : 1;
-        float2* hk = (float2*)((char*)mb_host + mb_k + mb_kbytes * (size_t)inorm);   // stays untouched until the wait below
-        size_t koff[3] = {0, 0, 0}, nk = 0;
-        for (int k = k0; k < 3; ++k) {
-            koff[k] = nk;
-            const int nn = (int)shape[k];
-            for (int a = 0; a < U; ++a)
-                for (int x = 0; x < nn; ++x) {
-                    const double ph = -2.0 * M_PI * ((double)a - (double)offs[k]) * fftfreq(nn, (double)uf, x);
-                    hk[nk++] = make_float2((float)cos(ph), (float)sin(ph));
-                }
-        }
-        const size_t kbytes = nk * sizeof(float2);
-        const long long nrows = (long long)nz * ny;
-        const size_t s1 = (size_t)nrows * U, s2 = (size_t)nz * U * U, s3 = (size_t)U * U * U;
-        // device layout: [kernel vectors of every normalisation | stage outputs of every normalisation]
-        float2* dk = (float2*)(up_base + (size_t)inorm * up_kbytes);
-        float2* o1 = (float2*)(up_base + (size_t)n_norm * up_kbytes + (size_t)inorm * (up_bytes - up_kbytes));
-        float2* o2 = o1 + s1;
-        float2* o3 = o2 + s2;
-        float2* mres = (float2*)((char*)mb_dev + mb_res + mb_res_stride * (size_t)inorm);     // the last stage writes host memory
-        if (ndim == 3) o3 = mres; else o2 = mres;
-        // one upload for all normalisations when their launches follow the last one (same strides in the mailbox and on the device)
-        // (copied by a kernel out of the mapped mailbox: a DMA upload would queue behind any tile upload in flight)
-        const char* hk_dev = (const char*)mb_dev + mb_k + mb_kbytes * (size_t)inorm;
-        int rcu = MVS_OK;
-        if (!fuse_xp) rcu = mvs_upload_from_mapped(c, dk, hk_dev, (kbytes + 15) / 16 * 16);
-        else if (inorm == n_norm - 1)
-            rcu = mvs_upload_from_mapped(c, up_base, (const char*)mb_dev + mb_k, ((size_t)inorm * up_kbytes + kbytes + 15) / 16 * 16);
-        if (rcu) return rcu;
-        NormState& st = state[inorm];
-        st.P = P; st.dk = dk; st.o1 = o1; st.o2 = o2; st.o3 = o3;
-        for (int k = 0; k < 3; ++k) st.koff[k] = koff[k];
-        st.nout = ndim == 3 ? s3 : s2;
-        if (!fuse_xp) {
-            // stage 1: x  -> (z, y, ux)
-            hipLaunchKernelGGL(updft_x_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, c->stream, P, dk + koff[2], o1, nrows, nx, U);
-        } else if (fuse_yx) {
-            if (inorm == n_norm - 1) {
-                // stages 1 and 2 of both normalisations: partial sums per (z, y chunk), folded by stage 3; they live in o1 (chunks * U <= ny)
-                UpdftYX q;
-                for (int j = 0; j < 2; ++j) {
-                    q.Kx[j] = state[j].dk + state[j].koff[2]; q.Ky[j] = state[j].dk + state[j].koff[1]; q.out[j] = state[j].o1;
-                    q.phase[j] = normalizations[j] ? 1 : 0;
-                }
-                const int rows_per_chunk = ((int)ny + yx_chunks - 1) / yx_chunks;
-                MVS_DUP("updft", hipLaunchKernelGGL(updft_yx2_kernel<3>, dim3((unsigned)(nz * yx_chunks)), dim3(256), 0, c->stream, P2, q, (int)nz, (int)ny, (int)nx,
-                                   rows_per_chunk, yx_chunks));
-                for (int j = 0; j < n_norm; ++j)
-                    MVS_DUP("updft_mid", hipLaunchKernelGGL(updft_mid_kernel, dim3((unsigned)std::min<long long>(((long long)s3 + 3) / 4, 4096)), dim3(256), 0, c->stream,
-                                       state[j].o1, state[j].dk + state[j].koff[0], state[j].o3, 1, (int)nz * yx_chunks, U * U, U, yx_chunks));
-            }
-            MVS_HIP_TRY(c, hipGetLastError());
-            continue;
-        } else if (inorm == n_norm - 1) {
-            // stage 1 of both normalisations from the plain cross power alone
-            UpdftX2 q;
-            for (int j = 0; j < 2; ++j) { q.K[j] = state[j].dk + state[j].koff[2]; q.out[j] = state[j].o1; q.phase[j] = normalizations[j] ? 1 : 0; }
-            hipLaunchKernelGGL(updft_x2_kernel<4>, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, c->stream, P2, q, nrows, (int)nx, U);
-        }
-        for (int j = (fuse_xp ? (inorm == n_norm - 1 ? 0 : n_norm) : inorm); j <= inorm && j < n_norm; ++j) {
-            const NormState& sj = state[j];
-            // stage 2: y  -> (z, uy, ux)
-            hipLaunchKernelGGL(updft_mid_kernel, dim3((unsigned)std::min<long long>(((long long)s2 + 3) / 4, 4096)), dim3(256), 0, c->stream, sj.o1, sj.dk + sj.koff[1], sj.o2, nz, ny, U, U);
-            // stage 3: z -> (uz, uy, ux)
-            if (ndim == 3)
-                hipLaunchKernelGGL(updft_mid_kernel, dim3((unsigned)std::min<long long>(((long long)s3 + 3) / 4, 4096)), dim3(256), 0, c->stream, sj.o2, sj.dk + sj.koff[0], sj.o3, 1, nz, U * U, U);
-        }
-        MVS_HIP_TRY(c, hipGetLastError());
-    }
-  }
-  MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-  c->timing_valid = true;
-  if (upsample_factor > 1) MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  // ---- phase 2: sub-pixel maximum of every refinement ----
-  for (int inorm = 0; inorm < n_norm; ++inorm) {
-    float (&shift)[3] = state[inorm].shift;
-    if (upsample_factor > 1) {
-        const float uf = (float)upsample_factor;
-        const int U = up_U;
-        const float dftshift = truncf((float)U / 2.f);
-        const int k0 = (ndim == 3) ? 0 : 1;
-        const float2* hres = (const float2*)((const char*)mb_host + mb_res + mb_res_stride * (size_t)inorm);
-        // argmax |.| (conj does not change the modulus), lowest flat index
-        float bu = -1.f;
-        size_t iu = 0;
-        for (size_t i = 0; i < state[inorm].nout; ++i) {
-            const float a = hypotf(hres[i].x, hres[i].y);
-            if (a > bu) { bu = a; iu = i; }
-        }
-        int m[3] = {0, 0, 0};
-        m[2] = (int)(iu % U);
-        m[1] = (int)((iu / U) % U);
-        if (ndim == 3) m[0] = (int)(iu / ((size_t)U * U));
-        for (int k = k0; k < 3; ++k) shift[k] += ((float)m[k] - dftshift) / uf;
-    }
-    double* shift_out = shifts_out + 3 * inorm;
-    for (int k = 0; k < 3; ++k) {
-        if (shape[k] == 1) shift[k] = 0.f;
-        shift_out[k] = (double)shift[k];
-    }
-  }
+    s.Z = (float2*)mvs_scratch(c, 6, (size_t)s.n * 8 * 4);
+    if (!s.Z) return mvs_alloc_failed(c);
+    s.P1 = s.Z + s.n;
+    s.P2 = s.P1 + s.n;
+    s.CC = s.P2 + s.n;
     return MVS_OK;
 }
 
-// ---- block-mean binning == sim.coarsen(bins, boundary="trim").mean().astype(dtype) (registration.py:1732-1741) ----
-namespace {
-template <typename T>
-__global__ void bin_mean_kernel(const T* __restrict__ in, long long sz, long long sy, T* __restrict__ out, int oz, int oy, int ox,
-                                int bz, int by, int bx) {
-    const long long n = (long long)oz * oy * ox;
-    const double count = (double)bz * by * bx;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const int x = (int)(i % ox);
-        const long long t = i / ox;
-        const int y = (int)(t % oy), z = (int)(t / oy);
-        double acc = 0.0;
-        for (int dz = 0; dz < bz; ++dz)
-            for (int dy = 0; dy < by; ++dy) {
-                const T* row = in + (long long)(z * bz + dz) * sz + (long long)(y * by + dy) * sy + (long long)x * bx;
-                for (int dx = 0; dx < bx; ++dx) acc += (double)row[dx];
-            }
-        out[i] = mvs_bin::mean_cast<T>(acc, count);   // sum / count in double; astype: truncation for integer dtypes
+// Z = fft(a + i b); the slab route transforms inside its own passes
+int forward_transform(Phasecorr& s) {
+    if (s.plan.route == pcp::kSlab) return MVS_OK;
+    if (s.plan.forward_reads_crops) {
+        MvsFftFuse ff;      // the first pass reads a and b themselves: no packed copy is written and read back
+        ff.re_src = s.da;
+        ff.im_src = s.db;
+        return mvs_fft3_c2c(s.c, s.Z, s.shape, false, &ff);
+    }
+    hipLaunchKernelGGL(pack_pair_kernel, dim3(s.plan.gb), dim3(256), 0, s.c->stream, s.da, s.db, s.Z, s.n);
+    return mvs_fft3_c2c(s.c, s.Z, s.shape, false);
+}
+
+int reserve_mailbox(Phasecorr& s) {
+    void *host = nullptr, *dev = nullptr;
+    const int rc = mvs_mailbox(s.c, s.mb.total, &host, &dev);
+    s.mb_host = (char*)host;
+    s.mb_dev = (char*)dev;
+    return rc;
+}
+
+// the packed routes end here: wait for the peaks and the DC term z0, and take the channel scales the device used from z0 (exact
+// powers of two), to report the peak heights unscaled
+int wait_for_packed_peaks(Phasecorr& s) {
+    MVS_HIP_TRY(s.c, hipStreamSynchronize(s.c->stream));
+    float s_phase, s_plain;
+    mvs_xpower_scales(*(const float2*)(s.mb_host + s.mb.z0), s.n, &s_phase, &s_plain);
+    for (int ch = 0; ch < 2; ++ch) s.packed_scale[ch] = s.norms[ch] ? s_phase : s_plain;
+    return MVS_OK;
+}
+
+// route kSlab: forward transform, cross power and inverse transform in three passes; peaks are in the mailbox
+int correlate_slab(Phasecorr& s) {
+    float* pv[2] = {s.peak_val(0), s.peak_val(1)};
+    long long* pi[2] = {s.peak_idx(0), s.peak_idx(1)};
+    const int rc = mvs_phasecorr_slab(s.c, s.da, s.db, s.Z, s.CC, s.P2, s.P1 /* scratch: the slabs' DC terms */, s.shape, s.plan.short_axis, s.sel(0),
+                                      s.sel(1), pv, pi, s.z0_dev());
+    if (rc) return rc;
+    s.c->reg_slab_pairs += 1;
+    return wait_for_packed_peaks(s);
+}
+
+// route kPacked: both correlations out of ONE inverse transform (real and imaginary channel); peaks are in the mailbox
+int correlate_packed(Phasecorr& s) {
+    MvsContext* c = s.c;
+    if (!s.plan.fuse_xp)
+        hipLaunchKernelGGL(xpower_packed_kernel, dim3(s.plan.gb), dim3(256), 0, c->stream, s.Z, s.P1, s.P2, s.CC, s.nz, s.ny, s.nx, s.sel(0), s.sel(1));
+    MvsFftFuse fp;
+    if (s.plan.last_pass_peaks) {      // no correlation volume written and read back
+        for (int ch = 0; ch < 2; ++ch) { fp.peak_val[ch] = s.peak_val(ch); fp.peak_idx[ch] = s.peak_idx(ch); }
+        fp.peak_cap = s.plan.ga;
+    }
+    if (s.plan.fuse_xp) { fp.xp_src = s.Z; fp.xp_p2 = s.P2; fp.xp_sel_a = s.sel(0); fp.xp_sel_b = s.sel(1); }
+    const int rc = mvs_fft3_c2c(c, s.CC, s.shape, true, &fp);
+    if (rc) return rc;
+    if (fp.xp_used != s.plan.fuse_xp || fp.n_peak != (s.plan.last_pass_peaks ? s.plan.n_peak : 0))
+        return mvs_fail(c, MVS_ERR_UNSUPPORTED, "phase correlation: the inverse transform did not take the planned fusions");
+    if (s.plan.last_pass_peaks)
+        hipLaunchKernelGGL(peek_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned int*)s.Z, (unsigned int*)s.z0_dev(), 2);
+    else
+        hipLaunchKernelGGL(argmax_abs2_kernel, dim3(s.plan.ga), dim3(256), 0, c->stream, s.CC, s.n, s.peak_val(0), s.peak_idx(0), s.peak_val(1),
+                           s.peak_idx(1), s.Z, s.z0_dev());
+    MVS_HIP_TRY(c, hipGetLastError());
+    return wait_for_packed_peaks(s);
+}
+
+// route kPerNorm: one cross power, one inverse transform and one round trip for this normalisation; peaks are in the mailbox (channel 0)
+int correlate_one_norm(Phasecorr& s, int inorm) {
+    MvsContext* c = s.c;
+    hipLaunchKernelGGL(xpower_packed_kernel, dim3(s.plan.gb), dim3(256), 0, c->stream, s.Z, s.P1, s.P2, s.CC, s.nz, s.ny, s.nx, s.sel(inorm), -1);
+    const int rc = mvs_fft3_c2c(c, s.CC, s.shape, true);   // cc (unnormalised inverse: argmax is scale invariant)
+    if (rc) return rc;
+    hipLaunchKernelGGL(argmax_abs_kernel<0>, dim3(s.plan.ga), dim3(256), 0, c->stream, s.CC, s.n, s.peak_val(0), s.peak_idx(0));
+    MVS_HIP_TRY(c, hipGetLastError());
+    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return MVS_OK;
+}
+
+// integer peak of one normalisation out of the mailbox -> outputs, signed shift
+void read_peaks(Phasecorr& s, int inorm, int64_t* peak_index_out, float* peak_abs_out) {
+    const bool packed = s.plan.route != pcp::kPerNorm;
+    const int ch = packed ? inorm : 0;
+    float best;
+    long long bi, peak[3];
+    pcp::argmax_partials((const float*)(s.mb_host + s.mb.peak_val(ch)), (const long long*)(s.mb_host + s.mb.peak_idx(ch)), s.plan.n_peak, &best, &bi);
+    if (packed) best /= s.packed_scale[inorm];
+    pcp::unravel(bi, s.shape, peak);
+    if (peak_index_out)
+        for (int k = 0; k < 3; ++k) peak_index_out[k] = peak[k];
+    if (peak_abs_out) *peak_abs_out = best / (float)s.n;   // ifftn's 1/N
+    pcp::peak_to_shift(peak, s.shape, s.norm[inorm].shift);
+}
+
+int reserve_refinement_scratch(Phasecorr& s) {
+    if (!s.plan.refine) return MVS_OK;
+    s.up_base = (char*)mvs_scratch(s.c, 7, s.up.total);
+    return s.up_base ? MVS_OK : mvs_alloc_failed(s.c);
+}
+
+// stage 2 (y -> (z, uy, ux)) and, in 3D, stage 3 (z -> (uz, uy, ux)) of one normalisation; the last one writes the mailbox
+void later_stages(Phasecorr& s, int j) {
+    const NormRefine& sj = s.norm[j];
+    const int U = s.plan.U;
+    hipLaunchKernelGGL(updft_mid_kernel, dim3((unsigned)std::min<long long>(((long long)s.up.s2 + 3) / 4, 4096)), dim3(256), 0, s.c->stream, sj.o1, sj.dk + sj.koff[1], sj.o2, s.nz, s.ny, U, U);
+    if (s.ndim == 3)
+        hipLaunchKernelGGL(updft_mid_kernel, dim3((unsigned)std::min<long long>(((long long)s.up.s3 + 3) / 4, 4096)), dim3(256), 0, s.c->stream, sj.o2, sj.dk + sj.koff[0], sj.o3, 1, s.nz, U * U, U);
+}
+
+// stage 1 (x -> (z, y, ux)) of ONE normalisation from its stored cross power, then its later stages
+int stage1_one_norm(Phasecorr& s, int inorm) {
+    const NormRefine& st = s.norm[inorm];
+    const long long nrows = (long long)s.nz * s.ny;
+    hipLaunchKernelGGL(updft_x_kernel, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, s.c->stream, st.P, st.dk + st.koff[2], st.o1, nrows, s.nx, s.plan.U);
+    later_stages(s, inorm);
+    MVS_HIP_TRY(s.c, hipGetLastError());
+    return MVS_OK;
+}
+
+// stage 1 of BOTH normalisations from the plain cross power alone, then their later stages
+int stage1_both_norms(Phasecorr& s) {
+    const long long nrows = (long long)s.nz * s.ny;
+    UpdftX2 q;
+    for (int j = 0; j < 2; ++j) { q.K[j] = s.norm[j].dk + s.norm[j].koff[2]; q.out[j] = s.norm[j].o1; q.phase[j] = s.sel(j); }
+    hipLaunchKernelGGL(updft_x2_kernel<4>, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, s.c->stream, s.P2, q, nrows, s.nx, s.plan.U);
+    for (int j = 0; j < s.n_norm; ++j) later_stages(s, j);
+    MVS_HIP_TRY(s.c, hipGetLastError());
+    return MVS_OK;
+}
+
+// stages 1 AND 2 of both normalisations: partial sums per (z, y chunk) in the stage-1 area (they fit: tests/test_phasecorr_plan_host.py),
+// folded by stage 3
+int stage1_and_2_both_norms(Phasecorr& s) {
+    const int U = s.plan.U, chunks = s.plan.yx_chunks;
+    UpdftYX q;
+    for (int j = 0; j < 2; ++j) {
+        q.Kx[j] = s.norm[j].dk + s.norm[j].koff[2]; q.Ky[j] = s.norm[j].dk + s.norm[j].koff[1]; q.out[j] = s.norm[j].o1;
+        q.phase[j] = s.sel(j);
+    }
+    MVS_DUP("updft", hipLaunchKernelGGL(updft_yx2_kernel<3>, dim3((unsigned)(s.nz * chunks)), dim3(256), 0, s.c->stream, s.P2, q, s.nz, s.ny, s.nx,
+                       s.plan.rows_per_chunk, chunks));
+    for (int j = 0; j < s.n_norm; ++j)
+        MVS_DUP("updft_mid", hipLaunchKernelGGL(updft_mid_kernel, dim3((unsigned)std::min<long long>(((long long)s.up.s3 + 3) / 4, 4096)), dim3(256), 0, s.c->stream,
+                           s.norm[j].o1, s.norm[j].dk + s.norm[j].koff[0], s.norm[j].o3, 1, s.nz * chunks, U * U, U, chunks));
+    MVS_HIP_TRY(s.c, hipGetLastError());
+    return MVS_OK;
+}
+
+// The upsampled DFT around one normalisation's integer peak: its kernel vectors go into the mailbox, and its launches are queued -- at
+// once when every normalisation runs its own stage 1, after the last normalisation when one launch serves both.  Nothing is waited for.
+int queue_refinements(Phasecorr& s, int inorm) {
+    NormRefine& st = s.norm[inorm];
+    float offs[3];
+    pcp::round_to_grid(st.shift, s.upsample, s.plan.U, offs);
+    float2* hk = (float2*)(s.mb_host + s.mb.kvec_of(inorm));   // stays untouched until the caller's wait
+    size_t nk = 0;
+    for (int k = (s.ndim == 3) ? 0 : 1; k < 3; ++k) {
+        st.koff[k] = nk;
+        nk += pcp::fill_kernel(hk + nk, (int)s.shape[k], s.plan.U, offs[k], s.upsample);
+    }
+    st.P = s.norms[inorm] ? s.P1 : s.P2;
+    st.dk = (float2*)(s.up_base + s.up.kvec_of(inorm));
+    st.o1 = (float2*)(s.up_base + s.up.stage_of(inorm));
+    st.o2 = st.o1 + s.up.s1;
+    st.o3 = st.o2 + s.up.s2;
+    (s.ndim == 3 ? st.o3 : st.o2) = (float2*)(s.mb_dev + s.mb.res_of(inorm));     // the last stage writes host memory
+    st.nout = s.ndim == 3 ? s.up.s3 : s.up.s2;
+    // (the vectors are copied by a kernel out of the mapped mailbox: a DMA upload would queue behind any tile upload in flight)
+    if (!s.plan.fuse_xp) {
+        const int rc = mvs_upload_from_mapped(s.c, st.dk, s.mb_dev + s.mb.kvec_of(inorm), pcp::upload_bytes(nk * sizeof(float2)));
+        return rc ? rc : stage1_one_norm(s, inorm);
+    }
+    if (inorm != s.n_norm - 1) return MVS_OK;
+    // one upload for all normalisations: the vectors lie kvec_stride apart in the mailbox and on the device alike
+    const int rc = mvs_upload_from_mapped(s.c, s.up_base, s.mb_dev + s.mb.kvec, pcp::upload_bytes((size_t)inorm * s.up.kvec_stride + nk * sizeof(float2)));
+    if (rc) return rc;
+    return s.plan.fuse_yx ? stage1_and_2_both_norms(s) : stage1_both_norms(s);
+}
+
+// sub-pixel maximum of every refinement (their results are in the mailbox), then the shifts go out
+void finish_shifts(Phasecorr& s, double* shifts_out) {
+    for (int inorm = 0; inorm < s.n_norm; ++inorm) {
+        NormRefine& st = s.norm[inorm];
+        if (s.plan.refine) {
+            const size_t iu = pcp::subpixel_argmax((const float2*)(s.mb_host + s.mb.res_of(inorm)), st.nout);
+            pcp::add_subpixel(st.shift, iu, s.plan.U, s.ndim, s.upsample);
+        }
+        pcp::zero_unit_axes(st.shift, s.shape);
+        for (int k = 0; k < 3; ++k) shifts_out[3 * inorm + k] = (double)st.shift[k];
     }
 }
-// uint16, bin 2 along x, rows 16-byte aligned: a thread produces 4 consecutive outputs of a row from one 16-byte load per
-// input row (the generic kernel reads element by element: 1.3 TB/s on a 512^3 tile).  Integer sums are exact in double,
-// so the order of the additions does not matter and the result equals the generic kernel's.
-__global__ __launch_bounds__(256) void bin_mean_u16x2_kernel(const unsigned short* __restrict__ in, long long sz, long long sy,
-                                                             unsigned short* __restrict__ out, int oz, int oy, int ox, int bz, int by) {
-    const int gx = ox >> 2;                                   // groups of 4 outputs per row (ox % 4 == 0)
-    const long long ngroups = (long long)oz * oy * gx;
-    const double count = (double)bz * by * 2;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (long long)gridDim.x * blockDim.x) {
-        const int xg = (int)(g % gx);
-        const long long t = g / gx;
-        const int y = (int)(t % oy), z = (int)(t / oy);
-        unsigned int acc[4] = {0u, 0u, 0u, 0u};               // at most 2 * by * bz * 65535: fits for by * bz <= 32767
-        for (int dz = 0; dz < bz; ++dz)
-            for (int dy = 0; dy < by; ++dy) {
-                const u32x4 v = *reinterpret_cast<const u32x4*>(in + (long long)(z * bz + dz) * sz + (long long)(y * by + dy) * sy + (long long)xg * 8);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc[k] += (v[k] & 0xffffu) + (v[k] >> 16);
-            }
-        unsigned short r[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = mvs_bin::mean_cast<unsigned short>(acc[k], count);   // astype: truncation
-        *reinterpret_cast<uint2*>(out + ((long long)z * oy + y) * ox + (long long)xg * 4) =
-            make_uint2((unsigned int)r[0] | ((unsigned int)r[1] << 16), (unsigned int)r[2] | ((unsigned int)r[3] << 16));
-    }
-}
-// the same for up to kBinBatch views of one shape in one launch: blockIdx.y = view (pointer table in the kernel arguments)
-constexpr int kBinBatch = 32;
-struct BinBatch {
-    const unsigned short* in[kBinBatch];
-    unsigned short* out[kBinBatch];
-};
-__global__ __launch_bounds__(256) void bin_mean_u16x2_batch_kernel(BinBatch B, long long sz, long long sy, int oz, int oy, int ox, int bz, int by) {
-    const unsigned short* __restrict__ in = B.in[blockIdx.y];
-    unsigned short* __restrict__ out = B.out[blockIdx.y];
-    const int gx = ox >> 2;
-    const long long ngroups = (long long)oz * oy * gx;
-    const double count = (double)bz * by * 2;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (long long)gridDim.x * blockDim.x) {
-        const int xg = (int)(g % gx);
-        const long long t = g / gx;
-        const int y = (int)(t % oy), z = (int)(t / oy);
-        unsigned int acc[4] = {0u, 0u, 0u, 0u};
-        for (int dz = 0; dz < bz; ++dz)
-            for (int dy = 0; dy < by; ++dy) {
-                const u32x4 v = *reinterpret_cast<const u32x4*>(in + (long long)(z * bz + dz) * sz + (long long)(y * by + dy) * sy + (long long)xg * 8);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc[k] += (v[k] & 0xffffu) + (v[k] >> 16);
-            }
-        unsigned short r[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = mvs_bin::mean_cast<unsigned short>(acc[k], count);   // astype: truncation
-        *reinterpret_cast<uint2*>(out + ((long long)z * oy + y) * ox + (long long)xg * 4) =
-            make_uint2((unsigned int)r[0] | ((unsigned int)r[1] << 16), (unsigned int)r[2] | ((unsigned int)r[3] << 16));
-    }
-}
+
 }  // namespace
 
-static int bin_mean_impl(int device, const void* in, int32_t dtype, int32_t mem, const int64_t shape[3], const int64_t stride[3],
-                         const int64_t bin[3], void* out, int32_t out_mem, bool wait);
-
-// mvs_bin_mean_async for n views of one shape, stride and dtype in one call (and, for 16-bit tiles binned by 2 along x, one launch per
-// kBinBatch views): registration.register bins all tiles of a mosaic before its pairs start.
-extern "C" int mvs_bin_mean_batch_async(int device, int32_t n_views, const void* const* in, int32_t dtype, const int64_t shape[3],
-                                        const int64_t stride[3], const int64_t bin[3], void* const* out) {
+extern "C" int mvs_phasecorr_multi(int device, const float* fixed, const float* moving, int32_t mem, int32_t ndim,
+                                   const int64_t shape[3], const int32_t* normalizations, int32_t n_norm,
+                                   int32_t upsample_factor, double* shifts_out, int64_t* peak_indices_out,
+                                   float* peak_abs_out_all) {
     MvsContext* c;
     int rc = mvs_check_ready(device, &c);
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> lock(c->mu);
-    if (n_views < 0 || (n_views > 0 && (!in || !out)) || !shape || !stride || !bin) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_bin_mean_batch_async: NULL argument");
-    bool vec = dtype == MVS_U16 && stride[2] == 1 && bin[2] == 2 && bin[0] >= 1 && bin[1] >= 1 && shape[0] >= bin[0] && shape[1] >= bin[1] &&
-               shape[2] >= 2 && (shape[2] / 2) % 4 == 0 && stride[1] % 8 == 0 && stride[0] % 8 == 0 && bin[0] * bin[1] <= 16384;
-    for (int v = 0; v < n_views && vec; ++v) vec = in[v] && out[v] && ((uintptr_t)in[v] % 16) == 0 && ((uintptr_t)out[v] % 8) == 0;
-    if (!vec) {
-        for (int v = 0; v < n_views; ++v) {
-            rc = bin_mean_impl(device, in[v], dtype, MVS_MEM_DEVICE, shape, stride, bin, out[v], MVS_MEM_DEVICE, false);
-            if (rc) return rc;
-        }
-        return MVS_OK;
-    }
-    MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
-    const int oz = (int)(shape[0] / bin[0]), oy = (int)(shape[1] / bin[1]), ox = (int)(shape[2] / 2);
-    const long long n = (long long)oz * oy * ox;
-    for (int v0 = 0; v0 < n_views; v0 += kBinBatch) {
-        const int nb = std::min(kBinBatch, n_views - v0);
-        BinBatch B;
-        for (int k = 0; k < kBinBatch; ++k) {
-            B.in[k] = (const unsigned short*)in[v0 + std::min(k, nb - 1)];
-            B.out[k] = (unsigned short*)out[v0 + std::min(k, nb - 1)];
-        }
-        hipLaunchKernelGGL(bin_mean_u16x2_batch_kernel, dim3(grid_for(n / 4), nb), dim3(256), 0, c->stream, B, (long long)stride[0], (long long)stride[1],
-                           oz, oy, ox, (int)bin[0], (int)bin[1]);
-    }
-    MVS_HIP_TRY(c, hipGetLastError());
-    return MVS_OK;
-}
-
-extern "C" int mvs_bin_mean(int device, const void* in, int32_t dtype, int32_t mem, const int64_t shape[3],
-                            const int64_t stride[3], const int64_t bin[3], void* out, int32_t out_mem) {
-    return bin_mean_impl(device, in, dtype, mem, shape, stride, bin, out, out_mem, true);
-}
-
-// The same launch without the final wait (device memory on both sides only): the caller orders later work with
-// mvs_synchronize(device) -- used to bin all tiles of a mosaic while the host builds its overlap graph.
-extern "C" int mvs_bin_mean_async(int device, const void* in, int32_t dtype, const int64_t shape[3], const int64_t stride[3],
-                                  const int64_t bin[3], void* out) {
-    return bin_mean_impl(device, in, dtype, MVS_MEM_DEVICE, shape, stride, bin, out, MVS_MEM_DEVICE, false);
-}
-
-static int bin_mean_impl(int device, const void* in, int32_t dtype, int32_t mem, const int64_t shape[3], const int64_t stride[3],
-                         const int64_t bin[3], void* out, int32_t out_mem, bool wait) {
-    MvsContext* c;
-    int rc = mvs_check_ready(device, &c);
+    Phasecorr s;
+    rc = validate_and_stage(s, c, device, fixed, moving, mem, ndim, shape, normalizations, n_norm, upsample_factor, shifts_out);
     if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    if (!in || !out || !shape || !stride || !bin) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_bin_mean: NULL argument");
-    const size_t es = mvs_dtype_size(dtype);
-    if (!es) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_bin_mean: bad dtype");
-    if (stride[2] != 1) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "mvs_bin_mean: x stride must be 1");
-    int o[3];
-    for (int k = 0; k < 3; ++k) {
-        if (bin[k] < 1 || shape[k] < bin[k]) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_bin_mean: bad bin/shape on axis %d", k);
-        o[k] = (int)(shape[k] / bin[k]);
+    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
+    rc = forward_transform(s);
+    if (rc) return rc;
+    rc = reserve_mailbox(s);
+    if (rc) return rc;
+    // two different normalisations share one correlation pass and one host round trip ...
+    if (s.plan.route == pcp::kSlab) rc = correlate_slab(s);
+    else if (s.plan.route == pcp::kPacked) rc = correlate_packed(s);
+    if (rc) return rc;
+    rc = reserve_refinement_scratch(s);
+    if (rc) return rc;
+    // ... otherwise every normalisation has its own.  Per normalisation: integer peak -> upsampled DFT around it; the refinements
+    // of all normalisations are queued before the host waits once for their results.
+    for (int inorm = 0; inorm < n_norm; ++inorm) {
+        if (s.plan.route == pcp::kPerNorm) rc = correlate_one_norm(s, inorm);
+        if (rc) return rc;
+        read_peaks(s, inorm, peak_indices_out ? peak_indices_out + 3 * inorm : nullptr, peak_abs_out_all ? peak_abs_out_all + inorm : nullptr);
+        if (s.plan.refine) rc = queue_refinements(s, inorm);
+        if (rc) return rc;
     }
-    MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
-    const void* din = in;
-    long long sz = stride[0], sy = stride[1];
-    if (mem == MVS_MEM_HOST) {
-        if (stride[1] != shape[2] || stride[0] != shape[1] * shape[2])
-            return mvs_fail(c, MVS_ERR_UNSUPPORTED, "mvs_bin_mean: host input must be C-contiguous");
-        const size_t nb = (size_t)shape[0] * shape[1] * shape[2] * es;
-        void* s = mvs_scratch(c, 4, nb);
-        if (!s) return mvs_alloc_failed(c);
-        MVS_HIP_TRY(c, hipMemcpyAsync(s, in, nb, hipMemcpyHostToDevice, c->stream));
-        din = s;
-    }
-    const long long n = (long long)o[0] * o[1] * o[2];
-    void* dout = out;
-    if (out_mem == MVS_MEM_HOST) {
-        dout = mvs_scratch(c, 5, (size_t)n * es);
-        if (!dout) return mvs_alloc_failed(c);
-    }
-    const int gb = grid_for(n);
-    const bool vec_u16 = dtype == MVS_U16 && bin[2] == 2 && o[2] % 4 == 0 && sy % 8 == 0 && sz % 8 == 0 && ((uintptr_t)din % 16) == 0 &&
-                         ((uintptr_t)dout % 8) == 0 && bin[0] * bin[1] <= 16384;
-    if (vec_u16) {
-        hipLaunchKernelGGL(bin_mean_u16x2_kernel, dim3(grid_for(n / 4)), dim3(256), 0, c->stream, (const unsigned short*)din, sz, sy,
-                           (unsigned short*)dout, o[0], o[1], o[2], (int)bin[0], (int)bin[1]);
-    } else
-        mvs_dispatch_dtype(dtype, [&](auto tag) {
-            using T = decltype(tag);
-            hipLaunchKernelGGL(bin_mean_kernel<T>, dim3(gb), dim3(256), 0, c->stream, (const T*)din, sz, sy, (T*)dout, o[0], o[1], o[2],
-                               (int)bin[0], (int)bin[1], (int)bin[2]);
-        });
-    MVS_HIP_TRY(c, hipGetLastError());
-    if (out_mem == MVS_MEM_HOST) MVS_HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)n * es, hipMemcpyDeviceToHost, c->stream));
-    if (wait) MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
+    c->timing_valid = true;
+    if (s.plan.refine) MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    finish_shifts(s, shifts_out);
     return MVS_OK;
 }

@@ -21,8 +21,6 @@
 #include <cstdlib>
 #include <vector>
 
-int mvs_device_nanminmax(MvsContext* c, const float* d_in, long long n, float* mn, float* mx, long long* nvalid);   // mvs_reg.hip
-
 namespace {
 
 constexpr int kStatBlocks = 1024;    // workgroups (= partial results per candidate) of the statistics kernels

@@ -1,5 +1,5 @@
 """GPU: every block-mean binning kernel against numpy's ``a[trim].reshape(...).mean(axis=...).astype(dtype)`` in float64, at the edges
-of the conditions that pick a kernel (csrc/mvs_reg.hip bin_mean_impl / mvs_bin_mean_batch_async, csrc/mvs_fuse.hip crop_bin_kernel):
+of the conditions that pick a kernel (csrc/mvs_bin.hip bin_mean_impl / mvs_bin_mean_batch_async, csrc/mvs_fuse.hip crop_bin_kernel):
 
   bin_mean_kernel<T>             the generic kernel: any dtype, bins, stride, alignment
   bin_mean_u16x2_kernel          uint16, bin 2 along x, binned width % 4 == 0, y / z strides % 8 == 0, input 16-byte and output 8-byte

@@ -715,3 +715,38 @@ def test_three_pass_phase_correlation_equals_the_single_axis_passes(hip_device, 
     got, want = np.asarray(res[0][0][0], dtype=float), np.array(sh, dtype=float)
     assert min(np.abs(got - want).max(), np.abs(got + want).max()) <= 0.5
 
+
+# the smallest crops that reach each route and stage-1 variant of mvs_phasecorr_multi (csrc/mvs_phasecorr_plan.h; the CPU route table of
+# tests/test_phasecorr_plan_host.py): shape, shift (below a quarter of each axis), normalisations, does it take the three-pass form
+ROUTE_CASES = {
+    "slab": ((64, 64, 18), (3, -5, 2), ("phase", None), True),
+    "merged_stages_1_and_2": ((4, 6, 64), (0, 1, -7), ("phase", None), False),
+    "fused_cross_power_3d": ((2, 3, 64), (0, 0, 5), ("phase", None), False),
+    "fused_cross_power_2d": ((20, 64), (3, -6), ("phase", None), False),
+    "packed_unfused": ((3, 5, 130), (0, 1, -9), ("phase", None), False),
+    "one_inverse_per_normalisation": ((4, 6, 64), (0, 1, -7), ("phase", "phase"), False),
+    "stand_alone_peak_kernel": ((130, 6, 64), (7, 1, -4), ("phase", None), False),
+    "peaks_from_the_last_inverse_pass": ((18, 6, 64), (-2, 1, 6), ("phase", None), False),
+}
+
+
+@pytest.mark.parametrize("route", sorted(ROUTE_CASES))
+def test_phasecorr_every_route_matches_the_oracle(hip_device, route):
+    """One small pair per route of the phase correlation -- three-pass form, packed pair of correlations with the merged refinement stages
+    1 and 2, with the fused cross power alone (3D and 2D), without any fusion (a 130-sample x axis runs on the LDS kernel), one inverse
+    transform per normalisation, peaks from the stand-alone kernel (130-sample z axis) and from the last inverse pass -- against the
+    oracle, each normalisation by the standard of test_phasecorr_peak_index_bit_exact_and_shift.  The oracle's peak is unique on every
+    input: its largest |cc| exceeds the second largest by 2.0e-4 of itself at the least ((3, 5, 130), no normalisation; float32
+    rounding of these transforms is about 1e-6)."""
+    from multiview_stitcher_amd import _lib, _reg_ops
+
+    shape, shift, norms, slab = ROUTE_CASES[route]
+    a, b = _pair(shape, shift, noise=0.002)
+    _lib.get_counter("reg_slab_pairs", reset=True)
+    got = _reg_ops.phase_cross_correlation_multi(a, b, upsample_factor=2, normalizations=norms)
+    assert _lib.get_counter("reg_slab_pairs", reset=True) == (1.0 if slab else 0.0)
+    for (s, gdbg), norm in zip(got, norms):
+        want, wdbg = ro.phase_cross_correlation(a, b, upsample_factor=2, normalization=norm, return_debug=True)
+        np.testing.assert_array_equal(gdbg["peak_index"], wdbg["peak_index"])
+        np.testing.assert_array_equal(np.asarray(s, dtype=np.float64), np.asarray(want, dtype=np.float64))
+        assert abs(gdbg["peak_abs"] - wdbg["peak_abs"]) <= 1e-4 * abs(wdbg["peak_abs"]) + 1e-7
