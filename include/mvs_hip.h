@@ -318,6 +318,18 @@ int mvs_phasecorr_multi(int device, const float* fixed, const float* moving, int
                         int32_t ndim, const int64_t shape[3], const int32_t* normalizations,
                         int32_t n_norm, int32_t upsample_factor, double* shifts_out,
                         int64_t* peak_indices_out, float* peak_abs_out);
+/* mvs_phasecorr_multi -- the same launches -- that also hands out what the upsampled-DFT refinement computed, for tests of
+ * its kernels.  refined_out: n_norm blocks of U^ndim complex64 values (interleaved re, im), U = ceil(1.5 upsample_factor),
+ * in the order [(uz,) uy, ux].  They are skimage's _upsampled_dft(image_product.conj(), ...) BEFORE its final .conj() (the
+ * kernels form k * conj(v)); the sub-pixel maximum is the arg max of their moduli either way.  The values are in the units
+ * of skimage's: the cross power the refinement reads is stored without the channel scales of the packed inverse transform.
+ * refined_capacity counts floats: below 2 * n_norm * U^ndim, or refined_out NULL, returns MVS_ERR_INVALID_ARG before
+ * anything runs.  upsample_factor == 1 has no refinement: nothing is written and refined_out may be NULL. */
+int mvs_phasecorr_multi_refined(int device, const float* fixed, const float* moving, int32_t mem,
+                                int32_t ndim, const int64_t shape[3], const int32_t* normalizations,
+                                int32_t n_norm, int32_t upsample_factor, double* shifts_out,
+                                int64_t* peak_indices_out, float* peak_abs_out, float* refined_out,
+                                int64_t refined_capacity);
 
 /* Intensity normalisation of one registration input == skimage.exposure.rescale_intensity(im,
  * in_range=(nanmin(im), nanmax(im)), out_range=(0, 1)) as called at registration.py:381-389:

@@ -168,6 +168,11 @@ SIGNATURES = {
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32,
          C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_float)],
     ),
+    "mvs_phasecorr_multi_refined": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int32,
+         C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_float), C.c_void_p, C.c_int64],
+    ),
     "mvs_rescale_intensity": (
         C.c_int,
         [C.c_int, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),

@@ -74,9 +74,13 @@ def fftn(a, inverse=False, device=0):
     return out
 
 
-def phase_cross_correlation_multi(reference_image, moving_image, upsample_factor=1, normalizations=("phase", None), device=0):
+def phase_cross_correlation_multi(reference_image, moving_image, upsample_factor=1, normalizations=("phase", None), device=0,
+                                  return_refined=False):
     """``phase_cross_correlation`` for several normalisations of one image pair; the forward transforms are
-    shared (mvs_phasecorr_multi).  Returns a list of (shift, debug) like ``phase_cross_correlation(return_debug=True)``."""
+    shared (mvs_phasecorr_multi).  Returns a list of (shift, debug) like ``phase_cross_correlation(return_debug=True)``.
+    ``return_refined``: the same launches through mvs_phasecorr_multi_refined; ``debug["refined"]`` is then what the upsampled-DFT
+    refinement computed, a complex64 array of ``ceil(1.5 * upsample_factor)`` samples per axis -- skimage's
+    ``_upsampled_dft(image_product.conj(), ...)`` before its final ``.conj()`` -- or None for ``upsample_factor == 1``."""
     lib = _lib.init(device)
     if tuple(reference_image.shape) != tuple(moving_image.shape):
         raise ValueError("images must be same shape")
@@ -94,13 +98,26 @@ def phase_cross_correlation_multi(reference_image, moving_image, upsample_factor
     shift = (C.c_double * (3 * nn))()
     peak = (C.c_int64 * (3 * nn))()
     pabs = (C.c_float * nn)()
-    rc = lib.mvs_phasecorr_multi(device, p0, p1, m0, ndim, _lib.i64x3(shape3(shape)), norms, nn, int(upsample_factor),
-                                 shift, peak, pabs)
-    _lib.check(rc, device, "mvs_phasecorr_multi")
+    refined = None
+    if return_refined:
+        U = int(np.ceil(np.float32(upsample_factor) * np.float32(1.5)))
+        if int(upsample_factor) > 1:
+            refined = np.zeros((nn,) + (U,) * ndim, dtype=np.complex64)
+        rc = lib.mvs_phasecorr_multi_refined(device, p0, p1, m0, ndim, _lib.i64x3(shape3(shape)), norms, nn, int(upsample_factor),
+                                             shift, peak, pabs, refined.ctypes.data if refined is not None else None,
+                                             2 * refined.size if refined is not None else 0)
+        _lib.check(rc, device, "mvs_phasecorr_multi_refined")
+    else:
+        rc = lib.mvs_phasecorr_multi(device, p0, p1, m0, ndim, _lib.i64x3(shape3(shape)), norms, nn, int(upsample_factor),
+                                     shift, peak, pabs)
+        _lib.check(rc, device, "mvs_phasecorr_multi")
     out = []
     for i in range(nn):
         s = np.array(list(shift)[3 * i + 3 - ndim:3 * i + 3], dtype=np.float32)
-        out.append((s, {"peak_index": np.array(list(peak)[3 * i + 3 - ndim:3 * i + 3]), "peak_abs": float(pabs[i])}))
+        debug = {"peak_index": np.array(list(peak)[3 * i + 3 - ndim:3 * i + 3]), "peak_abs": float(pabs[i])}
+        if return_refined:
+            debug["refined"] = refined[i] if refined is not None else None
+        out.append((s, debug))
     return out
 
 

@@ -13,6 +13,7 @@
 
 #include <rocprim/warp/warp_reduce.hpp>
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <vector>
@@ -812,29 +813,27 @@ int queue_refinements(Phasecorr& s, int inorm) {
     return s.plan.fuse_yx ? stage1_and_2_both_norms(s) : stage1_both_norms(s);
 }
 
-// sub-pixel maximum of every refinement (their results are in the mailbox), then the shifts go out
-void finish_shifts(Phasecorr& s, double* shifts_out) {
+// sub-pixel maximum of every refinement (their results are in the mailbox), then the shifts go out; refined_out (may be NULL) takes a
+// copy of every normalisation's result, nout values each
+void finish_shifts(Phasecorr& s, double* shifts_out, float2* refined_out) {
     for (int inorm = 0; inorm < s.n_norm; ++inorm) {
         NormRefine& st = s.norm[inorm];
         if (s.plan.refine) {
-            const size_t iu = pcp::subpixel_argmax((const float2*)(s.mb_host + s.mb.res_of(inorm)), st.nout);
+            const float2* res = (const float2*)(s.mb_host + s.mb.res_of(inorm));
+            const size_t iu = pcp::subpixel_argmax(res, st.nout);
             pcp::add_subpixel(st.shift, iu, s.plan.U, s.ndim, s.upsample);
+            if (refined_out) std::copy(res, res + st.nout, refined_out + (size_t)inorm * st.nout);
         }
         pcp::zero_unit_axes(st.shift, s.shape);
         for (int k = 0; k < 3; ++k) shifts_out[3 * inorm + k] = (double)st.shift[k];
     }
 }
 
-}  // namespace
-
-extern "C" int mvs_phasecorr_multi(int device, const float* fixed, const float* moving, int32_t mem, int32_t ndim,
-                                   const int64_t shape[3], const int32_t* normalizations, int32_t n_norm,
-                                   int32_t upsample_factor, double* shifts_out, int64_t* peak_indices_out,
-                                   float* peak_abs_out_all) {
-    MvsContext* c;
-    int rc = mvs_check_ready(device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
+// the body of mvs_phasecorr_multi and mvs_phasecorr_multi_refined: the same launches whether or not the refinement is read back
+int phasecorr_multi(MvsContext* c, int device, const float* fixed, const float* moving, int32_t mem, int32_t ndim, const int64_t shape[3],
+                    const int32_t* normalizations, int32_t n_norm, int32_t upsample_factor, double* shifts_out, int64_t* peak_indices_out,
+                    float* peak_abs_out_all, float2* refined_out) {
+    int rc;
     Phasecorr s;
     rc = validate_and_stage(s, c, device, fixed, moving, mem, ndim, shape, normalizations, n_norm, upsample_factor, shifts_out);
     if (rc) return rc;
@@ -861,6 +860,39 @@ extern "C" int mvs_phasecorr_multi(int device, const float* fixed, const float* 
     MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
     c->timing_valid = true;
     if (s.plan.refine) MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    finish_shifts(s, shifts_out);
+    finish_shifts(s, shifts_out, refined_out);
     return MVS_OK;
+}
+
+}  // namespace
+
+extern "C" int mvs_phasecorr_multi(int device, const float* fixed, const float* moving, int32_t mem, int32_t ndim,
+                                   const int64_t shape[3], const int32_t* normalizations, int32_t n_norm,
+                                   int32_t upsample_factor, double* shifts_out, int64_t* peak_indices_out,
+                                   float* peak_abs_out_all) {
+    MvsContext* c;
+    const int rc = mvs_check_ready(device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    return phasecorr_multi(c, device, fixed, moving, mem, ndim, shape, normalizations, n_norm, upsample_factor, shifts_out, peak_indices_out,
+                           peak_abs_out_all, nullptr);
+}
+
+extern "C" int mvs_phasecorr_multi_refined(int device, const float* fixed, const float* moving, int32_t mem, int32_t ndim,
+                                           const int64_t shape[3], const int32_t* normalizations, int32_t n_norm,
+                                           int32_t upsample_factor, double* shifts_out, int64_t* peak_indices_out,
+                                           float* peak_abs_out_all, float* refined_out, int64_t refined_capacity) {
+    MvsContext* c;
+    const int rc = mvs_check_ready(device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::recursive_mutex> lock(c->mu);
+    // refused before anything is staged or launched
+    if (upsample_factor > 1 && (ndim == 2 || ndim == 3) && n_norm >= 1) {
+        const long long U = pcp::refine_samples(upsample_factor);
+        const long long need = 2 * (long long)n_norm * (ndim == 3 ? U * U * U : U * U);
+        if (!refined_out) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_phasecorr_multi_refined: NULL refined_out");
+        if (refined_capacity < need) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_phasecorr_multi_refined: refined_capacity too small");
+    }
+    return phasecorr_multi(c, device, fixed, moving, mem, ndim, shape, normalizations, n_norm, upsample_factor, shifts_out, peak_indices_out,
+                           peak_abs_out_all, (float2*)refined_out);
 }

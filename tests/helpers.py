@@ -221,6 +221,30 @@ def _pair(shape, shift, seed=0, sigma=1.0, noise=0.0):
     return a, b
 
 
+def _pair_fractional(shape, shift, seed=0, sigma=0.8, noise=0.002):
+    """Two float32 windows of one field, the second moved by the FRACTIONAL ``shift`` (b[i] = field[i + shift]): a smoothed
+    zero-mean texture of unit standard deviation, 12 samples of margin per side, moved as a whole by the Fourier shift theorem in
+    float64, then cropped.  Zero mean: the plain correlation is peaked like the phase-normalised one (no DC pedestal), so both
+    normalisations leave a margin between the refinement's maximum and its runner-up (tests/refine_cases.py)."""
+    import scipy.fft
+
+    rng = np.random.default_rng(seed)
+    pad = 12
+    big = ndimage.gaussian_filter(rng.standard_normal(tuple(s + 2 * pad for s in shape)), sigma)
+    big /= big.std()
+    phase = 1
+    for axis, d in enumerate(shift):
+        f = scipy.fft.fftfreq(big.shape[axis]).reshape([-1 if k == axis else 1 for k in range(big.ndim)])
+        phase = phase * np.exp(2j * np.pi * f * d)
+    moved = scipy.fft.ifftn(scipy.fft.fftn(big) * phase).real
+    window = tuple(slice(pad, pad + s) for s in shape)
+    a = np.ascontiguousarray(big[window]).astype(np.float32)
+    b = np.ascontiguousarray(moved[window]).astype(np.float32)
+    if noise:
+        b = b + noise * rng.standard_normal(shape).astype(np.float32)
+    return a, b
+
+
 def _check_scores(a, b, t_cands, region_mode):
     """mvs_score_candidates against the oracle's candidate loop on rescaled inputs."""
     from multiview_stitcher_amd import _reg_ops

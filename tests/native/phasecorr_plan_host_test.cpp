@@ -7,6 +7,7 @@
 //   L <checked> <wrong> ...    layouts: regions apart, at the offsets of the formulas used before, totals equal, uploads of 16-byte units
 //   Y <checked> <wrong>        the chunk partials of the merged stages 1 and 2 fit the stage-1 area, the chunks cover the rows
 //   U / A / M / KV / TP / TS   host arithmetic (see main)
+// Called with arguments it prints the plan of the cases they name instead (print_plans; tests/test_refine_cases_host.py).
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -366,9 +367,30 @@ void print_arithmetic() {
                 printf("X %u %u %lld %u %u\n", bits(re), bits(im), n, bits(sp), bits(sl));
             }
 }
+
+// ---- 5. the plan of given cases (tests/test_refine_cases_host.py) ------------------------------------------------------------------
+// every argument "ndim,nz,ny,nx,n_norm,norm0,norm1,upsample,switch bits" (bits as in check_routes_and_layouts: 1 reg_unfused,
+// 2 materialize_shifts, 4 fft_no_slab, 8 fft_no_line, 16 fft_no_pair) gives one line
+//   PL <argument> <route> <fuse_xp> <fuse_yx> <yx_chunks> <rows_per_chunk> <forward_reads_crops> <last_pass_peaks> <n_peak>
+int print_plans(int argc, char** argv) {
+    for (int i = 1; i < argc; ++i) {
+        long long v[9];
+        if (sscanf(argv[i], "%lld,%lld,%lld,%lld,%lld,%lld,%lld,%lld,%lld", v, v + 1, v + 2, v + 3, v + 4, v + 5, v + 6, v + 7, v + 8) != 9) return 2;
+        const int64_t shape[3] = {v[1], v[2], v[3]};
+        const int32_t norms[2] = {(int32_t)v[5], (int32_t)v[6]};
+        pcp::Switches sw;
+        sw.reg_unfused = v[8] & 1; sw.materialize_shifts = v[8] & 2; sw.fft_no_slab = v[8] & 4; sw.fft_no_line = v[8] & 8; sw.fft_no_pair = v[8] & 16;
+        const pcp::Plan p = pcp::plan((int)v[0], shape, norms, (int)v[4], (int)v[7], sw);
+        printf("PL %s %s %d %d %d %d %d %d %d\n", argv[i], p.route == pcp::kSlab ? "slab" : p.route == pcp::kPacked ? "packed" : "per_norm", (int)p.fuse_xp,
+               (int)p.fuse_yx, p.yx_chunks, p.rows_per_chunk, (int)p.forward_reads_crops, (int)p.last_pass_peaks, p.n_peak);
+    }
+    printf("done\n");
+    return 0;
+}
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1) return print_plans(argc, argv);
     check_passes();
     check_routes_and_layouts();
     print_arithmetic();
