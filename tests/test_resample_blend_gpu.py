@@ -4,6 +4,7 @@ pre-transform with cval = NaN, registration.py:318-338) and mvs_blend_weights (w
 weights.py:391-511), plus the hand-derived blending ramp of tests/test_weights_oracle.py through the HIP fuse."""
 import numpy as np
 import pytest
+from scipy.ndimage import affine_transform
 
 from oracle import fuse_oracle as fo
 from tests.helpers import bb_to_dicts
@@ -21,10 +22,35 @@ def _random_affine(ndim, rng, rot=0.3, scale=0.1, shift=4.0):
     return a
 
 
+EXACT_KINDS = ("rot90", "rot270", "mirror", "swap")
+
+
+def _exact_pixel_affine(kind, shape):
+    """Pixel matrix and integer offset of the kinds whose view borders fall on output voxels: a turn in the yx plane by np.pi / 2
+    (np.cos leaves 6.1e-17 in the matrix: where the other term of a coordinate is 0 it becomes 6.1e-17 * index, inside) or by
+    3 * np.pi / 2 (-1.8e-16: there the coordinate is below 0, outside, for every index but 0), a mirror along x, a swap of y and x.
+    Elsewhere the coordinates are exactly 0.0 .. n - 1."""
+    ndim, (ny, nx) = len(shape), shape[-2:]
+    m, o = np.eye(ndim), np.zeros(ndim)
+    if ndim == 3:
+        o[0] = -2.0
+    if kind in ("rot90", "rot270"):
+        a = np.pi / 2 if kind == "rot90" else 3 * np.pi / 2
+        m[-2:, -2:] = [[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]
+        o[-2:] = [ny - 1, 0.0] if kind == "rot90" else [0.0, nx - 1]
+    elif kind == "mirror":
+        m[-1, -1] = -1.0
+        o[-2:] = [-3.0, nx - 1 + 4]
+    else:
+        m[-2:, -2:] = [[0.0, 1.0], [1.0, 0.0]]
+        o[-2:] = [0.0, -5.0]
+    return m, o
+
+
 @pytest.mark.parametrize("ndim", [2, 3])
 @pytest.mark.parametrize("order", [0, 1])
 @pytest.mark.parametrize("dtype", [np.uint16, np.float32, np.uint8])
-@pytest.mark.parametrize("kind", ["translation", "integer", "affine"])
+@pytest.mark.parametrize("kind", ["translation", "integer", "affine", *EXACT_KINDS])
 def test_resample_matches_scipy_with_nan_cval(hip_device, ndim, order, dtype, kind):
     from multiview_stitcher_amd import transformation
 
@@ -44,8 +70,15 @@ def test_resample_matches_scipy_with_nan_cval(hip_device, ndim, order, dtype, ki
     if kind == "integer":                                                # same grid, integer pixel offsets
         in_s = np.ones(ndim)
         out_bb = fo.bb(in_o - 2.0, np.ones(ndim), out_shape)
-    want = fo.transform_array(data.astype(np.float32), p, in_o, in_s, out_bb, order=order, cval=np.nan)
-    m, o = transformation.get_pixel_affine(p, in_o, in_s, out_bb["origin"], out_bb["spacing"])
+    if kind in EXACT_KINDS:
+        # the pixel affine itself, not derived from origins and spacings: that derivation rounds the matrix to 10 decimals
+        m, o = _exact_pixel_affine(kind, shape)
+        want = affine_transform(data.astype(np.float32), matrix=m, offset=o, output_shape=out_shape, mode="constant", cval=np.nan,
+                                order=order)
+        assert np.isnan(want).any() and (~np.isnan(want)).mean() > 0.3
+    else:
+        want = fo.transform_array(data.astype(np.float32), p, in_o, in_s, out_bb, order=order, cval=np.nan)
+        m, o = transformation.get_pixel_affine(p, in_o, in_s, out_bb["origin"], out_bb["spacing"])
     got = transformation.resample_array(data, m, o, out_shape, order=order, cval=np.nan)
     assert got.dtype == np.float32 and got.shape == want.shape
     np.testing.assert_array_equal(np.isnan(got), np.isnan(want))        # exact in-bounds classification
@@ -54,7 +87,7 @@ def test_resample_matches_scipy_with_nan_cval(hip_device, ndim, order, dtype, ki
 
 
 @pytest.mark.parametrize("ndim", [2, 3])
-@pytest.mark.parametrize("kind", ["identity", "translation", "affine"])
+@pytest.mark.parametrize("kind", ["identity", "translation", "affine", "rot90", "mirror", "swap"])
 def test_blend_weights_match_oracle(hip_device, ndim, kind):
     from multiview_stitcher_amd import weights
 
@@ -68,8 +101,22 @@ def test_blend_weights_match_oracle(hip_device, ndim, kind):
     elif kind == "translation":
         p = np.eye(ndim + 1)
         p[:ndim, ndim] = rng.uniform(-4, 4, ndim)
-    else:
+    elif kind == "affine":
         p = _random_affine(ndim, rng, rot=0.2)
+    else:
+        # unit spacings, origins and offsets whole numbers: the view's borders lie on output voxels
+        src = fo.bb(np.zeros(ndim), np.ones(ndim), shape)
+        tgt = fo.bb(np.full(ndim, -4.0), np.ones(ndim), tuple(int(n * 1.3) for n in shape))
+        p = np.eye(ndim + 1)
+        if kind == "rot90":
+            p[ndim - 2:ndim, ndim - 2:ndim] = [[np.cos(np.pi / 2), -np.sin(np.pi / 2)], [np.sin(np.pi / 2), np.cos(np.pi / 2)]]
+            p[ndim - 2, ndim] = shape[-1] - 1 + 2
+        elif kind == "mirror":
+            p[ndim - 1, ndim - 1] = -1.0
+            p[ndim - 1, ndim] = shape[-1] - 1 + 3
+        else:
+            p[ndim - 2:ndim, ndim - 2:ndim] = [[0.0, 1.0], [1.0, 0.0]]
+            p[ndim - 2:ndim, ndim] = [2.0, -1.0]
     bw = dict(zip(sd, [3.0, 10.0, 6.0][-ndim:]))
     want = fo.get_blending_weights(tgt, src, p, blending_widths=bw)
     got = weights.get_blending_weights(bb_to_dicts(tgt, sd), bb_to_dicts(src, sd), p, blending_widths=bw)
