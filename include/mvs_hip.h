@@ -827,6 +827,60 @@ int mvs_stack_quantiles(int device, const mvs_view_t* views, int32_t n_views, in
 int mvs_plane_apply(int device, const mvs_view_t* view, int32_t ndim, const float* coeff, int32_t coeff_mem, void* out, int32_t out_dtype,
                     int32_t out_mem);
 
+/* Non-rigid tile refinement (nonrigid.fit_fields / apply_fields): a local correction of what one affine per tile cannot describe
+ * (stage non-linearity, field curvature, refractive distortion), between registration and fusion.  The reference has no
+ * counterpart; BigStitcher's non-rigid fusion is the model.  Every view carries a grid of nodes[] = (gz, gy, gx) cells under THE
+ * CELL RULE of the intensity maps (above; 2D: gz == 1; 1 .. MVS_FIELD_MAX_NODES per axis) with one displacement vector d per cell,
+ * in pixels of that view, in axis order z, y, x.  The displacements are fitted on the host from the shifts that block matching
+ * finds in the overlaps (mvs_block_match) and applied to whole tiles by mvs_field_warp.
+ *
+ * mvs_block_match: for every box ("block") of the overlap grid of a pair and every integer shift s of a search window, the six
+ * moments of the sample pairs (f(g), m(g + s)), g in the block.  Views (uint8 / uint16 / float32, one dtype for both, else
+ * MVS_ERR_UNSUPPORTED; host or device memory; strided windows with stride[2] == 1), halfspaces and the meaning of matrix / offset
+ * (grid index -> pixel of the tile) are those of mvs_pair_moments.  A block is lo[k] <= index[k] < lo[k] + n[k] (z, y, x; 2D:
+ * lo[0] == 0, n[0] == 1, radius[0] == 0).  0 <= radius[k] <= MVS_BLOCKMATCH_MAX_RADIUS and, per block, prod n + prod (n + 2 r) <=
+ * MVS_BLOCKMATCH_MAX_FLOATS, else MVS_ERR_UNSUPPORTED.  1 <= n_blocks <= MVS_BLOCKMATCH_MAX_BLOCKS and n_blocks * S * 48 bytes <=
+ * MVS_BLOCKMATCH_MAX_RESULT_BYTES, else MVS_ERR_INVALID_ARG: callers batch.
+ * out (host memory): n_blocks * S * MVS_PAIR_MOMENTS_LEN doubles, S = prod (2 r_k + 1); the shift index runs z slowest and x
+ * fastest, each axis from -r_k to r_k.  Row (block, s) = (n, mean_f, mean_m, M2_f, M2_m, C_fm) over the pairs (f(g), m(g + s)).  A
+ * pair is counted iff every halfspace holds at g, the fixed coordinate of g is in bounds and f is finite, and the moving coordinate
+ * of the integer grid point g + s is in bounds and m is finite (the halfspaces are not tested at g + s).  All six are 0 when n == 0.
+ * Coordinates and samples follow the per-voxel rule of mvs_pair_moments (double, no contraction, float32 linear sample; the same
+ * device code), so a moving sample depends on g + s only.
+ * One workgroup of 4 waves per block.  Every sample of the block and of the block grown by r on every side is taken once and
+ * kept in LDS (x fastest; NaN marks "not counted"); wave w takes the shifts w, w + 4, ...; for one shift lane l folds the block
+ * voxels l, l + 64, ... in index order into sums shifted by its first counted pair, then the lanes merge by the update of Chan,
+ * Golub and LeVeque in the fixed shuffle tree of mvs_pair_moments.  No atomics, no completion counters, no second launch; a
+ * block's rows do not depend on the other blocks of the call and equal inputs give equal bits.  Waits for the result; runs on the
+ * lane of `device`. */
+#define MVS_BLOCKMATCH_MAX_RADIUS 8
+#define MVS_BLOCKMATCH_MAX_FLOATS 15360   /* block + grown moving block in LDS: 60 KB, static */
+#define MVS_BLOCKMATCH_MAX_BLOCKS 4096    /* per call; the wrapper batches, also so that the result stays <= 64 MiB */
+#define MVS_BLOCKMATCH_MAX_RESULT_BYTES (64 << 20)
+typedef struct { int64_t lo[3], n[3]; } mvs_block_t;
+int mvs_block_match(int device, const mvs_view_t* fixed, const mvs_view_t* moving, int32_t ndim,
+                    const double* halfspaces, int32_t n_halfspaces, const mvs_block_t* blocks,
+                    int32_t n_blocks, const int32_t radius[3], double* out);
+
+/* mvs_field_warp: out(p) = view(clamp(p + d(p), 0, n - 1)), read with the linear sampler of mvs_resample.  Only data / dtype / mem /
+ * shape / stride of `view` are read (uint8 / uint16 / float32; host C-contiguous, or device with stride[2] == 1).  field (host):
+ * (gz, gy, gx, 3) float32, (d_z, d_y, d_x) per cell, all finite (else MVS_ERR_INVALID_ARG); in 2D the z component is ignored
+ * (taken as 0).  tables (host): the per-axis tables of mvs_intensity_apply (lower cell i and weight t of cell i + 1 per pixel
+ * index; the upper cell is min(i + 1, g - 1)).
+ * Arithmetic: d is interpolated in float32 without contraction, lerp(u, v, t) = u + t * (v - u), per component: per row (z, y)
+ * along z, then along y -- lerp(lerp(d[z0][y0], d[z1][y0], tz), lerp(d[z0][y1], d[z1][y1], tz), ty) -- and per voxel along x.  The
+ * coordinate is c_k = min(max((double)p_k + (double)d_k, 0), n_k - 1) per axis and the value the linear float32 sample at c with
+ * all taps read (a NaN tap poisons a float32 sample; a zero field returns finite input bits).  A float32 output stores the value
+ * (NaN stays NaN); an integer output stores rintf(value) (half to even) saturated to the type's range, a NaN as 0.
+ * out: C-contiguous, shape of the view, in out_mem; out_dtype is the view's dtype or float32 (else MVS_ERR_UNSUPPORTED).  The
+ * kernel gathers: when out overlaps the view's memory the call returns MVS_ERR_INVALID_ARG.  One wave per row, four rows per
+ * workgroup: the row's gx displacement vectors in LDS, then every lane interpolates along x and gathers; stores of 16 bytes per
+ * lane from the row's first 16-byte aligned output element on, with a scalar head and tail.  Waits for the result; runs on the
+ * lane of `device`. */
+#define MVS_FIELD_MAX_NODES 16
+int mvs_field_warp(int device, const mvs_view_t* view, int32_t ndim, const int32_t nodes[3],
+                   const float* field, const void* tables, void* out, int32_t out_dtype, int32_t out_mem);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,11 @@ MVS_INTENSITY_MAX_RECORDS = 1024
 MVS_INTENSITY_BLOCK_VOXELS = 256
 MVS_INTENSITY_MAX_BLOCKS = 1024
 MVS_STACK_MAX_VIEWS = 4096
+MVS_BLOCKMATCH_MAX_RADIUS = 8
+MVS_BLOCKMATCH_MAX_FLOATS = 15360
+MVS_BLOCKMATCH_MAX_BLOCKS = 4096
+MVS_BLOCKMATCH_MAX_RESULT_BYTES = 64 << 20
+MVS_FIELD_MAX_NODES = 16
 MVS_STACK_MAX_QUANTILES = 4
 ERR_UNSUPPORTED = -4            # MVS_ERR_UNSUPPORTED
 
@@ -120,6 +125,13 @@ class mvs_intensity_record_t(C.Structure):
         ("n", C.c_int64 * 3),
         ("cell_f", C.c_int32 * 3),
         ("cell_m", C.c_int32 * 3),
+    ]
+
+
+class mvs_block_t(C.Structure):
+    _fields_ = [
+        ("lo", C.c_int64 * 3),
+        ("n", C.c_int64 * 3),
     ]
 
 
@@ -321,6 +333,15 @@ SIGNATURES = {
     "mvs_plane_apply": (
         C.c_int,
         [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32],
+    ),
+    "mvs_block_match": (
+        C.c_int,
+        [C.c_int, C.POINTER(mvs_view_t), C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_double), C.c_int32, C.POINTER(mvs_block_t), C.c_int32,
+         C.POINTER(C.c_int32), C.POINTER(C.c_double)],
+    ),
+    "mvs_field_warp": (
+        C.c_int,
+        [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32],
     ),
 }
 

@@ -285,19 +285,10 @@ extern "C" int mvs_intensity_apply(int device, const mvs_view_t* view, int32_t n
         static_cast<TileApplyArgs&>(P) = A;
         P.gz = cells[0]; P.gy = cells[1]; P.gx = cells[2];
         // coefficients and tables: scratch slot 2 (tables: per axis z, y, x the int32 lower cell of every pixel, then its float32 weight)
-        const size_t coeff_bytes = sizeof(float) * 2 * (size_t)cells[0] * cells[1] * cells[2];
-        const size_t table_bytes = 8 * ((size_t)P.nz + P.ny + P.nx);
-        char* small = (char*)mvs_scratch(c, 2, align_up(coeff_bytes) + table_bytes);
-        if (!small) return mvs_alloc_failed(c);
-        MVS_HIP_TRY(c, hipMemcpyAsync(small, coeff, coeff_bytes, hipMemcpyHostToDevice, c->stream));
-        MVS_HIP_TRY(c, hipMemcpyAsync(small + align_up(coeff_bytes), tables, table_bytes, hipMemcpyHostToDevice, c->stream));
-        P.coeff = (const float*)small;
-        char* t = small + align_up(coeff_bytes);
-        for (int k = 0; k < 3; ++k) {
-            P.cell[k] = (const int*)t;
-            P.frac[k] = (const float*)(t + 4 * (size_t)view->shape[k]);
-            t += 8 * (size_t)view->shape[k];
-        }
+        const void* dcoeff = nullptr;
+        const int rc2 = mvs_tile_apply_tables(c, view, coeff, sizeof(float) * 2 * (size_t)cells[0] * cells[1] * cells[2], tables, &dcoeff, P.cell, P.frac);
+        if (rc2) return rc2;
+        P.coeff = (const float*)dcoeff;
         const long long rows = (long long)P.nz * P.ny;
         nblocks = (int)std::min<long long>((rows + kApplyRows - 1) / kApplyRows, kApplyMaxBlocks);
         return MVS_OK;

@@ -51,6 +51,26 @@ struct TileApplyArgs {
     int nz, ny, nx;
 };
 
+// For the `prepare` of the entries that interpolate per-cell values (mvs_intensity_apply, mvs_field_warp): the host's `values`
+// (value_bytes of them) and its per-axis `tables` -- for z, y, x in turn shape[k] int32 lower cells, then shape[k] float32 weights
+// -- through scratch slot 2.  *dvalues, cell[k] and frac[k] are where the kernel reads them.
+inline int mvs_tile_apply_tables(MvsContext* c, const mvs_view_t* view, const void* values, size_t value_bytes, const void* tables, const void** dvalues,
+                                 const int* cell[3], const float* frac[3]) {
+    const size_t table_bytes = 8 * ((size_t)view->shape[0] + view->shape[1] + view->shape[2]);
+    char* small = (char*)mvs_scratch(c, 2, align_up(value_bytes) + table_bytes);
+    if (!small) return mvs_alloc_failed(c);
+    MVS_HIP_TRY(c, hipMemcpyAsync(small, values, value_bytes, hipMemcpyHostToDevice, c->stream));
+    MVS_HIP_TRY(c, hipMemcpyAsync(small + align_up(value_bytes), tables, table_bytes, hipMemcpyHostToDevice, c->stream));
+    *dvalues = small;
+    char* t = small + align_up(value_bytes);
+    for (int k = 0; k < 3; ++k) {
+        cell[k] = (const int*)t;
+        frac[k] = (const float*)(t + 4 * (size_t)view->shape[k]);
+        t += 8 * (size_t)view->shape[k];
+    }
+    return MVS_OK;
+}
+
 // One apply entry point after its own refusals: the refusals both share, the context, the tile through scratch slot 0, the output
 // (scratch slot 1 for a host result), `prepare(c, args)` for the entry's coefficients and launch geometry (scratch slot 2 is
 // its), the timed `launch(tin, tout)` with tout of the input's type or float, and the download.
