@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._metric_ops import box3, moments_in_groups, pair_call_views
 from .transformation import shape3, tile_view
 
 
@@ -38,13 +39,6 @@ def axis_table(n, g):
     return lower.astype(np.int32), (u - lower).astype(np.float32)
 
 
-def _i32x3(vals, ndim, fill):
-    vals = [int(v) for v in vals]
-    if len(vals) != ndim:
-        raise ValueError(f"expected {ndim} values, got {len(vals)}")
-    return (C.c_int32 * 3)(*([fill] * (3 - ndim) + vals))
-
-
 def cell_pair_moments(fixed, moving, fixed_affine, moving_affine, cells_f, cells_m, records, halfspaces=None, device=0, batch=None):
     """Moments of the sample pairs of two tiles per record (mvs_intensity_pair_moments): an ``(R, 6)`` float64 array with the rows
     ``(n, mean_f, mean_m, M2_f, M2_m, C_fm)``.
@@ -62,32 +56,19 @@ def cell_pair_moments(fixed, moving, fixed_affine, moving_affine, cells_f, cells
     batch = _lib.MVS_INTENSITY_MAX_RECORDS if batch is None else int(batch)
     if not 1 <= batch <= _lib.MVS_INTENSITY_MAX_RECORDS:
         raise ValueError(f"batch must be 1..{_lib.MVS_INTENSITY_MAX_RECORDS}")
-    fview, keep_f = tile_view(fixed, fixed_affine[0], fixed_affine[1], device)
-    mview, keep_m = tile_view(moving, moving_affine[0], moving_affine[1], device)
-    hs = np.zeros((0, ndim + 1)) if halfspaces is None else np.asarray(halfspaces, dtype=np.float64).reshape(-1, ndim + 1)
-    if len(hs) > _lib.MVS_PAIR_MAX_HALFSPACES:
-        raise ValueError(f"at most {_lib.MVS_PAIR_MAX_HALFSPACES} halfspaces")
-    hs3 = np.zeros((len(hs), 4))
-    hs3[:, 3 - ndim:] = hs                       # 2-D: a_z = 0
-    cf, cm = _i32x3(cells_f, ndim, 1), _i32x3(cells_m, ndim, 1)
-    out = np.zeros((len(records), _lib.MVS_PAIR_MOMENTS_LEN))
-    dp = C.POINTER(C.c_double)
-    k = 3 - ndim
-    for r0 in range(0, len(records), batch):
-        group = records[r0:r0 + batch]
+    fview, mview, hs_ptr, n_hs, keep = pair_call_views(fixed, moving, fixed_affine, moving_affine, halfspaces, ndim, device)
+    cf, cm = _lib.i32x3(cells_f, ndim, 1), _lib.i32x3(cells_m, ndim, 1)
+
+    def call(group):
         recs = (_lib.mvs_intensity_record_t * len(group))()
-        for rec, row in zip(recs, group):
-            rec.lo[:] = [0] * k + row[0].tolist()
-            rec.n[:] = [1] * k + row[1].tolist()
-            rec.cell_f[:] = [0] * k + row[2].tolist()
-            rec.cell_m[:] = [0] * k + row[3].tolist()
+        for rec, row in zip(recs, box3(group, (0, 1, 0, 0))):
+            rec.lo[:], rec.n[:], rec.cell_f[:], rec.cell_m[:] = row
         res = np.zeros((len(group), _lib.MVS_PAIR_MOMENTS_LEN))
-        rc = lib.mvs_intensity_pair_moments(device, C.byref(fview), C.byref(mview), ndim, cf, cm, hs3.ctypes.data_as(dp) if len(hs3) else None,
-                                            len(hs3), recs, len(group), res.ctypes.data_as(dp))
-        _lib.check(rc, device, "mvs_intensity_pair_moments")
-        out[r0:r0 + len(group)] = res
-    del keep_f, keep_m
-    return out
+        _lib.check(lib.mvs_intensity_pair_moments(device, C.byref(fview), C.byref(mview), ndim, cf, cm, hs_ptr, n_hs, recs, len(group),
+                                                  res.ctypes.data_as(C.POINTER(C.c_double))), device, "mvs_intensity_pair_moments")
+        return res
+
+    return moments_in_groups(records, batch, call)      # (`keep` lives until here)
 
 
 def apply_to_tile(name, data, out, out_dtype, device, call):
@@ -137,4 +118,4 @@ def apply_map(data, coeff, out=None, out_dtype=None, device=0):
     cells = coeff.shape[:-1]
     tables = np.concatenate([part.view(np.uint8) for n, g in zip(shape3(data.shape), shape3(cells)) for part in axis_table(n, g)])
     return apply_to_tile("mvs_intensity_apply", data, out, out_dtype, device, lambda view, out_ptr, out_code, out_mem: lib.mvs_intensity_apply(
-        device, view, ndim, _i32x3(cells, ndim, 1), coeff.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(tables.ctypes.data), out_ptr, out_code, out_mem))
+        device, view, ndim, _lib.i32x3(cells, ndim, 1), coeff.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(tables.ctypes.data), out_ptr, out_code, out_mem))

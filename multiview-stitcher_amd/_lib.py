@@ -411,6 +411,13 @@ def i64x3(vals):
     return (C.c_int64 * 3)(*[int(v) for v in vals])
 
 
+def i32x3(vals, ndim, fill):      # ``fill`` along the z that a 2-D call lacks
+    vals = [int(v) for v in vals]
+    if len(vals) != ndim:
+        raise ValueError(f"expected {ndim} values, got {len(vals)}")
+    return (C.c_int32 * 3)(*([fill] * (3 - ndim) + vals))
+
+
 def synchronize(device=0):
     """Block until all work queued on the context's stream has finished (mvs_synchronize)."""
     check(init(device).mvs_synchronize(int(device)), device, "mvs_synchronize")

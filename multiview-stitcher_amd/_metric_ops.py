@@ -1,5 +1,5 @@
-"""Thin array-level wrapper of the registration metrics entry point of libmvs_hip.so (mvs_pair_moments) and the NCC its moments
-give."""
+"""Thin array-level wrapper of the registration metrics entry point of libmvs_hip.so (mvs_pair_moments), the NCC its moments give,
+and the call frame it shares with the other pair-moment wrappers (``_intensity_ops.cell_pair_moments``, ``_nonrigid_ops.block_match``)."""
 
 from __future__ import annotations
 
@@ -10,6 +10,42 @@ import numpy as np
 
 from . import _lib
 from .transformation import embed3, shape3, tile_view
+
+_DP = C.POINTER(C.c_double)
+
+
+def pair_call_views(fixed, moving, fixed_affine, moving_affine, halfspaces, ndim, device):
+    """``(fview, mview, hs_ptr, n_hs, keep)``: the ``tile_view`` of both tiles, the halfspace rows ``(a.., b)`` embedded as
+    ``(a_z, a_y, a_x, b)`` (2-D: ``a_z = 0``) behind a double pointer (None without halfspaces), their count, and what must stay
+    alive until the last call has returned (its last item is the embedded array)."""
+    fview, keep_f = tile_view(fixed, fixed_affine[0], fixed_affine[1], device)
+    mview, keep_m = tile_view(moving, moving_affine[0], moving_affine[1], device)
+    hs = np.zeros((0, ndim + 1)) if halfspaces is None else np.asarray(halfspaces, dtype=np.float64).reshape(-1, ndim + 1)
+    if len(hs) > _lib.MVS_PAIR_MAX_HALFSPACES:
+        raise ValueError(f"at most {_lib.MVS_PAIR_MAX_HALFSPACES} halfspaces")
+    hs3 = np.zeros((len(hs), 4))
+    hs3[:, 3 - ndim:] = hs
+    return fview, mview, hs3.ctypes.data_as(_DP) if len(hs3) else None, len(hs3), (keep_f, keep_m, hs3)
+
+
+def moments_in_groups(rows, batch, call, per_row=()):
+    """``call(group) -> moments`` over groups of at most ``batch`` consecutive ``rows``: the zero-filled float64 array
+    ``(N,) + per_row + (6,)`` of all of them, in input order."""
+    out = np.zeros((len(rows),) + tuple(per_row) + (_lib.MVS_PAIR_MOMENTS_LEN,))
+    for i0 in range(0, len(rows), batch):
+        out[i0:i0 + batch] = call(rows[i0:i0 + batch])
+    return out
+
+
+def box3(rows, fill=(0, 1)):
+    """Integer rows ``(..., R, ndim)`` of 2-D or 3-D calls on three axes, as nested lists: row ``r`` gets ``fill[r]`` along the z that
+    a 2-D row lacks (boxes ``lo, n``: 0 and 1).  One call per group: conversions per record are what a large group spends its time in."""
+    rows = np.asarray(rows)
+    if rows.shape[-1] == 3:
+        return rows.tolist()
+    out = np.empty(rows.shape[:-1] + (3,), dtype=np.int64)
+    out[..., 0], out[..., 1:] = fill, rows
+    return out.tolist()
 
 
 def pair_moments(fixed, moving, fixed_affine, cand_affines, grid_shape, halfspaces=None, device=0):
@@ -26,28 +62,18 @@ def pair_moments(fixed, moving, fixed_affine, cand_affines, grid_shape, halfspac
     ndim = len(grid_shape)
     if ndim not in (2, 3):
         raise ValueError("pair_moments needs a 2-D or 3-D grid")
-    fview, keep_f = tile_view(fixed, fixed_affine[0], fixed_affine[1], device)
-    mview, keep_m = tile_view(moving, np.eye(ndim), np.zeros(ndim), device)
-    hs = np.zeros((0, ndim + 1)) if halfspaces is None else np.asarray(halfspaces, dtype=np.float64).reshape(-1, ndim + 1)
-    if len(hs) > _lib.MVS_PAIR_MAX_HALFSPACES:
-        raise ValueError(f"at most {_lib.MVS_PAIR_MAX_HALFSPACES} halfspaces")
-    hs3 = np.zeros((len(hs), 4))
-    hs3[:, 3 - ndim:] = hs                       # 2-D: a_z = 0
+    fview, mview, hs_ptr, n_hs, keep = pair_call_views(fixed, moving, fixed_affine, (np.eye(ndim), np.zeros(ndim)), halfspaces, ndim, device)
     embedded = [embed3(np.asarray(m, dtype=np.float64), np.asarray(o, dtype=np.float64)) for m, o in cand_affines]
-    out = np.zeros((len(embedded), _lib.MVS_PAIR_MOMENTS_LEN))
-    dp = C.POINTER(C.c_double)
-    for k0 in range(0, len(embedded), _lib.MVS_PAIR_MAX_CANDIDATES):
-        group = embedded[k0:k0 + _lib.MVS_PAIR_MAX_CANDIDATES]
+
+    def call(group):
         cm = np.ascontiguousarray([m.reshape(9) for m, _ in group], dtype=np.float64)
         co = np.ascontiguousarray([o for _, o in group], dtype=np.float64)
         res = np.zeros((len(group), _lib.MVS_PAIR_MOMENTS_LEN))
-        rc = lib.mvs_pair_moments(device, C.byref(fview), C.byref(mview), len(group), cm.ctypes.data_as(dp), co.ctypes.data_as(dp), ndim,
-                                  _lib.i64x3(shape3(grid_shape)), hs3.ctypes.data_as(dp) if len(hs3) else None, len(hs3),
-                                  res.ctypes.data_as(dp))
-        _lib.check(rc, device, "mvs_pair_moments")
-        out[k0:k0 + len(group)] = res
-    del keep_f, keep_m
-    return out
+        _lib.check(lib.mvs_pair_moments(device, C.byref(fview), C.byref(mview), len(group), cm.ctypes.data_as(_DP), co.ctypes.data_as(_DP), ndim,
+                                        _lib.i64x3(shape3(grid_shape)), hs_ptr, n_hs, res.ctypes.data_as(_DP)), device, "mvs_pair_moments")
+        return res
+
+    return moments_in_groups(embedded, _lib.MVS_PAIR_MAX_CANDIDATES, call)      # (`keep` lives until here)
 
 
 def ncc_from_moments(m):

@@ -8,8 +8,9 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._intensity_ops import _i32x3, apply_to_tile, axis_table
-from .transformation import shape3, tile_view
+from ._intensity_ops import apply_to_tile, axis_table
+from ._metric_ops import box3, moments_in_groups, pair_call_views
+from .transformation import shape3
 
 
 def n_shifts(radius):
@@ -37,30 +38,19 @@ def block_match(fixed, moving, fixed_affine, moving_affine, blocks, radius, half
     batch = limit if batch is None else int(batch)
     if not 1 <= batch <= limit:
         raise ValueError(f"batch must be 1..{limit}")
-    fview, keep_f = tile_view(fixed, fixed_affine[0], fixed_affine[1], device)
-    mview, keep_m = tile_view(moving, moving_affine[0], moving_affine[1], device)
-    hs = np.zeros((0, ndim + 1)) if halfspaces is None else np.asarray(halfspaces, dtype=np.float64).reshape(-1, ndim + 1)
-    if len(hs) > _lib.MVS_PAIR_MAX_HALFSPACES:
-        raise ValueError(f"at most {_lib.MVS_PAIR_MAX_HALFSPACES} halfspaces")
-    hs3 = np.zeros((len(hs), 4))
-    hs3[:, 3 - ndim:] = hs                       # 2-D: a_z = 0
-    r3 = _i32x3(radius, ndim, 0)
-    out = np.zeros((len(blocks), S, _lib.MVS_PAIR_MOMENTS_LEN))
-    dp = C.POINTER(C.c_double)
-    k = 3 - ndim
-    for b0 in range(0, len(blocks), batch):
-        group = blocks[b0:b0 + batch]
+    fview, mview, hs_ptr, n_hs, keep = pair_call_views(fixed, moving, fixed_affine, moving_affine, halfspaces, ndim, device)
+    r3 = _lib.i32x3(radius, ndim, 0)
+
+    def call(group):
         recs = (_lib.mvs_block_t * len(group))()
-        for rec, row in zip(recs, group):
-            rec.lo[:] = [0] * k + row[0].tolist()
-            rec.n[:] = [1] * k + row[1].tolist()
+        for rec, row in zip(recs, box3(group[:, :2])):
+            rec.lo[:], rec.n[:] = row
         res = np.zeros((len(group), S, _lib.MVS_PAIR_MOMENTS_LEN))
-        rc = lib.mvs_block_match(device, C.byref(fview), C.byref(mview), ndim, hs3.ctypes.data_as(dp) if len(hs3) else None, len(hs3), recs,
-                                 len(group), r3, res.ctypes.data_as(dp))
-        _lib.check(rc, device, "mvs_block_match")
-        out[b0:b0 + len(group)] = res
-    del keep_f, keep_m
-    return out
+        _lib.check(lib.mvs_block_match(device, C.byref(fview), C.byref(mview), ndim, hs_ptr, n_hs, recs, len(group), r3, res.ctypes.data_as(C.POINTER(C.c_double))),
+                   device, "mvs_block_match")
+        return res
+
+    return moments_in_groups(blocks, batch, call, per_row=(S,))      # (`keep` lives until here)
 
 
 def warp_field(data, field, out=None, out_dtype=None, device=0):
@@ -81,4 +71,4 @@ def warp_field(data, field, out=None, out_dtype=None, device=0):
     field3[..., 3 - ndim:] = field.reshape(tuple(shape3(nodes)) + (ndim,))
     tables = np.concatenate([part.view(np.uint8) for n, g in zip(shape3(data.shape), shape3(nodes)) for part in axis_table(n, g)])
     return apply_to_tile("mvs_field_warp", data, out, out_dtype, device, lambda view, out_ptr, out_code, out_mem: lib.mvs_field_warp(
-        device, view, ndim, _i32x3(nodes, ndim, 1), field3.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(tables.ctypes.data), out_ptr, out_code, out_mem))
+        device, view, ndim, _lib.i32x3(nodes, ndim, 1), field3.ctypes.data_as(C.POINTER(C.c_float)), C.c_void_p(tables.ctypes.data), out_ptr, out_code, out_mem))

@@ -10,6 +10,7 @@
 #include "mvs_internal.h"
 #include "mvs_fuse_dev.h"
 #include "mvs_pair_voxel_dev.h"
+#include "mvs_pair_frame.h"
 #include "mvs_intensity_dev.h"
 #include "mvs_tile_apply.h"
 
@@ -89,17 +90,11 @@ __global__ __launch_bounds__(kPairBlockThreads) void intensity_moments_kernel(In
     }
 }
 
-// One wave per record: lane l folds its run of ceil(nb / 64) consecutive workgroup results of the record in index order, then the
-// lanes merge in the tree of wave_merge -- the fold of pair_moments_fold_kernel, per record.
+// One wave per record folds the results of the record's workgroups (pair_moments_fold, mvs_pair_voxel_dev.h).
 __global__ __launch_bounds__(64) void intensity_fold_kernel(const PairMoments* partial, const int* first_block, PairMoments* out) {
-    const int r = blockIdx.x, lane = threadIdx.x;
-    const int b0 = first_block[r], nb = first_block[r + 1] - b0;
-    const int run = (nb + 63) / 64;
-    const int lo = lane * run, hi = min(lo + run, nb);
-    PairMoments m = pair_moments_empty();
-    for (int i = lo; i < hi; ++i) m = pair_moments_merge(m, partial[b0 + i]);
-    m = wave_merge(m);
-    if (lane == 0) out[r] = m;
+    const int r = blockIdx.x, b0 = first_block[r];
+    const PairMoments m = pair_moments_fold(partial + b0, 1, first_block[r + 1] - b0, threadIdx.x);
+    if (threadIdx.x == 0) out[r] = m;
 }
 
 // ---- apply ------------------------------------------------------------------------------------------------------------------------
@@ -197,18 +192,14 @@ extern "C" int mvs_intensity_pair_moments(int device, const mvs_view_t* fixed, c
     const char* what = "mvs_intensity_pair_moments";
     MvsContext* c0 = mvs_ctx(device);
     if (!fixed || !moving || !cells_f || !cells_m || !records || !out) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: NULL argument", what);
-    if (ndim != 2 && ndim != 3) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: ndim must be 2 or 3", what);
-    if (n_halfspaces < 0 || n_halfspaces > MVS_PAIR_MAX_HALFSPACES || (n_halfspaces > 0 && !halfspaces))
-        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: n_halfspaces must be 0..%d (with their equations)", what, MVS_PAIR_MAX_HALFSPACES);
+    int rc = mvs_pair_check_counts(c0, what, ndim, halfspaces, n_halfspaces);
+    if (rc) return rc;
     if (n_records < 1 || n_records > MVS_INTENSITY_MAX_RECORDS)
         return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: n_records must be 1..%d", what, MVS_INTENSITY_MAX_RECORDS);
-    int rc = check_cells(c0, what, cells_f, ndim);
+    rc = check_cells(c0, what, cells_f, ndim);
     if (!rc) rc = check_cells(c0, what, cells_m, ndim);
-    if (!rc) rc = mvs_check_tile_view(c0, what, fixed, ndim);
-    if (!rc) rc = mvs_check_tile_view(c0, what, moving, ndim);
+    if (!rc) rc = mvs_pair_check_views(c0, what, fixed, moving, ndim);
     if (rc) return rc;
-    if (fixed->dtype != moving->dtype)
-        return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "%s: the views must share one dtype (%d and %d given)", what, fixed->dtype, moving->dtype);
     std::vector<int> first_block((size_t)n_records + 1);
     first_block[0] = 0;
     for (int r = 0; r < n_records; ++r) {
@@ -222,52 +213,30 @@ extern "C" int mvs_intensity_pair_moments(int device, const mvs_view_t* fixed, c
         if ((double)R.n[0] * (double)R.n[1] * (double)R.n[2] > 9e15) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: record %d: box too large", what, r);
         first_block[r + 1] = first_block[r] + record_blocks(R);
     }
-    MvsContext* c;
-    rc = mvs_check_ready(device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
-
     IntensityArgs P;
-    const mvs_view_t* both[2] = {fixed, moving};
-    DevView* dv[2] = {&P.fixed, &P.moving};
-    rc = mvs_stage_tile_views(c, both, 2, ndim, nullptr, dv);
-    if (rc) return rc;
-    if (n_halfspaces) memcpy(P.hs, halfspaces, sizeof(double) * 4 * n_halfspaces);
-    P.n_hs = n_halfspaces;
     P.n_records = n_records;
-    for (int k = 0; k < 3; ++k) {
-        P.cells_f[k] = cells_f[k];
-        P.cells_m[k] = cells_m[k];
-    }
-
+    memcpy(P.cells_f, cells_f, sizeof(P.cells_f));
+    memcpy(P.cells_m, cells_m, sizeof(P.cells_m));
     const int total_blocks = first_block[n_records];
-    const size_t rec_bytes = align_up(sizeof(mvs_intensity_record_t) * (size_t)n_records), fb_bytes = align_up(sizeof(int) * ((size_t)n_records + 1));
-    char* tables = (char*)mvs_scratch(c, 2, rec_bytes + fb_bytes);
-    if (!tables) return mvs_alloc_failed(c);
-    P.recs = (const mvs_intensity_record_t*)tables;
-    P.first_block = (const int*)(tables + rec_bytes);
-    P.partial = (PairMoments*)mvs_scratch(c, 1, sizeof(PairMoments) * (size_t)total_blocks);
-    if (!P.partial) return mvs_alloc_failed(c);
-    void *mb_host = nullptr, *mb_dev = nullptr;
-    rc = mvs_mailbox(c, sizeof(PairMoments) * (size_t)n_records, &mb_host, &mb_dev);
-    if (rc) return rc;
-
-    // (pageable sources: both copies have left the host buffers when the calls return)
-    MVS_HIP_TRY(c, hipMemcpyAsync(tables, records, sizeof(mvs_intensity_record_t) * (size_t)n_records, hipMemcpyHostToDevice, c->stream));
-    MVS_HIP_TRY(c, hipMemcpyAsync(tables + rec_bytes, first_block.data(), sizeof(int) * ((size_t)n_records + 1), hipMemcpyHostToDevice, c->stream));
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    mvs_dispatch_dtype(fixed->dtype, [&](auto tag) {
-        hipLaunchKernelGGL((intensity_moments_kernel<decltype(tag)>), dim3(total_blocks), dim3(kPairBlockThreads), 0, c->stream, P);
-    });
-    MVS_HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(intensity_fold_kernel, dim3(n_records), dim3(64), 0, c->stream, (const PairMoments*)P.partial, P.first_block, (PairMoments*)mb_dev);
-    MVS_HIP_TRY(c, hipGetLastError());
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->timing_valid = true;
-    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    memcpy(out, mb_host, sizeof(PairMoments) * (size_t)n_records);
-    return MVS_OK;
+    const size_t out_bytes = sizeof(PairMoments) * (size_t)n_records;
+    auto prepare = [&](MvsContext* c, void** host, void** dev) -> int {
+        const size_t rec_bytes = align_up(sizeof(mvs_intensity_record_t) * (size_t)n_records), fb_bytes = align_up(sizeof(int) * ((size_t)n_records + 1));
+        char* tables = (char*)mvs_scratch(c, 2, rec_bytes + fb_bytes);
+        if (!tables) return mvs_alloc_failed(c);
+        P.recs = (const mvs_intensity_record_t*)tables;
+        P.first_block = (const int*)(tables + rec_bytes);
+        P.partial = (PairMoments*)mvs_scratch(c, 1, sizeof(PairMoments) * (size_t)total_blocks);
+        if (!P.partial) return mvs_alloc_failed(c);
+        const int rc2 = mvs_mailbox(c, out_bytes, host, dev);
+        if (rc2) return rc2;
+        // (pageable sources: both copies have left the host buffers when the calls return)
+        MVS_HIP_TRY(c, hipMemcpyAsync(tables, records, sizeof(mvs_intensity_record_t) * (size_t)n_records, hipMemcpyHostToDevice, c->stream));
+        MVS_HIP_TRY(c, hipMemcpyAsync(tables + rec_bytes, first_block.data(), sizeof(int) * ((size_t)n_records + 1), hipMemcpyHostToDevice, c->stream));
+        return MVS_OK;
+    };
+    return mvs_pair_frame(device, fixed, moving, ndim, halfspaces, n_halfspaces, P, out, out_bytes, prepare,
+        [&](auto tag, hipStream_t s) { hipLaunchKernelGGL((intensity_moments_kernel<decltype(tag)>), dim3(total_blocks), dim3(kPairBlockThreads), 0, s, P); },
+        [&](hipStream_t s, void* dev) { hipLaunchKernelGGL(intensity_fold_kernel, dim3(n_records), dim3(64), 0, s, (const PairMoments*)P.partial, P.first_block, (PairMoments*)dev); });
 }
 
 extern "C" int mvs_intensity_apply(int device, const mvs_view_t* view, int32_t ndim, const int32_t cells[3], const float* coeff, const void* tables,

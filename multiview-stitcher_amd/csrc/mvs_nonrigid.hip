@@ -10,6 +10,7 @@
 #include "mvs_internal.h"
 #include "mvs_fuse_dev.h"
 #include "mvs_pair_voxel_dev.h"
+#include "mvs_pair_frame.h"
 #include "mvs_intensity_dev.h"
 #include "mvs_tile_apply.h"
 
@@ -194,9 +195,8 @@ extern "C" int mvs_block_match(int device, const mvs_view_t* fixed, const mvs_vi
     const char* what = "mvs_block_match";
     MvsContext* c0 = mvs_ctx(device);
     if (!fixed || !moving || !blocks || !radius || !out) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: NULL argument", what);
-    if (ndim != 2 && ndim != 3) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: ndim must be 2 or 3", what);
-    if (n_halfspaces < 0 || n_halfspaces > MVS_PAIR_MAX_HALFSPACES || (n_halfspaces > 0 && !halfspaces))
-        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: n_halfspaces must be 0..%d (with their equations)", what, MVS_PAIR_MAX_HALFSPACES);
+    int rc = mvs_pair_check_counts(c0, what, ndim, halfspaces, n_halfspaces);
+    if (rc) return rc;
     long long S = 1;
     for (int k = 0; k < 3; ++k) {
         if (radius[k] < 0 || (k < 3 - ndim && radius[k] != 0)) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: radius[%d] = %d (0 along z in 2D)", what, k, (int)radius[k]);
@@ -207,11 +207,8 @@ extern "C" int mvs_block_match(int device, const mvs_view_t* fixed, const mvs_vi
     if (n_blocks < 1 || n_blocks > MVS_BLOCKMATCH_MAX_BLOCKS || (long long)n_blocks * S * (long long)sizeof(PairMoments) > MVS_BLOCKMATCH_MAX_RESULT_BYTES)
         return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: n_blocks must be 1..%d and the result at most %d bytes (%d blocks of %lld shifts given)", what,
                         MVS_BLOCKMATCH_MAX_BLOCKS, MVS_BLOCKMATCH_MAX_RESULT_BYTES, (int)n_blocks, S);
-    int rc = mvs_check_tile_view(c0, what, fixed, ndim);
-    if (!rc) rc = mvs_check_tile_view(c0, what, moving, ndim);
+    rc = mvs_pair_check_views(c0, what, fixed, moving, ndim);
     if (rc) return rc;
-    if (fixed->dtype != moving->dtype)
-        return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "%s: the views must share one dtype (%d and %d given)", what, fixed->dtype, moving->dtype);
     for (int b = 0; b < n_blocks; ++b) {
         const mvs_block_t& B = blocks[b];
         long long nf = 1, ng = 1;
@@ -225,39 +222,21 @@ extern "C" int mvs_block_match(int device, const mvs_view_t* fixed, const mvs_vi
         if (nf + ng > MVS_BLOCKMATCH_MAX_FLOATS)
             return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "%s: block %d: %lld + %lld samples exceed the %d that fit the LDS", what, b, nf, ng, MVS_BLOCKMATCH_MAX_FLOATS);
     }
-    MvsContext* c;
-    rc = mvs_check_ready(device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
-
     MatchArgs P;
-    const mvs_view_t* both[2] = {fixed, moving};
-    DevView* dv[2] = {&P.fixed, &P.moving};
-    rc = mvs_stage_tile_views(c, both, 2, ndim, nullptr, dv);
-    if (rc) return rc;
-    if (n_halfspaces) memcpy(P.hs, halfspaces, sizeof(double) * 4 * n_halfspaces);
-    P.n_hs = n_halfspaces;
     for (int k = 0; k < 3; ++k) P.r[k] = radius[k];
     const size_t block_bytes = sizeof(mvs_block_t) * (size_t)n_blocks, out_bytes = sizeof(PairMoments) * (size_t)n_blocks * (size_t)S;
-    void* dblocks = mvs_scratch(c, 2, block_bytes);
-    if (!dblocks) return mvs_alloc_failed(c);
-    P.blocks = (const mvs_block_t*)dblocks;
-    P.out = (PairMoments*)mvs_scratch(c, 1, out_bytes);
-    if (!P.out) return mvs_alloc_failed(c);
-
-    // (pageable source: the copy has left the host buffer when the call returns)
-    MVS_HIP_TRY(c, hipMemcpyAsync(dblocks, blocks, block_bytes, hipMemcpyHostToDevice, c->stream));
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    mvs_dispatch_dtype(fixed->dtype, [&](auto tag) {
-        hipLaunchKernelGGL((block_match_kernel<decltype(tag)>), dim3(n_blocks), dim3(kMatchThreads), 0, c->stream, P);
-    });
-    MVS_HIP_TRY(c, hipGetLastError());
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->timing_valid = true;
-    MVS_HIP_TRY(c, hipMemcpyAsync(out, P.out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return MVS_OK;
+    auto prepare = [&](MvsContext* c, void**, void** dev) -> int {
+        void* dblocks = mvs_scratch(c, 2, block_bytes);
+        if (!dblocks) return mvs_alloc_failed(c);
+        P.blocks = (const mvs_block_t*)dblocks;
+        P.out = (PairMoments*)mvs_scratch(c, 1, out_bytes);
+        if (!(*dev = P.out)) return mvs_alloc_failed(c);
+        // (pageable source: the copy has left the host buffer when the call returns)
+        MVS_HIP_TRY(c, hipMemcpyAsync(dblocks, blocks, block_bytes, hipMemcpyHostToDevice, c->stream));
+        return MVS_OK;
+    };
+    return mvs_pair_frame(device, fixed, moving, ndim, halfspaces, n_halfspaces, P, out, out_bytes, prepare,
+        [&](auto tag, hipStream_t s) { hipLaunchKernelGGL((block_match_kernel<decltype(tag)>), dim3(n_blocks), dim3(kMatchThreads), 0, s, P); }, [](hipStream_t, void*) {});
 }
 
 extern "C" int mvs_field_warp(int device, const mvs_view_t* view, int32_t ndim, const int32_t nodes[3], const float* field, const void* tables,

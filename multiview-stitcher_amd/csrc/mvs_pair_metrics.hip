@@ -13,6 +13,7 @@
 #include "mvs_internal.h"
 #include "mvs_fuse_dev.h"
 #include "mvs_pair_voxel_dev.h"
+#include "mvs_pair_frame.h"
 
 #include <algorithm>
 #include <cmath>
@@ -79,16 +80,10 @@ __global__ __launch_bounds__(kPairBlockThreads) void pair_moments_kernel(PairArg
     }
 }
 
-// One wave per candidate: lane l folds its run of ceil(n_records / 64) consecutive records in index order, then the lanes merge
-// in the tree of wave_merge -- every record's place in the tree is a function of (n_records, its index) only.
+// One wave per candidate folds the candidate's record of every workgroup (pair_moments_fold, mvs_pair_voxel_dev.h).
 __global__ __launch_bounds__(64) void pair_moments_fold_kernel(const PairMoments* records, int n_records, int n_cand, PairMoments* out) {
-    const int k = blockIdx.x, lane = threadIdx.x;
-    const int run = (n_records + 63) / 64;
-    const int lo = lane * run, hi = min(lo + run, n_records);
-    PairMoments r = pair_moments_empty();
-    for (int i = lo; i < hi; ++i) r = pair_moments_merge(r, records[(long long)i * n_cand + k]);
-    r = wave_merge(r);
-    if (lane == 0) out[k] = r;
+    const PairMoments r = pair_moments_fold(records + blockIdx.x, n_cand, n_records, threadIdx.x);
+    if (threadIdx.x == 0) out[blockIdx.x] = r;
 }
 
 template <typename T>
@@ -106,57 +101,34 @@ void launch_pair_moments(const PairArgs& P, int nblocks, hipStream_t s) {
 extern "C" int mvs_pair_moments(int device, const mvs_view_t* fixed, const mvs_view_t* moving, int32_t n_candidates,
                                 const double* cand_matrix, const double* cand_offset, int32_t ndim, const int64_t grid_shape[3],
                                 const double* halfspaces, int32_t n_halfspaces, double* out) {
+    const char* what = "mvs_pair_moments";
     MvsContext* c0 = mvs_ctx(device);
-    if (!fixed || !moving || !cand_matrix || !cand_offset || !grid_shape || !out)
-        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_pair_moments: NULL argument");
-    if (ndim != 2 && ndim != 3) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_pair_moments: ndim must be 2 or 3");
+    if (!fixed || !moving || !cand_matrix || !cand_offset || !grid_shape || !out) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: NULL argument", what);
+    if (ndim != 2 && ndim != 3) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: ndim must be 2 or 3", what);      // (here too: n_candidates comes before the halfspaces)
     if (n_candidates < 1 || n_candidates > MVS_PAIR_MAX_CANDIDATES)
-        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_pair_moments: n_candidates must be 1..%d", MVS_PAIR_MAX_CANDIDATES);
-    if (n_halfspaces < 0 || n_halfspaces > MVS_PAIR_MAX_HALFSPACES || (n_halfspaces > 0 && !halfspaces))
-        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_pair_moments: n_halfspaces must be 0..%d (with their equations)", MVS_PAIR_MAX_HALFSPACES);
+        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: n_candidates must be 1..%d", what, MVS_PAIR_MAX_CANDIDATES);
+    int rc = mvs_pair_check_counts(c0, what, ndim, halfspaces, n_halfspaces);
+    if (rc) return rc;
     for (int k = 0; k < 3; ++k)
         if (grid_shape[k] < 1 || grid_shape[k] > 0x7fffffffLL || (k < 3 - ndim && grid_shape[k] != 1))
-            return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_pair_moments: grid_shape must be positive (and 1 along z in 2D)");
-    const mvs_view_t* both[2] = {fixed, moving};
-    for (const mvs_view_t* v : both) {
-        const int rc = mvs_check_tile_view(c0, "mvs_pair_moments", v, ndim);
-        if (rc) return rc;
-    }
-    if (fixed->dtype != moving->dtype)
-        return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_pair_moments: the views must share one dtype (%d and %d given)", fixed->dtype, moving->dtype);
-    MvsContext* c;
-    int rc = mvs_check_ready(device, &c);
+            return mvs_fail(c0, MVS_ERR_INVALID_ARG, "%s: grid_shape must be positive (and 1 along z in 2D)", what);
+    rc = mvs_pair_check_views(c0, what, fixed, moving, ndim);
     if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
 
     PairArgs P;
-    DevView* dv[2] = {&P.fixed, &P.moving};
-    rc = mvs_stage_tile_views(c, both, 2, ndim, nullptr, dv);
-    if (rc) return rc;
     memcpy(P.cm, cand_matrix, sizeof(double) * 9 * n_candidates);
     memcpy(P.co, cand_offset, sizeof(double) * 3 * n_candidates);
-    if (n_halfspaces) memcpy(P.hs, halfspaces, sizeof(double) * 4 * n_halfspaces);
     P.n_cand = n_candidates;
-    P.n_hs = n_halfspaces;
     P.gz = (int)grid_shape[0]; P.gy = (int)grid_shape[1]; P.gx = (int)grid_shape[2];
-
     const long long n = (long long)grid_shape[0] * grid_shape[1] * grid_shape[2];
     const int nblocks = (int)std::min<long long>((n + kPairBlockThreads - 1) / kPairBlockThreads, kPairMaxBlocks);
-    P.records = (PairMoments*)mvs_scratch(c, 1, sizeof(PairMoments) * (size_t)nblocks * n_candidates);
-    if (!P.records) return mvs_alloc_failed(c);
-    void *mb_host = nullptr, *mb_dev = nullptr;
-    rc = mvs_mailbox(c, sizeof(PairMoments) * (size_t)n_candidates, &mb_host, &mb_dev);
-    if (rc) return rc;
-
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    mvs_dispatch_dtype(fixed->dtype, [&](auto tag) { launch_pair_moments<decltype(tag)>(P, nblocks, c->stream); });
-    MVS_HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(pair_moments_fold_kernel, dim3(n_candidates), dim3(64), 0, c->stream, P.records, nblocks, n_candidates, (PairMoments*)mb_dev);
-    MVS_HIP_TRY(c, hipGetLastError());
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->timing_valid = true;
-    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    memcpy(out, mb_host, sizeof(PairMoments) * (size_t)n_candidates);
-    return MVS_OK;
+    const size_t out_bytes = sizeof(PairMoments) * (size_t)n_candidates;
+    auto prepare = [&](MvsContext* c, void** host, void** dev) -> int {
+        P.records = (PairMoments*)mvs_scratch(c, 1, sizeof(PairMoments) * (size_t)nblocks * n_candidates);
+        if (!P.records) return mvs_alloc_failed(c);
+        return mvs_mailbox(c, out_bytes, host, dev);
+    };
+    return mvs_pair_frame(device, fixed, moving, ndim, halfspaces, n_halfspaces, P, out, out_bytes, prepare,
+        [&](auto tag, hipStream_t s) { launch_pair_moments<decltype(tag)>(P, nblocks, s); },
+        [&](hipStream_t s, void* dev) { hipLaunchKernelGGL(pair_moments_fold_kernel, dim3(n_candidates), dim3(64), 0, s, P.records, nblocks, n_candidates, (PairMoments*)dev); });
 }

@@ -53,6 +53,16 @@ def match_oracle(ndim, dtype_name):
     return no.block_moments(c["fixed"], c["moving"], c["fixed_affine"], c["moving_affine"], c["blocks"], c["radius"], c["halfspaces"])
 
 
+def largest_block(grid, limit=7680):
+    """``(1, 2, ndim)`` blocks with the largest box at ``lo = 0`` of ``grid`` that has at most ``limit`` points (of equally large ones
+    the one with the longest rows, then planes).  7680: at radius 0 the grown block is the block, and mvs_block_match keeps both
+    (MVS_BLOCKMATCH_MAX_FLOATS = 15 360 samples)."""
+    shapes = np.stack(np.meshgrid(*[np.arange(1, g + 1) for g in grid], indexing="ij"), axis=-1).reshape(-1, len(grid))
+    shapes = shapes[shapes.prod(axis=1) <= limit]
+    n = max(shapes.tolist(), key=lambda s: (int(np.prod(s)),) + tuple(s[::-1]))
+    return np.array([[[0] * len(grid), n]], dtype=np.int64)
+
+
 # ---- the distorted mosaics ------------------------------------------------------------------------------------------------------
 # per case: the mosaic's ndim and the arguments of fit_fields; "2d_tight" has a window that is too small for some blocks (rim) and a
 # threshold that some peaks miss (low_ncc)

@@ -104,6 +104,26 @@ def test_rows_do_not_depend_on_the_other_blocks_of_the_call(hip_device):
     assert match(c, batch=1).tobytes() == full.tobytes()
 
 
+@pytest.mark.parametrize("dtype_name", ["u16", "f32"])
+@pytest.mark.parametrize("ndim", [2, 3])
+def test_one_block_at_radius_zero_is_pair_moments_of_its_box(hip_device, ndim, dtype_name):
+    """mvs_block_match against mvs_pair_moments, as test_rows_partition_the_samples_of_the_pair of tests/test_intensity_gpu.py ties
+    mvs_intensity_pair_moments to it: the largest block at the grid's origin that fits the kernel, radius 0, against the grid of the
+    block's shape.  A voxel that one of the two drops shows in n; the rest are double sums of at most 1e5 terms merged in
+    different trees, 1e-9 relative (the oracles agree within that: tests/test_nonrigid_host.py)."""
+    c = nc.match_case(ndim, dtype_name)
+    block = nc.largest_block(c["grid_shape"])
+    n = tuple(int(v) for v in block[0, 1])
+    got = _nonrigid_ops.block_match(c["fixed"], c["moving"], c["fixed_affine"], c["moving_affine"], block, (0,) * ndim, c["halfspaces"])
+    assert got.shape == (1, 1, 6)
+    row = got[0, 0]
+    whole = _metric_ops.pair_moments(c["fixed"], c["moving"], c["fixed_affine"], [c["moving_affine"]], n, c["halfspaces"])[0]
+    print("block", n, "row", row, "whole", whole)
+    assert row[0] == whole[0] and whole[0] > 500
+    np.testing.assert_allclose(row[1:3], whole[1:3], rtol=1e-9)
+    np.testing.assert_allclose(row[3:], whole[3:], rtol=1e-9, atol=1e-9 * max(whole[3], whole[4]))
+
+
 # ---- refusals -------------------------------------------------------------------------------------------------------------------------
 def test_refusals(hip_device):
     c = nc.match_case(3, "u16")

@@ -5,6 +5,7 @@ import pytest
 
 from multiview_stitcher_amd import intensity, nonrigid
 from tests import intensity_oracle as io
+from tests import metrics_oracle as mo
 from tests import nonrigid_cases as nc
 from tests import nonrigid_oracle as no
 
@@ -285,3 +286,19 @@ def test_the_oracle_leaves_margins_on_the_end_to_end_cases(name):
     else:
         assert info["rms_after"] < 0.7 * info["rms_before"] and nc.oracle_ratio(name) < 0.7
     assert all(np.abs(e).max() <= 1.5 for e in nc.mosaic(nc.FIT[name]["ndim"])["distortions"])
+
+
+@pytest.mark.parametrize("dtype_name", ["u16", "f32"])
+@pytest.mark.parametrize("ndim", [2, 3])
+def test_a_block_at_radius_zero_is_the_pair_of_its_box_in_both_oracles(ndim, dtype_name):
+    """What test_one_block_at_radius_zero_is_pair_moments_of_its_box of tests/test_nonrigid_gpu.py relies on: the restatements of
+    mvs_block_match and of mvs_pair_moments agree on the block it takes, within the tolerances it uses."""
+    c = nc.match_case(ndim, dtype_name)
+    block = nc.largest_block(c["grid_shape"])
+    n = tuple(int(v) for v in block[0, 1])
+    assert n == ((96, 45) if ndim == 2 else (8, 48, 20)) and int(np.prod(n)) <= 7680
+    row = no.block_moments(c["fixed"], c["moving"], c["fixed_affine"], c["moving_affine"], block, (0,) * ndim, c["halfspaces"])[0, 0]
+    whole = mo.pair_moments(c["fixed"], c["moving"], c["fixed_affine"], [c["moving_affine"]], n, c["halfspaces"])[0]
+    assert row[0] == whole[0] and whole[0] > 500
+    np.testing.assert_allclose(row[1:3], whole[1:3], rtol=1e-9)
+    np.testing.assert_allclose(row[3:], whole[3:], rtol=1e-9, atol=1e-9 * max(whole[3], whole[4]))
