@@ -881,6 +881,66 @@ int mvs_block_match(int device, const mvs_view_t* fixed, const mvs_view_t* movin
 int mvs_field_warp(int device, const mvs_view_t* view, int32_t ndim, const int32_t nodes[3],
                    const float* field, const void* tables, void* out, int32_t out_dtype, int32_t out_mem);
 
+/* Sample masks and mask-driven pair selection (masks.py): where the sample is, so that only the pairs of views whose sample masks
+ * touch are registered.  Replaces registration.get_pairs_from_sample_masks (registration.py:3256-3292: fuse of mask_i * (i + 1) with
+ * nanmin at order 0) and mv_graph.get_connected_labels (mv_graph.py:895-931) of the reference; the threshold is one Otsu threshold
+ * for the whole acquisition, from one histogram over all tiles.  All four results are integers or selections: integer atomics
+ * only, no floating-point atomics, equal inputs give equal bits.  All four wait for the result and run on the context lane of
+ * `device`.
+ *
+ * mvs_tile_histogram: over n_tiles >= 1 tiles of one dtype (uint8 / uint16 / float32, else MVS_ERR_UNSUPPORTED) whose shapes may
+ * differ.  Only data / dtype / mem / shape / stride are read; stride[2] == 1; device tiles may be strided windows, host tiles are
+ * C-contiguous (packed into one device block for the duration of the call); rows of at most 2^29 voxels.
+ * n_bins == 0: *min_out, *max_out and *n_valid_out receive minimum, maximum and number of the voxels that are not NaN (min / max:
+ * NaN when there is none): per-workgroup partials and a second small launch.
+ * 1 <= n_bins <= MVS_HIST_MAX_BINS (above: MVS_ERR_UNSUPPORTED): counts_out (host, n_bins uint64) receives the counts of
+ * numpy.histogram(values.astype(float64), bins=n_bins, range=(lo, hi)) over all tiles together, exactly.  edges (host): numpy's own
+ * n_bins + 1 float64 edges, lo = edges[0] < hi = edges[n_bins].  THE INDEX RULE, in float64 without contraction: a NaN and a value
+ * outside [lo, hi] are not counted; k = trunc((v - lo) / (hi - lo) * n_bins); k == n_bins becomes n_bins - 1; one step down when
+ * v < edges[k], else one step up when v >= edges[k + 1] and k is not the last bin.
+ * A wave takes one row of one tile: 16-byte loads from the row's first 16-byte aligned element on, a scalar head and tail.  A
+ * workgroup counts into uint32 bins in LDS (LDS integer atomics; the grid is sized so that a workgroup sees fewer than 2^32 voxels)
+ * and flushes them once with global uint64 integer atomics. */
+#define MVS_HIST_MAX_BINS 4096
+int mvs_tile_histogram(int device, const mvs_view_t* tiles, int32_t n_tiles, int32_t n_bins, const double* edges, uint64_t* counts_out,
+                       double* min_out, double* max_out, int64_t* n_valid_out);
+
+/* mvs_mask_threshold: mask_out (device memory, uint8, C-contiguous, the tile's shape) = 1 where tile > threshold, else 0.  tile:
+ * uint8 / uint16 / float32 in device memory, stride[2] == 1 (only data / dtype / mem / shape / stride are read).  An integer voxel is
+ * compared exactly, (double)v > threshold; a float32 voxel against (float)threshold; a NaN gives 0.
+ * radius[] (z, y, x; 2D: radius[0] ignored), 0 <= radius[k] <= MVS_MASK_MAX_DILATE (above: MVS_ERR_UNSUPPORTED): the mask is then
+ * dilated by the flat box of 2 radius[k] + 1 voxels per axis, scipy.ndimage.maximum_filter(mask, size=2 r + 1, mode="constant",
+ * cval=0), as separable line passes x, y, z on uint8 work volumes whose rows start on 16-byte boundaries.  Every lane takes 16
+ * voxels: the x pass reads the 16-byte groups around its own as bits and ORs a window of 2 r + 1 bits by doubling, the y / z passes
+ * OR the 16-byte groups of the 2 r + 1 rows / planes.  *n_set_out (may be NULL): the number of set voxels of mask_out. */
+#define MVS_MASK_MAX_DILATE 32
+int mvs_mask_threshold(int device, const mvs_view_t* tile, int32_t ndim, double threshold, const int32_t radius[3], void* mask_out,
+                       int64_t* n_set_out);
+
+/* mvs_label_fuse: the reference's fuse(mask_i * (i + 1), fusion_func=nanmin, interpolation_order=0) followed by its nan_to_num, on
+ * one output grid.  views: n_views >= 1 uint8 masks (else MVS_ERR_UNSUPPORTED), host (C-contiguous) or device memory (stride[2] ==
+ * 1); matrix / offset map an index of the output grid to a pixel of the view, as for mvs_fuse_chunk (fusion.fuse_np's
+ * get_pixel_affines derivation; the weight fields are not read).  out: int32, out_shape (z, y, x; 2D: out_shape[0] == 1),
+ * C-contiguous, in out_mem.  Per output voxel p and every view v whose coordinate is in bounds (0 <= c <= n - 1 on every axis, in
+ * float64 without contraction, as mvs_resample tests it) the value is mask_v(floor(c + 0.5)) ? v + 1 : 0 -- the voxel mvs_resample
+ * picks at order 0 -- and out(p) their minimum, zeros included; 0 where no view covers p.  Bricks of 4 x 4 x 64 (2D: 16 x 64) voxels;
+ * a workgroup culls the views against its brick, 64 at a time, as the generic fuse kernel does: any number of views. */
+int mvs_label_fuse(int device, const mvs_view_t* views, int32_t n_views, int32_t ndim, const int64_t out_shape[3], int32_t* out,
+                   int32_t out_mem);
+
+/* mvs_label_contacts: which labels touch (mv_graph.py:895-931).  labels: int32, device memory, C-contiguous, shape (z, y, x; 2D:
+ * shape[0] == 1); values outside 1 .. n_labels count as background.  1 <= n_labels <= MVS_LABEL_MAX (above: MVS_ERR_UNSUPPORTED; the
+ * matrix is at most 32 MiB).  counts_out (host): n_labels x n_labels uint64; C[a - 1][b - 1], a < b, is the number of voxel pairs
+ * (p, p + o) with labels {a, b}, o over the half neighbourhood of `connectivity` = the number of axes that may differ, 1 .. ndim:
+ * the offsets in {-1, 0, 1}^ndim with at most that many non-zero components whose first non-zero component is +1 -- 2 / 4 offsets in
+ * 2D, 3 / 9 / 13 in 3D, anti-diagonals such as (+1, -1) included.  Everything else of the matrix is 0.  (The reference compares the
+ * +1 shifts along one axis in 2D, one or two axes in 3D, and lists ordered pairs.)
+ * A wave takes 64 consecutive voxels of a row; per offset, consecutive lanes with the same label pair are combined by one shuffle and
+ * one ballot and the first lane of the run adds its length with one global uint64 integer atomic. */
+#define MVS_LABEL_MAX 2048
+int mvs_label_contacts(int device, const int32_t* labels, int32_t ndim, const int64_t shape[3], int32_t n_labels, int32_t connectivity,
+                       uint64_t* counts_out);
+
 #ifdef __cplusplus
 }
 #endif

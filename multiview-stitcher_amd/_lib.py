@@ -43,6 +43,9 @@ MVS_BLOCKMATCH_MAX_BLOCKS = 4096
 MVS_BLOCKMATCH_MAX_RESULT_BYTES = 64 << 20
 MVS_FIELD_MAX_NODES = 16
 MVS_STACK_MAX_QUANTILES = 4
+MVS_HIST_MAX_BINS = 4096
+MVS_MASK_MAX_DILATE = 32
+MVS_LABEL_MAX = 2048
 ERR_UNSUPPORTED = -4            # MVS_ERR_UNSUPPORTED
 
 DTYPE_CODES = {np.dtype(np.uint8): MVS_U8, np.dtype(np.uint16): MVS_U16, np.dtype(np.float32): MVS_F32}
@@ -343,6 +346,14 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32],
     ),
+    "mvs_tile_histogram": (
+        C.c_int,
+        [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_double),
+         C.POINTER(C.c_double), C.POINTER(C.c_int64)],
+    ),
+    "mvs_mask_threshold": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_double, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int64)]),
+    "mvs_label_fuse": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_int32]),
+    "mvs_label_contacts": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

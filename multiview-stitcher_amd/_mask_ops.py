@@ -1,0 +1,168 @@
+"""Thin array-level wrappers of the sample-mask entry points of libmvs_hip.so (mvs_tile_histogram, mvs_mask_threshold,
+mvs_label_fuse, mvs_label_contacts); the limits are checked here first, so that a refusal needs no device."""
+
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .device import DeviceArray, is_device_array
+from .transformation import fill_view_geometry, shape3, tile_view, view_data
+
+
+def check_n_bins(n_bins):
+    n_bins = int(n_bins)
+    if not 1 <= n_bins <= _lib.MVS_HIST_MAX_BINS:
+        raise ValueError(f"n_bins must be 1..{_lib.MVS_HIST_MAX_BINS}, not {n_bins}")
+    return n_bins
+
+
+def check_radius(radius, ndim):
+    """``radius`` (one int or one per axis) as ``ndim`` ints in 0..MVS_MASK_MAX_DILATE."""
+    radius = [int(radius)] * ndim if isinstance(radius, (int, np.integer)) else [int(r) for r in radius]
+    if len(radius) != ndim:
+        raise ValueError(f"expected one dilation radius or {ndim}, got {len(radius)}")
+    if min(radius) < 0 or max(radius) > _lib.MVS_MASK_MAX_DILATE:
+        raise ValueError(f"a dilation radius must be 0..{_lib.MVS_MASK_MAX_DILATE}, not {radius}")
+    return radius
+
+
+def check_n_labels(n_labels):
+    n_labels = int(n_labels)
+    if not 1 <= n_labels <= _lib.MVS_LABEL_MAX:
+        raise ValueError(f"the number of labels must be 1..{_lib.MVS_LABEL_MAX}, not {n_labels}")
+    return n_labels
+
+
+def _tile_views(tiles, device):
+    """The ``mvs_view_t`` array of whole 2-D / 3-D tiles of one dtype (numpy arrays or, possibly strided, DeviceArrays) and what
+    keeps their memory alive."""
+    if not len(tiles):
+        raise ValueError("no tiles")
+    views = (_lib.mvs_view_t * len(tiles))()
+    keep = []
+    for i, data in enumerate(tiles):
+        ndim = len(data.shape)
+        if ndim not in (2, 3):
+            raise ValueError("tiles are 2-D or 3-D")
+        if np.dtype(data.dtype) not in _lib.DTYPE_CODES:
+            raise TypeError(f"unsupported dtype {data.dtype} (uint8 / uint16 / float32)")
+        views[i], kept = tile_view(data, np.eye(ndim), np.zeros(ndim), device)
+        keep.append(kept)
+    if len({v.dtype for v in views}) != 1:
+        raise TypeError("the tiles must share one dtype")
+    return views, keep
+
+
+def value_range(tiles, device=0):
+    """``(min, max, n)`` over the voxels of all ``tiles`` that are not NaN (mvs_tile_histogram with n_bins == 0); min and max are
+    NaN when n == 0."""
+    lib = _lib.init(device)
+    views, keep = _tile_views(tiles, device)
+    lo, hi, n = C.c_double(), C.c_double(), C.c_int64()
+    _lib.check(lib.mvs_tile_histogram(device, views, len(tiles), 0, None, None, C.byref(lo), C.byref(hi), C.byref(n)), device, "mvs_tile_histogram")
+    del keep
+    return float(lo.value), float(hi.value), int(n.value)
+
+
+def bin_edges(n_bins, lo, hi):
+    """numpy's own edges of ``np.histogram(..., bins=n_bins, range=(lo, hi))``."""
+    return np.histogram_bin_edges(np.empty(0, dtype=np.float64), bins=int(n_bins), range=(float(lo), float(hi)))
+
+
+def histogram(tiles, n_bins, lo, hi, device=0):
+    """The uint64 counts of ``np.histogram(values.astype(float64), bins=n_bins, range=(lo, hi))`` over the voxels of all ``tiles``
+    together (mvs_tile_histogram); NaNs and values outside the range are left out."""
+    n_bins = check_n_bins(n_bins)
+    if not float(hi) > float(lo):
+        raise ValueError("histogram needs lo < hi")
+    lib = _lib.init(device)
+    views, keep = _tile_views(tiles, device)
+    edges = np.ascontiguousarray(bin_edges(n_bins, lo, hi), dtype=np.float64)
+    counts = np.zeros(n_bins, dtype=np.uint64)
+    _lib.check(lib.mvs_tile_histogram(device, views, len(tiles), n_bins, edges.ctypes.data_as(C.POINTER(C.c_double)),
+                                      counts.ctypes.data_as(C.POINTER(C.c_uint64)), None, None, None), device, "mvs_tile_histogram")
+    del keep
+    return counts
+
+
+def threshold_mask(tile, threshold, radius=0, device=0):
+    """``(mask, n_set)``: the uint8 DeviceArray ``tile > threshold``, dilated by the flat box of ``2 radius + 1`` voxels per axis
+    (``scipy.ndimage.maximum_filter(mask, size=2 r + 1, mode="constant", cval=0)``), and its number of set voxels
+    (mvs_mask_threshold).  ``tile``: 2-D / 3-D uint8 / uint16 / float32; a numpy array is uploaded first."""
+    ndim = len(tile.shape)
+    if ndim not in (2, 3):
+        raise ValueError("tiles are 2-D or 3-D")
+    radius = check_radius(radius, ndim)
+    if np.dtype(tile.dtype) not in _lib.DTYPE_CODES:
+        raise TypeError(f"unsupported dtype {tile.dtype} (uint8 / uint16 / float32)")
+    lib = _lib.init(device)
+    if not is_device_array(tile):
+        tile = DeviceArray.from_host(tile, device)
+    view, keep = tile_view(tile, np.eye(ndim), np.zeros(ndim), device)
+    out = DeviceArray.empty(tile.shape, np.uint8, device)
+    n_set = C.c_int64()
+    _lib.check(lib.mvs_mask_threshold(device, C.byref(view), ndim, float(threshold), _lib.i32x3(radius, ndim, 0), C.c_void_p(out.ptr), C.byref(n_set)),
+               device, "mvs_mask_threshold")
+    out.mark_written()
+    del keep
+    return out, int(n_set.value)
+
+
+def fuse_labels(masks, matrices, offsets, out_shape, device=0, out_on_device=False):
+    """The int32 label volume of shape ``out_shape``: per voxel the minimum over the views ``i`` that cover it at order 0 of
+    ``masks[i] ? i + 1 : 0``, and 0 where none does (mvs_label_fuse).  ``masks``: uint8 arrays (numpy or DeviceArray);
+    ``matrices[i]``, ``offsets[i]`` map an index of the output grid to a pixel of view ``i`` (``transformation.get_pixel_affines``)."""
+    lib = _lib.init(device)
+    ndim = len(out_shape)
+    if ndim not in (2, 3) or any(len(m.shape) != ndim for m in masks):
+        raise ValueError("fuse_labels needs 2-D or 3-D masks and an output shape of the same rank")
+    views = (_lib.mvs_view_t * len(masks))()
+    keep = []
+    for view, mask, matrix, offset in zip(views, masks, matrices, offsets):
+        if np.dtype(mask.dtype) != np.uint8:
+            raise TypeError(f"masks are uint8, not {mask.dtype}")
+        ptr, s3, st3, mem, kept = view_data(mask, device)
+        fill_view_geometry(view, ptr, _lib.MVS_U8, mem, s3, st3, matrix, offset)
+        keep.append(kept)
+    shape = tuple(int(s) for s in out_shape)
+    out = DeviceArray.empty(shape, np.int32, device) if out_on_device else np.empty(shape, dtype=np.int32)
+    ptr, mem = (out.ptr, _lib.MVS_MEM_DEVICE) if out_on_device else (out.ctypes.data, _lib.MVS_MEM_HOST)
+    _lib.check(lib.mvs_label_fuse(device, views, len(masks), ndim, _lib.i64x3(shape3(shape)), C.c_void_p(ptr), mem), device, "mvs_label_fuse")
+    if out_on_device:
+        out.mark_written()
+    del keep
+    return out
+
+
+def label_contacts(labels, n_labels, connectivity=None, device=0):
+    """The ``(n_labels, n_labels)`` uint64 matrix of contact counts of a 2-D / 3-D int32 label volume (mvs_label_contacts):
+    ``C[a - 1, b - 1]``, ``a < b``, counts the voxel pairs ``(p, p + o)`` with the labels ``{a, b}``, ``o`` over the half
+    neighbourhood in which up to ``connectivity`` axes differ (default: all).  ``labels``: numpy array (uploaded) or contiguous
+    DeviceArray."""
+    n_labels = check_n_labels(n_labels)
+    ndim = len(labels.shape)
+    if ndim not in (2, 3):
+        raise ValueError("label volumes are 2-D or 3-D")
+    connectivity = ndim if connectivity is None else int(connectivity)
+    if not 1 <= connectivity <= ndim:
+        raise ValueError(f"connectivity must be 1..{ndim}")
+    if np.dtype(labels.dtype) != np.int32:
+        raise TypeError(f"label volumes are int32, not {labels.dtype}")
+    lib = _lib.init(device)
+    if is_device_array(labels):
+        if not labels.is_contiguous():
+            raise TypeError("mvs_label_contacts needs a contiguous device array")
+        labels = labels.on_device(device)
+        labels.wait_ready(device)
+        dev = labels
+    else:
+        host = np.ascontiguousarray(labels)
+        dev = DeviceArray.empty(host.shape, np.int32, device)
+        _lib.check(lib.mvs_memcpy_h2d(device, dev.ptr, host.ctypes.data, host.nbytes), device, "h2d")
+    counts = np.zeros((n_labels, n_labels), dtype=np.uint64)
+    _lib.check(lib.mvs_label_contacts(device, C.c_void_p(dev.ptr), ndim, _lib.i64x3(shape3(labels.shape)), n_labels, connectivity,
+                                      counts.ctypes.data_as(C.POINTER(C.c_uint64))), device, "mvs_label_contacts")
+    return counts

@@ -126,24 +126,6 @@ template <> struct Vec4<float> { typedef float4 type; };
 template <> struct Vec4<unsigned short> { typedef ushort4 type; };
 template <> struct Vec4<unsigned char> { typedef uchar4 type; };
 
-// Conservative test: can any voxel of the brick (chunk index box lo..hi, inclusive)
-// land inside view V?  Exact classification happens per voxel afterwards.
-__device__ __forceinline__ bool brick_hits_view(const DevView& V, const int lo[3], const int hi[3]) {
-    const int n[3] = {V.nz, V.ny, V.nx};
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        double cmin = V.off[d], cmax = V.off[d];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            double a = V.m[d * 3 + k] * (double)lo[k], b = V.m[d * 3 + k] * (double)hi[k];
-            cmin += fmin(a, b);
-            cmax += fmax(a, b);
-        }
-        if (cmax < -1e-3 || cmin > (double)(n[d] - 1) + 1e-3) return false;
-    }
-    return true;
-}
-
 template <typename TOut>
 __device__ __forceinline__ void store_row4(TOut* out, long long row, int x0, int ox, const float r[4]);
 

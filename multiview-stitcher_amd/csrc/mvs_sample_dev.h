@@ -1,5 +1,6 @@
 // mvs_sample_dev.h -- internal: the one nearest / linear sampler of a view (DevView) that the generic fuse kernel, mvs_resample
-// (mvs_fuse.hip) and the pair metrics kernel (mvs_pair_metrics.hip) share, so that a voxel sampled by any of them has the same bits.
+// (mvs_fuse.hip) and the pair metrics kernel (mvs_pair_metrics.hip) share, so that a voxel sampled by any of them has the same bits;
+// and the brick / view test by which the generic fuse kernel and the label fuse kernel (mvs_masks.hip) cull views.
 #pragma once
 #include "mvs_fuse_dev.h"
 
@@ -53,4 +54,22 @@ __device__ __forceinline__ float sample_view(const DevView& V, double cz, double
 // scipy's in-bounds test of a linear sample (NI_GeometricTransform, mode "constant"): 0 <= c <= n - 1 on every axis
 __device__ __forceinline__ bool view_in_bounds(const DevView& V, double cz, double cy, double cx) {
     return !(cz < 0.0 || cz > (double)(V.nz - 1) || cy < 0.0 || cy > (double)(V.ny - 1) || cx < 0.0 || cx > (double)(V.nx - 1));
+}
+
+// Conservative test: can any voxel of the brick (chunk index box lo..hi, inclusive)
+// land inside view V?  Exact classification happens per voxel afterwards.
+__device__ __forceinline__ bool brick_hits_view(const DevView& V, const int lo[3], const int hi[3]) {
+    const int n[3] = {V.nz, V.ny, V.nx};
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        double cmin = V.off[d], cmax = V.off[d];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            double a = V.m[d * 3 + k] * (double)lo[k], b = V.m[d * 3 + k] * (double)hi[k];
+            cmin += fmin(a, b);
+            cmax += fmax(a, b);
+        }
+        if (cmax < -1e-3 || cmin > (double)(n[d] - 1) + 1e-3) return false;
+    }
+    return true;
 }

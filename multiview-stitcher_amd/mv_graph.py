@@ -837,21 +837,45 @@ def prune_to_axis_aligned_edges(g, max_angle=0.05):
     return out
 
 
+def otsu_from_histogram(counts, lo, hi):
+    """Otsu's threshold (Otsu 1979, as skimage.filters.threshold_otsu computes it) from the ``counts`` of a histogram of
+    ``len(counts)`` equal bins over ``[lo, hi]`` (numpy's edges of that range): the centre of the bin that maximises the
+    between-class variance.  Host, float64; what ``threshold_otsu`` and ``masks.otsu_threshold`` share."""
+    counts = np.asarray(counts).astype(np.float64)
+    edges = np.histogram_bin_edges(np.empty(0, dtype=np.float64), bins=len(counts), range=(float(lo), float(hi)))
+    centers = (edges[:-1] + edges[1:]) / 2.0
+    w1 = np.cumsum(counts)
+    w2 = np.cumsum(counts[::-1])[::-1]
+    with np.errstate(invalid="ignore", divide="ignore"):      # (bins before the first / after the last sample: 0 / 0, weight 0)
+        m1 = np.cumsum(counts * centers) / w1
+        m2 = (np.cumsum((counts * centers)[::-1]) / w2[::-1])[::-1]
+    var12 = w1[:-1] * w2[1:] * (m1[:-1] - m2[1:]) ** 2
+    return centers[np.argmax(var12)]
+
+
 def threshold_otsu(values, nbins=256):
     """skimage.filters.threshold_otsu on a 1-D sample (the call of mv_graph.py:858-881): 256-bin histogram over the value
     range, threshold = centre of the bin that maximises the between-class variance."""
     values = np.asarray(values, dtype=np.float64).ravel()
     if values.min() == values.max():
         return values[0]
-    counts, edges = np.histogram(values, bins=nbins, range=(values.min(), values.max()))
-    centers = (edges[:-1] + edges[1:]) / 2.0
-    counts = counts.astype(np.float64)
-    w1 = np.cumsum(counts)
-    w2 = np.cumsum(counts[::-1])[::-1]
-    m1 = np.cumsum(counts * centers) / w1
-    m2 = (np.cumsum((counts * centers)[::-1]) / w2[::-1])[::-1]
-    var12 = w1[:-1] * w2[1:] * (m1[:-1] - m2[1:]) ** 2
-    return centers[np.argmax(var12)]
+    counts, _ = np.histogram(values, bins=nbins, range=(values.min(), values.max()))
+    return otsu_from_histogram(counts, values.min(), values.max())
+
+
+def get_connected_labels(labels, structure=None, connectivity=None, n_labels=None, device=0):
+    """mv_graph.get_connected_labels (mv_graph.py:895-931) on the GPU: the pairs of labels of a 2-D / 3-D label image that touch,
+    as an ``(n, 2)`` int64 array of 0-based indices (label - 1), a thin wrapper of ``masks.contact_pairs``.  ``structure`` is accepted
+    and ignored, as the reference does (it overwrites it with ones).
+
+    Difference from the reference: it compares the ``+1`` shifts along one axis in 2-D, or along one or two axes in 3-D, and
+    returns every pair in both orders as it meets it (``(a, b)`` and ``(b, a)`` are separate rows).  This function tests the full
+    neighbourhood (``connectivity=None``: all axes may differ, diagonals and anti-diagonals included) and returns each unordered
+    pair once as ``(i, j)``, ``i < j``, sorted: a superset of the reference's unordered pairs."""
+    from . import masks
+
+    pairs = masks.contact_pairs(labels, connectivity=connectivity, n_labels=n_labels, device=device)
+    return np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
 
 
 def filter_edges(g, weight_key="overlap", threshold=None):

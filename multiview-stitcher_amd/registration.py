@@ -1723,3 +1723,15 @@ def register(msims, transform_key=None, reg_channel_index=None, reg_channel=None
                 "pairwise_registration": {"edges": edges, "results": all_results,
                                           "metrics": {"qualities": {e: r["quality"] for e, r in zip(edges, all_results[0])}}}}
     return params
+
+
+def get_pairs_from_sample_masks(mask_sims, transform_key="affine_manual", fused_mask_spacing=None, device=0):
+    """registration.get_pairs_from_sample_masks (registration.py:3256-3292) on the GPU: the pairs of views whose binary sample
+    masks overlap or touch under ``transform_key``.  Returns ``(pairs, fused_labels)``: ``masks.fuse_labels`` of the masks (spacing
+    ``fused_mask_spacing``, default the first mask's) and ``masks.contact_pairs`` of that label image -- sorted ``(i, j)``, ``i < j``,
+    each unordered pair once under full connectivity (``mv_graph.get_connected_labels`` states the difference from the
+    reference's list).  ``pairs`` goes straight into ``register(..., pairs=pairs)``; ``masks.sample_masks`` makes the masks."""
+    from . import masks
+
+    fused_labels = masks.fuse_labels(mask_sims, transform_key, spacing=fused_mask_spacing, device=device)
+    return masks.contact_pairs(fused_labels, device=device), fused_labels
