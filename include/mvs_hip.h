@@ -941,6 +941,74 @@ int mvs_label_fuse(int device, const mvs_view_t* views, int32_t n_views, int32_t
 int mvs_label_contacts(int device, const int32_t* labels, int32_t ndim, const int64_t shape[3], int32_t n_labels, int32_t connectivity,
                        uint64_t* counts_out);
 
+/* Masked normalised cross-correlation of two overlap crops (registration.masked_correlation_registration): Padfield 2012, what
+ * skimage.registration.phase_cross_correlation computes when it is given reference_mask / moving_mask.  The reference only ever calls
+ * that variant with inverted masks (registration.py:433-443), where it contributes t = 0; this entry is the variant itself.
+ *
+ * THE CONTRACT.  Crops F (fixed) and M (moving): float32, C-contiguous, one shape n = (z, y, x) (2D: shape[0] == 1), in opts->mem.
+ * A voxel of F is valid when it is finite, fixed_mask (uint8, the crop's shape, in opts->mask_mem; may be NULL) is non-zero there and,
+ * with has_valid_above[0], (double)F(x) > valid_above[0]; likewise M with moving_mask and index 1.  For every integer shift s of the
+ * window |s_d| <= S_d (S_d = max_shift[d]; n_d - 1 where that is negative or larger):
+ *   Omega(s) = {x : F valid at x, x + s inside the crop, M valid at x + s},  N(s) = |Omega(s)|,
+ *   r(s) = the Pearson correlation of F(x) and M(x + s) over Omega(s); 0 where sqrt(dF dM) <= 1e3 FLT_EPSILON max_s sqrt(dF dM) (the
+ *          rule of skimage at float32), dF and dM the sums of squared deviations of either crop over Omega(s); clipped to [-1, 1].
+ * A shift is eligible when N(s) >= max(overlap_ratio * max_s N(s), min_overlap), both maxima over the window.  The result is the
+ * eligible shift with the largest r, among equals the one with the lowest flat index of the window (first axis slowest, s ascending):
+ * M(x + peak) ~ F(x), the convention of the other pair functions.
+ *
+ * THE CHAIN, one stream, no host step in the middle.  Padded length per axis P_d = the smallest power of two >= n_d + S_d (1 where
+ * n_d == 1): the circular correlation is then alias-free on the window.  prod(P) > MVS_MASKED_CORR_MAX_VOXELS is refused with
+ * MVS_ERR_UNSUPPORTED before any device is touched (three complex64 volumes of prod(P): 6.4 GB at the limit); a lower max_shift is
+ * the way out.  Statistics: count, sum (float64), min, max of the valid voxels per crop, per-workgroup partials and a second small
+ * launch; mu = sum / count, range = max - min (1 where 0).  Pack: Z1 = f + i g, Z2 = vF + i vM, Z3 = f^2 + i g^2, zero-padded, with
+ * f = (F - mu_F) / range_F on valid voxels and 0 elsewhere (r is invariant to both; the centring keeps the sums below out of float32
+ * cancellation).  Three forward transforms (the transform of mvs_fft_c2c).  One combine kernel separates the six real spectra by
+ * A(k) = (Z(k) + conj Z(-k)) / 2, B(k) = (Z(k) - conj Z(-k)) / 2i and forms, in place and scaled by 1 / prod(P),
+ * X1 = corr(vF, vM) + i corr(f, g), X2 = corr(f, vM) + i corr(vF, g), X3 = corr(f^2, vM) + i corr(vF, g^2) with
+ * corr(a, b)(s) = sum_x a(x) b(x + s), spectrum conj(A) B; one thread owns the pair {k, -k mod P}.  Three inverse transforms.  Over
+ * the window only (at the wrapped indices): (a) the maxima of rint(N) and of sqrt(dF dM), dF = cF2 - cF^2 / N clamped at 0, N taken
+ * as max(rint(N), 1); (b) r = (cFM - cF cM / N) / sqrt(dF dM) under the rule above, eligibility on rint(N), the arg-max per
+ * workgroup; then one workgroup folds those and writes the record.  Fixed-tree reductions and no atomics: equal inputs give equal bits.
+ *
+ * r_out / n_out (host memory, may be NULL): the window's r (float32) and rint(N) (int32), shape (2 S_z + 1, 2 S_y + 1, 2 S_x + 1).
+ * A status other than MVS_MASKED_CORR_OK is not an error (the call returns 0): TOO_FEW_VALID (a crop with fewer than min_overlap
+ * valid voxels) before CONSTANT_CROP (min == max over a crop's valid voxels) before NO_ELIGIBLE_SHIFT (no eligible shift whose
+ * denominator is above the tolerance); peak and r are then not to be used (with no eligible shift at all: peak 0, r NaN). */
+#define MVS_MASKED_CORR_MAX_VOXELS (1LL << 28)
+enum mvs_masked_corr_status {
+    MVS_MASKED_CORR_OK = 0,
+    MVS_MASKED_CORR_NO_ELIGIBLE_SHIFT = 1,
+    MVS_MASKED_CORR_TOO_FEW_VALID = 2,
+    MVS_MASKED_CORR_CONSTANT_CROP = 3
+};
+typedef struct mvs_masked_corr_opts_t {
+    int32_t ndim;               /* 2 or 3                                              */
+    int32_t mem;                /* enum mvs_mem of both crops                          */
+    int32_t mask_mem;           /* enum mvs_mem of the masks that are given            */
+    int32_t has_valid_above[2]; /* fixed, moving                                       */
+    int32_t reserved;
+    double valid_above[2];
+    double overlap_ratio;       /* in (0, 1]                                           */
+    int64_t min_overlap;        /* >= 1                                                */
+    int64_t max_shift[3];       /* z, y, x; negative: n - 1                            */
+} mvs_masked_corr_opts_t;
+typedef struct mvs_masked_corr_result_t {
+    int32_t status;             /* enum mvs_masked_corr_status                         */
+    int32_t peak[3];            /* z, y, x                                             */
+    float r;                    /* at the peak                                         */
+    int32_t reserved;
+    int64_t n_peak;             /* N at the peak                                       */
+    int64_t n_max;              /* max N over the window                               */
+    int64_t n_valid[2];         /* valid voxels of the fixed and of the moving crop    */
+    float neighbour_r[6];       /* r at peak - e_d ([2 d]) and peak + e_d ([2 d + 1]); NaN outside the window */
+    int32_t neighbour_ok[6];    /* ... inside the window and eligible                  */
+    int64_t padded[3];          /* P                                                   */
+    int64_t max_shift[3];       /* S                                                   */
+} mvs_masked_corr_result_t;
+int mvs_masked_corr(int device, const float* fixed, const float* moving, const uint8_t* fixed_mask, const uint8_t* moving_mask,
+                    const int64_t shape[3], const mvs_masked_corr_opts_t* opts, mvs_masked_corr_result_t* result, float* r_out,
+                    int32_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,8 @@ MVS_STACK_MAX_QUANTILES = 4
 MVS_HIST_MAX_BINS = 4096
 MVS_MASK_MAX_DILATE = 32
 MVS_LABEL_MAX = 2048
+MVS_MASKED_CORR_MAX_VOXELS = 1 << 28
+MVS_MASKED_CORR_OK, MVS_MASKED_CORR_NO_ELIGIBLE_SHIFT, MVS_MASKED_CORR_TOO_FEW_VALID, MVS_MASKED_CORR_CONSTANT_CROP = 0, 1, 2, 3
 ERR_UNSUPPORTED = -4            # MVS_ERR_UNSUPPORTED
 
 DTYPE_CODES = {np.dtype(np.uint8): MVS_U8, np.dtype(np.uint16): MVS_U16, np.dtype(np.float32): MVS_F32}
@@ -98,6 +100,36 @@ class mvs_deconv_opts_t(C.Structure):
 
 
 MVS_DECONV_PREPARE_WEIGHTS = 1
+
+
+class mvs_masked_corr_opts_t(C.Structure):
+    _fields_ = [
+        ("ndim", C.c_int32),
+        ("mem", C.c_int32),
+        ("mask_mem", C.c_int32),
+        ("has_valid_above", C.c_int32 * 2),
+        ("reserved", C.c_int32),
+        ("valid_above", C.c_double * 2),
+        ("overlap_ratio", C.c_double),
+        ("min_overlap", C.c_int64),
+        ("max_shift", C.c_int64 * 3),
+    ]
+
+
+class mvs_masked_corr_result_t(C.Structure):
+    _fields_ = [
+        ("status", C.c_int32),
+        ("peak", C.c_int32 * 3),
+        ("r", C.c_float),
+        ("reserved", C.c_int32),
+        ("n_peak", C.c_int64),
+        ("n_max", C.c_int64),
+        ("n_valid", C.c_int64 * 2),
+        ("neighbour_r", C.c_float * 6),
+        ("neighbour_ok", C.c_int32 * 6),
+        ("padded", C.c_int64 * 3),
+        ("max_shift", C.c_int64 * 3),
+    ]
 
 
 class mvs_dct_opts_t(C.Structure):
@@ -354,6 +386,11 @@ SIGNATURES = {
     "mvs_mask_threshold": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_double, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int64)]),
     "mvs_label_fuse": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_int32]),
     "mvs_label_contacts": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
+    "mvs_masked_corr": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(mvs_masked_corr_opts_t),
+         C.POINTER(mvs_masked_corr_result_t), C.c_void_p, C.c_void_p],
+    ),
 }
 
 _lib = None

@@ -192,6 +192,56 @@ def affine_registration(fixed_data, moving_data, transform_type="rigid", shrink_
                                            initial_affine, fit_intensity, device, return_debug, metric, n_bins)
 
 
+def masked_correlation_registration(fixed_data, moving_data, fixed_mask=None, moving_mask=None, valid_above=None, overlap_ratio=0.3,
+                                    min_overlap=None, max_shift=None, subpixel=True, device=0, return_debug=False):
+    """Translation between two same-shape overlap crops (float32, NaN = outside the view) by masked normalised cross-correlation
+    (Padfield 2012; ``skimage.registration.phase_cross_correlation`` with ``reference_mask`` / ``moving_mask``): a drop-in
+    ``pairwise_reg_func`` for overlaps that are not boxes (rotated or opposite views, whose zero-filled wedges mislead the plain
+    phase correlation) and for sparse samples on a dark or structured background.
+
+    A voxel counts when it is finite, its mask (``fixed_mask`` / ``moving_mask``: arrays of the crops' shape, non-zero = data) is
+    set, and it exceeds ``valid_above`` (a scalar, or a ``(fixed, moving)`` pair; e.g. ``masks.otsu_threshold(tiles)`` through
+    ``pairwise_reg_func_kwargs``).  For every integer shift ``s`` with ``|s_d| <= max_shift_d`` (a scalar or one value per axis, in
+    px; default ``n_d - 1``) the Pearson correlation ``r(s)`` of ``fixed(x)`` and ``moving(x + s)`` is taken over the voxels that
+    count in both; the result is the shift with the largest ``r`` among those whose overlap ``N(s)`` is at least
+    ``max(overlap_ratio * max N, min_overlap)`` (``min_overlap`` defaults to ``4 ** ndim``).  Tiny overlaps correlate perfectly by
+    chance: that is what the overlap rule is for.  One ``mvs_masked_corr`` call: three forward and three inverse transforms of the
+    crops zero-padded to powers of two ``>= n_d + max_shift_d``; more than 2^28 padded voxels raise ``NotImplementedError`` (pass a
+    smaller ``max_shift``).  ``subpixel`` refines every axis by the vertex of the parabola through ``r`` at the peak and its two
+    neighbours (host, float64, clamped to half a px), on an axis only when both neighbours lie in the window, have enough overlap
+    and the curvature is negative.
+
+    Returns ``{"affine_matrix": translation mapping fixed px -> moving px, "quality": r at the integer peak, in [-1, 1]}``.  The
+    quality is the quantity that was maximised and costs no further pass over the crops; the other pair functions report a masked
+    Spearman coefficient of the aligned crops instead, so qualities of different pair functions are not on one scale.
+    ``return_debug`` adds ``"debug": {"r", "n"`` (the window volumes, shape ``2 max_shift + 1``), ``"peak", "n_peak", "n_max",
+    "n_valid", "padded_shape", "max_shift", "status", "subpixel"}``.  Warns and returns the identity with quality NaN when a crop has
+    fewer than ``min_overlap`` valid voxels, is constant on them, or no shift qualifies."""
+    from . import _masked_corr_ops as ops
+
+    im0, im1 = _as_array(fixed_data), _as_array(moving_data)
+    ndim = len(im0.shape)
+    thr = (valid_above, valid_above) if valid_above is None or np.isscalar(valid_above) else tuple(valid_above)
+    if len(thr) != 2:
+        raise ValueError("valid_above is a scalar or a (fixed, moving) pair")
+    res = ops.masked_corr(im0, im1, None if fixed_mask is None else _as_array(fixed_mask), None if moving_mask is None else _as_array(moving_mask),
+                          thr, overlap_ratio, 4 ** ndim if min_overlap is None else min_overlap, max_shift, device, want_volumes=return_debug)
+    delta = [0.0] * ndim
+    if res["status"] != _lib.MVS_MASKED_CORR_OK:
+        warnings.warn(f"Masked correlation: {ops.STATUS_MESSAGES[res['status']]}. Assuming identity transform.", UserWarning, stacklevel=2)
+        out = {"affine_matrix": param_utils.identity_transform(ndim), "quality": np.nan}
+    else:
+        if subpixel:
+            delta = [ops.subpixel_offset(res["r"], res["neighbour_r"][2 * d], res["neighbour_r"][2 * d + 1], res["neighbour_ok"][2 * d],
+                                         res["neighbour_ok"][2 * d + 1]) for d in range(ndim)]
+        out = {"affine_matrix": param_utils.affine_from_translation([float(p) + dl for p, dl in zip(res["peak"], delta)]), "quality": res["r"]}
+    if return_debug:
+        out["debug"] = {"r": res["r_volume"], "n": res["n_volume"], "peak": res["peak"], "n_peak": res["n_peak"], "n_max": res["n_max"],
+                        "n_valid": res["n_valid"], "padded_shape": res["padded_shape"], "max_shift": res["max_shift"], "status": res["status"],
+                        "subpixel": delta}
+    return out
+
+
 def registration_marker_based(fixed_points, moving_points, transform_type="rigid", num_neighbors=3, redundancy=1, descriptor_ratio=3.0,
                               descriptor_distance_threshold=None, descriptor_threshold_scale=1.0, ransac_max_error=5.0,
                               ransac_min_inlier_ratio=0.1, ransac_min_inlier_factor=3.0, ransac_num_iterations=1000, icp=False,
