@@ -168,6 +168,9 @@ int mvs_set_option(int device, const char* key, int64_t value);
  * column met more than 64 views, and that the generic kernel redid, counts in both; content-based and DCT-weighted chunks count in
  * none).  With option "no_regions" = 1 a weighted-average chunk goes to the column kernel, which by default takes it only when the
  * region planner declines (more than 8 views on a cell, too many cells or regions); tests assert the family they were built for.
+ * Content-based chunks that took the bit-faithful passes: "cb_exact_chunks", "cb_exact_large_chunks" (of these, the ones with more than
+ * 8 views or a pool beyond 32-bit indices: boxes read from global memory), and their line launches by kernel: "cb_exact_paired_launches"
+ * (value and mask in one launch), "cb_exact_lds_launches" / "cb_exact_tap_launches" (separate passes, LDS-staged / tap by tap).
  * reset != 0 clears an accumulating counter after reading. */
 int mvs_get_counter(int device, const char* key, int32_t reset, double* value_out);
 /* Device time (ms, hipEvent) spent in the kernels of the most recent compute

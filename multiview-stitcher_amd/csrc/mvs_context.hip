@@ -260,6 +260,11 @@ static const MvsCounter kCounters[] = {
     {"cb_mask_boxes", nullptr, &MvsContext::cb_mask_boxes},
     {"cb_line_launches", nullptr, &MvsContext::cb_line_launches},
     {"cb_overflows_redone", nullptr, &MvsContext::cb_overflows},
+    {"cb_exact_chunks", nullptr, &MvsContext::cb_exact_chunks},
+    {"cb_exact_large_chunks", nullptr, &MvsContext::cb_exact_large_chunks},
+    {"cb_exact_paired_launches", nullptr, &MvsContext::cb_exact_paired_launches},
+    {"cb_exact_lds_launches", nullptr, &MvsContext::cb_exact_lds_launches},
+    {"cb_exact_tap_launches", nullptr, &MvsContext::cb_exact_tap_launches},
     {"fuse_rows_chunks", nullptr, &MvsContext::fuse_rows_chunks},
     {"fuse_region_chunks", nullptr, &MvsContext::fuse_region_chunks},
     {"fuse_column_chunks", nullptr, &MvsContext::fuse_column_chunks},

@@ -991,6 +991,7 @@ int cb_exact_paired_passes(CbCall& K) {
             L.T = p.T;
             const dim3 g((unsigned)((L.n_lines + L.T - 1) / L.T), p.split ? 2 : 1), b(256);
             hipLaunchKernelGGL(kPairKernels[p.split ? 1 : 0][p.src][p.dst], g, b, p.lds, K.c->stream, P, L, radius, fw, pf);
+            K.c->cb_exact_paired_launches += 1;
         }
     }
     MVS_HIP_TRY(K.c, hipGetLastError());
@@ -1011,6 +1012,7 @@ void cb_gauss_separate(CbCall& K, const float* src, float* dst, const CbBox& B, 
             hipLaunchKernelGGL(gauss1d_lds_kernel, dim3((unsigned)((L.n_lines + L.T - 1) / L.T)), dim3(256), cb_single_lds(L.len, radius, L.T), K.c->stream, cur, d, L,
                                radius, fw, axis == 2 ? 1 : 0);
         else hipLaunchKernelGGL(gauss1d_kernel, dim3(gbb), dim3(256), 0, K.c->stream, cur, d, Sb, axis, radius, fw, L.b0, L.full);
+        (L.T ? K.c->cb_exact_lds_launches : K.c->cb_exact_tap_launches) += 1;
         cur = d;
     }
 }
@@ -1040,6 +1042,8 @@ int cb_exact_path(CbCall& K) {
     if (!rc) { cb_exact_plan(K); rc = cb_scratch(K); }
     if (!rc) rc = cb_upload_block(K);
     if (rc) return rc;
+    K.c->cb_exact_chunks += 1;
+    if (!K.small) K.c->cb_exact_large_chunks += 1;
     cb_resample_blend_normalize(K);
     if (K.mask_tables) {
         cb_exact_mask_tables(K);

@@ -88,6 +88,9 @@ struct MvsContext {
     int* cb_flag_host = nullptr;  // mapped pinned word the device raises when a view's mask list overflows (fast path) ...
     int* cb_flag_dev = nullptr;   // ... its device alias; read by the call itself (host results) or through counter "cb_overflow"
     long long cb_overflows = 0, cb_line_launches = 0;
+    // the route of the bit-faithful passes (read-only counters of the same names): chunks, those of them that are not `small`, and the line
+    // launches by kernel: gauss1d_pair_kernel, gauss1d_lds_kernel, gauss1d_kernel
+    long long cb_exact_chunks = 0, cb_exact_large_chunks = 0, cb_exact_paired_launches = 0, cb_exact_lds_launches = 0, cb_exact_tap_launches = 0;
     bool cb_nosplit = false;      // test switch: the y / z passes of the paired path keep both quantities in one workgroup
     bool cb_unpaired = false;     // test switch: content-based weights through the separate value / mask line passes of rounds 1-3
     int fft_slab_axes = 4;        // short axes (bit k = axis k of (z, y, x)) whose crops take the three-pass phase correlation: by default only
