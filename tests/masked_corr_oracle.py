@@ -1,5 +1,6 @@
 """numpy-only oracle of registration.masked_correlation_registration (mvs_masked_corr): the definition as a float64 brute-force sum over
-every shift of the window, and a float32 restatement of the device chain (statistics, pack, transforms, spectral combine, window
+every shift of the window (or over a list of shifts), the same definition through float64 transforms for windows too large for the
+sum, and a float32 restatement of the device chain (statistics, pack, transforms, spectral combine, window
 search) that sizes the tolerances of the GPU tests on the CPU."""
 import itertools
 
@@ -46,6 +47,28 @@ def select(F, M, vF, vM, r, n, den_ok, overlap_ratio, min_overlap):
     return eligible, n_max, peak_w, status
 
 
+def brute_force_at(F, M, shifts, fixed_mask=None, moving_mask=None, valid_above=(None, None)):
+    """The definition at the given shifts (a sequence of ndim-tuples), in float64: the overlap count ``n``, the numerator ``num`` and
+    the denominator ``den`` of Pearson's r over the voxels valid in both crops, one entry per shift (0 where nothing overlaps)."""
+    shape = F.shape
+    vF, vM = validity(F, fixed_mask, valid_above[0]), validity(M, moving_mask, valid_above[1])
+    shifts = [tuple(int(k) for k in s) for s in shifts]
+    num, den, n = np.zeros(len(shifts)), np.zeros(len(shifts)), np.zeros(len(shifts), dtype=np.int64)
+    F64, M64 = np.where(vF, F, 0).astype(np.float64), np.where(vM, M, 0).astype(np.float64)
+    for w, s in enumerate(shifts):
+        slF = tuple(slice(max(0, -k), min(m, m - k)) for k, m in zip(s, shape))      # x
+        slM = tuple(slice(max(0, k), min(m, m + k)) for k, m in zip(s, shape))       # x + s
+        both = vF[slF] & vM[slM]
+        n[w] = both.sum()
+        if n[w] == 0:
+            continue
+        a, b = F64[slF][both], M64[slM][both]
+        a, b = a - a.mean(), b - b.mean()
+        num[w] = (a * b).sum()
+        den[w] = np.sqrt((a * a).sum() * (b * b).sum())
+    return n, num, den
+
+
 def brute_force(F, M, fixed_mask=None, moving_mask=None, valid_above=(None, None), overlap_ratio=0.3, min_overlap=None, max_shift=None):
     """The definition, in float64.  Returns a dict: ``r``, ``n`` (window volumes, shape 2 S + 1), ``eligible``, ``n_max``, ``peak``
     (the shift, or None), ``peak_window`` (its window index), ``status``, ``shifts``."""
@@ -54,20 +77,7 @@ def brute_force(F, M, fixed_mask=None, moving_mask=None, valid_above=(None, None
     min_overlap = 4 ** ndim if min_overlap is None else int(min_overlap)
     vF, vM = validity(F, fixed_mask, valid_above[0]), validity(M, moving_mask, valid_above[1])
     window = [2 * s + 1 for s in S]
-    num, den, n = np.zeros(window), np.zeros(window), np.zeros(window, dtype=np.int64)
-    F64, M64 = np.where(vF, F, 0).astype(np.float64), np.where(vM, M, 0).astype(np.float64)
-    for s in itertools.product(*[range(-k, k + 1) for k in S]):
-        slF = tuple(slice(max(0, -k), min(m, m - k)) for k, m in zip(s, shape))      # x
-        slM = tuple(slice(max(0, k), min(m, m + k)) for k, m in zip(s, shape))       # x + s
-        both = vF[slF] & vM[slM]
-        w = tuple(k + q for k, q in zip(s, S))
-        n[w] = both.sum()
-        if n[w] == 0:
-            continue
-        a, b = F64[slF][both], M64[slM][both]
-        a, b = a - a.mean(), b - b.mean()
-        num[w] = (a * b).sum()
-        den[w] = np.sqrt((a * a).sum() * (b * b).sum())
+    n, num, den = (a.reshape(window) for a in brute_force_at(F, M, itertools.product(*[range(-k, k + 1) for k in S]), fixed_mask, moving_mask, valid_above))
     tol = 1e3 * FLT_EPS * den.max()
     den_ok = den > tol
     r = np.clip(np.where(den_ok, num / np.where(den_ok, den, 1.0), 0.0), -1.0, 1.0)
@@ -76,9 +86,50 @@ def brute_force(F, M, fixed_mask=None, moving_mask=None, valid_above=(None, None
             "peak": None if peak_w is None else [int(p) - s for p, s in zip(peak_w, S)]}
 
 
-def float32_chain(F, M, fixed_mask=None, moving_mask=None, valid_above=(None, None), overlap_ratio=0.3, min_overlap=None, max_shift=None):
+def fft_float64(F, M, fixed_mask=None, moving_mask=None, valid_above=(None, None), overlap_ratio=0.3, min_overlap=None, max_shift=None):
+    """The definition through transforms, in float64, for windows the brute force cannot afford: each crop centred and scaled over its
+    valid voxels (``(v - mean) / range``; r does not depend on either), the six correlations by ``numpy.fft`` on the padded shape,
+    then the window arithmetic of the device chain (``rint(N)``, ``max(N, 1)``, the clamps at 0, the ``1e3 FLT_EPS`` rule, the clip)
+    and ``select``.  The result dict of ``brute_force`` plus ``den`` (of the scaled crops) and ``tol`` (the bound it is held against)."""
+    shape, ndim = F.shape, F.ndim
+    S = default_shifts(shape, max_shift)
+    P = padded_shape(shape, S)
+    min_overlap = 4 ** ndim if min_overlap is None else int(min_overlap)
+    vF, vM = validity(F, fixed_mask, valid_above[0]), validity(M, moving_mask, valid_above[1])
+
+    def centred(im, v):
+        out = np.zeros(shape)
+        if v.any():
+            vals = im[v].astype(np.float64)
+            rng = vals.max() - vals.min()
+            out[v] = (vals - vals.mean()) / (rng if rng > 0 else 1.0)
+        return out
+
+    f, g = centred(F, vF), centred(M, vM)
+    axes = tuple(range(ndim))
+    spec = {k: np.fft.rfftn(a, s=P, axes=axes) for k, a in (("f", f), ("g", g), ("vF", vF.astype(np.float64)), ("vM", vM.astype(np.float64)), ("f2", f * f), ("g2", g * g))}
+    idx = np.ix_(*[np.arange(-s, s + 1) % p for s, p in zip(S, P)])
+    corr = lambda a, b: np.fft.irfftn(np.conj(spec[a]) * spec[b], s=P, axes=axes)[idx]      # sum_x a(x) b(x + s) on the window
+    N, cFM, cF, cM, cF2, cM2 = corr("vF", "vM"), corr("f", "g"), corr("f", "vM"), corr("vF", "g"), corr("f2", "vM"), corr("vF", "g2")
+    nr = np.rint(N)
+    nc = np.maximum(nr, 1.0)
+    den = np.sqrt(np.maximum(cF2 - cF * cF / nc, 0.0) * np.maximum(cM2 - cM * cM / nc, 0.0))
+    num = cFM - cF * cM / nc
+    tol = 1e3 * FLT_EPS * den.max()
+    den_ok = den > tol
+    r = np.clip(np.where(den_ok, num / np.where(den_ok, den, 1.0), 0.0), -1.0, 1.0)
+    n = nr.astype(np.int64)
+    eligible, n_max, peak_w, status = select(F, M, vF, vM, r, n, den_ok, overlap_ratio, min_overlap)
+    return {"r": r, "n": n, "eligible": eligible, "n_max": n_max, "peak_window": peak_w, "status": status, "shifts": S, "padded_shape": P,
+            "den": den, "tol": tol, "peak": None if peak_w is None else [int(p) - s for p, s in zip(peak_w, S)]}
+
+
+def float32_chain(F, M, fixed_mask=None, moving_mask=None, valid_above=(None, None), overlap_ratio=0.3, min_overlap=None, max_shift=None,
+                  centre=True):
     """The device chain restated in float32 / complex64 numpy (numpy >= 2 transforms complex64 in single precision): the same
-    centring, the same packed transforms and two-for-one separation, the same window arithmetic.  Same result dict."""
+    centring, the same packed transforms and two-for-one separation, the same window arithmetic.  Same result dict, plus ``n_raw``:
+    N of the window before ``rint``.  ``centre=False`` leaves the mean in (what the chain would be without its statistics pass: the
+    tests show on data with an offset that the centring is needed)."""
     f32, c64 = np.float32, np.complex64
     shape, ndim = F.shape, F.ndim
     S = default_shifts(shape, max_shift)
@@ -90,7 +141,7 @@ def float32_chain(F, M, fixed_mask=None, moving_mask=None, valid_above=(None, No
         out = np.zeros(shape, f32)
         if v.any():
             vals = im[v].astype(f32)
-            mu = f32(vals.astype(np.float64).sum() / v.sum())
+            mu = f32(vals.astype(np.float64).sum() / v.sum()) if centre else f32(0)
             rng = f32(vals.max() - vals.min())
             out[v] = (vals - mu) / (rng if rng > 0 else f32(1))
         return out
@@ -133,7 +184,7 @@ def float32_chain(F, M, fixed_mask=None, moving_mask=None, valid_above=(None, No
     n = nr.astype(np.int64)
     eligible, n_max, peak_w, status = select(F, M, vF, vM, r, n, den_ok, overlap_ratio, min_overlap)
     return {"r": r, "n": n, "eligible": eligible, "n_max": n_max, "peak_window": peak_w, "status": status, "shifts": S, "padded_shape": P,
-            "peak": None if peak_w is None else [int(p) - s for p, s in zip(peak_w, S)]}
+            "n_raw": N, "peak": None if peak_w is None else [int(p) - s for p, s in zip(peak_w, S)]}
 
 
 def subpixel(r, eligible, peak_w):

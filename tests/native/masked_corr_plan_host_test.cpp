@@ -3,6 +3,7 @@
 //   P <nz> <ny> <nx> <Sz> <Sy> <Sx> : code, S, P, W, voxels, padded, window, blocks of the three grids
 //   A <n> <S>                       : the alias-free property of padded_length(n, S) on a 1-D example, and that half that length breaks it
 //   W <n...>                        : window_to_padded of every window entry of a small plan against a direct computation
+//   E <nz> <ny> <nx>                : window, window_to_padded of the first and of the last window entry (the large test cases)
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -21,6 +22,14 @@ static void print_plan(int ndim, long long nz, long long ny, long long nx, long 
                     (long long)p.P[0], (long long)p.P[1], (long long)p.P[2], (long long)p.W[0], (long long)p.W[1], (long long)p.W[2], p.voxels, p.padded,
                     p.window, p.voxel_blocks, p.padded_blocks, p.window_blocks);
     std::printf("\n");
+}
+
+// window_to_padded at the first and the last entry of the window of a plan
+static void print_ends(int ndim, long long nz, long long ny, long long nx, long long sz, long long sy, long long sx) {
+    const int64_t shape[3] = {nz, ny, nx}, ms[3] = {sz, sy, sx};
+    Plan p;
+    if (make_plan(ndim, shape, ms, &p) != kPlanOk) std::exit(1);
+    std::printf("E %lld %lld %lld : %lld %lld %lld\n", nz, ny, nx, p.window, window_to_padded(p, 0), window_to_padded(p, p.window - 1));
 }
 
 // integer sequences a, b of n samples: mismatches between the circular correlation at length P and the linear one over |s| <= S
@@ -63,6 +72,13 @@ int main() {
     print_plan(4, 1, 16, 16, -1, -1, -1);
     print_plan(3, 0, 16, 16, -1, -1, -1);
     print_plan(3, 4294967296LL, 1, 1, -1, -1, -1);
+    // the large test cases: more than kMaxBlocks * kThreads = 262144 items in a grid (a second trip of the grid-stride loops)
+    print_plan(2, 1, 520, 520, -1, 300, 300);
+    print_plan(3, 20, 130, 130, 3, 40, 40);
+    print_plan(2, 1, 3, 4100, -1, 1, 10);
+    print_ends(2, 1, 520, 520, -1, 300, 300);
+    print_ends(3, 20, 130, 130, 3, 40, 40);
+    print_ends(2, 1, 3, 4100, -1, 1, 10);
 
     const int ex[][2] = {{17, 16}, {17, 4}, {13, 12}, {20, 19}, {16, 15}, {16, 0}, {5, 4}, {2, 1}, {31, 9}, {40, 7}};
     for (const auto& e : ex) {
