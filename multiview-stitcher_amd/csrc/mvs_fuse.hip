@@ -27,14 +27,16 @@
 #include "mvs_bin_dev.h"
 #include "mvs_dct_dev.h"
 #include "mvs_fuse_tr.h"
+#include "mvs_fuse_chunk_plan.h"
 
 #include <cmath>
 #include <cstring>
 #include <type_traits>
 
+using namespace mvs_fuse_chunk_plan;      // brick constants, view geometry, route and layouts of a chunk
+
 namespace {
 
-constexpr int kBrickX = 64;      // voxels along x per brick (16 lanes x 4 voxels)
 constexpr int kVPT = 4;          // voxels per thread along x
 constexpr int kLdsTables = 8;    // blend tables staged in LDS per pass
 
@@ -290,10 +292,6 @@ __device__ __forceinline__ void store_row4(TOut* out, long long row, int x0, int
 // a lane 4 consecutive voxels: inputs arrive as (unaligned) 8/16-byte vector loads per stencil
 // row, the result leaves as one aligned 8/16-byte store.
 // =============================================================================================
-constexpr int kTrBrickX = 256;   // voxels along x per wavefront (64 lanes x 4)
-constexpr int kTrRows = 4;       // consecutive y rows per wavefront
-constexpr int kTrPlanes = 4;     // z planes per workgroup (one per wavefront)
-
 #define MVS_GLOBAL __attribute__((address_space(1)))
 
 template <typename T> struct RowVec;
@@ -333,7 +331,6 @@ __device__ __forceinline__ void row_taps(const MVS_GLOBAL TIn* p, bool fracx, fl
 }
 
 constexpr int kRowValid = 1, kRowInside = 2, kRowAllOne = 4, kRowXTab = 8;
-constexpr int kXTabMargin = 4;   // table entries kept on either side of [lo_x, hi_x] (a lane reads 4 consecutive ones)
 constexpr int kCand = 16;   // candidate views evaluated per round (16 views x 4 rows = 64 lanes)
 
 
@@ -447,8 +444,6 @@ __device__ __forceinline__ void row_refetch(__amdgpu_buffer_rsrc_t r, int o, uns
         for (int j = 0; j < 5; ++j) w[j] = __float_as_uint(v[j]);
     }
 }
-
-constexpr int kTrGroups = 8;   // row groups (of kTrRows rows) a wavefront walks with one culled view list
 
 // Wavefront-independent fast-path kernel: no hand-offs between wavefronts, no barriers.
 // Each wavefront owns a column of kTrGroups x kTrRows consecutive y rows x 256 voxels of one z plane.
@@ -809,108 +804,6 @@ __global__ __launch_bounds__(256) void fuse_tr_kernel(TrParams P) {
     }
 }
 
-// ---- host side of the fast path ---------------------------------------------------------------
-// c(i) = fl(i + off) is what the generic kernel (and scipy) test against [0, n-1] for an identity
-// matrix; it is monotone in i, so the in-bounds set is an integer interval found exactly here.
-// Index frame (mvs_fuse_opts_t.index_origin): `off` refers to frame index i = chunk index + org and to the whole view's pixel
-// grid, in which the slab starts at pixel `ioff`: in bounds iff ioff <= fl(i + off) <= ioff + n - 1.
-static void exact_valid_range(double off, int n, int n_out, int* lo_out, int* hi_out, long long org = 0, long long ioff = 0) {
-    auto c = [off](long long i) { return (double)i + off; };
-    const double cmin = (double)ioff, cmax = (double)(ioff + n - 1);
-    long long lo = (long long)ceil(cmin - off);
-    while (c(lo - 1) >= cmin) --lo;
-    while (c(lo) < cmin) ++lo;
-    long long hi = (long long)floor(cmax - off);
-    while (c(hi + 1) <= cmax) ++hi;
-    while (c(hi) > cmax) --hi;
-    lo -= org;
-    hi -= org;
-    if (lo < 0) lo = 0;
-    if (hi > n_out - 1) hi = n_out - 1;
-    *lo_out = (int)std::min<long long>(lo, 0x7fffffff);
-    *hi_out = (int)std::max<long long>(hi, -1);   // lo > hi: the view never contributes
-}
-
-// Decide whether a view qualifies for the translation fast path and derive its constants.
-static void prepare_translation_view(DevView* d, int order, int fusion, const int64_t chunk_shape[3], size_t elem_size,
-                                     const int64_t* org = nullptr, const int64_t* ioff = nullptr) {
-    static const int64_t zero3[3] = {0, 0, 0};
-    if (!org) org = zero3;
-    if (!ioff) ioff = zero3;
-    d->tr_ok = 0;
-    static const double I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    for (int k = 0; k < 9; ++k)
-        if (d->m[k] != I9[k]) return;
-    const int n[3] = {d->nz, d->ny, d->nx};
-    for (int k = 0; k < 3; ++k) {
-        if (!(fabs(d->off[k]) < 1048576.0) || n[k] > 65536 || chunk_shape[k] > 65536) return;
-        if (std::llabs(org[k]) > (1 << 24) || std::llabs(ioff[k]) > (1 << 24)) return;
-        if (!(fabs(d->off[k] + (double)(org[k] - ioff[k])) < 65536.0)) return;
-    }
-    if (fusion == MVS_FUSE_WEIGHTED_AVERAGE) {
-        const int offd[6] = {1, 2, 3, 5, 6, 7};
-        for (int k : offd)
-            if (d->wm[k] != 0.0) return;
-        // closed-form check of the support table: edt == min_d(ws_d * tent(i_d))
-        const int nz = d->wnz;
-        float sz = INFINITY, sy, sx;
-        if (nz == 5) {
-            sz = d->edt[(1 * 5 + 2) * 5 + 2];
-            sy = d->edt[(2 * 5 + 1) * 5 + 2];
-            sx = d->edt[(2 * 5 + 2) * 5 + 1];
-        } else {
-            sy = d->edt[1 * 5 + 2];
-            sx = d->edt[2 * 5 + 1];
-        }
-        for (int i = 0; i < nz; ++i)
-            for (int j = 0; j < 5; ++j)
-                for (int k = 0; k < 5; ++k) {
-                    float t = fminf(sy * (float)std::min(j, 4 - j), sx * (float)std::min(k, 4 - k));
-                    if (nz == 5) t = fminf(t, sz * (float)std::min(i, 4 - i));
-                    if (t != d->edt[(i * 5 + j) * 5 + k]) return;
-                }
-        d->ws[0] = (nz == 5) ? sz : 0.f;
-        d->ws[1] = sy;
-        d->ws[2] = sx;
-        for (int k = 0; k < 3; ++k) {
-            d->sup_k[k] = 0.f;
-            d->sup_ilo[k] = d->sup_ihi[k] = 0;
-            d->sup_flo[k] = d->sup_fhi[k] = 0.f;
-            if (k == 0 && nz == 1) continue;
-            const double wm = d->wm[k * 4], wo = d->woff[k];
-            if (!(wm > 0.0)) return;
-            const double lo = -wo / wm;          // frame index where the support coordinate is 0
-            const double hi = (4.0 - wo) / wm;   // ... and 4
-            if (!(fabs(lo) < 1e6) || !(fabs(hi) < 1e6)) return;
-            d->sup_k[k] = (float)wm;
-            d->sup_ilo[k] = (int)((long long)floor(lo) - org[k]);     // chunk index = frame index - org (integers: exact)
-            d->sup_flo[k] = (float)(lo - floor(lo));
-            d->sup_ihi[k] = (int)((long long)ceil(hi) - org[k]);
-            d->sup_fhi[k] = (float)(ceil(hi) - hi);
-        }
-    }
-    d->span = (long long)(d->nz - 1) * d->stride_z + (long long)(d->ny - 1) * d->stride_y + d->nx;
-    if (d->stride_z > 0x7fffffffLL || d->stride_y > 0x7fffffffLL || d->stride_z < 0 || d->stride_y < 0) return;
-    // 32-bit signed byte offsets in the buffer loads; windows may start up to a few rows before / after the slab
-    if ((long long)d->span * (long long)elem_size >= (1ll << 31) - (1ll << 27) || (long long)d->stride_z * (long long)elem_size >= (1ll << 26)) return;
-    for (int k = 0; k < 3; ++k) {
-        const double off = d->off[k];
-        // slab pixel = chunk index + org + off - ioff: the integer parts are combined as integers, so the fraction (and with
-        // it every interpolation weight) does not depend on which chunk / slab the voxel is seen through
-        if (order == 0) {
-            d->io[k] = (int)((long long)floor(off + 0.5) + org[k] - ioff[k]);
-            d->fw[k] = 0.f;
-        } else {
-            const double f = floor(off);
-            d->io[k] = (int)((long long)f + org[k] - ioff[k]);
-            d->fw[k] = (float)(off - f);
-        }
-        exact_valid_range(off, n[k], (int)chunk_shape[k], &d->lo[k], &d->hi[k], org[k], ioff[k]);
-    }
-    d->pad[0] = (order == 0) ? 0.f : 1.f;   // carried into TrView.linear
-    d->tr_ok = 1;
-}
-
 // Single-view resample to float32 with an arbitrary cval (transformation.py:136-139).
 template <typename TIn, int ORDER>
 __global__ __launch_bounds__(256) void resample_kernel(DevView V, float* out, int oz, int oy, int ox, float cval, int z0, int y0, int x0) {
@@ -1211,27 +1104,6 @@ __global__ __launch_bounds__(256) void blend_batch_kernel(const DevView* __restr
     }
 }
 
-int fill_dev_view(MvsContext* c, const mvs_view_t& v, int ndim, const void* dev_data, DevView* d) {
-    if (v.stride[2] != 1) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "view stride along x must be 1");
-    for (int k = 0; k < 3; ++k)
-        if (v.shape[k] < 1 || v.shape[k] > 0x7fffffffLL)
-            return mvs_fail(c, MVS_ERR_INVALID_ARG, "view shape[%d]=%lld out of range", k, (long long)v.shape[k]);
-    d->data = dev_data;
-    d->stride_z = v.stride[0];
-    d->stride_y = v.stride[1];
-    d->nz = (int)v.shape[0];
-    d->ny = (int)v.shape[1];
-    d->nx = (int)v.shape[2];
-    d->wnz = (ndim == 3) ? 5 : 1;
-    memcpy(d->m, v.matrix, sizeof(d->m));
-    memcpy(d->off, v.offset, sizeof(d->off));
-    memcpy(d->wm, v.w_matrix, sizeof(d->wm));
-    memcpy(d->woff, v.w_offset, sizeof(d->woff));
-    memcpy(d->edt, v.edt, sizeof(d->edt));
-    d->pad[0] = d->pad[1] = d->pad[2] = 0.f;
-    return MVS_OK;
-}
-
 template <typename TIn, typename TOut>
 void launch_fuse(const FuseParams& P, int order, int fusion, int nblocks, hipStream_t s) {
 #define MVS_LAUNCH(O, F) hipLaunchKernelGGL((fuse_kernel<TIn, TOut, O, F>), dim3(nblocks), dim3(256), 0, s, P)
@@ -1250,30 +1122,6 @@ void launch_fuse(const FuseParams& P, int order, int fusion, int nblocks, hipStr
 #undef MVS_LAUNCH
 }
 
-static void fill_tr_view(const DevView& d, TrView* t) {
-    memset(t, 0, sizeof(*t));
-    for (int k = 0; k < 3; ++k) {
-        t->lo[k] = d.lo[k];
-        t->hi[k] = d.hi[k];
-        t->io[k] = d.io[k];
-        t->fw[k] = d.fw[k];
-        t->sup_ilo[k] = d.sup_ilo[k];
-        t->sup_ihi[k] = d.sup_ihi[k];
-        t->sup_flo[k] = d.sup_flo[k];
-        t->sup_fhi[k] = d.sup_fhi[k];
-        t->sup_k[k] = d.sup_k[k];
-        t->ws[k] = d.ws[k];
-    }
-    t->wnz = d.wnz;
-    t->n[0] = d.nz; t->n[1] = d.ny; t->n[2] = d.nx;
-    t->linear = d.pad[0] != 0.f ? 1 : 0;
-    t->data = (unsigned long long)d.data;
-    t->span = d.span;
-    t->stride_y = (int)d.stride_y;
-    t->stride_z = (int)d.stride_z;
-    t->xtab_off = 0;
-}
-
 template <typename TIn, typename TOut>
 void launch_fuse_tr(const TrParams& P, int fusion, int nblocks, hipStream_t s) {
     if (fusion == MVS_FUSE_WEIGHTED_AVERAGE)
@@ -1286,15 +1134,14 @@ void launch_fuse_tr(const TrParams& P, int fusion, int nblocks, hipStream_t s) {
 
 }  // namespace
 
-// Translation-path record of a view for callers outside this file (mvs_gauss.hip): prepare_translation_view + the chunk frame +
-// fill_tr_view.  Returns false when the view does not qualify (rotated / scaled views, a support table that is not the closed form).
-bool mvs_prepare_tr_view(DevView* d, int order, const int64_t chunk_shape[3], size_t elem_size, const int64_t org[3], const int64_t ioff[3],
-                         TrView* out) {
-    prepare_translation_view(d, order, MVS_FUSE_WEIGHTED_AVERAGE, chunk_shape, elem_size, org, ioff);
-    mvs_view_to_chunk_frame(d, org, ioff);
-    if (!d->tr_ok) return false;
-    fill_tr_view(*d, out);
-    return true;
+// Device record of a view (fill_dev_view, mvs_fuse_chunk_plan.h) behind the two checks every kernel that reads one relies on
+int mvs_fill_dev_view(MvsContext* c, const mvs_view_t& v, int ndim, const void* dev_data, DevView* d) {
+    if (v.stride[2] != 1) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "view stride along x must be 1");
+    for (int k = 0; k < 3; ++k)
+        if (v.shape[k] < 1 || v.shape[k] > 0x7fffffffLL)
+            return mvs_fail(c, MVS_ERR_INVALID_ARG, "view shape[%d]=%lld out of range", k, (long long)v.shape[k]);
+    fill_dev_view(v, ndim, dev_data, d);
+    return MVS_OK;
 }
 
 // What every chunk entry requires of its arguments; `what` is the entry's name, the prefix of the messages.
@@ -1368,7 +1215,7 @@ int mvs_stage_tile_views(MvsContext* c, const mvs_view_t* const* views, int n, i
         if (rc) return rc;
         if (dev_data) dev_data[i] = dptr;
         if (!dviews) continue;
-        rc = fill_dev_view(c, *views[i], ndim, dptr, dviews[i]);
+        rc = mvs_fill_dev_view(c, *views[i], ndim, dptr, dviews[i]);
         if (rc) return rc;
         dviews[i]->tr_ok = 0;
     }
@@ -1387,196 +1234,223 @@ extern "C" int mvs_fuse_chunk(int device, const mvs_view_t* views, int32_t n_vie
     return mvs_fuse_chunk_impl(c, views, n_views, opts, out, nullptr, false);
 }
 
-// The entry has checked the arguments (mvs_check_chunk_args), holds the context's lock and has set the device.
-// `dct` (mvs_fuse_chunk_dct): weighted average without content-based weights, through the generic kernel only
-int mvs_fuse_chunk_impl(MvsContext* c, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out,
-                        const DctLookup* dct, bool keep_start) {
-    int rc;
-    const int dtype = views[0].dtype;
-    int64_t os[3];
-    for (int k = 0; k < 3; ++k) os[k] = opts->out_shape[k] - 2 * opts->trim[k];
+// ---- one chunk of mvs_fuse_chunk: the call's arguments, its plan (mvs_fuse_chunk_plan.h), where its records lie and what the steps
+// derive.  The steps queue on the context's stream in the order the driver calls them; none allocates on the heap (the records are
+// built in the pinned staging slot). ----
+namespace {
+struct ChunkCall {
+    MvsContext* c; const mvs_view_t* views; int n_views; const mvs_fuse_opts_t* opts; void* out; const DctLookup* dct; bool keep_start;
+    int dtype; size_t es, host_bytes, out_bytes;
+    int64_t os[3];                                  // the trimmed result
+    ParamBlock B; DevView *hviews, *dviews;         // the parameter block in the pinned slot and in scratch slot 2 ...
+    TrView* htr; const TrView* dtr; const int* dcull;      // ... and its parts
+    Route R; size_t xtab_total;
+    void* dout;                                     // the result on the device
+    bool done;                                      // the row or the region kernels took the chunk
+    int* overflow;                                  // device word the column kernel raises
+};
 
-    if (opts->weights == MVS_WEIGHTS_CONTENT_BASED) {
+// Shapes and element size.  *handed_off: content-based weights are another driver's (mvs_gauss.hip), whose code is returned.
+int chunk_begin(ChunkCall& K, MvsContext* c, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out, const DctLookup* dct,
+                bool keep_start, bool* handed_off) {
+    K.c = c; K.views = views; K.n_views = n_views; K.opts = opts; K.out = out; K.dct = dct; K.keep_start = keep_start;
+    K.dtype = views[0].dtype; K.es = mvs_dtype_size(K.dtype);
+    for (int k = 0; k < 3; ++k) K.os[k] = opts->out_shape[k] - 2 * opts->trim[k];
+    K.xtab_total = 0; K.done = false; K.overflow = nullptr;
+    *handed_off = opts->weights == MVS_WEIGHTS_CONTENT_BASED;
+    if (*handed_off) {
         if (opts->fusion != MVS_FUSE_WEIGHTED_AVERAGE)
             return mvs_fail(c, MVS_ERR_UNSUPPORTED, "content_based weights need weighted_average fusion");
         return mvs_fuse_content_based(c, views, n_views, opts, out);
     }
     if (opts->weights != MVS_WEIGHTS_NONE)
         return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_fuse_chunk: unknown weights %d", opts->weights);
+    return MVS_OK;
+}
 
-    // stage host slabs into device scratch (slot 0)
-    const size_t es = mvs_dtype_size(dtype);
-    size_t host_bytes = 0;
-    rc = mvs_stage_views_bytes(c, views, n_views, es, &host_bytes);
+// Host slabs go through scratch slot 0; every view's records are built in the pinned slot, and with all of them the route is known.
+int chunk_stage_views(ChunkCall& K) {
+    MvsContext* c = K.c;
+    const mvs_fuse_opts_t* opts = K.opts;
+    int rc = mvs_stage_views_bytes(c, K.views, K.n_views, K.es, &K.host_bytes);
     if (rc) return rc;
     char* slab_base = nullptr;
-    if (host_bytes) {
-        slab_base = (char*)mvs_scratch(c, 0, host_bytes);
-        if (!slab_base) return mvs_alloc_failed(c);
-    }
-    const size_t views_bytes = align_up(sizeof(DevView) * (size_t)n_views);
-    const size_t cull_bytes = align_up(sizeof(int) * 6 * (size_t)n_views);
-    const size_t params_bytes = views_bytes + cull_bytes + sizeof(TrView) * (size_t)n_views;
-    DevView* hviews = (DevView*)mvs_pinned(c, params_bytes);
-    if (!hviews) return mvs_alloc_failed(c);
-    DevView* dviews = (DevView*)mvs_scratch(c, 2, params_bytes);
-    if (!dviews) return mvs_alloc_failed(c);
+    if (K.host_bytes && !(slab_base = (char*)mvs_scratch(c, 0, K.host_bytes))) return mvs_alloc_failed(c);
+    K.B = param_block(K.n_views);
+    if (!(K.hviews = (DevView*)mvs_pinned(c, K.B.total))) return mvs_alloc_failed(c);
+    if (!(K.dviews = (DevView*)mvs_scratch(c, 2, K.B.total))) return mvs_alloc_failed(c);
+    int* hcull = (int*)((char*)K.hviews + K.B.cull);
+    K.htr = (TrView*)((char*)K.hviews + K.B.tr);
+    K.dcull = (const int*)((const char*)K.dviews + K.B.cull);
+    K.dtr = (const TrView*)((const char*)K.dviews + K.B.tr);
 
     size_t cursor = 0;
-    for (int i = 0; i < n_views; ++i) {
+    bool all_tr_ok = true;
+    for (int i = 0; i < K.n_views; ++i) {
         const void* dptr;
-        rc = mvs_stage_view(c, views[i], es, slab_base, &cursor, &dptr);
+        rc = mvs_stage_view(c, K.views[i], K.es, slab_base, &cursor, &dptr);
         if (rc) return rc;
-        rc = fill_dev_view(c, views[i], opts->ndim, dptr, &hviews[i]);
+        rc = mvs_fill_dev_view(c, K.views[i], opts->ndim, dptr, &K.hviews[i]);
         if (rc) return rc;
-        prepare_translation_view(&hviews[i], opts->order, opts->fusion, opts->out_shape, es, opts->index_origin, views[i].index_offset);
-        mvs_view_to_chunk_frame(&hviews[i], opts->index_origin, views[i].index_offset);
+        if (!tr_view_in_chunk(&K.hviews[i], opts->order, opts->fusion, opts->out_shape, K.es, opts->index_origin, K.views[i].index_offset, &K.htr[i]))
+            all_tr_ok = false;
     }
-    bool use_tr = !c->force_generic && !dct;
-    for (int i = 0; i < n_views && use_tr; ++i) use_tr = hviews[i].tr_ok != 0;
-    // Float tiles with linear interpolation: scipy multiplies the second tap of every axis by its (possibly zero) weight,
-    // so a NaN there poisons the sample.  Only the row kernels (weighted average) and the generic kernel read all taps;
-    // the column / region kernels read one tap at integer offsets, so they are not used for such tiles.
-    const bool nan_exact = (dtype == MVS_F32 && opts->order == 1);
-    if (nan_exact && opts->fusion != MVS_FUSE_WEIGHTED_AVERAGE) use_tr = false;
-    size_t xtab_total = 0;
-    int* hcull = (int*)((char*)hviews + views_bytes);
-    TrView* htr = (TrView*)((char*)hviews + views_bytes + cull_bytes);
-    if (use_tr)
-        for (int i = 0; i < n_views; ++i) {
-            for (int k = 0; k < 3; ++k) {
-                hcull[(2 * k) * n_views + i] = hviews[i].lo[k];
-                hcull[(2 * k + 1) * n_views + i] = hviews[i].hi[k];
-            }
-            fill_tr_view(hviews[i], &htr[i]);
-            htr[i].xtab_off = (int)xtab_total + kXTabMargin;
-            xtab_total += (size_t)std::max(hviews[i].hi[2] - hviews[i].lo[2] + 1, 0) + 2 * kXTabMargin;
+    K.R = route(RouteInputs{K.dtype, opts->order, opts->fusion, K.dct != nullptr, all_tr_ok, c->force_generic, c->rows_v1, c->no_regions, K.n_views});
+    for (int i = 0; i < K.n_views && K.R.use_tr; ++i) {
+        for (int k = 0; k < 3; ++k) {
+            hcull[(2 * k) * K.n_views + i] = K.hviews[i].lo[k];
+            hcull[(2 * k + 1) * K.n_views + i] = K.hviews[i].hi[k];
         }
-    { const int rcu = mvs_upload_small(c, dviews, hviews, params_bytes); if (rcu) return rcu; }
-    mvs_pinned_mark(c, 0);
-
-    const size_t out_bytes = (size_t)os[0] * os[1] * os[2] * es;
-    void* dout = out;
-    if (opts->out_mem == MVS_MEM_HOST) {
-        dout = mvs_scratch(c, 1, out_bytes);
-        if (!dout) return mvs_alloc_failed(c);
+        K.htr[i].xtab_off = xtab_add(&K.xtab_total, K.hviews[i].lo[2], K.hviews[i].hi[2]);
     }
+    return MVS_OK;
+}
 
+// mvs_pinned_mark FOLLOWS the upload: the slot is busy until it has run
+int chunk_upload_params(ChunkCall& K) {
+    const int rc = mvs_upload_small(K.c, K.dviews, K.hviews, K.B.total);
+    if (rc) return rc;
+    mvs_pinned_mark(K.c, 0);
+    return MVS_OK;
+}
+
+int chunk_output(ChunkCall& K) {
+    K.out_bytes = (size_t)K.os[0] * K.os[1] * K.os[2] * K.es;
+    K.dout = K.out;
+    if (K.opts->out_mem == MVS_MEM_HOST && !(K.dout = mvs_scratch(K.c, 1, K.out_bytes))) return mvs_alloc_failed(K.c);
+    return MVS_OK;
+}
+
+int chunk_grid(ChunkCall& K, GridKind kind, BrickGrid* g) {
+    *g = brick_grid(kind, K.os);
+    return g->fits_one_launch() ? MVS_OK : mvs_fail(K.c, MVS_ERR_UNSUPPORTED, "chunk too large for one launch");
+}
+
+// Direct-load row-owning kernels.  Float tiles take them by default: they read both taps of every axis even at integer offsets, so a
+// NaN next to a tap poisons the sample exactly as scipy's zero-weight multiply does (the region kernels read one tap there).  Other
+// dtypes: opt-in ("rows_v1"), the region kernels are faster so far.
+int chunk_try_rows(ChunkCall& K) {
+    const int rc = mvs_fuse_rows(K.c, K.htr, K.dtr, K.n_views, K.dtype, K.dout, K.os, K.opts->trim, &K.done);
+    if (rc) return rc;
+    if (K.done) K.c->fuse_rows_chunks += 1;
+    return MVS_OK;
+}
+
+int chunk_try_regions(ChunkCall& K) {
+    const int rc = mvs_fuse_regions(K.c, K.htr, K.dtr, K.n_views, K.dtype, K.dout, K.os, K.opts->trim, &K.done);
+    if (rc) return rc;
+    if (K.done) K.c->fuse_region_chunks += 1;
+    return MVS_OK;
+}
+
+// Column kernel on the grid the driver has checked: the x-weight table and the overflow word in scratch slot 3
+int chunk_column(ChunkCall& K) {
+    MvsContext* c = K.c;
+    const BrickGrid G = brick_grid(family_grid(kColumn), K.os);
+    TrParams T;
+    T.views = K.dtr;
+    T.cull = K.dcull;
+    T.nviews = K.n_views;
+    T.out = K.dout;
+    T.oz = (int)K.os[0]; T.oy = (int)K.os[1]; T.ox = (int)K.os[2];
+    T.tz = (int)K.opts->trim[0]; T.ty = (int)K.opts->trim[1]; T.tx = (int)K.opts->trim[2];
+    T.nbz = G.nbz; T.nby = G.nby; T.nbx = G.nbx;
+    T.is3d = (K.os[0] > 1) ? 1 : 0;
+    T.ablate = c->ablate;
+    float* xtab = (float*)mvs_scratch(c, 3, xtab_bytes(K.xtab_total));
+    if (!xtab) return mvs_alloc_failed(c);
+    T.xtab = xtab;
+    T.overflow = K.overflow = (int*)(xtab + xtab_overflow_at(K.xtab_total));
+    MVS_HIP_TRY(c, hipMemsetAsync(T.overflow, 0, sizeof(int), c->stream));
+    if (K.opts->fusion == MVS_FUSE_WEIGHTED_AVERAGE) {
+        hipLaunchKernelGGL(xweight_table_kernel, dim3(16, K.n_views), dim3(256), 0, c->stream, T.views, K.n_views, xtab);
+    }
+    mvs_dispatch_dtype(K.dtype, [&](auto tag) {
+        using E = decltype(tag);
+        launch_fuse_tr<E, E>(T, K.opts->fusion, (int)G.nblocks, c->stream);
+    });
+    c->fuse_column_chunks += 1;
+    return MVS_OK;
+}
+
+// Generic kernel on its own grid: the chunk's family, or the one that redoes what another gave up on
+int chunk_generic(ChunkCall& K) {
+    MvsContext* c = K.c;
+    BrickGrid G;
+    { const int rc = chunk_grid(K, family_grid(kGeneric), &G); if (rc) return rc; }
     FuseParams P;
-    P.views = dviews;
-    P.nviews = n_views;
-    P.out = dout;
-    P.oz = (int)os[0]; P.oy = (int)os[1]; P.ox = (int)os[2];
-    P.tz = (int)opts->trim[0]; P.ty = (int)opts->trim[1]; P.tx = (int)opts->trim[2];
-    P.cull = (const int*)((const char*)dviews + views_bytes);
+    P.views = K.dviews;
+    P.nviews = K.n_views;
+    P.out = K.dout;
+    P.oz = (int)K.os[0]; P.oy = (int)K.os[1]; P.ox = (int)K.os[2];
+    P.tz = (int)K.opts->trim[0]; P.ty = (int)K.opts->trim[1]; P.tx = (int)K.opts->trim[2];
+    P.nbz = G.nbz; P.nby = G.nby; P.nbx = G.nbx;
+    P.bz = G.bz; P.by = G.by;
+    P.cull = K.dcull;
     P.ablate = c->ablate;
-    P.dct = dct ? *dct : DctLookup{};
-    long long nblocks = 0;
-    auto set_brick_grid = [&](bool tr) {
-        if (tr) {
-            P.bz = (os[0] > 1) ? kTrPlanes : 1;
-            P.by = (os[0] > 1) ? kTrRows * kTrGroups : 4 * kTrRows * kTrGroups;
-        } else {
-            P.bz = (os[0] > 1) ? 4 : 1;
-            P.by = (os[0] > 1) ? 4 : 16;
-        }
-        const int brick_x = tr ? kTrBrickX : kBrickX;
-        P.nbz = (P.oz + P.bz - 1) / P.bz;
-        P.nby = (P.oy + P.by - 1) / P.by;
-        P.nbx = (P.ox + brick_x - 1) / brick_x;
-        nblocks = (long long)P.nbz * P.nby * P.nbx;
-    };
-    auto launch_generic = [&] {
-        mvs_dispatch_dtype(dtype, [&](auto tag) {
-            using E = decltype(tag);
-            launch_fuse<E, E>(P, opts->order, opts->fusion, (int)nblocks, c->stream);
-        });
-    };
-    set_brick_grid(use_tr);
-    if (nblocks > 0x7fffffffLL) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "chunk too large for one launch");
+    P.dct = K.dct ? *K.dct : DctLookup{};
+    mvs_dispatch_dtype(K.dtype, [&](auto tag) {
+        using E = decltype(tag);
+        launch_fuse<E, E>(P, K.opts->order, K.opts->fusion, (int)G.nblocks, c->stream);
+    });
+    c->fuse_generic_chunks += 1;
+    return MVS_OK;
+}
 
-    if (!keep_start) MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    int* tr_overflow_ptr = nullptr;
-    bool regions_done = false;
-    // counter "fuse_plan_ms" speaks of THIS chunk: a family that does not plan it must not leave the time of an earlier chunk behind
-    mvs_rows_clear_plan_ms(c);
-    mvs_regions_clear_plan_ms(c);
-    if (!regions_done && use_tr && opts->fusion == MVS_FUSE_WEIGHTED_AVERAGE && (c->rows_v1 || (dtype == MVS_F32 && opts->order == 1))) {
-        // direct-load row-owning kernels.  Float tiles take them by default: they read both taps of every axis even at
-        // integer offsets, so a NaN next to a tap poisons the sample exactly as scipy's zero-weight multiply does
-        // (the region kernels read one tap there).  Other dtypes: opt-in ("rows_v1"), the region kernels are faster so far.
-        rc = mvs_fuse_rows(c, htr, (const TrView*)((const char*)dviews + views_bytes + cull_bytes), n_views, dtype, dout, os,
-                           opts->trim, &regions_done);
-        if (rc) return rc;
-        if (regions_done) c->fuse_rows_chunks += 1;
-    }
-    if (!regions_done && nan_exact && use_tr) {   // float tiles the row kernels could not take: generic kernel
-        use_tr = false;
-        set_brick_grid(false);
-        if (nblocks > 0x7fffffffLL) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "chunk too large for one launch");
-    }
-    if (!regions_done && use_tr && opts->fusion == MVS_FUSE_WEIGHTED_AVERAGE && !c->no_regions) {
-        rc = mvs_fuse_regions(c, htr, (const TrView*)((const char*)dviews + views_bytes + cull_bytes), n_views, dtype, dout, os,
-                              opts->trim, &regions_done);
-        if (rc) return rc;
-        if (regions_done) c->fuse_region_chunks += 1;
-    }
-    if (regions_done) {
-        // fused by the row or region kernels
-    } else if (use_tr) {
-        TrParams T;
-        T.views = (const TrView*)((const char*)dviews + views_bytes + cull_bytes);
-        T.cull = P.cull;
-        T.nviews = n_views;
-        T.out = dout;
-        T.oz = P.oz; T.oy = P.oy; T.ox = P.ox;
-        T.tz = P.tz; T.ty = P.ty; T.tx = P.tx;
-        T.nbz = P.nbz; T.nby = P.nby; T.nbx = P.nbx;
-        T.is3d = (os[0] > 1) ? 1 : 0;
-        T.ablate = c->ablate;
-        float* xtab = (float*)mvs_scratch(c, 3, (xtab_total + 64) * sizeof(float) + 256);
-        if (!xtab) return mvs_alloc_failed(c);
-        T.xtab = xtab;
-        T.overflow = (int*)(xtab + xtab_total + 64);
-        MVS_HIP_TRY(c, hipMemsetAsync(T.overflow, 0, sizeof(int), c->stream));
-        tr_overflow_ptr = T.overflow;
-        if (opts->fusion == MVS_FUSE_WEIGHTED_AVERAGE) {
-            hipLaunchKernelGGL(xweight_table_kernel, dim3(16, n_views), dim3(256), 0, c->stream, T.views, n_views, xtab);
-        }
-        mvs_dispatch_dtype(dtype, [&](auto tag) {
-            using E = decltype(tag);
-            launch_fuse_tr<E, E>(T, opts->fusion, (int)nblocks, c->stream);
-        });
-        c->fuse_column_chunks += 1;
-    } else {
-        launch_generic();
-        c->fuse_generic_chunks += 1;
-    }
+// A column that met more than 64 views raised the word: redo the chunk with the generic kernel (bricks of 4x4x64)
+int chunk_overflow_redo(ChunkCall& K) {
+    MvsContext* c = K.c;
+    int ovf = 0;
+    MVS_HIP_TRY(c, hipMemcpyAsync(&ovf, K.overflow, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!ovf) return MVS_OK;
+    const int rc = chunk_generic(K);
+    if (rc) return rc;
     MVS_HIP_TRY(c, hipGetLastError());
-    if (use_tr && !regions_done && n_views > 64) {
-        int ovf = 0;
-        MVS_HIP_TRY(c, hipMemcpyAsync(&ovf, tr_overflow_ptr, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (ovf) {
-            // a column met more than 64 views: redo the chunk with the generic kernel (bricks of 4x4x64)
-            set_brick_grid(false);
-            if (nblocks > 0x7fffffffLL) return mvs_fail(c, MVS_ERR_UNSUPPORTED, "chunk too large for one launch");
-            launch_generic();
-            c->fuse_generic_chunks += 1;
-            MVS_HIP_TRY(c, hipGetLastError());
-        }
-    }
+    return MVS_OK;
+}
+
+// ev_stop closes the call's timing.  A host result is copied back and waited for; a device result is not waited for unless host slabs
+// were staged through scratch that the next call may overwrite.
+int chunk_finish(ChunkCall& K) {
+    MvsContext* c = K.c;
     MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
     c->timing_valid = true;
-
-    if (opts->out_mem == MVS_MEM_HOST) {
-        MVS_HIP_TRY(c, hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (K.opts->out_mem == MVS_MEM_HOST) {
+        MVS_HIP_TRY(c, hipMemcpyAsync(K.out, K.dout, K.out_bytes, hipMemcpyDeviceToHost, c->stream));
         MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else if (host_bytes) {
-        // host slabs were staged through scratch that the next call may overwrite
+    } else if (K.host_bytes) {
         MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     return MVS_OK;
+}
+}  // namespace
+
+// The entry has checked the arguments (mvs_check_chunk_args), holds the context's lock and has set the device.
+// `dct` (mvs_fuse_chunk_dct): weighted average without content-based weights, through the generic kernel only; that caller has
+// recorded ev_start in front of its own work (keep_start).  The route is the table of route() in mvs_fuse_chunk_plan.h.
+int mvs_fuse_chunk_impl(MvsContext* c, const mvs_view_t* views, int32_t n_views, const mvs_fuse_opts_t* opts, void* out,
+                        const DctLookup* dct, bool keep_start) {
+    ChunkCall K;
+    bool handed_off;
+    int rc = chunk_begin(K, c, views, n_views, opts, out, dct, keep_start, &handed_off);
+    if (rc || handed_off) return rc;
+    if ((rc = chunk_stage_views(K))) return rc;
+    if ((rc = chunk_upload_params(K))) return rc;
+    if ((rc = chunk_output(K))) return rc;
+    BrickGrid first;
+    if ((rc = chunk_grid(K, K.R.first_grid, &first))) return rc;
+
+    if (!keep_start) MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
+    // counter "fuse_plan_ms" speaks of THIS chunk: a family that does not plan it must not leave the time of an earlier chunk behind
+    mvs_rows_clear_plan_ms(c);
+    mvs_regions_clear_plan_ms(c);
+    if (K.R.try_rows && (rc = chunk_try_rows(K))) return rc;
+    if (!K.done && K.R.try_regions && (rc = chunk_try_regions(K))) return rc;
+    if (!K.done && (rc = K.R.fallback == kColumn ? chunk_column(K) : chunk_generic(K))) return rc;
+    MVS_HIP_TRY(c, hipGetLastError());
+    if (!K.done && K.R.read_overflow && (rc = chunk_overflow_redo(K))) return rc;
+    return chunk_finish(K);
 }
 
 namespace {
@@ -1589,7 +1463,7 @@ int stage_single_view(MvsContext* c, const mvs_view_t* view, int ndim, bool need
     mvs_view_t tmp = *view;
     tmp.shape[0] = tmp.shape[1] = tmp.shape[2] = 1;
     tmp.stride[0] = tmp.stride[1] = tmp.stride[2] = 1;
-    return fill_dev_view(c, tmp, ndim, view->data, d);
+    return mvs_fill_dev_view(c, tmp, ndim, view->data, d);
 }
 }  // namespace
 
@@ -1711,10 +1585,6 @@ int mvs_crop_bin_impl(int device, const mvs_view_t* view, const int32_t bin[3], 
 }
 
 // ---- helpers shared with mvs_gauss.hip (content-based weights) --------------------------------
-int mvs_fill_dev_view(MvsContext* c, const mvs_view_t& v, int ndim, const void* dev_data, DevView* d) {
-    return fill_dev_view(c, v, ndim, dev_data, d);
-}
-
 void mvs_launch_resample(MvsContext* c, const DevView& d, int dtype, int order, float cval, float* out, const int64_t shape[3], const int* box0,
                          MvsCropStats* crop_stats, int crop_stats_k) {
     const long long n = (long long)shape[0] * shape[1] * shape[2];
@@ -1810,54 +1680,4 @@ void mvs_launch_boxes_batch(MvsContext* c, const DevView* hviews, const DevView*
         for (int i = 0; i < n_views; ++i) TV.v[i] = tr[i];
         hipLaunchKernelGGL(blend_tr_batch_kernel, dim3(nw), dim3(256), 0, c->stream, TV, W);
     } else if (nw > 0) hipLaunchKernelGGL(blend_batch_kernel, dim3(nw), dim3(256), 0, c->stream, dviews, W);
-}
-
-// Index frame -> chunk frame for the kernels that evaluate the full affine map per voxel (generic fuse kernel, resample,
-// blend): c = M (p + org) + off - ioff = M p + (off + M org - ioff).  (The translation fast path keeps the integer parts apart,
-// see prepare_translation_view; here the last bit of a coordinate may depend on the chunk, as it does in the reference.)
-void mvs_view_to_chunk_frame(DevView* d, const int64_t org[3], const int64_t ioff[3]) {
-    if (!(org[0] | org[1] | org[2] | ioff[0] | ioff[1] | ioff[2])) return;
-    const double o[3] = {(double)org[0], (double)org[1], (double)org[2]};
-    for (int k = 0; k < 3; ++k) {
-        d->off[k] = (((o[0] * d->m[3 * k] + o[1] * d->m[3 * k + 1]) + o[2] * d->m[3 * k + 2]) + d->off[k]) - (double)ioff[k];
-        d->woff[k] = ((o[0] * d->wm[3 * k] + o[1] * d->wm[3 * k + 1]) + o[2] * d->wm[3 * k + 2]) + d->woff[k];
-    }
-}
-
-// Chunk-index box [lo, hi] (inclusive; lo > hi: empty) outside of which view `d` is certainly out of bounds: exact for
-// translations (the interval scipy's in-bounds test yields, as in the fast path), the bounding box of the slab's corners mapped
-// into the chunk (+- 2 voxels) otherwise.
-void mvs_view_chunk_box(const DevView& d, const int64_t shape[3], int lo[3], int hi[3]) {
-    static const double I9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    bool ident = true;
-    for (int k = 0; k < 9; ++k) ident = ident && d.m[k] == I9[k];
-    const int n[3] = {d.nz, d.ny, d.nx};
-    if (ident) {
-        for (int k = 0; k < 3; ++k) {
-            if (!(fabs(d.off[k]) < 1e9)) { lo[k] = 0; hi[k] = (int)shape[k] - 1; continue; }
-            exact_valid_range(d.off[k], n[k], (int)shape[k], &lo[k], &hi[k]);
-        }
-        return;
-    }
-    const double* m = d.m;
-    const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-    for (int k = 0; k < 3; ++k) { lo[k] = 0; hi[k] = (int)shape[k] - 1; }
-    if (!(fabs(det) > 1e-12)) return;
-    const double inv[9] = {(m[4] * m[8] - m[5] * m[7]) / det, (m[2] * m[7] - m[1] * m[8]) / det, (m[1] * m[5] - m[2] * m[4]) / det,
-                           (m[5] * m[6] - m[3] * m[8]) / det, (m[0] * m[8] - m[2] * m[6]) / det, (m[2] * m[3] - m[0] * m[5]) / det,
-                           (m[3] * m[7] - m[4] * m[6]) / det, (m[1] * m[6] - m[0] * m[7]) / det, (m[0] * m[4] - m[1] * m[3]) / det};
-    double bl[3] = {1e300, 1e300, 1e300}, bh[3] = {-1e300, -1e300, -1e300};
-    for (int q = 0; q < 8; ++q) {
-        const double in[3] = {(q & 4) ? (double)(n[0] - 1) - d.off[0] : -d.off[0], (q & 2) ? (double)(n[1] - 1) - d.off[1] : -d.off[1],
-                              (q & 1) ? (double)(n[2] - 1) - d.off[2] : -d.off[2]};
-        for (int k = 0; k < 3; ++k) {
-            const double o = inv[3 * k] * in[0] + inv[3 * k + 1] * in[1] + inv[3 * k + 2] * in[2];
-            bl[k] = std::min(bl[k], o);
-            bh[k] = std::max(bh[k], o);
-        }
-    }
-    for (int k = 0; k < 3; ++k) {
-        lo[k] = (int)std::max(0.0, std::floor(bl[k]) - 2.0);
-        hi[k] = (int)std::min((double)shape[k] - 1.0, std::ceil(bh[k]) + 2.0);
-    }
 }

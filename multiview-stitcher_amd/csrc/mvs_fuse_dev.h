@@ -13,7 +13,8 @@ struct DevView {
     double wm[9];
     double woff[3];
     float edt[125];
-    // ---- translation fast path (valid when tr_ok): matrix == I, diagonal support map ----
+    // ---- translation fast path (valid when tr_ok): matrix == I, diagonal support map; set by prepare_translation_view
+    // (mvs_fuse_chunk_plan.h) ----
     int tr_ok;
     int io[3];        // input index = chunk index + io
     float fw[3];      // fractional interpolation weights (0 => single tap on that axis)
@@ -38,6 +39,7 @@ int mvs_stage_views_bytes(MvsContext* c, const mvs_view_t* views, int n_views, s
 // ... then, per view, queue its upload at area + *cursor; *dev_data = where the kernels read the view (v.data for a device view)
 int mvs_stage_view(MvsContext* c, const mvs_view_t& v, size_t es, char* area, size_t* cursor, const void** dev_data);
 
+// the record of a view that reads its data at dev_data (checks the x stride and the shape; the fill itself: mvs_fuse_chunk_plan.h)
 int mvs_fill_dev_view(MvsContext* c, const mvs_view_t& v, int ndim, const void* dev_data, DevView* d);
 
 // ---- the prologue of the entries that take one or two whole tiles (metrics, PSF extraction, intensity, shading, mvs_resample) ----
@@ -59,12 +61,10 @@ struct TrView;
 void mvs_launch_boxes_batch(MvsContext* c, const DevView* hviews, const DevView* dviews, int n_views, int dtype, int order, float cval,
                             float* const* res_out, float* const* blend_out, const int64_t (*shapes)[3], const int (*box0)[3],
                             const TrView* tr = nullptr);
-bool mvs_prepare_tr_view(DevView* d, int order, const int64_t chunk_shape[3], size_t elem_size, const int64_t org[3], const int64_t ioff[3],
-                         TrView* out);
 // the translation-path kernel families of a chunk (mvs_fuse_region.hip, mvs_fuse_rows.hip); *done: the family took the chunk
 int mvs_fuse_regions(MvsContext* c, const TrView* htr, const TrView* dtr, int n_views, int dtype, void* dout, const int64_t os[3],
                      const int64_t trim[3], bool* done);
 int mvs_fuse_rows(MvsContext* c, const TrView* htr, const TrView* dtr, int n_views, int dtype, void* dout, const int64_t os[3],
                   const int64_t trim[3], bool* done);
-void mvs_view_chunk_box(const DevView& d, const int64_t shape[3], int lo[3], int hi[3]);
-void mvs_view_to_chunk_frame(DevView* d, const int64_t org[3], const int64_t ioff[3]);
+// The host arithmetic on these records -- the translation-path constants (tr_view_in_chunk), the chunk frame (view_to_chunk_frame) and
+// the chunk box (view_chunk_box) -- is mvs_fuse_chunk_plan.h's.

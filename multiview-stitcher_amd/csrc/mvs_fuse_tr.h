@@ -1,6 +1,7 @@
 // mvs_fuse_tr.h -- internal: per-view record and blend-weight arithmetic of the translation fast path,
 // shared by the column kernel (mvs_fuse.hip), the region kernel (mvs_fuse_region.hip) and the host-side
-// region classification (same float formulas on both sides).
+// region classification (same float formulas on both sides).  The host fills the record from a view's
+// DevView: prepare_translation_view and fill_tr_view in mvs_fuse_chunk_plan.h.
 #pragma once
 #include "mvs_internal.h"
 

@@ -23,6 +23,7 @@
 #include "mvs_cb_plan.h"
 #include "mvs_fuse_dev.h"
 #include "mvs_fuse_tr.h"
+#include "mvs_fuse_chunk_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -794,10 +795,11 @@ int cb_geometry(CbCall& K, bool fast) {
     K.pool = CbPool(); K.VS = CbFastViews{}; K.VS.nv = K.n_views;
     for (int i = 0; i < K.n_views; ++i) {
         { const int rc = mvs_fill_dev_view(K.c, K.views[i], K.ndim, K.views[i].data, &K.dvs[i]); if (rc) return rc; }
-        if (!fast) mvs_view_to_chunk_frame(&K.dvs[i], K.opts->index_origin, K.views[i].index_offset);
-        else if (!mvs_prepare_tr_view(&K.dvs[i], K.opts->order, K.opts->out_shape, K.es, K.opts->index_origin, K.views[i].index_offset, &K.trv[i])) K.tr_all = false;
+        if (!fast) mvs_fuse_chunk_plan::view_to_chunk_frame(&K.dvs[i], K.opts->index_origin, K.views[i].index_offset);
+        else if (!mvs_fuse_chunk_plan::tr_view_in_chunk(&K.dvs[i], K.opts->order, MVS_FUSE_WEIGHTED_AVERAGE, K.opts->out_shape, K.es, K.opts->index_origin,
+                                                        K.views[i].index_offset, &K.trv[i])) K.tr_all = false;
         int lo[3], hi[3], row0, tab0;
-        mvs_view_chunk_box(K.dvs[i], K.opts->out_shape, lo, hi);
+        mvs_fuse_chunk_plan::view_chunk_box(K.dvs[i], K.opts->out_shape, lo, hi);
         const CbBox& B = K.boxes[i];
         cb_box_add(&K.pool, lo, hi, &K.boxes[i], &row0, &tab0);
         if (fast) K.VS.v[i] = CbFastView{(int)B.off, {B.n[0], B.n[1], B.n[2]}, {B.lo[0], B.lo[1], B.lo[2]}, row0, tab0, 0, 0, 0, 0, 0, 0};

@@ -98,8 +98,9 @@ struct MvsContext {
     bool fft_no_slab = false;     // test switch: crops of the slab kind (mvs_fft_slab.hip) run the six single-axis passes instead
     bool fft_no_line = false;     // test switch: lengths of the whole-line DFT kernel run on the Bluestein kernels instead
     bool no_regions = false;      // test switch: skip the region kernel (use the column kernel)
-    // chunks of mvs_fuse_chunk by the kernel family that fused them (mvs_fuse_chunk_impl): row kernels, region kernels, column kernel,
-    // generic kernel.  A chunk the column kernel gave up on (more than 64 views on a column) and the generic kernel redid counts in both.
+    // chunks of mvs_fuse_chunk by the kernel family that fused them (the steps of mvs_fuse_chunk_impl bump them; which family is asked:
+    // route() in mvs_fuse_chunk_plan.h): row kernels, region kernels, column kernel, generic kernel.  A chunk the column kernel gave up
+    // on (more than 64 views on a column) and the generic kernel redid counts in both.
     long long fuse_rows_chunks = 0, fuse_region_chunks = 0, fuse_column_chunks = 0, fuse_generic_chunks = 0;
     bool deconv_general = false;  // test switch "deconv_general": mvs_mv_deconv takes the general direct convolution even for separable kernels
     bool dct_general = false;     // test switch "dct_general": the DCT quality pass takes its general (global scratch) path for every block size

@@ -16,8 +16,8 @@ def _in_bounds(name):
 
 
 def _views_per_brick(name):
-    """Per brick of the generic kernel the number of views with an in-bounds voxel.  The brick is the one of csrc/mvs_fuse.hip
-    (kBrickX = 64 voxels along x; set_brick_grid(false): 4 x 4 in z, y for a 3D result, 1 x 16 for a 2D one), counted in the index of
+    """Per brick of the generic kernel the number of views with an in-bounds voxel.  The brick is the one of csrc/mvs_fuse_chunk_plan.h
+    (kBrickX = 64 voxels along x; brick_grid(kGenericBricks): 4 x 4 in z, y for a 3D result, 1 x 16 for a 2D one), counted in the index of
     the trimmed result.  The kernel's cull (brick_hits_view) is conservative, so it lists at least these views."""
     inb = _in_bounds(name)
     if inb.ndim == 3:
