@@ -235,6 +235,12 @@ int mvs_resample(int device, const mvs_view_t* view, const int64_t out_shape[3],
  * (weights.py:391-511): resampled 5^ndim support + cosine ramp, NOT normalised. */
 int mvs_blend_weights(int device, const mvs_view_t* view, int32_t ndim,
                       const int64_t out_shape[3], float* out, int32_t out_mem);
+/* The same volume in an INDEX FRAME: w_matrix / w_offset of `view` are derived for the frame's grid, and the volume's first voxel
+ * is voxel index_origin (z,y,x; |index_origin| and index_origin + out_shape at most 2^30) of that grid.  The coordinates are formed
+ * from the integer sum index + index_origin, so a voxel gets the same bits in any chunk of the frame (mvs_multiband_fuse's
+ * chunk-invariant winner map rests on it).  index_origin 0 is mvs_blend_weights. */
+int mvs_blend_weights_at(int device, const mvs_view_t* view, int32_t ndim, const int64_t out_shape[3],
+                         const int64_t index_origin[3], float* out, int32_t out_mem);
 
 /* ---- DCT-entropy fusion weights ------------------------------------------------ *
  * Options of weights.content_based_dct (weights.py:77-290 of the reference). */
@@ -292,6 +298,37 @@ typedef struct mvs_deconv_opts_t {
 int mvs_mv_deconv(int device, const float* views, float* weights, int32_t n_views, const int64_t shape[3], int32_t ndim,
                   const float* kernels1, const float* kernels2, const int64_t ksize[3], const float* sep1, const float* sep2,
                   const mvs_deconv_opts_t* opts, void* out, int32_t out_mem);
+
+/* ---- multi-band pyramid fusion -------------------------------------------------- *
+ * Options of mvs_multiband_fuse. */
+typedef struct mvs_multiband_opts_t {
+    int32_t levels[3];        /* L_d >= 0: decimations of axis z,y,x (2D data: levels[0] == 0); at most 6               */
+    int64_t index_origin[3];  /* global output-grid index of the array's first sample per axis: REDUCE keeps GLOBAL even
+                                 indices, so every chunk of one stack decimates on the same lattice                      */
+    int64_t trim[3];          /* halo trimmed off the result per axis z,y,x                                              */
+    int32_t out_dtype;        /* enum mvs_dtype of the result; integers: round half to even, saturate (mvs_intensity_apply) */
+    int32_t flags;            /* reserved, 0                                                                             */
+} mvs_multiband_opts_t;
+
+/* mvs_multiband_fuse: multi-band blending (Burt & Adelson 1983) of n_views resampled views.  views / weights: device float32,
+ * n_views x shape (z,y,x; 2D data as shape[0] == 1); V: NaN (any non-finite) = outside the view; B: raw blending weights >= 0.
+ * Pointwise:  m_v = isfinite(V_v);  w_v = m_v ? B_v : 0;  cov = sum w > 0;  W_v = cov ? w_v / sum w : 0;  I_v = m_v ? V_v : 0;
+ *   F0 = sum_v W_v I_v;  D_v = m_v ? I_v - F0 : 0;  A_v = cov && v == argmax_u w_u (the lowest index wins ties; the float32 values
+ *   themselves are compared).
+ * Pyramid:  level l+1 decimates axis d only if levels[d] > l; L = max_d levels[d].  REDUCE along a decimated axis: taps
+ *   [1,4,6,4,1]/16, samples kept at GLOBAL even indices, samples outside the array 0; level l+1 holds EVERY coarse sample whose 5-tap
+ *   window meets level l's extent [s, s+n): K from ceil((s-2)/2) to floor((s+n+1)/2).  EXPAND along a decimated axis: global even
+ *   g = 2K: (c[K-1] + 6 c[K] + c[K+1]) / 8; odd g = 2K+1: (c[K] + c[K+1]) / 2; missing coarse samples 0.  Both separable, axis order z,y,x.
+ * Blend and collapse, l = L .. 0, with gD, gA the reduced D_v, A_v:  Ahat_{v,l} = gA_{v,l} / sum_u gA_{u,l} where that sum is > 0,
+ *   else 0;  lap_{v,l} = gD_{v,l} - EXPAND(gD_{v,l+1}) (top level: gD_{v,L});  r_l = sum_v Ahat_{v,l} lap_{v,l} + EXPAND(r_{l+1}),
+ *   summed in view order.
+ * Result: cov ? F0 + r_0 : 0, trimmed by opts->trim and cast to opts->out_dtype into `out` (shape - 2 trim; host or device per
+ *   out_mem).  Where the views agree or only one covers, the result is F0; levels 0 is the hard-seam mosaic; the result at a voxel
+ *   depends on inputs within 4 (2^levels[d] - 1) voxels per axis.  Every sum has a fixed order: equal inputs give equal bits, and a
+ *   voxel gets the same bits in any chunk that holds that radius around it.  A device result is not waited for.
+ * MVS_ERR_UNSUPPORTED (never a crash): n_views < 1 or > 254, ndim not 2 or 3, a level < 0 or > 6. */
+int mvs_multiband_fuse(int device, const float* views, const float* weights, int32_t n_views, const int64_t shape[3], int32_t ndim,
+                       const mvs_multiband_opts_t* opts, void* out, int32_t out_mem);
 
 /* ---- registration ------------------------------------------------------------ *
  * mvs_phasecorr == skimage.registration.phase_cross_correlation(fixed, moving,

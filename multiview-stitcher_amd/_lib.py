@@ -102,6 +102,20 @@ class mvs_deconv_opts_t(C.Structure):
 MVS_DECONV_PREPARE_WEIGHTS = 1
 
 
+class mvs_multiband_opts_t(C.Structure):
+    _fields_ = [
+        ("levels", C.c_int32 * 3),
+        ("index_origin", C.c_int64 * 3),
+        ("trim", C.c_int64 * 3),
+        ("out_dtype", C.c_int32),
+        ("flags", C.c_int32),
+    ]
+
+
+MVS_MULTIBAND_MAX_LEVELS = 6
+MVS_MULTIBAND_MAX_VIEWS = 254
+
+
 class mvs_masked_corr_opts_t(C.Structure):
     _fields_ = [
         ("ndim", C.c_int32),
@@ -195,6 +209,8 @@ SIGNATURES = {
     "mvs_fuse_chunk": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(mvs_fuse_opts_t), C.c_void_p]),
     "mvs_resample": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.POINTER(C.c_int64), C.c_int32, C.c_float, C.c_void_p, C.c_int32]),
     "mvs_blend_weights": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_int32]),
+    "mvs_blend_weights_at": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p,
+                                       C.c_int32]),
     "mvs_fuse_chunk_dct": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(mvs_fuse_opts_t), C.POINTER(mvs_dct_opts_t),
                                      C.c_void_p]),
     "mvs_content_dct_weights": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(mvs_dct_opts_t),
@@ -203,6 +219,10 @@ SIGNATURES = {
         C.c_int,
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64),
          C.c_void_p, C.c_void_p, C.POINTER(mvs_deconv_opts_t), C.c_void_p, C.c_int32],
+    ),
+    "mvs_multiband_fuse": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.POINTER(mvs_multiband_opts_t), C.c_void_p, C.c_int32],
     ),
     "mvs_phasecorr": (
         C.c_int,

@@ -1504,14 +1504,19 @@ int mvs_resample_impl(int device, const mvs_view_t* view, const int64_t out_shap
     return MVS_OK;
 }
 
-extern "C" int mvs_blend_weights(int device, const mvs_view_t* view, int32_t ndim,
-                                 const int64_t out_shape[3], float* out, int32_t out_mem) {
+namespace {
+// mvs_blend_weights / mvs_blend_weights_at: the volume's first voxel is voxel `origin` of the grid the view's w_matrix / w_offset refer to
+int blend_weights_impl(int device, const mvs_view_t* view, int32_t ndim, const int64_t out_shape[3], const int64_t origin[3], float* out,
+                       int32_t out_mem) {
     MvsContext* c;
     int rc = mvs_check_ready(device, &c);
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> lock(c->mu);
-    if (!view || !out_shape || !out) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_blend_weights: NULL argument");
+    if (!view || !out_shape || !origin || !out) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_blend_weights: NULL argument");
     if (ndim != 2 && ndim != 3) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_blend_weights: ndim must be 2 or 3");
+    for (int k = 0; k < 3; ++k)
+        if (origin[k] && (out_shape[k] < 1 || origin[k] < -(1LL << 30) || origin[k] + out_shape[k] > (1LL << 30)))
+            return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_blend_weights_at: index_origin out of range on axis %d", k);
     MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
     DevView d;
     rc = stage_single_view(c, view, ndim, false, &d);
@@ -1525,7 +1530,7 @@ extern "C" int mvs_blend_weights(int device, const mvs_view_t* view, int32_t ndi
     int nblocks = (int)std::min<long long>((n + 255) / 256, 256 * 16);
     MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     hipLaunchKernelGGL(blend_kernel, dim3(nblocks), dim3(256), 0, c->stream, d, dout, (int)out_shape[0],
-                       (int)out_shape[1], (int)out_shape[2], 0, 0, 0);
+                       (int)out_shape[1], (int)out_shape[2], (int)origin[0], (int)origin[1], (int)origin[2]);
     MVS_HIP_TRY(c, hipGetLastError());
     MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
     c->timing_valid = true;
@@ -1533,6 +1538,18 @@ extern "C" int mvs_blend_weights(int device, const mvs_view_t* view, int32_t ndi
         MVS_HIP_TRY(c, hipMemcpyAsync(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
     return MVS_OK;
+}
+}  // namespace
+
+extern "C" int mvs_blend_weights(int device, const mvs_view_t* view, int32_t ndim,
+                                 const int64_t out_shape[3], float* out, int32_t out_mem) {
+    static const int64_t zero[3] = {0, 0, 0};
+    return blend_weights_impl(device, view, ndim, out_shape, zero, out, out_mem);
+}
+
+extern "C" int mvs_blend_weights_at(int device, const mvs_view_t* view, int32_t ndim, const int64_t out_shape[3],
+                                    const int64_t index_origin[3], float* out, int32_t out_mem) {
+    return blend_weights_impl(device, view, ndim, out_shape, index_origin, out, out_mem);
 }
 
 

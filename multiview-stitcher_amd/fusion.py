@@ -26,8 +26,9 @@ import warnings
 
 import numpy as np
 
-from . import _lib, msi_utils, mv_deconv, mv_graph, ngff_utils, param_utils, streaming, weights, zarr_io
+from . import _lib, msi_utils, multiband, mv_deconv, mv_graph, ngff_utils, param_utils, streaming, weights, zarr_io
 from . import device as dev_mod
+from .multiband import multi_band_fusion  # noqa: F401  (fusion.multi_band_fusion)
 from .mv_deconv import PSFType, multi_view_deconvolution  # noqa: F401  (fusion.multi_view_deconvolution, fusion.PSFType)
 from .weights import content_based_dct  # noqa: F401  (fusion.content_based_dct)
 from . import spatial_image_utils as si_utils
@@ -78,6 +79,7 @@ BUILTIN = {
     "simple_average_fusion": simple_average_fusion,
     "content_based": content_based,
     "multi_view_deconvolution": multi_view_deconvolution,   # not a kernel mode: fuse_np's deconvolution branch
+    "multi_band_fusion": multi_band_fusion,                 # not a kernel mode: fuse_np's multi-band branch
     "content_based_dct": content_based_dct,                 # weights of fuse_np's mvs_fuse_chunk_dct branch
 }
 
@@ -198,6 +200,10 @@ def fuse_np(
                    [_bb_dicts(b, sdims) for b in full_view_bbs], int(interpolation_order), blending_widths, shrink_distance, device)
     if fusion_func is multi_view_deconvolution:
         return _fuse_np_deconvolution(chunk, fusion_func_kwargs, output_on_backend, out)
+    if fusion_func is multi_band_fusion:
+        if weights_func is not None:
+            raise NotImplementedError("multi_band_fusion cannot be combined with a weights_func: its bands are blended by hard-seam masks")
+        return _fuse_np_multiband(chunk, fusion_func_kwargs, output_on_backend, out, frame_origin)
     dct = weights_func is content_based_dct and fusion_func in _FUSION_CODES
     if dct and _FUSION_CODES[fusion_func] != _lib.MVS_FUSE_WEIGHTED_AVERAGE:
         dct, weights_func = False, None      # only a fusion_func with fusion_weights asks for them (_core.py:1665)
@@ -369,26 +375,17 @@ def _launch_chunk(lib, chunk, views, opts, dopts, out, output_on_backend, cb_che
     return result
 
 
-def _fuse_np_deconvolution(chunk, fusion_func_kwargs, output_on_backend, out):
-    """fuse_np with ``fusion_func=multi_view_deconvolution`` (_core.py:1608-1713 around mv_deconv.py:251-501), all on the
-    device: every view resampled by mvs_resample (float32, NaN outside) and its blending weights by mvs_blend_weights
-    into two (V, *S) stacks; mvs_mv_deconv masks the weights by ~isnan and normalises them, deconvolves, trims the halo,
-    applies nan_to_num and casts to the input dtype.  ``output_spacing`` is the chunk spacing unless the caller passed
-    one (_core.py:1658-1662).  Only the result crosses PCIe, and only when a host result is asked for."""
+def _resampled_stacks(chunk, weights_frame=None):
+    """The prologue the stack-based fusion functions share (_core.py:1608-1649): every view of the chunk resampled by mvs_resample
+    (float32, NaN outside) and its raw blending weights by mvs_blend_weights, as two device stacks (V, *S).  The parameters are
+    derived per chunk, as the reference does.  ``weights_frame`` = (frame origin (zyx array), index_origin (3 ints)): the blending
+    weights are derived for the frame's grid instead and the chunk enters as an integer index shift (mvs_blend_weights_at), so a
+    voxel's weights have the same bits in every chunk of the frame."""
     sims, params, sdims, out_bb, device = chunk.sims, chunk.params, chunk.sdims, chunk.out_bb, chunk.device
     lib = _lib.init(device)
-    ndim = len(sdims)
-    kw = dict(fusion_func_kwargs or {})
-    for k in ("transformed_views", "blending_weights", "device"):
-        if k in kw:
-            raise TypeError(f"fusion_func_kwargs must not set {k!r}: fuse_np supplies it")
-    if kw.get("output_spacing") is None:
-        kw["output_spacing"] = dict(out_bb["spacing"])
+    ndim, n = len(sdims), len(sims)
     out_shape = tuple(int(out_bb["shape"][d]) for d in sdims)
     o_origin, o_spacing = _as_zyx(out_bb["origin"], sdims), _as_zyx(out_bb["spacing"], sdims)
-    n = len(sims)
-    kernels = mv_deconv._kernels(n, ndim, kw.get("psfs"), kw.get("psf_type", PSFType.EFFICIENT_BAYESIAN), kw["output_spacing"],
-                                 kw.get("na", 0.8), kw.get("wavelength_um", 0.5))
     S = int(np.prod(out_shape))
     views_t = DeviceArray.empty((n,) + out_shape, np.float32, device)
     blend = DeviceArray.empty((n,) + out_shape, np.float32, device)
@@ -407,16 +404,76 @@ def _fuse_np_deconvolution(chunk, fusion_func_kwargs, output_on_backend, out):
                               _lib.MVS_MEM_DEVICE)
         _lib.check(rc, device, "mvs_resample")
         wview = _lib.mvs_view_t()
-        weights.fill_view_weights(wview, chunk.full_view_bbs[i], param, o_origin, o_spacing, chunk.blending_widths,
-                                  chunk.shrink_distance)
-        rc = lib.mvs_blend_weights(device, C.byref(wview), ndim, s3, C.c_void_p(blend.ptr + 4 * i * S), _lib.MVS_MEM_DEVICE)
+        weights.fill_view_weights(wview, chunk.full_view_bbs[i], param, o_origin if weights_frame is None else weights_frame[0], o_spacing,
+                                  chunk.blending_widths, chunk.shrink_distance)
+        if weights_frame is None:
+            rc = lib.mvs_blend_weights(device, C.byref(wview), ndim, s3, C.c_void_p(blend.ptr + 4 * i * S), _lib.MVS_MEM_DEVICE)
+        else:
+            rc = lib.mvs_blend_weights_at(device, C.byref(wview), ndim, s3, _lib.i64x3(weights_frame[1]), C.c_void_p(blend.ptr + 4 * i * S),
+                                          _lib.MVS_MEM_DEVICE)
         _lib.check(rc, device, "mvs_blend_weights")
+    return views_t, blend
+
+
+def _supplied_kwargs(fusion_func_kwargs):
+    """A copy of ``fusion_func_kwargs`` without the arguments fuse_np supplies itself (setting one is a ``TypeError``)."""
+    kw = dict(fusion_func_kwargs or {})
+    for k in ("transformed_views", "blending_weights", "device"):
+        if k in kw:
+            raise TypeError(f"fusion_func_kwargs must not set {k!r}: fuse_np supplies it")
+    return kw
+
+
+def _fuse_np_deconvolution(chunk, fusion_func_kwargs, output_on_backend, out):
+    """fuse_np with ``fusion_func=multi_view_deconvolution`` (_core.py:1608-1713 around mv_deconv.py:251-501), all on the
+    device: every view resampled by mvs_resample (float32, NaN outside) and its blending weights by mvs_blend_weights
+    into two (V, *S) stacks; mvs_mv_deconv masks the weights by ~isnan and normalises them, deconvolves, trims the halo,
+    applies nan_to_num and casts to the input dtype.  ``output_spacing`` is the chunk spacing unless the caller passed
+    one (_core.py:1658-1662).  Only the result crosses PCIe, and only when a host result is asked for."""
+    ndim = len(chunk.sdims)
+    kw = _supplied_kwargs(fusion_func_kwargs)
+    if kw.get("output_spacing") is None:
+        kw["output_spacing"] = dict(chunk.out_bb["spacing"])
+    kernels = mv_deconv._kernels(len(chunk.sims), ndim, kw.get("psfs"), kw.get("psf_type", PSFType.EFFICIENT_BAYESIAN), kw["output_spacing"],
+                                 kw.get("na", 0.8), kw.get("wavelength_um", 0.5))
+    views_t, blend = _resampled_stacks(chunk)
     trim = list(chunk.trim.values())
     on_device = out is not None or output_on_backend
     res = mv_deconv._run(views_t, blend, ndim, kernels, kw.get("n_iterations", 10), kw.get("lambda_reg", 0.0),
-                         kw.get("min_value", 1e-4), kw.get("sample_boundary_erosion_px", 0), trim, chunk.input_dtype, on_device, device,
+                         kw.get("min_value", 1e-4), kw.get("sample_boundary_erosion_px", 0), trim, chunk.input_dtype, on_device, chunk.device,
                          prepare_weights=True, out=out)
     return res
+
+
+def _fuse_np_multiband(chunk, fusion_func_kwargs, output_on_backend, out, frame_origin):
+    """fuse_np with ``fusion_func=multi_band_fusion``, all on the device: the stacks of ``_resampled_stacks``, then ONE
+    mvs_multiband_fuse call (masking, pyramids, blend, collapse, halo trim, cast to the input dtype).  The pyramids decimate on the
+    lattice of ``frame_origin``: ``index_origin = (chunk origin - frame origin) / spacing``; an origin off that grid (not within 1e-6 of
+    integers) issues an ``IndexFrameWarning`` and the chunk is anchored at 0.  Only the result crosses PCIe, and only when a host
+    result is asked for."""
+    sdims, ndim = chunk.sdims, len(chunk.sdims)
+    kw = _supplied_kwargs(fusion_func_kwargs)
+    unknown = sorted(set(kw) - {"n_levels", "index_origin"})
+    if unknown:
+        raise TypeError(f"multi_band_fusion got unexpected fusion_func_kwargs {unknown}")
+    if "index_origin" in kw:
+        raise TypeError("fusion_func_kwargs must not set 'index_origin': fuse_np derives it from frame_origin")
+    levels3 = multiband._levels3(kw.get("n_levels", 3), ndim)
+    origin3, weights_frame = [0, 0, 0], None
+    if frame_origin is not None:
+        io_ = (_as_zyx(chunk.out_bb["origin"], sdims) - _as_zyx(frame_origin, sdims)) / _as_zyx(chunk.out_bb["spacing"], sdims)
+        if np.all(np.abs(io_ - np.round(io_)) < 1e-6):
+            origin3[3 - ndim:] = [int(v) for v in np.round(io_)]
+            # the winner map compares the weights themselves: they are derived once for the frame, the chunk is an index shift
+            weights_frame = (_as_zyx(frame_origin, sdims), origin3)
+        else:
+            warnings.warn(
+                "fuse_np: frame_origin cannot be applied -- the chunk origin is not on the frame's grid (largest distance from it: "
+                f"{float(np.abs(io_ - np.round(io_)).max()):.3g} px); the pyramids of this chunk are anchored at its own first sample, so its "
+                "voxels may differ from the same voxels fused through another chunk", IndexFrameWarning, stacklevel=3)
+    views_t, blend = _resampled_stacks(chunk, weights_frame)
+    on_device = out is not None or output_on_backend
+    return multiband._run(views_t, blend, ndim, levels3, origin3, list(chunk.trim.values()), chunk.input_dtype, on_device, chunk.device, out=out)
 
 
 def _host_weighted_average_fusion(transformed_views, blending_weights, fusion_weights=None):
@@ -1181,10 +1238,11 @@ def _chunk_call(call, ns_index, entry, device):
         weights_func=call.weights_func, weights_func_kwargs=call.weights_func_kwargs,
         trim_overlap_in_pixels=(call.halo if call.trim_overlap else 0), interpolation_order=call.interpolation_order, full_view_bbs=fvb,
         blending_widths=call.blending_widths, shrink_distance=0, backend="hip", device=device, _cb_check=False)
-    if _kernel_fused(call.fusion_func, call.weights_func):
+    kernel_fused = _kernel_fused(call.fusion_func, call.weights_func)
+    if kernel_fused or call.fusion_func is multi_band_fusion:      # (the multi-band pyramids decimate on the frame's lattice)
         origin = call.frame_origin if call.frame_origin is not None else call.osp["origin"]
         kwargs["frame_origin"] = {d: origin[d] for d in cbb["origin"]}
-        if call.record is not None and not entry["fuse_planewise"]:
+        if kernel_fused and call.record is not None and not entry["fuse_planewise"]:
             kwargs["_record"] = call.record
             call.record["calls"] = call.record.get("calls", 0) + 1
             call.record["view_index"] = idxs
