@@ -17,14 +17,15 @@
 #include <cstring>
 #include <vector>
 
+#include "mvs_deconv_plan.h"
 #include "mvs_internal.h"
+#include "mvs_stack_frame.h"
 
 namespace {
 
-constexpr int GX = 8, GY = 8;       // threads of a general-path workgroup (one wave)
-constexpr int RX = 8, RY = 4;       // outputs per thread along x / y
-constexpr int TX = GX * RX, TY = GY * RY;   // output tile 64 x 32
-constexpr int KMAX = 63;            // largest kernel extent per axis of the general path
+namespace dp = mvs_deconv_plan;
+using dp::GX, dp::GY, dp::RX, dp::RY, dp::TX, dp::TY;      // the tile constants the kernels read
+static_assert(dp::kOk == MVS_OK && dp::kInvalidArg == MVS_ERR_INVALID_ARG && dp::kUnsupported == MVS_ERR_UNSUPPORTED, "make_plan returns MVS_* codes");
 
 __device__ __forceinline__ int mirror_index(int i, int n) {
     if (n == 1) return 0;
@@ -293,194 +294,204 @@ __global__ void deconv_out_kernel(const float* __restrict__ psi, const unsigned 
     }
 }
 
-int grid_for(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 255) / 256, 256 * 32)); }
+const char* const NAME = "mvs_mv_deconv";
+
+// One mvs_mv_deconv call: its arguments, the frame, the plan, the host tables and the carved work area.  The steps below run in the
+// order of the entry point.
+struct DeconvCall {
+    const float* views;
+    float* weights;
+    int V;
+    const int64_t* shape;
+    int ndim;
+    const float *kernels1, *kernels2;
+    const int64_t* ksize;
+    const float *sep1, *sep2;
+    const mvs_deconv_opts_t* opts;
+    void* out;
+    int32_t out_mem;
+    MvsStackFrame F;
+    dp::Plan plan;
+    std::vector<float> htaps;
+    std::vector<float> sep_cval;        // per view: cval of the y and z passes of the back projection
+    float *psi, *wr, *pa, *pb, *bmax, *peak, *dtaps;
+    unsigned char *m0, *m1;
+    const unsigned char* mask = nullptr;   // the eroded coverage, when there is an erosion
+    int pgrid;                          // workgroups of the element-wise kernels over a view
+    Epi e{};
+};
+
+// argument checks: they need no device
+int dc_check(MvsContext* c0, const DeconvCall& K) {
+    const mvs_deconv_opts_t* opts = K.opts;
+    if (!K.views || !K.weights || !K.shape || !K.kernels1 || !K.kernels2 || !K.ksize || !opts || !K.out)
+        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: NULL argument");
+    if (K.V < 1) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: n_views must be >= 1");
+    if (K.ndim != 2 && K.ndim != 3) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: ndim must be 2 or 3");
+    if (int rc = mvs_stack_check_out(c0, NAME, K.out_mem, opts->out_dtype)) return rc;
+    if (opts->n_iterations < 0 || opts->erosion_px < 0) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: negative n_iterations / erosion");
+    for (int k = 0; k < 3; ++k) {
+        if (K.shape[k] < 1 || K.shape[k] > 0x7fffffffLL || K.ksize[k] < 1)
+            return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: bad shape / kernel size on axis %d", k);
+        if (int rc = mvs_stack_check_trim(c0, NAME, K.shape, opts->trim, k)) return rc;
+        if (K.ksize[k] > dp::KMAX)
+            return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_mv_deconv: kernel extent %lld on axis %d exceeds the limit of %d", (long long)K.ksize[k], k, dp::KMAX);
+    }
+    if (K.ndim == 2 && (K.shape[0] != 1 || K.ksize[0] != 1))
+        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: 2D data has shape[0] == ksize[0] == 1");
+    return mvs_stack_check_size(c0, NAME, (long long)K.shape[0] * K.shape[1] * K.shape[2], K.V);
+}
+
+// the plan (mvs_deconv_plan.h) and the host tap tables
+int dc_plan_and_taps(DeconvCall& K) {
+    MvsContext* c = K.F.c;
+    const bool separable = K.sep1 && K.sep2 && !c->deconv_general;
+    const int rc = dp::make_plan(K.shape, K.ksize, K.V, separable, K.opts->erosion_px > 0, K.opts->trim, K.opts->out_dtype, K.out_mem == MVS_MEM_HOST, &K.plan);
+    if (rc) return mvs_fail(c, rc, "mvs_mv_deconv: bad shape / kernel size");      // (dc_check has refused these already)
+    dp::make_taps(K.plan, K.V, K.kernels1, K.kernels2, K.sep1, K.sep2, &K.htaps, &K.sep_cval);
+    K.pgrid = dp::grid_for(K.plan.S);
+    return MVS_OK;
+}
+
+// the work area, carved as the plan lays it out
+int dc_reserve(DeconvCall& K) {
+    const dp::Plan& p = K.plan;
+    int rc = K.F.reserve(p.total, p.off_out, K.out, K.out_mem, p.box.out_bytes);
+    if (rc) return rc;
+    char* W = K.F.W;
+    K.psi = (float*)(W + p.off_psi);
+    K.wr = (float*)(W + p.off_wr);
+    K.pa = (float*)(W + p.off_a);
+    K.pb = (float*)(W + p.off_b);
+    K.m0 = (unsigned char*)(W + p.off_m0);
+    K.m1 = (unsigned char*)(W + p.off_m1);
+    K.bmax = (float*)(W + p.off_bm);
+    K.peak = (float*)(W + p.off_pk);
+    K.dtaps = (float*)(W + p.off_tp);
+    return MVS_OK;
+}
+
+int dc_upload_taps(DeconvCall& K) {
+    MvsContext* c = K.F.c;
+    MVS_HIP_TRY(c, hipMemcpyAsync(K.dtaps, K.htaps.data(), K.htaps.size() * 4, hipMemcpyHostToDevice, c->stream));
+    return MVS_OK;
+}
+
+// the weights (when the caller passed raw ones), the first estimate, its peak (for the Tikhonov step), and the epilogues' constants
+int dc_prepare(DeconvCall& K) {
+    MvsContext* c = K.F.c;
+    const mvs_deconv_opts_t* opts = K.opts;
+    const long long S = K.plan.S;
+    if (opts->flags & MVS_DECONV_PREPARE_WEIGHTS) {
+        hipLaunchKernelGGL(deconv_weights_kernel, dim3(K.pgrid), dim3(256), 0, c->stream, K.views, K.weights, K.V, S);
+        MVS_HIP_TRY(c, hipGetLastError());
+    }
+    const float minv = (float)opts->min_value;
+    const int lambda_on = opts->lambda_reg > 0.0;
+    hipLaunchKernelGGL(deconv_init_kernel, dim3(dp::kInitBlocks), dim3(256), 0, c->stream, K.views, (const float*)K.weights, K.V, S, minv, K.psi, K.bmax);
+    MVS_HIP_TRY(c, hipGetLastError());
+    if (lambda_on) {
+        hipLaunchKernelGGL(deconv_peak_kernel, dim3(1), dim3(256), 0, c->stream, (const float*)K.bmax, dp::kInitBlocks, K.peak);
+        MVS_HIP_TRY(c, hipGetLastError());
+    }
+    K.e.psi = K.psi;
+    K.e.peak = K.peak;
+    K.e.minv = minv;
+    K.e.l2 = (float)(2.0 * opts->lambda_reg);
+    K.e.lf = (float)opts->lambda_reg;
+    K.e.lambda_on = lambda_on;
+    return MVS_OK;
+}
+
+// forward and back projection of view v, general direct path
+int dc_view_general(DeconvCall& K, int v) {
+    MvsContext* c = K.F.c;
+    const dp::Plan& p = K.plan;
+    const dim3 ggrid(p.grid_x, p.grid_y, p.grid_z);
+    const float* t1 = K.dtaps + (long long)v * p.kvolp;
+    const float* t2 = K.dtaps + (long long)(K.V + v) * p.kvolp;
+    hipLaunchKernelGGL(deconv_conv_general<0>, ggrid, dim3(64), p.lds_bytes, c->stream, (const float*)K.psi, K.wr, t1, p.nz, p.ny, p.nx, p.kz, p.ky, p.kxp,
+                       p.az, p.ay, p.ax, 0.f, K.e);
+    MVS_HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(deconv_conv_general<1>, ggrid, dim3(64), p.lds_bytes, c->stream, (const float*)K.wr, (float*)nullptr, t2, p.nz, p.ny, p.nx, p.kz,
+                       p.ky, p.kxp, p.az, p.ay, p.ax, 1.f, K.e);
+    MVS_HIP_TRY(c, hipGetLastError());
+    return MVS_OK;
+}
+
+// forward and back projection of view v, separable path: x, y, z passes with the epilogue in the z pass
+int dc_view_separable(DeconvCall& K, int v) {
+    MvsContext* c = K.F.c;
+    const dp::Plan& p = K.plan;
+    const dim3 grid(K.pgrid), block(256);
+    const float* t1 = K.dtaps + (long long)v * p.ksep;
+    const float* t2 = K.dtaps + (long long)(K.V + v) * p.ksep;
+    const int nz = p.nz, ny = p.ny, nx = p.nx, kz = p.kz, ky = p.ky, kx = p.kx;
+    hipLaunchKernelGGL((deconv_pass<2, 0, 0>), grid, block, 0, c->stream, (const float*)K.psi, K.pa, t1 + kz + ky, nz, ny, nx, kx, p.ax, 0.f, K.e);
+    hipLaunchKernelGGL((deconv_pass<1, 0, 0>), grid, block, 0, c->stream, (const float*)K.pa, K.pb, t1 + kz, nz, ny, nx, ky, p.ay, 0.f, K.e);
+    hipLaunchKernelGGL((deconv_pass<0, 0, 1>), grid, block, 0, c->stream, (const float*)K.pb, K.wr, t1, nz, ny, nx, kz, p.az, 0.f, K.e);
+    hipLaunchKernelGGL((deconv_pass<2, 1, 0>), grid, block, 0, c->stream, (const float*)K.wr, K.pa, t2 + kz + ky, nz, ny, nx, kx, p.ax, 1.f, K.e);
+    hipLaunchKernelGGL((deconv_pass<1, 1, 0>), grid, block, 0, c->stream, (const float*)K.pa, K.pb, t2 + kz, nz, ny, nx, ky, p.ay, K.sep_cval[2 * v], K.e);
+    hipLaunchKernelGGL((deconv_pass<0, 1, 2>), grid, block, 0, c->stream, (const float*)K.pb, (float*)nullptr, t2, nz, ny, nx, kz, p.az,
+                       K.sep_cval[2 * v + 1], K.e);
+    MVS_HIP_TRY(c, hipGetLastError());
+    return MVS_OK;
+}
+
+// one view's update of the estimate: the epilogues read this view and its weights
+int dc_view(DeconvCall& K, int v) {
+    K.e.img = K.views + v * K.plan.S;
+    K.e.w = K.weights + v * K.plan.S;
+    return K.plan.separable ? dc_view_separable(K, v) : dc_view_general(K, v);
+}
+
+// the union coverage eroded erosion_px times (mv_deconv.py:485-499)
+int dc_erosion_mask(DeconvCall& K) {
+    MvsContext* c = K.F.c;
+    const dp::Plan& p = K.plan;
+    if (K.opts->erosion_px <= 0) return MVS_OK;
+    hipLaunchKernelGGL(deconv_coverage_kernel, dim3(K.pgrid), dim3(256), 0, c->stream, K.views, K.V, p.S, K.m0);
+    unsigned char *src = K.m0, *dst = K.m1;
+    for (int k = 0; k < K.opts->erosion_px; ++k) {
+        hipLaunchKernelGGL(deconv_erode_kernel, dim3(K.pgrid), dim3(256), 0, c->stream, (const unsigned char*)src, dst, p.nz, p.ny, p.nx, K.ndim);
+        std::swap(src, dst);
+    }
+    MVS_HIP_TRY(c, hipGetLastError());
+    K.mask = src;
+    return MVS_OK;
+}
+
+// the estimate, masked, trimmed and cast, where the frame wants the result
+int dc_write_result(DeconvCall& K) {
+    MvsContext* c = K.F.c;
+    const dp::Plan& p = K.plan;
+    const int oz = (int)p.box.oz, oy = (int)p.box.oy, ox = (int)p.box.ox;
+    const int ogrid = dp::grid_for(p.box.oz * p.box.oy * p.box.ox);
+    const int t0 = (int)K.opts->trim[0], t1 = (int)K.opts->trim[1], t2 = (int)K.opts->trim[2];
+    mvs_dispatch_dtype(K.opts->out_dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(deconv_out_kernel<T>, dim3(ogrid), dim3(256), 0, c->stream, (const float*)K.psi, K.mask, p.ny, p.nx, oz, oy, ox, t0, t1, t2,
+                           (T*)K.F.dout);
+    });
+    MVS_HIP_TRY(c, hipGetLastError());
+    return MVS_OK;
+}
 
 }  // namespace
 
 extern "C" int mvs_mv_deconv(int device, const float* views, float* weights, int32_t n_views, const int64_t shape[3], int32_t ndim,
                              const float* kernels1, const float* kernels2, const int64_t ksize[3], const float* sep1, const float* sep2,
                              const mvs_deconv_opts_t* opts, void* out, int32_t out_mem) {
-    MvsContext* c0 = mvs_ctx(device);
-    // argument checks first: they need no device
-    if (!views || !weights || !shape || !kernels1 || !kernels2 || !ksize || !opts || !out)
-        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: NULL argument");
-    if (n_views < 1) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: n_views must be >= 1");
-    if (ndim != 2 && ndim != 3) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: ndim must be 2 or 3");
-    if (out_mem != MVS_MEM_HOST && out_mem != MVS_MEM_DEVICE) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: bad out_mem");
-    if (opts->out_dtype != MVS_U8 && opts->out_dtype != MVS_U16 && opts->out_dtype != MVS_F32)
-        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: bad out_dtype");
-    if (opts->n_iterations < 0 || opts->erosion_px < 0) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: negative n_iterations / erosion");
-    for (int k = 0; k < 3; ++k) {
-        if (shape[k] < 1 || shape[k] > 0x7fffffffLL || ksize[k] < 1)
-            return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: bad shape / kernel size on axis %d", k);
-        if (opts->trim[k] < 0 || 2 * opts->trim[k] >= shape[k])
-            return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: trim on axis %d leaves nothing", k);
-        if (ksize[k] > KMAX)
-            return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_mv_deconv: kernel extent %lld on axis %d exceeds the limit of %d", (long long)ksize[k], k, KMAX);
-    }
-    if (ndim == 2 && (shape[0] != 1 || ksize[0] != 1)) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: 2D data has shape[0] == ksize[0] == 1");
-    if ((long long)shape[0] * shape[1] * shape[2] * n_views > (1LL << 40)) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_mv_deconv: too large");
-
-    MvsContext* c;
-    int rc = mvs_check_ready(device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
-    const int nz = (int)shape[0], ny = (int)shape[1], nx = (int)shape[2];
-    const int kz = (int)ksize[0], ky = (int)ksize[1], kx = (int)ksize[2];
-    const long long S = (long long)nz * ny * nx;
-    const int V = n_views;
-    const bool separable = sep1 && sep2 && !c->deconv_general;
-    const int kxp = (kx + 3) & ~3;
-    const int az = kz - 1 - kz / 2, ay = ky - 1 - ky / 2, ax = kx - 1 - kx / 2;
-
-    // host tap tables in correlation order: general [set][v][kz][ky][kxp] (x zero-padded), separable [set][v][kz + ky + kx]
-    const long long kvol = (long long)kz * ky * kx, kvolp = (long long)kz * ky * kxp, ksep = kz + ky + kx;
-    std::vector<float> htaps;
-    std::vector<float> sep_cval;          // per view: cval of the y and z passes of the back projection
-    if (separable) {
-        htaps.resize(2 * V * ksep);
-        sep_cval.resize(2 * (size_t)V);
-        for (int s = 0; s < 2; ++s)
-            for (int v = 0; v < V; ++v) {
-                const float* src = (s ? sep2 : sep1) + v * ksep;
-                float* dst = htaps.data() + (s * V + v) * ksep;
-                const int len[3] = {kz, ky, kx};
-                int off = 0;
-                for (int ax_ = 0; ax_ < 3; ++ax_) {
-                    for (int j = 0; j < len[ax_]; ++j) dst[off + j] = src[off + len[ax_] - 1 - j];
-                    off += len[ax_];
-                }
-                if (s == 1) {
-                    double sx = 0.0, sy = 0.0;
-                    for (int j = 0; j < kx; ++j) sx += src[kz + ky + j];
-                    for (int j = 0; j < ky; ++j) sy += src[kz + j];
-                    sep_cval[2 * v] = (float)sx;
-                    sep_cval[2 * v + 1] = (float)(sx * sy);
-                }
-            }
-    } else {
-        htaps.assign(2 * V * kvolp, 0.f);
-        for (int s = 0; s < 2; ++s)
-            for (int v = 0; v < V; ++v) {
-                const float* src = (s ? kernels2 : kernels1) + v * kvol;
-                float* dst = htaps.data() + (s * V + v) * kvolp;
-                for (int z = 0; z < kz; ++z)
-                    for (int y = 0; y < ky; ++y)
-                        for (int x = 0; x < kx; ++x)
-                            dst[((long long)z * ky + y) * kxp + x] = src[((long long)(kz - 1 - z) * ky + (ky - 1 - y)) * kx + (kx - 1 - x)];
-            }
-    }
-
-    // device work area: psi | wr | two pass buffers (separable) | two masks (erosion) | block maxima | peak | taps
-    const int init_blocks = 1024;
-    const size_t fS = (size_t)S * 4;
-    size_t off_psi = 0, off_wr = off_psi + fS, off_a = off_wr + fS, off_b = off_a + (separable ? fS : 0);
-    size_t off_m0 = off_b + (separable ? fS : 0);
-    size_t off_m1 = off_m0 + (opts->erosion_px > 0 ? align_up((size_t)S) : 0);
-    size_t off_bm = off_m1 + (opts->erosion_px > 0 ? align_up((size_t)S) : 0);
-    size_t off_pk = off_bm + init_blocks * 4;
-    size_t off_tp = off_pk + 256;
-    size_t off_out = off_tp + align_up(htaps.size() * 4);
-    const size_t out_elem = mvs_dtype_size(opts->out_dtype);
-    const long long oz = nz - 2 * opts->trim[0], oy = ny - 2 * opts->trim[1], ox = nx - 2 * opts->trim[2];
-    const size_t out_bytes = (size_t)(oz * oy * ox) * out_elem;
-    size_t total = off_out + (out_mem == MVS_MEM_HOST ? out_bytes : 0);
-    MvsWorkArea work(c);
-    rc = work.alloc(total);
-    if (rc) return rc;
-    char* W = (char*)work.ptr;
-    float* psi = (float*)(W + off_psi);
-    float* wr = (float*)(W + off_wr);
-    float* pa = (float*)(W + off_a);
-    float* pb = (float*)(W + off_b);
-    unsigned char* m0 = (unsigned char*)(W + off_m0);
-    unsigned char* m1 = (unsigned char*)(W + off_m1);
-    float* bmax = (float*)(W + off_bm);
-    float* peak = (float*)(W + off_pk);
-    float* dtaps = (float*)(W + off_tp);
-    void* dout = out_mem == MVS_MEM_HOST ? (void*)(W + off_out) : out;
-
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    MVS_HIP_TRY(c, hipMemcpyAsync(dtaps, htaps.data(), htaps.size() * 4, hipMemcpyHostToDevice, c->stream));
-    const int pgrid = grid_for(S);
-    if (opts->flags & MVS_DECONV_PREPARE_WEIGHTS) {
-        hipLaunchKernelGGL(deconv_weights_kernel, dim3(pgrid), dim3(256), 0, c->stream, views, (float*)weights, V, S);
-        MVS_HIP_TRY(c, hipGetLastError());
-    }
-    const float minv = (float)opts->min_value;
-    const int lambda_on = opts->lambda_reg > 0.0;
-    hipLaunchKernelGGL(deconv_init_kernel, dim3(init_blocks), dim3(256), 0, c->stream, views, weights, V, S, minv, psi, bmax);
-    MVS_HIP_TRY(c, hipGetLastError());
-    if (lambda_on) {
-        hipLaunchKernelGGL(deconv_peak_kernel, dim3(1), dim3(256), 0, c->stream, (const float*)bmax, init_blocks, peak);
-        MVS_HIP_TRY(c, hipGetLastError());
-    }
-    Epi e{};
-    e.psi = psi;
-    e.peak = peak;
-    e.minv = minv;
-    e.l2 = (float)(2.0 * opts->lambda_reg);
-    e.lf = (float)opts->lambda_reg;
-    e.lambda_on = lambda_on;
-    const dim3 ggrid((nx + TX - 1) / TX, (ny + TY - 1) / TY, nz);
-    const size_t glds = (size_t)(TY + ky - 1) * (TX + kxp) * 4;
-    for (int it = 0; it < opts->n_iterations; ++it) {
-        for (int v = 0; v < V; ++v) {
-            e.img = views + v * S;
-            e.w = weights + v * S;
-            if (!separable) {
-                const float* t1 = dtaps + (long long)v * kvolp;
-                const float* t2 = dtaps + (long long)(V + v) * kvolp;
-                hipLaunchKernelGGL(deconv_conv_general<0>, ggrid, dim3(64), glds, c->stream, (const float*)psi, wr, t1, nz, ny, nx, kz, ky, kxp,
-                                   az, ay, ax, 0.f, e);
-                MVS_HIP_TRY(c, hipGetLastError());
-                hipLaunchKernelGGL(deconv_conv_general<1>, ggrid, dim3(64), glds, c->stream, (const float*)wr, (float*)nullptr, t2, nz, ny, nx,
-                                   kz, ky, kxp, az, ay, ax, 1.f, e);
-                MVS_HIP_TRY(c, hipGetLastError());
-            } else {
-                const float* t1 = dtaps + (long long)v * ksep;
-                const float* t2 = dtaps + (long long)(V + v) * ksep;
-                hipLaunchKernelGGL((deconv_pass<2, 0, 0>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)psi, pa, t1 + kz + ky, nz, ny, nx, kx, ax, 0.f, e);
-                hipLaunchKernelGGL((deconv_pass<1, 0, 0>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)pa, pb, t1 + kz, nz, ny, nx, ky, ay, 0.f, e);
-                hipLaunchKernelGGL((deconv_pass<0, 0, 1>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)pb, wr, t1, nz, ny, nx, kz, az, 0.f, e);
-                hipLaunchKernelGGL((deconv_pass<2, 1, 0>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)wr, pa, t2 + kz + ky, nz, ny, nx, kx, ax, 1.f, e);
-                hipLaunchKernelGGL((deconv_pass<1, 1, 0>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)pa, pb, t2 + kz, nz, ny, nx, ky, ay, sep_cval[2 * v], e);
-                hipLaunchKernelGGL((deconv_pass<0, 1, 2>), dim3(pgrid), dim3(256), 0, c->stream, (const float*)pb, (float*)nullptr, t2, nz, ny, nx, kz, az,
-                                   sep_cval[2 * v + 1], e);
-                MVS_HIP_TRY(c, hipGetLastError());
-            }
-        }
-    }
-    const unsigned char* mask = nullptr;
-    if (opts->erosion_px > 0) {     // mv_deconv.py:485-499
-        hipLaunchKernelGGL(deconv_coverage_kernel, dim3(pgrid), dim3(256), 0, c->stream, views, V, S, m0);
-        unsigned char *src = m0, *dst = m1;
-        for (int k = 0; k < opts->erosion_px; ++k) {
-            hipLaunchKernelGGL(deconv_erode_kernel, dim3(pgrid), dim3(256), 0, c->stream, (const unsigned char*)src, dst, nz, ny, nx, (int)ndim);
-            std::swap(src, dst);
-        }
-        MVS_HIP_TRY(c, hipGetLastError());
-        mask = src;
-    }
-    const int ogrid = grid_for(oz * oy * ox);
-    const int t0 = (int)opts->trim[0], t1 = (int)opts->trim[1], t2 = (int)opts->trim[2];
-    if (opts->out_dtype == MVS_F32)
-        hipLaunchKernelGGL(deconv_out_kernel<float>, dim3(ogrid), dim3(256), 0, c->stream, (const float*)psi, mask, ny, nx, (int)oz, (int)oy, (int)ox,
-                           t0, t1, t2, (float*)dout);
-    else if (opts->out_dtype == MVS_U16)
-        hipLaunchKernelGGL(deconv_out_kernel<unsigned short>, dim3(ogrid), dim3(256), 0, c->stream, (const float*)psi, mask, ny, nx, (int)oz, (int)oy,
-                           (int)ox, t0, t1, t2, (unsigned short*)dout);
-    else
-        hipLaunchKernelGGL(deconv_out_kernel<unsigned char>, dim3(ogrid), dim3(256), 0, c->stream, (const float*)psi, mask, ny, nx, (int)oz, (int)oy,
-                           (int)ox, t0, t1, t2, (unsigned char*)dout);
-    MVS_HIP_TRY(c, hipGetLastError());
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->timing_valid = true;
-    if (out_mem == MVS_MEM_HOST) {
-        MVS_HIP_TRY(c, hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
-        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    // the work area goes back to the pool; the pool hands it out again only to work later on this stream
-    return work.release();
+    DeconvCall K{views, weights, n_views, shape, ndim, kernels1, kernels2, ksize, sep1, sep2, opts, out, out_mem};
+    int rc = dc_check(mvs_ctx(device), K);
+    if (!rc) rc = K.F.begin(device);
+    if (!rc) rc = dc_plan_and_taps(K);
+    if (!rc) rc = dc_reserve(K);
+    if (!rc) rc = dc_upload_taps(K);
+    if (!rc) rc = dc_prepare(K);
+    for (int it = 0; !rc && it < opts->n_iterations; ++it)
+        for (int v = 0; !rc && v < n_views; ++v) rc = dc_view(K, v);
+    if (!rc) rc = dc_erosion_mask(K);
+    if (!rc) rc = dc_write_result(K);
+    return rc ? rc : K.F.finish();
 }

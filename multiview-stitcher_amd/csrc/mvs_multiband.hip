@@ -17,6 +17,7 @@
 #include "mvs_intensity_dev.h"
 #include "mvs_internal.h"
 #include "mvs_multiband_plan.h"
+#include "mvs_stack_frame.h"
 
 namespace {
 
@@ -284,129 +285,145 @@ int dec_of(const mp::Plan& p, int l) {
     return (p.axis[0].decimated[l] ? DEC_Z : 0) | (p.axis[1].decimated[l] ? DEC_Y : 0) | (p.axis[2].decimated[l] ? DEC_X : 0);
 }
 
+const char* const NAME = "mvs_multiband_fuse";
+
+// One mvs_multiband_fuse call: its arguments, the frame, the plan and the work area laid out over it.  The steps below run in the
+// order of the entry point.
+struct MultibandCall {
+    const float *views, *weights;
+    int V;
+    const int64_t* shape;
+    int ndim;
+    const mvs_multiband_opts_t* opts;
+    void* out;
+    int32_t out_mem;
+    MvsStackFrame F;
+    mp::Plan plan;
+    mvs_stack_frame::OutBox box;
+    mp::WorkArea area;
+
+    int L() const { return plan.top; }
+    int* flag() const { return (int*)(F.W + area.flag); }
+    float* F0() const { return (float*)(F.W + area.f0); }
+    unsigned char* win() const { return (unsigned char*)(F.W + area.win); }
+    float* gD(int l) const { return (float*)(F.W + area.d[l]); }
+    float* gA(int l) const { return (float*)(F.W + area.a[l]); }
+    float* r(int l) const { return (float*)(F.W + area.r[l]); }
+};
+
+// argument checks (they need no device) and the plan
+int mb_check_and_plan(MvsContext* c0, MultibandCall& K) {
+    const mvs_multiband_opts_t* opts = K.opts;
+    if (!K.views || !K.weights || !K.shape || !opts || !K.out) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_multiband_fuse: NULL argument");
+    if (K.V < 1 || K.V > mp::kMaxViews) return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_multiband_fuse: n_views must be in 1 .. %d", mp::kMaxViews);
+    if (K.ndim != 2 && K.ndim != 3) return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_multiband_fuse: ndim must be 2 or 3");
+    for (int k = 0; k < 3; ++k)
+        if (opts->levels[k] < 0 || opts->levels[k] > mp::kMaxLevels)
+            return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_multiband_fuse: levels[%d] = %d is outside 0 .. %d", k, (int)opts->levels[k], mp::kMaxLevels);
+    if (int rc = mvs_stack_check_out(c0, NAME, K.out_mem, opts->out_dtype)) return rc;
+    if (K.ndim == 2 && (K.shape[0] != 1 || opts->levels[0] != 0 || opts->trim[0] != 0))
+        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_multiband_fuse: 2D data has shape[0] == 1, levels[0] == 0 and trim[0] == 0");
+    if (!mp::make_plan(opts->levels, opts->index_origin, K.shape, &K.plan))
+        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_multiband_fuse: a shape or an index_origin is out of range");
+    for (int k = 0; k < 3; ++k)
+        if (int rc = mvs_stack_check_trim(c0, NAME, K.shape, opts->trim, k)) return rc;
+    if (int rc = mvs_stack_check_size(c0, NAME, K.plan.size[0], K.V)) return rc;
+    K.box = mvs_stack_frame::out_box(K.shape, opts->trim, opts->out_dtype);
+    K.area = mp::work_area(K.plan, K.V, K.out_mem == MVS_MEM_HOST ? K.box.out_bytes : 0);
+    return MVS_OK;
+}
+
+// F0, D_v (= gD of level 0), the winner map and the flag
+int mb_prepare(MultibandCall& K) {
+    MvsContext* c = K.F.c;
+    const long long S = K.plan.size[0];
+    MVS_HIP_TRY(c, hipMemsetAsync(K.flag(), 0, mp::kFlagBytes, c->stream));
+    const int vec = (S % 4 == 0) && ((uintptr_t)K.views % 16 == 0) && ((uintptr_t)K.weights % 16 == 0);
+    hipLaunchKernelGGL(mb_prepare_kernel, dim3(mp::grid_blocks((S + 3) / 4, mp::kThreads)), dim3(mp::kThreads), 0, c->stream, K.views, K.weights, K.V, S, vec,
+                       K.F0(), K.gD(0), K.win(), K.flag());
+    MVS_HIP_TRY(c, hipGetLastError());
+    return MVS_OK;
+}
+
+// gD, gA of levels 1 .. L, each from the level below
+int mb_reduce_levels(MultibandCall& K) {
+    MvsContext* c = K.F.c;
+    for (int l = 0; l < K.L(); ++l) {
+        ReduceArgs a{};
+        a.d_in = K.gD(l);
+        a.a_in = l ? K.gA(l) : nullptr;
+        a.win = K.win();
+        a.d_out = K.gD(l + 1);
+        a.a_out = K.gA(l + 1);
+        a.in = level_of(K.plan, l);
+        a.out = level_of(K.plan, l + 1);
+        a.dec = dec_of(K.plan, l);
+        a.V = K.V;
+        a.s_in = K.plan.size[l];
+        a.s_out = K.plan.size[l + 1];
+        const long long steps = 2LL * K.V * a.out.n[0] * mp::tiles_y(a.out.n[1]) * mp::tiles_x(a.out.n[2]);
+        hipLaunchKernelGGL(mb_reduce_kernel, dim3(mp::grid_blocks(steps, 1)), dim3(mp::kThreads), 0, c->stream, a, (const int*)K.flag());
+        MVS_HIP_TRY(c, hipGetLastError());
+    }
+    return MVS_OK;
+}
+
+// what the collapse of level l reads
+CollapseArgs collapse_args(const MultibandCall& K, int l) {
+    const int L = K.L();
+    CollapseArgs a{};
+    a.d = K.gD(l);
+    a.a = l ? K.gA(l) : nullptr;
+    a.win = K.win();
+    a.d_up = l < L ? K.gD(l + 1) : nullptr;
+    a.r_up = l < L ? K.r(l + 1) : nullptr;
+    a.cur = level_of(K.plan, l);
+    a.up = level_of(K.plan, l < L ? l + 1 : l);
+    a.dec = l < L ? dec_of(K.plan, l) : 0;
+    a.V = K.V;
+    a.s_cur = K.plan.size[l];
+    a.s_up = l < L ? K.plan.size[l + 1] : 0;
+    return a;
+}
+
+// r of levels L .. 1, from the top down
+int mb_collapse_levels(MultibandCall& K) {
+    MvsContext* c = K.F.c;
+    for (int l = K.L(); l > 0; --l) {
+        const CollapseArgs a = collapse_args(K, l);
+        hipLaunchKernelGGL(mb_collapse_kernel, dim3(mp::grid_blocks(a.s_cur, mp::kThreads)), dim3(mp::kThreads), 0, c->stream, a, K.r(l), (const int*)K.flag());
+        MVS_HIP_TRY(c, hipGetLastError());
+    }
+    return MVS_OK;
+}
+
+// level 0 with the epilogue: F0 + r_0, trimmed and cast, where the frame wants the result
+int mb_level0_out(MultibandCall& K) {
+    MvsContext* c = K.F.c;
+    const CollapseArgs a = collapse_args(K, 0);
+    const int oz = (int)K.box.oz, oy = (int)K.box.oy, ox = (int)K.box.ox;
+    const int grid = mp::grid_blocks(K.box.oz * K.box.oy * K.box.ox, mp::kThreads);
+    const int t0 = (int)K.opts->trim[0], t1 = (int)K.opts->trim[1], t2 = (int)K.opts->trim[2];
+    mvs_dispatch_dtype(K.opts->out_dtype, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL(mb_collapse_out_kernel<T>, dim3(grid), dim3(mp::kThreads), 0, c->stream, a, (const float*)K.F0(), t0, t1, t2, oz, oy, ox,
+                           (T*)K.F.dout, (const int*)K.flag());
+    });
+    MVS_HIP_TRY(c, hipGetLastError());
+    return MVS_OK;
+}
+
 }  // namespace
 
 extern "C" int mvs_multiband_fuse(int device, const float* views, const float* weights, int32_t n_views, const int64_t shape[3], int32_t ndim,
                                   const mvs_multiband_opts_t* opts, void* out, int32_t out_mem) {
-    MvsContext* c0 = mvs_ctx(device);
-    // argument checks first: they need no device
-    if (!views || !weights || !shape || !opts || !out) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_multiband_fuse: NULL argument");
-    if (n_views < 1 || n_views > mp::kMaxViews)
-        return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_multiband_fuse: n_views must be in 1 .. %d", mp::kMaxViews);
-    if (ndim != 2 && ndim != 3) return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_multiband_fuse: ndim must be 2 or 3");
-    for (int k = 0; k < 3; ++k)
-        if (opts->levels[k] < 0 || opts->levels[k] > mp::kMaxLevels)
-            return mvs_fail(c0, MVS_ERR_UNSUPPORTED, "mvs_multiband_fuse: levels[%d] = %d is outside 0 .. %d", k, (int)opts->levels[k], mp::kMaxLevels);
-    if (out_mem != MVS_MEM_HOST && out_mem != MVS_MEM_DEVICE) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_multiband_fuse: bad out_mem");
-    if (opts->out_dtype != MVS_U8 && opts->out_dtype != MVS_U16 && opts->out_dtype != MVS_F32)
-        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_multiband_fuse: bad out_dtype");
-    if (ndim == 2 && (shape[0] != 1 || opts->levels[0] != 0 || opts->trim[0] != 0))
-        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_multiband_fuse: 2D data has shape[0] == 1, levels[0] == 0 and trim[0] == 0");
-    mp::Plan plan;
-    if (!mp::make_plan(opts->levels, opts->index_origin, shape, &plan))
-        return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_multiband_fuse: a shape or an index_origin is out of range");
-    for (int k = 0; k < 3; ++k)
-        if (opts->trim[k] < 0 || 2 * opts->trim[k] >= shape[k])
-            return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_multiband_fuse: trim on axis %d leaves nothing", k);
-    if (plan.size[0] * n_views > (1LL << 40)) return mvs_fail(c0, MVS_ERR_INVALID_ARG, "mvs_multiband_fuse: too large");
-
-    MvsContext* c;
-    int rc = mvs_check_ready(device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::recursive_mutex> lock(c->mu);
-    MVS_HIP_TRY(c, hipSetDevice(mvs_hip_device(device)));
-    const int V = n_views, L = plan.top;
-    const long long S = plan.size[0];
-
-    // device work area: flag | F0 | winner map | gD of levels 0 .. L | gA of levels 1 .. L | r of levels 1 .. L | host result staging
-    size_t off = 256;
-    const size_t off_f0 = off;
-    off += align_up((size_t)S * 4);
-    const size_t off_win = off;
-    off += align_up((size_t)S);
-    size_t off_d[mp::kMaxLevels + 1], off_a[mp::kMaxLevels + 1], off_r[mp::kMaxLevels + 1];
-    for (int l = 0; l <= L; ++l) {
-        off_d[l] = off;
-        off += align_up((size_t)plan.size[l] * 4 * V);
-    }
-    off_a[0] = off_r[0] = 0;
-    for (int l = 1; l <= L; ++l) {
-        off_a[l] = off;
-        off += align_up((size_t)plan.size[l] * 4 * V);
-    }
-    for (int l = 1; l <= L; ++l) {
-        off_r[l] = off;
-        off += align_up((size_t)plan.size[l] * 4);
-    }
-    const size_t off_out = off;
-    const size_t out_elem = mvs_dtype_size(opts->out_dtype);
-    const long long oz = shape[0] - 2 * opts->trim[0], oy = shape[1] - 2 * opts->trim[1], ox = shape[2] - 2 * opts->trim[2];
-    const size_t out_bytes = (size_t)(oz * oy * ox) * out_elem;
-    MvsWorkArea work(c);
-    rc = work.alloc(off_out + (out_mem == MVS_MEM_HOST ? out_bytes : 0));
-    if (rc) return rc;
-    char* W = (char*)work.ptr;
-    int* flag = (int*)W;
-    float* F0 = (float*)(W + off_f0);
-    unsigned char* win = (unsigned char*)(W + off_win);
-    void* dout = out_mem == MVS_MEM_HOST ? (void*)(W + off_out) : out;
-
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    MVS_HIP_TRY(c, hipMemsetAsync(flag, 0, 256, c->stream));
-    const int vec = (S % 4 == 0) && ((uintptr_t)views % 16 == 0) && ((uintptr_t)weights % 16 == 0);
-    hipLaunchKernelGGL(mb_prepare_kernel, dim3(mp::grid_blocks((S + 3) / 4, mp::kThreads)), dim3(mp::kThreads), 0, c->stream, views, weights, V, S, vec,
-                       F0, (float*)(W + off_d[0]), win, flag);
-    MVS_HIP_TRY(c, hipGetLastError());
-    for (int l = 0; l < L; ++l) {
-        ReduceArgs a{};
-        a.d_in = (const float*)(W + off_d[l]);
-        a.a_in = l ? (const float*)(W + off_a[l]) : nullptr;
-        a.win = win;
-        a.d_out = (float*)(W + off_d[l + 1]);
-        a.a_out = (float*)(W + off_a[l + 1]);
-        a.in = level_of(plan, l);
-        a.out = level_of(plan, l + 1);
-        a.dec = dec_of(plan, l);
-        a.V = V;
-        a.s_in = plan.size[l];
-        a.s_out = plan.size[l + 1];
-        const long long steps = 2LL * V * a.out.n[0] * mp::tiles_y(a.out.n[1]) * mp::tiles_x(a.out.n[2]);
-        hipLaunchKernelGGL(mb_reduce_kernel, dim3(mp::grid_blocks(steps, 1)), dim3(mp::kThreads), 0, c->stream, a, (const int*)flag);
-        MVS_HIP_TRY(c, hipGetLastError());
-    }
-    for (int l = L; l >= 0; --l) {
-        CollapseArgs a{};
-        a.d = (const float*)(W + off_d[l]);
-        a.a = l ? (const float*)(W + off_a[l]) : nullptr;
-        a.win = win;
-        a.d_up = l < L ? (const float*)(W + off_d[l + 1]) : nullptr;
-        a.r_up = l < L ? (const float*)(W + off_r[l + 1]) : nullptr;
-        a.cur = level_of(plan, l);
-        a.up = level_of(plan, l < L ? l + 1 : l);
-        a.dec = l < L ? dec_of(plan, l) : 0;
-        a.V = V;
-        a.s_cur = plan.size[l];
-        a.s_up = l < L ? plan.size[l + 1] : 0;
-        if (l > 0) {
-            hipLaunchKernelGGL(mb_collapse_kernel, dim3(mp::grid_blocks(a.s_cur, mp::kThreads)), dim3(mp::kThreads), 0, c->stream, a, (float*)(W + off_r[l]),
-                               (const int*)flag);
-        } else {
-            const int grid = mp::grid_blocks(oz * oy * ox, mp::kThreads);
-            const int t0 = (int)opts->trim[0], t1 = (int)opts->trim[1], t2 = (int)opts->trim[2];
-            mvs_dispatch_dtype(opts->out_dtype, [&](auto tag) {
-                using T = decltype(tag);
-                hipLaunchKernelGGL(mb_collapse_out_kernel<T>, dim3(grid), dim3(mp::kThreads), 0, c->stream, a, (const float*)F0, t0, t1, t2, (int)oz, (int)oy,
-                                   (int)ox, (T*)dout, (const int*)flag);
-            });
-        }
-        MVS_HIP_TRY(c, hipGetLastError());
-    }
-    MVS_HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->timing_valid = true;
-    if (out_mem == MVS_MEM_HOST) {
-        MVS_HIP_TRY(c, hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
-        MVS_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    // the work area goes back to the pool; the pool hands it out again only to work later on this stream
-    return work.release();
+    MultibandCall K{views, weights, n_views, shape, ndim, opts, out, out_mem};
+    int rc = mb_check_and_plan(mvs_ctx(device), K);
+    if (!rc) rc = K.F.begin(device);
+    if (!rc) rc = K.F.reserve(K.area.total, K.area.out, out, out_mem, K.box.out_bytes);
+    if (!rc) rc = mb_prepare(K);
+    if (!rc) rc = mb_reduce_levels(K);
+    if (!rc) rc = mb_collapse_levels(K);
+    if (!rc) rc = mb_level0_out(K);
+    return rc ? rc : K.F.finish();
 }

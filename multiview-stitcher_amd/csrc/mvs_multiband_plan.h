@@ -9,6 +9,8 @@
 #pragma once
 #include <cstdint>
 
+#include "mvs_stack_frame.h"
+
 namespace mvs_multiband_plan {
 
 constexpr int kMaxLevels = 6;         // levels per axis: the radius 4 (2^L - 1) is 252 voxels at 6
@@ -22,6 +24,7 @@ constexpr long long kMaxIndex = 1LL << 29;   // |index_origin| and every extent 
 constexpr int kTileY = 16, kTileX = 32;
 constexpr int kWinY = 2 * kTileY + 3, kWinX = 2 * kTileX + 3;
 constexpr int kLdsBytes = (kWinY + kTileY) * kWinX * 4;      // the window and its y-reduced rows: 13,668 bytes
+constexpr int kFlagBytes = 256;       // head of the work area: the "views differ somewhere" word, cleared with its padding
 
 inline long long floor_half(long long a) { return a >= 0 ? a / 2 : -((-a + 1) / 2); }
 inline long long ceil_half(long long a) { return -floor_half(-a); }
@@ -75,6 +78,28 @@ inline long long coarse_samples(const Plan& p) {
     long long s = 0;
     for (int l = 1; l <= p.top; ++l) s += p.size[l];
     return s;
+}
+
+// The device work area of one call, every part on a 256-byte boundary: flag | F0 | winner map | gD of levels 0 .. L (n_views planes
+// each) | gA of levels 1 .. L | r of levels 1 .. L (one plane) | `staged_bytes` of a host result.
+struct WorkArea {
+    size_t flag, f0, win;
+    size_t d[kMaxLevels + 1], a[kMaxLevels + 1], r[kMaxLevels + 1];      // (a[0], r[0] and the levels above the top: 0, not held)
+    size_t out, total;
+};
+
+inline WorkArea work_area(const Plan& p, int n_views, size_t staged_bytes) {
+    WorkArea w = {};
+    mvs_stack_frame::Layout L;
+    w.flag = L.take(kFlagBytes, 256);
+    w.f0 = L.take((size_t)p.size[0] * 4, 256);
+    w.win = L.take((size_t)p.size[0], 256);
+    for (int l = 0; l <= p.top; ++l) w.d[l] = L.take((size_t)p.size[l] * 4 * n_views, 256);
+    for (int l = 1; l <= p.top; ++l) w.a[l] = L.take((size_t)p.size[l] * 4 * n_views, 256);
+    for (int l = 1; l <= p.top; ++l) w.r[l] = L.take((size_t)p.size[l] * 4, 256);
+    w.out = L.take(staged_bytes, 1);
+    w.total = L.total;
+    return w;
 }
 
 // The voxels whose inputs can reach a result: 4 (2^levels - 1) per axis (required_overlap).

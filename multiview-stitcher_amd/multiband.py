@@ -36,7 +36,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .device import DeviceArray, is_device_array
+from ._stack_ops import run_stack_call, stack_dims, stack_inputs
 
 MAX_LEVELS = _lib.MVS_MULTIBAND_MAX_LEVELS
 MAX_VIEWS = _lib.MVS_MULTIBAND_MAX_VIEWS
@@ -74,32 +74,18 @@ def _run(views, weights, ndim, levels3, origin3, trim, out_dtype, out_on_device,
     ``out_dtype``; a DeviceArray or a numpy array.  ``out``: a contiguous DeviceArray of the result shape and dtype to write into
     (with ``out_on_device``)."""
     lib = _lib.init(device)
-    n_views = views.shape[0]
-    shape = (1,) * (3 - ndim) + tuple(views.shape[1:])
-    t3 = [0] * (3 - ndim) + [int(t) for t in trim]
-    res_shape = tuple(s - 2 * t for s, t in zip(views.shape[1:], trim))
-    opts = _lib.mvs_multiband_opts_t()
-    for k in range(3):
-        opts.levels[k] = levels3[k]
-        opts.index_origin[k] = origin3[k]
-        opts.trim[k] = t3[k]
-    opts.out_dtype = _lib.DTYPE_CODES[np.dtype(out_dtype)]
-    opts.flags = 0
-    if out_on_device:
-        if out is None:
-            out = DeviceArray.empty(res_shape, out_dtype, device)
-        elif tuple(out.shape) != res_shape or not out.is_contiguous() or out.dtype != np.dtype(out_dtype):
-            raise ValueError("out must be a contiguous DeviceArray of the result shape and dtype")
-        optr, omem = out.ptr, _lib.MVS_MEM_DEVICE
-    else:
-        out = np.empty(res_shape, dtype=out_dtype)
-        optr, omem = out.ctypes.data, _lib.MVS_MEM_HOST
-    rc = lib.mvs_multiband_fuse(device, C.c_void_p(views.ptr), C.c_void_p(weights.ptr), n_views, _lib.i64x3(shape), ndim, C.byref(opts),
-                                C.c_void_p(optr), omem)
-    _lib.check(rc, device, "mvs_multiband_fuse")
-    if out_on_device:
-        out.mark_written()
-    return out
+
+    def call(shape3, t3, out_dtype_code, out_ptr, out_mem):
+        opts = _lib.mvs_multiband_opts_t()
+        opts.levels[:] = levels3
+        opts.index_origin[:] = origin3
+        opts.trim[:] = t3
+        opts.out_dtype = out_dtype_code
+        opts.flags = 0
+        return lib.mvs_multiband_fuse(device, C.c_void_p(views.ptr), C.c_void_p(weights.ptr), views.shape[0], _lib.i64x3(shape3), ndim, C.byref(opts),
+                                      C.c_void_p(out_ptr), out_mem)
+
+    return run_stack_call("mvs_multiband_fuse", views, ndim, trim, out_dtype, out_on_device, device, out, call)
 
 
 def multi_band_fusion(transformed_views, blending_weights, n_levels=3, index_origin=None, device=0):
@@ -111,31 +97,14 @@ def multi_band_fusion(transformed_views, blending_weights, n_levels=3, index_ori
     mosaic).  ``index_origin``: the global output-grid index of the array's first sample per axis (a sequence or a dict; default 0):
     chunks of one stack that pass their own agree bit for bit where each holds ``required_overlap`` voxels around a result.  At most
     254 views."""
-    on_dev = is_device_array(transformed_views)
-    n_views = int(transformed_views.shape[0])
-    ndim = len(transformed_views.shape) - 1
-    if ndim not in (2, 3):
-        raise ValueError("multi_band_fusion fuses 2D or 3D views: transformed_views is (n_views, [z,] y, x)")
-    if tuple(blending_weights.shape) != tuple(transformed_views.shape):
-        raise ValueError("blending_weights must have the shape of transformed_views")
+    name = "multi_band_fusion"
+    n_views, ndim = stack_dims(name, transformed_views, blending_weights)
     if not 1 <= n_views <= MAX_VIEWS:
         raise ValueError(f"multi_band_fusion takes 1..{MAX_VIEWS} views, got {n_views}")
-    levels3, origin3 = _levels3(n_levels, ndim), _origin3(index_origin, ndim)
-    if on_dev:
-        if not is_device_array(blending_weights):
-            blending_weights = DeviceArray.from_host(np.ascontiguousarray(blending_weights, dtype=np.float32), device)
-        for a in (transformed_views, blending_weights):
-            if a.dtype != np.float32 or not a.is_contiguous():
-                raise TypeError("device inputs of multi_band_fusion are contiguous float32 DeviceArrays")
-            a.wait_ready(device)
-        return _run(transformed_views, blending_weights, ndim, levels3, origin3, [0] * ndim, np.float32, True, device)
-    host = np.asarray(transformed_views)
-    in_dtype = host.dtype
-    views = DeviceArray.from_host(np.ascontiguousarray(host, dtype=np.float32), device)
-    weights = DeviceArray.from_host(np.ascontiguousarray(blending_weights, dtype=np.float32), device)
-    out_dtype = in_dtype if in_dtype in _lib.DTYPE_CODES else np.dtype(np.float32)
-    res = _run(views, weights, ndim, levels3, origin3, [0] * ndim, out_dtype, False, device)
-    return res.astype(in_dtype, copy=False)
+    levels3, origin3 = _levels3(n_levels, ndim), _origin3(index_origin, ndim)      # (their errors come before any upload)
+    views, weights, ndim, out_dtype, on_dev, cast_dtype = stack_inputs(name, transformed_views, blending_weights, device)
+    res = _run(views, weights, ndim, levels3, origin3, [0] * ndim, out_dtype, on_dev, device)
+    return res if cast_dtype is None else res.astype(cast_dtype, copy=False)
 
 
 def _required_overlap(func_kwargs):

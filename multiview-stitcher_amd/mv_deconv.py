@@ -17,7 +17,7 @@ import numpy as np
 from scipy import ndimage
 
 from . import _lib
-from .device import DeviceArray, is_device_array
+from ._stack_ops import run_stack_call, stack_dims, stack_inputs
 
 KERNEL_LIMIT = 63          # largest kernel extent per axis of the direct convolution (csrc/mvs_deconv.hip)
 SEPARABLE_TOL = 1e-6       # rank-1 test: max |K - outer(marginals)| <= SEPARABLE_TOL * max |K|
@@ -174,36 +174,22 @@ def _run(views, weights, ndim, kernels, n_iterations, lambda_reg, min_value, ero
     DeviceArray of the result shape and dtype to write into (with ``out_on_device``)."""
     k1, k2, s1, s2 = kernels
     lib = _lib.init(device)
-    n_views = views.shape[0]
-    shape = (1,) * (3 - ndim) + tuple(views.shape[1:])
-    t3 = [0] * (3 - ndim) + [int(t) for t in trim]
-    res_shape = tuple(s - 2 * t for s, t in zip(views.shape[1:], trim))
-    opts = _lib.mvs_deconv_opts_t()
-    opts.n_iterations = int(n_iterations)
-    opts.erosion_px = int(erosion_px)
-    opts.lambda_reg = float(lambda_reg)
-    opts.min_value = float(min_value)
-    for k in range(3):
-        opts.trim[k] = t3[k]
-    opts.out_dtype = _lib.DTYPE_CODES[np.dtype(out_dtype)]
-    opts.flags = _lib.MVS_DECONV_PREPARE_WEIGHTS if prepare_weights else 0
-    if out_on_device:
-        if out is None:
-            out = DeviceArray.empty(res_shape, out_dtype, device)
-        elif tuple(out.shape) != res_shape or not out.is_contiguous() or out.dtype != np.dtype(out_dtype):
-            raise ValueError("out must be a contiguous DeviceArray of the result shape and dtype")
-        optr, omem = out.ptr, _lib.MVS_MEM_DEVICE
-    else:
-        out = np.empty(res_shape, dtype=out_dtype)
-        optr, omem = out.ctypes.data, _lib.MVS_MEM_HOST
-    rc = lib.mvs_mv_deconv(device, C.c_void_p(views.ptr), C.c_void_p(weights.ptr), n_views, _lib.i64x3(shape), ndim,
-                           k1.ctypes.data, k2.ctypes.data, _lib.i64x3(k1.shape[1:]),
-                           None if s1 is None else s1.ctypes.data, None if s2 is None else s2.ctypes.data,
-                           C.byref(opts), C.c_void_p(optr), omem)
-    _lib.check(rc, device, "mvs_mv_deconv")
-    if out_on_device:
-        out.mark_written()
-    return out
+
+    def call(shape3, t3, out_dtype_code, out_ptr, out_mem):
+        opts = _lib.mvs_deconv_opts_t()
+        opts.n_iterations = int(n_iterations)
+        opts.erosion_px = int(erosion_px)
+        opts.lambda_reg = float(lambda_reg)
+        opts.min_value = float(min_value)
+        opts.trim[:] = t3
+        opts.out_dtype = out_dtype_code
+        opts.flags = _lib.MVS_DECONV_PREPARE_WEIGHTS if prepare_weights else 0
+        return lib.mvs_mv_deconv(device, C.c_void_p(views.ptr), C.c_void_p(weights.ptr), views.shape[0], _lib.i64x3(shape3), ndim,
+                                 k1.ctypes.data, k2.ctypes.data, _lib.i64x3(k1.shape[1:]),
+                                 None if s1 is None else s1.ctypes.data, None if s2 is None else s2.ctypes.data,
+                                 C.byref(opts), C.c_void_p(out_ptr), out_mem)
+
+    return run_stack_call("mvs_mv_deconv", views, ndim, trim, out_dtype, out_on_device, device, out, call)
 
 
 def multi_view_deconvolution(
@@ -227,31 +213,13 @@ def multi_view_deconvolution(
     without a host round trip.  ``psfs``: one PSF per view (else ``ValueError``), zero-padded to a common shape; without
     them the PSF is estimated from ``output_spacing`` (``na``, ``wavelength_um``) or is a 1.5-pixel Gaussian.  Kernels
     larger than 63 along an axis raise ``NotImplementedError``."""
-    on_dev = is_device_array(transformed_views)
-    n_views = int(transformed_views.shape[0])
-    ndim = len(transformed_views.shape) - 1
-    if ndim not in (2, 3):
-        raise ValueError("multi_view_deconvolution fuses 2D or 3D views: transformed_views is (n_views, [z,] y, x)")
-    if tuple(blending_weights.shape) != tuple(transformed_views.shape):
-        raise ValueError("blending_weights must have the shape of transformed_views")
-    kernels = _kernels(n_views, ndim, psfs, psf_type, output_spacing, na, wavelength_um)
-    if on_dev:
-        if not is_device_array(blending_weights):
-            blending_weights = DeviceArray.from_host(np.ascontiguousarray(blending_weights, dtype=np.float32), device)
-        for a in (transformed_views, blending_weights):
-            if a.dtype != np.float32 or not a.is_contiguous():
-                raise TypeError("device inputs of multi_view_deconvolution are contiguous float32 DeviceArrays")
-            a.wait_ready(device)
-        return _run(transformed_views, blending_weights, ndim, kernels, n_iterations, lambda_reg, min_value,
-                    sample_boundary_erosion_px, [0] * ndim, np.float32, True, device)
-    host = np.asarray(transformed_views)
-    in_dtype = host.dtype
-    views = DeviceArray.from_host(np.ascontiguousarray(host, dtype=np.float32), device)
-    weights = DeviceArray.from_host(np.ascontiguousarray(blending_weights, dtype=np.float32), device)
-    out_dtype = in_dtype if in_dtype in _lib.DTYPE_CODES else np.dtype(np.float32)
-    res = _run(views, weights, ndim, kernels, n_iterations, lambda_reg, min_value, sample_boundary_erosion_px,
-               [0] * ndim, out_dtype, False, device)
-    return res.astype(in_dtype, copy=False)
+    name = "multi_view_deconvolution"
+    n_views, ndim = stack_dims(name, transformed_views, blending_weights)
+    kernels = _kernels(n_views, ndim, psfs, psf_type, output_spacing, na, wavelength_um)      # (its errors come before any upload)
+    views, weights, ndim, out_dtype, on_dev, cast_dtype = stack_inputs(name, transformed_views, blending_weights, device)
+    res = _run(views, weights, ndim, kernels, n_iterations, lambda_reg, min_value, sample_boundary_erosion_px, [0] * ndim, out_dtype,
+               on_dev, device)
+    return res if cast_dtype is None else res.astype(cast_dtype, copy=False)
 
 
 # ---- PSFs measured from beads --------------------------------------------------------------------------------------------------

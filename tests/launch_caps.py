@@ -120,8 +120,8 @@ ROWS = [
     dict(name="DCT general quality", source=os.path.join(CSRC, "mvs_dct_weights.hip"), cap=4096,
          pattern=r"n = std::max<long long>\(1, std::min<long long>\(\{n, items, (\d+)\}\)\);", per_block=1, min_trips=2.0, lib_constant=None,
          cases=[("2 views, dct_size 2", DCT_GENERAL_SHAPE, dct_general_items(DCT_GENERAL_SHAPE, DCT_GENERAL_SIZE))]),
-    # the element-wise kernels of the deconvolution launched with grid_for(S) and grid_for(oz * oy * ox): a lane per voxel
-    dict(name="deconvolution element-wise", source=os.path.join(CSRC, "mvs_deconv.hip"), cap=256 * 32,
+    # the element-wise kernels of the deconvolution launched with grid_for(S) and grid_for(oz * oy * ox) of its plan header: a lane per voxel
+    dict(name="deconvolution element-wise", source=os.path.join(CSRC, "mvs_deconv_plan.h"), cap=256 * 32,
          pattern=r"int grid_for\(long long n\) \{ return \(int\)std::max<long long>\(1, std::min<long long>\(\(n \+ 255\) / 256, (\d+ \* \d+)\)\); \}",
          per_block=256, min_trips=2.0, lib_constant=None, cases=[("2 views", ELEMENTWISE_SHAPE, prod(ELEMENTWISE_SHAPE))]),
 ]

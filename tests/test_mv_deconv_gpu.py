@@ -1,7 +1,8 @@
 """GPU: multi-view deconvolution (fusion.multi_view_deconvolution, csrc/mvs_deconv.hip) against the numpy / scipy
 restatement of the reference (tests/deconv_oracle.py): the direct function on both convolution paths, fuse_np against
 the oracle chain resample + blending weights + restatement, a chunked fuse() (in memory and to Zarr) against the
-per-chunk oracle composed into the mosaic, and DeviceArray in / out.  The edge cases (do.edge_cases(): tile edges, the
+per-chunk oracle composed into the mosaic, DeviceArray in / out, and the call frame the deconvolution shares with multi-band
+fusion (trimmed host / device / caller-supplied results of both, bit for bit).  The edge cases (do.edge_cases(): tile edges, the
 widest and tallest kernels, even and asymmetric kernels on both paths, thin chunks, voxels no view covers, 65 views)
 run a few iterations each; tests/test_mv_deconv_host.py shows that each would catch the kernel mistakes it targets."""
 import functools
@@ -346,3 +347,51 @@ def test_device_arrays_in_and_out(hip_device):
                                           n_iterations=ITERATIONS, device=hip_device, **kw)
     assert is_device_array(got) and got.dtype == np.float32
     np.testing.assert_array_equal(got.get(), want)
+
+
+def _frame_run(entry, shape):
+    """``run(trim, out_on_device, out=None)`` of one stack entry point on two views of ``shape`` with a uint16 result: the
+    deconvolution with one iteration of the default 1.5-pixel Gaussian kernels, multi-band fusion with n_levels = 1."""
+    from multiview_stitcher_amd import multiband, mv_deconv
+    from multiview_stitcher_amd.device import DeviceArray
+
+    def run(trim, out_on_device, out=None, device=None):
+        ndim = len(shape)
+        rng = np.random.default_rng(17)
+        views = (rng.random((2,) + shape) * 900 + 50).astype(np.float32)
+        views[0][..., :5] = np.nan
+        views[1][..., -4:, :] = np.nan
+        blend = (rng.random((2,) + shape) + 0.1).astype(np.float32)
+        blend /= blend.sum(0)
+        dv, dw = DeviceArray.from_host(views, device), DeviceArray.from_host(blend, device)
+        if entry == "mv_deconv":
+            kernels = mv_deconv._kernels(2, ndim, None, "EFFICIENT_BAYESIAN", None, 0.8, 0.5)
+            return mv_deconv._run(dv, dw, ndim, kernels, 1, 0.0, 1e-4, 0, list(trim), np.uint16, out_on_device, device, out=out)
+        return multiband._run(dv, dw, ndim, [0] * (3 - ndim) + [1] * ndim, [0, 0, 0], list(trim), np.uint16, out_on_device, device, out=out)
+
+    return run
+
+
+@pytest.mark.parametrize("shape,trim", [((24, 40), (2, 3)), ((6, 12, 20), (1, 2, 3))])
+@pytest.mark.parametrize("entry", ["mv_deconv", "multiband"])
+def test_stack_frame_trim_and_result_paths(hip_device, entry, shape, trim):
+    """The frame both stack entry points share (csrc/mvs_stack_frame.h, _stack_ops.run_stack_call), called through ``_run`` with a
+    non-zero trim and a uint16 result: the host result, the device result and the device result written into a caller's ``out``
+    are bit-equal, of shape S - 2 trim, and equal to the interior of the untrimmed result."""
+    from multiview_stitcher_amd.device import DeviceArray, is_device_array
+
+    run = _frame_run(entry, shape)
+    res_shape = tuple(s - 2 * t for s, t in zip(shape, trim))
+    host = run(trim, False, device=hip_device)
+    dev = run(trim, True, device=hip_device)
+    mine = DeviceArray.empty(res_shape, np.uint16, hip_device)
+    into = run(trim, True, out=mine, device=hip_device)
+    assert isinstance(host, np.ndarray) and is_device_array(dev) and into is mine
+    assert host.dtype == np.uint16 and host.shape == res_shape and tuple(dev.shape) == res_shape and dev.dtype == np.uint16
+    assert host.tobytes() == dev.get().tobytes() == mine.get().tobytes()
+    whole = run([0] * len(shape), False, device=hip_device)
+    assert whole.shape == shape and whole.max() > 0
+    interior = whole[tuple(slice(t, s - t) for s, t in zip(shape, trim))]
+    assert np.array_equal(host, interior)
+    with pytest.raises(ValueError, match="out must be a contiguous DeviceArray of the result shape and dtype"):
+        run(trim, True, out=DeviceArray.empty(shape, np.uint16, hip_device), device=hip_device)

@@ -1,9 +1,12 @@
 """CPU: the host side of multi-view deconvolution -- the restatement (tests/deconv_oracle.py) and the project's PSF /
 compound-kernel helpers against the reference's outputs (tests/golden/mv_deconv_ref.npz), required_overlap, the
-rank-1 test, the public names, the C ABI's struct and argument checks (no device needed)."""
+rank-1 test, the public names, the C ABI's struct and argument checks (no device needed), and csrc/mvs_deconv_plan.h with
+csrc/mvs_stack_frame.h compiled for the host under the address and undefined-behaviour sanitizers."""
 import ctypes
 import functools
 import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -226,3 +229,145 @@ def test_edge_cases_are_separate_and_targeted():
         if "uncovered" in name or name == "3d_zero_iterations":
             assert np.all(np.isnan(views), axis=0).any(), name
     assert edge["2d_views65"][0].shape[0] == 65
+
+
+# --- csrc/mvs_deconv_plan.h and csrc/mvs_stack_frame.h on the host: what mvs_mv_deconv decides without the device ---
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TAP_EXTENTS = [(1, 1, 1), (1, 3, 3), (4, 6, 8), (5, 1, 12), (1, 63, 5), (1, 62, 4), (1, 7, 12)]
+TAP_CASES = [(V, k) for V in (1, 3) for k in TAP_EXTENTS] + [(1, (63, 63, 63))]
+AREA_SHAPES = [(1, 4, 4), (1, 37, 53), (5, 6, 7)]
+# id -> levels, index_origin, shape, trim, views of the two multi-band work areas (uint8 result)
+MULTIBAND_AREAS = {2: ((0, 2, 2), (0, -7, 5), (1, 37, 53), (0, 2, 3), 3), 3: ((1, 2, 2), (3, 0, -4), (5, 22, 31), (1, 2, 3), 2)}
+
+
+def _align(v, a=256):
+    return (v + a - 1) // a * a
+
+
+def _disjoint_and_closed(parts, total):
+    """``parts``: (offset, bytes) of the parts in use; they do not overlap and the last one ends at ``total``."""
+    parts = sorted(p for p in parts if p[1])
+    for (o0, n0), (o1, _) in zip(parts, parts[1:]):
+        assert o0 + n0 <= o1, parts
+    assert parts[-1][0] + parts[-1][1] == total, (parts, total)
+
+
+def _parent_deconv_area(S, sep, ero, host, taps, out_bytes):
+    """The chained offsets of mvs_mv_deconv before the layout builder (mvs_deconv.hip:375-388 of the parent commit)."""
+    fS = 4 * S
+    o = {"psi": 0}
+    o["wr"] = o["psi"] + fS
+    o["a"] = o["wr"] + fS
+    o["b"] = o["a"] + (fS if sep else 0)
+    o["m0"] = o["b"] + (fS if sep else 0)
+    o["m1"] = o["m0"] + (_align(S) if ero else 0)
+    o["bm"] = o["m1"] + (_align(S) if ero else 0)
+    o["pk"] = o["bm"] + 1024 * 4
+    o["tp"] = o["pk"] + 256
+    o["out"] = o["tp"] + _align(taps * 4)
+    o["total"] = o["out"] + (out_bytes if host else 0)
+    return o
+
+
+def _parent_multiband_area(size, V, staged):
+    """The chained offsets of mvs_multiband_fuse before the layout builder (mvs_multiband.hip:321-346 of the parent commit)."""
+    top = len(size) - 1
+    off = 256
+    o = {"flag": 0, "f0": off}
+    off += _align(size[0] * 4)
+    o["win"] = off
+    off += _align(size[0])
+    for name, first, planes in (("d", 0, V), ("a", 1, V), ("r", 1, 1)):
+        o[name] = []
+        for lv in range(first, top + 1):
+            o[name].append(off)
+            off += _align(size[lv] * 4 * planes)
+    o["out"], o["total"] = off, off + staged
+    return o
+
+
+def test_plan_headers_under_sanitizers(tmp_path):
+    """tests/native/deconv_plan_host_test.cpp: a stand-alone program of mvs_deconv_plan.h and mvs_stack_frame.h, built with the host
+    compiler and -fsanitize=address,undefined and run directly.  Its tap tables, pad values, anchors, plan facts and work-area
+    layouts (the multi-band one among them) equal the numpy restatement and the parent commit's offset formulas."""
+    from tests import multiband_oracle as mo
+
+    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
+    assert cxx is not None, "no host C++ compiler"
+    exe, table_file = tmp_path / "deconv_plan_host_test", tmp_path / "taps.f32"
+    cmd = [cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "multiview-stitcher_amd", "csrc"),
+           os.path.join(ROOT, "tests", "native", "deconv_plan_host_test.cpp"), "-o", str(exe)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([str(exe), str(table_file)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    lines = [ln.split() for ln in r.stdout.strip().splitlines()]
+    assert lines[-1] == ["done"]
+    print(r.stdout[-4000:])
+
+    # tap tables: kernels of distinct values, factors whose sums are not 1 (as the program fills them)
+    tables = np.fromfile(table_file, dtype=np.float32)
+    at = 0
+    t_lines = [[int(v) for v in ln[1:]] for ln in lines if ln[0] == "T"]
+    assert [(ln[0], tuple(ln[1:4])) for ln in t_lines] == TAP_CASES
+    for V, kz, ky, kx, kxp in t_lines:
+        assert kxp % 4 == 0 and kx <= kxp < kx + 4
+        kvol, ksep = kz * ky * kx, kz + ky + kx
+        k1 = (np.arange(V * kvol) + 1).astype(np.float32).reshape(V, kz, ky, kx)
+        want = np.zeros((2, V, kz, ky, kxp), np.float32)
+        want[0, ..., :kx], want[1, ..., :kx] = np.flip(k1, (1, 2, 3)), np.flip(k1 + np.float32(V * kvol), (1, 2, 3))
+        assert np.array_equal(tables[at:at + want.size], want.ravel()), (V, kz, ky, kx)
+        at += want.size
+        j, v = np.arange(ksep)[None, :], np.arange(V)[:, None]
+        sep = np.stack([(0.25 + 0.01 * j + v).astype(np.float32), (0.5 + 0.03 * j + 0.1 * v).astype(np.float32)])      # [set][v][kz + ky + kx]
+        want = np.concatenate([np.flip(sep[..., :kz], -1), np.flip(sep[..., kz:kz + ky], -1), np.flip(sep[..., kz + ky:], -1)], axis=-1)
+        assert np.array_equal(tables[at:at + want.size], want.ravel()), (V, kz, ky, kx)
+        at += want.size
+        sx, sy = sep[1][:, kz + ky:].astype(np.float64).sum(1), sep[1][:, kz:kz + ky].astype(np.float64).sum(1)
+        assert np.abs(sx - 1).min() > 0.01 and np.abs(sx * sy - 1).min() > 0.01
+        want = np.stack([sx.astype(np.float32), (sx * sy).astype(np.float32)], axis=1)      # [v][(y pass, z pass)]
+        assert np.array_equal(tables[at:at + want.size], want.ravel()), (V, kz, ky, kx)
+        at += want.size
+    assert at == tables.size
+
+    assert [[int(v) for v in ln[1:]] for ln in lines if ln[0] == "A"] == [[k, k - 1 - k // 2] for k in range(1, 64)]
+
+    facts = {ln[1]: ln[2:] for ln in lines if ln[0] == "F"}
+    assert facts == {"lds_bytes_63": ["48128"], "grid_100x100": ["2", "4", "1"], "extent_64": ["UNSUPPORTED"], "extent_0": ["INVALID_ARG"],
+                     "grid_for": ["1", "2", "8192"], "tile": ["8", "8", "8", "4", "64", "32"], "kmax": ["63"], "init_blocks": ["1024"]}
+    assert int(facts["lds_bytes_63"][0]) == 94 * 128 * 4 < 65536
+
+    # the deconvolution's work area: 2 views, kernels (1, 5, 7), trim (0, 1, 1), a uint16 result
+    w_lines = [[int(v) for v in ln[1:]] for ln in lines if ln[0] == "W"]
+    assert [tuple(ln[:6]) for ln in w_lines] == [s + (sep, ero, host) for s in AREA_SHAPES for sep in (0, 1) for ero in (0, 1) for host in (0, 1)]
+    for nz, ny, nx, sep, ero, host, *rest in w_lines:
+        got = dict(zip(("psi", "wr", "a", "b", "m0", "m1", "bm", "pk", "tp", "out", "total"), rest))
+        out_bytes, taps, S = rest[11:]
+        assert S == nz * ny * nx and out_bytes == nz * (ny - 2) * (nx - 2) * 2
+        assert taps == 2 * 2 * ((1 + 5 + 7) if sep else 1 * 5 * 8)
+        assert got == _parent_deconv_area(S, sep, ero, host, taps, out_bytes), (nz, ny, nx, sep, ero, host)
+        fS = 4 * S
+        parts = [(got["psi"], fS), (got["wr"], fS), (got["bm"], 4096), (got["pk"], 256), (got["tp"], _align(4 * taps))]
+        parts += [(got["a"], fS), (got["b"], fS)] if sep else []
+        parts += [(got["m0"], _align(S)), (got["m1"], _align(S))] if ero else []
+        parts += [(got["out"], out_bytes)] if host else []
+        _disjoint_and_closed(parts, got["total"])
+        assert got["total"] - got["out"] == (out_bytes if host else 0)
+
+    # the multi-band work area of one 2-D and one 3-D plan with 2 levels
+    m_lines = [[int(v) for v in ln[1:]] for ln in lines if ln[0] == "M"]
+    assert [(ln[0], ln[2] > 0) for ln in m_lines] == [(2, False), (2, True), (3, False), (3, True)]
+    for ident, V, staged, top, *rest in m_lines:
+        levels, origin, shape, trim, views = MULTIBAND_AREAS[ident]
+        assert (V, top) == (views, 2) and staged in (0, int(np.prod([s - 2 * t for s, t in zip(shape, trim)])))
+        size, rest = rest[:top + 1], rest[top + 1:]
+        axes = [mo.axis_geometry(o, n, lv, top) for o, n, lv in zip(origin, shape, levels)]
+        assert size == [int(np.prod([a[lv][1] for a in axes])) for lv in range(top + 1)]
+        got = {"flag": rest[0], "f0": rest[1], "win": rest[2], "d": rest[3:4 + top], "a": rest[4 + top:4 + 2 * top], "r": rest[4 + 2 * top:4 + 3 * top],
+               "out": rest[4 + 3 * top], "total": rest[5 + 3 * top]}
+        assert len(rest) == 6 + 3 * top and got == _parent_multiband_area(size, V, staged), (ident, staged)
+        parts = [(got["flag"], 256), (got["f0"], _align(4 * size[0])), (got["win"], _align(size[0])), (got["out"], staged)]
+        parts += [(o, _align(4 * V * size[lv])) for lv, o in enumerate(got["d"])] + [(o, _align(4 * V * size[lv + 1])) for lv, o in enumerate(got["a"])]
+        parts += [(o, _align(4 * size[lv + 1])) for lv, o in enumerate(got["r"])]
+        assert all(o % 256 == 0 for o, _ in parts)
+        _disjoint_and_closed(parts, got["total"])
