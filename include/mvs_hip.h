@@ -166,7 +166,7 @@ int mvs_set_option(int device, const char* key, int64_t value);
  * "fuse_column_chunks" / "fuse_generic_chunks": chunks of mvs_fuse_chunk by the kernel family that fused them (row kernels, region
  * kernels, column kernel, generic kernel; one count per family a call launched: a chunk that the column kernel gave up on because a
  * column met more than 64 views, and that the generic kernel redid, counts in both; content-based and DCT-weighted chunks count in
- * none).  With option "no_regions" = 1 a weighted-average chunk goes to the column kernel, which by default takes it only when the
+ * none; "fuse_weighted_chunks": the chunks of mvs_fuse_chunk_weighted, which count in none of the four).  With option "no_regions" = 1 a weighted-average chunk goes to the column kernel, which by default takes it only when the
  * region planner declines (more than 8 views on a cell, too many cells or regions); tests assert the family they were built for.
  * Content-based chunks that took the bit-faithful passes: "cb_exact_chunks", "cb_exact_large_chunks" (of these, the ones with more than
  * 8 views or a pool beyond 32-bit indices: boxes read from global memory), and their line launches by kernel: "cb_exact_paired_launches"
@@ -980,6 +980,59 @@ int mvs_label_fuse(int device, const mvs_view_t* views, int32_t n_views, int32_t
 #define MVS_LABEL_MAX 2048
 int mvs_label_contacts(int device, const int32_t* labels, int32_t ndim, const int64_t shape[3], int32_t n_labels, int32_t connectivity,
                        uint64_t* counts_out);
+
+/* Masks as fusion weights (masks.feather, fuse(view_weights=)): a binary mask becomes a feathered uint8 weight tile, and the
+ * weighted chunk entry takes one such tile per view next to the image.
+ *
+ * mvs_mask_feather: out (uint8, C-contiguous, the mask's shape, in out_mem) = W(p) = rint(252 (1 - cos(pi min(t, 1))) / 2), with
+ *   t^2 = min over the ZERO voxels q of the mask of sum_k ((p_k - q_k) / width[k])^2.
+ * mask: uint8, nonzero = use; host (C-contiguous; staged for the duration of the call) or device memory (stride[2] == 1; may be a
+ * strided window); only data / dtype / mem / shape / stride are read.  width[] (z, y, x; 2D: width[0] ignored): the feather width
+ * per axis in voxels, 1 <= width[k] <= MVS_FEATHER_MAX_WIDTH (below: MVS_ERR_INVALID_ARG, above: MVS_ERR_UNSUPPORTED).  Voxels
+ * outside the array do not count as zero; a zero voxel gives 0; a mask without a zero gives MVS_FEATHER_FULL_WEIGHT everywhere; with
+ * every width 1 the result is 0 / 252 (no feather).
+ * WHAT IS EXACT.  D = prod_k width[k]^2 <= 2^30 and P_k = D / width[k]^2 are integers, and N(p) = min(D, min_q sum_k (p_k - q_k)^2
+ * P_k) = D min(t, 1)^2 is computed exactly in uint32 by separable min-plus passes: x (the nearest zero of the row within the width,
+ * from the zero voxels of 80 positions as bits), then y, then z (min over |j| <= width of N_prev(p + j e_k) + j^2 P_k, capped at D
+ * after every pass; a capped value plus one term is at most 2^31).  The last pass forms W = rint(252 (0.5 (1 - cos(pi sqrt((double)N /
+ * D))))) in float64, to nearest even; N == 0 and N == D give 0 and 252 without the cosine.  At t = 0, 1/3, 1/2, 2/3, 1 -- the only
+ * rational t with a rational cosine -- 252 times the ramp is an integer, so no exact tie reaches the rounding; a voxel whose value
+ * before rounding lies within an ulp of a half-integer may differ by one from another libm.  Integer minima in a fixed order, no
+ * atomics: equal inputs give equal bytes.
+ * MEMORY.  The passes run in z slabs with a halo of width[0] planes: two uint32 plane sets of (planes + 2 width[0]) ny nx voxels in
+ * device scratch, at most 256 MiB together unless one plane with its halo needs more.  mvs_set_option "feather_slab_planes" = n
+ * fixes the output planes per slab (0, the default: sized to that budget); the result does not depend on it.  Waits for the result;
+ * runs on the context lane of `device`. */
+#define MVS_FEATHER_MAX_WIDTH 32
+#define MVS_FEATHER_FULL_WEIGHT 252
+int mvs_mask_feather(int device, const mvs_view_t* mask, int32_t ndim, const int32_t width[3], void* out, int32_t out_mem);
+
+/* mvs_fuse_chunk_weighted: mvs_fuse_chunk through the generic (full affine map per voxel) kernel with a weight tile per view.
+ * views, opts, out: as for mvs_fuse_chunk (index frame and index_offset included); opts->weights other than MVS_WEIGHTS_NONE is
+ * MVS_ERR_UNSUPPORTED.  wviews[i]: the weight tile of view i -- uint8, host (C-contiguous) or device memory (stride[2] == 1), with
+ * its own shape, stride, matrix and offset (a tile may live on a coarser grid than the image; matrix / offset map an index of the
+ * frame to a pixel of the tile); always the WHOLE tile: index_offset must be 0.  data == NULL: the view has no weights (m = 1).
+ * Only data / dtype / mem / shape / stride / matrix / offset / index_offset of a weight tile are read.
+ * Per output voxel p (chunk index + opts->index_origin), views in view order:
+ *   1. the image sample s_v, the in-bounds test and, under weighted average, the blend weight b_v, with the bits the generic kernel
+ *      of mvs_fuse_chunk gives them (float64 coordinates without contraction, float32 interpolation);
+ *   2. m_v = the linear sample of the tile / 252 as a float32: the coordinate clamped per axis into [0, n - 1] (scipy's
+ *      mode="nearest"), a stored value above 252 counted as 252, lerp(u, v, t) = u + t (v - u) along x, then y, then z (exact where
+ *      the taps are equal: an all-252 tile gives exactly 1), one division by 252 -- all in float64, the coefficients being
+ *      differences of float64 coordinates -- and one rounding to float32.  (A float32 coefficient of a coordinate an integer -+ 1e-10
+ *      is 0 or 1; step 3 would then see a tile edge differently from scipy's float64 sum.);
+ *   3. view v takes part iff it is in bounds, s_v is not NaN and m_v > 0;
+ *   4. weighted average: sum (b_v m_v) s_v / sum (b_v m_v) over the views that take part, accumulated in view order in float32 with
+ *      the single-view state of the generic kernel (one view: s_v itself), 0 where the sum of weights is 0; max and simple average:
+ *      over the views that take part; 0 where none does;
+ *   5. nan_to_num, the halo trim and the truncating cast of mvs_fuse_chunk.
+ * Views are culled per brick of 4 x 4 x 64 (2D: 16 x 64) voxels in view order, so the float32 sums have one order whatever the
+ * chunking.  With every m_v == 1 a voxel goes through the float32 operations of the generic kernel in the same order: the result has
+ * the bits of mvs_fuse_chunk under option "force_generic".  uint8 / uint16 / float32, 2D and 3D, any number of views.  Counter
+ * "fuse_weighted_chunks" counts the chunks; the family counters of mvs_fuse_chunk stay untouched.  A host result is waited for; a
+ * device result is waited for only when host slabs or tiles were staged. */
+int mvs_fuse_chunk_weighted(int device, const mvs_view_t* views, const mvs_view_t* wviews, int32_t n_views, const mvs_fuse_opts_t* opts,
+                            void* out);
 
 /* Masked normalised cross-correlation of two overlap crops (registration.masked_correlation_registration): Padfield 2012, what
  * skimage.registration.phase_cross_correlation computes when it is given reference_mask / moving_mask.  The reference only ever calls

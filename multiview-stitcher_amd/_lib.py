@@ -46,6 +46,8 @@ MVS_STACK_MAX_QUANTILES = 4
 MVS_HIST_MAX_BINS = 4096
 MVS_MASK_MAX_DILATE = 32
 MVS_LABEL_MAX = 2048
+MVS_FEATHER_MAX_WIDTH = 32
+MVS_FEATHER_FULL_WEIGHT = 252
 MVS_MASKED_CORR_MAX_VOXELS = 1 << 28
 MVS_MASKED_CORR_OK, MVS_MASKED_CORR_NO_ELIGIBLE_SHIFT, MVS_MASKED_CORR_TOO_FEW_VALID, MVS_MASKED_CORR_CONSTANT_CROP = 0, 1, 2, 3
 ERR_UNSUPPORTED = -4            # MVS_ERR_UNSUPPORTED
@@ -207,6 +209,7 @@ SIGNATURES = {
     "mvs_copy_into": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64),
                                 C.POINTER(C.c_int64)]),
     "mvs_fuse_chunk": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(mvs_fuse_opts_t), C.c_void_p]),
+    "mvs_fuse_chunk_weighted": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.POINTER(mvs_view_t), C.c_int32, C.POINTER(mvs_fuse_opts_t), C.c_void_p]),
     "mvs_resample": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.POINTER(C.c_int64), C.c_int32, C.c_float, C.c_void_p, C.c_int32]),
     "mvs_blend_weights": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_int32]),
     "mvs_blend_weights_at": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p,
@@ -406,6 +409,7 @@ SIGNATURES = {
     "mvs_mask_threshold": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_double, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int64)]),
     "mvs_label_fuse": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_int32]),
     "mvs_label_contacts": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
+    "mvs_mask_feather": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32]),
     "mvs_masked_corr": (
         C.c_int,
         [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(mvs_masked_corr_opts_t),

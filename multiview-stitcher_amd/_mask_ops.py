@@ -111,6 +111,44 @@ def threshold_mask(tile, threshold, radius=0, device=0):
     return out, int(n_set.value)
 
 
+def check_feather_width(width, ndim):
+    """``width`` (one int or one per axis) as ``ndim`` ints in 1..MVS_FEATHER_MAX_WIDTH; the one number 0 means no feather, which
+    is width 1 on every axis (a step of one voxel is already the whole width)."""
+    if isinstance(width, (int, np.integer)) and not isinstance(width, bool):
+        width = [1 if int(width) == 0 else int(width)] * ndim
+    else:
+        if any(isinstance(w, bool) or not isinstance(w, (int, np.integer)) for w in width):
+            raise TypeError(f"a feather width is an integer number of voxels, not {list(width)}")
+        width = [int(w) for w in width]
+    if len(width) != ndim:
+        raise ValueError(f"expected one feather width or {ndim}, got {len(width)}")
+    if min(width) < 1 or max(width) > _lib.MVS_FEATHER_MAX_WIDTH:
+        raise ValueError(f"a feather width must be 1..{_lib.MVS_FEATHER_MAX_WIDTH} (or the one number 0: no feather), not {width}")
+    return width
+
+
+def feather(mask, width, device=0, out_on_device=False):
+    """The uint8 weight tile ``rint(252 (1 - cos(pi min(t, 1))) / 2)`` of a 2-D / 3-D uint8 mask, ``t`` the distance to the mask's
+    nearest zero voxel in units of ``width`` per axis (mvs_mask_feather).  ``mask``: numpy array or (possibly strided, x contiguous)
+    DeviceArray; the result is a numpy array, or a DeviceArray with ``out_on_device``."""
+    ndim = len(mask.shape)
+    if ndim not in (2, 3):
+        raise ValueError("masks are 2-D or 3-D")
+    width = check_feather_width(width, ndim)
+    if np.dtype(mask.dtype) != np.uint8:
+        raise TypeError(f"masks are uint8, not {mask.dtype}")
+    lib = _lib.init(device)
+    view, keep = tile_view(mask, np.eye(ndim), np.zeros(ndim), device)
+    shape = tuple(int(s) for s in mask.shape)
+    out = DeviceArray.empty(shape, np.uint8, device) if out_on_device else np.empty(shape, dtype=np.uint8)
+    ptr, mem = (out.ptr, _lib.MVS_MEM_DEVICE) if out_on_device else (out.ctypes.data, _lib.MVS_MEM_HOST)
+    _lib.check(lib.mvs_mask_feather(device, C.byref(view), ndim, _lib.i32x3(width, ndim, 1), C.c_void_p(ptr), mem), device, "mvs_mask_feather")
+    if out_on_device:
+        out.mark_written()
+    del keep
+    return out
+
+
 def fuse_labels(masks, matrices, offsets, out_shape, device=0, out_on_device=False):
     """The int32 label volume of shape ``out_shape``: per voxel the minimum over the views ``i`` that cover it at order 0 of
     ``masks[i] ? i + 1 : 0``, and 0 where none does (mvs_label_fuse).  ``masks``: uint8 arrays (numpy or DeviceArray);

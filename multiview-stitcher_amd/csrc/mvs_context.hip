@@ -236,6 +236,11 @@ static int set_option(MvsContext* c, const char* key, int64_t value) {
         c->psf_batch = value;
         return MVS_OK;
     }
+    if (!strcmp(key, "feather_slab_planes")) {
+        if (value < 0) return mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_set_option: feather_slab_planes is 0 (automatic) or a number of planes");
+        c->feather_slab_planes = value;
+        return MVS_OK;
+    }
     if (!strcmp(key, "ablate")) {
         c->ablate = (int)value;
         return MVS_OK;
@@ -269,6 +274,7 @@ static const MvsCounter kCounters[] = {
     {"fuse_region_chunks", nullptr, &MvsContext::fuse_region_chunks},
     {"fuse_column_chunks", nullptr, &MvsContext::fuse_column_chunks},
     {"fuse_generic_chunks", nullptr, &MvsContext::fuse_generic_chunks},
+    {"fuse_weighted_chunks", nullptr, &MvsContext::fuse_weighted_chunks},
 };
 
 extern "C" {

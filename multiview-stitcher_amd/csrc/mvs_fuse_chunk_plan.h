@@ -217,6 +217,24 @@ inline void fill_dev_view(const mvs_view_t& v, int ndim, const void* dev_data, D
     d->pad[0] = d->pad[1] = d->pad[2] = 0.f;
 }
 
+// The record of a weight tile that reads its data at dev_data (NULL: no weights), in the chunk frame: the tile is whole
+// (index_offset 0), so c = M (p + org) + off with the operation order of view_to_chunk_frame.
+inline void fill_weight_view(const mvs_view_t& v, const void* dev_data, const int64_t org[3], WeightView* d) {
+    memset(d, 0, sizeof(*d));
+    d->data = (const unsigned char*)dev_data;
+    if (!dev_data) return;
+    d->stride_z = v.stride[0];
+    d->stride_y = v.stride[1];
+    d->nz = (int)v.shape[0];
+    d->ny = (int)v.shape[1];
+    d->nx = (int)v.shape[2];
+    memcpy(d->m, v.matrix, sizeof(d->m));
+    memcpy(d->off, v.offset, sizeof(d->off));
+    if (!(org[0] | org[1] | org[2])) return;
+    const double o[3] = {(double)org[0], (double)org[1], (double)org[2]};
+    for (int k = 0; k < 3; ++k) d->off[k] = ((o[0] * d->m[3 * k] + o[1] * d->m[3 * k + 1]) + o[2] * d->m[3 * k + 2]) + d->off[k];
+}
+
 // A filled view as the chunk sees it: its translation-path constants in the index frame, then the chunk frame for the kernels that
 // evaluate the affine map, then -- when the view qualifies (returns true; not rotated / scaled views, nor, under weighted average, a
 // support table that is not the closed form) -- its translation-path record.

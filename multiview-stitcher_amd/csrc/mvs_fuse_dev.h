@@ -29,6 +29,16 @@ struct DevView {
     float pad[3];     // pad[0]: 1 = linear interpolation (set with tr_ok)
 };
 
+// Device record of a view's weight tile (mvs_fuse_chunk_weighted): uint8, the whole tile on a grid of its own.  data == NULL: the
+// view has no weights (1 everywhere).  m / off map a chunk index to a pixel of the tile (fill_weight_view, mvs_fuse_chunk_plan.h).
+struct WeightView {
+    const unsigned char* data;
+    long long stride_z, stride_y;   // bytes
+    int nz, ny, nx;
+    int pad;
+    double m[9];
+    double off[3];
+};
 
 // ---- the prologue the chunk entries share (mvs_fuse.hip) ----
 // what every entry requires of (views, opts, out); `what` = the entry's name, the prefix of the messages

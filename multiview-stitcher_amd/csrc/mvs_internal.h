@@ -102,6 +102,8 @@ struct MvsContext {
     // route() in mvs_fuse_chunk_plan.h): row kernels, region kernels, column kernel, generic kernel.  A chunk the column kernel gave up
     // on (more than 64 views on a column) and the generic kernel redid counts in both.
     long long fuse_rows_chunks = 0, fuse_region_chunks = 0, fuse_column_chunks = 0, fuse_generic_chunks = 0;
+    long long fuse_weighted_chunks = 0;   // chunks of mvs_fuse_chunk_weighted (mvs_fuse_weighted.hip: its own kernel, none of the families above)
+    long long feather_slab_planes = 0;    // option "feather_slab_planes": output planes per z slab of mvs_mask_feather (0: sized to its scratch budget); the result does not depend on it
     bool deconv_general = false;  // test switch "deconv_general": mvs_mv_deconv takes the general direct convolution even for separable kernels
     bool dct_general = false;     // test switch "dct_general": the DCT quality pass takes its general (global scratch) path for every block size
     long long psf_batch = 0;      // option "psf_batch": beads per launch of mvs_psf_extract (0: sized to a scratch budget); the result does not depend on it

@@ -164,6 +164,7 @@ def fuse_np(
     device=0,
     out=None,
     frame_origin=None,
+    view_weights=None,
     _record=None,
     _cb_check=True,
 ):
@@ -186,9 +187,21 @@ def fuse_np(
     turns that warning into an error: its guarantee would be lost).  Voxel-exact agreement across chunkings holds on the
     translation fast path (identity pixel matrices); the generic kernel folds ``M @ origin`` into its offsets in floating
     point, so rotated / scaled views agree across chunkings to rounding (~1e-9 px in the coordinates), not bit for bit.
+
+    ``view_weights`` (optional): one feathered weight tile per view (``masks.feather``), or None for a view without one -- a
+    uint8 sim, numpy array or ``DeviceArray`` of the view's spatial rank, always the WHOLE view's tile even where ``sims[i]`` is
+    a slab.  A sim brings its own origin and spacing, in the view's own physical frame (it may live on a coarser grid, as
+    ``masks.sample_masks(binning=...)`` returns it), and ``params[i]`` is applied to it whatever transforms it carries; a plain
+    array has the whole view's shape and takes its origin and spacing (``full_view_bbs[i]``).  The chunk is then fused by
+    ``mvs_fuse_chunk_weighted``: a view drops out where its weight is 0 and fades in with it (include/mvs_hip.h).  Built-in
+    fusion functions without a ``weights_func`` only; anything else is refused by name.
     """
     if backend not in ("hip", None):
         raise ValueError("multiview_stitcher_amd.fusion.fuse_np only implements backend='hip'")
+    if view_weights is not None:
+        _check_view_weights_call(fusion_func, weights_func, "fuse_np")
+        if len(view_weights) != len(sims):
+            raise ValueError(f"view_weights: one entry per view ({len(sims)}), got {len(view_weights)}")
     check_interpolation_order(interpolation_order, "interpolation_order")
     lib = _lib.init(device)
     sdims = si_utils.get_spatial_dims_from_sim(sims[0])
@@ -217,7 +230,67 @@ def fuse_np(
     frame = _index_frame(chunk, frame_origin, _record)
     views, ptrs, mems, keep = _view_records(chunk, frame)
     opts, dopts = _fuse_opts(chunk, _FUSION_CODES[fusion_func], weights_code, weights_func_kwargs, frame.index_origin, dct)
+    if view_weights is not None:
+        wviews, tiles_alive = _weight_records(chunk, frame, view_weights)      # noqa: F841  (alive until the launch has returned)
+        return _launch_chunk(lib, chunk, views, opts, dopts, out, output_on_backend, False, None, ptrs, mems, wviews=wviews)
     return _launch_chunk(lib, chunk, views, opts, dopts, out, output_on_backend, weights_code and _cb_check, _record, ptrs, mems)
+
+
+def _check_view_weights_call(fusion_func, weights_func, who):
+    """``view_weights`` go with the kernel modes without a ``weights_func``; every other combination is refused by name."""
+    if weights_func is not None:
+        raise NotImplementedError(f"{who}: view_weights cannot be combined with a weights_func "
+                                  f"({getattr(weights_func, '__name__', weights_func)!r}): the weighted chunk kernel has no content-based weights")
+    if fusion_func is multi_view_deconvolution:
+        raise NotImplementedError(f"{who}: view_weights cannot be combined with multi_view_deconvolution")
+    if fusion_func is multi_band_fusion:
+        raise NotImplementedError(f"{who}: view_weights cannot be combined with multi_band_fusion: its bands are blended by hard-seam masks")
+    if fusion_func not in _FUSION_CODES:
+        raise NotImplementedError(f"{who}: view_weights cannot be combined with the user callable {getattr(fusion_func, '__name__', fusion_func)!r}; "
+                                  "they go with weighted_average_fusion, max_fusion and simple_average_fusion")
+
+
+def _weight_tile(entry, view_bb, sdims, who, i):
+    """``(data, origin, spacing)`` of the weight tile of view ``i``: a sim's own coordinates, or the whole view's for a plain array
+    of its shape.  ``t`` / ``c`` dims (per-time-point weight tiles) are refused by name."""
+    if isinstance(entry, si_utils.SpatialImage) or msi_utils.is_msim(entry):
+        sim = msi_utils.get_sim_from_msim(entry, scale="scale0") if msi_utils.is_msim(entry) else entry
+        for d in sim.dims:
+            if d in ("t", "c"):
+                raise NotImplementedError(f"{who}: view_weights[{i}] has a {d!r} dim; per-time-point / per-channel weight tiles are not supported "
+                                          "(one spatial tile per view)")
+        if list(si_utils.get_spatial_dims_from_sim(sim)) != list(sdims):
+            raise ValueError(f"{who}: view_weights[{i}] has dims {list(sim.dims)}, the view {list(sdims)}")
+        data, origin, spacing = sim.data, si_utils.get_origin_from_sim(sim, asarray=True), si_utils.get_spacing_from_sim(sim, asarray=True)
+    else:
+        data = entry if is_device_array(entry) else np.asarray(entry)
+        if tuple(int(n) for n in data.shape) != tuple(int(view_bb["shape"][d]) for d in sdims):
+            raise ValueError(f"{who}: view_weights[{i}] has shape {tuple(data.shape)}, the view {tuple(int(view_bb['shape'][d]) for d in sdims)}; "
+                             "a tile on another grid comes as a sim with its own coordinates")
+        origin, spacing = _as_zyx(view_bb["origin"], sdims), _as_zyx(view_bb["spacing"], sdims)
+    if np.dtype(data.dtype) != np.uint8:
+        raise TypeError(f"{who}: view_weights[{i}] is {data.dtype}; weight tiles are uint8 (masks.feather)")
+    return data, origin, spacing
+
+
+def _weight_records(chunk, frame, view_weights):
+    """The ``mvs_view_t`` array of the chunk's weight tiles (``data`` NULL where a view has none) and what keeps their memory alive.
+    The pixel affines are derived as ``_view_records`` derives the images': for the frame's origin, the chunk entering as an
+    integer index shift; a tile is whole, so its own index offset is 0."""
+    sdims, n = chunk.sdims, len(chunk.sims)
+    wviews = (_lib.mvs_view_t * n)()
+    keep = []
+    out_spacing = _as_zyx(chunk.out_bb["spacing"], sdims)
+    for i, entry in enumerate(view_weights):
+        if entry is None:
+            continue
+        data, origin, spacing = _weight_tile(entry, chunk.full_view_bbs[i], sdims, "fuse_np", i)
+        p_inv = np.linalg.inv(np.asarray(chunk.params[i], dtype=np.float64))
+        matrices, offsets = get_pixel_affines(p_inv[None], origin[None], spacing[None], frame.out_origin, out_spacing)
+        ptr, s3, st3, mem, kept = view_data(data, chunk.device, np.dtype(np.uint8))
+        fill_view_geometry(wviews[i], ptr, _lib.MVS_U8, mem, s3, st3, matrices[0], offsets[0])
+        keep.append(kept)
+    return wviews, keep
 
 
 # One fuse_np call with its arguments normalised, as the three forms (kernel modes, deconvolution, callables) receive it:
@@ -337,14 +410,17 @@ def _fuse_opts(chunk, fusion_code, weights_code, weights_func_kwargs, index_orig
     return opts, weights.dct_opts(ndim, **dkw)
 
 
-def _launch_chunk(lib, chunk, views, opts, dopts, out, output_on_backend, cb_check, record, ptrs, mems):
-    """One ``mvs_fuse_chunk`` (``mvs_fuse_chunk_dct`` with ``dopts``) launch into ``out`` / a new device array / a new host
-    array.  ``cb_check``: a content-based result left on the device is checked for a mask-list overflow.  ``record``: where
-    fuse()'s geometry-keyed replay remembers a launch whose views are all resident on the device (``mems``), or None."""
+def _launch_chunk(lib, chunk, views, opts, dopts, out, output_on_backend, cb_check, record, ptrs, mems, wviews=None):
+    """One ``mvs_fuse_chunk`` (``mvs_fuse_chunk_dct`` with ``dopts``, ``mvs_fuse_chunk_weighted`` with ``wviews``) launch into
+    ``out`` / a new device array / a new host array.  ``cb_check``: a content-based result left on the device is checked for a
+    mask-list overflow.  ``record``: where fuse()'s geometry-keyed replay remembers a launch whose views are all resident on the
+    device (``mems``), or None."""
     device, n = chunk.device, len(views)
     res_shape = [int(chunk.out_bb["shape"][d]) - 2 * chunk.trim[d] for d in chunk.sdims]
 
     def launch(dst):
+        if wviews is not None:
+            return lib.mvs_fuse_chunk_weighted(device, views, wviews, n, C.byref(opts), dst), "mvs_fuse_chunk_weighted"
         if dopts is not None:
             return lib.mvs_fuse_chunk_dct(device, views, n, C.byref(opts), C.byref(dopts), dst), "mvs_fuse_chunk_dct"
         return lib.mvs_fuse_chunk(device, views, n, C.byref(opts), dst), "mvs_fuse_chunk"
@@ -706,13 +782,14 @@ def _merged_chunksize(chunksize, shape, sdims, itemsize, max_bytes=None):
     return {d: block(d) for d in sdims}
 
 
-def _launch_budget(sims, out_shape, sdims, itemsize, device, cap):
+def _launch_budget(sims, out_shape, sdims, itemsize, device, cap, view_weights=None):
     """Output bytes one launch block of fuse(merge_chunks=True) may take so that the launch fits the device: the block
     itself plus the view slabs that have to be STAGED for it (host- or Zarr-backed views, and views resident on another
     GPU, are copied into device scratch; views already on ``device`` cost nothing) must stay below 90 % of the free
     device memory (``mvs_mem_info``).  The staged share is estimated per output byte: twice the mosaic-average (overlap
-    zones hold every voxel two to eight times) plus one whole view.  Never above ``cap`` (MVS_MAX_LAUNCH_BYTES /
-    MVS_MAX_STREAM_BYTES)."""
+    zones hold every voxel two to eight times) plus one whole view.  ``view_weights``: the weight tiles of the call stay resident
+    for all its blocks, so those that still have to be uploaded come off the free memory first.  Never above ``cap``
+    (MVS_MAX_LAUNCH_BYTES / MVS_MAX_STREAM_BYTES)."""
     try:
         free, _ = _lib.mem_info(device)
     except (RuntimeError, OSError, AttributeError):
@@ -726,9 +803,51 @@ def _launch_budget(sims, out_shape, sdims, itemsize, device, cap):
         staged += nb
         largest = max(largest, nb)
     out_total = max(int(np.prod([int(out_shape[d]) for d in sdims])) * itemsize, 1)
-    avail = int(0.9 * free) - largest
+    avail = int(0.9 * free) - largest - _weight_upload_bytes(view_weights, device)
     per_out_byte = 1.0 + 2.0 * staged / out_total
     return int(max(min(cap, avail / per_out_byte), 1))
+
+
+def _weight_data(entry):
+    """The array of a ``view_weights`` entry (a sim's data, or the entry itself)."""
+    if msi_utils.is_msim(entry):
+        entry = msi_utils.get_sim_from_msim(entry, scale="scale0")
+    return entry.data if isinstance(entry, si_utils.SpatialImage) else entry
+
+
+def _weight_upload_bytes(view_weights, device):
+    """Bytes of the weight tiles that are not yet resident on ``device`` (uint8: one byte per voxel)."""
+    total = 0
+    for entry in view_weights or ():
+        data = None if entry is None else _weight_data(entry)
+        if data is not None and not (is_device_array(data) and (data.device & 0xff) == (int(device) & 0xff)):
+            total += int(np.prod(data.shape))
+    return total
+
+
+def _resident_weight(data, device):
+    """A weight tile as a ``DeviceArray``: itself, or uploaded to ``device`` (once per fuse() call, what ``device.to_device`` does
+    for a view)."""
+    return data if is_device_array(data) else DeviceArray.from_host(np.ascontiguousarray(data), device)
+
+
+def _upload_view_weights(call):
+    """``dev_weights``: per view its weight tile resident on the device -- a sim keeps its coordinates, a plain array stays an array
+    -- or None.  Every tile is checked against its view first (``_weight_tile``), so a wrong entry fails before any block is fused."""
+    call.dev_weights = None
+    if call.view_weights is None:
+        return
+    call.dev_weights = []
+    for i, entry in enumerate(call.view_weights):
+        if entry is None:
+            call.dev_weights.append(None)
+            continue
+        data, _, _ = _weight_tile(entry, call.views_bb[i], call.sdims, "fuse", i)
+        dev = _resident_weight(data, call.device)
+        if isinstance(entry, si_utils.SpatialImage) or msi_utils.is_msim(entry):
+            sim = msi_utils.get_sim_from_msim(entry, scale="scale0") if msi_utils.is_msim(entry) else entry
+            dev = si_utils.SpatialImage(dev, sim.dims, {d: np.asarray(sim.coords[d]) for d in sim.dims}, {"transforms": {}})
+        call.dev_weights.append(dev)
 
 
 class IndexFrameWarning(RuntimeWarning):
@@ -895,6 +1014,7 @@ class _FuseCall:
     names (``images`` with the ``sims`` alias resolved; ``batch_options`` / ``zarr_options`` as dicts once parsed), and:
 
     replay_key, record   key of the geometry-keyed replay, and the dict fuse_np records its launch in (None: not eligible)
+    dev_weights          per view its ``view_weights`` tile resident on the device, or None (None altogether without the keyword)
     views                ``list(images)``, plain SpatialImages
     dtype                dtype of the views and of the result
     sdims, nsdims        spatial / non-spatial dims of the views
@@ -917,7 +1037,7 @@ class _FuseCall:
 
     def __init__(self, **arguments):
         self.__dict__.update(arguments)
-        self.replay_key = self.record = self.zarr_out = self.result = self.dev_full = None
+        self.replay_key = self.record = self.zarr_out = self.result = self.dev_full = self.dev_weights = None
         self.ome_zarr, self.plans = False, {}
 
 
@@ -948,6 +1068,7 @@ def _fuse_once(
     chunk_filter=None,
     merge_chunks=True,
     frame_origin=None,
+    view_weights=None,
 ):
     """Fuse input views (fusion.fuse, _core.py:782-1501), eagerly, on the HIP backend.
 
@@ -971,6 +1092,12 @@ def _fuse_once(
     ``frame_origin``: origin of the index frame all chunks are fused in (see ``fuse_np``); default: the output stack's
     origin, so chunked, merged and unchunked runs of one stack agree voxel for voxel.  ``sharding.fuse_shard`` passes the
     origin of the WHOLE mosaic, so that every rank's sub-box equals the corresponding part of the single-GPU result.
+    ``view_weights``: one feathered uint8 weight tile per view (``masks.feather`` of a mask; None for a view without one), see
+    ``fuse_np``: "do not use this part of this view".  Every tile is uploaded once per call and every block gets the whole tiles
+    of its views.  With the built-in fusion functions only; a ``weights_func``, ``multi_view_deconvolution``,
+    ``multi_band_fusion``, user callables, multiscale images, weight tiles with ``t`` / ``c`` dims and plane-wise blocks are
+    refused by name.  Such calls are left out of the geometry-keyed replay and of the block pipeline of streamed calls (their
+    blocks are fused one after the other); ``fuse_to_host`` carries the keyword.
     """
     if images is None:
         if sims is None:
@@ -986,7 +1113,14 @@ def _fuse_once(
         output_shape=output_shape, output_stack_properties=output_stack_properties, output_chunksize=output_chunksize,
         overlap_in_pixels=overlap_in_pixels, trim_overlap=trim_overlap, interpolation_order=interpolation_order, blending_widths=blending_widths,
         output_zarr_url=output_zarr_url, zarr_options=zarr_options, batch_options=batch_options, backend=backend,
-        output_on_backend=output_on_backend, device=device, chunk_filter=chunk_filter, merge_chunks=merge_chunks, frame_origin=frame_origin)
+        output_on_backend=output_on_backend, device=device, chunk_filter=chunk_filter, merge_chunks=merge_chunks, frame_origin=frame_origin,
+        view_weights=view_weights)
+    if view_weights is not None:
+        _check_view_weights_call(fusion_func, weights_func, "fuse")
+        if len(view_weights) != len(images):
+            raise ValueError(f"view_weights: one entry per view ({len(images)}), got {len(view_weights)}")
+        if any(msi_utils.is_msim(im) for im in images):
+            raise NotImplementedError("fuse: view_weights cannot be combined with multiscale images; fuse one scale with the tiles of that scale")
     hit = _replay_lookup(call)
     if hit is not None:
         return _replay_fuse(hit, images, transform_key, device)
@@ -1005,6 +1139,7 @@ def _fuse_once(
     _check_batch_options(call)
     _open_zarr_output(call)
     _allocate_result(call)
+    _upload_view_weights(call)
     if call.batch_options:
         _fuse_batches(call)
     else:
@@ -1022,7 +1157,7 @@ def _replay_lookup(call):
     remembered derivation, or None after setting ``replay_key`` / ``record`` when this call may make one."""
     if not (_REPLAY[0] and call.output_on_backend and call.output_zarr_url is None and not call.batch_options and call.chunk_filter is None
             and call.merge_chunks and call.weights_func is None and not call.fusion_func_kwargs and not call.weights_func_kwargs
-            and not call.zarr_options and call.backend in ("hip", None)):
+            and not call.zarr_options and call.backend in ("hip", None) and call.view_weights is None):
         return None
     call.replay_key = _replay_key(
         call.images, call.transform_key, call.fusion_func, call.device, call.output_spacing, call.output_stack_mode, call.output_origin,
@@ -1100,7 +1235,7 @@ def _launch_blocks(call):
     if not call.streamed and _HOST_STREAM[0] and _STREAM_PIPELINE[0] and not call.output_on_backend and not single_blocks and kernel_fused \
             and all(isinstance(s.data, np.ndarray) or is_device_array(s.data) for s in call.views) \
             and sum(int(np.prod(s.data.shape)) * np.dtype(s.dtype).itemsize for s in call.views) >= _HOST_STREAM_MIN_BYTES \
-            and _lib.device_count() > 0:
+            and call.view_weights is None and _lib.device_count() > 0:
         # plain host arrays (or resident tiles) in, host array out -- what a user of the reference calls: launch blocks of <= 1 GiB through the block
         # pipeline (slabs copied into pinned staging buffers by the I/O pool, asynchronous transfers under the launch blocks, results
         # copied out by the pool) instead of ONE launch block whose views mvs_fuse_chunk uploads from pageable memory, fuses and
@@ -1112,7 +1247,8 @@ def _launch_blocks(call):
             and not ("z" in call.sdims and int(call.chunksize["z"]) == 1 and call.osp["shape"]["z"] > 1)):
         # streamed inputs / outputs pass through host memory block by block: a smaller budget per launch block
         budget = _launch_budget(call.views, call.osp["shape"], call.sdims, call.dtype.itemsize, call.device,
-                                MAX_STREAM_BYTES if call.streamed else MAX_LAUNCH_BYTES)
+                                MAX_STREAM_BYTES if call.streamed else MAX_LAUNCH_BYTES,
+                                **({} if call.view_weights is None else {"view_weights": call.view_weights}))
         call.block_size = _merged_chunksize(call.chunksize, call.osp["shape"], call.sdims, call.dtype.itemsize, budget)
 
 
@@ -1246,6 +1382,11 @@ def _chunk_call(call, ns_index, entry, device):
             kwargs["_record"] = call.record
             call.record["calls"] = call.record.get("calls", 0) + 1
             call.record["view_index"] = idxs
+    if call.dev_weights is not None:
+        if entry["fuse_planewise"]:
+            raise NotImplementedError("fuse: view_weights cannot be combined with plane-wise blocks (an output chunk of one z plane on the "
+                                      "views' z grid is fused as a 2D chunk); choose an output_chunksize of more than one plane")
+        kwargs["view_weights"] = [call.dev_weights[iv] for iv in idxs]
     return kwargs
 
 
@@ -1307,7 +1448,7 @@ def _fuse_field(call, ns_index):
     # tiles read from Zarr stores and / or a result that leaves the device block by block: read-ahead, asynchronous transfers
     # and write-behind around the launch blocks (streaming.BlockPipeline) -- the same fuse_np calls in the same order
     pipelined = (call.streamed and _STREAM_PIPELINE[0] and call.dev_full is None and _kernel_fused(call.fusion_func, call.weights_func)
-                 and _lib.device_count() > 0)
+                 and call.view_weights is None and _lib.device_count() > 0)
     pipe = streaming.BlockPipeline(fuse_np, call.device) if pipelined else None
     try:
         for entry in entries:

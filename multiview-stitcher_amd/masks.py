@@ -5,9 +5,10 @@ shift.  This module says where the sample is: one Otsu threshold for the whole a
 tile (``sample_masks``), the fusion of the label images ``mask_i * (i + 1)`` by their minimum at interpolation order 0
 (``fuse_labels``) and the list of the labels that touch (``contact_pairs``).  ``registration.get_pairs_from_sample_masks`` and
 ``mv_graph.get_connected_labels`` compose them under the reference's names (registration.py:3256-3292, mv_graph.py:895-931); the
-pair list goes into ``registration.register(..., pairs=)``.
+pair list goes into ``registration.register(..., pairs=)``.  The same masks can keep parts of a view out of the mosaic: ``feather``
+turns a mask into a feathered weight tile for ``fusion.fuse(..., view_weights=)``.
 
-All voxel work runs in HIP kernels (csrc/mvs_masks.hip; include/mvs_hip.h states their rules and limits); every result is an
+All voxel work runs in HIP kernels (csrc/mvs_masks.hip, csrc/mvs_mask_feather.hip; include/mvs_hip.h states their rules and limits); every result is an
 integer or a selection, so equal inputs give equal bits.  2-D and 3-D; tiles in host memory or resident on the device; sims with
 ``t`` or ``c`` dims are refused (select a time point and a channel first).
 """
@@ -16,7 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _detect_ops, _mask_ops, fusion, msi_utils, param_utils
+from . import _detect_ops, _lib, _mask_ops, fusion, msi_utils, param_utils
 from . import spatial_image_utils as si_utils
 from .device import is_device_array
 from .mv_graph import otsu_from_histogram  # noqa: F401  (public here: the arithmetic mv_graph.threshold_otsu shares)
@@ -117,6 +118,38 @@ def sample_masks(msims_or_sims, threshold=None, binning=None, sigma=None, dilate
         out.append(si_utils.SpatialImage(mask if keep_on_device else mask.get(), sim.dims, {d: np.asarray(sim.coords[d]) for d in sim.dims},
                                          {"transforms": dict(sim.attrs.get("transforms", {}))}))
     return out
+
+
+FULL_WEIGHT = _lib.MVS_FEATHER_FULL_WEIGHT      # 252: a quarter, a half and three quarters of it are integers
+
+
+def feather(mask, width, device=0, keep_on_device=False):
+    """A binary mask as a feathered weight tile for ``fusion.fuse(view_weights=)``: uint8, 0 on the mask's zero voxels, rising to
+    ``FULL_WEIGHT`` over ``width`` voxels, ``W = rint(252 (1 - cos(pi min(t, 1))) / 2)`` with ``t`` the distance to the nearest zero
+    voxel of the mask in units of the width per axis (mvs_mask_feather; tests/mask_feather_oracle.py is its scipy restatement).
+
+    ``mask``: a 2-D / 3-D uint8 sim (``sample_masks``), numpy array or contiguous ``DeviceArray``; nonzero means "use".  ``width``:
+    one integer, one per dim or a dict naming every dim, each 1..32 voxels of the mask; the one number 0 means no feather (the
+    tile is 0 / ``FULL_WEIGHT``).  Voxels outside the array do not count as zero -- the tile's border is the business of the
+    blending weights -- and a mask without a zero gives ``FULL_WEIGHT`` everywhere.  A sim comes back as a sim with the mask's
+    coords and transforms; the data is a numpy array, or stays a ``DeviceArray`` with ``keep_on_device``."""
+    is_sim = isinstance(mask, si_utils.SpatialImage) or msi_utils.is_msim(mask)
+    sim = _spatial_sim(mask, "feather") if is_sim else None
+    data = sim.data if is_sim else mask
+    if not is_device_array(data):
+        data = np.asarray(data)
+    if len(data.shape) not in (2, 3):
+        raise ValueError("feather: masks are 2-D or 3-D")
+    sdims = si_utils.get_spatial_dims_from_sim(sim) if is_sim else ["z", "y", "x"][3 - len(data.shape):]
+    widths = _mask_ops.check_feather_width(width if np.ndim(width) == 0 and not isinstance(width, dict) else _per_axis(width, sdims, "width"), len(sdims))
+    if np.dtype(data.dtype) != np.uint8:
+        raise TypeError(f"feather: masks are uint8, not {data.dtype}")
+    if is_device_array(data) and not data.is_contiguous():
+        raise TypeError("feather needs a contiguous device mask")
+    out = _mask_ops.feather(data, widths, device, out_on_device=keep_on_device)
+    if not is_sim:
+        return out
+    return si_utils.SpatialImage(out, sim.dims, {d: np.asarray(sim.coords[d]) for d in sim.dims}, {"transforms": dict(sim.attrs.get("transforms", {}))})
 
 
 def fuse_labels(mask_sims, transform_key, spacing=None, device=0, output_on_backend=False):
