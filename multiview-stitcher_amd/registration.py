@@ -18,7 +18,8 @@ import threading
 
 import numpy as np
 
-from . import _lib, _reg_ops, param_utils
+from . import _lib, _reg_ops, msi_utils, param_utils
+from . import spatial_image_utils as si_utils
 from .device import is_device_array
 
 logger = logging.getLogger(__name__)
@@ -1229,6 +1230,101 @@ def _points_for_registration(sim, points_key, sdims, affine, window=None):
     return points if points.size == 0 else transform_pts(points, affine)
 
 
+def _is_plain_phase_correlation(func, kwargs):
+    """The built-in phase correlation with at most ``upsample_factor`` set: what the lean and the batched pair paths cover."""
+    return func is phase_correlation_registration and set(kwargs or {}) <= {"upsample_factor"}
+
+
+def _binned_view(sim, binning, device, cache):
+    """``sim`` binned by ``binning`` (the image itself when no axis is binned); with a ``cache`` every tile is binned once."""
+    if max(binning.values()) <= 1:
+        return sim
+    if cache is None:
+        return _bin_sim(sim, binning, device)
+    key = (id(sim.data), tuple(sorted(binning.items())))
+    # (the cache slot keeps sim.data alive, so its id() cannot be recycled for another tile while the cache lives)
+    out = cache.get_or_compute(key, lambda: _bin_sim(sim, binning, device), keep=sim.data)
+    ticket = cache.ticket_of(key)
+    if ticket is not None:       # pre-binned on another lane, possibly still in flight: this lane's stream waits for it (no host wait)
+        _lib.check(_lib.init(device).mvs_event_wait(device, ticket), device, "mvs_event_wait")
+    return out
+
+
+def _lean_pair_applies(sim1, sim2, sdims, closed_form, pairwise_reg_func, pairwise_reg_func_kwargs):
+    """The gate of _lean_register_pair: the default crop rule, the plain phase correlation, views without non-spatial dims."""
+    return closed_form and _is_plain_phase_correlation(pairwise_reg_func, pairwise_reg_func_kwargs) and _lean_enabled[0] \
+        and all(list(s_.dims) == list(sdims) for s_ in (sim1, sim2))
+
+
+def _pair_crop_boxes(sims_b, sdims, transform_key, overlap_tolerance, closed_form):
+    """The overlap boxes the pair's crops are cut to, and whether they are the closed form's: ``(ov, closed_form)``.  A pair whose
+    closed-form crop is not as long as the reference's takes the reference's boxes (the generic path -- user registration functions,
+    scaled views: the same rule as the fast paths, see _reference_crop_differs)."""
+    ov = _get_overlap_bboxes(sims_b[0], sims_b[1], transform_key, None, overlap_tolerance, closed_form=closed_form)
+    if ov is None:
+        raise ValueError("views do not overlap")
+    if closed_form and _KNIFE_CHECK[0]:
+        ov_ref = _get_overlap_bboxes(sims_b[0], sims_b[1], transform_key, None, overlap_tolerance, closed_form=False)
+        if ov_ref is not None:
+            osp = np.maximum(*[np.array([si_utils.get_spacing_from_sim(s)[d] for d in sdims]) for s in sims_b])
+            n_cf = np.floor((ov["uppers"][0] - ov["lowers"][0]) / osp + 1)
+            n_ref = np.floor((ov_ref["uppers"][0] - ov_ref["lowers"][0]) / osp + 1)
+            if not np.array_equal(n_cf, n_ref):
+                return ov_ref, False
+    return ov, closed_form
+
+
+def _crop_windows(sims_b, sdims, ov, tol=1e-6):
+    """Per view the coordinate selection {dim: slice} of its crop: its overlap box widened by one sample and ``tol`` on either side."""
+    spacings = [si_utils.get_spacing_from_sim(s) for s in sims_b]
+    return [{d: slice(ov["lowers"][i][k] - tol - spacings[i][d], ov["uppers"][i][k] + tol + spacings[i][d]) for k, d in enumerate(sdims)}
+            for i in range(2)]
+
+
+def _register_pair_points(sims, sims_b, sdims, windows, transform_key, points_key, prefilter_markers, pairwise_reg_func,
+                          pairwise_reg_func_kwargs, device):
+    """The point branch (registration.py:1839-1924): the function works in the space of transform_key.  Returns (transform, quality)."""
+    affines = [param_utils.select_time(si_utils.get_affine_from_sim(s_, transform_key), 0) for s_ in sims]
+    kw = dict(pairwise_reg_func_kwargs)
+    for name, s_, a_, w_ in zip(("fixed", "moving"), sims, affines, windows):
+        kw[f"{name}_points"] = _points_for_registration(s_, points_key, sdims, a_, w_ if prefilter_markers else None)
+    takes_data = [_has_keyword(pairwise_reg_func, k) for k in ("fixed_data", "moving_data")]
+    if any(takes_data) and not all(takes_data):
+        raise ValueError("Image-aware pairwise registration functions must accept both 'fixed_data' and 'moving_data'.")
+    crops = [si_utils.sim_sel_coords(s_, w_) for s_, w_ in zip(sims_b, windows)] if all(takes_data) or any(
+        _has_keyword(pairwise_reg_func, f"{n}_{q}") for n in ("fixed", "moving") for q in ("origin", "spacing")) else None
+    for name, k in (("fixed", 0), ("moving", 1)):
+        if _has_keyword(pairwise_reg_func, f"{name}_origin"):
+            kw[f"{name}_origin"] = si_utils.get_origin_from_sim(crops[k])
+        if _has_keyword(pairwise_reg_func, f"{name}_spacing"):
+            kw[f"{name}_spacing"] = si_utils.get_spacing_from_sim(crops[k])
+    if _has_keyword(pairwise_reg_func, "initial_affine"):
+        kw["initial_affine"] = np.matmul(np.linalg.inv(affines[1]), affines[0])
+    res = dispatch_pairwise_reg_func(pairwise_reg_func, fixed_data=crops[0].data if all(takes_data) else None,
+                                     moving_data=crops[1].data if all(takes_data) else None, skip_constant_check=True, device=device, **kw)
+    return np.asarray(res["affine_matrix"], dtype=np.float64), res["quality"]
+
+
+def _register_pair_pixels(sims_b, windows, ov, transform_key, pairwise_reg_func, pairwise_reg_func_kwargs, device):
+    """The pixel branch: both crops resampled onto the fixed view's grid, the function's pixel affine made physical.  Returns
+    (transform, quality)."""
+    crops = [si_utils.sim_sel_coords(sim, windows[i]) for i, sim in enumerate(sims_b)]
+    fixed, moving = sims_to_intrinsic_coord_system(crops[0], crops[1], transform_key, (ov["lowers"], ov["uppers"]), device)
+    res = dispatch_pairwise_reg_func(pairwise_reg_func, fixed_data=fixed, moving_data=moving, device=device,
+                                     **pairwise_reg_func_kwargs)
+    if isinstance(res, list):   # Q2: the reference's `[zeros(ndim)]` return is unusable downstream; surface it
+        raise RuntimeError("phase correlation produced no admissible shift candidate (registration.py:479-480)")
+    affine = np.asarray(res["affine_matrix"], dtype=np.float64)
+    return get_affine_from_intrinsic_affine(affine, fixed, moving, transform_key, transform_key), res["quality"]
+
+
+def _pair_result(transform, quality, sim1, sim2, transform_key, overlap_tolerance, closed_form):
+    """The result of a registered pair: its physical transform, its quality (None: NaN) and the pair's overlap box in world space."""
+    ovp = _get_overlap_bboxes(sim1, sim2, transform_key, transform_key, overlap_tolerance, closed_form=closed_form)
+    return {"transform": transform, "quality": float(quality) if quality is not None else np.nan,
+            "bbox": np.array([ovp["lowers"][0], ovp["uppers"][0]])}
+
+
 def register_pair_of_msims(msim1, msim2, transform_key, registration_binning=None, overlap_tolerance=None,
                            pairwise_reg_func=phase_correlation_registration, pairwise_reg_func_kwargs=None, device=0,
                            _bin_cache=None, reg_res_level=None, overlap_bbox="closed_form", points_key="beads", prefilter_markers=False):
@@ -1242,9 +1338,6 @@ def register_pair_of_msims(msim1, msim2, transform_key, registration_binning=Non
     ``prefilter_markers`` first restricts every view's points to its overlap window (the closed interval of the crop
     selection: lower - 1e-6 - spacing ... upper + 1e-6 + spacing per dim, in the view's own frame).  Image crops are passed
     only to a function that also takes ``fixed_data`` / ``moving_data``."""
-    from . import msi_utils
-    from . import spatial_image_utils as si_utils
-
     pairwise_reg_func_kwargs = dict(pairwise_reg_func_kwargs or {})
     point_aware = _is_point_aware(pairwise_reg_func)
     sim1, sim2, registration_binning = _select_registration_level(msim1, msim2, registration_binning, reg_res_level)
@@ -1252,29 +1345,13 @@ def register_pair_of_msims(msim1, msim2, transform_key, registration_binning=Non
         if is_device_array(s_.data):
             s_.data.wait_ready(device)       # (tiles uploaded with device.to_device_async: this lane's stream waits for them)
     sdims = si_utils.get_spatial_dims_from_sim(sim1)
-    ndim = len(sdims)
     overlap_tolerance = _normalise_tolerance(overlap_tolerance, sdims)
-
-    def binned(sim):
-        if max(registration_binning.values()) <= 1:
-            return sim
-        key = (id(sim.data), tuple(sorted(registration_binning.items())))
-        if _bin_cache is None:
-            return _bin_sim(sim, registration_binning, device)
-        # (the cache slot keeps sim.data alive, so its id() cannot be recycled for another tile while the cache lives)
-        out = _bin_cache.get_or_compute(key, lambda: _bin_sim(sim, registration_binning, device), keep=sim.data)
-        ticket = _bin_cache.ticket_of(key)
-        if ticket is not None:       # pre-binned on another lane, possibly still in flight: this lane's stream waits for it (no host wait)
-            _lib.check(_lib.init(device).mvs_event_wait(device, ticket), device, "mvs_event_wait")
-        return out
-
     if overlap_bbox not in ("closed_form", "reference"):
         raise ValueError("overlap_bbox must be 'closed_form' or 'reference'")
     closed_form = overlap_bbox == "closed_form"
-    reg_sims_b = [binned(sim1), binned(sim2)]
-    if closed_form and pairwise_reg_func is phase_correlation_registration and set(pairwise_reg_func_kwargs) <= {"upsample_factor"} and _lean_enabled[0] \
-            and all(list(s_.dims) == list(sdims) for s_ in (sim1, sim2)):
-        geoms = [_geom_of(s_, transform_key, _bin_cache) for s_ in (reg_sims_b[0], reg_sims_b[1], sim1, sim2)]
+    sims_b = [_binned_view(s_, registration_binning, device, _bin_cache) for s_ in (sim1, sim2)]
+    if _lean_pair_applies(sim1, sim2, sdims, closed_form, pairwise_reg_func, pairwise_reg_func_kwargs):
+        geoms = [_geom_of(s_, transform_key, _bin_cache) for s_ in (sims_b[0], sims_b[1], sim1, sim2)]
         if all(g.t is not None for g in geoms):
             tol_l = [overlap_tolerance[d] for d in sdims]
             plan = _lean_pair_plan(geoms[0], geoms[1], tol_l) if _KNIFE_CHECK[0] else None
@@ -1282,58 +1359,14 @@ def register_pair_of_msims(msim1, msim2, transform_key, registration_binning=Non
                 return _lean_register_pair(geoms[0], geoms[1], geoms[2], geoms[3], sdims, tol_l,
                                            pairwise_reg_func_kwargs.get("upsample_factor"), transform_key, device)
             closed_form = False      # the reference registers a crop one sample shorter: this pair takes its sequence
-    ov = _get_overlap_bboxes(reg_sims_b[0], reg_sims_b[1], transform_key, None, overlap_tolerance, closed_form=closed_form)
-    if ov is None:
-        raise ValueError("views do not overlap")
-    spacings = [si_utils.get_spacing_from_sim(s) for s in reg_sims_b]
-    if closed_form and _KNIFE_CHECK[0]:
-        # (the generic path -- user registration functions, scaled views: the same rule as the fast paths, see _reference_crop_differs)
-        ov_ref = _get_overlap_bboxes(reg_sims_b[0], reg_sims_b[1], transform_key, None, overlap_tolerance, closed_form=False)
-        if ov_ref is not None:
-            osp = np.maximum(np.array([spacings[0][d] for d in sdims]), np.array([spacings[1][d] for d in sdims]))
-            n_cf = np.floor((ov["uppers"][0] - ov["lowers"][0]) / osp + 1)
-            n_ref = np.floor((ov_ref["uppers"][0] - ov_ref["lowers"][0]) / osp + 1)
-            if not np.array_equal(n_cf, n_ref):
-                ov, closed_form = ov_ref, False
-    lowers, uppers = ov["lowers"], ov["uppers"]
-    tol = 1e-6
-    windows = [{d: slice(lowers[i][k] - tol - spacings[i][d], uppers[i][k] + tol + spacings[i][d]) for k, d in enumerate(sdims)}
-               for i in range(2)]
+    ov, closed_form = _pair_crop_boxes(sims_b, sdims, transform_key, overlap_tolerance, closed_form)
+    windows = _crop_windows(sims_b, sdims, ov)
     if point_aware:
-        # registration.py:1839-1924: the function works in the space of transform_key
-        affines = [param_utils.select_time(si_utils.get_affine_from_sim(s_, transform_key), 0) for s_ in (sim1, sim2)]
-        kw = dict(pairwise_reg_func_kwargs)
-        for name, s_, a_, w_ in zip(("fixed", "moving"), (sim1, sim2), affines, windows):
-            kw[f"{name}_points"] = _points_for_registration(s_, points_key, sdims, a_, w_ if prefilter_markers else None)
-        takes_data = [_has_keyword(pairwise_reg_func, k) for k in ("fixed_data", "moving_data")]
-        if any(takes_data) and not all(takes_data):
-            raise ValueError("Image-aware pairwise registration functions must accept both 'fixed_data' and 'moving_data'.")
-        crops = [si_utils.sim_sel_coords(s_, w_) for s_, w_ in zip(reg_sims_b, windows)] if all(takes_data) or any(
-            _has_keyword(pairwise_reg_func, f"{n}_{q}") for n in ("fixed", "moving") for q in ("origin", "spacing")) else None
-        for name, k in (("fixed", 0), ("moving", 1)):
-            if _has_keyword(pairwise_reg_func, f"{name}_origin"):
-                kw[f"{name}_origin"] = si_utils.get_origin_from_sim(crops[k])
-            if _has_keyword(pairwise_reg_func, f"{name}_spacing"):
-                kw[f"{name}_spacing"] = si_utils.get_spacing_from_sim(crops[k])
-        if _has_keyword(pairwise_reg_func, "initial_affine"):
-            kw["initial_affine"] = np.matmul(np.linalg.inv(affines[1]), affines[0])
-        res = dispatch_pairwise_reg_func(pairwise_reg_func, fixed_data=crops[0].data if all(takes_data) else None,
-                                         moving_data=crops[1].data if all(takes_data) else None, skip_constant_check=True, device=device, **kw)
-        ovp = _get_overlap_bboxes(sim1, sim2, transform_key, transform_key, overlap_tolerance, closed_form=closed_form)
-        return {"transform": np.asarray(res["affine_matrix"], dtype=np.float64),
-                "quality": float(res["quality"]) if res["quality"] is not None else np.nan,
-                "bbox": np.array([ovp["lowers"][0], ovp["uppers"][0]])}
-    reg_sims_b = [si_utils.sim_sel_coords(sim, windows[i]) for i, sim in enumerate(reg_sims_b)]
-    fixed, moving = sims_to_intrinsic_coord_system(reg_sims_b[0], reg_sims_b[1], transform_key, (lowers, uppers), device)
-    res = dispatch_pairwise_reg_func(pairwise_reg_func, fixed_data=fixed, moving_data=moving, device=device,
-                                     **pairwise_reg_func_kwargs)
-    if isinstance(res, list):   # Q2: the reference's `[zeros(ndim)]` return is unusable downstream; surface it
-        raise RuntimeError("phase correlation produced no admissible shift candidate (registration.py:479-480)")
-    affine = np.asarray(res["affine_matrix"], dtype=np.float64)
-    affine_phys = get_affine_from_intrinsic_affine(affine, fixed, moving, transform_key, transform_key)
-    ovp = _get_overlap_bboxes(sim1, sim2, transform_key, transform_key, overlap_tolerance, closed_form=closed_form)
-    return {"transform": affine_phys, "quality": float(res["quality"]) if res["quality"] is not None else np.nan,
-            "bbox": np.array([ovp["lowers"][0], ovp["uppers"][0]])}
+        transform, quality = _register_pair_points((sim1, sim2), sims_b, sdims, windows, transform_key, points_key, prefilter_markers,
+                                                   pairwise_reg_func, pairwise_reg_func_kwargs, device)
+    else:
+        transform, quality = _register_pair_pixels(sims_b, windows, ov, transform_key, pairwise_reg_func, pairwise_reg_func_kwargs, device)
+    return _pair_result(transform, quality, sim1, sim2, transform_key, overlap_tolerance, closed_form)
 
 
 def _prebin_views(sims, registration_binning, device, cache):
@@ -1414,17 +1447,8 @@ def compute_pairwise_registrations(msims, edges, transform_key, registration_bin
     """registration.compute_pairwise_registrations (registration.py:2622-2714): either hand all edges to a
     user ``pairwise_executor(msims, edges, register_kwargs)`` or loop over them on one device.  ``points_key`` /
     ``prefilter_markers`` go to ``register_pair_of_msims`` (point-aware registration functions)."""
-    register_kwargs = dict(transform_key=transform_key, registration_binning=registration_binning,
-                           overlap_tolerance=overlap_tolerance, pairwise_reg_func=pairwise_reg_func,
-                           pairwise_reg_func_kwargs=pairwise_reg_func_kwargs)
-    if reg_res_level is not None:       # (absent by default: executors written for the round-1 keyword set keep working)
-        register_kwargs["reg_res_level"] = reg_res_level
-    if overlap_bbox != "closed_form":
-        register_kwargs["overlap_bbox"] = overlap_bbox
-    if points_key != "beads":
-        register_kwargs["points_key"] = points_key
-    if prefilter_markers:
-        register_kwargs["prefilter_markers"] = True
+    register_kwargs = _executor_kwargs(transform_key, registration_binning, overlap_tolerance, pairwise_reg_func, pairwise_reg_func_kwargs,
+                                       reg_res_level, overlap_bbox, points_key, prefilter_markers)
     if pairwise_executor is not None:
         results = pairwise_executor(msims, list(edges), register_kwargs)
         if len(results) != len(edges):
@@ -1432,17 +1456,13 @@ def compute_pairwise_registrations(msims, edges, transform_key, registration_bin
         return results
     cache = _bin_cache if _bin_cache is not None else _BinCache()
     edges = list(edges)
-    _host_threads_default = host_threads is None
-    if host_threads is None:
-        host_threads = 16
-    n_threads = max(1, min(int(host_threads), len(edges), 16))   # 16 = context lanes per GPU (MVS_MAX_LANES)
-    if _batch_enabled[0] and _lean_enabled[0] and overlap_bbox == "closed_form" and pairwise_reg_func is phase_correlation_registration and reg_res_level is None \
-            and set(pairwise_reg_func_kwargs or {}) <= {"upsample_factor"}:
+    n_threads = max(1, min(16 if host_threads is None else int(host_threads), len(edges), 16))   # 16 = context lanes per GPU (MVS_MAX_LANES)
+    if _batched_route_applies(pairwise_reg_func, pairwise_reg_func_kwargs, reg_res_level, overlap_bbox):
         # all pairs in two library calls (plans + registrations on native worker threads): no interpreter in the pair loop
         # (native workers spin inside the HIP runtime between launches: 6-12 of them reach the GPU's pair throughput, 16 exhaust a
         # 16-core CPU quota and are throttled to half speed -- profiles/round5_lanes.txt; the default is 8)
         batched = _register_pairs_batched(msims, edges, transform_key, registration_binning, overlap_tolerance, pairwise_reg_func_kwargs,
-                                          device, min(n_threads, _BATCH_LANES[0] if _host_threads_default else 12), cache)
+                                          device, min(n_threads, _BATCH_LANES[0] if host_threads is None else 12), cache)
         if batched is not None:
             return batched
     if n_threads == 1:
@@ -1451,16 +1471,41 @@ def compute_pairwise_registrations(msims, edges, transform_key, registration_bin
     # context lane (stream + scratch + lock) of the GPU, so the kernels of one pair fill the host round trips and
     # the Python glue of another.  Results keep the order of `edges`.
     pool, lanes, lane_lock = _pair_pool(n_threads)
-
-    def work(i, j):
-        # each worker thread owns one context lane of the GPU (`device | lane << 8`: own stream, scratch and lock)
-        tid = threading.get_ident()
-        with lane_lock:
-            lane = lanes.setdefault(tid, len(lanes))
-        return register_pair_of_msims(msims[i], msims[j], device=(device & 0xff) | (lane << 8), _bin_cache=cache, **register_kwargs)
-
-    futs = [pool.submit(work, i, j) for i, j in edges]
+    futs = [pool.submit(_register_pair_on_own_lane, lanes, lane_lock, msims[i], msims[j], device, cache, register_kwargs) for i, j in edges]
     return [f.result() for f in futs]
+
+
+def _executor_kwargs(transform_key, registration_binning, overlap_tolerance, pairwise_reg_func, pairwise_reg_func_kwargs, reg_res_level,
+                     overlap_bbox, points_key, prefilter_markers):
+    """The keywords of register_pair_of_msims that a pairwise executor (and the per-pair loop) is handed.  The last four are
+    absent unless set: executors written for the first five keep working."""
+    register_kwargs = dict(transform_key=transform_key, registration_binning=registration_binning,
+                           overlap_tolerance=overlap_tolerance, pairwise_reg_func=pairwise_reg_func,
+                           pairwise_reg_func_kwargs=pairwise_reg_func_kwargs)
+    if reg_res_level is not None:
+        register_kwargs["reg_res_level"] = reg_res_level
+    if overlap_bbox != "closed_form":
+        register_kwargs["overlap_bbox"] = overlap_bbox
+    if points_key != "beads":
+        register_kwargs["points_key"] = points_key
+    if prefilter_markers:
+        register_kwargs["prefilter_markers"] = True
+    return register_kwargs
+
+
+def _batched_route_applies(pairwise_reg_func, pairwise_reg_func_kwargs, reg_res_level, overlap_bbox):
+    """The gate of _register_pairs_batched (which may still decline: _batch_coverage looks at the views)."""
+    return _batch_enabled[0] and _lean_enabled[0] and overlap_bbox == "closed_form" \
+        and _is_plain_phase_correlation(pairwise_reg_func, pairwise_reg_func_kwargs) and reg_res_level is None
+
+
+def _register_pair_on_own_lane(lanes, lane_lock, msim1, msim2, device, cache, register_kwargs):
+    """A pair on a worker thread of _pair_pool: each thread owns one context lane of the GPU (`device | lane << 8`: own stream,
+    scratch and lock)."""
+    tid = threading.get_ident()
+    with lane_lock:
+        lane = lanes.setdefault(tid, len(lanes))
+    return register_pair_of_msims(msim1, msim2, device=(device & 0xff) | (lane << 8), _bin_cache=cache, **register_kwargs)
 
 
 _PAIR_POOLS = {}
@@ -1603,6 +1648,175 @@ def resolve_translations(n_views, edges, pair_results, reference_view=0, weights
     return params
 
 
+class _RegisterCall:
+    """The state of one ``register`` call; every step below reads and fills it.  The arguments of ``register()`` under their own
+    names, and:
+
+    sims              the views as plain SpatialImages (scale0 of a multiscale image), all channels
+    ci                index of the registration channel (0 when there is no choice to make)
+    sims_reg          ``sims`` reduced to that channel: what is registered (device-resident copies once the upload is staged)
+    nt                number of time points
+    multiscale        pyramid levels take part: an image has more than scale0 or ``reg_res_level`` is given (set before the upload
+                      gate, which asks for it; the levels themselves are only built when it holds, and then nothing is uploaded)
+    levels_reg        per view the registration channel of every pyramid level, scale0 first (only when ``multiscale``)
+    bin_cache         the binned tiles the pairs of the call share (None with an executor, time points or pyramid levels)
+    sps, affs         per view: the stack properties, the affine under ``transform_key`` at time point 0
+    edges             the pairs that get registered, sorted ``(i, j)`` with ``i < j``
+    params_t          per time point the resolved parameters, one matrix per view
+    all_results       per time point the pair results, in the order of ``edges``
+    resolution_info   per time point what the groupwise resolution reports (None for "linear")
+    """
+
+    def __init__(self, **arguments):
+        self.__dict__.update(arguments)
+        self.params_t, self.all_results, self.resolution_info = [], [], []
+
+
+def _channel_of(s, ci):
+    return s.isel({"c": ci}) if "c" in s.dims else s
+
+
+def _registration_channel(call):
+    """``sims``, ``ci``, ``sims_reg``, ``nt``: the plain images, the channel that is registered, and the time points."""
+    call.sims = sims = [msi_utils.get_sim_from_msim(m) if msi_utils.is_msim(m) else m for m in call.msims]
+    call.ci = 0
+    if "c" in sims[0].dims and sims[0].sizes["c"] > 1:
+        if call.reg_channel is None and call.reg_channel_index is None:
+            raise Exception("Please choose a registration channel.")
+        call.ci = call.reg_channel_index if call.reg_channel is None else int(np.nonzero(sims[0].coords["c"] == call.reg_channel)[0][0])
+    call.sims_reg = [_channel_of(s, call.ci) for s in sims]
+    call.nt = call.sims_reg[0].sizes.get("t", 1) if "t" in call.sims_reg[0].dims else 1
+
+
+def _pyramid_levels(call):
+    """``multiscale``, ``levels_reg``, ``bin_cache``.  Pyramid levels take part only when an image has more than scale0 or a level
+    is asked for (registration.py:1639-1717)."""
+    call.multiscale = call.reg_res_level is not None or any(msi_utils.is_msim(m) and len(m.keys()) > 1 for m in call.msims)
+    call.levels_reg = [[_channel_of(msi_utils.get_sim_from_msim(m, scale=k), call.ci) for k in msi_utils.get_sorted_scale_keys(m)]
+                       if msi_utils.is_msim(m) else [_channel_of(m, call.ci)] for m in call.msims] if call.multiscale else None
+    # (binned copies of the tiles are only made when the batched pair path cannot take its crops from the raw tiles: it then
+    # queues the binning of all views itself, in groups with stream tickets -- see _crop_sources / _prebin_views)
+    call.bin_cache = _BinCache() if call.pairwise_executor is None and call.nt == 1 and not call.multiscale else None
+
+
+def _wants_async_upload(call):
+    """Plain host numpy tiles (or windows of Zarr arrays) of 256 MiB and more -- what a user of the reference hands over -- for the
+    built-in pair path on scale0.  (Whatever ``pairwise_reg_func_kwargs`` holds: the upload serves the per-pair paths as well as
+    the batched one, so the function alone is asked about.)"""
+    sims_reg = call.sims_reg
+    return _HOST_UPLOAD_ASYNC[0] and call.pairwise_executor is None and not call.multiscale \
+        and _is_plain_phase_correlation(call.pairwise_reg_func, None) \
+        and all((isinstance(s.data, np.ndarray) or type(s.data).__name__ in ("ZarrArray", "ZarrView"))
+                and list(s.dims) == list(si_utils.get_spatial_dims_from_sim(s)) for s in sims_reg) \
+        and sum(int(np.prod(s.data.shape)) * np.dtype(s.data.dtype).itemsize for s in sims_reg) >= (256 << 20) and _lib.device_count() > 0 \
+        and all(np.dtype(s.data.dtype) in _lib.DTYPE_CODES for s in sims_reg)
+
+
+def _stage_host_tiles(call):
+    """The tiles staged through pinned buffers and uploaded on the copy stream while the overlap graph is built and the first pairs
+    are registered (north star: 1.7-2.0 s of one synchronous pageable upload per tile before; streaming.upload_host_sims_async).
+    The caller's images are only read; results are written to them by _write_back."""
+    from .streaming import upload_host_sims_async
+
+    call.sims_reg = upload_host_sims_async(call.sims_reg, call.device & 0xff)
+
+
+def _registration_edges(call):
+    """``sps``, ``affs``, ``edges``: the overlap graph of the views (mv_graph.py:35-180) and its pruning to the pairs that get
+    registered (registration.py:2467-2491)."""
+    from . import mv_graph
+
+    call.sps = [si_utils.get_stack_properties_from_sim(s) for s in call.sims_reg]
+    call.affs = [param_utils.select_time(si_utils.get_affine_from_sim(s, call.transform_key), 0) for s in call.sims_reg]
+    tol = call.overlap_tolerance
+    if tol is not None and not isinstance(tol, dict):
+        tol = {d: float(tol) for d in call.sps[0]["spacing"]}
+    views = [dict(sp, transform=a) for sp, a in zip(call.sps, call.affs)]
+    pruning = (call.pre_registration_pruning_method, call.pre_reg_pruning_method_kwargs)
+    # axis-aligned views + the default pruning: graph, overlap volumes and pruning in one library call (host code)
+    call.edges = mv_graph.registration_edges_native(views, tol, call.pairs, *pruning) if _native_graph[0] else None
+    if call.edges is None:
+        g_views = mv_graph.build_view_adjacency_graph(views, overlap_tolerance=tol, pairs=call.pairs)
+        g_views = mv_graph.prune_view_adjacency_graph(g_views, *pruning)
+        call.edges = [tuple(sorted(e)) for e in g_views.edges()]
+
+
+def _field_at(call, s, it):
+    """Image ``s`` at time point ``it``: a shallow copy with its OWN transforms dict, so that the caller's images are never modified
+    (t-stacked affines of an image without a t axis would otherwise collapse to one time point for good)."""
+    tr = s.attrs.get("transforms", {})
+    if (call.pairwise_executor is None or getattr(call.pairwise_executor, "reads_only", False)) and "t" not in s.dims \
+            and all(np.ndim(v) == 2 for v in tr.values()):
+        # nothing to select and the built-in pair path (also behind sharding.ShardedPairExecutor, which says so) only reads:
+        # the image itself; any other user executor gets copies
+        return s
+    f = s.isel({"t": it}) if "t" in s.dims else s.copy()
+    f.attrs["transforms"] = {k: param_utils.select_time(v, it) for k, v in tr.items()}
+    return f
+
+
+def _fields_at(call, it):
+    """What compute_pairwise_registrations gets for time point ``it``: per view its field, or the pyramid of its fields."""
+    if not call.multiscale:
+        return [_field_at(call, s, it) for s in call.sims_reg]
+    levels = [[_field_at(call, s, it) for s in lv] for lv in call.levels_reg]
+    return [msi_utils.MultiscaleSpatialImage(fl, fl[0].attrs["transforms"]) for fl in levels]
+
+
+def _kept_edges(results, do_filter, threshold):
+    """Indices of the edges that go into the resolution.  mv_graph.filter_edges removes edges with quality < threshold only: a NaN
+    quality (constant overlap -> identity transform) stays in the graph, as in the reference."""
+    return [k for k, r in enumerate(results) if not (do_filter and r["quality"] < threshold)]
+
+
+def _resolve_group(call, results, keep):
+    """Groupwise resolution of one time point (registration.py:2560-2580 -> param_resolution.groupwise_resolution): (params, info)."""
+    from . import param_resolution
+
+    n, method = len(call.sims), call.groupwise_resolution_method
+    edges, kept = [call.edges[k] for k in keep], [results[k] for k in keep]
+    if method == "linear":
+        return resolve_translations(n, edges, kept), None
+    gkw = dict(call.groupwise_resolution_kwargs or {})
+    if method == "global_optimization" and _native_resolution[0] and keep and \
+            set(gkw) <= {"reference_view", "transform", "max_iter", "rel_tol", "abs_tol"}:
+        # a connected translation mosaic whose sweeps end below abs_tol: the whole resolution in one library call (host code)
+        fast = param_resolution.resolve_translations_native(n, edges, kept, [[sp["spacing"][d] for d in sp["spacing"]] for sp in call.sps],
+                                                            **gkw)
+        if fast is not None:
+            return fast[0], fast[1]
+    g = param_resolution.RegGraph(range(n), {v: call.sps[v] for v in range(n)})
+    for (i, j), r in zip(edges, kept):
+        g.add_edge(i, j, r["transform"], quality=r["quality"], bbox=r["bbox"])
+    p_nodes, info = param_resolution.groupwise_resolution(g, method, **gkw)
+    return [p_nodes[v] for v in range(n)], info
+
+
+def _stack_params(call):
+    """Per view its parameters: stacked over the time points when the images have a t axis."""
+    stacked = "t" in call.sims_reg[0].dims
+    return [np.stack([p[v] for p in call.params_t], axis=0) if stacked else call.params_t[0][v] for v in range(len(call.sims))]
+
+
+def _write_back(call, params):
+    """``new_transform_key`` on the caller's images: ``params`` rebased on ``transform_key``."""
+    for m, p in zip(call.msims, params):
+        if msi_utils.is_msim(m):
+            msi_utils.set_affine_transform(m, p, transform_key=call.new_transform_key, base_transform_key=call.transform_key)
+        else:
+            si_utils.set_sim_affine(m, p, call.new_transform_key, base_transform_key=call.transform_key)
+
+
+def _register_report(call, params):
+    """What ``return_dict=True`` returns."""
+    c = call.bin_cache
+    stats = None if c is None else {"hits": c.hits, "misses": c.misses, "pairs_with_raw_crops": c.raw_crops,
+                                    "pairs_on_reference_sequence": c.reference_pairs}
+    qualities = {e: r["quality"] for e, r in zip(call.edges, call.all_results[0])}
+    return {"params": params, "bin_cache_stats": stats, "groupwise_resolution": {"info": call.resolution_info},
+            "pairwise_registration": {"edges": call.edges, "results": call.all_results, "metrics": {"qualities": qualities}}}
+
+
 def register(msims, transform_key=None, reg_channel_index=None, reg_channel=None, new_transform_key=None,
              registration_binning=None, overlap_tolerance=0.0, pairwise_reg_func=phase_correlation_registration,
              pairwise_reg_func_kwargs=None, groupwise_resolution_method="global_optimization",
@@ -1639,140 +1853,37 @@ def register(msims, transform_key=None, reg_channel_index=None, reg_channel=None
     ``param_resolution.groupwise_resolution`` (``groupwise_resolution_method``: "global_optimization" (default),
     "shortest_paths", a callable, or "linear" for the plain least-squares solve of ``resolve_translations``;
     ``groupwise_resolution_kwargs`` e.g. ``{"transform": "rigid", "reference_view": 0}``)."""
-    from . import msi_utils, mv_graph, param_resolution
-    from . import spatial_image_utils as si_utils
-
     if transform_key is None:
         raise ValueError("transform_key must be provided")
-    sims = [msi_utils.get_sim_from_msim(m) if msi_utils.is_msim(m) else m for m in msims]
-    if "c" in sims[0].dims and sims[0].sizes["c"] > 1:
-        if reg_channel is None and reg_channel_index is None:
-            raise Exception("Please choose a registration channel.")
-        ci = reg_channel_index if reg_channel is None else int(np.nonzero(sims[0].coords["c"] == reg_channel)[0][0])
-    else:
-        ci = 0
-
-    def channel_of(s):
-        return s.isel({"c": ci}) if "c" in s.dims else s
-
-    sims_reg = [channel_of(s) for s in sims]
-    if _HOST_UPLOAD_ASYNC[0] and pairwise_executor is None and not any(msi_utils.is_msim(m) and len(m.keys()) > 1 for m in msims) \
-            and reg_res_level is None and pairwise_reg_func is phase_correlation_registration \
-            and all((isinstance(s.data, np.ndarray) or type(s.data).__name__ in ("ZarrArray", "ZarrView"))
-                    and list(s.dims) == list(si_utils.get_spatial_dims_from_sim(s)) for s in sims_reg) \
-            and sum(int(np.prod(s.data.shape)) * np.dtype(s.data.dtype).itemsize for s in sims_reg) >= (256 << 20) and _lib.device_count() > 0 \
-            and all(np.dtype(s.data.dtype) in _lib.DTYPE_CODES for s in sims_reg):
-        # plain host numpy tiles (or windows of Zarr arrays) -- what a user of the reference hands over: staged through pinned buffers and uploaded on the copy stream
-        # while the overlap graph is built and the first pairs are registered (north star: 1.7-2.0 s of one synchronous pageable upload
-        # per tile before; streaming.upload_host_sims_async).  The caller's images are only read; results are written to them below.
-        from .streaming import upload_host_sims_async
-
-        sims_reg = upload_host_sims_async(sims_reg, device & 0xff)
-    nt = sims_reg[0].sizes.get("t", 1) if "t" in sims_reg[0].dims else 1
-    # pyramid levels take part only when an image has more than scale0 or a level is asked for (registration.py:1639-1717)
-    multiscale = reg_res_level is not None or any(msi_utils.is_msim(m) and len(m.keys()) > 1 for m in msims)
-    if multiscale:
-        levels_reg = [[channel_of(msi_utils.get_sim_from_msim(m, scale=k)) for k in msi_utils.get_sorted_scale_keys(m)]
-                      if msi_utils.is_msim(m) else [channel_of(m)] for m in msims]
-
-    # (binned copies of the tiles are only made when the batched pair path cannot take its crops from the raw tiles: it then
-    # queues the binning of all views itself, in groups with stream tickets -- see _crop_sources / _prebin_views)
-    bin_cache = _BinCache() if pairwise_executor is None and nt == 1 and not multiscale else None
-
-    # (1) graph
-    sps = [si_utils.get_stack_properties_from_sim(s) for s in sims_reg]
-    affs = [param_utils.select_time(si_utils.get_affine_from_sim(s, transform_key), 0) for s in sims_reg]
-    # overlap graph of the views (mv_graph.py:35-180) and its pruning to the pairs that get registered (registration.py:2467-2491)
-    tol = overlap_tolerance
-    if tol is not None and not isinstance(tol, dict):
-        tol = {d: float(tol) for d in sps[0]["spacing"]}
-    views = [dict(sp, transform=a) for sp, a in zip(sps, affs)]
-    # axis-aligned views + the default pruning: graph, overlap volumes and pruning in one library call (host code)
-    edges = mv_graph.registration_edges_native(views, tol, pairs, pre_registration_pruning_method, pre_reg_pruning_method_kwargs) \
-        if _native_graph[0] else None
-    if edges is None:
-        g_views = mv_graph.build_view_adjacency_graph(views, overlap_tolerance=tol, pairs=pairs)
-        g_views = mv_graph.prune_view_adjacency_graph(g_views, pre_registration_pruning_method, pre_reg_pruning_method_kwargs)
-        edges = [tuple(sorted(e)) for e in g_views.edges()]
-
-    # (2) pairwise registrations per time point
-    params_t, all_results, resolution_info = [], [], []
-    for it in range(nt):
-        # per-time-point fields are shallow copies with their OWN transforms dict: the caller's images are never modified
-        # (t-stacked affines of an image without a t axis would otherwise collapse to one time point for good)
-        def field_of(s):
-            tr = s.attrs.get("transforms", {})
-            if (pairwise_executor is None or getattr(pairwise_executor, "reads_only", False)) and "t" not in s.dims \
-                    and all(np.ndim(v) == 2 for v in tr.values()):
-                # nothing to select and the built-in pair path (also behind sharding.ShardedPairExecutor, which says so) only reads:
-                # the image itself; any other user executor gets copies
-                return s
-            f = s.isel({"t": it}) if "t" in s.dims else s.copy()
-            f.attrs["transforms"] = {k: param_utils.select_time(v, it) for k, v in s.attrs.get("transforms", {}).items()}
-            return f
-
-        if multiscale:
-            fields = []
-            for lv in levels_reg:
-                fl = [field_of(s) for s in lv]
-                fields.append(msi_utils.MultiscaleSpatialImage(fl, fl[0].attrs["transforms"]))
-        else:
-            fields = [field_of(s) for s in sims_reg]
-        results = compute_pairwise_registrations(
-            fields, edges, transform_key, registration_binning, overlap_tolerance, pairwise_reg_func,
-            pairwise_reg_func_kwargs, pairwise_executor, device,
-            host_threads=n_parallel_pairwise_regs,
-            _bin_cache=bin_cache, reg_res_level=reg_res_level, overlap_bbox=overlap_bbox,
-            points_key=points_key, prefilter_markers=prefilter_markers,
-        )
-        keep = list(range(len(edges)))
-        if post_registration_do_quality_filter:
-            # mv_graph.filter_edges removes edges with quality < threshold only: a NaN quality (constant overlap ->
-            # identity transform) stays in the graph, as in the reference
-            keep = [k for k in keep if not (results[k]["quality"] < post_registration_quality_threshold)]
-        # (3) groupwise resolution (registration.py:2560-2580 -> param_resolution.groupwise_resolution)
-        if groupwise_resolution_method == "linear":
-            params_t.append(resolve_translations(len(sims), [edges[k] for k in keep], [results[k] for k in keep]))
-            resolution_info.append(None)
-        else:
-            fast = None
-            gkw = dict(groupwise_resolution_kwargs or {})
-            if groupwise_resolution_method == "global_optimization" and _native_resolution[0] and keep and \
-                    set(gkw) <= {"reference_view", "transform", "max_iter", "rel_tol", "abs_tol"}:
-                # a connected translation mosaic whose sweeps end below abs_tol: the whole resolution in one library call (host code)
-                fast = param_resolution.resolve_translations_native(
-                    len(sims), [edges[k] for k in keep], [results[k] for k in keep],
-                    [[sp["spacing"][d] for d in sp["spacing"]] for sp in sps], **gkw)
-            if fast is not None:
-                params_t.append(fast[0])
-                resolution_info.append(fast[1])
-                all_results.append(results)
-                continue
-            g = param_resolution.RegGraph(range(len(sims)), {v: sps[v] for v in range(len(sims))})
-            for k in keep:
-                g.add_edge(edges[k][0], edges[k][1], results[k]["transform"], quality=results[k]["quality"], bbox=results[k]["bbox"])
-            p_nodes, info = param_resolution.groupwise_resolution(g, groupwise_resolution_method, **dict(groupwise_resolution_kwargs or {}))
-            params_t.append([p_nodes[v] for v in range(len(sims))])
-            resolution_info.append(info)
-        all_results.append(results)
-    params = [np.stack([params_t[it][v] for it in range(nt)], axis=0) if "t" in sims_reg[0].dims else params_t[0][v]
-              for v in range(len(sims))]
-
-    # (4) write back
+    call = _RegisterCall(
+        msims=msims, transform_key=transform_key, reg_channel_index=reg_channel_index, reg_channel=reg_channel,
+        new_transform_key=new_transform_key, registration_binning=registration_binning, overlap_tolerance=overlap_tolerance,
+        pairwise_reg_func=pairwise_reg_func, pairwise_reg_func_kwargs=pairwise_reg_func_kwargs,
+        groupwise_resolution_method=groupwise_resolution_method, groupwise_resolution_kwargs=groupwise_resolution_kwargs,
+        pre_registration_pruning_method=pre_registration_pruning_method, pre_reg_pruning_method_kwargs=pre_reg_pruning_method_kwargs,
+        post_registration_do_quality_filter=post_registration_do_quality_filter,
+        post_registration_quality_threshold=post_registration_quality_threshold, pairs=pairs,
+        n_parallel_pairwise_regs=n_parallel_pairwise_regs, pairwise_executor=pairwise_executor, return_dict=return_dict, device=device,
+        reg_res_level=reg_res_level, overlap_bbox=overlap_bbox, points_key=points_key, prefilter_markers=prefilter_markers)
+    _registration_channel(call)
+    _pyramid_levels(call)
+    if _wants_async_upload(call):
+        _stage_host_tiles(call)
+    _registration_edges(call)                                                                    # (1) graph
+    for it in range(call.nt):
+        results = compute_pairwise_registrations(                                                # (2) pairwise registrations
+            _fields_at(call, it), call.edges, transform_key, registration_binning, overlap_tolerance, pairwise_reg_func,
+            pairwise_reg_func_kwargs, pairwise_executor, device, host_threads=n_parallel_pairwise_regs, _bin_cache=call.bin_cache,
+            reg_res_level=reg_res_level, overlap_bbox=overlap_bbox, points_key=points_key, prefilter_markers=prefilter_markers)
+        keep = _kept_edges(results, post_registration_do_quality_filter, post_registration_quality_threshold)
+        params_it, info = _resolve_group(call, results, keep)                                   # (3) groupwise resolution
+        call.params_t.append(params_it)
+        call.resolution_info.append(info)
+        call.all_results.append(results)
+    params = _stack_params(call)
     if new_transform_key is not None:
-        for m, p in zip(msims, params):
-            if msi_utils.is_msim(m):
-                msi_utils.set_affine_transform(m, p, transform_key=new_transform_key, base_transform_key=transform_key)
-            else:
-                si_utils.set_sim_affine(m, p, new_transform_key, base_transform_key=transform_key)
-    if return_dict:
-        return {"params": params, "bin_cache_stats": None if bin_cache is None else {"hits": bin_cache.hits, "misses": bin_cache.misses,
-                                                                                        "pairs_with_raw_crops": bin_cache.raw_crops,
-                                                                                        "pairs_on_reference_sequence": bin_cache.reference_pairs},
-                "groupwise_resolution": {"info": resolution_info},
-                "pairwise_registration": {"edges": edges, "results": all_results,
-                                          "metrics": {"qualities": {e: r["quality"] for e, r in zip(edges, all_results[0])}}}}
-    return params
+        _write_back(call, params)                                                                # (4) write back
+    return _register_report(call, params) if return_dict else params
 
 
 def get_pairs_from_sample_masks(mask_sims, transform_key="affine_manual", fused_mask_spacing=None, device=0):
