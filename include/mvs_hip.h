@@ -981,6 +981,71 @@ int mvs_label_fuse(int device, const mvs_view_t* views, int32_t n_views, int32_t
 int mvs_label_contacts(int device, const int32_t* labels, int32_t ndim, const int64_t shape[3], int32_t n_labels, int32_t connectivity,
                        uint64_t* counts_out);
 
+/* Stitching per-tile segmentations (labels.py): one int32 label tile per view, with ids that mean nothing outside their tile, becomes
+ * one label image.  The voxel count of every label (mvs_label_counts) and the co-occurrence table of the labels of every pair of
+ * overlapping tiles (mvs_label_pair_overlaps) go to the host, which matches labels across tiles and numbers the objects
+ * (labels.match_labels, float64); mvs_label_tiles_fuse then paints every view's labels through its look-up table.
+ * LABEL TILES are int32 BY CONTRACT: mvs_view_t.dtype is not read (enum mvs_dtype has no code for them and the image entry points
+ * keep refusing them).  Host tiles are C-contiguous and staged for the duration of the call; device tiles have stride[2] == 1 and
+ * may be strided windows; data is aligned to 4 bytes; 2D: shape[0] == 1.  A negative label is background (0).
+ * COORDINATES are float64 without contraction in the operation order of the sampler, c_k = ((M_k0 p_z + M_k1 p_y) + M_k2 p_x) + o_k.
+ * A tile is IN BOUNDS at p when 0 <= c_k <= n_k - 1 on every axis, and its voxel is q = floor(c + 0.5): the rule of mvs_resample /
+ * mvs_label_fuse at order 0.
+ * Integer atomics only: equal inputs give equal results (the triples of a table: after sorting).  All three wait for their result
+ * and run on the context lane of `device`.
+ *
+ * mvs_label_counts: counts_out (host, `capacity` uint64) receives n[l] = the number of voxels of `tile` with max(label, 0) == l, for
+ * l = 0 .. capacity - 1; only data / mem / shape / stride of the tile are read.  *max_label_out: the largest max(label, 0) of the
+ * tile.  A label >= capacity is not counted and is no error: the caller looks at *max_label_out and calls again with capacity =
+ * max + 1.  1 <= capacity <= MVS_LABEL_COUNT_MAX_CAPACITY (below: MVS_ERR_INVALID_ARG, above: MVS_ERR_UNSUPPORTED).
+ * A wave takes 64 consecutive voxels of a row at a time -- where they are whole and 16-byte aligned, as sixteen 16-byte loads handed
+ * out by shuffles -- and a contiguous range of such chunks in all.  Equal labels of consecutive lanes are combined by one shuffle
+ * and one ballot and the first lane of the run adds its length with one global uint64 integer atomic (the scheme of
+ * mvs_label_contacts); a chunk of ONE label is carried in registers into the next chunks while the label stays, so background and
+ * the inside of large objects cost one atomic per wave. */
+#define MVS_LABEL_COUNT_MAX_CAPACITY 2147483648LL
+int mvs_label_counts(int device, const mvs_view_t* tile, int32_t ndim, int64_t capacity, uint64_t* counts_out, int64_t* max_label_out);
+
+/* mvs_label_pair_overlaps: the co-occurrence table of ONE directed pair of label tiles (a, b).  b->matrix / b->offset map a pixel
+ * index of a to a pixel coordinate of b (transformation.get_pixel_affine with a's grid as the output grid); of a only data / mem /
+ * shape / stride are read.  For every voxel p of the box [box_lo, box_lo + box_n) of a (inside a, not empty, else
+ * MVS_ERR_INVALID_ARG; the caller passes a box that bounds b's footprint, and every voxel of it is still tested) at which b is in
+ * bounds, with la = max(A[p], 0) and lb = max(B[q], 0): when la | lb is not 0 the entry (la, lb) of the table counts one.  Rows with
+ * one zero label are part of the table: they carry the marginals.
+ * OUT: *n_unique_out = the number of entries of the table; la_out / lb_out (host, int32) and n_out (host, uint64), `capacity` each,
+ * receive min(n_unique, capacity) triples (la, lb, count) in NO DEFINED ORDER: the caller sorts.  Returns MVS_OK when the triples
+ * are the whole table and MVS_LABEL_INCOMPLETE (positive: not an error, mvs_last_error is not set) when n_unique > capacity; the
+ * caller calls again with a capacity >= n_unique.  1 <= capacity <= MVS_LABEL_PAIR_MAX_CAPACITY.
+ * THE TABLE is open addressing in device scratch of the call: the 64-bit key la << 32 | lb, the power of two >= 2 * capacity (at
+ * least 1024) slots of a uint64 key and a uint64 count, the first slot from the splitmix64 finaliser of the key, linear probing.
+ * An insertion is a lock-free compare-and-swap EMPTY -> key on the slot's key followed by an integer add on its count.  PROBING IS
+ * BOUNDED by the number of slots: with the table exhausted -- more entries than slots -- the voxel is dropped and a flag raised; the
+ * call then also returns MVS_LABEL_INCOMPLETE, *n_unique_out is the number of slots (a lower bound of the table's size, above
+ * capacity) and the counts of the triples are not to be used.  No lane waits for another one: no locks, no spinning on a flag.
+ * A wave takes 64 consecutive voxels of a row of the box at a time; equal pairs of consecutive lanes are combined before they touch
+ * the table, and a chunk of one pair is carried in registers as in mvs_label_counts.  A second small launch compacts the occupied
+ * slots, one integer atomic per wave. */
+#define MVS_LABEL_PAIR_MAX_CAPACITY 134217728LL
+#define MVS_LABEL_INCOMPLETE 1
+int mvs_label_pair_overlaps(int device, const mvs_view_t* a, const mvs_view_t* b, int32_t ndim, const int64_t box_lo[3],
+                            const int64_t box_n[3], int64_t capacity, int32_t* la_out, int32_t* lb_out, uint64_t* n_out,
+                            int64_t* n_unique_out);
+
+/* mvs_label_tiles_fuse: the label image of n_views >= 1 label tiles on one output grid.  views[i].matrix / offset map an index of
+ * the FRAME -- the whole output grid -- to a pixel of view i, as for mvs_label_fuse; the output is the box of out_shape (z, y, x;
+ * 2D: out_shape[0] == 1) voxels whose first voxel has the frame index index_origin (NULL: zeros).  The indices are shifted as
+ * integers, as the index frame of mvs_fuse_opts_t does, so a box equals the crop of the whole grid's result bit for bit.
+ * luts (NULL: every view the identity): per view a pointer into DEVICE memory to lut_len[i] >= 1 int32 entries, or NULL for the
+ * identity.  out: int32, C-contiguous, in out_mem.
+ * Per output voxel p, among the views in bounds, the winner w is the one with the largest d_v = min over the axes with n_k > 1 of
+ * min(c_k, (n_k - 1) - c_k) -- the interior-most view decides -- and ties go to the lowest view index.  out(p) = lut_w[L_w(q)], and 0
+ * when that label is negative or >= lut_len[w] (the identity has no upper limit) or no view is in bounds.  The winner's background
+ * wins too: seams are hard.
+ * Bricks of 4 x 4 x 64 (2D: 16 x 64) voxels; a workgroup culls the views against its brick, 64 at a time, as mvs_label_fuse does:
+ * any number of views. */
+int mvs_label_tiles_fuse(int device, const mvs_view_t* views, int32_t n_views, int32_t ndim, const int32_t* const* luts,
+                         const int64_t* lut_len, const int64_t out_shape[3], const int64_t index_origin[3], int32_t* out, int32_t out_mem);
+
 /* Masks as fusion weights (masks.feather, fuse(view_weights=)): a binary mask becomes a feathered uint8 weight tile, and the
  * weighted chunk entry takes one such tile per view next to the image.
  *

@@ -10,8 +10,8 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # ``multiview_stitcher_amd.metrics`` / ``.intensity`` / ``.nonrigid`` / ``.masks`` without an explicit submodule import (loaded at first use: they bind the HIP library)
-    if name in ("metrics", "intensity", "nonrigid", "masks"):
+    # ``multiview_stitcher_amd.metrics`` / ``.intensity`` / ``.nonrigid`` / ``.masks`` / ``.labels`` without an explicit submodule import (loaded at first use: they bind the HIP library)
+    if name in ("metrics", "intensity", "nonrigid", "masks", "labels"):
         import importlib
 
         return importlib.import_module(__name__ + "." + name)

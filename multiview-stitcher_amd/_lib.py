@@ -46,6 +46,9 @@ MVS_STACK_MAX_QUANTILES = 4
 MVS_HIST_MAX_BINS = 4096
 MVS_MASK_MAX_DILATE = 32
 MVS_LABEL_MAX = 2048
+MVS_LABEL_COUNT_MAX_CAPACITY = 1 << 31
+MVS_LABEL_PAIR_MAX_CAPACITY = 1 << 27
+MVS_LABEL_INCOMPLETE = 1        # mvs_label_pair_overlaps: more entries than `capacity` (not an error)
 MVS_FEATHER_MAX_WIDTH = 32
 MVS_FEATHER_FULL_WEIGHT = 252
 MVS_MASKED_CORR_MAX_VOXELS = 1 << 28
@@ -409,6 +412,17 @@ SIGNATURES = {
     "mvs_mask_threshold": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_double, C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int64)]),
     "mvs_label_fuse": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_void_p, C.c_int32]),
     "mvs_label_contacts": (C.c_int, [C.c_int, C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]),
+    "mvs_label_counts": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
+    "mvs_label_pair_overlaps": (
+        C.c_int,
+        [C.c_int, C.POINTER(mvs_view_t), C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64,
+         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int64)],
+    ),
+    "mvs_label_tiles_fuse": (
+        C.c_int,
+        [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+         C.POINTER(C.c_int64), C.c_void_p, C.c_int32],
+    ),
     "mvs_mask_feather": (C.c_int, [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32]),
     "mvs_masked_corr": (
         C.c_int,
