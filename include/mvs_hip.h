@@ -1046,6 +1046,32 @@ int mvs_label_pair_overlaps(int device, const mvs_view_t* a, const mvs_view_t* b
 int mvs_label_tiles_fuse(int device, const mvs_view_t* views, int32_t n_views, int32_t ndim, const int32_t* const* luts,
                          const int64_t* lut_len, const int64_t out_shape[3], const int64_t index_origin[3], int32_t* out, int32_t out_mem);
 
+/* mvs_label_components: the connected components of one thresholded tile, numbered as scipy.ndimage.label numbers them -- the step
+ * between a mask (mvs_mask_threshold) and the label tiles the entries above stitch.  `tile` is an IMAGE tile: UNLIKE the other label
+ * entries its dtype is read (uint8, uint16 or float32; else MVS_ERR_UNSUPPORTED).  Host tiles are C-contiguous and staged for the
+ * duration of the call; device tiles have stride[2] == 1 and may be strided windows; 2D: shape[0] == 1; only data / dtype / mem /
+ * shape / stride are read.  At most 2^31 - 1 voxels (above: MVS_ERR_UNSUPPORTED).
+ * FOREGROUND is (float)v > threshold: a voxel equal to the threshold and a NaN are background; a uint8 mask is labelled with
+ * threshold = 0.  NEIGHBOURHOOD: connectivity 1 .. ndim (else MVS_ERR_INVALID_ARG) is that of scipy.ndimage.
+ * generate_binary_structure(ndim, connectivity) -- the offsets in {-1, 0, 1}^ndim with at most `connectivity` non-zero components,
+ * whose half has the 2 / 4 (2D) and 3 / 9 / 13 (3D) offsets of mvs_label_contacts.
+ * OUT: labels_out, int32, C-contiguous, of the tile's shape, in out_mem: 0 at background; the components with at least min_voxels
+ * voxels carry the ids 1 .. n in ascending raster order of their first voxel (the numbering of scipy.ndimage.label), smaller ones
+ * are 0; min_voxels <= 1 keeps everything.  *n_labels_out = n.
+ * Launches: rows (a wave takes 64 consecutive voxels of a row at a time, 16-byte loads where they are whole and aligned, and writes
+ * per voxel the index of the first voxel of its run of foreground along x, carried across chunks), merge (per offset with a y or z
+ * component the first lane of every run of touching voxels joins the two runs by a lock-free union: find both roots, atomic minimum
+ * of the smaller into the larger one's parent, go on from the returned value when that one was no root any more), flatten (every
+ * voxel to its root; with min_voxels > 1 also the voxels per root, runs combined before the atomic as in mvs_label_counts), the
+ * numbering of the roots by an exclusive scan in raster order as three launches (counts per workgroup, one workgroup over the
+ * counts, ranks at the roots; no workgroup waits for another one), relabel.  A parent index is never above its voxel's own and is
+ * only ever lowered, so every chase ends and the root of a component is its first voxel in raster order whatever the order of
+ * execution.  Integer atomics only: equal inputs give equal bits.  The call waits for its result and runs on the context lane of
+ * `device`.  Scratch of the context's allocator: 4 bytes per voxel, 4 more with min_voxels > 1, 8 KiB for the scan; a host tile and
+ * a host result are staged next to it. */
+int mvs_label_components(int device, const mvs_view_t* tile, int32_t ndim, float threshold, int32_t connectivity, int64_t min_voxels,
+                         int32_t* labels_out, int32_t out_mem, int64_t* n_labels_out);
+
 /* Masks as fusion weights (masks.feather, fuse(view_weights=)): a binary mask becomes a feathered uint8 weight tile, and the
  * weighted chunk entry takes one such tile per view next to the image.
  *

@@ -1,6 +1,7 @@
-"""Thin array-level wrappers of the label-stitching entry points of libmvs_hip.so (mvs_label_counts, mvs_label_pair_overlaps,
-mvs_label_tiles_fuse).  Label tiles are int32 by contract: a host tile of another integer dtype is converted here, a device tile
-must be int32 already.  The capacities the entries ask for are the callers' business nowhere else: the retries live here."""
+"""Thin array-level wrappers of the label entry points of libmvs_hip.so (mvs_label_counts, mvs_label_pair_overlaps,
+mvs_label_tiles_fuse, mvs_label_components).  Label tiles are int32 by contract: a host tile of another integer dtype is converted
+here, a device tile must be int32 already.  The capacities the entries ask for are the callers' business nowhere else: the retries
+live here.  ``label_components`` alone takes IMAGE tiles (uint8 / uint16 / float32) and makes label tiles of them."""
 
 from __future__ import annotations
 
@@ -191,3 +192,54 @@ def fuse_label_tiles(tiles, matrices, offsets, luts, out_shape, index_origin=Non
         out.mark_written()
     del keep
     return out
+
+
+def as_image_tile(data, who="tile"):
+    """An image tile as mvs_label_components takes it: a 2-D / 3-D uint8 / uint16 / float32 array, in host memory (made
+    C-contiguous) or a DeviceArray with contiguous rows (strided windows are fine).  Nothing is converted: another dtype raises
+    TypeError."""
+    if not is_device_array(data):
+        data = np.asarray(data)
+    if np.dtype(data.dtype) not in _lib.DTYPE_CODES:
+        raise TypeError(f"{who}: image tiles are uint8, uint16 or float32, not {data.dtype}")
+    if len(data.shape) not in (2, 3):
+        raise ValueError(f"{who}: tiles are 2-D or 3-D")
+    if is_device_array(data):
+        if data.strides[-1] != 1 and data.shape[-1] > 1:
+            raise TypeError(f"{who}: device tiles need contiguous rows (stride 1 along x)")
+        return data
+    return np.ascontiguousarray(data)
+
+
+def label_components(tile, threshold, connectivity=1, min_voxels=1, device=0, out_on_device=False):
+    """``(labels, n)``: the connected components of the voxels of ``tile`` with ``(float32)v > (float32)threshold``, numbered as
+    ``scipy.ndimage.label`` numbers them under ``generate_binary_structure(ndim, connectivity)`` (mvs_label_components).  ``tile``: a
+    uint8 / uint16 / float32 host array or DeviceArray; ``threshold=None`` requires uint8 and means 0 (a mask).  Components with
+    fewer than ``min_voxels`` voxels become 0 and the others keep the ids ``1 .. n`` in order.  ``labels`` is int32 of the tile's
+    shape: a resident DeviceArray when ``out_on_device`` or when the tile is resident, else a numpy array."""
+    tile = as_image_tile(tile)
+    ndim = len(tile.shape)
+    if threshold is None:
+        if np.dtype(tile.dtype) != np.uint8:
+            raise TypeError(f"threshold=None labels a uint8 mask; a {tile.dtype} tile needs a threshold")
+        threshold = 0.0
+    threshold = float(np.float32(threshold))      # what the kernel compares with
+    connectivity, min_voxels = int(connectivity), int(min_voxels)
+    if not 1 <= connectivity <= ndim:
+        raise ValueError(f"connectivity must be 1 .. {ndim}, not {connectivity}")
+    if int(np.prod(tile.shape, dtype=np.int64)) < 1:
+        raise ValueError("an empty tile")
+    lib = _lib.init(device)
+    view, keep = label_view(tile, None, None, device)
+    view.dtype = _lib.DTYPE_CODES[np.dtype(tile.dtype)]
+    on_device = out_on_device or is_device_array(tile)
+    shape = tuple(int(s) for s in tile.shape)
+    out = DeviceArray.empty(shape, np.int32, device) if on_device else np.empty(shape, dtype=np.int32)
+    ptr, mem = (out.ptr, _lib.MVS_MEM_DEVICE) if on_device else (out.ctypes.data, _lib.MVS_MEM_HOST)
+    n = C.c_int64()
+    _lib.check(lib.mvs_label_components(device, C.byref(view), ndim, threshold, connectivity, max(min(min_voxels, 2**63 - 1), 0), C.c_void_p(ptr), mem,
+                                        C.byref(n)), device, "mvs_label_components")
+    if on_device:
+        out.mark_written()
+    del keep
+    return out, int(n.value)

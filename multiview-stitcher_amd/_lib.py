@@ -418,6 +418,10 @@ SIGNATURES = {
         [C.c_int, C.POINTER(mvs_view_t), C.POINTER(mvs_view_t), C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64,
          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_int64)],
     ),
+    "mvs_label_components": (
+        C.c_int,
+        [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_float, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)],
+    ),
     "mvs_label_tiles_fuse": (
         C.c_int,
         [C.c_int, C.POINTER(mvs_view_t), C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64),

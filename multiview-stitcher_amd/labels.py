@@ -11,6 +11,16 @@ integer, so equal inputs give equal bits.  2-D and 3-D; label tiles of any integ
 above 2^31 - 1 raises ValueError) or resident int32 ``DeviceArray``s (strided windows with contiguous rows are fine); negative
 labels are background.  Label sims with ``t`` or ``c`` dims raise NotImplementedError: one spatial label tile per view.
 ``masks.fuse_labels`` is a different tool: it paints the *view indices* of binary masks for pair selection.
+
+Where the segmentations come from a threshold, they are made here too: ``label_components`` turns every thresholded tile into
+objects (connected components with the numbering of ``scipy.ndimage.label``; csrc/mvs_components.hip), so a mosaic goes from
+images to one label image in three calls without a voxel leaving the device::
+
+    threshold = masks.otsu_threshold(msims, device=0)
+    tiles = labels.label_components(msims, threshold, connectivity=1, min_voxels=20, keep_on_device=True)
+    objects = labels.stitch_labels(tiles, "registered", output_on_backend=True)
+
+Objects that span tiles are ``stitch_labels``' business: ``label_components`` knows one tile at a time.
 """
 
 from __future__ import annotations
@@ -22,27 +32,58 @@ from . import spatial_image_utils as si_utils
 from .transformation import get_pixel_affine, get_pixel_affines
 
 
-def _label_sims(label_sims, who):
+def _label_sims(label_sims, who, param="label_sims", kind="label"):
     """The full-resolution spatial label images of the views; ``t`` / ``c`` dims are refused under the parameter's name."""
     sims = []
     for i, image in enumerate(label_sims):
         sim = msi_utils.get_sim_from_msim(image, scale="scale0") if msi_utils.is_msim(image) else image
         for d in sim.dims:
             if d in ("t", "c"):
-                raise NotImplementedError(f"{who}: label_sims[{i}] has a {d!r} dim; per-time-point / per-channel label tiles are not supported "
-                                          "(one spatial label tile per view)")
+                raise NotImplementedError(f"{who}: {param}[{i}] has a {d!r} dim; per-time-point / per-channel {kind} tiles are not supported "
+                                          f"(one spatial {kind} tile per view)")
         if len(si_utils.get_spatial_dims_from_sim(sim)) not in (2, 3):
-            raise ValueError(f"{who}: label sims are 2-D or 3-D")
+            raise ValueError(f"{who}: {kind} sims are 2-D or 3-D")
         sims.append(sim)
     if not sims:
         raise ValueError(f"{who}: no tiles")
     if len({tuple(si_utils.get_spatial_dims_from_sim(s)) for s in sims}) != 1:
-        raise ValueError(f"{who}: the label sims differ in their spatial dims")
+        raise ValueError(f"{who}: the {kind} sims differ in their spatial dims")
     return sims
 
 
 def _affine(sim, transform_key):
     return np.asarray(param_utils.select_time(si_utils.get_affine_from_sim(sim, transform_key), 0), dtype=np.float64)
+
+
+def label_components(images, threshold=None, connectivity=1, min_voxels=1, device=0, keep_on_device=False):
+    """Per view the int32 label sim of the connected components of its thresholded tile (mvs_label_components): the objects of one
+    tile, ready for ``stitch_labels(..., transform_key)``.
+
+    ``images``: sims or msims (scale0) -- uint8 / uint16 / float32 image tiles, or the uint8 masks of ``masks.sample_masks`` on the
+    tiles' own grids; host data or ``DeviceArray``s.  A voxel is foreground when ``(float32)v > (float32)threshold``: ``threshold``
+    is ROUNDED TO FLOAT32 before the comparison, a voxel equal to it and a NaN are background.  ``threshold``: one number, or one per
+    view; ``None`` requires uint8 tiles and means 0.  ``connectivity`` ``1 .. ndim`` is the neighbourhood of
+    ``scipy.ndimage.generate_binary_structure(ndim, connectivity)``; components with fewer than ``min_voxels`` voxels become
+    background.  Ids are ``1 .. n`` in ascending raster order of each component's first voxel -- the numbering of
+    ``scipy.ndimage.label`` -- and ``attrs["n_labels"]`` holds ``n``.
+
+    Every result has its source's dims, origin, spacing and every transform the source carries.  Its data is a numpy array, or a
+    resident ``DeviceArray`` with ``keep_on_device`` or when the source's is one.  Sims with ``t`` / ``c`` dims raise
+    NotImplementedError."""
+    sims = _label_sims(images, "label_components", param="images", kind="image")
+    thresholds = [threshold] * len(sims) if threshold is None or np.ndim(threshold) == 0 else list(threshold)
+    if len(thresholds) != len(sims):
+        raise ValueError(f"label_components: threshold: one number, or one per view ({len(sims)}), not {len(thresholds)}")
+    out = []
+    for sim, thr in zip(sims, thresholds):
+        data, n = _label_ops.label_components(sim.data, thr, connectivity=connectivity, min_voxels=min_voxels, device=device, out_on_device=keep_on_device)
+        sdims = si_utils.get_spatial_dims_from_sim(sim)
+        res = si_utils.to_spatial_image(data, dims=sdims, scale=si_utils.get_spacing_from_sim(sim), translation=si_utils.get_origin_from_sim(sim))
+        for key in si_utils.get_tranform_keys_from_sim(sim):
+            si_utils.set_sim_affine(res, si_utils.get_affine_from_sim(sim, key), key)
+        res.attrs["n_labels"] = n
+        out.append(res)
+    return out
 
 
 def label_counts(label_sims, device=0):
