@@ -63,8 +63,7 @@ __global__ __launch_bounds__(WAVES * 64) void mi_hist_kernel(MiParams P, unsigne
         for (int cpy = 0; cpy < P.copies; ++cpy) s += lds[cpy * P.stride + i];
         if (s != 0ull) atomicAdd(&hist[i], s);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off);
+    n = mvs_fold::wave_fold(mvs_fold::Sums<int>{{n}}).v[0];
     if (lane == 0 && n != 0) atomicAdd(&hist[nb2], (unsigned long long)n);
 }
 
@@ -137,38 +136,15 @@ __global__ __launch_bounds__(WAVES * 64) void mi_grad_kernel(MiParams P, const f
 // minimum, maximum and count of the finite values, per block: part[b] = (min, max), cnt[b]
 __global__ __launch_bounds__(256) void finite_range_kernel(const float* __restrict__ a, long long n, float2* __restrict__ part,
                                                            long long* __restrict__ cnt) {
-    float mn = INFINITY, mx = -INFINITY;
-    long long nv = 0;
+    mvs_fold::Range<long long> r = {INFINITY, -INFINITY, 0};
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const float v = a[i];
-        if (mvs_ar::finite_f(v)) {
-            mn = fminf(mn, v);
-            mx = fmaxf(mx, v);
-            ++nv;
-        }
+        if (mvs_ar::finite_f(v)) r.merge({v, v, 1});
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = fminf(mn, __shfl_down(mn, off));
-        mx = fmaxf(mx, __shfl_down(mx, off));
-        nv += __shfl_down(nv, off);
-    }
-    __shared__ float smn[4], smx[4];
-    __shared__ long long snv[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        smn[wave] = mn;
-        smx[wave] = mx;
-        snv[wave] = nv;
-    }
-    __syncthreads();
+    r = mvs_fold::block_fold<4>(r);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) {
-            mn = fminf(mn, smn[w]);
-            mx = fmaxf(mx, smx[w]);
-            nv += snv[w];
-        }
-        part[blockIdx.x] = make_float2(mn, mx);
-        cnt[blockIdx.x] = nv;
+        part[blockIdx.x] = make_float2(r.mn, r.mx);
+        cnt[blockIdx.x] = r.n;
     }
 }
 

@@ -10,6 +10,7 @@
 // (the per-sample arithmetic is mvs_affine_reg_dev.h).
 #pragma once
 #include "mvs_affine_reg_dev.h"
+#include "mvs_fold_dev.h"
 
 namespace mvs_aw {
 
@@ -99,11 +100,7 @@ __host__ __device__ __forceinline__ void walk_run(const Walk& P, long long z, in
 }
 
 // ---- device only: the reductions that follow a walk ----
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
+__device__ __forceinline__ double wave_sum(double v) { return mvs_fold::wave_fold(mvs_fold::Sums<double>{{v}}).v[0]; }
 
 // out[j] = sum over the blocks of partials[b][j]: thread t takes b = t, t + 256, ... in order, then a fixed tree in LDS
 static __global__ __launch_bounds__(256) void rows_sum_kernel(const double* __restrict__ partials, long long nblocks, int nout,

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "mvs_internal.h"
+#include "mvs_fold_dev.h"
 #include "mvs_fuse_dev.h"
 #include "mvs_dct_dev.h"
 
@@ -75,33 +76,24 @@ __device__ __forceinline__ void block_of(const DctGeom& g, int b, bool pad, Blk&
     k.vol = k.e[0] * k.e[1] * k.e[2];
 }
 
+// sum / minimum over the workgroup, in every thread.  The folds start from 0.0 / INFINITY: partials that are all -0.0 give +0.0,
+// partials that are all NaN give INFINITY.
 template <int NT>
-__device__ __forceinline__ double wg_sum(double v, double* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = 0.0;
-    for (int i = 0; i < NT / 64; ++i) r += red[i];
-    return r;
-}
+__device__ __forceinline__ double wg_sum(double v) { return 0.0 + mvs_fold::block_fold_all<NT / 64>(mvs_fold::Sums<double>{{v}}).v[0]; }
 
+struct MinPartial {
+    float v;
+    __device__ __forceinline__ void merge(const MinPartial& o) { v = fminf(v, o.v); }
+    template <typename S> __device__ __forceinline__ MinPartial shuffled(S sh, int off) const { return {sh(v, off)}; }
+};
 template <int NT>
-__device__ __forceinline__ float wg_min(float v, float* red) {
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_down(v, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = INFINITY;
-    for (int i = 0; i < NT / 64; ++i) r = fminf(r, red[i]);
-    return r;
-}
+__device__ __forceinline__ float wg_min(float v) { return fminf(INFINITY, mvs_fold::block_fold_all<NT / 64>(MinPartial{v}).v); }
 
 __device__ __forceinline__ int buf_index(const Blk& k, int z, int y, int x) { return (z * k.e[1] + y) * k.px + x; }
 
 // copy the block of one view into `buf`, count its valid voxels and fill the NaN ones; false: quality 0 (too few valid)
 template <int NT>
-__device__ bool load_block(const float* __restrict__ src, const DctGeom& g, const Blk& k, float* buf, double* redd, float* redf) {
+__device__ bool load_block(const float* __restrict__ src, const DctGeom& g, const Blk& k, float* buf) {
     double cnt = 0.0;
     float mn = INFINITY;
     for (int i = threadIdx.x; i < k.vol; i += NT) {
@@ -113,10 +105,10 @@ __device__ bool load_block(const float* __restrict__ src, const DctGeom& g, cons
             mn = fminf(mn, v);
         }
     }
-    const double n_valid = wg_sum<NT>(cnt, redd);
+    const double n_valid = wg_sum<NT>(cnt);
     if (n_valid < 0.2 * (double)k.vol) return false;
     if (n_valid < (double)k.vol) {
-        const float m = wg_min<NT>(mn, redf);
+        const float m = wg_min<NT>(mn);
         const float fill = (double)m > 0.0001 ? m : 0.f;
         for (int i = threadIdx.x; i < k.vol; i += NT) {
             const int x = i % k.e[2], r = i / k.e[2], y = r % k.e[1], z = r / k.e[1];
@@ -146,7 +138,7 @@ __device__ __forceinline__ void line_of(const Blk& k, int axis, int l, int& base
 
 // entropy quality of the transformed block (weights.py:223-251)
 template <int NT>
-__device__ float block_quality(const float* buf, const DctGeom& g, const Blk& k, double* redd) {
+__device__ float block_quality(const float* buf, const DctGeom& g, const Blk& k) {
     if (g.otf) {
         double ss = 0.0;
         for (int i = threadIdx.x; i < k.vol; i += NT) {
@@ -154,7 +146,7 @@ __device__ float block_quality(const float* buf, const DctGeom& g, const Blk& k,
             const double d = buf[buf_index(k, z, y, x)];
             ss += d * d;
         }
-        const float l2 = (float)sqrt(wg_sum<NT>(ss, redd));
+        const float l2 = (float)sqrt(wg_sum<NT>(ss));
         if (l2 == 0.f) return 0.f;
         double h = 0.0;
         for (int i = threadIdx.x; i < k.vol; i += NT) {
@@ -163,7 +155,7 @@ __device__ float block_quality(const float* buf, const DctGeom& g, const Blk& k,
             const float p = fabsf(buf[buf_index(k, z, y, x)]) / l2;
             if (p > 0.f) h -= (double)(p * log2f(p));
         }
-        h = wg_sum<NT>(h, redd);
+        h = wg_sum<NT>(h);
         float q = (float)((2.0 / (g.r_o * g.r_o)) * h);
         const float sg = q > 0.f ? 1.f : (q < 0.f ? -1.f : q);      // np.sign (0 -> 0, NaN -> NaN)
         q = powf(q, (float)g.exponent);
@@ -174,7 +166,7 @@ __device__ float block_quality(const float* buf, const DctGeom& g, const Blk& k,
         const int x = i % k.e[2], r = i / k.e[2], y = r % k.e[1], z = r / k.e[1];
         sa += fabs((double)buf[buf_index(k, z, y, x)]);
     }
-    const float dsl1 = (float)(wg_sum<NT>(sa, redd) / (double)k.vol);
+    const float dsl1 = (float)(wg_sum<NT>(sa) / (double)k.vol);
     if (dsl1 == 0.f) return 0.f;
     double h = 0.0;
     for (int i = threadIdx.x; i < k.vol; i += NT) {
@@ -182,7 +174,7 @@ __device__ float block_quality(const float* buf, const DctGeom& g, const Blk& k,
         const float p = fabsf(buf[buf_index(k, z, y, x)]) / dsl1;
         if (p > 0.f) h -= (double)(p * log2f(p));
     }
-    h = wg_sum<NT>(h, redd);
+    h = wg_sum<NT>(h);
     return (float)pow((double)dsl1 * h, g.exponent);      // a negative base with a fractional exponent: NaN
 }
 
@@ -191,13 +183,11 @@ __global__ __launch_bounds__(kLdsThreads) void dct_quality_lds(const float* __re
                                                                float* __restrict__ Q) {
     extern __shared__ float4 lds4[];
     float* buf = reinterpret_cast<float*>(lds4);
-    __shared__ double redd[kLdsThreads / 64];
-    __shared__ float redf[kLdsThreads / 64];
     const int v = blockIdx.x / g.nblocks, b = blockIdx.x % g.nblocks;
     Blk k;
     block_of(g, b, true, k);
     const long long S = (long long)g.S[0] * g.S[1] * g.S[2];
-    if (!load_block<kLdsThreads>(stack + v * S, g, k, buf, redd, redf)) {
+    if (!load_block<kLdsThreads>(stack + v * S, g, k, buf)) {
         if (threadIdx.x == 0) Q[blockIdx.x] = 0.f;
         return;
     }
@@ -222,7 +212,7 @@ __global__ __launch_bounds__(kLdsThreads) void dct_quality_lds(const float* __re
         }
         __syncthreads();
     }
-    const float q = block_quality<kLdsThreads>(buf, g, k, redd);
+    const float q = block_quality<kLdsThreads>(buf, g, k);
     if (threadIdx.x == 0) Q[blockIdx.x] = q;
 }
 
@@ -230,8 +220,6 @@ __global__ __launch_bounds__(kLdsThreads) void dct_quality_lds(const float* __re
 // the work items w, w + gridDim.x, ...
 __global__ __launch_bounds__(kGenThreads) void dct_quality_general(const float* __restrict__ stack, DctGeom g, float* __restrict__ scratch,
                                                                    long long slot_floats, int n_items, float* __restrict__ Q) {
-    __shared__ double redd[kGenThreads / 64];
-    __shared__ float redf[kGenThreads / 64];
     const long long bvol = (long long)g.ds[0] * g.ds[1] * g.ds[2];
     float* bufA = scratch + (long long)blockIdx.x * slot_floats;
     float* bufB = bufA + bvol;
@@ -242,7 +230,7 @@ __global__ __launch_bounds__(kGenThreads) void dct_quality_general(const float* 
         Blk k;
         block_of(g, b, false, k);
         __syncthreads();                 // (the previous item's readers of the slot are done)
-        if (!load_block<kGenThreads>(stack + v * S, g, k, bufA, redd, redf)) {
+        if (!load_block<kGenThreads>(stack + v * S, g, k, bufA)) {
             if (threadIdx.x == 0) Q[item] = 0.f;
             continue;
         }
@@ -273,7 +261,7 @@ __global__ __launch_bounds__(kGenThreads) void dct_quality_general(const float* 
             in = out;
             out = t;
         }
-        const float q = block_quality<kGenThreads>(in, g, k, redd);
+        const float q = block_quality<kGenThreads>(in, g, k);
         if (threadIdx.x == 0) Q[item] = q;
     }
 }

@@ -20,6 +20,7 @@
 // first axis which only looks at voxels above the threshold, compares, applies the neighbourhood-minimum rule at the remaining
 // candidates and appends them to the list with one integer atomicAdd per wave.
 #include "mvs_detect_dev.h"
+#include "mvs_fold_dev.h"
 #include "mvs_internal.h"
 
 #include <algorithm>
@@ -128,11 +129,8 @@ __global__ __launch_bounds__(256) void log_s_kernel(const float* __restrict__ P,
         }
     }
     if (LAST) {
-        __shared__ float wmax[4];
-        for (int off = 32; off > 0; off >>= 1) best = fmaxf(best, __shfl_down(best, off));
-        if (lane == 0) wmax[wave] = best;
-        __syncthreads();
-        if (threadIdx.x == 0) partial[blockIdx.x] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+        best = mvs_fold::block_fold<4>(mvs_fold::Max<float>{best}).v;
+        if (threadIdx.x == 0) partial[blockIdx.x] = best;
     }
 }
 

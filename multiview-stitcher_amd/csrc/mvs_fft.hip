@@ -176,32 +176,6 @@ __global__ __launch_bounds__(256) void fft_lines_kernel(FftArgs A) {
 // stages of the Stockham kernel with their LDS round trip, barrier and index arithmetic each (28.5 -> 13.7 us for a
 // 256-point pass over a 256 x 256 x 51 crop).  The inverse is the forward transform of the input with real and imaginary parts
 // swapped, swapped back on output.
-// workgroup reduction (256 threads) and the write of the workgroup's partials
-__device__ __forceinline__ void peak_flush(Peak2 p, const FftArgs& A) {
-    __shared__ float sv[2][4];
-    __shared__ long long si[2][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ob = __shfl_down(p.v[k], off);
-            const long long oi = __shfl_down(p.i[k], off);
-            if (ob > p.v[k] || (ob == p.v[k] && oi < p.i[k])) { p.v[k] = ob; p.i[k] = oi; }
-        }
-        if (lane == 0) { sv[k][wave] = p.v[k]; si[k][wave] = p.i[k]; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            for (int w = 1; w < 4; ++w)
-                if (sv[k][w] > p.v[k] || (sv[k][w] == p.v[k] && si[k][w] < p.i[k])) { p.v[k] = sv[k][w]; p.i[k] = si[k][w]; }
-            A.peak_val[k][blockIdx.x] = p.v[k];
-            A.peak_idx[k][blockIdx.x] = p.i[k];
-        }
-    }
-}
-
 template <int R1, int R2>
 __global__ __launch_bounds__(256) void fft_reg2_kernel(FftArgs A) {
     constexpr int M = R1 * R2, TPL = R1 > R2 ? R1 : R2, LPB = 256 / TPL;      // threads per line, lines per workgroup
@@ -279,7 +253,7 @@ __global__ __launch_bounds__(256) void fft_reg2_kernel(FftArgs A) {
             }
         }
     }
-    if (A.peak_val[0]) peak_flush(pk, A);
+    if (A.peak_val[0]) peak_flush<4>(pk, A.peak_val, A.peak_idx);
 }
 
 // Bluestein's chirp-z for short lines on the same register transforms (n <= 128: M = 64, 128 or 256 points): sample x chirp ->
@@ -362,7 +336,7 @@ __global__ __launch_bounds__(256) void bluestein_reg_kernel(FftArgs A) {
             }
         }
     }
-    if (A.peak_val[0]) peak_flush(pk, A);
+    if (A.peak_val[0]) peak_flush<4>(pk, A.peak_val, A.peak_idx);
 }
 
 struct FftPlan {

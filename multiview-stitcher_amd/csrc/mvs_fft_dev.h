@@ -2,6 +2,7 @@
 // DFT kernels of mvs_fft_lines*.hip (the latter are built in units of their own: ~30 fully unrolled instantiations).
 #pragma once
 #include "mvs_fft.h"
+#include "mvs_fold_dev.h"
 
 struct FftArgs {
     float2* data;
@@ -60,13 +61,42 @@ __device__ __forceinline__ float2 xp_load(const FftArgs& A, const XpLine& xl, lo
     return v;
 }
 // running argmax |Re| / |Im| with the lowest flat index among equal values (np.argmax)
-struct Peak2 { float v[2]; long long i[2]; };
+template <int C>
+struct Peak {
+    float v[C];
+    long long i[C];
+    __device__ __forceinline__ void merge(const Peak& o) {
+#pragma unroll
+        for (int k = 0; k < C; ++k)
+            if (o.v[k] > v[k] || (o.v[k] == v[k] && o.i[k] < i[k])) { v[k] = o.v[k]; i[k] = o.i[k]; }
+    }
+    template <typename S> __device__ __forceinline__ Peak shuffled(S sh, int off) const {
+        Peak o;
+#pragma unroll
+        for (int k = 0; k < C; ++k) { o.v[k] = sh(v[k], off); o.i[k] = sh(i[k], off); }
+        return o;
+    }
+};
+typedef Peak<2> Peak2;
 __device__ __forceinline__ void peak_init(Peak2& p) { p.v[0] = p.v[1] = -1.f; p.i[0] = p.i[1] = 0x7fffffffffffffffLL; }
 __device__ __forceinline__ void peak_add(Peak2& p, float2 o, long long idx) {
     const float a[2] = {fabsf(o.x), fabsf(o.y)};
 #pragma unroll
     for (int k = 0; k < 2; ++k)
         if (a[k] > p.v[k] || (a[k] == p.v[k] && idx < p.i[k])) { p.v[k] = a[k]; p.i[k] = idx; }
+}
+// fold of the workgroup's WAVES waves and the write of its two partials
+template <int WAVES>
+__device__ __forceinline__ void peak_flush(Peak2 p, float* const peak_val[2], long long* const peak_idx[2]) {
+    if constexpr (WAVES == 1) p = mvs_fold::wave_fold(p);
+    else p = mvs_fold::block_fold<WAVES>(p);
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            peak_val[k][blockIdx.x] = p.v[k];
+            peak_idx[k][blockIdx.x] = p.i[k];
+        }
+    }
 }
 // ---- two axes of a 3D transform in one pass: the slab kernels (mvs_fft_slab.inc) ---------------------------------------------------
 // A slab = all samples of two axes at one index of the third: S (short axis: a whole-line DFT length, mvs_dft_small.h) x L (64, 128

@@ -11,24 +11,6 @@ namespace {
 // wavefront copies its 64 lines (64 N contiguous samples) through LDS, coalesced on the global side, one line per lane on the
 // register side (line stride N | 1 float2: conflict-free 8-byte reads).  Carries every fusion of the other register kernels
 // (MvsFftFuse): real / imaginary parts from two float volumes, the cross power formed on the fly, the peak search instead of a store.
-__device__ __forceinline__ void peak_flush_wave(Peak2 p, const FftArgs& A) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ob = __shfl_down(p.v[k], off);
-            const long long oi = __shfl_down(p.i[k], off);
-            if (ob > p.v[k] || (ob == p.v[k] && oi < p.i[k])) { p.v[k] = ob; p.i[k] = oi; }
-        }
-    }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            A.peak_val[k][blockIdx.x] = p.v[k];
-            A.peak_idx[k][blockIdx.x] = p.i[k];
-        }
-    }
-}
-
 template <int N>
 __global__ __launch_bounds__(64) void dft_line_kernel(FftArgs A) {
     constexpr int LS = N | 1;
@@ -110,7 +92,7 @@ __global__ __launch_bounds__(64) void dft_line_kernel(FftArgs A) {
                 peak_add(pk, v[j], base + (long long)j * A.stride);
             });
         }
-        peak_flush_wave(pk, A);
+        peak_flush<1>(pk, A.peak_val, A.peak_idx);
         return;
     }
     if (contig) {

@@ -20,31 +20,6 @@
 
 namespace {
 
-__device__ __forceinline__ void slab_peak_flush(Peak2 p, const SlabArgs& A) {
-    __shared__ float sv[2][4];
-    __shared__ long long si[2][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ob = __shfl_down(p.v[k], off);
-            const long long oi = __shfl_down(p.i[k], off);
-            if (ob > p.v[k] || (ob == p.v[k] && oi < p.i[k])) { p.v[k] = ob; p.i[k] = oi; }
-        }
-        if (lane == 0) { sv[k][wave] = p.v[k]; si[k][wave] = p.i[k]; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            for (int w = 1; w < 4; ++w)
-                if (sv[k][w] > p.v[k] || (sv[k][w] == p.v[k] && si[k][w] < p.i[k])) { p.v[k] = sv[k][w]; p.i[k] = si[k][w]; }
-            A.peak_val[k][blockIdx.x] = p.v[k];
-            A.peak_idx[k][blockIdx.x] = p.i[k];
-        }
-    }
-}
-
 __device__ __forceinline__ float2 slab_load(const SlabArgs& A, long long g, bool inv) {
     if (A.re_src) {
         float re = A.re_src[g], im = A.im_src[g];          // NaN -> 0 (np.nan_to_num, registration.py:403-408)
@@ -166,7 +141,7 @@ __global__ __launch_bounds__(256) void slab_kernel(SlabArgs A) {
     if (L == 256) slab_long_axis<S, 16, 16>(v, T, tw, A, base, inv, pk);
     else if (L == 128) slab_long_axis<S, 16, 8>(v, T, tw, A, base, inv, pk);
     else slab_long_axis<S, 8, 8>(v, T, tw, A, base, inv, pk);
-    if (A.peak_val[0]) slab_peak_flush(pk, A);
+    if (A.peak_val[0]) peak_flush<4>(pk, A.peak_val, A.peak_idx);
 }
 
 template <int N, int LO>

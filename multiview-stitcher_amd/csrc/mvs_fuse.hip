@@ -22,6 +22,7 @@
 // in-bounds test (c < 0 || c > n-1 -> cval) classifies every voxel exactly as
 // NI_GeometricTransform does; interpolation and accumulation are float32.
 #include "mvs_internal.h"
+#include "mvs_fold_dev.h"
 #include "mvs_fuse_dev.h"
 #include "mvs_sample_dev.h"
 #include "mvs_bin_dev.h"
@@ -776,22 +777,12 @@ __global__ __launch_bounds__(256) void crop_int_kernel(const TIn* __restrict__ d
         }
     }
     if (stats) {
-        for (int off = 32; off > 0; off >>= 1) {
-            smn = fminf(smn, __shfl_down(smn, off));
-            smx = fmaxf(smx, __shfl_down(smx, off));
-            snv += __shfl_down(snv, off);
-        }
-        __shared__ float s_mn[4], s_mx[4];
-        __shared__ long long s_nv[4];
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        if (lane == 0) { s_mn[wave] = smn; s_mx[wave] = smx; s_nv[wave] = snv; }
-        __syncthreads();
+        const mvs_fold::Range<long long> r = mvs_fold::block_fold<4>(mvs_fold::Range<long long>{smn, smx, snv});
         if (threadIdx.x == 0) {
-            for (int w = 1; w < 4; ++w) { smn = fminf(smn, s_mn[w]); smx = fmaxf(smx, s_mx[w]); snv += s_nv[w]; }
             const int nb = gridDim.x;
-            ((float*)stats)[blockIdx.x] = smn;
-            ((float*)stats)[nb + blockIdx.x] = smx;
-            ((long long*)(stats + (size_t)nb * 8))[blockIdx.x] = snv;
+            ((float*)stats)[blockIdx.x] = r.mn;
+            ((float*)stats)[nb + blockIdx.x] = r.mx;
+            ((long long*)(stats + (size_t)nb * 8))[blockIdx.x] = r.n;
         }
     }
 }
@@ -886,22 +877,14 @@ __global__ __launch_bounds__(1024) void crop_bin_kernel(const TIn* __restrict__ 
                 if (in[j] && xg + j < ox && j >= dup) { smn = fminf(smn, v[j]); smx = fmaxf(smx, v[j]); ++snv; }
     }
     if (stats) {
-        for (int off = 32; off > 0; off >>= 1) {
-            smn = fminf(smn, __shfl_down(smn, off));
-            smx = fmaxf(smx, __shfl_down(smx, off));
-            snv += __shfl_down(snv, off);
-        }
-        __shared__ float s_mn[16], s_mx[16];      // (up to 1024 threads per workgroup: the statistics' layout fixes the NUMBER of
-        __shared__ long long s_nv[16];            // workgroups, so the kernel gets its memory-level parallelism from their size)
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        if (lane == 0) { s_mn[wave] = smn; s_mx[wave] = smx; s_nv[wave] = snv; }
-        __syncthreads();
+        // (up to 1024 threads per workgroup: the statistics' layout fixes the NUMBER of workgroups, so the kernel gets its
+        // memory-level parallelism from their size)
+        const mvs_fold::Range<long long> r = mvs_fold::block_fold<16>(mvs_fold::Range<long long>{smn, smx, snv}, (int)(blockDim.x >> 6));
         if (threadIdx.x == 0) {
-            for (int w = 1; w < (int)(blockDim.x >> 6); ++w) { smn = fminf(smn, s_mn[w]); smx = fmaxf(smx, s_mx[w]); snv += s_nv[w]; }
             const int nb = gridDim.x;
-            ((float*)stats)[blockIdx.x] = smn;
-            ((float*)stats)[nb + blockIdx.x] = smx;
-            ((long long*)(stats + (size_t)nb * 8))[blockIdx.x] = snv;
+            ((float*)stats)[blockIdx.x] = r.mn;
+            ((float*)stats)[nb + blockIdx.x] = r.mx;
+            ((long long*)(stats + (size_t)nb * 8))[blockIdx.x] = r.n;
         }
     }
 }

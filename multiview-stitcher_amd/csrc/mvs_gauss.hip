@@ -21,6 +21,7 @@
 // are skipped are exact zeros).  A chunk of a tile grid sees one view nearly whole and up to seven by a corner or a face:
 // 1.3 chunk volumes of filter work instead of 8 on the 2x2x2 probe.
 #include "mvs_cb_plan.h"
+#include "mvs_fold_dev.h"
 #include "mvs_fuse_dev.h"
 #include "mvs_fuse_tr.h"
 #include "mvs_fuse_chunk_plan.h"
@@ -161,42 +162,21 @@ __device__ __forceinline__ bool cb_mask_is_box(const CbMaskRec& r) {
 __global__ __launch_bounds__(256) void cb_mask_bbox_kernel(const float* __restrict__ im, const float* __restrict__ bw, CbBoxes8 BX, CbMaskRec* __restrict__ recs) {
     const CbBox32 B = BX.b[blockIdx.y];
     const long long n = (long long)B.n[0] * B.n[1] * B.n[2];
-    unsigned long long cnt = 0;
-    int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {-1, -1, -1};
+    mvs_fold::CountBox<unsigned long long> a = {0, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {-1, -1, -1}};
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const float x = im[B.off + i], w = bw[B.off + i];
         if ((x == x) && !(w < 1e-7f)) {
             const int bx = (int)(i % B.n[2]);
             const long long t = i / B.n[2];
             const int by = (int)(t % B.n[1]), bz = (int)(t / B.n[1]);
-            ++cnt;
-            lo[0] = min(lo[0], bz); hi[0] = max(hi[0], bz);
-            lo[1] = min(lo[1], by); hi[1] = max(hi[1], by);
-            lo[2] = min(lo[2], bx); hi[2] = max(hi[2], bx);
+            a.merge({1, {bz, by, bx}, {bz, by, bx}});
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        cnt += __shfl_down(cnt, off);
-        for (int k = 0; k < 3; ++k) { lo[k] = min(lo[k], __shfl_down(lo[k], off)); hi[k] = max(hi[k], __shfl_down(hi[k], off)); }
-    }
-    __shared__ unsigned long long s_cnt[4];
-    __shared__ int s_lo[4][3], s_hi[4][3];
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_cnt[w] = cnt;
-        for (int k = 0; k < 3; ++k) { s_lo[w][k] = lo[k]; s_hi[w][k] = hi[k]; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {      // one set of atomics per workgroup (a few hundred per view)
-        for (int q = 1; q < 4; ++q) {
-            cnt += s_cnt[q];
-            for (int k = 0; k < 3; ++k) { lo[k] = min(lo[k], s_lo[q][k]); hi[k] = max(hi[k], s_hi[q][k]); }
-        }
-        if (cnt) {
-            CbMaskRec* r = recs + blockIdx.y;
-            atomicAdd(&r->cnt, cnt);
-            for (int k = 0; k < 3; ++k) { atomicMin(&r->lo[k], lo[k]); atomicMax(&r->hi[k], hi[k]); }
-        }
+    a = mvs_fold::block_fold<4>(a);
+    if (threadIdx.x == 0 && a.n) {      // one set of atomics per workgroup (a few hundred per view)
+        CbMaskRec* r = recs + blockIdx.y;
+        atomicAdd(&r->cnt, a.n);
+        for (int k = 0; k < 3; ++k) { atomicMin(&r->lo[k], a.lo[k]); atomicMax(&r->hi[k], a.hi[k]); }
     }
 }
 

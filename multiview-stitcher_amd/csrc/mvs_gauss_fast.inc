@@ -93,33 +93,16 @@ __global__ __launch_bounds__(256) void cb_rows_kernel(const float* __restrict__ 
     }
 }
 __global__ __launch_bounds__(256) void cb_rec_reduce_kernel(const CbPartial* __restrict__ partials, int per_view, CbFastRec* __restrict__ recs) {
-    unsigned long long cnt = 0;
-    int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {-1, -1, -1};
+    mvs_fold::CountBox<unsigned long long> a = {0, {0x7fffffff, 0x7fffffff, 0x7fffffff}, {-1, -1, -1}};
     for (int i = threadIdx.x; i < per_view; i += blockDim.x) {
         const CbPartial P = partials[blockIdx.x * per_view + i];
-        cnt += P.cnt;
-        for (int k = 0; k < 3; ++k) { lo[k] = min(lo[k], P.lo[k]); hi[k] = max(hi[k], P.hi[k]); }
+        a.merge({P.cnt, {P.lo[0], P.lo[1], P.lo[2]}, {P.hi[0], P.hi[1], P.hi[2]}});
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        cnt += __shfl_down(cnt, off);
-        for (int k = 0; k < 3; ++k) { lo[k] = min(lo[k], __shfl_down(lo[k], off)); hi[k] = max(hi[k], __shfl_down(hi[k], off)); }
-    }
-    __shared__ unsigned long long s_cnt[4];
-    __shared__ int s_lo[4][3], s_hi[4][3];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_cnt[wave] = cnt;
-        for (int k = 0; k < 3; ++k) { s_lo[wave][k] = lo[k]; s_hi[wave][k] = hi[k]; }
-    }
-    __syncthreads();
+    a = mvs_fold::block_fold<4>(a);
     if (threadIdx.x == 0) {
-        for (int q = 1; q < 4; ++q) {
-            cnt += s_cnt[q];
-            for (int k = 0; k < 3; ++k) { lo[k] = min(lo[k], s_lo[q][k]); hi[k] = max(hi[k], s_hi[q][k]); }
-        }
         CbFastRec R;
-        R.cnt = cnt;
-        for (int k = 0; k < 3; ++k) { R.lo[k] = lo[k]; R.hi[k] = hi[k]; }
+        R.cnt = a.n;
+        for (int k = 0; k < 3; ++k) { R.lo[k] = a.lo[k]; R.hi[k] = a.hi[k]; }
         R.nmiss = 0;
         for (int k = 0; k < 7; ++k) R.pad[k] = 0;
         recs[blockIdx.x] = R;

@@ -80,7 +80,7 @@ __global__ __launch_bounds__(kPairBlockThreads) void intensity_moments_kernel(In
 
     __shared__ PairMoments lds[kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const PairMoments w = wave_merge(pair_sums_to_moments(acc));
+    const PairMoments w = mvs_fold::wave_fold(pair_sums_to_moments(acc));
     if (lane == 0) lds[wave] = w;
     __syncthreads();
     if (threadIdx.x == 0) {

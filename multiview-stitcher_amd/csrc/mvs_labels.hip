@@ -5,6 +5,7 @@
 // Every result is an integer: integer atomics only, equal inputs give equal results (the triples of a table after sorting).  Limits,
 // the table's key / hash / probe sequence and the launch geometry: mvs_labels_plan.h.
 #include "mvs_internal.h"
+#include "mvs_fold_dev.h"
 #include "mvs_fuse_dev.h"
 #include "mvs_labels_plan.h"
 
@@ -151,7 +152,7 @@ __global__ __launch_bounds__(kThreads) void label_counts_kernel(CountArgs P) {
         counter.count(lane < n && (long long)label < P.capacity ? label : -1, add);
     }
     counter.flush(add);
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
+    mx = mvs_fold::wave_fold(mvs_fold::Max<int>{mx}).v;
     if (lane == 0 && mx > 0) atomicMax(P.max_label, mx);
 }
 

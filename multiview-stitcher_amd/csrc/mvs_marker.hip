@@ -14,6 +14,7 @@
 // order without contraction: bead coordinates are world coordinates (1e6 with sub-pixel differences), where the expanded form
 // |a|^2 + |b|^2 - 2ab cancels.
 #include "mvs_internal.h"
+#include "mvs_fold_dev.h"
 
 #include <algorithm>
 #include <cmath>
@@ -242,10 +243,8 @@ __global__ __launch_bounds__(256) void score_kernel(const double* __restrict__ a
             sum += res;
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        cnt += __shfl_down(cnt, off);
-        sum += __shfl_down(sum, off);
-    }
+    cnt = mvs_fold::wave_fold(mvs_fold::Sums<int>{{cnt}}).v[0];
+    sum = mvs_fold::wave_fold(mvs_fold::Sums<double>{{sum}}).v[0];
     if (lane == 0) {
         count_out[h] = cnt;
         sum_out[h] = sum;

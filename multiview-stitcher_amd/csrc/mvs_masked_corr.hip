@@ -9,6 +9,7 @@
 // mvs_masked_corr_plan.h.
 #include "mvs_internal.h"
 #include "mvs_fft.h"
+#include "mvs_fold_dev.h"
 #include "mvs_masked_corr_plan.h"
 
 #include <cfloat>
@@ -45,6 +46,8 @@ struct StatPartial {
     double sum;
     long long n;
     float mn, mx;
+    __device__ __forceinline__ void merge(const StatPartial& o) { sum += o.sum; n += o.n; mn = fminf(mn, o.mn); mx = fmaxf(mx, o.mx); }
+    template <typename S> __device__ __forceinline__ StatPartial shuffled(S sh, int off) const { return {sh(sum, off), sh(n, off), sh(mn, off), sh(mx, off)}; }
 };
 
 // what the pack pass needs of a crop, and the status rule: n, mu = sum / n, range = max - min (1 where that is 0 or n == 0)
@@ -60,24 +63,6 @@ __device__ __forceinline__ bool voxel_valid(const Crops& C, int k, int i, float 
     return ok;
 }
 
-__device__ __forceinline__ void stat_merge(StatPartial& a, double sum, long long n, float mn, float mx) {
-    a.sum += sum;
-    a.n += n;
-    a.mn = fminf(a.mn, mn);
-    a.mx = fmaxf(a.mx, mx);
-}
-
-// The workgroup's fold of `a` in a fixed tree: xor shuffles within a wave, the waves in order.  Valid in thread 0.
-__device__ __forceinline__ StatPartial stat_block_fold(StatPartial a) {
-    __shared__ StatPartial s_part[kWaves];
-    for (int o = 32; o > 0; o >>= 1) stat_merge(a, __shfl_xor(a.sum, o), __shfl_xor(a.n, o), __shfl_xor(a.mn, o), __shfl_xor(a.mx, o));
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < kWaves; ++w) stat_merge(a, s_part[w].sum, s_part[w].n, s_part[w].mn, s_part[w].mx);
-    return a;
-}
-
 // ---- statistics ---------------------------------------------------------------------------------------------------------------------
 // grid (nb, 2): crop blockIdx.y, one partial per workgroup ...
 __global__ __launch_bounds__(kThreads) void mc_stats_kernel(Crops C, int voxels, StatPartial* partials) {
@@ -85,9 +70,9 @@ __global__ __launch_bounds__(kThreads) void mc_stats_kernel(Crops C, int voxels,
     StatPartial a{0.0, 0, INFINITY, -INFINITY};
     for (int i = blockIdx.x * kThreads + threadIdx.x; i < voxels; i += gridDim.x * kThreads) {
         const float v = C.im[k][i];
-        if (voxel_valid(C, k, i, v)) stat_merge(a, (double)v, 1, v, v);
+        if (voxel_valid(C, k, i, v)) a.merge({(double)v, 1, v, v});
     }
-    a = stat_block_fold(a);
+    a = mvs_fold::block_fold<kWaves>(a);
     if (threadIdx.x == 0) partials[k * gridDim.x + blockIdx.x] = a;
 }
 
@@ -95,11 +80,8 @@ __global__ __launch_bounds__(kThreads) void mc_stats_kernel(Crops C, int voxels,
 __global__ __launch_bounds__(kThreads) void mc_stats_final_kernel(const StatPartial* partials, int nb, CropNorm* norms) {
     const int k = blockIdx.x;
     StatPartial a{0.0, 0, INFINITY, -INFINITY};
-    for (int i = threadIdx.x; i < nb; i += kThreads) {
-        const StatPartial p = partials[k * nb + i];
-        stat_merge(a, p.sum, p.n, p.mn, p.mx);
-    }
-    a = stat_block_fold(a);
+    for (int i = threadIdx.x; i < nb; i += kThreads) a.merge(partials[k * nb + i]);
+    a = mvs_fold::block_fold<kWaves>(a);
     if (threadIdx.x == 0) {
         CropNorm r;
         r.n = a.n;
@@ -203,39 +185,20 @@ __device__ __forceinline__ bool shift_eligible(int n, int nmax, double overlap_r
 struct MaxPartial {
     int nmax;
     float denmax;
+    __device__ __forceinline__ void merge(const MaxPartial& o) { nmax = max(nmax, o.nmax); denmax = fmaxf(denmax, o.denmax); }
+    template <typename S> __device__ __forceinline__ MaxPartial shuffled(S sh, int off) const { return {sh(nmax, off), sh(denmax, off)}; }
 };
 struct PeakPartial {
     float r;            // -inf: none
     int w;              // window index, INT_MAX: none
     int any_positive;   // an eligible shift whose denominator is above the tolerance
+    // larger r wins, among equals the lower window index
+    __device__ __forceinline__ void merge(const PeakPartial& o) {
+        if (o.r > r || (o.r == r && o.w < w)) { r = o.r; w = o.w; }
+        any_positive |= o.any_positive;
+    }
+    template <typename S> __device__ __forceinline__ PeakPartial shuffled(S sh, int off) const { return {sh(r, off), sh(w, off), sh(any_positive, off)}; }
 };
-
-__device__ __forceinline__ void max_merge(MaxPartial& a, int n, float den) {
-    a.nmax = max(a.nmax, n);
-    a.denmax = fmaxf(a.denmax, den);
-}
-__device__ __forceinline__ MaxPartial max_block_fold(MaxPartial a) {
-    __shared__ MaxPartial s_part[kWaves];
-    for (int o = 32; o > 0; o >>= 1) max_merge(a, __shfl_xor(a.nmax, o), __shfl_xor(a.denmax, o));
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = a;
-    __syncthreads();
-    for (int w = 0; w < kWaves; ++w) max_merge(a, s_part[w].nmax, s_part[w].denmax);      // (every thread: the search needs it in all)
-    return a;
-}
-// larger r wins, among equals the lower window index
-__device__ __forceinline__ void peak_merge(PeakPartial& a, float r, int w, int any_positive) {
-    if (r > a.r || (r == a.r && w < a.w)) { a.r = r; a.w = w; }
-    a.any_positive |= any_positive;
-}
-__device__ __forceinline__ PeakPartial peak_block_fold(PeakPartial a) {
-    __shared__ PeakPartial s_part[kWaves];
-    for (int o = 32; o > 0; o >>= 1) peak_merge(a, __shfl_xor(a.r, o), __shfl_xor(a.w, o), __shfl_xor(a.any_positive, o));
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < kWaves; ++w) peak_merge(a, s_part[w].r, s_part[w].w, s_part[w].any_positive);
-    return a;
-}
 
 // (a) the largest rint(N) and the largest denominator of the window
 __global__ __launch_bounds__(kThreads) void mc_window_max_kernel(Dims D, const float2* __restrict__ X1, const float2* __restrict__ X2, const float2* __restrict__ X3,
@@ -244,9 +207,9 @@ __global__ __launch_bounds__(kThreads) void mc_window_max_kernel(Dims D, const f
     for (int w = blockIdx.x * kThreads + threadIdx.x; w < D.window; w += gridDim.x * kThreads) {
         const int wx = w % D.Wx, wy = (w / D.Wx) % D.Wy, wz = w / (D.Wx * D.Wy);
         const ShiftTerms t = shift_terms(X1, X2, X3, window_index(D, wz, wy, wx));
-        max_merge(a, t.n, t.den);
+        a.merge({t.n, t.den});
     }
-    a = max_block_fold(a);
+    a = mvs_fold::block_fold<kWaves>(a);
     if (threadIdx.x == 0) partials[blockIdx.x] = a;
 }
 
@@ -263,8 +226,8 @@ struct SearchArgs {
 __global__ __launch_bounds__(kThreads) void mc_window_search_kernel(Dims D, SearchArgs A, const float2* __restrict__ X1, const float2* __restrict__ X2,
                                                                     const float2* __restrict__ X3, PeakPartial* partials) {
     MaxPartial mp{0, 0.f};
-    for (int i = threadIdx.x; i < A.n_max_partials; i += kThreads) max_merge(mp, A.max_partials[i].nmax, A.max_partials[i].denmax);
-    mp = max_block_fold(mp);
+    for (int i = threadIdx.x; i < A.n_max_partials; i += kThreads) mp.merge(A.max_partials[i]);
+    mp = mvs_fold::block_fold_all<kWaves>(mp);      // (every thread: the search needs it in all)
     const float tol = 1e3f * FLT_EPSILON * mp.denmax;
     PeakPartial a{-INFINITY, INT_MAX, 0};
     for (int w = blockIdx.x * kThreads + threadIdx.x; w < D.window; w += gridDim.x * kThreads) {
@@ -273,9 +236,9 @@ __global__ __launch_bounds__(kThreads) void mc_window_search_kernel(Dims D, Sear
         const float r = shift_r(t, tol);
         if (A.r_out) A.r_out[w] = r;
         if (A.n_out) A.n_out[w] = t.n;
-        if (shift_eligible(t.n, mp.nmax, A.overlap_ratio, A.min_overlap)) peak_merge(a, r, w, t.den > tol ? 1 : 0);
+        if (shift_eligible(t.n, mp.nmax, A.overlap_ratio, A.min_overlap)) a.merge({r, w, t.den > tol ? 1 : 0});
     }
-    a = peak_block_fold(a);
+    a = mvs_fold::block_fold<kWaves>(a);
     if (threadIdx.x == 0) partials[blockIdx.x] = a;
 }
 
@@ -284,12 +247,12 @@ __global__ __launch_bounds__(kThreads) void mc_result_kernel(Dims D, SearchArgs 
                                                              const float2* __restrict__ X3, const PeakPartial* partials, int n_partials,
                                                              const CropNorm* norms, mvs_masked_corr_result_t* out) {
     MaxPartial mp{0, 0.f};
-    for (int i = threadIdx.x; i < A.n_max_partials; i += kThreads) max_merge(mp, A.max_partials[i].nmax, A.max_partials[i].denmax);
-    mp = max_block_fold(mp);
+    for (int i = threadIdx.x; i < A.n_max_partials; i += kThreads) mp.merge(A.max_partials[i]);
+    mp = mvs_fold::block_fold_all<kWaves>(mp);      // (every thread: the search needs it in all)
     const float tol = 1e3f * FLT_EPSILON * mp.denmax;
     PeakPartial a{-INFINITY, INT_MAX, 0};
-    for (int i = threadIdx.x; i < n_partials; i += kThreads) peak_merge(a, partials[i].r, partials[i].w, partials[i].any_positive);
-    a = peak_block_fold(a);
+    for (int i = threadIdx.x; i < n_partials; i += kThreads) a.merge(partials[i]);
+    a = mvs_fold::block_fold<kWaves>(a);
     if (threadIdx.x != 0) return;
     const CropNorm nf = norms[0], nm = norms[1];
     mvs_masked_corr_result_t R;

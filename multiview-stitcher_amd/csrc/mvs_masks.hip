@@ -5,6 +5,7 @@
 // mv_graph.get_connected_labels (mv_graph.py:895-931) of the reference.  Every result is an integer or a selection: integer atomics
 // only, equal inputs give equal bits.  Limits and launch geometry: mvs_masks_plan.h.
 #include "mvs_internal.h"
+#include "mvs_fold_dev.h"
 #include "mvs_fuse_dev.h"
 #include "mvs_masks_plan.h"
 #include "mvs_sample_dev.h"
@@ -22,15 +23,8 @@ static_assert(kMaxBins == MVS_HIST_MAX_BINS && kMaxDilate == MVS_MASK_MAX_DILATE
 // ---- shared device pieces -----------------------------------------------------------------------------------------------------------
 // Sum of `v` over the workgroup, added to *dst (if any) by one integer atomic.
 __device__ __forceinline__ void block_add_u64(unsigned long long v, unsigned long long* dst) {
-    __shared__ unsigned long long s_part[kWaves];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0 && dst) {
-        unsigned long long sum = 0;
-        for (int w = 0; w < kWaves; ++w) sum += s_part[w];
-        if (sum) atomicAdd(dst, sum);
-    }
+    const unsigned long long sum = mvs_fold::block_fold<kWaves>(mvs_fold::Sums<unsigned long long>{{v}}).v[0];
+    if (threadIdx.x == 0 && dst && sum) atomicAdd(dst, sum);
 }
 
 // The nx elements of a row at p, shared among the 64 lanes of a wave: 16-byte loads from the row's first 16-byte aligned element on,
@@ -65,10 +59,7 @@ struct HistArgs {
     long long total_rows;
 };
 
-struct RangePartial {
-    float mn, mx;
-    long long n;
-};
+typedef mvs_fold::Range<long long> RangePartial;
 
 // row r of the stack of all tiles: its tile (binary search over row0) and its address
 template <typename T>
@@ -85,16 +76,9 @@ __device__ __forceinline__ const T* hist_row(const HistArgs& P, long long r, int
     return (const T*)(t.data + (lr / t.ny) * t.sz + (lr % t.ny) * t.sy);
 }
 
-__device__ __forceinline__ void range_merge(RangePartial& a, float mn, float mx, long long n) {
-    a.mn = fminf(a.mn, mn);
-    a.mx = fmaxf(a.mx, mx);
-    a.n += n;
-}
-
 // minimum, maximum and number of the non-NaN voxels a workgroup sees: one partial per workgroup ...
 template <typename T>
 __global__ __launch_bounds__(kThreads) void hist_range_kernel(HistArgs P, RangePartial* partials) {
-    __shared__ RangePartial s_part[kWaves];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     RangePartial a{INFINITY, -INFINITY, 0};
     for (long long r = (long long)blockIdx.x * kWaves + wave; r < P.total_rows; r += (long long)gridDim.x * kWaves) {
@@ -102,31 +86,19 @@ __global__ __launch_bounds__(kThreads) void hist_range_kernel(HistArgs P, RangeP
         const T* p = hist_row<T>(P, r, &nx);
         visit_row<T>(p, nx, lane, [&](T raw) {
             const float v = (float)raw;
-            if (v == v) range_merge(a, v, v, 1);
+            if (v == v) a.merge({v, v, 1});
         });
     }
-    for (int o = 32; o > 0; o >>= 1) range_merge(a, __shfl_xor(a.mn, o), __shfl_xor(a.mx, o), __shfl_xor(a.n, o));
-    if (lane == 0) s_part[wave] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kWaves; ++w) range_merge(a, s_part[w].mn, s_part[w].mx, s_part[w].n);
-        partials[blockIdx.x] = a;
-    }
+    a = mvs_fold::block_fold<kWaves>(a);
+    if (threadIdx.x == 0) partials[blockIdx.x] = a;
 }
 
 // ... and one small launch that folds the partials
 __global__ __launch_bounds__(kThreads) void hist_range_final_kernel(const RangePartial* partials, int n, RangePartial* out) {
-    __shared__ RangePartial s_part[kWaves];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     RangePartial a{INFINITY, -INFINITY, 0};
-    for (int i = threadIdx.x; i < n; i += kThreads) range_merge(a, partials[i].mn, partials[i].mx, partials[i].n);
-    for (int o = 32; o > 0; o >>= 1) range_merge(a, __shfl_xor(a.mn, o), __shfl_xor(a.mx, o), __shfl_xor(a.n, o));
-    if (lane == 0) s_part[wave] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kWaves; ++w) range_merge(a, s_part[w].mn, s_part[w].mx, s_part[w].n);
-        *out = a;
-    }
+    for (int i = threadIdx.x; i < n; i += kThreads) a.merge(partials[i]);
+    a = mvs_fold::block_fold<kWaves>(a);
+    if (threadIdx.x == 0) *out = a;
 }
 
 // numpy's bin of v among n_bins equal bins over [edges[0], edges[n_bins]] (numpy/lib/_histograms_impl.py, the equal-bin path): the

@@ -95,7 +95,7 @@ __global__ __launch_bounds__(kMatchThreads) void block_match_kernel(MatchArgs P)
             if (y >= ny) { y -= ny; ++z; }
             z += dz;
         }
-        const PairMoments w = wave_merge(pair_sums_to_moments(acc));
+        const PairMoments w = mvs_fold::wave_fold(pair_sums_to_moments(acc));
         if (lane == 0) rows[s] = w;
     }
 }

@@ -69,7 +69,7 @@ __global__ __launch_bounds__(kPairBlockThreads) void pair_moments_kernel(PairArg
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) {
-        const PairMoments r = wave_merge(pair_sums_to_moments(acc[k]));
+        const PairMoments r = mvs_fold::wave_fold(pair_sums_to_moments(acc[k]));
         if (lane == 0) lds[wave][k] = r;
     }
     __syncthreads();

@@ -12,6 +12,11 @@ constexpr int kPairMaxBlocks = 2048;     // workgroups of one launch = min(ceil(
 // products of the two deviations.  n is kept as a double (exact up to 2^53).
 struct PairMoments {
     double n, mean_f, mean_m, m2_f, m2_m, c_fm;
+    // a partial of mvs_fold_dev.h: merge is pair_moments_merge(*this, b)
+    __device__ __forceinline__ void merge(const PairMoments& b);
+    template <typename S> __device__ __forceinline__ PairMoments shuffled(S sh, int off) const {
+        return PairMoments{sh(n, off), sh(mean_f, off), sh(mean_m, off), sh(m2_f, off), sh(m2_m, off), sh(c_fm, off)};
+    }
 };
 
 MVS_HD PairMoments pair_moments_empty() { return PairMoments{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}; }
@@ -70,3 +75,4 @@ MVS_HD PairMoments pair_moments_merge(const PairMoments& a, const PairMoments& b
     r.c_fm = (a.c_fm + b.c_fm) + df * dm * w;
     return r;
 }
+__device__ __forceinline__ void PairMoments::merge(const PairMoments& b) { *this = pair_moments_merge(*this, b); }

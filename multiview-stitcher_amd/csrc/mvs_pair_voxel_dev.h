@@ -1,8 +1,9 @@
 // mvs_pair_voxel_dev.h -- internal, device only: what the kernels that reduce sample pairs over an overlap grid share
 // (mvs_pair_metrics.hip, mvs_intensity.hip, mvs_nonrigid.hip): the per-voxel rule of mvs_pair_moments (halfspace mask, grid index ->
-// pixel, in-bounds test, linear float32 sample, finite test), the wave step of the fixed merge tree and the fold of the workgroups'
-// results by one wave.  One copy, so that a voxel counted by any of the kernels is the same voxel with the same bits.
+// pixel, in-bounds test, linear float32 sample, finite test) and the fold of the workgroups' results by one wave (the wave step of
+// the fixed merge tree is mvs_fold::wave_fold).  One copy, so that a voxel counted by any of the kernels is the same voxel with the same bits.
 #pragma once
+#include "mvs_fold_dev.h"
 #include "mvs_sample_dev.h"
 #include "mvs_pair_metrics_dev.h"
 
@@ -29,31 +30,13 @@ __device__ __forceinline__ bool pair_sample_finite(const DevView& V, double cz, 
     return isfinite(*v);
 }
 
-__device__ __forceinline__ PairMoments shfl_down_moments(const PairMoments& r, int off) {
-    PairMoments o;
-    o.n = __shfl_down(r.n, off, 64);
-    o.mean_f = __shfl_down(r.mean_f, off, 64);
-    o.mean_m = __shfl_down(r.mean_m, off, 64);
-    o.m2_f = __shfl_down(r.m2_f, off, 64);
-    o.m2_m = __shfl_down(r.m2_m, off, 64);
-    o.c_fm = __shfl_down(r.c_fm, off, 64);
-    return o;
-}
-
-// lane 0 gets the moments of the whole wave: at every step a lane is the left operand and the lane `off` above it the right one
-__device__ __forceinline__ PairMoments wave_merge(PairMoments r) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) r = pair_moments_merge(r, shfl_down_moments(r, off));
-    return r;
-}
-
 // The fold of the n results p[0], p[stride], ... by one wave: lane l merges its run of ceil(n / 64) consecutive ones in index order,
-// then the lanes merge in the tree of wave_merge -- every result's place in the tree is a function of (n, its index) only.  Lane 0
+// then the lanes merge in the tree of mvs_fold::wave_fold -- every result's place in the tree is a function of (n, its index) only.  Lane 0
 // gets the fold.
 __device__ __forceinline__ PairMoments pair_moments_fold(const PairMoments* p, long long stride, int n, int lane) {
     const int run = (n + 63) / 64;
     const int lo = lane * run, hi = min(lo + run, n);
     PairMoments r = pair_moments_empty();
     for (int i = lo; i < hi; ++i) r = pair_moments_merge(r, p[(long long)i * stride]);
-    return wave_merge(r);
+    return mvs_fold::wave_fold(r);
 }

@@ -12,6 +12,7 @@
 // order.  Beads pass through in batches sized to a scratch budget; B carries its accumulator from batch to batch, so the sum visits
 // the beads in the same order whatever the batch size, and equal inputs give equal bits.
 #include "mvs_internal.h"
+#include "mvs_fold_dev.h"
 #include "mvs_fuse_dev.h"
 #include "mvs_sample_dev.h"
 
@@ -41,28 +42,15 @@ struct PsfArgs {
     float* rows;                 // [bead - b0][offset]
 };
 
-// Sums of K doubles over the workgroup, the same value in every thread: lanes by shuffles (a lane is the left operand, the lane
-// `off` above it the right one), then the waves in wave order.  Every thread of the workgroup calls it.
+// Sums of K doubles over the workgroup, the same value in every thread (mvs_fold_dev.h).  Every thread of the workgroup calls it.
 template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double (*lds)[5]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+__device__ __forceinline__ void block_sum(double (&v)[K]) {
+    mvs_fold::Sums<double, K> s;
 #pragma unroll
-    for (int k = 0; k < K; ++k)
+    for (int k = 0; k < K; ++k) s.v[k] = v[k];
+    s = mvs_fold::block_fold_all<kWaves>(s);
 #pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
-    __syncthreads();                              // (the readers of the previous call are done with lds)
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) lds[wave][k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double s = lds[0][k];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) s += lds[w][k];
-        v[k] = s;
-    }
+    for (int k = 0; k < K; ++k) v[k] = s.v[k];
 }
 
 // window offset of flat index i (x fastest)
@@ -76,7 +64,6 @@ __device__ __forceinline__ void window_offset(const PsfArgs& P, int i, int& oz, 
 // Stage A.  grid = beads of the batch.  Loop exits are taken by the whole workgroup (they depend on block sums only).
 template <typename T>
 __global__ __launch_bounds__(kThreads) void psf_window_kernel(PsfArgs P) {
-    __shared__ double lds[kWaves][5];
     const long long b = (long long)P.b0 + blockIdx.x;
     float* row = P.rows + (long long)blockIdx.x * P.n_window;
     double cz = P.centers_in[3 * b], cy = P.centers_in[3 * b + 1], cx = P.centers_in[3 * b + 2];
@@ -101,7 +88,7 @@ __global__ __launch_bounds__(kThreads) void psf_window_kernel(PsfArgs P) {
             const bool shell = (P.first_axis == 0 && abs(oz) == P.r[0]) || abs(oy) == P.r[1] || abs(ox) == P.r[2];
             if (shell) a[0] += (double)s;
         }
-        block_sum<2>(a, lds);
+        block_sum<2>(a);
         if (a[1] > 0.0) {
             status = 1;
             bg = esum = NAN;
@@ -119,7 +106,7 @@ __global__ __launch_bounds__(kThreads) void psf_window_kernel(PsfArgs P) {
             mo[2] += (double)oy * e;
             mo[3] += (double)ox * e;
         }
-        block_sum<4>(mo, lds);
+        block_sum<4>(mo);
         esum = mo[0];
         if (!(esum > 0.0 && esum < INFINITY)) {
             status = 2;
@@ -164,7 +151,6 @@ __global__ __launch_bounds__(kThreads) void psf_finish_kernel(const double* __re
 // Stage C.  grid = beads of the batch; a bead that is not used leaves at once (the whole workgroup).
 __global__ __launch_bounds__(kThreads) void psf_ncc_kernel(const float* __restrict__ rows, const float* __restrict__ psf, const int32_t* __restrict__ status,
                                                            int b0, int n_window, float* __restrict__ stats) {
-    __shared__ double lds[kWaves][5];
     const long long b = (long long)b0 + blockIdx.x;
     if (status[b] != 0) return;
     const float* row = rows + (long long)blockIdx.x * n_window;
@@ -177,7 +163,7 @@ __global__ __launch_bounds__(kThreads) void psf_ncc_kernel(const float* __restri
         s[3] += p * p;
         s[4] += u * p;
     }
-    block_sum<5>(s, lds);
+    block_sum<5>(s);
     if (threadIdx.x == 0) {
         const double n = (double)n_window;
         const double vu = s[2] - s[0] * s[0] / n, vp = s[3] - s[1] * s[1] / n, cov = s[4] - s[0] * s[1] / n;

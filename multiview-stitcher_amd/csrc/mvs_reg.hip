@@ -9,7 +9,7 @@
 //   wrap to signed shift, then the matrix-multiply upsampled DFT around round(shift*u)/u
 // mvs_rescale_intensity == skimage.exposure.rescale_intensity(im, in_range=(nanmin, nanmax),
 // out_range=(0,1)) (registration.py:381-389).
-#include "mvs_fft.h"
+#include "mvs_fft_dev.h"
 
 #include <rocprim/warp/warp_reduce.hpp>
 
@@ -64,32 +64,19 @@ template <int COMP>
 __global__ __launch_bounds__(256) void argmax_abs_kernel(const float2* __restrict__ c, long long n, float* __restrict__ pval,
                                                          long long* __restrict__ pidx) {
     constexpr int comp = COMP;
-    float best = -1.f;
-    long long bi = 0x7fffffffffffffffLL;
+    Peak<1> best = {{-1.f}, {0x7fffffffffffffffLL}};
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const float2 v = c[i];
         float a;
         if (comp == 0) a = hypotf(v.x, v.y);
         else if (comp == 1) a = fabsf(v.x);
         else a = fabsf(v.y);
-        if (a > best || (a == best && i < bi)) { best = a; bi = i; }
+        best.merge({{a}, {i}});
     }
-    // wavefront shuffle reduction, then across the 4 wavefronts through LDS
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ob = __shfl_down(best, off);
-        const long long oi = __shfl_down(bi, off);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    __shared__ float sv[4];
-    __shared__ long long si[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { sv[wave] = best; si[wave] = bi; }
-    __syncthreads();
+    best = mvs_fold::block_fold<4>(best);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-        pval[blockIdx.x] = best;
-        pidx[blockIdx.x] = bi;
+        pval[blockIdx.x] = best.v[0];
+        pidx[blockIdx.x] = best.i[0];
     }
 }
 
@@ -99,38 +86,21 @@ __global__ __launch_bounds__(256) void argmax_abs_kernel(const float2* __restric
 __global__ __launch_bounds__(256) void argmax_abs2_kernel(const float2* __restrict__ c, long long n, float* __restrict__ pval,
                                                           long long* __restrict__ pidx, float* __restrict__ pval2, long long* __restrict__ pidx2,
                                                           const float2* __restrict__ z0_src, float2* __restrict__ z0_dst) {
-    float best[2] = {-1.f, -1.f};
-    long long bi[2] = {0x7fffffffffffffffLL, 0x7fffffffffffffffLL};
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float2 v = c[i];
-        const float a[2] = {fabsf(v.x), fabsf(v.y)};
-#pragma unroll
-        for (int k = 0; k < 2; ++k)
-            if (a[k] > best[k] || (a[k] == best[k] && i < bi[k])) { best[k] = a[k]; bi[k] = i; }
-    }
-    __shared__ float sv[2][4];
-    __shared__ long long si[2][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ob = __shfl_down(best[k], off);
-            const long long oi = __shfl_down(bi[k], off);
-            if (ob > best[k] || (ob == best[k] && oi < bi[k])) { best[k] = ob; bi[k] = oi; }
-        }
-        if (lane == 0) { sv[k][wave] = best[k]; si[k][wave] = bi[k]; }
-    }
-    __syncthreads();
+    Peak2 best;
+    peak_init(best);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) peak_add(best, c[i], i);
+    best = mvs_fold::block_fold<4>(best);
     if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            for (int w = 1; w < 4; ++w)
-                if (sv[k][w] > best[k] || (sv[k][w] == best[k] && si[k][w] < bi[k])) { best[k] = sv[k][w]; bi[k] = si[k][w]; }
-        }
-        pval[blockIdx.x] = best[0]; pidx[blockIdx.x] = bi[0];
-        pval2[blockIdx.x] = best[1]; pidx2[blockIdx.x] = bi[1];
+        pval[blockIdx.x] = best.v[0]; pidx[blockIdx.x] = best.i[0];
+        pval2[blockIdx.x] = best.v[1]; pidx2[blockIdx.x] = best.i[1];
         if (blockIdx.x == 0) *z0_dst = *z0_src;
     }
+}
+
+// sum of a complex value over the wavefront, in lane 0
+__device__ __forceinline__ float2 wave_sum2(float2 v) {
+    const mvs_fold::Sums<float, 2> s = mvs_fold::wave_fold(mvs_fold::Sums<float, 2>{{v.x, v.y}});
+    return make_float2(s.v[0], s.v[1]);
 }
 
 // Upsampled DFT, stage 1: contract the last (x) axis with kernel K (U x nx), input conj(P).
@@ -149,10 +119,7 @@ __global__ __launch_bounds__(256) void updft_x_kernel(const float2* __restrict__
             acc.x += k.x * p.x + k.y * p.y;
             acc.y += k.y * p.x - k.x * p.y;
         }
-        for (int off = 32; off > 0; off >>= 1) {
-            acc.x += __shfl_down(acc.x, off);
-            acc.y += __shfl_down(acc.y, off);
-        }
+        acc = wave_sum2(acc);
         if (lane == 0) out[row * U + a] = acc;
     }
 }
@@ -207,11 +174,7 @@ __global__ __launch_bounds__(256) void updft_x2_kernel(const float2* __restrict_
 #pragma unroll
         for (int a = 0; a < UM; ++a) {
             if (a < U) {
-                float2 r = acc[j][a];
-                for (int off = 32; off > 0; off >>= 1) {
-                    r.x += __shfl_down(r.x, off);
-                    r.y += __shfl_down(r.y, off);
-                }
+                const float2 r = wave_sum2(acc[j][a]);
                 if (lane == 0) q.out[j][row * U + a] = r;
             }
         }
@@ -323,42 +286,33 @@ __global__ __launch_bounds__(256) void updft_mid_kernel(const float2* __restrict
             acc.x += k.x * v.x - k.y * v.y;
             acc.y += k.x * v.y + k.y * v.x;
         }
-        for (int off = 32; off > 0; off >>= 1) {
-            acc.x += __shfl_down(acc.x, off);
-            acc.y += __shfl_down(acc.y, off);
-        }
+        acc = wave_sum2(acc);
         if (lane == 0) out[t] = acc;
     }
 }
 
-// nanmin / nanmax per block (float), finished on the host
-__global__ __launch_bounds__(256) void nanminmax_kernel(const float* __restrict__ a, long long n, float* __restrict__ pmin,
-                                                        float* __restrict__ pmax, long long* __restrict__ pvalid) {
-    float mn = INFINITY, mx = -INFINITY;
-    long long nv = 0;
+// nanmin / nanmax / count of one block's share of `a` into slot blockIdx.x of the partials [float min[nb] | float max[nb] |
+// long long count[nb]], finished on the host (fold_minmax_partials)
+__device__ __forceinline__ void nanminmax_block(const float* __restrict__ a, long long n, char* __restrict__ part, int nb) {
+    mvs_fold::Range<long long> r = {INFINITY, -INFINITY, 0};
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const float v = a[i];
         if (v == v) {
-            mn = fminf(mn, v); mx = fmaxf(mx, v); ++nv;
+            r.mn = fminf(r.mn, v); r.mx = fmaxf(r.mx, v); ++r.n;
             // upper half of the count: valid voxels that are NOT integers in [0, 65535] (an image of such integers can be rank-
             // ordered by 16-bit keys, see mvs_score.hip)
-            if (!(v >= 0.f && v <= 65535.f && v == floorf(v))) nv += 1ll << 32;
+            if (!(v >= 0.f && v <= 65535.f && v == floorf(v))) r.n += 1ll << 32;
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = fminf(mn, __shfl_down(mn, off));
-        mx = fmaxf(mx, __shfl_down(mx, off));
-        nv += __shfl_down(nv, off);
-    }
-    __shared__ float smn[4], smx[4];
-    __shared__ long long snv[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { smn[wave] = mn; smx[wave] = mx; snv[wave] = nv; }
-    __syncthreads();
+    r = mvs_fold::block_fold<4>(r);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) { mn = fminf(mn, smn[w]); mx = fmaxf(mx, smx[w]); nv += snv[w]; }
-        pmin[blockIdx.x] = mn; pmax[blockIdx.x] = mx; pvalid[blockIdx.x] = nv;
+        ((float*)part)[blockIdx.x] = r.mn;
+        ((float*)part)[nb + blockIdx.x] = r.mx;
+        ((long long*)(part + (size_t)nb * 8))[blockIdx.x] = r.n;
     }
+}
+__global__ __launch_bounds__(256) void nanminmax_kernel(const float* __restrict__ a, long long n, char* __restrict__ partials, int nb) {
+    nanminmax_block(a, n, partials, nb);
 }
 
 // (clip(im, lo, hi) - lo) / (hi - lo) * 1 + 0 in float32, NaN preserved (skimage rescale_intensity)
@@ -378,34 +332,7 @@ __global__ void rescale_kernel(const float* __restrict__ src, float* __restrict_
 // both crops of a pair in one launch (blockIdx.y = image): same bodies
 struct PairPtrs { const float* in[2]; float* out[2]; float lo[2], hi[2]; int degenerate[2]; };
 __global__ __launch_bounds__(256) void nanminmax_pair_kernel(PairPtrs P, long long n, char* __restrict__ partials, int nb) {
-    const int k = blockIdx.y;
-    const float* __restrict__ a = P.in[k];
-    char* part = partials + (size_t)k * nb * 16;
-    float mn = INFINITY, mx = -INFINITY;
-    long long nv = 0;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float v = a[i];
-        if (v == v) {
-            mn = fminf(mn, v); mx = fmaxf(mx, v); ++nv;
-            if (!(v >= 0.f && v <= 65535.f && v == floorf(v))) nv += 1ll << 32;      // (see nanminmax_kernel)
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = fminf(mn, __shfl_down(mn, off));
-        mx = fmaxf(mx, __shfl_down(mx, off));
-        nv += __shfl_down(nv, off);
-    }
-    __shared__ float smn[4], smx[4];
-    __shared__ long long snv[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { smn[wave] = mn; smx[wave] = mx; snv[wave] = nv; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) { mn = fminf(mn, smn[w]); mx = fmaxf(mx, smx[w]); nv += snv[w]; }
-        ((float*)part)[blockIdx.x] = mn;
-        ((float*)part)[nb + blockIdx.x] = mx;
-        ((long long*)(part + (size_t)nb * 8))[blockIdx.x] = nv;
-    }
+    nanminmax_block(P.in[blockIdx.y], n, partials + (size_t)blockIdx.y * nb * 16, nb);
 }
 __global__ void rescale_pair_kernel(PairPtrs P, long long n) {
     const int k = blockIdx.y;
@@ -456,10 +383,7 @@ int mvs_device_nanminmax(MvsContext* c, const float* d_in, long long n, float* m
     const int nb = grid_for(n);
     char* scratch = (char*)mvs_scratch(c, 3, (size_t)nb * 16);
     if (!scratch) return mvs_alloc_failed(c);
-    float* pmin = (float*)scratch;
-    float* pmax = pmin + nb;
-    long long* pval = (long long*)(scratch + (size_t)nb * 8);
-    hipLaunchKernelGGL(nanminmax_kernel, dim3(nb), dim3(256), 0, c->stream, d_in, n, pmin, pmax, pval);
+    hipLaunchKernelGGL(nanminmax_kernel, dim3(nb), dim3(256), 0, c->stream, d_in, n, scratch, nb);
     MVS_HIP_TRY(c, hipGetLastError());
     std::vector<char> h((size_t)nb * 16);
     MVS_HIP_TRY(c, hipMemcpyAsync(h.data(), scratch, h.size(), hipMemcpyDeviceToHost, c->stream));

@@ -10,6 +10,7 @@
 //   quality = spearmanr(im0[mask], im1t[mask] - 1)                                  (scipy.stats)
 // Everything voxel-sized runs on the device; the host only sees counters, bounding boxes and sums.
 #include "mvs_internal.h"
+#include "mvs_fold_dev.h"
 #include "mvs_prune_search.h"
 #include "mvs_rank_plan.h"
 
@@ -35,31 +36,25 @@ struct Shape3 { int nz, ny, nx; };
 // #valid voxels + bounding box of the valid voxels (min z,y,x, max z,y,x)
 struct VoxStats { unsigned long long cnt; int bb[6]; };
 // nanmax / has-NaN of the moving image over the SSIM region, and the sum of the SSIM map over its cropped interior
-struct RegionStats { float mx; int hasnan; double ssim_sum; };
+struct RegionStats {
+    float mx; int hasnan; double ssim_sum;
+    __device__ __forceinline__ void merge(const RegionStats& o) { mx = fmaxf(mx, o.mx); hasnan |= o.hasnan; ssim_sum += o.ssim_sum; }
+    template <typename S> __device__ __forceinline__ RegionStats shuffled(S sh, int off) const { return {sh(mx, off), sh(hasnan, off), sh(ssim_sum, off)}; }
+};
+// the same without the sum
+struct MaxNan {
+    float mx; int hasnan;
+    __device__ __forceinline__ void merge(const MaxNan& o) { mx = fmaxf(mx, o.mx); hasnan |= o.hasnan; }
+    template <typename S> __device__ __forceinline__ MaxNan shuffled(S sh, int off) const { return {sh(mx, off), sh(hasnan, off)}; }
+};
+typedef mvs_fold::CountBox<unsigned long long> VoxBox;      // VoxStats as a partial: lo = bb[0..2], hi = bb[3..5]
 
 __device__ __forceinline__ void block_reduce_voxstats(unsigned long long cnt, int mnz, int mny, int mnx, int mxz, int mxy, int mxx,
                                                       VoxStats* __restrict__ out) {
-    for (int off = 32; off > 0; off >>= 1) {
-        cnt += __shfl_down(cnt, off);
-        mnz = min(mnz, __shfl_down(mnz, off)); mny = min(mny, __shfl_down(mny, off)); mnx = min(mnx, __shfl_down(mnx, off));
-        mxz = max(mxz, __shfl_down(mxz, off)); mxy = max(mxy, __shfl_down(mxy, off)); mxx = max(mxx, __shfl_down(mxx, off));
-    }
-    __shared__ unsigned long long s_cnt[4];
-    __shared__ int s_bb[4][6];
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_cnt[wave] = cnt;
-        s_bb[wave][0] = mnz; s_bb[wave][1] = mny; s_bb[wave][2] = mnx; s_bb[wave][3] = mxz; s_bb[wave][4] = mxy; s_bb[wave][5] = mxx;
-    }
-    __syncthreads();
+    const VoxBox b = mvs_fold::block_fold<4>(VoxBox{cnt, {mnz, mny, mnx}, {mxz, mxy, mxx}});
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) {
-            cnt += s_cnt[w];
-            mnz = min(mnz, s_bb[w][0]); mny = min(mny, s_bb[w][1]); mnx = min(mnx, s_bb[w][2]);
-            mxz = max(mxz, s_bb[w][3]); mxy = max(mxy, s_bb[w][4]); mxx = max(mxx, s_bb[w][5]);
-        }
-        out->cnt = cnt;
-        out->bb[0] = mnz; out->bb[1] = mny; out->bb[2] = mnx; out->bb[3] = mxz; out->bb[4] = mxy; out->bb[5] = mxx;
+        out->cnt = b.n;
+        for (int k = 0; k < 3; ++k) { out->bb[k] = b.lo[k]; out->bb[3 + k] = b.hi[k]; }
     }
 }
 
@@ -403,18 +398,10 @@ __device__ __forceinline__ void ssim_first_pass_body(const float* __restrict__ i
             if (kY) { P.dst[1][o] = f[1][k]; P.dst[3][o] = f[3][k]; P.dst[4][o] = f[4][k]; }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        mx = fmaxf(mx, __shfl_down(mx, off));
-        hn |= __shfl_down(hn, off);
-    }
-    __shared__ float s_mx[4];
-    __shared__ int s_hn[4];
-    if ((threadIdx.x & 63) == 0) { s_mx[threadIdx.x >> 6] = mx; s_hn[threadIdx.x >> 6] = hn; }
-    __syncthreads();
+    const MaxNan r = mvs_fold::block_fold<4>(MaxNan{mx, hn});
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) { mx = fmaxf(mx, s_mx[w]); hn |= s_hn[w]; }
-        pmax[blockIdx.x] = mx;
-        phasnan[blockIdx.x] = hn;
+        pmax[blockIdx.x] = r.mx;
+        phasnan[blockIdx.x] = r.hasnan;
     }
 }
 
@@ -484,11 +471,8 @@ __global__ __launch_bounds__(256) void ssim_last_pass_kernel(Five P, Shape3 R, i
             acc += (double)((A1 * A2) / (B1 * B2));
         }
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
-    __shared__ double s[4];
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+    acc = mvs_fold::block_fold<4>(mvs_fold::Sums<double>{{acc}}).v[0];
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
 // 3D: the y pass and the x pass + SSIM of one candidate in ONE kernel.  A workgroup takes a 32 x 56 tile of the cropped
@@ -565,6 +549,7 @@ __device__ __forceinline__ void ssim_yx_fused_body(Five P, Shape3 R, float cov_n
             __syncthreads();
         }
     }
+    // (not mvs_fold::block_fold: with it the WIN = 7 kernel needs 170 registers instead of 167 and loses a wave per SIMD)
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
     __shared__ double sred[4];
     if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = acc;
@@ -778,20 +763,10 @@ __device__ __forceinline__ void ssim_fused_batch_body(const float* __restrict__ 
         }
     }
     if (nanmask) hn = 1;
-    for (int off = 32; off > 0; off >>= 1) {
-        mx = fmaxf(mx, __shfl_down(mx, off));
-        hn |= __shfl_down(hn, off);
-        acc += __shfl_down(acc, off);
-    }
-    __shared__ float r_mx[4];
-    __shared__ int r_hn[4];
-    __shared__ double r_acc[4];
-    if ((tid & 63) == 0) { r_mx[tid >> 6] = mx; r_hn[tid >> 6] = hn; r_acc[tid >> 6] = acc; }
-    __syncthreads();
+    const RegionStats r = mvs_fold::block_fold<4>(RegionStats{mx, hn, acc});
     if (tid == 0) {
-        for (int w = 1; w < 4; ++w) { mx = fmaxf(mx, r_mx[w]); hn |= r_hn[w]; acc += r_acc[w]; }
         const size_t o = (size_t)blockIdx.y * kStatBlocks + blockIdx.x;
-        pmax[o] = mx; phasnan[o] = hn; psum[o] = acc;
+        pmax[o] = r.mx; phasnan[o] = r.hasnan; psum[o] = r.ssim_sum;
     }
 }
 
@@ -918,22 +893,10 @@ __global__ __launch_bounds__(256) void finish_region_kernel(const float* __restr
                                                             const double* __restrict__ psum, RegionStats* __restrict__ out,
                                                             int nblk = kStatBlocks) {
     const size_t o = (size_t)blockIdx.x * kStatBlocks;
-    float mx = -INFINITY;
-    int hn = 0;
-    double sum = 0.0;
-    for (int i = threadIdx.x; i < nblk; i += 256) { mx = fmaxf(mx, pmax[o + i]); hn |= phasnan[o + i]; sum += psum[o + i]; }
-    for (int off = 32; off > 0; off >>= 1) {
-        mx = fmaxf(mx, __shfl_down(mx, off)); hn |= __shfl_down(hn, off); sum += __shfl_down(sum, off);
-    }
-    __shared__ float s_mx[4];
-    __shared__ int s_hn[4];
-    __shared__ double s_sum[4];
-    if ((threadIdx.x & 63) == 0) { s_mx[threadIdx.x >> 6] = mx; s_hn[threadIdx.x >> 6] = hn; s_sum[threadIdx.x >> 6] = sum; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) { mx = fmaxf(mx, s_mx[w]); hn |= s_hn[w]; sum += s_sum[w]; }
-        out[blockIdx.x].mx = mx; out[blockIdx.x].hasnan = hn; out[blockIdx.x].ssim_sum = sum;
-    }
+    RegionStats r = {-INFINITY, 0, 0.0};
+    for (int i = threadIdx.x; i < nblk; i += 256) r.merge({pmax[o + i], phasnan[o + i], psum[o + i]});
+    r = mvs_fold::block_fold<4>(r);
+    if (threadIdx.x == 0) out[blockIdx.x] = r;
 }
 
 // ---- Spearman: compaction of the jointly valid voxels, two chained radix sorts, rank correlation ------------
@@ -1133,14 +1096,9 @@ __global__ __launch_bounds__(256) void rankcorr_kernel(const float* __restrict__
                 sxy += a * b; sxx += a * a; syy += b * b;
             }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        sxy += __shfl_down(sxy, off); sxx += __shfl_down(sxx, off); syy += __shfl_down(syy, off);
-    }
-    __shared__ double s[3][4];
-    if ((threadIdx.x & 63) == 0) { s[0][threadIdx.x >> 6] = sxy; s[1][threadIdx.x >> 6] = sxx; s[2][threadIdx.x >> 6] = syy; }
-    __syncthreads();
+    const mvs_fold::Sums<double, 3> s = mvs_fold::block_fold<4>(mvs_fold::Sums<double, 3>{{sxy, sxx, syy}});
     if (threadIdx.x == 0)
-        for (int k = 0; k < 3; ++k) partial[blockIdx.x * 3 + k] = s[k][0] + s[k][1] + s[k][2] + s[k][3];
+        for (int k = 0; k < 3; ++k) partial[blockIdx.x * 3 + k] = s.v[k];
 }
 
 // ---- Spearman by histogram ranks (integer-valued crops, shifts that are multiples of 1/2) -------------------------------
@@ -1221,11 +1179,8 @@ __global__ __launch_bounds__(CORR ? 256 : 1024) void hist_rank_kernel(const floa
         }
     }
     if (CORR) {
-        for (int off = 32; off > 0; off >>= 1) sxy += __shfl_down(sxy, off);
-        __shared__ double s[4];
-        if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = sxy;
-        __syncthreads();
-        if (threadIdx.x == 0) partial[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+        sxy = mvs_fold::block_fold<4>(mvs_fold::Sums<double>{{sxy}}).v[0];
+        if (threadIdx.x == 0) partial[blockIdx.x] = sxy;
     } else if (parts) {
         // the private histogram goes out whole (coalesced, no atomics); hist_fold_kernel adds the workgroups' parts
         __syncthreads();
