@@ -438,6 +438,27 @@ int mvs_score_candidates(int device, const float* fixed, const float* moving, in
                          int32_t region_mode, double data_range, double im1_min,
                          int32_t quality_for_all,
                          double* ssim_out, double* spearman_out, int32_t* code_out);
+/* mvs_score_candidates as mvs_register_crops calls it -- only the arg max is needed, so the pruned arg-max search (option
+ * "ssim_prune") and its float32 walk (option "ssim_f32") may run: the same launches -- that also hands out what the search knew
+ * about every candidate, for tests of the walk kernels and of the hand-over between them.  value_bound: the largest absolute value
+ * of the two (rescaled) crops (the search runs when 1e-2 max(1, (value_bound / data_range)^2) <= 0.05).  The rank correlation
+ * is evaluated for the best-SSIM candidate(s) only (quality_for_all = 0).  Per candidate with code_out 0:
+ * state_out: MVS_SCORE_COMPLETE = walked over its whole volume; MVS_SCORE_DROPPED = left unfinished, ssim_out then holds the
+ * bound its mean could not exceed (below the best mean); MVS_SCORE_REWALKED = walked again by the float64 kernel, ssim_out is that
+ * walk's mean.  ssim_rounds_out: the mean SSIM the candidate had when the rounds ended, before any re-walk (NaN unless complete).
+ * A call that does not take the pruned search reports MVS_SCORE_COMPLETE and ssim_rounds_out = ssim_out.  Candidates with another
+ * code report state 0 and NaN.  Both arrays are required (NULL: MVS_ERR_INVALID_ARG).  Option "ssim_f32" = 0 (default 1): the
+ * rounds of the search run in float64 and nothing is walked again; counter "reg_rewalks": candidates walked again in float64
+ * (each also counts one volume in "reg_cand_volumes"). */
+#define MVS_SCORE_COMPLETE 1
+#define MVS_SCORE_DROPPED 2
+#define MVS_SCORE_REWALKED 4
+int mvs_score_candidates_argmax(int device, const float* fixed, const float* moving, int32_t mem,
+                                int32_t ndim, const int64_t shape[3],
+                                const double* t_candidates, int32_t n_candidates,
+                                int32_t region_mode, double data_range, double im1_min, double value_bound,
+                                double* ssim_out, double* spearman_out, int32_t* code_out,
+                                double* ssim_rounds_out, int32_t* state_out);
 
 /* The whole of registration.phase_correlation_registration (registration.py:353-565) for two same-shape
  * float32 overlap crops (NaN = outside the view) in one call: intensity normalisation, the two phase

@@ -53,6 +53,7 @@ MVS_FEATHER_MAX_WIDTH = 32
 MVS_FEATHER_FULL_WEIGHT = 252
 MVS_MASKED_CORR_MAX_VOXELS = 1 << 28
 MVS_MASKED_CORR_OK, MVS_MASKED_CORR_NO_ELIGIBLE_SHIFT, MVS_MASKED_CORR_TOO_FEW_VALID, MVS_MASKED_CORR_CONSTANT_CROP = 0, 1, 2, 3
+MVS_SCORE_COMPLETE, MVS_SCORE_DROPPED, MVS_SCORE_REWALKED = 1, 2, 4      # state_out bits of mvs_score_candidates_argmax
 ERR_UNSUPPORTED = -4            # MVS_ERR_UNSUPPORTED
 
 DTYPE_CODES = {np.dtype(np.uint8): MVS_U8, np.dtype(np.uint16): MVS_U16, np.dtype(np.float32): MVS_F32}
@@ -327,6 +328,12 @@ SIGNATURES = {
         [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double),
          C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
          C.POINTER(C.c_int32)],
+    ),
+    "mvs_score_candidates_argmax": (
+        C.c_int,
+        [C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double),
+         C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+         C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32)],
     ),
     "mvs_affine_normal_eq": (
         C.c_int,

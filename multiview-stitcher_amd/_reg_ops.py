@@ -214,6 +214,34 @@ def score_candidates(im0, im1, t_candidates, region_mode, data_range, im1_min, d
     return ssim[inverse], spear[inverse], code[inverse]
 
 
+def score_candidates_argmax(im0, im1, t_candidates, region_mode, data_range, im1_min, value_bound, device=0):
+    """The candidate loop as ``register_crops`` runs it (mvs_score_candidates_argmax): only the arg max is needed, so the pruned
+    search and its float32 walk may run.  ``t_candidates``: distinct rows, scored in the given order.  Returns (ssim, spearman, code,
+    ssim_rounds, state): ``state`` holds the ``_lib.MVS_SCORE_*`` bits, ``ssim_rounds`` the mean SSIM of a complete candidate when
+    the rounds of the search ended (NaN for the others); a dropped candidate's ``ssim`` is the bound its mean could not exceed."""
+    lib = _lib.init(device)
+    shape = tuple(int(s) for s in im0.shape)
+    ndim = len(shape)
+    p0, m0, k0 = _ptr_mem(im0)
+    p1, m1, k1 = _ptr_mem(im1)
+    if m0 != m1:
+        raise TypeError("both images must live on the same side (host or device)")
+    t = np.ascontiguousarray(np.asarray(t_candidates, dtype=np.float64).reshape(-1, ndim))
+    n = t.shape[0]
+    if len(np.unique(t, axis=0)) != n:
+        raise ValueError("score_candidates_argmax: duplicate candidates")
+    ssim, spear, rounds = (np.empty(n, dtype=np.float64) for _ in range(3))
+    code, state = (np.empty(n, dtype=np.int32) for _ in range(2))
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    rc = lib.mvs_score_candidates_argmax(
+        device, p0, p1, m0, ndim, _lib.i64x3(shape3(shape)), t.ctypes.data_as(dp), n, {"union": 0, "intersection": 1}[region_mode],
+        float(data_range), float(im1_min), float(value_bound), ssim.ctypes.data_as(dp), spear.ctypes.data_as(dp), code.ctypes.data_as(ip),
+        rounds.ctypes.data_as(dp), state.ctypes.data_as(ip),
+    )
+    _lib.check(rc, device, "mvs_score_candidates_argmax")
+    return ssim, spear, code, rounds, state
+
+
 def bin_mean(data, bins, device=0, wait=True, out=None):
     """``coarsen(bins, boundary="trim").mean().astype(dtype)`` (registration.py:1732-1741) on the GPU.
     ``data``: numpy array or (strided) DeviceArray, spatial dims only; ``bins``: per-axis ints.  ``wait=False`` (device

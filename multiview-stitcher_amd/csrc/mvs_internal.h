@@ -128,6 +128,9 @@ struct MvsScoreOpts {
     double value_bound = INFINITY;     // ... with the largest absolute value of the two (rescaled) crops
     const float* raw_u16_keys[2] = {nullptr, nullptr};   // integer-valued originals of the two crops (16-bit rank keys), or NULL
     float raw_range[4] = {0.f, 0.f, 0.f, 0.f};           // with raw_u16_keys: min, max of the fixed crop, min, max of the moving crop
+    // mvs_score_candidates_argmax: per candidate, what the arg-max search knew (both NULL or both set; see include/mvs_hip.h)
+    double* ssim_rounds_out = nullptr;
+    int32_t* state_out = nullptr;
 };
 // Profiling builds only (-DMVS_PROFILING_ABLATIONS): a kernel whose tag is listed in the environment variable MVS_DUP_KERNELS is
 // launched twice (idempotent launches only: the second one rewrites the same results).  The difference in the pair loop's wall time

@@ -78,10 +78,15 @@ struct WalkGeom {
 // the open candidates when it turns out to be such a candidate.
 //
 // margin > 0: the rounds are walked in float32 and the complete candidates that end within `margin` (mean SSIM) of the best are
-// walked again in float64 when there are two or more of them.  A float32 window variance is off by <= a few 1e-7 (values
-// rescaled to [0, 1], sums restarted per segment) against C2 = 9e-4 in the denominator -- up to ~1e-3 of a voxel's value in flat
-// regions, far less in the mean over a crop; 1e-3 of the MEAN is the margin (kPruneMarginF32).  Candidates are dropped only
-// when their bound stays below the best sum by it.
+// walked again in float64 when there are two or more of them; candidates are dropped only when their bound stays below the best
+// sum by it.  The arg max is the reference's if the float32 MEAN of every candidate is within margin / 2 of its float64 value: a
+// dropped candidate was more than the margin below the best in float32, so it is below it in float64; so is a complete one that
+// is not walked again; and the arg max compares float64 sums of the re-walked with float32 sums of the others, which are more than
+// margin - margin / 2 apart.  A float32 window variance is off by a few 1e-7 (values rescaled to [0, 1], sums restarted per
+// segment) against C2 = 9e-4 in the denominator.  Measured against the oracle (tests/test_ssim_f32_walk_gpu.py, table in DESIGN.md
+// 3.3): the mean is off by +1.0e-4 to +1.25e-4 on a bright flat background (level 0.9-0.97 of the range, texture 0.005-0.02), the
+// same for z segments of 7, 13 and 24 planes, by 1e-6 on mid-level texture -- a quarter of the margin / 2 = 5e-4 that
+// kPruneMarginF32 = 1e-3 allows.  The search keeps the sum the rounds ended with (round_sum) next to the re-walk's.
 //
 // Use: while (s.next_round(masks)) { walk candidate j on the residue classes masks[j] (in float64 when s.rewalk()); s.take(...) }
 constexpr int kPruneMaxCand = 16;
@@ -101,7 +106,7 @@ public:
         for (int r = 0; r < 32; ++r) this->vol_res[r] = vol_res[r];
         for (int j = 0; j < kPruneMaxCand; ++j) {
             in[j] = j < n && takes_part[j];
-            acc[j] = 0.0; amx[j] = -INFINITY; ahn[j] = 0; done[j] = 0; masks[j] = 0; dropped[j] = false; again[j] = false; ub[j] = 0.0;
+            acc[j] = 0.0; amx[j] = -INFINITY; ahn[j] = 0; done[j] = 0; masks[j] = 0; dropped[j] = false; again[j] = false; ub[j] = 0.0; racc[j] = 0.0;
         }
     }
 
@@ -143,6 +148,7 @@ public:
     int hasnan(int j) const { return ahn[j]; }
     bool pruned(int j) const { return dropped[j]; }
     bool rewalked(int j) const { return again[j]; }
+    double round_sum(int j) const { return again[j] ? racc[j] : acc[j]; }      // the sum the rounds ended with (a re-walk replaces acc)
     double volume_fraction(int j) const { return vol_of(done[j]) / Ntot; }      // of the rounds (a re-walk is one more volume)
     // for the debug line
     int classes_done(int j) const { return __builtin_popcount(done[j]); }
@@ -156,7 +162,7 @@ private:
     unsigned int kAll;
     double vol_res[32], Ntot, slack, margin, im1_min;
     bool in[kPruneMaxCand], dropped[kPruneMaxCand], again[kPruneMaxCand];
-    double acc[kPruneMaxCand], ub[kPruneMaxCand];
+    double acc[kPruneMaxCand], ub[kPruneMaxCand], racc[kPruneMaxCand];
     float amx[kPruneMaxCand];
     int ahn[kPruneMaxCand];
     unsigned int done[kPruneMaxCand], masks[kPruneMaxCand];
@@ -226,7 +232,7 @@ private:
             again[j] = near_best(j);
             masks[j] = again[j] ? kAll : 0u;
         }
-        for (int j = 0; j < nb; ++j) if (again[j]) acc[j] = 0.0;
+        for (int j = 0; j < nb; ++j) if (again[j]) { racc[j] = acc[j]; acc[j] = 0.0; }
         return true;
     }
 };

@@ -1421,6 +1421,10 @@ struct ScoreBatch {
     bool any_batched;
     float cov_norm;
     RegionStats h_rs[kMaxResident];
+    // the pruned search's per-candidate state (score_pruned; MVS_SCORE_* bits of include/mvs_hip.h) and the sums its rounds ended with
+    bool searched = false;
+    int h_state[kMaxResident];
+    double h_round_sum[kMaxResident];
 };
 
 // The scratch request and its layout, term by term.  The terms marked (mailbox) have no take -- those results are written to the
@@ -1794,6 +1798,9 @@ int score_pruned(ScoreCall& sc, ScoreBatch& b, double slack) {
         b.h_rs[j].mx = search.maximum(j);
         b.h_rs[j].hasnan = search.hasnan(j);
         b.h_rs[j].ssim_sum = search.sum(j);
+        const bool complete = in[j] && search.volume_fraction(j) == 1.0;
+        b.h_state[j] = (complete ? MVS_SCORE_COMPLETE : 0) | (search.pruned(j) ? MVS_SCORE_DROPPED : 0) | (search.rewalked(j) ? MVS_SCORE_REWALKED : 0);
+        b.h_round_sum[j] = complete ? search.round_sum(j) : NAN;
         if (in[j]) {
             c->reg_cand_volumes += search.volume_fraction(j);
             c->reg_pruned += search.pruned(j) ? 1 : 0;
@@ -1821,6 +1828,7 @@ int score_batch(ScoreCall& sc, ScoreBatch& b, size_t n_todo) {
             const int rc = score_pruned(sc, b, slack);
             if (rc) return rc;
             have_rs = true;
+            b.searched = true;
         }
     } else if (b.any_batched) {
         score_two_pass(sc, b);
@@ -1861,6 +1869,14 @@ void decode_results(ScoreCall& sc, const ScoreBatch& b) {
             double cropn = 1.0;
             for (int k = sc.k0; k < 3; ++k) cropn *= (double)((&R.nz)[k] - 2 * pad);
             sc.ssim_out[ic] = b.h_rs[j].ssim_sum / cropn;
+            if (sc.so->state_out && b.searched) {
+                sc.so->state_out[ic] = b.h_state[j];
+                sc.so->ssim_rounds_out[ic] = b.h_round_sum[j] / cropn;
+            }
+        }
+        if (sc.so->state_out && !b.searched) {      // scored in full, in one piece (or no SSIM at all: -1)
+            sc.so->state_out[ic] = MVS_SCORE_COMPLETE;
+            sc.so->ssim_rounds_out[ic] = sc.ssim_out[ic];
         }
     }
 }
@@ -1987,6 +2003,26 @@ extern "C" int mvs_score_candidates(int device, const float* fixed, const float*
                                      quality_for_all, ssim_out, spearman_out, code_out, MvsScoreOpts{});
 }
 
+// mvs_score_candidates as mvs_register_crops calls it (arg max only: the pruned search may run), handing out the search's state
+extern "C" int mvs_score_candidates_argmax(int device, const float* fixed, const float* moving, int32_t mem, int32_t ndim,
+                                           const int64_t shape[3], const double* t_candidates, int32_t n_candidates,
+                                           int32_t region_mode, double data_range, double im1_min, double value_bound,
+                                           double* ssim_out, double* spearman_out, int32_t* code_out, double* ssim_rounds_out,
+                                           int32_t* state_out) {
+    if (!ssim_rounds_out || !state_out) {
+        MvsContext* c;
+        const int rc = mvs_check_ready(device, &c);
+        return rc ? rc : mvs_fail(c, MVS_ERR_INVALID_ARG, "mvs_score_candidates_argmax: NULL output");
+    }
+    MvsScoreOpts so;
+    so.argmax_only = true;
+    so.value_bound = value_bound;
+    so.ssim_rounds_out = ssim_rounds_out;
+    so.state_out = state_out;
+    return mvs_score_candidates_impl(device, fixed, moving, mem, ndim, shape, t_candidates, n_candidates, region_mode, data_range, im1_min, 0,
+                                     ssim_out, spearman_out, code_out, so);
+}
+
 int mvs_score_candidates_impl(int device, const float* fixed, const float* moving, int32_t mem, int32_t ndim, const int64_t shape[3],
                               const double* t_candidates, int32_t n_candidates, int32_t region_mode, double data_range, double im1_min,
                               int32_t quality_for_all, double* ssim_out, double* spearman_out, int32_t* code_out, const MvsScoreOpts& so) {
@@ -2043,6 +2079,7 @@ int mvs_score_candidates_impl(int device, const float* fixed, const float* movin
         ssim_out[ic] = -1.0;
         spearman_out[ic] = -1.0;
         code_out[ic] = 0;
+        if (so.state_out) { so.state_out[ic] = 0; so.ssim_rounds_out[ic] = NAN; }
         if (passes_pretest(sc, t)) todo.push_back(ic);
         else code_out[ic] = 1;
     }

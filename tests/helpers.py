@@ -245,6 +245,23 @@ def _pair_fractional(shape, shift, seed=0, sigma=0.8, noise=0.002):
     return a, b
 
 
+def _sparse_pair(shape, shift, seed, invert, blob_frac=0.25, noise=0.0):
+    """Zero background with one textured blob; the moving crop holds the same blob displaced by ``shift`` (optionally with
+    inverted contrast, which makes the aligned candidate score BELOW an all-background one)."""
+    rng = np.random.default_rng(seed)
+    a = np.zeros(shape, np.float32)
+    b = np.zeros(shape, np.float32)
+    ext = [max(8, int(n * blob_frac)) for n in shape]
+    lo = [int(n * 0.1) + 6 for n in shape]
+    blob = ndimage.gaussian_filter(rng.random(tuple(ext)), 1.0).astype(np.float32) + 0.5
+    a[tuple(slice(l, l + e) for l, e in zip(lo, ext))] = blob
+    blob_b = (blob.max() + 0.5 - blob) if invert else blob
+    if noise:
+        blob_b = blob_b + noise * rng.standard_normal(blob.shape).astype(np.float32)
+    b[tuple(slice(l - d, l - d + e) for l, d, e in zip(lo, shift, ext))] = np.maximum(blob_b, 0.05)
+    return a, b
+
+
 def _check_scores(a, b, t_cands, region_mode):
     """mvs_score_candidates against the oracle's candidate loop on rescaled inputs."""
     from multiview_stitcher_amd import _reg_ops

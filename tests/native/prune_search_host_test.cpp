@@ -142,6 +142,13 @@ static void run(const Case& C) {
         CHECK(s.maximum(j) == fmx[j] && s.hasnan(j) == fhn[j], "candidate %d: region statistics", j);
         const double want = full[s.rewalked(j) ? 1 : p][j];
         CHECK(s.sum(j) == want || (want != want && s.sum(j) != s.sum(j)), "candidate %d: sum %.17g, complete sum %.17g", j, s.sum(j), want);
+        // the sum the rounds ended with survives the re-walk: the float32 complete sum next to the float64 one that replaced it
+        if (s.rewalked(j)) {
+            CHECK(s.round_sum(j) == full[0][j], "candidate %d: kept round sum %.17g, float32 complete sum %.17g", j, s.round_sum(j), full[0][j]);
+            CHECK(s.sum(j) == full[1][j], "candidate %d: sum after the re-walk %.17g, float64 complete sum %.17g", j, s.sum(j), full[1][j]);
+        } else {
+            CHECK(s.round_sum(j) == s.sum(j) || (s.sum(j) != s.sum(j) && s.round_sum(j) != s.round_sum(j)), "candidate %d: round sum %.17g, sum %.17g", j, s.round_sum(j), s.sum(j));
+        }
         if (!((double)s.maximum(j) > C.im1_min) || !std::isfinite(s.sum(j))) continue;      // the reference's `continue` / no number
         if (winner < 0 || s.sum(j) > s.sum(winner)) winner = j;
     }

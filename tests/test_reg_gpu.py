@@ -4,7 +4,7 @@ import pytest
 from scipy import ndimage
 
 from oracle import reg_oracle as ro
-from tests.helpers import _check_scores, _pair
+from tests.helpers import _check_scores, _pair, _sparse_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -613,23 +613,6 @@ def test_pruned_argmax_search_equals_full_scoring(hip_device, shape, shift, nois
     if noise == 0.0:      # the wrong-sign candidates of a clean pair leave after the first round
         assert stats[1]["reg_pruned"] >= stats[1]["reg_candidates"] - 2, stats
         assert stats[1]["reg_cand_volumes"] < 0.4 * stats[1]["reg_candidates"], stats
-
-
-def _sparse_pair(shape, shift, seed, invert, blob_frac=0.25, noise=0.0):
-    """Zero background with one textured blob; the moving crop holds the same blob displaced by ``shift`` (optionally with
-    inverted contrast, which makes the aligned candidate score BELOW an all-background one)."""
-    rng = np.random.default_rng(seed)
-    a = np.zeros(shape, np.float32)
-    b = np.zeros(shape, np.float32)
-    ext = [max(8, int(n * blob_frac)) for n in shape]
-    lo = [int(n * 0.1) + 6 for n in shape]
-    blob = ndimage.gaussian_filter(rng.random(tuple(ext)), 1.0).astype(np.float32) + 0.5
-    a[tuple(slice(l, l + e) for l, e in zip(lo, ext))] = blob
-    blob_b = (blob.max() + 0.5 - blob) if invert else blob
-    if noise:
-        blob_b = blob_b + noise * rng.standard_normal(blob.shape).astype(np.float32)
-    b[tuple(slice(l - d, l - d + e) for l, d, e in zip(lo, shift, ext))] = np.maximum(blob_b, 0.05)
-    return a, b
 
 
 @pytest.mark.parametrize("shape,shift,invert,noise", [((40, 96, 120), (2, -3, 4), True, 0.0), ((40, 96, 120), (3, 4, 5), True, 0.0),
