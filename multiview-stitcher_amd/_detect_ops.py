@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from .device import DeviceArray, is_device_array
-from .transformation import shape3
+from ._operands import dense_operand, shape3
 
 # device bytes per voxel of a whole-field detection: the response and up to three work volumes of mvs_log_response (16), or the
 # response, two running maxima and a smoothed sample volume of mvs_local_maxima (16)
@@ -41,16 +41,6 @@ def fits_device(n_voxels, itemsize, on_host, device=0):
     return need <= 0.8 * free
 
 
-def _image_ptr(image, device):
-    if is_device_array(image):
-        if not image.is_contiguous():
-            raise TypeError("detection kernels need contiguous device arrays")
-        image.wait_ready(device)      # the lane that runs the kernels waits for an upload still in flight
-        return image.ptr, _lib.MVS_MEM_DEVICE, image
-    image = np.ascontiguousarray(image)
-    return image.ctypes.data, _lib.MVS_MEM_HOST, image
-
-
 def _filter(image, sigmas, with_second_order, scale, max_range, device):
     lib = _lib.init(device)
     shape = tuple(int(s) for s in image.shape)
@@ -67,7 +57,7 @@ def _filter(image, sigmas, with_second_order, scale, max_range, device):
     dp = C.POINTER(C.c_double)
     taps0 = np.ascontiguousarray(np.concatenate([t for _, t in tables]))
     taps2 = np.ascontiguousarray(np.concatenate([gaussian_taps(s, 2)[1] for s in sigmas])) if with_second_order else None
-    ptr, mem, keep = _image_ptr(image, device)
+    ptr, mem, keep = dense_operand(image, _lib.DTYPE_CODES, device, "detection kernels")
     out = DeviceArray.empty(shape, np.float32, device)
     mx = C.c_float()
     rng = None if max_range is None else (C.c_int64 * 2)(int(max_range[0]), int(max_range[1]))
@@ -97,25 +87,26 @@ def local_maxima(response, window, threshold, sample=None, sample_window=None, b
     ``sample_window`` lies below ``bound`` (mvs_local_maxima).  Returns an (n, ndim) int64 array in raster order.  The device
     list holds ``capacity`` entries; when there are more detections the call is repeated with a list that holds them all."""
     lib = _lib.init(device)
-    if not is_device_array(response) or response.dtype != np.float32 or not response.is_contiguous():
+    if not is_device_array(response):
         raise TypeError("local_maxima needs a contiguous float32 DeviceArray")
+    rptr, _, response = dense_operand(response, (np.float32,), device, "the response of local_maxima")
     shape = tuple(int(s) for s in response.shape)
     ndim = len(shape)
     pad = [1] * (3 - ndim)
     win = (C.c_int32 * 3)(*(pad + [int(w) for w in window]))
     sptr, sdtype, swin, bnd = None, _lib.MVS_F32, None, 0.0
     if sample is not None:
-        if not is_device_array(sample) or tuple(sample.shape) != shape or not sample.is_contiguous() or sample.dtype not in _lib.DTYPE_CODES:
+        if not is_device_array(sample) or tuple(sample.shape) != shape:
             raise TypeError("the sample volume must be a contiguous DeviceArray of the response's shape (uint8/uint16/float32)")
-        sample.wait_ready(device)
-        sptr, sdtype = C.c_void_p(sample.ptr), _lib.DTYPE_CODES[sample.dtype]
+        ptr, _, sample = dense_operand(sample, _lib.DTYPE_CODES, device, "the sample volume of local_maxima")
+        sptr, sdtype = C.c_void_p(ptr), _lib.DTYPE_CODES[sample.dtype]
         swin = (C.c_int32 * 3)(*(pad + [int(w) for w in sample_window]))
         bnd = float(bound)
     cap = 4096 if capacity is None else int(capacity)
     while True:
         buf = np.empty((max(cap, 1), 3), dtype=np.int32)
         count = C.c_int64()
-        rc = lib.mvs_local_maxima(device, C.c_void_p(response.ptr), ndim, _lib.i64x3(shape3(shape)), win, float(np.float32(threshold)), sptr,
+        rc = lib.mvs_local_maxima(device, C.c_void_p(rptr), ndim, _lib.i64x3(shape3(shape)), win, float(np.float32(threshold)), sptr,
                                   sdtype, swin, bnd, buf.ctypes.data_as(C.POINTER(C.c_int32)), cap, C.byref(count))
         _lib.check(rc, device, "mvs_local_maxima")
         if count.value <= cap:

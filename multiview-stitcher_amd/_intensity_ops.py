@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._metric_ops import box3, moments_in_groups, pair_call_views
-from .transformation import shape3, tile_view
+from ._operands import result_array, shape3, tile_view, written
 
 
 # ---- the cell rule (include/mvs_hip.h) ------------------------------------------------------------------------------------------
@@ -75,34 +75,20 @@ def apply_to_tile(name, data, out, out_dtype, device, call):
     """What ``apply_map`` and ``_shading_ops.apply_plane`` share: the result is of the data's kind and of ``out_dtype`` (the input's
     dtype, the default, or float32); ``out`` (allocated when None) is a contiguous array of the data's kind and shape and of
     ``out_dtype``.  ``call(view, out_ptr, out_dtype_code, out_mem)`` runs entry point ``name`` and returns its code."""
-    from .device import DeviceArray, is_device_array
+    from .device import is_device_array
 
     ndim = len(data.shape)
-    on_dev = is_device_array(data)
     in_dtype = np.dtype(data.dtype)
     if in_dtype not in _lib.DTYPE_CODES:
         raise TypeError(f"unsupported dtype {in_dtype} (uint8 / uint16 / float32)")
     out_dtype = in_dtype if out_dtype is None else np.dtype(out_dtype)
     if out_dtype not in (in_dtype, np.dtype(np.float32)):
         raise TypeError(f"out_dtype must be the input's dtype or float32, not {out_dtype}")
-    shape = tuple(int(s) for s in data.shape)
-    if out is None:
-        out = DeviceArray.empty(shape, out_dtype, device) if on_dev else np.empty(shape, dtype=out_dtype)
-    if is_device_array(out) != on_dev or tuple(out.shape) != shape or np.dtype(out.dtype) != out_dtype:
-        raise ValueError("out must be of the data's kind and shape and of out_dtype")
-    if not (out.is_contiguous() if on_dev else out.flags.c_contiguous):
-        raise ValueError("out must be contiguous")
+    out, out_ptr, out_mem = result_array(data.shape, out_dtype, is_device_array(data), device, out)
     view, keep = tile_view(data, np.eye(ndim), np.zeros(ndim), device)
-    if on_dev:
-        out.wait_ready(device)
-        out_ptr, out_mem = out.ptr, _lib.MVS_MEM_DEVICE
-    else:
-        out_ptr, out_mem = out.ctypes.data, _lib.MVS_MEM_HOST
     _lib.check(call(C.byref(view), C.c_void_p(out_ptr), _lib.DTYPE_CODES[out_dtype], out_mem), device, name)
-    if on_dev:
-        out.mark_written()
     del keep
-    return out
+    return written(out)
 
 
 def apply_map(data, coeff, out=None, out_dtype=None, device=0):

@@ -11,9 +11,10 @@ import numpy as np
 
 from . import _lib
 from .device import DeviceArray, is_device_array
-from .transformation import embed3, shape3
+from ._operands import fill_view_geometry, result_array, shape3, view_data, written
 
 INT32_MAX = 2**31 - 1
+_TILE_DTYPES = (np.dtype(np.int32),) + tuple(_lib.DTYPE_CODES)      # label tiles, and the image tiles of label_components
 COUNT_CAPACITY = 1 << 16        # first try of mvs_label_counts: labels 0 .. 65 535
 PAIR_CAPACITY = 1 << 16         # first try of mvs_label_pair_overlaps: a table of 2^17 slots (2 MiB)
 
@@ -58,26 +59,12 @@ def label_view(tile, matrix, offset, device):
     """``(mvs_view_t, array to keep alive)`` of a label tile from ``as_label_tile``; ``matrix`` / ``offset`` (None: the identity)
     map an index of the walked grid to a pixel of the tile.  The dtype field is not read by the label entries."""
     ndim = len(tile.shape)
-    if is_device_array(tile):
-        tile = tile.on_device(device)
-        tile.wait_ready(device)
-        ptr, st, mem = tile.ptr, [int(v) for v in tile.strides], _lib.MVS_MEM_DEVICE
-    else:
-        st = [int(np.prod(tile.shape[k + 1:])) for k in range(ndim)]
-        ptr, mem = tile.ctypes.data, _lib.MVS_MEM_HOST
-    s3 = shape3(tile.shape)
-    if ndim == 2:
-        st = [st[0] * s3[1], st[0], st[1]]
-    st[2] = 1          # (the stride of an axis of one voxel is arbitrary)
-    m3, o3 = embed3(np.eye(ndim) if matrix is None else np.asarray(matrix, dtype=np.float64),
-                    np.zeros(ndim) if offset is None else np.asarray(offset, dtype=np.float64))
+    ptr, s3, st3, mem, keep = view_data(tile, device, allow=_TILE_DTYPES)
+    st3[2] = 1          # (the stride of an axis of one voxel is arbitrary)
     view = _lib.mvs_view_t()
-    view.data, view.dtype, view.mem = ptr, 0, mem
-    view.shape[:] = s3
-    view.stride[:] = st
-    view.matrix[:] = m3.reshape(-1).tolist()
-    view.offset[:] = o3.tolist()
-    return view, tile
+    fill_view_geometry(view, ptr, 0, mem, s3, st3, np.eye(ndim) if matrix is None else np.asarray(matrix, dtype=np.float64),
+                       np.zeros(ndim) if offset is None else np.asarray(offset, dtype=np.float64))
+    return view, keep
 
 
 def label_counts(tile, device=0, capacity=None):
@@ -183,15 +170,11 @@ def fuse_label_tiles(tiles, matrices, offsets, luts, out_shape, index_origin=Non
         keep.append(dev_block)
         lut_ptrs = (C.c_void_p * len(tiles))(*[None if t is None else dev_block.ptr + 4 * s for t, s in zip(hosts, starts)])
         lut_lens = (C.c_int64 * len(tiles))(*[0 if t is None else t.size for t in hosts])
-    shape = tuple(int(s) for s in out_shape)
-    out = DeviceArray.empty(shape, np.int32, device) if out_on_device else np.empty(shape, dtype=np.int32)
-    ptr, mem = (out.ptr, _lib.MVS_MEM_DEVICE) if out_on_device else (out.ctypes.data, _lib.MVS_MEM_HOST)
-    _lib.check(lib.mvs_label_tiles_fuse(device, views, len(tiles), ndim, lut_ptrs, lut_lens, _lib.i64x3(shape3(shape)),
+    out, ptr, mem = result_array(out_shape, np.int32, out_on_device, device)
+    _lib.check(lib.mvs_label_tiles_fuse(device, views, len(tiles), ndim, lut_ptrs, lut_lens, _lib.i64x3(shape3(out_shape)),
                                         _lib.i64x3([0] * (3 - ndim) + origin), C.c_void_p(ptr), mem), device, "mvs_label_tiles_fuse")
-    if out_on_device:
-        out.mark_written()
     del keep
-    return out
+    return written(out)
 
 
 def as_image_tile(data, who="tile"):
@@ -232,14 +215,9 @@ def label_components(tile, threshold, connectivity=1, min_voxels=1, device=0, ou
     lib = _lib.init(device)
     view, keep = label_view(tile, None, None, device)
     view.dtype = _lib.DTYPE_CODES[np.dtype(tile.dtype)]
-    on_device = out_on_device or is_device_array(tile)
-    shape = tuple(int(s) for s in tile.shape)
-    out = DeviceArray.empty(shape, np.int32, device) if on_device else np.empty(shape, dtype=np.int32)
-    ptr, mem = (out.ptr, _lib.MVS_MEM_DEVICE) if on_device else (out.ctypes.data, _lib.MVS_MEM_HOST)
+    out, ptr, mem = result_array(tile.shape, np.int32, out_on_device or is_device_array(tile), device)
     n = C.c_int64()
     _lib.check(lib.mvs_label_components(device, C.byref(view), ndim, threshold, connectivity, max(min(min_voxels, 2**63 - 1), 0), C.c_void_p(ptr), mem,
                                         C.byref(n)), device, "mvs_label_components")
-    if on_device:
-        out.mark_written()
     del keep
-    return out, int(n.value)
+    return written(out), int(n.value)

@@ -9,6 +9,7 @@ import math
 import numpy as np
 
 from . import _lib
+from ._operands import dense_operand, result_array, written
 from .device import DeviceArray, is_device_array
 
 
@@ -20,26 +21,21 @@ def to_device(rows, device=0):
     return out
 
 
-def _rows(a, device, what):
+def _point_set(a, device, what):
     """(pointer, mem code, keep-alive, shape) of an (n, dim) float64 set."""
-    if is_device_array(a):
-        if a.dtype != np.float64 or a.ndim != 2 or not a.is_contiguous():
-            raise TypeError(f"{what}: device sets must be contiguous (n, dim) float64 arrays")
-        a.wait_ready(device)
-        return a.ptr, _lib.MVS_MEM_DEVICE, a, a.shape
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    if a.ndim != 2:
-        raise ValueError(f"{what}: expected an (n, dim) array")
-    return a.ctypes.data, _lib.MVS_MEM_HOST, a, a.shape
+    ptr, mem, a = dense_operand(a, (np.float64,), device, what, host_dtype=np.float64)
+    if len(a.shape) != 2:
+        raise (TypeError if is_device_array(a) else ValueError)(f"{what}: expected an (n, dim) array")
+    return ptr, mem, a, a.shape
 
 
 def knn(ref, query, k, device=0):
     """The ``k`` nearest rows of ``ref`` for every row of ``query`` (mvs_knn): ``(indices int32, distances float64)``, both
     (n_query, k), ascending by distance, equal distances by ascending index; with k > n_ref the tail is -1 / +inf.  ``dim``
     above 15 or ``k`` above 16 raise NotImplementedError: there is no CPU fallback."""
-    rp, rmem, rkeep, rshape = _rows(ref, device, "knn")
+    rp, rmem, rkeep, rshape = _point_set(ref, device, "knn")
     same = query is ref
-    qp, qmem, qkeep, qshape = (rp, rmem, rkeep, rshape) if same else _rows(query, device, "knn")
+    qp, qmem, qkeep, qshape = (rp, rmem, rkeep, rshape) if same else _point_set(query, device, "knn")
     if rshape[1] != qshape[1]:
         raise ValueError("knn: reference and query rows differ in length")
     dim, k = int(rshape[1]), int(k)
@@ -76,7 +72,7 @@ def descriptors(points, neighbors, num_neighbors, redundancy, device=0, out_on_d
     s-th subset in itertools.combinations order.  ``neighbors``: (n, required) indices of each point's nearest other points."""
     num_neighbors, redundancy = int(num_neighbors), int(redundancy)
     check_descriptor_params(num_neighbors, redundancy)
-    pp, pmem, pkeep, pshape = _rows(points, device, "descriptors")
+    pp, pmem, pkeep, pshape = _point_set(points, device, "descriptors")
     required = num_neighbors + redundancy
     neighbors = np.ascontiguousarray(neighbors, dtype=np.int32)
     if neighbors.shape != (pshape[0], required):
@@ -84,18 +80,11 @@ def descriptors(points, neighbors, num_neighbors, redundancy, device=0, out_on_d
     lib = _lib.init(device)
     rows = pshape[0] * math.comb(required, num_neighbors)
     length = math.comb(num_neighbors + 1, 2)
-    if out_on_device:
-        out = DeviceArray.empty((rows, length), np.float64, device)
-        optr, omem = out.ptr, _lib.MVS_MEM_DEVICE
-    else:
-        out = np.empty((rows, length), dtype=np.float64)
-        optr, omem = out.ctypes.data, _lib.MVS_MEM_HOST
+    out, optr, omem = result_array((rows, length), np.float64, out_on_device, device)
     rc = lib.mvs_marker_descriptors(device, C.c_void_p(pp), pmem, pshape[0], int(pshape[1]), neighbors.ctypes.data_as(C.POINTER(C.c_int32)),
                                     num_neighbors, redundancy, C.c_void_p(optr), omem)
     _lib.check(rc, device, "mvs_marker_descriptors")
-    if out_on_device:
-        out.mark_written()
-    return out
+    return written(out)
 
 
 def score(affines, fixed, moving, max_error, device=0):

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from .device import DeviceArray, is_device_array
-from .transformation import fill_view_geometry, shape3, tile_view, view_data
+from ._operands import dense_operand, fill_view_geometry, result_array, shape3, tile_view, view_data, written
 
 
 def check_n_bins(n_bins):
@@ -139,14 +139,10 @@ def feather(mask, width, device=0, out_on_device=False):
         raise TypeError(f"masks are uint8, not {mask.dtype}")
     lib = _lib.init(device)
     view, keep = tile_view(mask, np.eye(ndim), np.zeros(ndim), device)
-    shape = tuple(int(s) for s in mask.shape)
-    out = DeviceArray.empty(shape, np.uint8, device) if out_on_device else np.empty(shape, dtype=np.uint8)
-    ptr, mem = (out.ptr, _lib.MVS_MEM_DEVICE) if out_on_device else (out.ctypes.data, _lib.MVS_MEM_HOST)
+    out, ptr, mem = result_array(mask.shape, np.uint8, out_on_device, device)
     _lib.check(lib.mvs_mask_feather(device, C.byref(view), ndim, _lib.i32x3(width, ndim, 1), C.c_void_p(ptr), mem), device, "mvs_mask_feather")
-    if out_on_device:
-        out.mark_written()
     del keep
-    return out
+    return written(out)
 
 
 def fuse_labels(masks, matrices, offsets, out_shape, device=0, out_on_device=False):
@@ -165,14 +161,10 @@ def fuse_labels(masks, matrices, offsets, out_shape, device=0, out_on_device=Fal
         ptr, s3, st3, mem, kept = view_data(mask, device)
         fill_view_geometry(view, ptr, _lib.MVS_U8, mem, s3, st3, matrix, offset)
         keep.append(kept)
-    shape = tuple(int(s) for s in out_shape)
-    out = DeviceArray.empty(shape, np.int32, device) if out_on_device else np.empty(shape, dtype=np.int32)
-    ptr, mem = (out.ptr, _lib.MVS_MEM_DEVICE) if out_on_device else (out.ctypes.data, _lib.MVS_MEM_HOST)
-    _lib.check(lib.mvs_label_fuse(device, views, len(masks), ndim, _lib.i64x3(shape3(shape)), C.c_void_p(ptr), mem), device, "mvs_label_fuse")
-    if out_on_device:
-        out.mark_written()
+    out, ptr, mem = result_array(out_shape, np.int32, out_on_device, device)
+    _lib.check(lib.mvs_label_fuse(device, views, len(masks), ndim, _lib.i64x3(shape3(out_shape)), C.c_void_p(ptr), mem), device, "mvs_label_fuse")
     del keep
-    return out
+    return written(out)
 
 
 def label_contacts(labels, n_labels, connectivity=None, device=0):
@@ -190,17 +182,12 @@ def label_contacts(labels, n_labels, connectivity=None, device=0):
     if np.dtype(labels.dtype) != np.int32:
         raise TypeError(f"label volumes are int32, not {labels.dtype}")
     lib = _lib.init(device)
-    if is_device_array(labels):
-        if not labels.is_contiguous():
-            raise TypeError("mvs_label_contacts needs a contiguous device array")
-        labels = labels.on_device(device)
-        labels.wait_ready(device)
-        dev = labels
-    else:
+    if not is_device_array(labels):
         host = np.ascontiguousarray(labels)
-        dev = DeviceArray.empty(host.shape, np.int32, device)
-        _lib.check(lib.mvs_memcpy_h2d(device, dev.ptr, host.ctypes.data, host.nbytes), device, "h2d")
+        labels = DeviceArray.empty(host.shape, np.int32, device)
+        _lib.check(lib.mvs_memcpy_h2d(device, labels.ptr, host.ctypes.data, host.nbytes), device, "h2d")
+    ptr, _, keep = dense_operand(labels, (np.int32,), device, "mvs_label_contacts")
     counts = np.zeros((n_labels, n_labels), dtype=np.uint64)
-    _lib.check(lib.mvs_label_contacts(device, C.c_void_p(dev.ptr), ndim, _lib.i64x3(shape3(labels.shape)), n_labels, connectivity,
+    _lib.check(lib.mvs_label_contacts(device, C.c_void_p(ptr), ndim, _lib.i64x3(shape3(labels.shape)), n_labels, connectivity,
                                       counts.ctypes.data_as(C.POINTER(C.c_uint64))), device, "mvs_label_contacts")
     return counts

@@ -8,8 +8,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._operands import operand_pair, shape3
 from .device import is_device_array
-from .transformation import shape3
 
 STATUS_MESSAGES = {
     _lib.MVS_MASKED_CORR_NO_ELIGIBLE_SHIFT: "no shift of the window has enough overlap and a positive variance in both crops",
@@ -71,29 +71,12 @@ def subpixel_offset(centre, left, right, left_ok=True, right_ok=True):
     return float(min(max(0.5 * (l - r) / curvature, -0.5), 0.5))
 
 
-def _crop(a, device):
-    if is_device_array(a):
-        if not a.is_contiguous() or a.dtype != np.float32:
-            raise TypeError("masked correlation needs contiguous float32 device arrays")
-        a = a.on_device(device)
-        a.wait_ready(device)
-        return a.ptr, _lib.MVS_MEM_DEVICE, a
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    return a.ctypes.data, _lib.MVS_MEM_HOST, a
-
-
-def _mask(m, device):
-    if m is None:
-        return None, None, None
-    if is_device_array(m):
-        if not m.is_contiguous() or m.dtype != np.uint8:
-            raise TypeError("masks in device memory must be contiguous uint8 arrays")
-        m = m.on_device(device)
-        m.wait_ready(device)
-        return m.ptr, _lib.MVS_MEM_DEVICE, m
+def _host_mask_as_uint8(m):
+    """A host mask (anything numpy turns into booleans) as uint8; None and DeviceArrays pass through."""
+    if m is None or is_device_array(m):
+        return m
     m = np.asarray(m)
-    m = np.ascontiguousarray(m if m.dtype == np.uint8 else m != 0, dtype=np.uint8)
-    return m.ctypes.data, _lib.MVS_MEM_HOST, m
+    return m if m.dtype == np.uint8 else (m != 0).astype(np.uint8)
 
 
 def masked_corr(fixed, moving, fixed_mask=None, moving_mask=None, valid_above=(None, None), overlap_ratio=0.3, min_overlap=1, shifts=None,
@@ -117,19 +100,14 @@ def masked_corr(fixed, moving, fixed_mask=None, moving_mask=None, valid_above=(N
     for m, name in ((fixed_mask, "fixed_mask"), (moving_mask, "moving_mask")):
         if m is not None and tuple(int(s) for s in m.shape) != shape:
             raise ValueError(f"{name} has shape {tuple(m.shape)}, the crops have {shape}")
-    if is_device_array(fixed) != is_device_array(moving):
-        raise TypeError("both crops must live on the same side (host or device)")
-    if fixed_mask is not None and moving_mask is not None and is_device_array(fixed_mask) != is_device_array(moving_mask):
-        raise TypeError("both masks must live on the same side (host or device)")
+    p0, p1, mem, keep = operand_pair(fixed, moving, (np.float32,), device, "masked correlation", host_dtype=np.float32, names="crops")
+    q0, q1, mask_mem, mask_keep = operand_pair(_host_mask_as_uint8(fixed_mask), _host_mask_as_uint8(moving_mask), (np.uint8,), device,
+                                               "masked correlation", names="masks")
     lib = _lib.init(device)
-    p0, mem0, keep0 = _crop(fixed, device)
-    p1, mem1, keep1 = _crop(moving, device)
-    q0, mmem0, mkeep0 = _mask(fixed_mask, device)
-    q1, mmem1, mkeep1 = _mask(moving_mask, device)
     opts = _lib.mvs_masked_corr_opts_t()
     opts.ndim = ndim
-    opts.mem = mem0
-    opts.mask_mem = next((m for m in (mmem0, mmem1) if m is not None), _lib.MVS_MEM_HOST)
+    opts.mem = mem
+    opts.mask_mem = mask_mem
     for k, thr in enumerate(valid_above):
         opts.has_valid_above[k] = 0 if thr is None else 1
         opts.valid_above[k] = 0.0 if thr is None else float(thr)
@@ -144,7 +122,7 @@ def masked_corr(fixed, moving, fixed_mask=None, moving_mask=None, valid_above=(N
     _lib.check(lib.mvs_masked_corr(device, p0, p1, q0, q1, _lib.i64x3(shape3(shape)), C.byref(opts), C.byref(res),
                                    r_vol.ctypes.data if want_volumes else None, n_vol.ctypes.data if want_volumes else None),
                device, "mvs_masked_corr")
-    del keep0, keep1, mkeep0, mkeep1
+    del keep, mask_keep
     k = 3 - ndim
     out = {
         "status": int(res.status),

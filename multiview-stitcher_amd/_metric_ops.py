@@ -9,7 +9,7 @@ import math
 import numpy as np
 
 from . import _lib
-from .transformation import embed3, shape3, tile_view
+from ._operands import embed3, shape3, tile_view
 
 _DP = C.POINTER(C.c_double)
 

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .transformation import tile_view
+from ._operands import tile_view
 
 STATUS_USED, STATUS_OUTSIDE, STATUS_EMPTY = 0, 1, 2      # status_out of mvs_psf_extract
 

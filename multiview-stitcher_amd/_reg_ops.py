@@ -7,35 +7,28 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .device import DeviceArray, is_device_array
-from .transformation import shape3, view_data
+from ._operands import dense_operand, fill_view_geometry, operand_pair, result_array, shape3, view_data, written
+from .device import is_device_array
+
+_F32 = (np.float32,)
 
 
-def _ptr_mem(a):
-    if is_device_array(a):
-        if not a.is_contiguous() or a.dtype != np.float32:
-            raise TypeError("registration kernels need contiguous float32 device arrays")
-        return a.ptr, _lib.MVS_MEM_DEVICE, a
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    return a.ctypes.data, _lib.MVS_MEM_HOST, a
+def _crop_pair(a, b, device, names="images"):
+    """The two float32 crops of one call: ``(pointer a, pointer b, mem, what keeps them alive)``."""
+    return operand_pair(a, b, _F32, device, "registration kernels", host_dtype=np.float32, names=names)
 
 
 def rescale_intensity(im, device=0, out_on_device=False):
     """skimage.exposure.rescale_intensity(im, in_range=(nanmin, nanmax), out_range=(0, 1)) on the GPU.
     Returns (rescaled float32, nanmin, nanmax, n_valid)."""
     lib = _lib.init(device)
-    ptr, mem, keep = _ptr_mem(im)
+    ptr, mem, keep = dense_operand(im, _F32, device, "registration kernels", host_dtype=np.float32)
     n = int(np.prod(im.shape))
     mn, mx, nv = C.c_float(), C.c_float(), C.c_int64()
-    if out_on_device:
-        out = DeviceArray.empty(im.shape, np.float32, device)
-        optr, omem = out.ptr, _lib.MVS_MEM_DEVICE
-    else:
-        out = np.empty(im.shape, dtype=np.float32)
-        optr, omem = out.ctypes.data, _lib.MVS_MEM_HOST
+    out, optr, omem = result_array(im.shape, np.float32, out_on_device, device)
     rc = lib.mvs_rescale_intensity(device, ptr, mem, n, optr, omem, C.byref(mn), C.byref(mx), C.byref(nv))
     _lib.check(rc, device, "mvs_rescale_intensity")
-    return out, float(mn.value), float(mx.value), int(nv.value)
+    return written(out), float(mn.value), float(mx.value), int(nv.value)
 
 
 def phase_cross_correlation(reference_image, moving_image, upsample_factor=1, normalization="phase", device=0,
@@ -49,10 +42,7 @@ def phase_cross_correlation(reference_image, moving_image, upsample_factor=1, no
         raise ValueError("normalization must be either phase or None")
     shape = tuple(int(s) for s in reference_image.shape)
     ndim = len(shape)
-    p0, m0, k0 = _ptr_mem(reference_image)
-    p1, m1, k1 = _ptr_mem(moving_image)
-    if m0 != m1:
-        raise TypeError("both images must live on the same side (host or device)")
+    p0, p1, m0, keep = _crop_pair(reference_image, moving_image, device)
     shift = (C.c_double * 3)()
     peak = (C.c_int64 * 3)()
     pabs = C.c_float()
@@ -89,10 +79,7 @@ def phase_cross_correlation_multi(reference_image, moving_image, upsample_factor
             raise ValueError("normalization must be either phase or None")
     shape = tuple(int(s) for s in reference_image.shape)
     ndim = len(shape)
-    p0, m0, k0 = _ptr_mem(reference_image)
-    p1, m1, k1 = _ptr_mem(moving_image)
-    if m0 != m1:
-        raise TypeError("both images must live on the same side (host or device)")
+    p0, p1, m0, keep = _crop_pair(reference_image, moving_image, device)
     nn = len(normalizations)
     norms = (C.c_int32 * nn)(*[1 if v == "phase" else 0 for v in normalizations])
     shift = (C.c_double * (3 * nn))()
@@ -127,10 +114,7 @@ def register_crops(im0, im1, upsample_factor, region_mode=None, constant_check=F
     lib = _lib.init(device)
     shape = tuple(int(s) for s in im0.shape)
     ndim = len(shape)
-    p0, m0, k0 = _ptr_mem(im0)
-    p1, m1, k1 = _ptr_mem(im1)
-    if m0 != m1:
-        raise TypeError("both images must live on the same side (host or device)")
+    p0, p1, m0, keep = _crop_pair(im0, im1, device)
     t = (C.c_double * 3)()
     q = C.c_double()
     status = C.c_int32()
@@ -147,30 +131,16 @@ def register_views(data0, matrix0, offset0, data1, matrix1, offset1, out_shape, 
     """Resample both overlap crops and register them in one library call (mvs_register_views).  ``data*``: DeviceArray slabs
     (strided windows allowed), ``matrix*`` (diagonal given as a list) / ``offset*``: the pixel affines of
     transformation.get_pixel_affine, ``out_shape``: the fixed view's overlap grid.  Returns like ``register_crops``."""
-    from .transformation import shape3
-
     lib = _lib.init(device)
     ndim = len(out_shape)
     views = (_lib.mvs_view_t * 2)()
+    keep = []
     for v, data, mdiag, off in ((views[0], data0, matrix0, offset0), (views[1], data1, matrix1, offset1)):
         if not is_device_array(data) or data.dtype not in _lib.DTYPE_CODES:
             raise TypeError("register_views needs DeviceArray slabs of a supported dtype")
-        k = 3 - ndim
-        m = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]
-        o = [0.0, 0.0, 0.0]
-        for a in range(ndim):
-            m[(k + a) * 4] = float(mdiag[a])
-            o[k + a] = float(off[a])
-        shp, st = [int(x) for x in data.shape], [int(x) for x in data.strides]
-        if ndim == 2:
-            shp, st = [1] + shp, [st[0] * shp[0]] + st
-        v.data = data.ptr
-        v.dtype = _lib.DTYPE_CODES[data.dtype]
-        v.mem = _lib.MVS_MEM_DEVICE
-        v.shape[:] = shp
-        v.stride[:] = st
-        v.matrix[:] = m
-        v.offset[:] = o
+        ptr, s3, st3, mem, kept = view_data(data, device)
+        fill_view_geometry(v, ptr, _lib.DTYPE_CODES[kept.dtype], mem, s3, st3, np.diag([float(m) for m in mdiag]), [float(o) for o in off])
+        keep.append(kept)
     t = (C.c_double * 3)()
     q = C.c_double()
     status = C.c_int32()
@@ -190,10 +160,7 @@ def score_candidates(im0, im1, t_candidates, region_mode, data_range, im1_min, d
     lib = _lib.init(device)
     shape = tuple(int(s) for s in im0.shape)
     ndim = len(shape)
-    p0, m0, k0 = _ptr_mem(im0)
-    p1, m1, k1 = _ptr_mem(im1)
-    if m0 != m1:
-        raise TypeError("both images must live on the same side (host or device)")
+    p0, p1, m0, keep = _crop_pair(im0, im1, device)
     t_all = np.asarray(t_candidates, dtype=np.float64).reshape(-1, ndim)
     # both phase-correlation variants usually agree, so the enumeration holds exact duplicates; scoring is a
     # pure function of t: evaluate each distinct vector once and scatter (list order / nanargmax unchanged)
@@ -222,10 +189,7 @@ def score_candidates_argmax(im0, im1, t_candidates, region_mode, data_range, im1
     lib = _lib.init(device)
     shape = tuple(int(s) for s in im0.shape)
     ndim = len(shape)
-    p0, m0, k0 = _ptr_mem(im0)
-    p1, m1, k1 = _ptr_mem(im1)
-    if m0 != m1:
-        raise TypeError("both images must live on the same side (host or device)")
+    p0, p1, m0, keep = _crop_pair(im0, im1, device)
     t = np.ascontiguousarray(np.asarray(t_candidates, dtype=np.float64).reshape(-1, ndim))
     n = t.shape[0]
     if len(np.unique(t, axis=0)) != n:
@@ -255,46 +219,33 @@ def bin_mean(data, bins, device=0, wait=True, out=None):
     dtype = np.dtype(data.dtype)
     if dtype not in _lib.DTYPE_CODES:
         raise TypeError(f"unsupported dtype {dtype}")
+    on_dev = is_device_array(data)
     ptr, s3, st3, mem, data = view_data(data, device, wait=False)
-    if mem == _lib.MVS_MEM_DEVICE:
-        if out is None:
-            out = DeviceArray.empty(oshape, dtype, device)
-        elif tuple(out.shape) != tuple(oshape) or out.dtype != dtype or not out.is_contiguous():
-            raise ValueError("bin_mean: out must be a contiguous DeviceArray of the binned shape and the input dtype")
-        optr, omem = out.ptr, _lib.MVS_MEM_DEVICE
-    else:
-        out = np.empty(oshape, dtype=dtype)
-        optr, omem = out.ctypes.data, _lib.MVS_MEM_HOST
+    out, optr, omem = result_array(oshape, dtype, on_dev, device, out if on_dev else None, "bin_mean: out")
     b3 = [1] * (3 - nd) + bins
-    if not wait and mem == _lib.MVS_MEM_DEVICE:
+    if not wait and on_dev:
         rc = lib.mvs_bin_mean_async(device, ptr, _lib.DTYPE_CODES[dtype], _lib.i64x3(s3), _lib.i64x3(st3), _lib.i64x3(b3), optr)
         _lib.check(rc, device, "mvs_bin_mean_async")
-        out.mark_written()
-        return out
+        return written(out)
     rc = lib.mvs_bin_mean(device, ptr, _lib.DTYPE_CODES[dtype], mem, _lib.i64x3(s3), _lib.i64x3(st3), _lib.i64x3(b3), optr, omem)
     _lib.check(rc, device, "mvs_bin_mean")
-    if is_device_array(out):
-        out.mark_written()
-    return out
+    return written(out)
 
 
-def _pose_geometry(fixed, moving, A, t):
+def _pose_geometry(fixed, moving, A, t, device):
     """The arguments the affine entry points share -- crop pointers, mem, ndim, shape, the pose ``(A, t)`` embedded into 3 x 3 / 3
     -- and the objects that keep them alive during the call."""
     shape = tuple(int(s) for s in fixed.shape)
     if tuple(moving.shape) != shape:
         raise ValueError("crops must have the same shape")
     ndim = len(shape)
-    p0, m0, k0 = _ptr_mem(fixed)
-    p1, m1, k1 = _ptr_mem(moving)
-    if m0 != m1:
-        raise TypeError("both crops must live on the same side (host or device)")
+    p0, p1, m0, keep = _crop_pair(fixed, moving, device, names="crops")
     A3 = np.eye(3)
     A3[3 - ndim:, 3 - ndim:] = np.asarray(A, dtype=np.float64).reshape(ndim, ndim)
     t3 = np.zeros(3)
     t3[3 - ndim:] = np.asarray(t, dtype=np.float64).reshape(ndim)
     dp = C.POINTER(C.c_double)
-    return (p0, p1, m0, ndim, _lib.i64x3(shape3(shape)), A3.ctypes.data_as(dp), t3.ctypes.data_as(dp)), (k0, k1, A3, t3)
+    return (p0, p1, m0, ndim, _lib.i64x3(shape3(shape)), A3.ctypes.data_as(dp), t3.ctypes.data_as(dp)), (keep, A3, t3)
 
 
 def affine_normal_equations(fixed, moving, A, t, gain=1.0, bias=0.0, device=0):
@@ -303,7 +254,7 @@ def affine_normal_equations(fixed, moving, A, t, gain=1.0, bias=0.0, device=0):
     voxel x samples moving at ``c + t + A (x - c)``.  Returns (H (P, P), b (P,), sum r^2, n valid, (sum v, sum F, sum vF,
     sum v^2, sum F^2)) with P = ndim (ndim + 1) and the parameters ordered as the rows of ``[A | t]``."""
     lib = _lib.init(device)
-    geom, keep = _pose_geometry(fixed, moving, A, t)
+    geom, keep = _pose_geometry(fixed, moving, A, t, device)
     ndim = geom[3]
     out = np.empty(_lib.MVS_AFFINE_NEQ_LEN, dtype=np.float64)
     rc = lib.mvs_affine_normal_eq(device, *geom, float(gain), float(bias), out.ctypes.data_as(C.POINTER(C.c_double)))
@@ -318,7 +269,7 @@ def affine_normal_equations(fixed, moving, A, t, gain=1.0, bias=0.0, device=0):
 def finite_range(a, device=0):
     """(minimum, maximum, count) of the finite values of a float32 crop (mvs_finite_range); NaN, NaN, 0 when it has none."""
     lib = _lib.init(device)
-    ptr, mem, keep = _ptr_mem(a)
+    ptr, mem, keep = dense_operand(a, _F32, device, "registration kernels", host_dtype=np.float32)
     mn, mx, nv = C.c_float(), C.c_float(), C.c_int64()
     rc = lib.mvs_finite_range(device, ptr, mem, int(np.prod(a.shape)), C.byref(mn), C.byref(mx), C.byref(nv))
     _lib.check(rc, device, "mvs_finite_range")
@@ -330,7 +281,7 @@ def affine_joint_hist(fixed, moving, A, t, n_bins, ranges, device=0):
     ``affine_normal_equations``; ``ranges`` = (f_lo, f_scale, m_lo, m_scale).  Returns (hist (B, B) int64: rows = fixed bin,
     columns = moving bin, in units of 2^-20 sample; n valid)."""
     lib = _lib.init(device)
-    geom, keep = _pose_geometry(fixed, moving, A, t)
+    geom, keep = _pose_geometry(fixed, moving, A, t, device)
     hist = np.empty((int(n_bins), int(n_bins)), dtype=np.int64)
     n = C.c_int64()
     rc = lib.mvs_affine_joint_hist(device, *geom, int(n_bins), *[float(v) for v in ranges], hist.ctypes.data_as(C.POINTER(C.c_int64)),
@@ -343,7 +294,7 @@ def affine_mi_gradient(fixed, moving, A, t, n_bins, ranges, table, device=0):
     """Gradient sums of the Mattes metric (mvs_affine_mi_gradient); ``table``: (B, B) L[a][b], passed as float32.  Returns
     (sums (P,) in the order of the rows of ``[A | t]``, n valid); d MI / d theta = (m_scale / n) * sums."""
     lib = _lib.init(device)
-    geom, keep = _pose_geometry(fixed, moving, A, t)
+    geom, keep = _pose_geometry(fixed, moving, A, t, device)
     tab = np.ascontiguousarray(table, dtype=np.float32)
     if tab.shape != (int(n_bins), int(n_bins)):
         raise ValueError("table must be n_bins x n_bins")

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from ._intensity_ops import apply_to_tile
-from .transformation import fill_view_geometry, shape3, view_data
+from ._operands import dense_operand, fill_view_geometry, shape3, view_data
 
 
 # ---- the rank rule (include/mvs_hip.h) --------------------------------------------------------------------------------------------
@@ -100,18 +100,9 @@ def apply_plane(data, coeff, out=None, out_dtype=None, device=0):
     per pixel, a numpy array or a contiguous ``DeviceArray`` (callers that correct many tiles upload it once).  ``data``, ``out``
     and ``out_dtype`` as in ``_intensity_ops.apply_map``: the result is of the data's kind, of the input's dtype (the default) or
     float32; ``out is data`` corrects a contiguous array in place."""
-    from .device import is_device_array
-
     lib = _lib.init(device)
     ndim = len(data.shape)
-    if is_device_array(coeff):
-        if np.dtype(coeff.dtype) != np.float32 or not coeff.is_contiguous():
-            raise ValueError("resident coefficients must be a contiguous float32 array")
-        coeff.wait_ready(device)
-        coeff_ptr, coeff_mem = coeff.ptr, _lib.MVS_MEM_DEVICE
-    else:
-        coeff = np.ascontiguousarray(coeff, dtype=np.float32)
-        coeff_ptr, coeff_mem = coeff.ctypes.data, _lib.MVS_MEM_HOST
+    coeff_ptr, coeff_mem, coeff = dense_operand(coeff, (np.float32,), device, "the coefficients of apply_plane", host_dtype=np.float32, error=ValueError)
     if ndim not in (2, 3) or tuple(coeff.shape) != tuple(int(s) for s in data.shape[-2:]) + (2,):
         raise ValueError("apply_plane needs a 2-D or 3-D tile and coefficients of shape (H, W, 2)")
     return apply_to_tile("mvs_plane_apply", data, out, out_dtype, device, lambda view, out_ptr, out_code, out_mem: lib.mvs_plane_apply(

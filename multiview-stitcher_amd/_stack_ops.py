@@ -7,6 +7,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
+from ._operands import dense_operand, result_array, written
 from .device import DeviceArray, is_device_array
 
 
@@ -30,11 +31,8 @@ def stack_inputs(name, transformed_views, blending_weights, device):
     if is_device_array(transformed_views):
         if not is_device_array(blending_weights):
             blending_weights = DeviceArray.from_host(np.ascontiguousarray(blending_weights, dtype=np.float32), device)
-        for a in (transformed_views, blending_weights):
-            if a.dtype != np.float32 or not a.is_contiguous():
-                raise TypeError(f"device inputs of {name} are contiguous float32 DeviceArrays")
-            a.wait_ready(device)
-        return transformed_views, blending_weights, ndim, np.dtype(np.float32), True, None
+        views, weights = (dense_operand(a, (np.float32,), device, f"device inputs of {name}")[2] for a in (transformed_views, blending_weights))
+        return views, weights, ndim, np.dtype(np.float32), True, None
     host = np.asarray(transformed_views)
     views = DeviceArray.from_host(np.ascontiguousarray(host, dtype=np.float32), device)
     weights = DeviceArray.from_host(np.ascontiguousarray(blending_weights, dtype=np.float32), device)
@@ -50,16 +48,6 @@ def run_stack_call(name, views, ndim, trim, out_dtype, out_on_device, device, ou
     shape3 = (1,) * (3 - ndim) + tuple(views.shape[1:])
     t3 = [0] * (3 - ndim) + [int(t) for t in trim]
     res_shape = tuple(s - 2 * t for s, t in zip(views.shape[1:], trim))
-    if out_on_device:
-        if out is None:
-            out = DeviceArray.empty(res_shape, out_dtype, device)
-        elif tuple(out.shape) != res_shape or not out.is_contiguous() or out.dtype != np.dtype(out_dtype):
-            raise ValueError("out must be a contiguous DeviceArray of the result shape and dtype")
-        optr, omem = out.ptr, _lib.MVS_MEM_DEVICE
-    else:
-        out = np.empty(res_shape, dtype=out_dtype)
-        optr, omem = out.ctypes.data, _lib.MVS_MEM_HOST
+    out, optr, omem = result_array(res_shape, out_dtype, out_on_device, device, out if out_on_device else None)
     _lib.check(call(shape3, t3, _lib.DTYPE_CODES[np.dtype(out_dtype)], optr, omem), device, name)
-    if out_on_device:
-        out.mark_written()
-    return out
+    return written(out)

@@ -14,6 +14,7 @@ import numpy as np
 
 from . import _lib, param_utils
 from . import spatial_image_utils as si_utils
+from ._operands import embed3, fill_view_geometry, result_array, shape3, tile_view, view_data, written  # noqa: F401 (the first six: their old home)
 
 
 def _as_zyx(value, sdims):
@@ -86,75 +87,6 @@ def embed3_stack(matrices, offsets):
     return m3.reshape(n, 9), o3
 
 
-def embed3(matrix, offset):
-    """Embed an ndim-D pixel affine into the 3D (z,y,x) form the C ABI takes (2D: z -> z)."""
-    ndim = len(offset)
-    m3 = np.eye(3)
-    o3 = np.zeros(3)
-    k = 3 - ndim
-    m3[k:, k:] = matrix
-    o3[k:] = offset
-    return m3, o3
-
-
-def shape3(shape):
-    shape = [int(s) for s in shape]
-    return [1] * (3 - len(shape)) + shape
-
-
-def view_data(data, device, dtype=None, wait=True):
-    """Where the C entries find a view's voxels: ``(pointer, 3D shape, 3D element strides, MVS_MEM_* code, array to keep
-    alive until the call is over)``.  A DeviceArray is used in place (``wait``: first brought to ``device`` and this lane's
-    stream made to wait for an upload still in flight); a host array is made C-contiguous, cast to ``dtype`` if one is given
-    and to float32 if its own is none of the kernels'.  2D data is a single z plane."""
-    from .device import is_device_array
-
-    if is_device_array(data):
-        if dtype is not None and data.dtype != dtype:
-            raise TypeError("all views of a chunk must share one dtype")
-        if wait:
-            data = data.on_device(device)     # a tile resident on another GPU: peer copy, cached per (tile, device)
-            data.wait_ready(device)           # a tile still on its way (device.to_device_async)
-        if data.dtype not in _lib.DTYPE_CODES:
-            raise TypeError(f"unsupported dtype {data.dtype}")
-        ptr, st, mem = data.ptr, [int(v) for v in data.strides], _lib.MVS_MEM_DEVICE
-    else:
-        data = np.ascontiguousarray(data, dtype=dtype)
-        if data.dtype not in _lib.DTYPE_CODES:
-            data = data.astype(np.float32)
-        st = [int(np.prod(data.shape[k + 1:])) for k in range(data.ndim)]   # C order; numpy's strides of size-1 axes are arbitrary
-        ptr, mem = data.ctypes.data, _lib.MVS_MEM_HOST
-    s3 = shape3(data.shape)
-    if len(st) == 2:
-        st = [st[0] * s3[1], st[0], st[1]]
-    return ptr, s3, st, mem, data
-
-
-def fill_view_geometry(view, data_ptr, dtype_code, mem, shape, strides_elems, matrix, offset):
-    """Fill the data/geometry half of an ``mvs_view_t``."""
-    m3, o3 = embed3(matrix, offset)
-    s3 = shape3(shape)
-    st3 = [int(s) for s in strides_elems]
-    if len(st3) == 2:  # 2D slab: a single z plane
-        st3 = [st3[0] * s3[1], st3[0], st3[1]]
-    view.data = data_ptr
-    view.dtype = dtype_code
-    view.mem = mem
-    view.shape[:] = s3
-    view.stride[:] = st3
-    view.offset[:] = o3.tolist()
-    view.matrix[:] = m3.reshape(-1).tolist()
-
-
-def tile_view(data, matrix, offset, device):
-    """``(mvs_view_t, array to keep alive)`` of one whole tile for the entry points that take tiles (metrics, PSF extraction,
-    intensity, shading): ``view_data`` and ``fill_view_geometry`` with the tile's own dtype."""
-    view = _lib.mvs_view_t()
-    ptr, s3, st3, mem, keep = view_data(data, device)
-    fill_view_geometry(view, ptr, _lib.DTYPE_CODES[np.dtype(keep.dtype)], mem, s3, st3, matrix, offset)
-    return view, keep
-
-
 def check_interpolation_order(order, name):
     """The reference forwards ``order`` to scipy.ndimage.affine_transform unchanged (transformation.py:85-94,
     fusion/_core.py:797, 1627); the HIP resampler has nearest (0) and bi / trilinear (1) taps only.  Higher spline orders
@@ -169,26 +101,17 @@ def resample_array(data, matrix, offset, output_shape, order=1, cval=0.0, device
     """scipy.ndimage.affine_transform(data, matrix, offset, output_shape, order, 'constant', cval)
     for order 0|1 on the GPU; float32 result (transformation.py:136-139).  ``data`` may be a numpy
     array or a (possibly strided) DeviceArray; the result stays on the device in the latter case."""
-    from .device import DeviceArray, is_device_array
+    from .device import is_device_array
 
     lib = _lib.init(device)
-    view = _lib.mvs_view_t()
-    on_dev = is_device_array(data)
     if out_on_device is None:
-        out_on_device = on_dev
-    ptr, s3, st3, mem, keep = view_data(data, device, wait=False)
-    fill_view_geometry(view, ptr, _lib.DTYPE_CODES[keep.dtype], mem, s3, st3, matrix, offset)
-    oshape = tuple(int(s) for s in output_shape)
-    if out_on_device:
-        out = DeviceArray.empty(oshape, np.float32, device)
-        optr, omem = out.ptr, _lib.MVS_MEM_DEVICE
-    else:
-        out = np.empty(oshape, dtype=np.float32)
-        optr, omem = out.ctypes.data, _lib.MVS_MEM_HOST
+        out_on_device = is_device_array(data)
+    view, keep = tile_view(data, matrix, offset, device)
+    out, optr, omem = result_array(output_shape, np.float32, out_on_device, device)
     rc = lib.mvs_resample(device, C.byref(view), _lib.i64x3(shape3(output_shape)), int(order), float(cval), optr, omem)
     _lib.check(rc, device, "mvs_resample")
     del keep
-    return out
+    return written(out)
 
 
 def transform_sim(

@@ -12,7 +12,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .transformation import _as_zyx, embed3, get_pixel_affine, shape3
+from ._operands import dense_operand, embed3, result_array, shape3, written
+from .transformation import _as_zyx, get_pixel_affine
 
 DEFAULT_BLENDING_WIDTHS = {"z": 3, "y": 10, "x": 10}
 
@@ -184,13 +185,9 @@ def content_based_dct(transformed_views, dct_size=32, exponent=1.0, otf_support_
 
     lib = _lib.init(device)
     on_dev = is_device_array(transformed_views)
-    if on_dev:
-        views = transformed_views.on_device(device)
-        views.wait_ready(device)
-        if views.dtype != np.float32 or not views.is_contiguous():
-            views = DeviceArray.from_host(np.ascontiguousarray(views.get(), dtype=np.float32), device)
-    else:
-        views = np.ascontiguousarray(transformed_views, dtype=np.float32)
+    if on_dev and (transformed_views.dtype != np.float32 or not transformed_views.is_contiguous()):
+        transformed_views = DeviceArray.from_host(np.ascontiguousarray(transformed_views.get(), dtype=np.float32), device)
+    ptr, mem, views = dense_operand(transformed_views, (np.float32,), device, "content_based_dct", host_dtype=np.float32)
     nv, spatial = int(views.shape[0]), tuple(int(s) for s in views.shape[1:])
     ndim = len(spatial)
     if ndim not in (2, 3):
@@ -201,21 +198,12 @@ def content_based_dct(transformed_views, dct_size=32, exponent=1.0, otf_support_
     if opts.has_output_chunksize:
         sizes = [min(sizes[k], opts.output_chunksize[k]) for k in range(3)]
     nblocks = tuple(max(1, -(-s3[k] // min(sizes[k], s3[k]))) for k in range(3 - ndim, 3))
-    if on_dev:
-        out = DeviceArray.empty((nv,) + spatial, np.float32, device)
-        q = DeviceArray.empty((nv,) + nblocks, np.float32, device) if return_quality else None
-        rc = lib.mvs_content_dct_weights(device, C.c_void_p(views.ptr), nv, _lib.i64x3(s3), ndim, C.byref(opts), C.c_void_p(out.ptr),
-                                         C.c_void_p(q.ptr) if q is not None else None, _lib.MVS_MEM_DEVICE)
-        _lib.check(rc, device, "mvs_content_dct_weights")
-        out.mark_written()
-        if q is not None:
-            q.mark_written()
-    else:
-        out = np.empty((nv,) + spatial, np.float32)
-        q = np.empty((nv,) + nblocks, np.float32) if return_quality else None
-        rc = lib.mvs_content_dct_weights(device, views.ctypes.data, nv, _lib.i64x3(s3), ndim, C.byref(opts), out.ctypes.data,
-                                         q.ctypes.data if q is not None else None, _lib.MVS_MEM_HOST)
-        _lib.check(rc, device, "mvs_content_dct_weights")
+    out, optr, _ = result_array((nv,) + spatial, np.float32, on_dev, device)
+    q, qptr, _ = result_array((nv,) + nblocks, np.float32, on_dev, device) if return_quality else (None, None, None)
+    rc = lib.mvs_content_dct_weights(device, C.c_void_p(ptr), nv, _lib.i64x3(s3), ndim, C.byref(opts), C.c_void_p(optr), C.c_void_p(qptr), mem)
+    _lib.check(rc, device, "mvs_content_dct_weights")
+    written(out)
+    written(q)
     return (out, q) if return_quality else out
 
 
